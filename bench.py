@@ -15,8 +15,16 @@ Prints ONE JSON line on rank 0, including
   roofline     algorithmic bytes (14 342 B/block) / average kernel
                duration measured with HIP events on the launch stream, vs the
                8 TB/s HBM3E peak (MI355X_MICROARCH.md)
-  cpu_baseline the reference's own AVX2 kernels (oracle/_ref, compiled from
-               /root/reference) on the GPU box's host cores, bounded sample
+
+A plain run only sets up, warms up, times --steps steps and prints the line.
+--full adds what takes work of its own, after the timed steps:
+  digest       [blocks, sum eob, sum sad, checksum(qcoeff)], all-reduced over ranks
+  roofline.box_* / contiguous_outputs_* / clock figures  (skipped by --no-probes)
+  secondary    the PCIe-inclusive figure (skipped by --no-probes)
+  cpu_baseline the reference's own AVX2 kernels (oracle/_ref, built by
+               oracle/Makefile from the reference sources) on the GPU box's
+               host cores, bounded sample (skipped by --no-cpu-baseline)
+--dump-outputs DIR writes the last timed step's outputs (rank 0) as .npy files.
 """
 import argparse
 import ctypes
@@ -34,6 +42,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 BYTES_PER_BLOCK = 2 * 1024 + 3 * 4096 + 2 + 4      # 14 342
 HBM_PEAK_GBS = 8000.0                               # MI355X HBM3E spec peak
 QINDEX = 100
+DUMP_SEED = 20260
+DUMP_ROWS = 1 << 10             # coefficient rows --dump-outputs writes: 3 arrays x 1024 x 1024 float64 = 24 MiB
+DUMP_SCALARS = 1 << 20          # eob / sad entries it writes: 2 x 2^20 float64 = 16 MiB
 
 
 def host_cores():
@@ -180,6 +191,27 @@ def cpu_baseline(src_np, pred_np, qrow, gpu_out, budget_s=14.0):
         out["gpu_equals_cpu_on_sample"] = bool(ok)
         out["verified_blocks"] = int(nv)
         return out
+
+
+def dump_index(n, k):
+    """the blocks --dump-outputs writes of an array of n blocks when at most k fit: None = all of them, else k sorted indices drawn
+    from DUMP_SEED (the same for every run with the same --blocks)"""
+    return None if n <= k else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(torch, outs, dirname):
+    """--dump-outputs: what a caller of the timed path receives - coeff / qcoeff / dqcoeff [blocks, 1024], eob, sad [blocks] - as
+    float64 .npy files (every value is an integer, exact in float64); at most DUMP_ROWS / DUMP_SCALARS blocks each (dump_index)."""
+    os.makedirs(dirname, exist_ok=True)
+
+    def sample(t, k):
+        idx = dump_index(t.shape[0], k)
+        return t if idx is None else t.index_select(0, torch.from_numpy(idx).to(t.device))
+    co, q, dq, eob, sad = outs
+    for name, t in (("coeff", co), ("qcoeff", q), ("dqcoeff", dq)):
+        np.save(os.path.join(dirname, name + ".npy"), sample(t, DUMP_ROWS).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(dirname, "eob.npy"), sample(eob, DUMP_SCALARS).cpu().numpy().view(np.uint16).astype(np.float64))
+    np.save(os.path.join(dirname, "sad.npy"), sample(sad, DUMP_SCALARS).cpu().numpy().view(np.uint32).astype(np.float64))
 
 
 def box_probe(torch, dsp, dev, big, src, iters=5):
@@ -338,12 +370,20 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=1 << 20, help="32x32 blocks per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-probes", action="store_true", help="skip the box fill / copy probe and the PCIe-inclusive secondary figure")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also compute the output digest, the probes, the PCIe-inclusive figure and the CPU "
+                         "baseline (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy, float64, a fixed sample of large arrays")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-probes", action="store_true",
+                    help="with --full: skip the box fill / copy probe and the PCIe-inclusive secondary figure")
     ap.add_argument("--rehearse", action="store_true",
                     help="N > 1 on a ONE-GPU box: every rank uses cuda:0 and the process group is gloo (RCCL cannot put two ranks "
                          "on one device); walks exactly the multi-rank code path of the driver's 8-GPU run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # One process per GPU.  Launched bare (`python bench.py --gpus N`, WORLD_SIZE unset) this process only starts the N
     # ranks as children and relays rank 0's line: it has imported neither torch nor the HIP library at this point.
@@ -382,10 +422,12 @@ def main():
     # Data layout in HBM: the three coefficient arrays the kernel writes at the same time are allocated FAR APART
     # (SvtHipDsp.alloc_spread = svt_hip_malloc_spread: 32 GiB spacers between them, freed again).  Inside one contiguous 12 GiB
     # allocation - how this bench placed them until round 3 - the same kernel runs 20 - 25 % slower on the same box, whatever the
-    # skew between the arrays (profiles/r03_placement_probe*.log); that placement is still measured below, outside the timed
-    # region, and reported as roofline.contiguous_outputs_*.  SVT_BENCH_PLACEMENT=contiguous times it as `value` instead.
+    # skew between the arrays (profiles/r03_placement_probe*.log); a --full run still measures that placement below, outside the
+    # timed region, and reports it as roofline.contiguous_outputs_*.  SVT_BENCH_PLACEMENT=contiguous times it as `value` instead.
     placement = os.environ.get("SVT_BENCH_PLACEMENT", "spread")
-    big = torch.empty(3 * n * 1024, dtype=torch.int32, device=dev)      # one 12 GiB allocation: the probes' buffer and the contiguous placement
+    # one 12 GiB allocation: the probes' buffer and the contiguous placement.  A plain run allocates it too (it is never touched), so that
+    # the spread arrays below land where they land in a --full run.
+    big = torch.empty(3 * n * 1024, dtype=torch.int32, device=dev)
     contiguous = (big[:n * 1024].view(n, 1024), big[n * 1024:2 * n * 1024].view(n, 1024), big[2 * n * 1024:].view(n, 1024))
     small = (torch.zeros(n, dtype=torch.int16, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
     if placement == "spread":
@@ -422,15 +464,19 @@ def main():
     kernel_ms = ev0.elapsed_time(ev1) / max(args.steps, 1)    # one kernel per step, back to back
 
     # ---- outside the timed region -----------------------------------------------------------------------------------
-    # digest of this rank's outputs: [blocks, sum eob, sum sad, checksum(qcoeff)] — ranks add (sharding.py)
-    chk = 0
-    for lo in range(0, n, 1 << 16):
-        hi = min(n, lo + (1 << 16))
-        w = (torch.arange(lo * 1024, hi * 1024, device=dev, dtype=torch.int64) % 8191) + 1
-        chk = (chk + int(((outs[1][lo:hi].reshape(-1).to(torch.int64) * w) % sharding.DIGEST_MOD).sum().item())) % sharding.DIGEST_MOD
-        del w
-    digest = np.array([n, int((outs[3].to(torch.int64) & 0xffff).sum().item()), int((outs[4].to(torch.int64) & 0xffffffff).sum().item()),
-                       chk], dtype=np.int64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, outs, args.dump_outputs)
+    digest = None
+    if args.full:
+        # digest of this rank's outputs: [blocks, sum eob, sum sad, checksum(qcoeff)] — ranks add (sharding.py)
+        chk = 0
+        for lo in range(0, n, 1 << 16):
+            hi = min(n, lo + (1 << 16))
+            w = (torch.arange(lo * 1024, hi * 1024, device=dev, dtype=torch.int64) % 8191) + 1
+            chk = (chk + int(((outs[1][lo:hi].reshape(-1).to(torch.int64) * w) % sharding.DIGEST_MOD).sum().item())) % sharding.DIGEST_MOD
+            del w
+        digest = np.array([n, int((outs[3].to(torch.int64) & 0xffff).sum().item()),
+                           int((outs[4].to(torch.int64) & 0xffffffff).sum().item()), chk], dtype=np.int64)
     per_rank = [kernel_ms]
     if world > 1:
         import torch.distributed as dist
@@ -440,7 +486,8 @@ def main():
         km = [torch.zeros(1, dtype=torch.float64, device=cdev) for _ in range(world)]
         dist.all_gather(km, torch.tensor([kernel_ms], dtype=torch.float64, device=cdev))
         per_rank = [float(k.item()) for k in km]
-        digest = sharding.allreduce_digest(digest, None if args.rehearse else dev)
+        if args.full:
+            digest = sharding.allreduce_digest(digest, None if args.rehearse else dev)
 
     result = None
     if rank == 0:
@@ -467,7 +514,7 @@ def main():
                     "kernel": "fwd32_kernel<IN_U8,QUANT,WITH_SAD>",
                     "per_rank": [{"rank": r, "kernel_ms": k, "achieved": BYTES_PER_BLOCK * n / (k * 1e-3) / 1e9,
                                   "frac": BYTES_PER_BLOCK * n / (k * 1e-3) / 1e9 / HBM_PEAK_GBS} for r, k in enumerate(per_rank)]}
-        if not args.no_probes:
+        if args.full and not args.no_probes:
             # same process, same buffers, right after the timed steps: tells a slow box from a slow kernel
             roofline.update(box_probe(torch, dsp, dev, big, src))
             roofline["frac_of_box_fill"] = achieved / roofline["box_fill_GBps"]
@@ -529,12 +576,12 @@ def main():
                        "blocks_per_gpu": n, "global_blocks": n * world, "tx_size": "TX_32X32",
                        "tx_type": "DCT_DCT", "parallelism": f"block-range shard x{world}, no collective"},
             "roofline": roofline,
-            "digest_blocks_eob_sad_qchk": [int(v) for v in digest],
+            **({"digest_blocks_eob_sad_qchk": [int(v) for v in digest]} if args.full else {}),
             "device": dsp.device_name(),
         }
-        if world == 1 and not args.no_probes:
+        if args.full and world == 1 and not args.no_probes:
             result["secondary"] = pcie_inclusive(torch, dsp, pkg, dev, src, pred, qrow, iscan, min(n, 1 << 16))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ns = min(n, 1 << 18)
             result["cpu_baseline"] = cpu_baseline(src[:ns].cpu().numpy(), pred[:ns].cpu().numpy(), qrow,
                                                   tuple(o[:ns] for o in outs))

@@ -15,14 +15,16 @@ outputs of the reference's scalar C functions.
 Run here (needs /root/reference):   python tests/golden/make_golden.py
 """
 import ctypes
+import json
 import os
+import re
 import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-from svtlibs import TX_H, TX_SIZES, TX_TYPES, TX_W, ptr, ref, txfm_allowed  # noqa: E402
+from svtlibs import TX_H, TX_SIZES, TX_TYPES, TX_W, product, ptr, ref, ref_slot_types, txfm_allowed  # noqa: E402
 
 c_int = ctypes.c_int
 R = ref()
@@ -752,6 +754,21 @@ def gen_me_setup():
     np.savez_compressed(os.path.join(HERE, "me_setup.npz"), **d)
 
 
+def gen_rtcd_slots():
+    """rtcd_slots.json: for every slot of the product's registry (svt_hip_rtcd_slot_name), the parameter types of the reference's
+    dispatch global of that name in aom_dsp_rtcd.h (svtlibs.ref_slot_types), read from the tree oracle/Makefile compiles (its
+    REF variable; REF in the environment overrides it, as it does for make)"""
+    root = os.path.dirname(os.path.dirname(HERE))
+    rd = os.environ.get("REF") or re.search(r"^REF\s*\?=\s*(\S+)", open(os.path.join(root, "oracle", "Makefile")).read(), re.M).group(1)
+    text = open(os.path.join(rd, "Source", "Lib", "Common", "Codec", "aom_dsp_rtcd.h")).read()
+    lib = product()
+    lib.svt_hip_rtcd_slot_name.restype = ctypes.c_char_p
+    names = [lib.svt_hip_rtcd_slot_name(i).decode() for i in range(lib.svt_hip_rtcd_slot_count())]
+    slots = {n: ref_slot_types(text, n) for n in names}
+    with open(os.path.join(HERE, "rtcd_slots.json"), "w") as f:
+        f.write("{\n" + ",\n".join(f"{json.dumps(n)}: {json.dumps(t)}" for n, t in sorted(slots.items())) + "\n}\n")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:                    # one family only: python make_golden.py cfl_levels
         globals()["gen_" + sys.argv[1]]()
@@ -769,6 +786,7 @@ if __name__ == "__main__":
     gen_bip()
     gen_picture()
     gen_me_setup()
+    gen_rtcd_slots()
     for f in sorted(os.listdir(HERE)):
         if f.endswith(".npz"):
             print(f, os.path.getsize(os.path.join(HERE, f)))

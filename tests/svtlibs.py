@@ -8,6 +8,7 @@
 """
 import ctypes
 import os
+import re
 import subprocess
 
 import numpy as np
@@ -74,6 +75,35 @@ def product():
         path = os.path.join(PKG, "libsvt_hip_dsp.so")
         _cache["product"] = ctypes.CDLL(path)
     return _cache["product"]
+
+
+def rtcd_param_types(params):
+    """a C parameter list reduced to its types, token for token: the reference's and the drop-in header's type names mapped to
+    one spelling, parameter NAMES dropped (they differ between the two)"""
+    p = re.sub(r"\b(svt_tx_type_t|TxType)\b", "TXTYPE", params)
+    p = re.sub(r"\b(svt_tx_size_t|TxSize)\b", "TXSIZE", p)
+    p = re.sub(r"\b(svt_tran_low_t|tran_low_t)\b", "int32_t", p)
+    p = re.sub(r"\b(svt_txfm_param|TxfmParam)\b", "TXFMPARAM", p)
+    p = re.sub(r"\bunsigned int\b", "uint32_t", p)
+    p = re.sub(r"\bint\b", "int32_t", p)
+    parts = []
+    for a in p.split(","):
+        a = a.strip()
+        a = re.sub(r"\s*\b[A-Za-z_][A-Za-z0-9_]*\s*(\[\s*\d*\s*\])?$", lambda m: "[]" if m.group(1) else "", a) if not a.endswith("*") else a
+        parts.append(re.sub(r"\s+", "", a.replace("const", "")))
+    return parts
+
+
+def ref_slot_types(rtcd_text, name):
+    """rtcd_param_types of dispatch global `name` in the text of the reference's aom_dsp_rtcd.h.  The 19 highbd paeth predictors
+    are `#define`d to their C function there (:1264-1320: listed for the pred_high[][] table, not as an RTCD pointer): their C
+    function's prototype."""
+    m = re.search(r"RTCD_EXTERN\s+[^;(]*\(\s*\*\s*" + re.escape(name) + r"\s*\)\s*\(([^;]*)\)\s*;", rtcd_text)
+    if not m:
+        assert name.startswith("aom_highbd_paeth_predictor_") and re.search(r"#define\s+" + re.escape(name) + r"\s+" + re.escape(name) + "_c",
+                                                                            rtcd_text), name
+        m = re.search(r"void\s+" + re.escape(name) + r"_c\s*\(([^;]*)\)\s*;", rtcd_text)
+    return rtcd_param_types(m.group(1))
 
 
 def quant_tables(bd=8):

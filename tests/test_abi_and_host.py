@@ -121,43 +121,23 @@ def test_slot_registry_is_complete_and_consistent(pkg):
     assert lib.svt_hip_rtcd_override_slot(b"no_such_slot", ctypes.byref(slot)) != 0 and slot.value == 0x1234
 
 
-REF_RTCD = "/root/reference/Source/Lib/Common/Codec/aom_dsp_rtcd.h"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_RTCD), reason="needs /root/reference (reads its dispatch header as text)")
 def test_slot_names_and_signatures_are_the_references(pkg):
-    """every registry name is a dispatch global of the reference's aom_dsp_rtcd.h (the 19 highbd paeth predictors are
-    `#define`d to their C function there, :1264-1320: listed for the pred_high[][] table, not as an RTCD pointer), and the
-    drop-in's parameter list equals the reference's, token for token, after type-name normalisation"""
+    """every registry name is a dispatch global of the reference's aom_dsp_rtcd.h, and the drop-in's parameter list equals the
+    reference's, token for token, after type-name normalisation (svtlibs.rtcd_param_types).  The reference's side is
+    tests/golden/rtcd_slots.json: slot name -> parameter types, written by make_golden.py from the header (svtlibs.ref_slot_types)."""
+    import json
+    import svtlibs
     lib = pkg.load_library()
-    ref = open(REF_RTCD).read()
+    ref = json.load(open(os.path.join(ROOT, "tests", "golden", "rtcd_slots.json")))
     hdr = subprocess.check_output(["gcc", "-E", "-P", "-I", os.path.join(ROOT, "include"), HDR]).decode()
-
-    def norm(params):
-        p = re.sub(r"\b(svt_tx_type_t|TxType)\b", "TXTYPE", params)
-        p = re.sub(r"\b(svt_tx_size_t|TxSize)\b", "TXSIZE", p)
-        p = re.sub(r"\b(svt_tran_low_t|tran_low_t)\b", "int32_t", p)
-        p = re.sub(r"\b(svt_txfm_param|TxfmParam)\b", "TXFMPARAM", p)
-        p = re.sub(r"\bunsigned int\b", "uint32_t", p)
-        p = re.sub(r"\bint\b", "int32_t", p)
-        # parameter NAMES differ; keep types only: drop the identifier before ',' or end
-        parts = []
-        for a in p.split(","):
-            a = a.strip()
-            a = re.sub(r"\s*\b[A-Za-z_][A-Za-z0-9_]*\s*(\[\s*\d*\s*\])?$", lambda m: "[]" if m.group(1) else "", a) if not a.endswith("*") else a
-            parts.append(re.sub(r"\s+", "", a.replace("const", "")))
-        return parts
-
+    names = registry(lib)
+    assert set(names) == set(ref)
     checked = 0
-    for n in registry(lib):
-        m = re.search(r"RTCD_EXTERN\s+[^;(]*\(\s*\*\s*" + re.escape(n) + r"\s*\)\s*\(([^;]*)\)\s*;", ref)
-        if not m:
-            assert n.startswith("aom_highbd_paeth_predictor_") and re.search(r"#define\s+" + re.escape(n) + r"\s+" + re.escape(n) + "_c", ref), n
-            m = re.search(r"void\s+" + re.escape(n) + r"_c\s*\(([^;]*)\)\s*;", ref)
+    for n in names:
         sym = "svt_hip_residual_kernel" if n == "ResidualKernel" else "svt_hip_" + n
         d = re.search(r"\b" + sym + r"\s*\(([^;]*)\)\s*;", hdr)
         assert d, sym
-        assert norm(m.group(1)) == norm(d.group(1)), (n, norm(m.group(1)), norm(d.group(1)))
+        assert ref[n] == svtlibs.rtcd_param_types(d.group(1)), (n, ref[n], svtlibs.rtcd_param_types(d.group(1)))
         checked += 1
     assert checked == EXPECTED_SLOTS
 

@@ -37,7 +37,7 @@ def run2(script, extra, port, launcher=False):
 
 @pytest.mark.parametrize("launcher", [False, True])
 def test_bench_two_ranks_rehearsal(launcher):
-    r = run2("bench.py", ["--steps", "3", "--warmup", "1", "--blocks", "65536"], 29611, launcher)
+    r = run2("bench.py", ["--steps", "3", "--warmup", "1", "--blocks", "65536", "--full"], 29611, launcher)
     assert r["n_gpus"] == 2 and r["steps"] == 3 and r["warmup"] == 1 and r["scaling"] == "weak"
     assert r["config"]["global_blocks"] == 2 * 65536 and r["value"] > 0 and r["roofline"]["frac"] > 0
     assert [p["rank"] for p in r["roofline"]["per_rank"]] == [0, 1] and all(p["frac"] > 0 for p in r["roofline"]["per_rank"])
@@ -47,7 +47,7 @@ def test_bench_two_ranks_rehearsal(launcher):
 
 def test_bench_digest_of_two_ranks_is_the_sum_of_the_two_seeds():
     """rank r draws its blocks from seed 13596 + r: the all-reduced digest equals one-process runs' digests added"""
-    r2 = run2("bench.py", ["--steps", "1", "--warmup", "1", "--blocks", "16384", "--no-probes"], 29613)
+    r2 = run2("bench.py", ["--steps", "1", "--warmup", "1", "--blocks", "16384", "--full", "--no-probes"], 29613)
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
@@ -55,7 +55,7 @@ def test_bench_digest_of_two_ranks_is_the_sum_of_the_two_seeds():
     for rank in (0, 1):
         e = dict(env, SVT_BENCH_SEED_RANK=str(rank))
         r1 = _json_line(subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--blocks", "16384",
-                                        "--no-probes", "--no-cpu-baseline"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600))
+                                        "--full", "--no-probes", "--no-cpu-baseline"], cwd=ROOT, env=e, capture_output=True, text=True, timeout=600))
         assert r1["n_gpus"] == 1
         tot = [a + b for a, b in zip(tot, r1["digest_blocks_eob_sad_qchk"])]
     tot[3] %= (1 << 31) - 1

@@ -6,7 +6,7 @@ tag=$1
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 400 python3 bench.py > $out/bench.log 2>&1 && tail -1 $out/bench.log > $out/bench.json || { echo "bench failed"; exit 1; }
+timeout -k 10 400 python3 bench.py --full > $out/bench.log 2>&1 && tail -1 $out/bench.log > $out/bench.json || { echo "bench failed"; exit 1; }
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $out/stats -o stats --output-format csv -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-probes > $out/stats.log 2>&1 || echo "stats pass failed"
 f=$(find $out/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/kernel_stats.csv
 i=0
