@@ -150,6 +150,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_picture_luma8.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_int, c_void_p]
     L.svt_hip_picture_decimate.argtypes = [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint32,
                                            c_uint32, c_uint32, c_void_p]
+    L.svt_hip_full_loop_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.svt_hip_full_loop_frame.restype = c_int
     return L
 
 
@@ -984,3 +986,54 @@ class SvtHipDsp:
                                                       tabs[4].ctypes.data, self._p(iscan), self._p(co), self._p(q),
                                                       self._p(dq), self._p(eob), self._stream()), "svt_hip_fwd_quant_batch")
         return outs
+
+    # -- mode-decision full loop: residual -> transform -> quantiser -> distortion per (block, transform type) ----------------
+    class FullLoopGroup(ctypes.Structure):
+        _fields_ = [("d_src", c_void_p), ("src_stride", c_uint32), ("d_src_xy", c_void_p),
+                    ("d_pred", c_void_p), ("pred_stride", c_uint32), ("d_pred_xy", c_void_p),
+                    ("nblocks", c_uint32), ("tx_size", c_int32), ("ntypes", c_int32), ("tx_types", ctypes.c_uint8 * 16),
+                    ("d_iscan", c_void_p), ("d_dist", c_void_p), ("d_eob", c_void_p), ("d_qcoeff", c_void_p), ("d_dqcoeff", c_void_p)]
+
+    def make_full_loop_groups(self, groups):
+        """groups: list of dicts with tensors src, pred (planes or dense [n, H, W] uint8), optional src_xy / pred_xy (int32
+        x | y << 16; absent: dense), iscan (int16 [ntypes, NC] in tx_types order), dist (int64 [n, ntypes, 2]), eob (int16 [n, ntypes]),
+        optional qcoeff / dqcoeff (int32 [n, ntypes, NC]), plus src_stride / pred_stride, nblocks, tx_size, tx_types.
+        -> ctypes array (keep the tensors alive!)"""
+        arr = (self.FullLoopGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+            types = list(g["tx_types"])
+            tt = (ctypes.c_uint8 * 16)(*(types + [0] * (16 - len(types)))[:16])
+            arr[i] = self.FullLoopGroup(P("src"), g.get("src_stride", 0), P("src_xy"), P("pred"), g.get("pred_stride", 0), P("pred_xy"),
+                                        g["nblocks"], g["tx_size"], g.get("ntypes", len(types)), tt, P("iscan"), P("dist"), P("eob"),
+                                        P("qcoeff"), P("dqcoeff"))
+        return arr
+
+    def full_loop_frame(self, groups, qrow, flavour=1):
+        """groups: a ctypes array from make_full_loop_groups (or the list of dicts itself); one quantiser row set (qrow)"""
+        if isinstance(groups, list):
+            keep = groups
+            groups = self.make_full_loop_groups(keep)
+            n = len(keep)
+        else:
+            n = len(groups)
+        tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
+        return self.lib.svt_hip_full_loop_frame(groups, n, flavour, tabs[0].ctypes.data, tabs[1].ctypes.data, tabs[2].ctypes.data,
+                                                tabs[3].ctypes.data, tabs[4].ctypes.data, self._stream())
+
+    def full_loop(self, src, pred, tx_size, tx_types, qrow, flavour=1, want_qcoeff=False, want_dqcoeff=False, iscan=None):
+        """Dense batches: src, pred uint8 [n, H, W].  tx_types: 1..16 distinct types; iscan: int16 [ntypes, NC] device tensor
+        (default: the reference's scans from tables).  -> dist int64 [n, T, 2], eob int16 [n, T], qcoeff | None, dqcoeff | None"""
+        t = self.torch
+        n, T = src.shape[0], len(tx_types)
+        nc = min(TX_W[tx_size], 32) * min(TX_H[tx_size], 32)
+        if iscan is None:
+            import numpy as np
+            iscan = t.from_numpy(np.stack([tables.scan_tables(tx_size, ty)[1] for ty in tx_types]).astype(np.int16)).to(src.device)
+        dist = t.empty((n, T, 2), dtype=t.int64, device=src.device)
+        eob = t.empty((n, T), dtype=t.int16, device=src.device)
+        q = t.empty((n, T, nc), dtype=t.int32, device=src.device) if want_qcoeff else None
+        dq = t.empty((n, T, nc), dtype=t.int32, device=src.device) if want_dqcoeff else None
+        g = dict(src=src, pred=pred, nblocks=n, tx_size=tx_size, tx_types=tx_types, iscan=iscan, dist=dist, eob=eob, qcoeff=q, dqcoeff=dq)
+        self._check(self.full_loop_frame([g], qrow, flavour), "svt_hip_full_loop_frame")
+        return dist, eob, q, dq

@@ -57,7 +57,7 @@ extern int g_tune_inv32_var;
 int require_init();
 int launch_status(const char* what);
 }  // namespace svthost
-namespace svtdev { struct FrameDesc; }
+namespace svtdev { struct FrameDesc; struct QParams; }
 namespace svthost {
 // svt_hip_frame.hip: the one-launch form of svt_hip_encode_recon_frame (its kernel lives in a translation unit of its own)
 int launch_enc_frame_one(const svtdev::FrameDesc* fd, uint32_t total_wgs, int is_16bit, hipStream_t s);
@@ -66,6 +66,8 @@ extern const int kTxW[SVT_TX_SIZES_ALL];
 extern const int kTxH[SVT_TX_SIZES_ALL];
 bool txfm_allowed(int tx_size, int tx_type);
 int frame_groups_check(const svt_hip_frame_group* groups, int ngroups);      // svt_hip_txfm.hip
+svtdev::QParams quant_params(const int16_t* zbin, const int16_t* round, const int16_t* quant, const int16_t* quant_shift,
+                             const int16_t* dequant, int log_scale);                  // svt_hip_txfm.hip (make_qparams)
 
 #define TX_SWITCH(tx_size, CALL)                                                                  \
     switch (tx_size) {                                                                            \

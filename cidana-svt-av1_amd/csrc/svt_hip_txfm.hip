@@ -150,6 +150,12 @@ int launch_inv(const int32_t* in, void* dst, int is16, int32_t stride, size_t pi
 }
 }  // namespace
 
+// the quantiser scalars for the other translation units (svt_hip_full_loop.hip)
+svtdev::QParams svthost::quant_params(const int16_t* zbin, const int16_t* round, const int16_t* quant, const int16_t* quant_shift,
+                                      const int16_t* dequant, int log_scale) {
+    return make_qparams(zbin, round, quant, quant_shift, dequant, log_scale);
+}
+
 // ===========================================================================
 // (B) batched API
 // ===========================================================================

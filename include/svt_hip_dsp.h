@@ -543,6 +543,41 @@ int svt_hip_picture_full_distortion32_batch(const int32_t *d_coeff, size_t coeff
                                             const uint32_t *d_count_non_zero_coeffs, int flavour, uint64_t *d_out,
                                             size_t nblocks, void *stream);
 
+/* The luma mode-decision full loop, fused: ProductFullLoop (EbFullLoop.c:724-925) and ProductFullLoopTxSearch (:927-1100) for many
+ * (transform size, type list) groups in one call.  Per block of a group and per type of its list, in the list's order:
+ *   residual = src - pred                                          (ResidualKernel, EbProductCodingLoop.c:1969; 8-bit, BIT_INCREMENT_8BIT
+ *                                                                   at EbFullLoop.c:799 / :1026)
+ *   coeff, three_quad_energy = av1_estimate_transform(DEFAULT_SHAPE) (:763, EbTransforms.c:4918; partial-frequency shapes are compiled
+ *                                                                   out of the reference)
+ *   qcoeff, dqcoeff, eob = av1_quantize_inv_quantize               (flat qmatrix: aom_highbd_quantize_b{,_32x32,_64x64}; :650 eob ==
+ *                                                                   count_non_zero_coeffs)
+ *   dist[2] = picture_full_distortion32_bits(coeff, dqcoeff, eob)  (EbPictureOperators.c:349-400: {DIST_CALC_RESIDUAL, _PREDICTION};
+ *                                                                   eob 0: the cbf_zero kernel, {sum c^2, sum c^2}; flavour as in
+ *                                                                   svt_hip_picture_full_distortion32_batch)
+ *   dist[i] = RIGHT_SIGNED_SHIFT(dist[i] + three_quad_energy, (1 - av1_get_tx_scale(tx_size)) * 2)      (:829-835, :1062-1068)
+ * coeff and dqcoeff never leave the device's registers unless d_qcoeff / d_dqcoeff ask for them.  Left to the caller: the rate
+ * (entropy code), the skip of a non-DCT type whose eob is 0 (:1034) and the allowed type set (:952-984).
+ * Blocks: d_*_xy[b] = x | y << 16 on a plane with the given row stride (in samples), or NULL: dense W * H samples per block (many
+ * candidates of one source block each repeat its origin in d_src_xy).  d_iscan: ntypes consecutive iscans of min(W,32) * min(H,32)
+ * entries in tx_types order (8-byte aligned); d_dist / d_qcoeff / d_dqcoeff 16-byte aligned.  One quantiser row set per call (the MD
+ * tables at the picture's qindex); quant_shift must be a power of two (every av1_build_quantizer table is), else
+ * SVT_HIP_ERR_INVALID.  Every argument, empty groups' tx_size / types included, is validated before the first launch; the call
+ * only enqueues work (one launch per register class and per 16 groups) and can be captured into a HIP graph. */
+typedef struct svt_hip_full_loop_group {
+    const void *d_src;  uint32_t src_stride;  const uint32_t *d_src_xy;   /* source plane + block origins; NULL xy: dense */
+    const void *d_pred; uint32_t pred_stride; const uint32_t *d_pred_xy;  /* candidate predictions, same addressing */
+    uint32_t nblocks;
+    int32_t tx_size;
+    int32_t ntypes;  uint8_t tx_types[16];      /* 1 .. 16 distinct types, each defined for tx_size */
+    const int16_t *d_iscan;                      /* ntypes x min(W,32) * min(H,32), in tx_types order */
+    uint64_t *d_dist;                            /* [nblocks][ntypes][2] {DIST_CALC_RESIDUAL, DIST_CALC_PREDICTION}, shifted */
+    uint16_t *d_eob;                             /* [nblocks][ntypes] (== y_count_non_zero_coeffs) */
+    int32_t *d_qcoeff, *d_dqcoeff;               /* optional (NULL: not written), [nblocks][ntypes][min(W,32) * min(H,32)] */
+} svt_hip_full_loop_group;
+int svt_hip_full_loop_frame(const svt_hip_full_loop_group *groups, int ngroups, int flavour,
+                            const int16_t *zbin, const int16_t *round, const int16_t *quant,
+                            const int16_t *quant_shift, const int16_t *dequant, void *stream);
+
 /* Open-loop intra search: open_loop_intra_search_sb, EbMotionEstimation.c:8694-8850,
  * for all blocks of ONE size of a picture (or of many pictures' worth of blocks) in one call.
  * d_pic points at picture sample (0, 0) (buffer_y + origin_y * stride_y + origin_x), width x height are
