@@ -64,6 +64,11 @@ int launch_enc_frame_one(const svtdev::FrameDesc* fd, uint32_t total_wgs, int is
 
 extern const int kTxW[SVT_TX_SIZES_ALL];
 extern const int kTxH[SVT_TX_SIZES_ALL];
+// blocks per workgroup of a staged body (enc_staged_body, full_loop_body): StagedGeom<W, H>::WAVES waves of TxGeom<W, H>::BPW blocks
+inline uint32_t staged_blocks_per_wg(int tx_size) {
+    const int w = kTxW[tx_size], h = kTxH[tx_size], m = w > h ? w : h;
+    return (uint32_t)((w * h >= 4096 ? 2 : 4) * (64 / m));
+}
 bool txfm_allowed(int tx_size, int tx_type);
 int frame_groups_check(const svt_hip_frame_group* groups, int ngroups);      // svt_hip_txfm.hip
 svtdev::QParams quant_params(const int16_t* zbin, const int16_t* round, const int16_t* quant, const int16_t* quant_shift,

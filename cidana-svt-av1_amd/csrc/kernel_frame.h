@@ -44,25 +44,6 @@ struct FrameDesc {
 };
 static_assert(sizeof(FrameDesc) <= 4000, "kernel arguments");
 
-// register class of a transform size (TxSize numbering of the reference, EbDefinitions.h:615-650)
-__host__ __device__ constexpr int frame_class_of(int tx_size) {
-    // sizes with both sides <= 16: TX_4X4 0, 8X8 1, 16X16 2, 4X8 5, 8X4 6, 8X16 7, 16X8 8, 4X16 13, 16X4 14 (a bit mask, not a table:
-    // the device evaluates this with a run-time size)
-    constexpr unsigned small = (1u << 0) | (1u << 1) | (1u << 2) | (1u << 5) | (1u << 6) | (1u << 7) | (1u << 8) | (1u << 13) | (1u << 14);
-    return tx_size == 4 ? 2 : (((small >> tx_size) & 1u) ? 0 : 1);
-}
-// blocks one 256-thread workgroup of the body takes: 4x4 one block per lane; staged bodies WAVES x BPW; 32x32 F32_WAVES x 2;
-// 64x64 E64_WAVES x 2
-inline uint32_t frame_blocks_per_wg(int tx_size) {        // host only
-    static const int kW[19] = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64};
-    static const int kH[19] = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16};
-    if (tx_size == 0) return 256;
-    if (tx_size == 3) return F32_WAVES * 2;
-    if (tx_size == 4) return E64_WAVES * 2;
-    const int w = kW[tx_size], h = kH[tx_size], m = w > h ? w : h;
-    return (uint32_t)((w * h >= 4096 ? 2 : 4) * (64 / m));
-}
-
 template <typename PixT, int CLS> struct FrameLds;
 template <typename PixT> struct FrameLds<PixT, 0> {
     static constexpr int BYTES = cmax(cmax(cmax(EncStagedLds<16, 16, PixT>::BYTES, EncStagedLds<8, 8, PixT>::BYTES),
@@ -92,16 +73,10 @@ template <int CLS> struct FrameWaves { static constexpr int MIN = CLS == 3 ? 3 :
 template <typename PixT, int BD, int CLS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FrameWaves<CLS>::MIN))) void enc_frame_kernel(const FrameDesc fd) {
     __shared__ __attribute__((aligned(16))) char lds[FrameLds<PixT, CLS>::BYTES];
-    // which group (uniform: scalar compares against the table in the kernel arguments)
-    int gi = 0;
-    uint32_t start = 0;
-#pragma unroll 1
-    for (int i = 0; i < fd.ngroups; i++) {
-        if (blockIdx.x >= fd.g[i].wg_end) { gi = i + 1; start = fd.g[i].wg_end; }
-    }
+    uint32_t bid;
+    const int gi = group_of(fd, bid);
     if (gi >= fd.ngroups) return;
     const FrameGroupDev& G = fd.g[gi];
-    const uint32_t bid = blockIdx.x - start;
     const PixT* src = reinterpret_cast<const PixT*>(G.src);
     const PixT* pred = reinterpret_cast<const PixT*>(G.pred);
     PixT* recon = reinterpret_cast<PixT*>(G.recon);

@@ -70,9 +70,9 @@ extern "C" int svt_hip_full_loop_frame(const svt_hip_full_loop_group* groups, in
         };
         for (int g = 0; g < ngroups; g++) {
             const svt_hip_full_loop_group& G = groups[g];
-            if (G.nblocks == 0 || full_loop_class_of(G.tx_size) != cls) continue;
-            const int w = kTxW[G.tx_size], h = kTxH[G.tx_size], pels = w * h;
-            const uint32_t per_wg = full_loop_blocks_per_wg(w, h), wgs = (G.nblocks + per_wg - 1) / per_wg;
+            if (G.nblocks == 0 || tx_class_of(G.tx_size) != cls) continue;
+            const int pels = kTxW[G.tx_size] * kTxH[G.tx_size];
+            const uint32_t per_wg = staged_blocks_per_wg(G.tx_size), wgs = (G.nblocks + per_wg - 1) / per_wg;
             if (fd.ngroups == FL_MAX_GROUPS || (size_t)total + wgs > 0x7fffffffu)
                 if (int rc = flush()) return rc;
             FullLoopGroupDev& D = fd.g[fd.ngroups++];

@@ -515,6 +515,14 @@ extern "C" int svt_hip_fwd_quant_planes_batch(const void* d_src, uint32_t src_st
 
 // ---- frame-level fan-out: independent groups on internal streams, forked from and joined into the caller's stream ----
 namespace {
+// blocks one 256-thread workgroup of an enc_frame_kernel body takes: 4x4 one block per lane; 32x32 F32_WAVES x 2; 64x64 E64_WAVES x 2;
+// the staged bodies staged_blocks_per_wg
+uint32_t frame_blocks_per_wg(int tx_size) {
+    if (tx_size == SVT_TX_4X4) return 256;
+    if (tx_size == SVT_TX_32X32) return F32_WAVES * 2;
+    if (tx_size == SVT_TX_64X64) return E64_WAVES * 2;
+    return staged_blocks_per_wg(tx_size);
+}
 }  // namespace
 
 // argument checks of a frame call's groups (also used by svt_hip_encode_recon_frame_ex before it enqueues its first phase)
@@ -564,7 +572,7 @@ extern "C" int svt_hip_encode_recon_frame(const svt_hip_frame_group* groups, int
             const svt_hip_frame_group& G = groups[g];
             if (G.nblocks == 0) continue;
             ok = !G.d_coeff && G.d_recon != G.d_src && (((uintptr_t)G.d_qcoeff) & 15) == 0;      // (type / size validated above)
-            per_class[mode == 1 ? 3 : frame_class_of(G.tx_size)]++;
+            per_class[mode == 1 ? 3 : tx_class_of(G.tx_size)]++;
         }
         if ((is_16bit && bd != 10) || (!is_16bit && bd != 8)) ok = false;
         for (int c = 0; c < 4; c++) ok = ok && per_class[c] <= FRAME_MAX_GROUPS;
@@ -584,7 +592,7 @@ extern "C" int svt_hip_encode_recon_frame(const svt_hip_frame_group* groups, int
             for (int k = 0; k < ngroups && ok; k++) {
                 const svt_hip_frame_group& G = groups[order[k]];
                 if (G.nblocks == 0) continue;
-                const int pels = kTxW[G.tx_size] * kTxH[G.tx_size], c = mode == 1 ? 3 : frame_class_of(G.tx_size);
+                const int pels = kTxW[G.tx_size] * kTxH[G.tx_size], c = mode == 1 ? 3 : tx_class_of(G.tx_size);
                 FrameGroupDev& D = fd[c].g[fd[c].ngroups];
                 D.qp = make_qparams(zbin, round, quant, quant_shift, dequant, pels > 1024 ? 2 : (pels > 256 ? 1 : 0));
                 for (int i = 0; i < 2; i++) ok = ok && D.qp.quant_shift[i] >= 0 && D.qp.dequant[i] >= 0 && D.qp.round[i] >= 0;
