@@ -152,6 +152,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
                                            c_uint32, c_uint32, c_void_p]
     L.svt_hip_full_loop_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     L.svt_hip_full_loop_frame.restype = c_int
+    L.svt_hip_intra_fast_loop_frame.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p]
+    L.svt_hip_intra_fast_loop_frame.restype = c_int
+    L.svt_hip_md_intra_candidates.argtypes = [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_void_p, c_void_p]
+    L.svt_hip_md_intra_candidates.restype = c_int
     return L
 
 
@@ -1020,6 +1024,98 @@ class SvtHipDsp:
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         return self.lib.svt_hip_full_loop_frame(groups, n, flavour, tabs[0].ctypes.data, tabs[1].ctypes.data, tabs[2].ctypes.data,
                                                 tabs[3].ctypes.data, tabs[4].ctypes.data, self._stream())
+
+    # -- mode-decision fast loop, intra candidates: prediction -> distortion per (block, candidate) ------------------------------
+    FAST_SAD, FAST_SSD = 0, 1
+
+    class FastLoopGroup(ctypes.Structure):
+        _fields_ = [("d_src", c_void_p), ("src_stride", c_uint32), ("d_src_xy", c_void_p),
+                    ("d_top_neigh", c_void_p), ("d_left_neigh", c_void_p), ("neigh_pitch", c_int32),
+                    ("d_blocks", c_void_p), ("nblocks", c_uint32), ("tx_size", c_int32),
+                    ("ncand", c_int32), ("modes", ctypes.c_uint8 * 64), ("angle_deltas", ctypes.c_int8 * 64),
+                    ("d_dist", c_void_p), ("d_pred", c_void_p)]
+
+    def make_fast_loop_groups(self, groups):
+        """groups: list of dicts with tensors src (plane or dense [n, H, W] uint8), optional src_xy (int32 x | y << 16; absent:
+        dense), top / left (uint8 [n, pitch], element 0 = the corner), blocks (uint8 [n, 8], IntraBlk layout), dist (int64
+        [n, ncand]), optional pred (uint8 [n, ncand, H, W]), plus src_stride, nblocks, tx_size, modes, deltas (host lists; ncand
+        defaults to len(modes)).  -> ctypes array (keep the tensors alive!)"""
+        arr = (self.FastLoopGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+            modes, deltas = list(g["modes"])[:64], list(g["deltas"])[:64]
+            m = (ctypes.c_uint8 * 64)(*(modes + [0] * (64 - len(modes))))
+            d = (ctypes.c_int8 * 64)(*(deltas + [0] * (64 - len(deltas))))
+            top = g.get("top")
+            arr[i] = self.FastLoopGroup(P("src"), g.get("src_stride", 0), P("src_xy"), P("top"), P("left"),
+                                        g.get("neigh_pitch", top.shape[1] if top is not None else 0), P("blocks"), g["nblocks"],
+                                        g["tx_size"], g.get("ncand", len(modes)), m, d, P("dist"), P("pred"))
+        return arr
+
+    def intra_fast_loop_frame(self, groups, metric, flavour=1):
+        """groups: a ctypes array from make_fast_loop_groups (or the list of dicts itself) -> the library's return code"""
+        if isinstance(groups, list):
+            keep = groups
+            groups = self.make_fast_loop_groups(keep)
+            n = len(keep)
+        else:
+            n = len(groups)
+        return self.lib.svt_hip_intra_fast_loop_frame(groups, n, metric, flavour, self._stream())
+
+    def intra_fast_loop(self, src, top, left, blocks, tx_size, modes, deltas, metric, flavour=1, want_pred=False, src_xy=None, src_stride=0):
+        """One group: src dense uint8 [n, H, W] (or a plane with src_xy / src_stride), top / left uint8 [n, pitch], blocks uint8 [n, 8];
+        modes / deltas: the host candidate list.  -> dist int64 [n, ncand], pred uint8 [n, ncand, H, W] | None"""
+        t = self.torch
+        n, nc = blocks.shape[0], len(modes)
+        w, h = (TX_W[tx_size], TX_H[tx_size]) if 0 <= tx_size < 19 else (4, 4)        # the library reports a bad tx_size
+        dist = t.empty((n, nc), dtype=t.int64, device=blocks.device)
+        pred = t.empty((n, nc, h, w), dtype=t.uint8, device=blocks.device) if want_pred else None
+        g = dict(src=src, src_xy=src_xy, src_stride=src_stride, top=top, left=left, blocks=blocks, nblocks=n, tx_size=tx_size,
+                 modes=modes, deltas=deltas, dist=dist, pred=pred)
+        self._check(self.intra_fast_loop_frame([g], metric, flavour), "svt_hip_intra_fast_loop_frame")
+        return dist, pred
+
+    @staticmethod
+    def md_intra_candidates(bwidth, bheight, sq_size, bsize, intra_pred_mode=0, is_16bit=False):
+        """The luma candidate list inject_intra_candidates enumerates for one block (EbModeDecision.c:2364-2530; the rules of
+        svt_hip_md_intra_candidates): (modes uint8[], angle_deltas int8[]) in AV1 PredictionMode numbering.  bsize: AV1 block_size
+        (BLOCK_4X4 = 0 .. BLOCK_64X16 = 21); sq_size: the side of the enclosing square partition block."""
+        import numpy as np
+        angle = [0, 90, 180, 45, 135, 113, 157, 203, 67]
+        last = 11 if is_16bit else 12
+        big_or_thin = sq_size > 16 or bwidth == 4 or bheight == 4
+        no_z2 = no_refine = no_angle = False
+        if intra_pred_mode == 3:
+            no_angle = True
+        elif intra_pred_mode == 2:
+            no_angle = big_or_thin
+        elif intra_pred_mode == 1:
+            no_z2 = no_refine = big_or_thin
+        nd = 7 if bsize >= 3 and not no_refine else 1
+        modes, deltas = [], []
+        for m in range(last + 1):
+            if 1 <= m <= 8:
+                if no_angle:
+                    continue
+                for k in range(nd):
+                    d = 0 if nd == 1 else k - (nd >> 1)
+                    p = angle[m] + 3 * d
+                    if no_z2 and 90 < p < 180:
+                        continue
+                    modes.append(m); deltas.append(d)
+            else:
+                modes.append(m); deltas.append(0)
+        return np.array(modes, np.uint8), np.array(deltas, np.int8)
+
+    @staticmethod
+    def md_intra_candidates_lib(bwidth, bheight, sq_size, bsize, intra_pred_mode=0, is_16bit=False):
+        """the same list from the library's host helper (svt_hip_md_intra_candidates; no device needed)"""
+        import numpy as np
+        m = np.zeros(64, np.uint8); d = np.zeros(64, np.int8)
+        n = load_library().svt_hip_md_intra_candidates(bwidth, bheight, sq_size, bsize, intra_pred_mode, int(is_16bit), m.ctypes.data, d.ctypes.data)
+        if n < 0:
+            raise SvtHipError(f"svt_hip_md_intra_candidates = {n}")
+        return m[:n].copy(), d[:n].copy()
 
     def full_loop(self, src, pred, tx_size, tx_types, qrow, flavour=1, want_qcoeff=False, want_dqcoeff=False, iscan=None):
         """Dense batches: src, pred uint8 [n, H, W].  tx_types: 1..16 distinct types; iscan: int16 [ntypes, NC] device tensor

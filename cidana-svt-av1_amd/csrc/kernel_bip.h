@@ -15,7 +15,7 @@
 // HBM - every wave ran every stage (a stage is predicated per lane, but the wave issues it if ONE of its blocks needs it) and the
 // per-pixel `switch` over the predictor kind was executed once per kind present in the wave.  Now:
 //   * the block size is a template parameter (loops unrolled, no run-time divisions);
-//   * svt_hip_intra_order_blocks_batch (bip_order_*_kernel below) sorts the batch's block indices by predictor kind on the
+//   * svt_hip_intra_order_blocks_batch (bip_order_tile_kernel, svt_hip_intra.hip) sorts the batch's block indices by predictor kind on the
 //     device (count, scan of 13 bins, scatter) and the kernel walks the batch through that order: a wave's blocks then share
 //     a kind except at the 12 class boundaries;
 //   * stages 2 - 4 are skipped by the whole wave when none of its blocks is angled / up-sampled (a ballot), and a wave whose
@@ -106,88 +106,56 @@ __device__ __forceinline__ int bip_kind_of(const BipBlk& d, int w, int h, int& p
     return mode == 9 ? IM_SMOOTH : (mode == 10 ? IM_SMOOTH_V : (mode == 11 ? IM_SMOOTH_H : IM_PAETH));
 }
 
-// ---- ordering pass: block indices grouped by kind inside TILES of BIP_ORDER_TILE consecutive blocks (a counting sort over the
-// IM_MODES = 13 bins in LDS; the order inside a bin is whatever the atomics give - the prediction of a block does not depend on its
-// place in the order).  One kernel, no global counters: the first version sorted the whole batch (count kernel + scatter kernel, 17 +
-// 20 us per 2^20 blocks, each a single residency round of 256 workgroups waiting on 13 contended global atomics); a wave only needs
-// ITS four blocks to share a kind, and a tile of 4 096 blocks holds ~ 315 of each, so the waves of a tile are uniform except at its
-// (at most 12) kind boundaries - 1.2 % of the waves; a mixed wave runs every kind it holds, several times a uniform wave's cost
-// (tiles of 1 024 blocks measured no faster than the global sort for that reason).  1 024 threads per workgroup: 256 workgroups of
-// 16 waves keep enough loads in flight.
-constexpr int BIP_ORDER_ITEMS = 4;
-constexpr int BIP_ORDER_THREADS = 1024;
-constexpr int BIP_ORDER_TILE = BIP_ORDER_THREADS * BIP_ORDER_ITEMS;
-__global__ __launch_bounds__(BIP_ORDER_THREADS) void bip_order_tile_kernel(const BipBlk* __restrict__ blks, int w, int h, uint32_t* __restrict__ order, uint32_t nblocks) {
-    __shared__ uint32_t s_cnt[16], s_base[16];
-    if (threadIdx.x < 16) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    const uint32_t base = blockIdx.x * (uint32_t)BIP_ORDER_TILE;
-    BipBlk d[BIP_ORDER_ITEMS];
+// ---- per-block steps, shared by bip_kernel and fast_loop_kernel (kernel_fast_loop.h) ------------------------------------------
+// A block is served by a group of LPB consecutive lanes of a wave; `lane` is the lane's index inside that group.  No step fences
+// on entry; each one that writes LDS ends with the wave-level fence its readers need.
+template <int W, int H>
+struct BipGeom {
+    static constexpr int LPB = bip_lanes_per_block(W, H), BPW = 64 / LPB, EL = bip_edge_len(W, H);
+    static constexpr int LSH = LPB == 4 ? 2 : (LPB == 8 ? 3 : (LPB == 16 ? 4 : (LPB == 32 ? 5 : 6)));
+    static constexpr int NR = (W + H + LPB - 1) / LPB;        // rounds of LPB lanes over w + h samples (<= 3)
+    // A lane predicts PPL = min(W, 16) samples of one row per item: one address, one 4 .. 32-byte store (16 bytes per lane is the
+    // store shape the HBM likes) and a quarter of the loop overhead of the first version's 4 samples per step.
+    static constexpr int PPL = W >= 16 ? 16 : W, CPR = W / PPL, ITEMS = CPR * H;
+    static constexpr int NI = (ITEMS + LPB - 1) / LPB;        // items per lane
+};
+
+// The raw edges of one block, in registers: the w + h samples of both rows (the row of a block holds them whatever is "available":
+// neigh_pitch >= 1 + 2 max(w, h)) plus the three single samples the defaults read.  Which of them count, and what replaces the others,
+// is applied in LDS by bip_edges - the first version loaded the descriptor, then the samples it selected (top[min(i, avail - 1)]):
+// two dependent round trips to HBM in a kernel whose waves do little else than wait for them.
+template <int W, int H>
+struct BipRaw {
+    int t[BipGeom<W, H>::NR], l[BipGeom<W, H>::NR];
+    int top_m1, top_0, left_0;
+};
+template <typename PixT, int W, int H>
+__device__ __forceinline__ void bip_load_raw(BipRaw<W, H>& R, const PixT* __restrict__ top, const PixT* __restrict__ left, int lane) {
+    constexpr int LPB = BipGeom<W, H>::LPB;
 #pragma unroll
-    for (int k = 0; k < BIP_ORDER_ITEMS; k++) {                 // the tile's descriptors, coalesced, all loads in flight together
-        const uint32_t i = base + k * (uint32_t)BIP_ORDER_THREADS + threadIdx.x;
-        d[k] = blks[i < nblocks ? i : 0u];
+    for (int t = 0; t < BipGeom<W, H>::NR; t++) {
+        const int i = lane + t * LPB;
+        R.t[t] = i < W + H ? (int)top[i] : 0;
+        R.l[t] = i < W + H ? (int)left[i] : 0;
     }
-    uint32_t kind[BIP_ORDER_ITEMS], local[BIP_ORDER_ITEMS];
-#pragma unroll
-    for (int k = 0; k < BIP_ORDER_ITEMS; k++) {
-        const uint32_t i = base + k * (uint32_t)BIP_ORDER_THREADS + threadIdx.x;
-        int pa;
-        kind[k] = (uint32_t)bip_kind_of(d[k], w, h, pa);
-        local[k] = i < nblocks ? atomicAdd(&s_cnt[kind[k]], 1u) : 0u;
-    }
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        uint32_t start = 0;                                     // bin start = the counts of the bins before it
-        for (int k = 0; k < (int)threadIdx.x; k++) start += s_cnt[k];
-        s_base[threadIdx.x] = start;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < BIP_ORDER_ITEMS; k++) {
-        const uint32_t i = base + k * (uint32_t)BIP_ORDER_THREADS + threadIdx.x;
-        if (i < nblocks) order[base + s_base[kind[k]] + local[k]] = i;
-    }
+    R.top_m1 = (int)top[-1]; R.top_0 = (int)top[0]; R.left_0 = (int)left[0];
 }
 
-template <typename PixT, int W, int H>
-__global__ __launch_bounds__(64 * BIP_WAVES) void bip_kernel(
-    PixT* __restrict__ dst, int32_t dst_stride, size_t dst_block_pitch, const uint32_t* __restrict__ dst_offsets,
-    const PixT* __restrict__ top_all, const PixT* __restrict__ left_all, int32_t neigh_pitch, const BipBlk* __restrict__ blks,
-    const uint32_t* __restrict__ order, int bd, uint32_t nblocks) {
+// What the pixel step needs of a block once its edges are prepared
+struct BipPred {
+    int kind, dc, dx, dy, up_a, up_l, last_a, last_l, bl_s, tr_s, tl_s;
+};
+
+// Stages 1 - 5 of build_intra_predictors for one block and one (mode, angle_delta) - the descriptor's: the raw samples to LDS (A / L:
+// the block's above / left edge, 16-bit, positions [-16, EL - 16)), extension, corner, smoothing, up-sampling, the pair form of the
+// angled kinds (PA / PL) and DC.  Every stage rewrites the edges from R, so the step can run again on the same LDS for another mode
+// once the caller has fenced the previous pixel step's reads.  Ends fenced: A, L, PA, PL are ready for bip_pixels.
+template <int W, int H>
+__device__ __forceinline__ BipPred bip_edges(const BipRaw<W, H>& R, const BipBlk& d, uint16_t* A, uint16_t* L, uint32_t* PA, uint32_t* PL,
+                                             int bd, int lane) {
     constexpr int w = W, h = H;
-    constexpr int LPB = bip_lanes_per_block(W, H), bpw = 64 / LPB, EL = bip_edge_len(W, H);
-    constexpr int lsh = LPB == 4 ? 2 : (LPB == 8 ? 3 : (LPB == 16 ? 4 : (LPB == 32 ? 5 : 6)));
-    __shared__ __attribute__((aligned(16))) uint16_t s_edge[BIP_WAVES * bpw * 2 * EL];          // [wave][block of the wave][above | left][EL]
-    // the directional pixel loops read the edges in PAIR form (dword i = edge[i] | edge[i + 1] << 16, kernel_intra.h): built once per
-    // block after the edge stages, clamped at the last valid sample - a pixel is then one ds_read_b32 + one v_dot2_u32_u16 and the
-    // reference's "base >= max_base -> edge[max_base]" falls out of the same interpolation ((32 e + 16) >> 5 == e)
-    __shared__ __attribute__((aligned(16))) uint32_t s_pair[BIP_WAVES * bpw * 2 * EL];
-    const int wv = threadIdx.x >> 6, sub = (threadIdx.x & 63) >> lsh;
-    const int lane = threadIdx.x & (LPB - 1);                 // lane inside the block's group
-    const uint32_t blk_id = (blockIdx.x * BIP_WAVES + (uint32_t)wv) * (uint32_t)bpw + (uint32_t)sub;
-    const bool live = blk_id < nblocks;
-    const uint32_t b = live ? (order ? order[blk_id] : blk_id) : (order ? order[0] : 0u);      // a spare group replays a block without storing
-    const PixT* __restrict__ top = top_all + (size_t)b * neigh_pitch + 1;       // element 0 is the corner: top[-1]
-    const PixT* __restrict__ left = left_all + (size_t)b * neigh_pitch + 1;
-    // Every global load of the block is issued here, side by side: the descriptor AND the raw w + h samples of both edges (the row
-    // of a block holds them whatever is "available": neigh_pitch >= 1 + 2 max(w, h)).  Which of them count, and what replaces the
-    // others, is applied in LDS below - the first version loaded the descriptor, then the samples it selected (top[min(i, avail - 1)]):
-    // two dependent round trips to HBM in a kernel whose waves do little else than wait for them.
-    constexpr int NR = (W + H + LPB - 1) / LPB;               // rounds of LPB lanes over w + h samples (<= 3)
-    int raw_t[NR], raw_l[NR];
-#pragma unroll
-    for (int t = 0; t < NR; t++) {
-        const int i = lane + t * LPB;
-        raw_t[t] = i < W + H ? (int)top[i] : 0;
-        raw_l[t] = i < W + H ? (int)left[i] : 0;
-    }
-    const int top_m1 = (int)top[-1], top_0 = (int)top[0], left_0 = (int)left[0];
-    const BipBlk d = blks[b];
-    uint16_t* A = s_edge + (size_t)((wv * bpw + sub) * 2) * EL + 16;
-    uint16_t* L = A + EL;
-    uint32_t* PA = s_pair + (size_t)((wv * bpw + sub) * 2) * EL + 16;
-    uint32_t* PL = PA + EL;
+    constexpr int LPB = BipGeom<W, H>::LPB, NR = BipGeom<W, H>::NR;
+    const int top_m1 = R.top_m1, top_0 = R.top_0, left_0 = R.left_0;
     const int maxv = (1 << bd) - 1, base = 128 << (bd - 8);
 
     const int mode = d.mode > 12 ? 12 : d.mode;
@@ -225,7 +193,7 @@ __global__ __launch_bounds__(64 * BIP_WAVES) void bip_kernel(
 #pragma unroll
     for (int t = 0; t < NR; t++) {
         const int i = lane + t * LPB;
-        if (i < W + H) { A[i] = (uint16_t)raw_t[t]; L[i] = (uint16_t)raw_l[t]; }
+        if (i < W + H) { A[i] = (uint16_t)R.t[t]; L[i] = (uint16_t)R.l[t]; }
     }
     wave_lds_fence();
     {
@@ -320,13 +288,16 @@ __global__ __launch_bounds__(64 * BIP_WAVES) void bip_kernel(
         }
     wave_lds_fence();
     }
-    // ---- stage 5: prediction ---------------------------------------------------------------------------------------------
+    // ---- stage 5: prediction set-up ---------------------------------------------------------------------------------------
     // resolve to one of the predictor kinds
     int kind;
     if (const_fill) kind = IM_DC_128;
     else if (is_dr) kind = p_angle == 90 ? IM_V : (p_angle == 180 ? IM_H : (p_angle < 90 ? IM_Z1 : (p_angle < 180 ? IM_Z2 : IM_Z3))); else if (mode == 0) kind = n_left > 0 ? (n_top > 0 ? IM_DC : IM_DC_LEFT) : (n_top > 0 ? IM_DC_TOP : IM_DC_128);       // dc_pred[left][top], :3851
     else kind = mode == 9 ? IM_SMOOTH : (mode == 10 ? IM_SMOOTH_V : (mode == 11 ? IM_SMOOTH_H : IM_PAETH));
     // pair form of the edges for the angled kinds (the wave skips it when none of its blocks is one)
+    // the directional pixel loops read the edges in PAIR form (dword i = edge[i] | edge[i + 1] << 16, kernel_intra.h): built once per
+    // block after the edge stages, clamped at the last valid sample - a pixel is then one ds_read_b32 + one v_dot2_u32_u16 and the
+    // reference's "base >= max_base -> edge[max_base]" falls out of the same interpolation ((32 e + 16) >> 5 == e)
     const bool is_z = kind == IM_Z1 || kind == IM_Z2 || kind == IM_Z3;
     // last valid staged sample of each edge: without up-sampling [-1, need - 1], with it [-2, 2 need - 2] (av1_upsample_intra_edge);
     // for zone 1 / 3 that is max_base = (w + h - 1) << up
@@ -347,116 +318,161 @@ __global__ __launch_bounds__(64 * BIP_WAVES) void bip_kernel(
         for (int m = LPB >> 1; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, 64);
         dc = (sum + ((na + nl) >> 1)) / (na + nl);
     }
-    const size_t boff = dst_offsets ? (size_t)dst_offsets[b] : (size_t)b * dst_block_pitch;
-    PixT* __restrict__ out = dst + boff;
-    // A lane writes PPL = min(W, 16) samples of one row per step: one address, one 4 .. 32-byte store (16 bytes per lane is the store
-    // shape the HBM likes) and a quarter of the loop overhead of the first version's 4 samples per step.
-    constexpr int PPL = W >= 16 ? 16 : W, CPR = W / PPL, items = CPR * H;
-    const int bl_s = (int)L[h - 1], tr_s = (int)A[w - 1], tl_s = (int)A[-1];
-    // KC::value >= 0: every block of the wave has this kind - the switch below is resolved at compile time; -1: mixed wave
-    auto predict = [&](auto KC) {
-    constexpr int KU = decltype(KC)::value;
+    BipPred P;
+    P.kind = kind; P.dc = dc; P.dx = dx; P.dy = dy; P.up_a = up_a; P.up_l = up_l; P.last_a = last_a; P.last_l = last_l;
+    P.bl_s = (int)L[h - 1]; P.tr_s = (int)A[w - 1]; P.tl_s = (int)A[-1];
+    return P;
+}
+
+// The PPL samples of row r, columns c0 .. c0 + PPL - 1 of the prediction (reads A, L, PA, PL as bip_edges left them).  KU >= 0: the
+// block's kind is KU (the switch below is resolved at compile time); -1: P.kind at run time.
+template <int KU, typename PixT, int W, int H>
+__device__ __forceinline__ void bip_pixels(const BipPred& P, const uint16_t* A, const uint16_t* L, const uint32_t* PA, const uint32_t* PL,
+                                           int bd, int r, int c0, int (&px)[BipGeom<W, H>::PPL]) {
+    constexpr int w = W, h = H, PPL = BipGeom<W, H>::PPL;
+    const int maxv = (1 << bd) - 1;
+    const int kk = KU >= 0 ? KU : P.kind;
+    const int up_a = P.up_a, up_l = P.up_l, dx = P.dx, dy = P.dy;
+    // the row's samples of the above edge as 16-bit pairs (aligned: c0 is a multiple of PPL, the edge arrays start 16-byte aligned)
+    uint32_t aw[PPL / 2];
+    if (KU < 0 || KU == IM_V || KU == IM_SMOOTH || KU == IM_SMOOTH_V || KU == IM_PAETH) {
+        const uint32_t* ap = reinterpret_cast<const uint32_t*>(A + c0);
 #pragma unroll
-    for (int q0 = 0; q0 < items; q0 += LPB) {
-        const int q = q0 + lane;
-        if (items % LPB != 0 && q >= items) break;
-        const int r = q / CPR, c0 = (q % CPR) * PPL;
-        const int kk = KU >= 0 ? KU : kind;
-        // the row's samples of the above edge as 16-bit pairs (aligned: c0 is a multiple of PPL, the edge arrays start 16-byte aligned)
-        uint32_t aw[PPL / 2];
-        if (KU < 0 || KU == IM_V || KU == IM_SMOOTH || KU == IM_SMOOTH_V || KU == IM_PAETH) {
-            const uint32_t* ap = reinterpret_cast<const uint32_t*>(A + c0);
-#pragma unroll
-            for (int k = 0; k < PPL / 2; k++) aw[k] = ap[k];
-        }
-        const int lr = (int)L[r < H ? r : 0];
-        const int whr = kSmWeights[h + r];
-        // zone 1 / 2: the row's position on the above edge and its weight pair
-        const int z_x = (kk == IM_Z2 ? -dx : dx) * (r + 1);
-        const int z_b = z_x >> (6 - up_a);
-        const uint32_t z_sh = (uint32_t)(((z_x * (1 << up_a)) & 0x3f) >> 1), z_w = z_sh * 0xffffu + 32u;
-        int px[PPL];
-#pragma unroll
-        for (int k = 0; k < PPL; k++) {
-            const int c = c0 + k;
-            const int ac = (int)((aw[k >> 1] >> (16 * (k & 1))) & 0xffffu);
-            int v;
-            switch (kk) {
-            case IM_V: v = ac; break;
-            case IM_H: v = lr; break;
-            case IM_SMOOTH: {
-                const int ww = kSmWeights[w + c];
-                v = (whr * ac + (256 - whr) * bl_s + ww * lr + (256 - ww) * tr_s + 256) >> 9;
-            } break;
-            case IM_SMOOTH_V: v = (whr * ac + (256 - whr) * bl_s + 128) >> 8; break;
-            case IM_SMOOTH_H: { const int ww = kSmWeights[w + c]; v = (ww * lr + (256 - ww) * tr_s + 128) >> 8; } break;
-            case IM_PAETH: {
-                const int t = ac, l = lr, pb = t + l - tl_s;
-                const int pl = abs(pb - l), pt = abs(pb - t), ptl = abs(pb - tl_s);
-                v = (pl <= pt && pl <= ptl) ? l : (pt <= ptl ? t : tl_s);
-            } break;
-            case IM_Z1: {     // av1_dr_prediction_z1 (:370 / :3394): base >= max_base reads the pair (e, e) at max_base
-                v = (int)dir_lerp2(PA[min(z_b + (c << up_a), last_a)], z_w);
-                if (sizeof(PixT) == 2) v = min(v, maxv);
-            } break;
-            case IM_Z3: {     // av1_dr_prediction_z3 (:447 / :3475)
-                const int y = dy * (c + 1), bs = (y >> (6 - up_l)) + (r << up_l);
-                const uint32_t sh = (uint32_t)(((y << up_l) & 0x3f) >> 1);
-                v = (int)dir_lerp2(PL[min(bs, last_l)], sh * 0xffffu + 32u);          // (32 - sh) | sh << 16
-                if (sizeof(PixT) == 2) v = min(v, maxv);
-            } break;
-            case IM_Z2: {     // av1_dr_prediction_z2 (:405 / :3431)
-                const int base1 = z_b + (c << up_a);
-                const bool ab = base1 >= -(1 << up_a);
-                const int y = (r << 6) - dy * (c + 1), base2 = y >> (6 - up_l);
-                const uint32_t sh2 = (uint32_t)(((y * (1 << up_l)) & 0x3f) >> 1);
-                const uint32_t* pp = ab ? PA + base1 : PL + base2;
-                v = (int)dir_lerp2(*pp, ab ? z_w : sh2 * 0xffffu + 32u);
-                if (sizeof(PixT) == 2) v = min(v, maxv);
-            } break;
-            default: v = dc; break;          // IM_DC, IM_DC_TOP, IM_DC_LEFT, IM_DC_128 and the constant fill
-            }
-            px[k] = v;
-        }
-        if (live) {
-            PixT* o = out + (size_t)r * dst_stride + c0;
-            constexpr int NB = PPL * (int)sizeof(PixT);          // 4 .. 32 bytes
-            uint32_t pw[NB / 4];
-#pragma unroll
-            for (int k = 0; k < NB / 4; k++) {
-                if (sizeof(PixT) == 1) pw[k] = (uint32_t)px[4 * k] | ((uint32_t)px[4 * k + 1] << 8) | ((uint32_t)px[4 * k + 2] << 16) | ((uint32_t)px[4 * k + 3] << 24);
-                else pw[k] = (uint32_t)px[2 * k] | ((uint32_t)px[2 * k + 1] << 16);
-            }
-            constexpr int AL = NB >= 16 ? 16 : NB;               // widest store unit
-            if ((reinterpret_cast<uintptr_t>(o) & (AL - 1)) == 0) {
-                if constexpr (NB == 4) *reinterpret_cast<uint32_t*>(o) = pw[0];
-                else if constexpr (NB == 8) *reinterpret_cast<uint2*>(o) = make_uint2(pw[0], pw[1]);
-                else {
-#pragma unroll
-                    for (int k = 0; k < NB / 16; k++) reinterpret_cast<uint4*>(o)[k] = make_uint4(pw[4 * k], pw[4 * k + 1], pw[4 * k + 2], pw[4 * k + 3]);
-                }
-            } else if ((reinterpret_cast<uintptr_t>(o) & 3) == 0) {
-#pragma unroll
-                for (int k = 0; k < NB / 4; k++) reinterpret_cast<uint32_t*>(o)[k] = pw[k];
-            } else {
-#pragma unroll
-                for (int k = 0; k < PPL; k++) o[k] = (PixT)px[k];
-            }
-        }
+        for (int k = 0; k < PPL / 2; k++) aw[k] = ap[k];
     }
-    };
+    const int lr = (int)L[r < H ? r : 0];
+    const int whr = kSmWeights[h + r];
+    // zone 1 / 2: the row's position on the above edge and its weight pair
+    const int z_x = (kk == IM_Z2 ? -dx : dx) * (r + 1);
+    const int z_b = z_x >> (6 - up_a);
+    const uint32_t z_sh = (uint32_t)(((z_x * (1 << up_a)) & 0x3f) >> 1), z_w = z_sh * 0xffffu + 32u;
+#pragma unroll
+    for (int k = 0; k < PPL; k++) {
+        const int c = c0 + k;
+        const int ac = (int)((aw[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+        int v;
+        switch (kk) {
+        case IM_V: v = ac; break;
+        case IM_H: v = lr; break;
+        case IM_SMOOTH: {
+            const int ww = kSmWeights[w + c];
+            v = (whr * ac + (256 - whr) * P.bl_s + ww * lr + (256 - ww) * P.tr_s + 256) >> 9;
+        } break;
+        case IM_SMOOTH_V: v = (whr * ac + (256 - whr) * P.bl_s + 128) >> 8; break;
+        case IM_SMOOTH_H: { const int ww = kSmWeights[w + c]; v = (ww * lr + (256 - ww) * P.tr_s + 128) >> 8; } break;
+        case IM_PAETH: {
+            const int t = ac, l = lr, pb = t + l - P.tl_s;
+            const int pl = abs(pb - l), pt = abs(pb - t), ptl = abs(pb - P.tl_s);
+            v = (pl <= pt && pl <= ptl) ? l : (pt <= ptl ? t : P.tl_s);
+        } break;
+        case IM_Z1: {     // av1_dr_prediction_z1 (:370 / :3394): base >= max_base reads the pair (e, e) at max_base
+            v = (int)dir_lerp2(PA[min(z_b + (c << up_a), P.last_a)], z_w);
+            if (sizeof(PixT) == 2) v = min(v, maxv);
+        } break;
+        case IM_Z3: {     // av1_dr_prediction_z3 (:447 / :3475)
+            const int y = dy * (c + 1), bs = (y >> (6 - up_l)) + (r << up_l);
+            const uint32_t sh = (uint32_t)(((y << up_l) & 0x3f) >> 1);
+            v = (int)dir_lerp2(PL[min(bs, P.last_l)], sh * 0xffffu + 32u);          // (32 - sh) | sh << 16
+            if (sizeof(PixT) == 2) v = min(v, maxv);
+        } break;
+        case IM_Z2: {     // av1_dr_prediction_z2 (:405 / :3431)
+            const int base1 = z_b + (c << up_a);
+            const bool ab = base1 >= -(1 << up_a);
+            const int y = (r << 6) - dy * (c + 1), base2 = y >> (6 - up_l);
+            const uint32_t sh2 = (uint32_t)(((y * (1 << up_l)) & 0x3f) >> 1);
+            const uint32_t* pp = ab ? PA + base1 : PL + base2;
+            v = (int)dir_lerp2(*pp, ab ? z_w : sh2 * 0xffffu + 32u);
+            if (sizeof(PixT) == 2) v = min(v, maxv);
+        } break;
+        default: v = P.dc; break;          // IM_DC, IM_DC_TOP, IM_DC_LEFT, IM_DC_128 and the constant fill
+        }
+        px[k] = v;
+    }
+}
+
+// N = PPL samples to o: one 4 .. 32-byte store when the address allows
+template <typename PixT, int N>
+__device__ __forceinline__ void bip_store_row(PixT* o, const int (&px)[N]) {
+    constexpr int NB = N * (int)sizeof(PixT);          // 4 .. 32 bytes
+    uint32_t pw[NB / 4];
+#pragma unroll
+    for (int k = 0; k < NB / 4; k++) {
+        if (sizeof(PixT) == 1) pw[k] = (uint32_t)px[4 * k] | ((uint32_t)px[4 * k + 1] << 8) | ((uint32_t)px[4 * k + 2] << 16) | ((uint32_t)px[4 * k + 3] << 24);
+        else pw[k] = (uint32_t)px[2 * k] | ((uint32_t)px[2 * k + 1] << 16);
+    }
+    constexpr int AL = NB >= 16 ? 16 : NB;               // widest store unit
+    if ((reinterpret_cast<uintptr_t>(o) & (AL - 1)) == 0) {
+        if constexpr (NB == 4) *reinterpret_cast<uint32_t*>(o) = pw[0];
+        else if constexpr (NB == 8) *reinterpret_cast<uint2*>(o) = make_uint2(pw[0], pw[1]);
+        else {
+#pragma unroll
+            for (int k = 0; k < NB / 16; k++) reinterpret_cast<uint4*>(o)[k] = make_uint4(pw[4 * k], pw[4 * k + 1], pw[4 * k + 2], pw[4 * k + 3]);
+        }
+    } else if ((reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+#pragma unroll
+        for (int k = 0; k < NB / 4; k++) reinterpret_cast<uint32_t*>(o)[k] = pw[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; k++) o[k] = (PixT)px[k];
+    }
+}
+
+// F(std::integral_constant<int, K>) with K = the kind every block of the wave shares (the `switch` is taken once per wave, on a
+// scalar), or K = -1 for a wave of mixed kinds
+template <typename F>
+__device__ __forceinline__ void bip_by_kind(int kind, F&& f) {
     const int kind0 = __builtin_amdgcn_readfirstlane(kind);
     if (__builtin_amdgcn_ballot_w64(kind != kind0) == 0) {
         switch (kind0) {
-#define BIP_CASE(K) case K: predict(std::integral_constant<int, K>{}); break;
+#define BIP_CASE(K) case K: f(std::integral_constant<int, K>{}); break;
         BIP_CASE(IM_DC) BIP_CASE(IM_V) BIP_CASE(IM_H) BIP_CASE(IM_SMOOTH) BIP_CASE(IM_SMOOTH_V) BIP_CASE(IM_SMOOTH_H) BIP_CASE(IM_PAETH)
         BIP_CASE(IM_DC_TOP) BIP_CASE(IM_DC_LEFT) BIP_CASE(IM_DC_128) BIP_CASE(IM_Z1) BIP_CASE(IM_Z2)
 #undef BIP_CASE
-        default: predict(std::integral_constant<int, IM_Z3>{}); break;
+        default: f(std::integral_constant<int, IM_Z3>{}); break;
         }
     } else {
-        predict(std::integral_constant<int, -1>{});
+        f(std::integral_constant<int, -1>{});
     }
+}
+
+template <typename PixT, int W, int H>
+__global__ __launch_bounds__(64 * BIP_WAVES) void bip_kernel(
+    PixT* __restrict__ dst, int32_t dst_stride, size_t dst_block_pitch, const uint32_t* __restrict__ dst_offsets,
+    const PixT* __restrict__ top_all, const PixT* __restrict__ left_all, int32_t neigh_pitch, const BipBlk* __restrict__ blks,
+    const uint32_t* __restrict__ order, int bd, uint32_t nblocks) {
+    using G = BipGeom<W, H>;
+    constexpr int LPB = G::LPB, bpw = G::BPW, EL = G::EL, PPL = G::PPL, CPR = G::CPR, items = G::ITEMS;
+    __shared__ __attribute__((aligned(16))) uint16_t s_edge[BIP_WAVES * bpw * 2 * EL];          // [wave][block of the wave][above | left][EL]
+    __shared__ __attribute__((aligned(16))) uint32_t s_pair[BIP_WAVES * bpw * 2 * EL];          // the pair form (bip_edges)
+    const int wv = threadIdx.x >> 6, sub = (threadIdx.x & 63) >> G::LSH;
+    const int lane = threadIdx.x & (LPB - 1);                 // lane inside the block's group
+    const uint32_t blk_id = (blockIdx.x * BIP_WAVES + (uint32_t)wv) * (uint32_t)bpw + (uint32_t)sub;
+    const bool live = blk_id < nblocks;
+    const uint32_t b = live ? (order ? order[blk_id] : blk_id) : (order ? order[0] : 0u);      // a spare group replays a block without storing
+    // Every global load of the block is issued here, side by side: the descriptor AND the raw samples of both edges
+    BipRaw<W, H> R;
+    bip_load_raw<PixT, W, H>(R, top_all + (size_t)b * neigh_pitch + 1, left_all + (size_t)b * neigh_pitch + 1, lane);   // element 0 is the corner
+    const BipBlk d = blks[b];
+    uint16_t* A = s_edge + (size_t)((wv * bpw + sub) * 2) * EL + 16;
+    uint16_t* L = A + EL;
+    uint32_t* PA = s_pair + (size_t)((wv * bpw + sub) * 2) * EL + 16;
+    uint32_t* PL = PA + EL;
+    const BipPred P = bip_edges<W, H>(R, d, A, L, PA, PL, bd, lane);
+
+    const size_t boff = dst_offsets ? (size_t)dst_offsets[b] : (size_t)b * dst_block_pitch;
+    PixT* __restrict__ out = dst + boff;
+    bip_by_kind(P.kind, [&](auto KC) {
+        constexpr int KU = decltype(KC)::value;
+#pragma unroll
+        for (int q0 = 0; q0 < items; q0 += LPB) {
+            const int q = q0 + lane;
+            if (items % LPB != 0 && q >= items) break;
+            const int r = q / CPR, c0 = (q % CPR) * PPL;
+            int px[PPL];
+            bip_pixels<KU, PixT, W, H>(P, A, L, PA, PL, bd, r, c0, px);
+            if (live) bip_store_row<PixT, PPL>(out + (size_t)r * dst_stride + c0, px);
+        }
+    });
 }
 
 }  // namespace svtdev

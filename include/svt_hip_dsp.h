@@ -130,6 +130,14 @@ int svt_hip_get_scan(int tx_size, int tx_type, int16_t *scan, int16_t *iscan);
 #define SVT_HIP_OIS_MAX_CANDIDATES 61
 int svt_hip_ois_candidates(uint32_t bsize, int temporal_layer_index, int intra_pred_mode, int is_used_as_reference,
                            int is_16bit, uint8_t *modes, int8_t *angle_deltas);
+/* the luma candidate list inject_intra_candidates enumerates for one block (EbModeDecision.c:2364-2530, MR_MODE 0): DC_PRED ..
+ * PAETH_PRED (.. SMOOTH_H_PRED when is_16bit, encoder_bit_depth > 8), 7 angle deltas -3..3 per directional mode when bsize >=
+ * BLOCK_8X8 (AV1 block_size enum order), thinned by the picture's intra_pred_mode 0..3 (disable_z2_prediction /
+ * disable_angle_refinement / disable_angle_prediction from sq_size > 16 and 4-sample sides).  sq_size is blk_geom->sq_size, the
+ * side of the enclosing square partition block.  Arrays of SVT_HIP_FAST_LOOP_MAX_CANDIDATES; returns the count (<= 61) or
+ * SVT_HIP_ERR_INVALID. */
+int svt_hip_md_intra_candidates(uint32_t bwidth, uint32_t bheight, uint32_t sq_size, int bsize, int intra_pred_mode, int is_16bit,
+                                uint8_t *modes, int8_t *angle_deltas);
 
 /* ============================================================================
  * (B) batched API — device pointers, `stream` is a hipStream_t (NULL = default)
@@ -713,6 +721,45 @@ int svt_hip_build_intra_predictors_ordered_batch(void *d_dst, int32_t dst_stride
                                                  const void *d_left_neigh, int32_t neigh_pitch,
                                                  const svt_hip_intra_blk *d_blocks, const uint32_t *d_order, int tx_size,
                                                  int is_16bit, int bd, size_t nblocks, void *stream);
+
+/* The intra candidates of the mode-decision fast loop, fused: perform_fast_loop (EbProductCodingLoop.c:1152-1300) for one plane
+ * and many (transform size, candidate list) groups in one call.  Per block of a group and per candidate of its list, in the list's
+ * order: the prediction of build_intra_predictors (as svt_hip_build_intra_predictors_batch: the block's descriptor gives
+ * availability, filt_type and disable_edge_filter, the candidate gives mode and angle delta; the descriptor's own mode / angle_delta
+ * are ignored) and its distortion against the source block, 8-bit samples:
+ *   SVT_HIP_FAST_SAD   the plain W x H SAD every NxMSadKernelSubSampled_funcPtrArray entry computes (fast_loop_nx_m_sad_kernel and
+ *                      the AVX2 kernels agree), either flavour, all 19 sizes;
+ *   SVT_HIP_FAST_SSD   SVT_HIP_FLAVOUR_C: the exact sum of (src - pred)^2 over the W x H block, spatial_full_distortion_kernel with
+ *                      (bwidth, bheight).  DELIBERATE DIVERGENCE: the reference's call site (:3059-3077) passes (bheight, bwidth)
+ *                      into (area_width, area_height); this is the corrected call, all 19 sizes.
+ *                      SVT_HIP_FLAVOUR_AVX2: the arithmetic of the table entry the encoder runs (the SSSE3 kernels
+ *                      spatial_full_distortion_kernel{4x4,8x8,16_mx_n}, EbPictureOperators_Intrinsic_SSE4_1.c:495-620): per
+ *                      sample t = (a - b) & 255, d = t <= 128 ? t : 256 - t, d * d, summed in 32 bits.  Square sizes only: on a
+ *                      non-square block the reference's kernels read samples outside the block (the 4x4 / 8x8 kernels cover a
+ *                      fixed square, the swapped area covers other rows), stale prediction rows included - a result that cannot be
+ *                      reproduced, so the call returns SVT_HIP_ERR_INVALID (the second divergence).
+ * Chroma (CHROMA_MODE_0, UV modes other than UV_CFL_PRED): one group per plane with the chroma size; the caller adds the Cb and Cr
+ * distortions.  d_dist[b * ncand + c] receives the distortion; d_pred (optional, 16-byte aligned; NULL: not written) the predictions,
+ * dense [nblocks][ncand][H][W].  Source: d_src_xy[b] = x | y << 16 on a plane of src_stride samples, or NULL: dense W * H samples per
+ * block.  Neighbours as in svt_hip_build_intra_predictors_batch (element 0 = the corner, neigh_pitch >= 1 + 2 * max(W, H)).
+ * The candidate list is a HOST array in the group (svt_hip_md_intra_candidates gives inject_intra_candidates' list).  Every argument,
+ * empty groups' tx_size and lists included, is validated before the first launch; invalid input (ncand outside 1 .. 64, a mode above
+ * 12, a delta outside -3 .. 3 or on a non-directional mode, NULL required pointers, d_dist not 8-byte aligned, d_pred not 16-byte
+ * aligned, the AVX2-flavour SSD on a non-square size) returns SVT_HIP_ERR_INVALID and launches nothing.  The call only enqueues work
+ * (one launch per non-empty group, the group in the kernel arguments) and can be captured into a HIP graph. */
+enum { SVT_HIP_FAST_SAD = 0, SVT_HIP_FAST_SSD = 1 };
+#define SVT_HIP_FAST_LOOP_MAX_CANDIDATES 64
+typedef struct svt_hip_fast_loop_group {
+    const uint8_t *d_src; uint32_t src_stride; const uint32_t *d_src_xy;   /* plane + x | y << 16 origins; NULL xy: dense W * H */
+    const uint8_t *d_top_neigh, *d_left_neigh; int32_t neigh_pitch;      /* as svt_hip_build_intra_predictors_batch */
+    const svt_hip_intra_blk *d_blocks;   /* per block: filt_type, disable_edge_filter, n_*_px; mode / angle_delta ignored */
+    uint32_t nblocks;
+    int32_t tx_size;                     /* 0 .. 18 */
+    int32_t ncand; uint8_t modes[64]; int8_t angle_deltas[64];          /* HOST-side list, 1 .. 64 entries */
+    uint64_t *d_dist;                    /* [nblocks][ncand] */
+    uint8_t *d_pred;                     /* optional (NULL: not written), [nblocks][ncand][H][W] dense */
+} svt_hip_fast_loop_group;
+int svt_hip_intra_fast_loop_frame(const svt_hip_fast_loop_group *groups, int ngroups, int metric, int flavour, void *stream);
 
 /* HOST helper, no device work: the first half of av1_predict_intra_block / av1_predict_intra_block_16bit
  * (EbIntraPrediction.c:4078-4333, 4336-4566) - up / left availability from the block's mode-info position,
