@@ -40,6 +40,18 @@ QParams make_qparams(const int16_t* zbin, const int16_t* round, const int16_t* q
     }
     return qp;
 }
+// a negative quant_shift, dequant or (rounded) round entry: outside the 24-bit arithmetic of the fused kernels (dev_common.h
+// quant_one<1 / 2>).  Each caller decides what that means: an error, or another kernel.
+bool qparams_negative(const QParams& qp) {
+    for (int i = 0; i < 2; i++)
+        if (qp.quant_shift[i] < 0 || qp.dequant[i] < 0 || qp.round[i] < 0) return true;
+    return false;
+}
+// every pointer 16-B aligned (NULL counts as aligned: an output the caller did not ask for)
+template <typename... P>
+bool aligned16(const P*... p) { return ((... | (uintptr_t)p) & 15) == 0; }
+// workgroups of a 32x32 launch that gives each wave two blocks (kernel_fused32.h)
+uint32_t f32_grid(size_t nblocks, int waves = F32_WAVES) { return (uint32_t)((nblocks + 2 * waves - 1) / (2 * waves)); }
 
 
 // ---------------------------------------------------------------------------
@@ -167,14 +179,12 @@ extern "C" int svt_hip_fwd_txfm2d_batch(const int16_t* d_in, uint32_t in_stride,
     if (!d_in || !d_out) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
     if (!txfm_allowed(tx_size, tx_type)) return set_err(SVT_HIP_ERR_INVALID, "tx_size %d / tx_type %d not defined by the reference", tx_size, tx_type);
     if (bd != 8 && bd != 10) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
-    if (nblocks == 0) return SVT_HIP_OK;
     if (nblocks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "nblocks too large");
     hipStream_t s = (hipStream_t)stream;
     if (tx_size == SVT_TX_32X32 && in_stride == 32 && in_block_pitch == 1024 && ((uintptr_t)d_in & 15) == 0 &&
         ((uintptr_t)d_out & 15) == 0 && (tx_type == SVT_DCT_DCT || tx_type == SVT_IDTX)) {
-        const uint32_t npairs = (uint32_t)((nblocks + 1) / 2);
         QParams qp = {};
-        hipLaunchKernelGGL((fwd32_kernel<0, false, false>), dim3((npairs + F32_WAVES - 1) / F32_WAVES), dim3(F32_WAVES * 64), 0,
+        hipLaunchKernelGGL((fwd32_kernel<0, false, false>), dim3(f32_grid(nblocks)), dim3(F32_WAVES * 64), 0,
                            s, (const void*)d_in, (const uint8_t*)nullptr, d_out, (int32_t*)nullptr, (int32_t*)nullptr,
                            (uint16_t*)nullptr, (uint32_t*)nullptr, (const int16_t*)nullptr, qp, tx_type == SVT_IDTX ? 1 : 0,
                            (uint32_t)nblocks);
@@ -197,7 +207,6 @@ extern "C" int svt_hip_pack64_batch(int32_t* d_coeff, uint64_t* d_energy, size_t
     if (nblocks == 0) return SVT_HIP_OK;
     if (tx_size < 0 || tx_size >= SVT_TX_SIZES_ALL || !d_coeff) return set_err(SVT_HIP_ERR_INVALID, "bad argument");
     const int w = kTxW[tx_size], h = kTxH[tx_size];
-    if (nblocks == 0) return SVT_HIP_OK;
     if (w != 64 && h != 64) {
         if (d_energy) HIP_TRY(hipMemsetAsync(d_energy, 0, nblocks * sizeof(uint64_t), (hipStream_t)stream));
         return SVT_HIP_OK;
@@ -217,7 +226,6 @@ extern "C" int svt_hip_inv_txfm2d_add_batch(const int32_t* d_coeff, void* d_dst,
     if (!txfm_allowed(tx_size, tx_type)) return set_err(SVT_HIP_ERR_INVALID, "tx_size %d / tx_type %d not defined by the reference", tx_size, tx_type);
     if (bd != 8 && bd != 10 && bd != 12) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
     if (!dst_is_16bit && bd != 8) return set_err(SVT_HIP_ERR_INVALID, "8-bit destination needs bd = 8");
-    if (nblocks == 0) return SVT_HIP_OK;
     hipStream_t s = (hipStream_t)stream;
     if (bd > 10) {
         // bd 12 (not an encoder configuration, only the C inverse kernels define it): the general kernel with 64-bit
@@ -229,14 +237,14 @@ extern "C" int svt_hip_inv_txfm2d_add_batch(const int32_t* d_coeff, void* d_dst,
     if (tx_size == SVT_TX_32X32 && ((uintptr_t)d_coeff & 15) == 0 && (tx_type == SVT_DCT_DCT || tx_type == SVT_IDTX)) {
         if (!dst_is_16bit && (g_tune_inv32_waves != 4 || g_tune_inv32_var != 0)) {     // tuning probes (tools/tune_inv32.py)
 #define INVV(WV, VR) if (g_tune_inv32_waves == WV && g_tune_inv32_var == VR) { \
-            hipLaunchKernelGGL((inv32_kernel<uint8_t, 8, WV, VR>), dim3((uint32_t)((nblocks + 2 * WV - 1) / (2 * WV))), dim3(WV * 64), 0, s, d_coeff, \
+            hipLaunchKernelGGL((inv32_kernel<uint8_t, 8, WV, VR>), dim3(f32_grid(nblocks, WV)), dim3(WV * 64), 0, s, d_coeff, \
                                (uint8_t*)d_dst, dst_stride, dst_block_pitch, d_dst_offsets, tx_type == SVT_IDTX ? 1 : 0, (uint32_t)nblocks); \
             return launch_status("inv32 probe"); }
             INVV(4, 1) INVV(4, 2) INVV(4, 4) INVV(4, 5) INVV(2, 0) INVV(4, 8)
 #undef INVV
             return set_err(SVT_HIP_ERR_INVALID, "inv32 probe variant not built");
         }
-        const uint32_t grid = (uint32_t)((nblocks + 2 * F32_WAVES - 1) / (2 * F32_WAVES));
+        const uint32_t grid = f32_grid(nblocks);
 #define INV32(T, B) hipLaunchKernelGGL((inv32_kernel<T, B>), dim3(grid), dim3(F32_WAVES * 64), 0, s, d_coeff, (T*)d_dst, dst_stride, \
                                       dst_block_pitch, d_dst_offsets, tx_type == SVT_IDTX ? 1 : 0, (uint32_t)nblocks)
         if (dst_is_16bit) { if (bd == 8) INV32(uint16_t, 8); else INV32(uint16_t, 10); }
@@ -269,7 +277,6 @@ extern "C" int svt_hip_quantize_b_batch(const int32_t* d_coeff, size_t n_coeffs,
         return set_err(SVT_HIP_ERR_INVALID, "NULL argument");
     if (n_coeffs < 16 || n_coeffs > 4096 || (n_coeffs & 15)) return set_err(SVT_HIP_ERR_INVALID, "n_coeffs %zu", n_coeffs);
     if (log_scale < 0 || log_scale > 2) return set_err(SVT_HIP_ERR_INVALID, "log_scale %d", log_scale);
-    if (nblocks == 0) return SVT_HIP_OK;
     const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, log_scale);
     hipStream_t s = (hipStream_t)stream;
     const int n = (int)n_coeffs;
@@ -302,35 +309,29 @@ extern "C" int svt_hip_fwd_quant_sad_batch(const uint8_t* d_src, const uint8_t* 
         return svt_hip_fwd_quant_planes_batch(d_src, 0, d_pred, 0, nullptr, nblocks, 0, 8, tx_size, tx_type, zbin, round, quant,
                                               quant_shift, dequant, d_iscan, d_coeff, d_qcoeff, d_dqcoeff, d_eob, d_sad,
                                               nullptr, stream);
-    if (nblocks == 0) return SVT_HIP_OK;
     if (nblocks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "nblocks too large");
     const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, 1);
-    // FAST24 precondition of the fused kernel (dev_common.h quant_one<true>)
-    for (int i = 0; i < 2; i++)
-        if (qp.quant_shift[i] < 0 || qp.dequant[i] < 0 || qp.round[i] < 0)
-            return set_err(SVT_HIP_ERR_INVALID, "negative quantizer table entry");
-    const uint32_t npairs = (uint32_t)((nblocks + 1) / 2);
-    uint32_t grid = (npairs + F32_WAVES - 1) / F32_WAVES;
+    if (qparams_negative(qp)) return set_err(SVT_HIP_ERR_INVALID, "negative quantizer table entry");
+    uint32_t grid = f32_grid(nblocks);
     const uint32_t max_grid = (uint32_t)g_num_cu * (uint32_t)g_tune_f32_wg_per_cu;
     if (g_tune_f32_wg_per_cu > 0 && grid > max_grid) grid = max_grid;
     hipStream_t s = (hipStream_t)stream;
     // QMODE 2 needs power-of-two quant_shift (every av1_build_quantizer table); else the 24-bit general form
-#define F32_LAUNCH_Q(SAD, MW, NT, QM)                                                                              \
-    hipLaunchKernelGGL((fwd32_kernel<1, true, SAD, MW, NT, QM>), dim3(grid), dim3(F32_WAVES * 64), 0, s,           \
+#define F32_LAUNCH_Q(SAD, NT, QM)                                                                                  \
+    hipLaunchKernelGGL((fwd32_kernel<1, true, SAD, NT, QM>), dim3(grid), dim3(F32_WAVES * 64), 0, s,               \
                        (const void*)d_src, d_pred, d_coeff, d_qcoeff, d_dqcoeff, d_eob, d_sad, d_iscan, qp,           \
                        tx_type == SVT_IDTX ? 1 : 0, (uint32_t)nblocks)
     const bool fastq = qp.fast_ok && !g_tune_f32_qmode1;
     if (g_tune_f32_nt && fastq) {
-        if (d_sad) F32_LAUNCH_Q(true, 1, true, 2); else F32_LAUNCH_Q(false, 1, true, 2);
+        if (d_sad) F32_LAUNCH_Q(true, true, 2); else F32_LAUNCH_Q(false, true, 2);
     } else if (g_tune_f32_nt) {
-        if (d_sad) F32_LAUNCH_Q(true, 1, true, 1); else F32_LAUNCH_Q(false, 1, true, 1);
+        if (d_sad) F32_LAUNCH_Q(true, true, 1); else F32_LAUNCH_Q(false, true, 1);
     } else if (!fastq) {
-        if (d_sad) F32_LAUNCH_Q(true, 1, false, 1); else F32_LAUNCH_Q(false, 1, false, 1);
+        if (d_sad) F32_LAUNCH_Q(true, false, 1); else F32_LAUNCH_Q(false, false, 1);
     } else {
-        if (d_sad) F32_LAUNCH_Q(true, 1, false, 2); else F32_LAUNCH_Q(false, 1, false, 2);
+        if (d_sad) F32_LAUNCH_Q(true, false, 2); else F32_LAUNCH_Q(false, false, 2);
     }
 #undef F32_LAUNCH_Q
-#undef F32_LAUNCH
     return launch_status("fwd_quant_sad_32x32");
 }
 
@@ -353,10 +354,8 @@ static int encode_recon_impl(const void* d_src_v, uint32_t src_stride, const voi
     hipStream_t s = (hipStream_t)stream;
     if (tx_size == SVT_TX_32X32 && (tx_type == SVT_DCT_DCT || tx_type == SVT_IDTX)) {
         const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, 1);
-        bool ok = qp.fast_ok;
-        for (int i = 0; i < 2; i++) ok = ok && qp.quant_shift[i] >= 0 && qp.dequant[i] >= 0 && qp.round[i] >= 0;
-        if (ok && ((d_coeff != nullptr) == (d_dqcoeff != nullptr))) {
-            const uint32_t grid = (uint32_t)((nblocks + 2 * F32_WAVES - 1) / (2 * F32_WAVES));
+        if (qp.fast_ok && !qparams_negative(qp) && ((d_coeff != nullptr) == (d_dqcoeff != nullptr))) {
+            const uint32_t grid = f32_grid(nblocks);
 #define ENC32(T, B, KEEP, SAD) hipLaunchKernelGGL((enc32_kernel<T, B, KEEP, SAD>), dim3(grid), dim3(F32_WAVES * 64), 0, s, (const T*)d_src_v, \
                                          (const T*)d_pred_v, (T*)d_recon_v, d_coeff, d_qcoeff, d_dqcoeff, d_eob, d_sad, d_iscan, qp,          \
                                          tx_type == SVT_IDTX ? 1 : 0, (uint32_t)nblocks, d_xy, src_stride, pred_stride, recon_stride)
@@ -370,8 +369,7 @@ static int encode_recon_impl(const void* d_src_v, uint32_t src_stride, const voi
     if (tx_size == SVT_TX_4X4 && ((d_coeff != nullptr) == (d_dqcoeff != nullptr)) && !g_tune_no_enc_staged) {
         // one lane per block, everything in registers (enc4_kernel); any quantiser table
         const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, 0);
-        bool fast = qp.fast_ok;
-        for (int i = 0; i < 2; i++) fast = fast && qp.quant_shift[i] >= 0 && qp.dequant[i] >= 0 && qp.round[i] >= 0;
+        const bool fast = qp.fast_ok && !qparams_negative(qp);
         const dim3 grid((uint32_t)((nblocks + 255) / 256));
 #define ENC4(T, B, KEEP) hipLaunchKernelGGL((enc4_kernel<T, B, KEEP>), grid, dim3(256), 0, s, (const T*)d_src_v, (const T*)d_pred_v, (T*)d_recon_v, \
                                            d_coeff, d_qcoeff, d_dqcoeff, d_eob, d_sad, d_iscan, qp, fast ? 1 : 0, tx_type, (uint32_t)nblocks, d_xy,         \
@@ -384,10 +382,8 @@ static int encode_recon_impl(const void* d_src_v, uint32_t src_stride, const voi
     {   // every other size: the staged fused kernel (dense 8-bit batches, power-of-two quant_shift tables)
         const int pels = kTxW[tx_size] * kTxH[tx_size];
         const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, pels > 1024 ? 2 : (pels > 256 ? 1 : 0));
-        bool ok = qp.fast_ok && pels > 16 && !g_tune_no_enc_staged && ((d_coeff != nullptr) == (d_dqcoeff != nullptr));
-        for (int i = 0; i < 2; i++) ok = ok && qp.quant_shift[i] >= 0 && qp.dequant[i] >= 0 && qp.round[i] >= 0;
-        ok = ok && (((uintptr_t)d_qcoeff | (uintptr_t)d_coeff | (uintptr_t)d_dqcoeff) & 15) == 0;
-        ok = ok && (d_xy || (((uintptr_t)d_src | (uintptr_t)d_pred | (uintptr_t)d_recon) & 15) == 0);
+        const bool ok = qp.fast_ok && pels > 16 && !g_tune_no_enc_staged && ((d_coeff != nullptr) == (d_dqcoeff != nullptr)) &&
+                        !qparams_negative(qp) && aligned16(d_qcoeff, d_coeff, d_dqcoeff) && (d_xy || aligned16(d_src, d_pred, d_recon));
         if (ok && tx_size == SVT_TX_64X64 && !g_tune_no_enc64) {
             // two blocks per wave, pruned 64-point networks (kernel_enc64.h)
             const dim3 grid((uint32_t)((nblocks + 2 * E64_WAVES - 1) / (2 * E64_WAVES)));
@@ -470,16 +466,14 @@ extern "C" int svt_hip_fwd_quant_planes_batch(const void* d_src, uint32_t src_st
     if (nblocks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "nblocks too large");
     const int pels = kTxW[tx_size] * kTxH[tx_size];
     const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, pels > 1024 ? 2 : (pels > 256 ? 1 : 0));
-    for (int i = 0; i < 2; i++)
-        if (qp.quant_shift[i] < 0 || qp.dequant[i] < 0 || qp.round[i] < 0) return set_err(SVT_HIP_ERR_INVALID, "negative quantizer table entry");
+    if (qparams_negative(qp)) return set_err(SVT_HIP_ERR_INVALID, "negative quantizer table entry");
     hipStream_t s = (hipStream_t)stream;
     if (tx_size == SVT_TX_32X32 && (tx_type == SVT_DCT_DCT || tx_type == SVT_IDTX) && qp.fast_ok && !d_energy && !g_tune_no_f32p &&
-        (d_xy || is_16bit) && ((uintptr_t)d_coeff & 15) == 0 && ((uintptr_t)d_qcoeff & 15) == 0 && ((uintptr_t)d_dqcoeff & 15) == 0) {
+        (d_xy || is_16bit) && aligned16(d_coeff, d_qcoeff, d_dqcoeff)) {
         // the tuned 32x32 kernel on planes / 10-bit samples (dense 16-bit batches are "planes" of stride 32 with a NULL table)
-        const uint32_t npairs = (uint32_t)((nblocks + 1) / 2);
-        const uint32_t grid = (npairs + F32_WAVES - 1) / F32_WAVES;
+        const uint32_t grid = f32_grid(nblocks);
         const int idtx = tx_type == SVT_IDTX ? 1 : 0;
-#define F32P(INM, SAD, PL) hipLaunchKernelGGL((fwd32_kernel<INM, true, SAD, 1, false, 2, PL>), dim3(grid), dim3(F32_WAVES * 64), 0, s, d_src, d_pred, \
+#define F32P(INM, SAD, PL) hipLaunchKernelGGL((fwd32_kernel<INM, true, SAD, false, 2, PL>), dim3(grid), dim3(F32_WAVES * 64), 0, s, d_src, d_pred, \
                                           d_coeff, d_qcoeff, d_dqcoeff, d_eob, d_sad, d_iscan, qp, idtx, (uint32_t)nblocks, src_stride, pred_stride, d_xy)
         if (is_16bit) { if (d_xy) F32P(2, false, true); else F32P(2, false, false); }
         else { if (d_sad) F32P(1, true, true); else F32P(1, false, true); }
@@ -487,8 +481,7 @@ extern "C" int svt_hip_fwd_quant_planes_batch(const void* d_src, uint32_t src_st
         return launch_status("fwd_quant_32x32_planes");
     }
     if (tx_size == SVT_TX_64X64 && !g_tune_no_staged && !g_tune_no_enc64 && qp.fast_ok && !d_energy &&
-        (d_xy || (((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_pred & 15) == 0)) &&
-        ((uintptr_t)d_coeff & 15) == 0 && ((uintptr_t)d_qcoeff & 15) == 0 && ((uintptr_t)d_dqcoeff & 15) == 0) {
+        (d_xy || aligned16(d_src, d_pred)) && aligned16(d_coeff, d_qcoeff, d_dqcoeff)) {
         // two blocks per wave, forward networks pruned to the 32 kept outputs (the forward half of enc64_kernel); callers that
         // want three_quad_energy keep the one-block kernel, which forms the discarded coefficients
         const dim3 grid((uint32_t)((nblocks + 2 * E64_WAVES - 1) / (2 * E64_WAVES)));
@@ -502,8 +495,7 @@ extern "C" int svt_hip_fwd_quant_planes_batch(const void* d_src, uint32_t src_st
         return launch_status("fwd_quant_64x64");
     }
     // staged (coalesced) kernels: dense batches need 16-B aligned inputs, plane-addressed blocks do not
-    if (!g_tune_no_staged && qp.fast_ok && pels > 16 && (d_xy || (((uintptr_t)d_src & 15) == 0 && ((uintptr_t)d_pred & 15) == 0)) &&
-        ((uintptr_t)d_coeff & 15) == 0 && ((uintptr_t)d_qcoeff & 15) == 0 && ((uintptr_t)d_dqcoeff & 15) == 0) {
+    if (!g_tune_no_staged && qp.fast_ok && pels > 16 && (d_xy || aligned16(d_src, d_pred)) && aligned16(d_coeff, d_qcoeff, d_dqcoeff)) {
 #define CALLS(W, H) launch_fq_staged<W, H>(d_src, d_pred, is_16bit, d_xy, src_stride, pred_stride, nblocks, tx_type, qp, d_iscan, d_coeff, d_qcoeff, d_dqcoeff, d_eob, d_sad, d_energy, s)
         TX_SWITCH(tx_size, CALLS)
 #undef CALLS
@@ -595,8 +587,7 @@ extern "C" int svt_hip_encode_recon_frame(const svt_hip_frame_group* groups, int
                 const int pels = kTxW[G.tx_size] * kTxH[G.tx_size], c = mode == 1 ? 3 : tx_class_of(G.tx_size);
                 FrameGroupDev& D = fd[c].g[fd[c].ngroups];
                 D.qp = make_qparams(zbin, round, quant, quant_shift, dequant, pels > 1024 ? 2 : (pels > 256 ? 1 : 0));
-                for (int i = 0; i < 2; i++) ok = ok && D.qp.quant_shift[i] >= 0 && D.qp.dequant[i] >= 0 && D.qp.round[i] >= 0;
-                ok = ok && D.qp.fast_ok;
+                ok = ok && D.qp.fast_ok && !qparams_negative(D.qp);
                 D.src = G.d_src; D.pred = G.d_pred; D.recon = G.d_recon; D.qcoeff = G.d_qcoeff; D.eob = G.d_eob; D.xy = G.d_xy; D.iscan = G.d_iscan;
                 D.src_stride = G.src_stride; D.pred_stride = G.pred_stride; D.recon_stride = G.recon_stride; D.nblocks = G.nblocks; D.tx_size = G.tx_size; D.tx_type = G.tx_type;
                 const uint32_t per_wg = frame_blocks_per_wg(G.tx_size);
@@ -682,8 +673,7 @@ extern "C" int svt_hip_fwd_quant_batch(const int16_t* d_residual, size_t nblocks
     if (tx_size == SVT_TX_32X32 && bd == 8 && qp.fast_ok && ((uintptr_t)d_residual & 15) == 0 &&
         (tx_type == SVT_DCT_DCT || tx_type == SVT_IDTX)) {
         // 24-bit quantiser arithmetic needs 8-bit-range residuals (|coeff| < 2^17)
-        const uint32_t npairs = (uint32_t)((nblocks + 1) / 2);
-        hipLaunchKernelGGL((fwd32_kernel<0, true, false>), dim3((npairs + F32_WAVES - 1) / F32_WAVES), dim3(F32_WAVES * 64), 0, s,
+        hipLaunchKernelGGL((fwd32_kernel<0, true, false>), dim3(f32_grid(nblocks)), dim3(F32_WAVES * 64), 0, s,
                            (const void*)d_residual, (const uint8_t*)nullptr, d_coeff, d_qcoeff, d_dqcoeff, d_eob,
                            (uint32_t*)nullptr, d_iscan, qp, tx_type == SVT_IDTX ? 1 : 0, (uint32_t)nblocks);
         return launch_status("fwd32_quant");

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of two builds of the library on the same box, interleaved: tools/ab/lib_a.so against tools/ab/lib_b.so (tools/make_ab_lib.sh).
 usage: ab_kernels.py <workload> [<workload> ...]      workloads: enc8 enc16 enc32 enc64 inv8 inv16 inv32 fq8 fq16 fwd8 fwd16 (dense 8-bit batches),
-       fqp8 fqp16 (fwd_quant_planes on a 8192x4096 plane), fl8 fl16 fl32 fl64 (full_loop, dense, AVX2 flavour, DCT_DCT) and fl8x16 fl16x16
+       fqp8 fqp16 (fwd_quant_planes on a 8192x4096 plane; fqp32h: a 10-bit plane), encp32 encp32h (encode_recon_planes, 8- / 10-bit plane), fl8 fl16 fl32 fl64 (full_loop, dense, AVX2 flavour, DCT_DCT) and fl8x16 fl16x16
        (every allowed type), c4 (one 1080p frame, five sizes, svt_hip_encode_recon_frame), ois8 ois16 (open-loop intra search of a 1080p
        picture), bip, me85 me209
 Prints per workload the minimum and median of 6 interleaved rounds per library and whether the two libraries' outputs are equal."""
@@ -60,15 +60,27 @@ def workload(name, d):
         pred = (src.to(torch.int16) + torch.randint(-20, 21, (n, S, S), dtype=torch.int16, device=dev, generator=g)).clamp(0, 255).to(torch.uint8)
         iscan = torch.from_numpy(np.stack([pkg.tables.scan_tables(s_, t)[1] for t in types]).astype(np.int16)).to(dev)
         return (lambda: d.full_loop(src, pred, s_, types, qrow, flavour=1, iscan=iscan)), n, 2 * S * S + 18 * len(types)
-    if name.startswith("fqp"):           # fwd_quant_planes: every block of a 8192x4096 plane
-        S = int(name[3:]); s_ = {4: 0, 8: 1, 16: 2, 32: 3, 64: 4}[S]
+    if name.startswith("fqp") or name.startswith("encp"):      # fwd_quant_planes / encode_recon_planes: every block of a 8192x4096 plane
+        hbd = name.endswith("h")                                # ...h: 10-bit samples in 16-bit planes
+        S = int(name.rstrip("h")[3 if name.startswith("fqp") else 4:]); s_ = {4: 0, 8: 1, 16: 2, 32: 3, 64: 4}[S]
         PW, PH = 8192, 4096
-        src = torch.randint(0, 256, (PH, PW), dtype=torch.uint8, device=dev, generator=g)
-        pred = (src.to(torch.int16) + torch.randint(-20, 21, (PH, PW), dtype=torch.int16, device=dev, generator=g)).clamp(0, 255).to(torch.uint8)
+        top, dt, es = (1024, torch.int16, 2) if hbd else (256, torch.uint8, 1)
+        if hbd:
+            qrow = {k: v[100].copy() for k, v in pkg.tables.quant_tables(10).items()}
+        src = torch.randint(0, top, (PH, PW), dtype=dt, device=dev, generator=g)
+        pred = (src.to(torch.int16) + torch.randint(-20, 21, (PH, PW), dtype=torch.int16, device=dev, generator=g)).clamp(0, top - 1).to(dt)
         xy = torch.from_numpy(np.array([(y << 16) | x for y in range(0, PH, S) for x in range(0, PW, S)], np.uint32).view(np.int32)).to(dev)
         iscan = torch.from_numpy(pkg.tables.scan_tables(s_, 0)[1]).to(dev)
         nc = min(S, 32) ** 2
-        return (lambda: d.fwd_quant_planes(src, PW, pred, PW, xy, s_, 0, qrow, iscan, want_sad=True)), xy.shape[0], 2 * S * S + 12 * nc + 6
+        bd = 10 if hbd else 8
+        if name.startswith("encp"):
+            recon = torch.empty_like(pred)
+
+            def encp():
+                o = d.encode_recon_planes(src, PW, pred, PW, recon, PW, xy, s_, 0, qrow, iscan, bd=bd)
+                return [o["qcoeff"], o["eob"], recon]
+            return encp, xy.shape[0], 3 * S * S * es + 4 * nc + 2
+        return (lambda: d.fwd_quant_planes(src, PW, pred, PW, xy, s_, 0, qrow, iscan, bd=bd, want_sad=not hbd)), xy.shape[0], 2 * S * S * es + 12 * nc + 6
     if name[:3] in ("enc", "inv", "fwd") or name[:2] == "fq":
         S = int(name[3:] if name[:2] != "fq" else name[2:]); s_ = {4: 0, 8: 1, 16: 2, 32: 3, 64: 4}[S]
         n = (1 << 20) * 1024 // (S * S) if S <= 32 else 1 << 18

@@ -25,7 +25,7 @@ for f in glob.glob(f"{out}/pmc_*.csv"):
             agg[r["Counter_Name"]].append(float(r["Counter_Value"]))
 mean = {k: sum(v) / len(v) for k, v in agg.items()}
 blocks = 1 << 20
-res = {"round": int(tag[1:3]) if tag[:1] == "r" and tag[1:3].isdigit() else None, "tag": tag, "kernel": "fwd32_kernel<true,true,true,1,false,2> (headline fused chain)", "blocks": blocks,
+res = {"round": int(tag[1:3]) if tag[:1] == "r" and tag[1:3].isdigit() else None, "tag": tag, "kernel": "fwd32_kernel<1,true,true,false,2> (headline fused chain)", "blocks": blocks,
        "command": "rocprofv3 --kernel-trace --pmc <C> -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-probes (one pass per counter group)"}
 if "FETCH_SIZE" in mean and "WRITE_SIZE" in mean:
     rd = 2 * mean["FETCH_SIZE"] * 1024; wr = mean["WRITE_SIZE"] * 1024
