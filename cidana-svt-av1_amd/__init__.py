@@ -156,6 +156,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_intra_fast_loop_frame.restype = c_int
     L.svt_hip_md_intra_candidates.argtypes = [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_void_p, c_void_p]
     L.svt_hip_md_intra_candidates.restype = c_int
+    L.svt_hip_cdef_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.svt_hip_cdef_search_frame.restype = c_int
+    L.svt_hip_cdef_apply_frame.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
+    L.svt_hip_cdef_apply_frame.restype = c_int
     return L
 
 
@@ -1074,6 +1078,63 @@ class SvtHipDsp:
                  modes=modes, deltas=deltas, dist=dist, pred=pred)
         self._check(self.intra_fast_loop_frame([g], metric, flavour), "svt_hip_intra_fast_loop_frame")
         return dist, pred
+
+    class CdefPic(ctypes.Structure):
+        """svt_hip_cdef_pic"""
+        _fields_ = [("d_rec", c_void_p * 3), ("rec_stride", c_uint32 * 3), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3),
+                    ("d_dst", c_void_p * 3), ("dst_stride", c_uint32 * 3), ("d_skip", c_void_p), ("skip_stride", c_uint32),
+                    ("width", c_uint32), ("height", c_uint32), ("bit_depth", c_int32), ("base_qindex", c_int32), ("npics", c_uint32),
+                    ("rec_pitch", ctypes.c_uint64 * 3), ("src_pitch", ctypes.c_uint64 * 3), ("dst_pitch", ctypes.c_uint64 * 3),
+                    ("skip_pitch", ctypes.c_uint64)]
+
+    def make_cdef_pic(self, rec, skip, width, height, bit_depth, base_qindex, src=None, dst=None):
+        """rec / src / dst: (Y, Cb, Cr) tensors, uint8 (bit depth 8) or uint16 / int16 (10), [rows, stride] for one picture or
+        [npics, rows, stride] for a stack; skip: uint8 [height / 8 (or more), stride] (or [npics, ..]).  -> CdefPic (keep the tensors
+        alive!)"""
+        p = self.CdefPic()
+        stack = rec[0].dim() == 3
+        p.npics = rec[0].shape[0] if stack else 1
+        for planes, ptr, stride, pitch in ((rec, p.d_rec, p.rec_stride, p.rec_pitch), (src, p.d_src, p.src_stride, p.src_pitch),
+                                           (dst, p.d_dst, p.dst_stride, p.dst_pitch)):
+            if planes is None:
+                continue
+            for i, t in enumerate(planes):
+                assert t.is_contiguous() and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
+                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.shape[-1], (t.shape[-2] * t.shape[-1] if stack else 0)
+        assert skip.is_contiguous() and skip.element_size() == 1
+        p.d_skip, p.skip_stride, p.skip_pitch = skip.data_ptr(), skip.shape[-1], (skip.shape[-2] * skip.shape[-1] if stack else 0)
+        p.width, p.height, p.bit_depth, p.base_qindex = width, height, bit_depth, base_qindex
+        return p
+
+    def cdef_search_frame(self, rec, src, skip, width, height, bit_depth, base_qindex, start_gi=0, end_gi=64, mse=None, count=None):
+        """svt_hip_cdef_search_frame (cdef_seg_search for every 64x64 filter block).  -> mse int64 [(npics,) 2, nfb, 64] (0 = luma,
+        1 = Cb + Cr), count int32 [(npics,) nfb]; the strength pick from the table (finish_cdef_search) stays with the caller."""
+        t = self.torch
+        p = self.make_cdef_pic(rec, skip, width, height, bit_depth, base_qindex, src=src)
+        nfb = ((width + 63) // 64) * ((height + 63) // 64)
+        lead = (p.npics,) if rec[0].dim() == 3 else ()
+        if mse is None:
+            mse = t.empty(lead + (2, nfb, 64), dtype=t.int64, device=rec[0].device)
+        if count is None:
+            count = t.empty(lead + (nfb,), dtype=t.int32, device=rec[0].device)
+        assert mse.is_contiguous() and mse.numel() == p.npics * 2 * nfb * 64 and count.is_contiguous() and count.numel() == p.npics * nfb
+        self._check(self.lib.svt_hip_cdef_search_frame(ctypes.addressof(p), start_gi, end_gi, self._p(mse), self._p(count), self._stream()),
+                    "svt_hip_cdef_search_frame")
+        return mse, count
+
+    def cdef_apply_frame(self, rec, skip, luma_strength, chroma_strength, width, height, bit_depth, base_qindex, dst=None):
+        """svt_hip_cdef_apply_frame (av1_cdef_frame).  luma_strength / chroma_strength: int8 [(npics,) nfb], 0 .. 63 or -1 = leave the
+        filter block alone.  -> dst (Y, Cb, Cr), shaped as rec; only the picture area is written."""
+        t = self.torch
+        if dst is None:
+            dst = tuple(t.zeros_like(x) for x in rec)
+        p = self.make_cdef_pic(rec, skip, width, height, bit_depth, base_qindex, dst=dst)
+        nfb = ((width + 63) // 64) * ((height + 63) // 64)
+        for s in (luma_strength, chroma_strength):
+            assert s.dtype == t.int8 and s.is_contiguous() and s.numel() == p.npics * nfb
+        self._check(self.lib.svt_hip_cdef_apply_frame(ctypes.addressof(p), self._p(luma_strength), self._p(chroma_strength), self._stream()),
+                    "svt_hip_cdef_apply_frame")
+        return dst
 
     @staticmethod
     def md_intra_candidates(bwidth, bheight, sq_size, bsize, intra_pred_mode=0, is_16bit=False):

@@ -761,6 +761,53 @@ typedef struct svt_hip_fast_loop_group {
 } svt_hip_fast_loop_group;
 int svt_hip_intra_fast_loop_frame(const svt_hip_fast_loop_group *groups, int ngroups, int metric, int flavour, void *stream);
 
+/* CDEF for whole 4:2:0 pictures: the strength search and the apply.  One descriptor serves both calls: a picture (or a stack of
+ * npics pictures of one geometry, *_pitch samples / skip_pitch bytes apart) of width x height luma samples, both multiples of 8 as the
+ * reference's padded pictures are; planes of uint8 (bit_depth 8) or uint16 (bit_depth 10; coeff_shift = bit_depth - 8) samples with
+ * strides in samples; a skip map with one byte per 8x8 luma block (non-zero: every mode-info unit of the block is skipped, what
+ * is_8x8_block_skip, EbCdef.c:380, returns), height / 8 rows of skip_stride bytes; base_qindex (both dampings are
+ * 3 + (base_qindex >> 6), EbCdefProcess.c:128-129; cdef_filter_fb adds coeff_shift and takes one off for chroma, EbCdef.c:286-287).
+ * Filter blocks are 64x64 luma samples, fb = fbr * nhfb + fbc, nhfb = (width + 63) / 64, nvfb = (height + 63) / 64, nfb = nhfb * nvfb.
+ *
+ * svt_hip_cdef_search_frame: cdef_seg_search (EbCdefProcess.c:89-258; 16-bit :260) for every filter block - the reference's mse_seg
+ * table.  Per filter block, plane and gi in [start_gi, end_gi) (the reference: 0 .. 8 at cdef_filter_mode 1, 0 .. 64 otherwise, or
+ * a window round the reference frame's strength, :217-220): the list of non-skipped 8x8 blocks (sb_compute_cdef_list, EbCdef.c:390;
+ * a filter block with an empty list is left out, sb_all_skip :360); the input tile from the unfiltered d_rec with CDEF_VERY_LARGE
+ * outside the picture (:203-216); direction and variance per 8x8 luma block (cdef_find_dir, EbCdef.c:129, reused by chroma);
+ * cdef_filter_fb (EbCdef.c:273) with pri = gi / 4, sec = gi % 4 (+ 1 if 3), luma primary strength through adjust_strength (:267),
+ * direction 0 when the primary strength is 0, cdef_filter_block (:204) to the letter; compute_cdef_dist (:1360) against d_src: luma
+ * dist_8x8_16bit (:1305, binary64, reproduced bit for bit) per 8x8 block, chroma mse_4x4_16bit (:1346), each plane's sum shifted
+ * right by 2 * coeff_shift.  d_mse[((pic * 2 + 0) * nfb + fb) * 64 + gi] = luma, [.. + 1 ..] = Cb + Cr; d_count[pic * nfb + fb] =
+ * the length of the list.  Entries of left-out filter blocks and of gi outside the window are written as 0, so every entry of both
+ * arrays is defined after the call.  Filtered samples are not stored.  The serving dispatch slots (aom_dsp_rtcd.h:78-88, 270-276):
+ * cdef_find_dir, cdef_filter_block, copy_rect8_8bit_to_16bit, dist_8x8_16bit, mse_4x4_16bit.
+ * NOT here: the choice of the picture's strength set from mse_seg (finish_cdef_search, EbCdef.c:1410, joint_strength_search_dual
+ * :1259) - a few thousand sequential table look-ups that stay with the caller on the host.
+ *
+ * svt_hip_cdef_apply_frame: av1_cdef_frame (EbCdef.c:471; 16-bit :801).  d_luma_strength / d_chroma_strength [pic * nfb + fb]: the
+ * filter block's strengths 0 .. 63 (cdef_strengths[] / cdef_uv_strengths[] of the block's mbmi.cdef_strength), -1 in either = leave
+ * the filter block alone.  A filter block left alone, with both strengths 0 or with an empty list is copied (:600-604); otherwise every
+ * listed 8x8 block of all three planes goes through cdef_filter_block (pri = s / 4, sec = s % 4 (+ 1 if 3), luma through
+ * adjust_strength, chroma with luma's direction) and every other sample is copied.  The reference filters in place and keeps the
+ * unfiltered neighbour rows / columns in line buffers (:620-760); here d_rec is read and d_dst written, two distinct buffers, which
+ * computes the same picture.  Every sample of the width x height (chroma: half) area of d_dst is written, nothing outside it.
+ *
+ * Every argument is validated before the launch (SVT_HIP_ERR_INVALID: a side that is not a multiple of 8, a window outside 0 .. 64 or
+ * empty, a bit depth other than 8 / 10, base_qindex outside 0 .. 255, NULL planes / map / outputs, a stride below the width, d_mse not
+ * 8-byte aligned, d_dst == d_rec); each call is one kernel launch that only enqueues and can be captured into a HIP graph. */
+typedef struct svt_hip_cdef_pic {
+    const void *d_rec[3];  uint32_t rec_stride[3];   /* filter input: the deblocked reconstruction (Y, Cb, Cr) */
+    const void *d_src[3];  uint32_t src_stride[3];   /* the source picture (search only) */
+    void *d_dst[3];        uint32_t dst_stride[3];   /* the filtered picture (apply only) */
+    const uint8_t *d_skip; uint32_t skip_stride;
+    uint32_t width, height;
+    int32_t bit_depth, base_qindex;
+    uint32_t npics;                                 /* >= 1 */
+    uint64_t rec_pitch[3], src_pitch[3], dst_pitch[3], skip_pitch;      /* between the pictures of a stack (ignored for npics 1) */
+} svt_hip_cdef_pic;
+int svt_hip_cdef_search_frame(const svt_hip_cdef_pic *pic, int start_gi, int end_gi, uint64_t *d_mse, int32_t *d_count, void *stream);
+int svt_hip_cdef_apply_frame(const svt_hip_cdef_pic *pic, const int8_t *d_luma_strength, const int8_t *d_chroma_strength, void *stream);
+
 /* HOST helper, no device work: the first half of av1_predict_intra_block / av1_predict_intra_block_16bit
  * (EbIntraPrediction.c:4078-4333, 4336-4566) - up / left availability from the block's mode-info position,
  * has_top_right (:1567) and has_bottom_left (:1755), and the four sample counts handed to build_intra_predictors.
