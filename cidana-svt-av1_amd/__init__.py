@@ -160,7 +160,47 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_cdef_search_frame.restype = c_int
     L.svt_hip_cdef_apply_frame.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
     L.svt_hip_cdef_apply_frame.restype = c_int
+    L.svt_hip_motion_estimate_frame_scratch_bytes.argtypes = [c_void_p, c_uint32]
+    L.svt_hip_motion_estimate_frame_scratch_bytes.restype = c_size_t
+    L.svt_hip_motion_estimate_frame.argtypes = [c_void_p] * 4 + [c_uint32] + [c_void_p] * 6 + [c_size_t, c_void_p]
+    L.svt_hip_motion_estimate_frame.restype = c_int
     return L
+
+
+class MeFrameParams(ctypes.Structure):
+    """svt_hip_me_frame_params: what MotionEstimateLcu reads of its picture, sequence and ME context (include/svt_hip_dsp.h)"""
+    _fields_ = [(n, c_int32) for n in ("picture_width", "picture_height", "slice_type", "temporal_layer_index", "hierarchical_levels",
+                                       "enable_hme_flag", "enable_hme_level0_flag", "enable_hme_level1_flag", "enable_hme_level2_flag",
+                                       "number_hme_search_region_in_width", "number_hme_search_region_in_height",
+                                       "hme_level0_total_search_area_width", "hme_level0_total_search_area_height")] + \
+               [("hme_search_area_in_width_array", (ctypes.c_uint16 * 2) * 3), ("hme_search_area_in_height_array", (ctypes.c_uint16 * 2) * 3)] + \
+               [(n, c_int32) for n in ("search_area_width", "search_area_height")] + [("ref_pic_poc", c_int32 * 2)] + \
+               [(n, c_int32) for n in ("is_used_as_reference_flag", "max_number_of_pus_per_sb", "nsq_search_level", "cu8x8_mode",
+                                       "fractional_search_method", "flavour")]
+
+    @classmethod
+    def from_lcu_prm(cls, prm):
+        """from the int32 parameter block of oracle/ref_me.c's ref_motion_estimate_lcu (its slots 2 / 3, the SB origin, and 27 .. 41,
+        the picture geometry, are not parameters of a picture call)"""
+        p = cls()
+        (p.picture_width, p.picture_height, p.slice_type, p.temporal_layer_index, p.hierarchical_levels) = (int(prm[i]) for i in (0, 1, 4, 6, 7))
+        (p.enable_hme_flag, p.enable_hme_level0_flag, p.enable_hme_level1_flag, p.enable_hme_level2_flag) = (int(prm[i]) for i in (8, 9, 10, 11))
+        p.is_used_as_reference_flag, p.search_area_width, p.search_area_height = int(prm[12]), int(prm[13]), int(prm[14])
+        p.number_hme_search_region_in_width, p.number_hme_search_region_in_height = int(prm[15]), int(prm[16])
+        p.hme_level0_total_search_area_width, p.hme_level0_total_search_area_height = int(prm[17]), int(prm[18])
+        p.ref_pic_poc[0], p.ref_pic_poc[1], p.flavour = int(prm[19]), int(prm[20]), int(prm[21])
+        p.cu8x8_mode, p.fractional_search_method, p.max_number_of_pus_per_sb, p.nsq_search_level = (int(prm[i]) for i in (23, 24, 25, 26))
+        for lv in range(3):
+            for i in range(2):
+                p.hme_search_area_in_width_array[lv][i] = int(prm[42 + 4 * lv + i])
+                p.hme_search_area_in_height_array[lv][i] = int(prm[44 + 4 * lv + i])
+        return p
+
+
+class MePyramid(ctypes.Structure):
+    """svt_hip_me_pyramid: the padded full / quarter / sixteenth luma buffers of one picture (or of a stack of pictures)"""
+    _fields_ = [("d_plane", c_void_p * 3), ("stride", c_uint32 * 3), ("origin_x", c_uint32 * 3), ("origin_y", c_uint32 * 3),
+                ("pitch", ctypes.c_uint64 * 3)]
 
 
 class Y4mInfo(ctypes.Structure):
@@ -780,14 +820,15 @@ class SvtHipDsp:
                                                       sixteenth.stride(0) if sixteenth is not None else 0, s_origin[0], s_origin[1],
                                                       self._stream()), "svt_hip_picture_decimate")
 
-    def hme_level_regions(self, src_pic, src_stride, ref_pic00, ref_stride, sb_origin, sb_size, centers, center_shift, params_list):
+    def hme_level_regions(self, src_pic, src_stride, ref_pic00, ref_stride, sb_origin, sb_size, centers, center_shift, params_list, out=None):
         """hme_level for 1 .. 4 search regions in one launch (svt_hip_hme_level_regions_batch).  centers: int16 [regions, n, 2] or
-        None.  -> (best_sad int64 [regions, n], mv int16 [regions, n, 2])"""
+        None; params_list: HmeParams, as a list or a ctypes array.  -> (best_sad int64 [regions, n], mv int16 [regions, n, 2]),
+        written into `out` (such a pair) when given"""
         t = self.torch
         n, nr = sb_origin.shape[0], len(params_list)
-        arr = (self.HmeParams * nr)(*params_list)
-        best = t.empty((nr, n), dtype=t.int64, device=sb_origin.device)
-        mv = t.empty((nr, n, 2), dtype=t.int16, device=sb_origin.device)
+        arr = params_list if isinstance(params_list, ctypes.Array) else (self.HmeParams * nr)(*params_list)
+        best, mv = out if out is not None else (t.empty((nr, n), dtype=t.int64, device=sb_origin.device),
+                                                t.empty((nr, n, 2), dtype=t.int16, device=sb_origin.device))
         self._check(self.lib.svt_hip_hme_level_regions_batch(self._p(src_pic), src_stride, self._p(ref_pic00), ref_stride, self._p(sb_origin),
                                                              self._p(sb_size), self._p(centers) if centers is not None else None, center_shift,
                                                              ctypes.addressof(arr), nr, self._p(best), self._p(mv), n, self._stream()),
@@ -890,14 +931,15 @@ class SvtHipDsp:
         _fields_ = [("x_mv_l0", ctypes.c_int16), ("y_mv_l0", ctypes.c_int16), ("x_mv_l1", ctypes.c_int16), ("y_mv_l1", ctypes.c_int16),
                     ("distortion", ctypes.c_uint32 * 3), ("direction", ctypes.c_uint8 * 3), ("total_me_candidate_index", ctypes.c_uint8)]
 
-    def me_setup(self, src_pic00, src_stride, ref_pic00, ref_stride, sb_origin, sb_size, hme_sad, hme_mv, params):
+    def me_setup(self, src_pic00, src_stride, ref_pic00, ref_stride, sb_origin, sb_size, hme_sad, hme_mv, params, out=None):
         """svt_hip_me_setup_batch: search centre (best HME region, CheckZeroZeroCenter) and clipped search area per task.
         src_pic00 / ref_pic00: uint8 views whose data_ptr() is sample (0, 0) of the padded planes; sb_origin / sb_size int16 [n, 2];
-        hme_sad int64 [regions, n] and hme_mv int16 [regions, n, 2] (or None).  -> (center int16 [n, 2], area int16 [n, 4])"""
+        hme_sad int64 [regions, n] and hme_mv int16 [regions, n, 2] (or None).  -> (center int16 [n, 2], area int16 [n, 4]), written
+        into `out` (such a pair) when given"""
         t = self.torch
         n = sb_origin.shape[0]
-        center = t.empty((n, 2), dtype=t.int16, device=sb_origin.device)      # (every entry is written by the kernel)
-        area = t.empty((n, 4), dtype=t.int16, device=sb_origin.device)
+        center, area = out if out is not None else (t.empty((n, 2), dtype=t.int16, device=sb_origin.device),      # (every entry is written by the kernel)
+                                                    t.empty((n, 4), dtype=t.int16, device=sb_origin.device))
         self._check(self.lib.svt_hip_me_setup_batch(self._p(src_pic00), src_stride, self._p(ref_pic00), ref_stride, self._p(sb_origin),
                                                     self._p(sb_size), self._p(hme_sad) if hme_sad is not None else None,
                                                     self._p(hme_mv) if hme_mv is not None else None, ctypes.byref(params), self._p(center),
@@ -921,14 +963,18 @@ class SvtHipDsp:
         return best_sad, best_mv
 
     def me_bipred(self, src_pic00, src_stride, ref0_pic00, ref0_stride, ref1_pic00, ref1_stride, sb_origin, best_sad0, best_mv0, best_sad1=None,
-                  best_mv1=None, npus=209, bipred_all_pus=True, sub_sad=True):
+                  best_mv1=None, npus=209, bipred_all_pus=True, sub_sad=True, out=None):
         """svt_hip_me_bipred_batch -> (bipred_sad int32 [n, pu_pitch] in storage order, results uint8 [n, npus, 24] = svt_hip_me_result
-        rows in raster PU order)"""
+        rows in raster PU order); `out`: such a pair to write into (its bipred_sad is zeroed first, as a fresh one is)"""
         t = self.torch
         n = sb_origin.shape[0]
         pitch = best_sad0.shape[1]
-        bip = t.zeros((n, pitch), dtype=t.int32, device=sb_origin.device)
-        res = t.empty((n, npus, ctypes.sizeof(self.MeResult)), dtype=t.uint8, device=sb_origin.device)      # (every row is written)
+        if out is not None:
+            bip, res = out
+            bip.zero_()
+        else:
+            bip = t.zeros((n, pitch), dtype=t.int32, device=sb_origin.device)
+            res = t.empty((n, npus, ctypes.sizeof(self.MeResult)), dtype=t.uint8, device=sb_origin.device)      # (every row is written)
         two = best_sad1 is not None
         self._check(self.lib.svt_hip_me_bipred_batch(self._p(src_pic00), src_stride, self._p(ref0_pic00) if two else None, ref0_stride,
                                                      self._p(ref1_pic00) if two else None, ref1_stride, self._p(sb_origin), self._p(best_sad0),
@@ -951,6 +997,46 @@ class SvtHipDsp:
             out[..., 4 + 2 * k] = d[..., k]
             out[..., 5 + 2 * k] = a[..., 20 + k]
         out[..., 10] = a[..., 23]
+        return out
+
+    # -- MotionEstimateLcu for a whole picture: one call, three launches ---------------------------------------------------
+    MeFrameParams = MeFrameParams
+    MePyramid = MePyramid
+
+    def me_pyramid(self, planes, origins):
+        """planes: the padded full / quarter / sixteenth luma buffers, 2-D uint8 tensors [rows, stride] (one picture) or 3-D
+        [pictures, rows, stride] (a stack); a level may be None when its HME level is off.  origins: (x, y) of sample (0, 0) per level"""
+        p = MePyramid()
+        for k, (t, o) in enumerate(zip(planes, origins)):
+            if t is None:
+                continue
+            p.d_plane[k] = t.data_ptr()
+            p.stride[k], p.origin_x[k], p.origin_y[k] = t.stride(-2), int(o[0]), int(o[1])
+            p.pitch[k] = t.stride(0) if t.dim() == 3 else 0
+        p._keep = planes
+        return p
+
+    def motion_estimate_frame(self, src, ref0, ref1, params, n_pictures=1, out=None, scratch=None):
+        """svt_hip_motion_estimate_frame.  src / ref0 / ref1: MePyramid (ref1 None for a P picture); params: MeFrameParams.
+        -> dict of device tensors, s = n_pictures * SBs: best_sad, best_mv int32 [s, nl, 209] (uint32 values), area_origin int16 [s, nl, 2],
+        bipred_sad int32 [s, 209], results uint8 [s, 209, 24] (svt_hip_me_result rows; me_results_as_rows).  `out` / `scratch`: a
+        dict and a tensor of an earlier call to write into (the call allocates nothing itself)."""
+        t = self.torch
+        nsb = ((params.picture_width + 63) // 64) * ((params.picture_height + 63) // 64)
+        nl = 1 if params.slice_type == 1 else 2
+        s = max(1, n_pictures) * max(1, nsb)
+        if out is None:
+            out = {"best_sad": t.empty((s, nl, 209), dtype=t.int32, device=self.device), "best_mv": t.empty((s, nl, 209), dtype=t.int32, device=self.device),
+                   "area_origin": t.empty((s, nl, 2), dtype=t.int16, device=self.device), "bipred_sad": t.empty((s, 209), dtype=t.int32, device=self.device),
+                   "results": t.empty((s, 209, ctypes.sizeof(self.MeResult)), dtype=t.uint8, device=self.device)}
+        if scratch is None:
+            need = self.lib.svt_hip_motion_estimate_frame_scratch_bytes(ctypes.addressof(params), n_pictures)
+            scratch = t.empty(max(256, need), dtype=t.uint8, device=self.device)
+        self._check(self.lib.svt_hip_motion_estimate_frame(ctypes.addressof(src), ctypes.addressof(ref0), ctypes.addressof(ref1) if ref1 is not None else None,
+                                                           ctypes.addressof(params), n_pictures, self._p(out["best_sad"]), self._p(out["best_mv"]),
+                                                           self._p(out["area_origin"]), self._p(out["bipred_sad"]), self._p(out["results"]),
+                                                           self._p(scratch), scratch.numel(), self._stream()), "svt_hip_motion_estimate_frame")
+        out["_scratch"] = scratch
         return out
 
     # -- general fused chain on planes ------------------------------------------------------

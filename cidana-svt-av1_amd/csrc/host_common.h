@@ -57,8 +57,12 @@ extern int g_tune_inv32_var;
 int require_init();
 int launch_status(const char* what);
 }  // namespace svthost
-namespace svtdev { struct FrameDesc; struct QParams; }
+namespace svtdev { struct FrameDesc; struct QParams; struct MePuMap; }
 namespace svthost {
+// svt_hip_pixel.hip: the LDS row pitch of the motion search's reference window, and the raster PU order of the me_results rows
+// (shared with svt_hip_me_frame.hip)
+uint32_t me_window_pitch(uint32_t win_w);
+const svtdev::MePuMap& me_pu_map();
 // svt_hip_frame.hip: the one-launch form of svt_hip_encode_recon_frame (its kernel lives in a translation unit of its own)
 int launch_enc_frame_one(const svtdev::FrameDesc* fd, uint32_t total_wgs, int is_16bit, hipStream_t s);
 

@@ -278,7 +278,7 @@ extern "C" int svt_hip_sad_search_planes_batch(const uint8_t* d_src_plane, uint3
 // the first pitch (144 B for a 64-wide area, == 16 mod 128) the second row's lanes landed on the first row's banks: 31 % of the
 // kernel's LDS cycles were bank conflicts (profiles/r03_a_pmc_me_sb.json); the 4-points-per-lane kernel's dword reads (16 lanes
 // per search row) collide the same way.
-static uint32_t me_window_pitch(uint32_t win_w) {
+uint32_t svthost::me_window_pitch(uint32_t win_w) {
     uint32_t p = ((win_w + 15) & ~15u) + 16;
     while ((p & 127) != 64) p += 16;
     return p;
@@ -489,7 +489,7 @@ extern "C" int svt_hip_me_fullpel_search_areas_batch(const uint8_t* d_src, uint3
 
 // raster PU order (partitionWidth / partitionHeight / puSearchIndexMap, EbMotionEstimation.h:178-315): 14 shape groups, each a
 // raster walk of its grid; the storage index is the PU of the result rows with the same rectangle (me_pu_rect)
-static const MePuMap& me_pu_map() {
+const MePuMap& svthost::me_pu_map() {
     static const MePuMap m = [] {
         MePuMap t;
         memset(&t, 0, sizeof(t));

@@ -530,6 +530,71 @@ int svt_hip_me_bipred_batch(const uint8_t *d_src_pic, uint32_t src_stride, const
  * reference's tab8x8 / tab16x16 / tab32x16 ... tables (EbMotionEstimation.h:90-175), derived from the rectangles */
 int svt_hip_me_pu_storage_index(int pu_index);
 
+/* ---- MotionEstimateLcu for a whole picture (EbMotionEstimation.c:7527; the per-picture entry of the motion estimation stage) ----
+ * svt_hip_motion_estimate_frame runs, for every 64x64 SB of a picture in raster order and for list 0 (P) or lists 0 and 1 (B),
+ * what the stage calls above run when they are chained: the enabled HME levels over all search regions, the best region (the
+ * second entry of the reference's region sort for list 1 of a picture whose two references are the same picture; no HME centre
+ * at all for that list on a base-layer picture, :7656), CheckZeroZeroCenter, the search area's round-up / clip / round-down, the
+ * full-pel search over that area (85 or 209 PUs) and BiPredictionSearch with the me_results rows.  It derives the SB origins,
+ * the plane offsets and the svt_hip_hme_params rows itself and issues three launches (prologue, search, bi-prediction); nothing
+ * is allocated, nothing returns to the host, the call only enqueues and can be captured into a HIP graph.  Sub-pel refinement
+ * is outside this path (use_subpel_flag = 0), as for the stage calls.
+ *
+ * Pictures: a pyramid is the padded 8-bit luma picture and its 1/4 and 1/16 decimations (svt_hip_picture_pad / _decimate), level
+ * k = 0 full, 1 quarter, 2 sixteenth: d_plane[k] is the START of the padded buffer, the picture's sample (0, 0) sits at
+ * (origin_x[k], origin_y[k]), rows are stride[k] bytes apart.  Level k's picture is (picture_width >> k) x (picture_height >> k).
+ * The padding must be at least 64 >> k samples on every side (origin_x[k], origin_y[k] >= 64 >> k, stride[k] >= origin_x[k] +
+ * width + (64 >> k), as many rows below the picture), which the encoder's pictures have (68 / 34 / 17).  n_pictures > 1: a stack
+ * of pictures under one parameter set, picture i of every plane at pitch[k] * i bytes (each against ITS OWN references, picture i
+ * of ref0 / ref1).  ref1 is NULL for a P picture and required for a B picture.
+ *
+ * Outputs, all on the device, SB index s = picture * nsb + sb_y * nsbx + sb_x (nsbx = (width + 63) / 64, nsb = nsbx * nsby),
+ * nl = 1 (P) or 2 (B):
+ *   d_best_sad, d_best_mv  uint32 [s][nl][209]  p_sb_best_sad / p_sb_best_mv of each list in EbMeTierZeroPu order (the order
+ *                          svt_hip_me_pu_storage_index maps to); with 85 PUs the entries 85 .. 208 are 0
+ *   d_area_origin          int16 [s][nl][2]     x_search_area_origin / y_search_area_origin of each list
+ *   d_bipred_sad           uint32 [s][209]      p_sb_bipred_sad (storage order); 0 where no bi-prediction is made (P pictures,
+ *                                               PUs past 20 when cu8x8_mode != 0 with 85 PUs)
+ *   d_results              [s][209]             the me_results rows in raster PU order, rows past the PU count zeroed
+ * d_scratch: svt_hip_motion_estimate_frame_scratch_bytes(params, n_pictures) bytes, 16-byte aligned (the per-SB search areas).
+ *
+ * Every argument is checked before the first launch (SVT_HIP_ERR_INVALID): NULL planes or outputs, a picture whose sides are not
+ * multiples of 8 or exceed 16384, padding or strides below the above, a slice type other than B / P, temporal_layer_index outside
+ * 0 .. hierarchical_levels (<= 5), region counts outside 1 .. 2, HME on with no level on, a level's area arrays with a zero,
+ * search areas beyond what the stage calls take (more than 4096 points after the width's round-up to 8, or windows beyond their
+ * LDS), a PU count other than 85 / 209, an unknown flavour, the same-POC second-best rule on a non-square region grid, and
+ * SVT_HIP_FLAVOUR_AVX2 on a picture whose width is not a multiple of 64 while HME level 0 is on: the reference's AVX2 HME kernels
+ * are undefined on the 2- .. 12-wide sixteenth blocks of a partial SB column.  n_pictures = 0 is a successful no-op. */
+enum { SVT_HIP_SLICE_B = 0, SVT_HIP_SLICE_P = 1 };           /* EB_SLICE */
+typedef struct svt_hip_me_pyramid {
+    const uint8_t *d_plane[3];
+    uint32_t stride[3], origin_x[3], origin_y[3];
+    uint64_t pitch[3];                                /* between the pictures of a stack (ignored for n_pictures 1) */
+} svt_hip_me_pyramid;
+typedef struct svt_hip_me_frame_params {              /* what MotionEstimateLcu reads of its picture, sequence and ME context */
+    int32_t picture_width, picture_height;            /* luma_width / luma_height */
+    int32_t slice_type;                               /* SVT_HIP_SLICE_B / SVT_HIP_SLICE_P */
+    int32_t temporal_layer_index, hierarchical_levels;/* HME_LEVEL_0_SEARCH_AREA_MULTIPLIER_X / _Y [levels][layer] widen level 0 */
+    int32_t enable_hme_flag, enable_hme_level0_flag, enable_hme_level1_flag, enable_hme_level2_flag;
+    int32_t number_hme_search_region_in_width, number_hme_search_region_in_height;        /* 1 or 2 each */
+    int32_t hme_level0_total_search_area_width, hme_level0_total_search_area_height;
+    uint16_t hme_search_area_in_width_array[3][2];    /* hme_level{0,1,2}_search_area_in_width_array[region] */
+    uint16_t hme_search_area_in_height_array[3][2];
+    int32_t search_area_width, search_area_height;    /* before the round-up to 8 */
+    int32_t ref_pic_poc[2];                           /* ref_pic_poc_array[list]: only their equality is read */
+    int32_t is_used_as_reference_flag;                /* CheckZeroZeroCenter runs */
+    int32_t max_number_of_pus_per_sb;                 /* 85: FullPelSearch_LCU; 209: open_loop_me_fullpel_search_sblock (pic_depth_mode <= PIC_ALL_C_DEPTH_MODE) */
+    int32_t nsq_search_level;                         /* carried for the caller; the reference forces is_nsq_table_used off (:7633) */
+    int32_t cu8x8_mode;                               /* != CU_8x8_MODE_0 with 85 PUs: bi-prediction on PUs 0 .. 20 only (:8305) */
+    int32_t fractional_search_method;                 /* SUB_SAD_SEARCH (0): bi-prediction SAD on every other row, doubled */
+    int32_t flavour;                                  /* SVT_HIP_FLAVOUR_C / _AVX2 */
+} svt_hip_me_frame_params;
+size_t svt_hip_motion_estimate_frame_scratch_bytes(const svt_hip_me_frame_params *params, uint32_t n_pictures);    /* 0: bad parameters */
+int svt_hip_motion_estimate_frame(const svt_hip_me_pyramid *src, const svt_hip_me_pyramid *ref0, const svt_hip_me_pyramid *ref1,
+                                  const svt_hip_me_frame_params *params, uint32_t n_pictures, uint32_t *d_best_sad,
+                                  uint32_t *d_best_mv, int16_t *d_area_origin, uint32_t *d_bipred_sad, svt_hip_me_result *d_results,
+                                  void *d_scratch, size_t scratch_bytes, void *stream);
+
 /* K7 coefficient-domain distortion (full_distortion_kernel32_bits_func_ptr_array /
  * full_distortion_kernel_cbf_zero32_bits_func_ptr_array, EbPictureOperators.h:268-280;
  * C: EbPictureOperators.c:283-346).  d_out: uint64[nblocks][2] =

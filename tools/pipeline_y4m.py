@@ -49,8 +49,9 @@ def synthetic_clip(path, w, h, nf, seed=3, pan=(3, 1), bd=8):
 
 
 class Pipeline:
-    def __init__(self, dsp, path, qindex=100, use_graph=False):
+    def __init__(self, dsp, path, qindex=100, use_graph=False, me_frame=False):
         self.dsp = dsp
+        self.me_frame = me_frame
         self.use_graph, self.graph, self.graph_out, self.count = use_graph, None, None, 0
         self.pi = frames.PictureInput(dsp, pkg, path, origin=(68, 68))
         pi = self.pi
@@ -84,6 +85,18 @@ class Pipeline:
         self.src_off = ((self.sb_xy[:, 1] + self.pad) * self.stride + self.sb_xy[:, 0] + self.pad).to(torch.int32)
         self.SW = self.SH = 64
         self.me_setup_params = dsp.MeSetupParams(W, H, W, H, self.SW, self.SH, 2, 2, 0, 1)      # 2 x 2 HME regions, CheckZeroZeroCenter on
+        # the same stages as ONE call (svt_hip_motion_estimate_frame): a P picture of the top temporal layer (level-0 multiplier 100)
+        mp = self.me_frame_params = dsp.MeFrameParams()
+        mp.picture_width, mp.picture_height, mp.slice_type, mp.temporal_layer_index, mp.hierarchical_levels = W, H, 1, 1, 1
+        mp.enable_hme_flag = mp.enable_hme_level0_flag = mp.enable_hme_level1_flag = mp.enable_hme_level2_flag = 1
+        mp.number_hme_search_region_in_width = mp.number_hme_search_region_in_height = 2
+        for level, (w_, h_) in hw.items():
+            for i in range(2):
+                mp.hme_search_area_in_width_array[level][i], mp.hme_search_area_in_height_array[level][i] = int(w_[i]), int(h_[i])
+        mp.hme_level0_total_search_area_width, mp.hme_level0_total_search_area_height = int(hw[0][0].sum()), int(hw[0][1].sum())
+        mp.search_area_width, mp.search_area_height, mp.is_used_as_reference_flag, mp.max_number_of_pus_per_sb = self.SW, self.SH, 1, 209
+        mp.ref_pic_poc[0], mp.ref_pic_poc[1] = 0, 1
+        self.me_frame_out = None
         # open-loop intra search groups
         self.ois_groups = []
         for bsize in (8, 16, 32, 64):
@@ -109,7 +122,16 @@ class Pipeline:
         pic = y[self.pad:, self.pad:]
         # open-loop intra search on the source picture
         out["ois"] = dsp.ois_search_frame(pic, y.stride(0), self.W, self.H, self.ois_groups)
-        if self.prev is not None:
+        if self.prev is not None and self.me_frame:
+            # HME 0 / 1 / 2, ME set-up and the search in one call; the bi-prediction launch writes a P picture's me_results rows
+            pads = [(self.pad >> k, self.pad >> k) for k in range(3)]
+            o = dsp.motion_estimate_frame(dsp.me_pyramid([y, pi.quarter, pi.sixteenth], pads),
+                                          dsp.me_pyramid([self.prev["pyr"][2], self.prev["pyr"][1], self.prev["pyr"][0]], pads), None,
+                                          self.me_frame_params, out=self.me_frame_out, scratch=self.me_frame_out and self.me_frame_out["_scratch"])
+            self.me_frame_out = o
+            out["me_area_origin"], out["me_sad"], out["me_mv"] = o["area_origin"][:, 0], o["best_sad"][:, 0], o["best_mv"][:, 0]
+            out["_cur_luma"] = y
+        elif self.prev is not None:
             pyr_cur = {0: pi.sixteenth, 1: pi.quarter, 2: y}
             # the four regions of a level in one launch, three launches per picture
             centres = None
@@ -128,6 +150,7 @@ class Pipeline:
             out["_cur_luma"] = y                                                  # (a view, for tests; not part of the digest)
             out["me_sad"], out["me_mv"] = dsp.me_fullpel_search_areas(y, self.stride, self.src_off, self.prev["pyr"][2], self.stride, self.src_off, area,
                                                                       self.SW, self.SH, nsq=True)
+        if self.prev is not None:
             # encode pass: source against the previous picture at zero motion (views into the padded buffers, no copies)
             if self.fp is None:
                 self.fp = frames.FramePass(dsp, pkg, self.interior(planes), self.interior(self.prev["planes"]), is_16bit=pi.is16)
@@ -192,6 +215,8 @@ def main():
     ap.add_argument("--size", default="1920x1080")
     ap.add_argument("--bd", type=int, default=8, choices=(8, 10), help="bit depth of the synthetic clip")
     ap.add_argument("--graph", action="store_true", help="capture the per-picture analysis into a HIP graph and replay it")
+    ap.add_argument("--me-frame", action="store_true", help="HME, ME set-up and the search through svt_hip_motion_estimate_frame (one call, "
+                    "three launches); a stage-call pass runs first and the digests both paths share must be equal")
     a = ap.parse_args()
     dsp = pkg.SvtHipDsp(0)
     tmp = None
@@ -203,7 +228,7 @@ def main():
         synthetic_clip(path, w, h, a.frames, bd=a.bd)
     results = []
     for rep in range(2):                                  # the second pass is timed (page cache, allocator, first-launch costs settled)
-        p = Pipeline(dsp, path, use_graph=a.graph)
+        p = Pipeline(dsp, path, use_graph=a.graph, me_frame=a.me_frame and rep == 1)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         n, last = 0, None
@@ -218,9 +243,15 @@ def main():
         del p.graph
         p.pi.close()
     n, dt, dg = results[-1]
-    assert results[0][2] == dg, "the two passes disagree"
+    if a.me_frame:                                        # pass 0 took the stage calls, pass 1 the one call: what both produce must be equal
+        shared = sorted(set(results[0][2]) & set(dg))
+        assert {"me_sad_sum", "me_mv_sum", "ois_best_sum", "enc_digest"} <= set(shared), shared
+        assert all(results[0][2][k] == dg[k] for k in shared), "the stage calls and svt_hip_motion_estimate_frame disagree"
+        print(json.dumps({"me_frame_equals_stage_calls_on": shared, "stage_calls_digest": results[0][2]}), flush=True)
+    else:
+        assert results[0][2] == dg, "the two passes disagree"
     print(json.dumps({"file": os.path.basename(path), "picture": f"{p.W}x{p.H}", "frames": n, "seconds": round(dt, 4), "frames_per_s": round(n / dt, 1),
-                      "ms_per_frame": round(1e3 * dt / n, 3), "hip_graph": bool(a.graph), "stages": "input + decimation, OIS (4 sizes), HME 0/1/2, ME set-up + 209 PUs per-SB areas, encode pass (5 sizes, YUV)",
+                      "ms_per_frame": round(1e3 * dt / n, 3), "hip_graph": bool(a.graph), **({"me_frame": True} if a.me_frame else {}), "stages": "input + decimation, OIS (4 sizes), HME 0/1/2, ME set-up + 209 PUs per-SB areas, encode pass (5 sizes, YUV)",
                       "last_frame_digest": dg, "device": dsp.device_name()}), flush=True)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     json.dump({"picture": f"{p.W}x{p.H}", "bd": a.bd, "frames": n, "seconds": dt, "frames_per_s": n / dt, "ms_per_frame": 1e3 * dt / n, "hip_graph": bool(a.graph),
