@@ -1,6 +1,6 @@
 // host_common.h — host-side state and helpers shared by the translation units of libsvt_hip_dsp.so
-// (svt_hip_core.hip defines them; svt_hip_txfm.hip / svt_hip_pixel.hip / svt_hip_intra.hip hold the entry points of one
-// kernel family each, so that the library builds as four parallel hipcc jobs).
+// (svt_hip_core.hip defines them; every other svt_hip_*.hip holds the entry points of one kernel family, so that the library
+// builds as ten parallel hipcc jobs).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -12,9 +12,11 @@
 #include <mutex>
 
 #include "../../include/svt_hip_dsp.h"
+#include "group_table.h"
 #include "host_err.h"
 
 namespace svthost {
+static_assert(kGroupTooLarge == SVT_HIP_ERR_INVALID, "group_table.h");
 
 
 extern std::atomic<int> g_inited;
@@ -72,6 +74,11 @@ extern const int kTxH[SVT_TX_SIZES_ALL];
 inline uint32_t staged_blocks_per_wg(int tx_size) {
     const int w = kTxW[tx_size], h = kTxH[tx_size], m = w > h ? w : h;
     return (uint32_t)((w * h >= 4096 ? 2 : 4) * (64 / m));
+}
+// the quantiser's log_scale of a transform size (av1_get_tx_scale): 1 above 256 pixels, 2 above 1024
+inline int tx_log_scale(int tx_size) {
+    const int pels = kTxW[tx_size] * kTxH[tx_size];
+    return pels > 1024 ? 2 : (pels > 256 ? 1 : 0);
 }
 bool txfm_allowed(int tx_size, int tx_type);
 int frame_groups_check(const svt_hip_frame_group* groups, int ngroups);      // svt_hip_txfm.hip

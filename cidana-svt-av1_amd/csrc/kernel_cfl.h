@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "dev_common.h"
+#include "group_table.h"
 
 namespace svtdev {
 
@@ -230,28 +231,23 @@ __global__ __launch_bounds__(256) void txb_init_levels_kernel(const int32_t* __r
 constexpr int LEVELS_MAX_GROUPS = 48;
 struct LevelsGroupDev {
     const int32_t* coeff; uint8_t* levels;
-    uint32_t levels_pitch, w, h, lpb, ndw, row_magic, nblocks;
-    uint32_t wg_end;                 // bit 31: 16-byte stores (buffer and pitch 16-byte aligned)
+    uint32_t levels_pitch, w, h, lpb, ndw, row_magic, nblocks, wg_end;
+    uint32_t wide;                   // 16-byte stores (buffer and pitch 16-byte aligned)
 };
 struct LevelsFrameDesc { int32_t ngroups; LevelsGroupDev g[LEVELS_MAX_GROUPS]; };
 static_assert(sizeof(LevelsFrameDesc) <= 4000, "kernel arguments");
 
 __global__ __launch_bounds__(256) void levels_frame_kernel(const LevelsFrameDesc fd) {
-    int gi = 0;
-    uint32_t start = 0;
-#pragma unroll 1
-    for (int i = 0; i < fd.ngroups; i++) {
-        const uint32_t e = fd.g[i].wg_end & 0x7fffffffu;
-        if (blockIdx.x >= e) { gi = i + 1; start = e; }
-    }
+    uint32_t bid;
+    const int gi = group_of(fd, bid);
     if (gi >= fd.ngroups) return;
     const LevelsGroupDev& G = fd.g[gi];
     const uint32_t lsh = __builtin_ctz(G.lpb);
-    const uint32_t blk = (blockIdx.x - start) * (256u >> lsh) + (threadIdx.x >> lsh);
+    const uint32_t blk = bid * (256u >> lsh) + (threadIdx.x >> lsh);
     if (blk >= G.nblocks) return;
     const int32_t* cb = G.coeff + (size_t)blk * (G.w * G.h);
     uint32_t* ob = reinterpret_cast<uint32_t*>(G.levels + (size_t)blk * G.levels_pitch);
-    if (G.wg_end >> 31) txb_levels_body<true>(cb, ob, G.w, G.h, threadIdx.x & (G.lpb - 1), G.lpb, G.ndw, G.row_magic);
+    if (G.wide) txb_levels_body<true>(cb, ob, G.w, G.h, threadIdx.x & (G.lpb - 1), G.lpb, G.ndw, G.row_magic);
     else txb_levels_body<false>(cb, ob, G.w, G.h, threadIdx.x & (G.lpb - 1), G.lpb, G.ndw, G.row_magic);
 }
 
@@ -263,20 +259,24 @@ struct CflGroupDev {
     int32_t round_offset, num_pel_log2;
 };
 struct CflFrameDesc { int32_t ngroups; CflGroupDev g[CFL_MAX_GROUPS]; };
+static_assert(sizeof(CflFrameDesc) <= 4000, "kernel arguments");
 
 template <typename PixT>
 __global__ __launch_bounds__(256) void cfl_frame_kernel(const CflFrameDesc fd, int hi) {
+    // group_of's loop (group_table.h) spelled out: through the function the register allocator sees the same statements in another
+    // order and the VGPR counts change (8-bit 46 for 43, 10-bit 40 for 42)
     int gi = 0;
     uint32_t start = 0;
 #pragma unroll 1
     for (int i = 0; i < fd.ngroups; i++) {
         if (blockIdx.x >= fd.g[i].wg_end) { gi = i + 1; start = fd.g[i].wg_end; }
     }
+    const uint32_t bid = blockIdx.x - start;
     if (gi >= fd.ngroups) return;
     const CflGroupDev& G = fd.g[gi];
     const uint32_t lpb = G.lpb, w = G.w, h = G.h;
     const uint32_t lsh = __builtin_ctz(lpb);
-    const uint32_t blk = (blockIdx.x - start) * (256u >> lsh) + (threadIdx.x >> lsh), l = threadIdx.x & (lpb - 1);
+    const uint32_t blk = bid * (256u >> lsh) + (threadIdx.x >> lsh), l = threadIdx.x & (lpb - 1);
     const bool valid = blk < G.nblocks;
     const uint32_t cs = w < 8 ? 4u : 8u;                    // chroma samples per chunk
     const uint32_t cpr_sh = w == 32 ? 2u : (w == 16 ? 1u : 0u);

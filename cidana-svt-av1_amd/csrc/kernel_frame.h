@@ -21,6 +21,7 @@
 // (tests/test_kernel_resources.py).  Covered: all 19 transform sizes, every transform type the reference defines for them,
 // qcoeff + eob + recon outputs, 8 / 10 bit, power-of-two quant_shift tables.
 #pragma once
+#include "group_table.h"
 #include "kernel_enc64.h"
 #include "kernel_fused32.h"
 #include "kernel_txfm_staged.h"
@@ -44,22 +45,16 @@ struct FrameDesc {
 };
 static_assert(sizeof(FrameDesc) <= 4000, "kernel arguments");
 
+// LDS of a size's body: enc4_body none, enc32_body the tuned kernel's, the staged bodies their own
+#define SVT_FRAME_LDS(N, W, H) (W * H == 16 ? 0 : (W == 32 && H == 32 ? ENC32_LDS_BYTES : EncStagedLds<W, H, PixT>::BYTES)),
 template <typename PixT, int CLS> struct FrameLds;
-template <typename PixT> struct FrameLds<PixT, 0> {
-    static constexpr int BYTES = cmax(cmax(cmax(EncStagedLds<16, 16, PixT>::BYTES, EncStagedLds<8, 8, PixT>::BYTES),
-                                           cmax(EncStagedLds<8, 16, PixT>::BYTES, EncStagedLds<16, 8, PixT>::BYTES)),
-                                      cmax(cmax(EncStagedLds<4, 8, PixT>::BYTES, EncStagedLds<8, 4, PixT>::BYTES),
-                                           cmax(EncStagedLds<4, 16, PixT>::BYTES, EncStagedLds<16, 4, PixT>::BYTES)));
-};
-template <typename PixT> struct FrameLds<PixT, 1> {
-    static constexpr int BYTES = cmax(cmax(cmax(ENC32_LDS_BYTES, EncStagedLds<16, 32, PixT>::BYTES), cmax(EncStagedLds<32, 16, PixT>::BYTES, EncStagedLds<8, 32, PixT>::BYTES)),
-                                      cmax(cmax(EncStagedLds<32, 8, PixT>::BYTES, EncStagedLds<32, 64, PixT>::BYTES),
-                                           cmax(EncStagedLds<64, 32, PixT>::BYTES, cmax(EncStagedLds<16, 64, PixT>::BYTES, EncStagedLds<64, 16, PixT>::BYTES))));
-};
+template <typename PixT> struct FrameLds<PixT, 0> { static constexpr int BYTES = cmax_of({SVT_TX_CLASS0(SVT_FRAME_LDS, SVT_FRAME_LDS)}); };
+template <typename PixT> struct FrameLds<PixT, 1> { static constexpr int BYTES = cmax_of({SVT_TX_CLASS1(SVT_FRAME_LDS, SVT_FRAME_LDS)}); };
 template <typename PixT> struct FrameLds<PixT, 2> { static constexpr int BYTES = E64_WAVES * E64_WAVE_LDS; };
 template <typename PixT> struct FrameLds<PixT, 3> {       // every size in one launch
     static constexpr int BYTES = cmax(cmax(FrameLds<PixT, 0>::BYTES, FrameLds<PixT, 1>::BYTES), FrameLds<PixT, 2>::BYTES);
 };
+#undef SVT_FRAME_LDS
 
 #define SVT_FRAME_STAGED(W, H)                                                                                                         \
     enc_staged_body<W, H, false, PixT, BD>(src, pred, recon, nullptr, G.qcoeff, nullptr, G.eob, nullptr, G.iscan, G.qp, G.tx_type, G.nblocks, G.xy, \
@@ -80,7 +75,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FrameWaves<
     const PixT* src = reinterpret_cast<const PixT*>(G.src);
     const PixT* pred = reinterpret_cast<const PixT*>(G.pred);
     PixT* recon = reinterpret_cast<PixT*>(G.recon);
-#define SVT_FRAME_CASE(N, W, H) case N: SVT_FRAME_STAGED(W, H); break;
+// a size's body: 4x4 and 32x32 have kernels of their own, every other size of classes 0 and 1 is staged
+#define SVT_FRAME_BODY(W, H) if constexpr (W * H == 16) SVT_FRAME_ENC4; else if constexpr (W == 32 && H == 32) SVT_FRAME_ENC32; else SVT_FRAME_STAGED(W, H)
+#define SVT_FRAME_CASE(N, W, H) case N: SVT_FRAME_BODY(W, H); break;
+#define SVT_FRAME_DEFAULT(N, W, H) default: SVT_FRAME_BODY(W, H); break;          // the last size of a class
 #define SVT_FRAME_ENC4 enc4_body<PixT, BD, false>(src, pred, recon, nullptr, G.qcoeff, nullptr, G.eob, nullptr, G.iscan, G.qp, 1, G.tx_type, G.nblocks, G.xy, G.src_stride, \
                                                   G.pred_stride, G.recon_stride, bid)
 #define SVT_FRAME_ENC32 enc32_body<PixT, BD, false, false>(src, pred, recon, nullptr, G.qcoeff, nullptr, G.eob, nullptr, G.iscan, G.qp, G.tx_type == 9 /* IDTX */ ? 1 : 0, \
@@ -91,29 +89,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(FrameWaves<
         // the five SQUARE sizes only: with all nineteen bodies inlined into one function the compiler left their register arrays
         // in scratch (2.7 KiB per lane); a call with rectangular groups is launched by class
         switch (G.tx_size) {
-        case 0: SVT_FRAME_ENC4; break;
-        SVT_FRAME_CASE(1, 8, 8) SVT_FRAME_CASE(2, 16, 16)
-        case 3: SVT_FRAME_ENC32; break;
+        SVT_FRAME_CASE(0, 4, 4) SVT_FRAME_CASE(1, 8, 8) SVT_FRAME_CASE(2, 16, 16) SVT_FRAME_CASE(3, 32, 32)
         default: SVT_FRAME_ENC64; break;
         }
     } else if constexpr (CLS == 0) {
-        switch (G.tx_size) {
-        case 0: SVT_FRAME_ENC4; break;
-        SVT_FRAME_CASE(1, 8, 8) SVT_FRAME_CASE(2, 16, 16) SVT_FRAME_CASE(5, 4, 8) SVT_FRAME_CASE(6, 8, 4)
-        SVT_FRAME_CASE(7, 8, 16) SVT_FRAME_CASE(8, 16, 8) SVT_FRAME_CASE(13, 4, 16)
-        default: SVT_FRAME_STAGED(16, 4); break;          // 14
-        }
+        switch (G.tx_size) { SVT_TX_CLASS0(SVT_FRAME_CASE, SVT_FRAME_DEFAULT) }
     } else if constexpr (CLS == 1) {
-        switch (G.tx_size) {
-        case 3: SVT_FRAME_ENC32; break;
-        SVT_FRAME_CASE(9, 16, 32) SVT_FRAME_CASE(10, 32, 16) SVT_FRAME_CASE(11, 32, 64) SVT_FRAME_CASE(12, 64, 32)
-        SVT_FRAME_CASE(15, 8, 32) SVT_FRAME_CASE(16, 32, 8) SVT_FRAME_CASE(17, 16, 64)
-        default: SVT_FRAME_STAGED(64, 16); break;         // 18
-        }
+        switch (G.tx_size) { SVT_TX_CLASS1(SVT_FRAME_CASE, SVT_FRAME_DEFAULT) }
     } else {
         SVT_FRAME_ENC64;
     }
 #undef SVT_FRAME_CASE
+#undef SVT_FRAME_DEFAULT
+#undef SVT_FRAME_BODY
 #undef SVT_FRAME_ENC4
 #undef SVT_FRAME_ENC32
 #undef SVT_FRAME_ENC64

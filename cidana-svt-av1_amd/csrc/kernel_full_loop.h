@@ -19,6 +19,7 @@
 //   eob == 0      both = sum c^2 (the cbf_zero kernel)
 // Register classes (launch bounds as the frame kernel's): 0 both sides <= 16, 1 a 32- or 64-sample side except 64x64, 2 64x64.
 #pragma once
+#include "group_table.h"
 #include "kernel_txfm_staged.h"
 
 namespace svtdev {
@@ -51,18 +52,16 @@ struct FullLoopLds {
     static constexpr int BYTES = StagedGeom<W, H>::WAVES * WAVE;
 };
 template <int CLS> struct FullLoopClass;
+#define SVT_FL_LDS(N, W, H) FullLoopLds<W, H>::BYTES,
 template <> struct FullLoopClass<0> {
     static constexpr int THREADS = 256;
-    static constexpr int LDS = cmax(cmax(cmax(FullLoopLds<16, 16>::BYTES, FullLoopLds<8, 8>::BYTES), cmax(FullLoopLds<4, 4>::BYTES, FullLoopLds<8, 16>::BYTES)),
-                                    cmax(cmax(FullLoopLds<16, 8>::BYTES, FullLoopLds<4, 8>::BYTES), cmax(cmax(FullLoopLds<8, 4>::BYTES, FullLoopLds<4, 16>::BYTES),
-                                                                                                         FullLoopLds<16, 4>::BYTES)));
+    static constexpr int LDS = cmax_of({SVT_TX_CLASS0(SVT_FL_LDS, SVT_FL_LDS)});
 };
 template <> struct FullLoopClass<1> {
     static constexpr int THREADS = 256;
-    static constexpr int LDS = cmax(cmax(cmax(FullLoopLds<32, 32>::BYTES, FullLoopLds<16, 32>::BYTES), cmax(FullLoopLds<32, 16>::BYTES, FullLoopLds<8, 32>::BYTES)),
-                                    cmax(cmax(FullLoopLds<32, 8>::BYTES, FullLoopLds<32, 64>::BYTES), cmax(cmax(FullLoopLds<64, 32>::BYTES, FullLoopLds<16, 64>::BYTES),
-                                                                                                           FullLoopLds<64, 16>::BYTES)));
+    static constexpr int LDS = cmax_of({SVT_TX_CLASS1(SVT_FL_LDS, SVT_FL_LDS)});
 };
+#undef SVT_FL_LDS
 template <> struct FullLoopClass<2> {
     static constexpr int THREADS = 128;                   // 64x64: two waves of one block each
     static constexpr int LDS = FullLoopLds<64, 64>::BYTES;
@@ -174,22 +173,16 @@ __global__ __launch_bounds__(FullLoopClass<CLS>::THREADS) void full_loop_kernel(
     if (gi >= fd.ngroups) return;
     const FullLoopGroupDev& F = fd.g[gi];
 #define SVT_FL_CASE(N, W, H) case N: full_loop_body<W, H>(F, fd.avx2, bid, lds); break;
+#define SVT_FL_DEFAULT(N, W, H) default: full_loop_body<W, H>(F, fd.avx2, bid, lds); break;      // the last size of a class
     if constexpr (CLS == 0) {
-        switch (F.tx_size) {
-        SVT_FL_CASE(0, 4, 4) SVT_FL_CASE(1, 8, 8) SVT_FL_CASE(2, 16, 16) SVT_FL_CASE(5, 4, 8) SVT_FL_CASE(6, 8, 4)
-        SVT_FL_CASE(7, 8, 16) SVT_FL_CASE(8, 16, 8) SVT_FL_CASE(13, 4, 16)
-        default: full_loop_body<16, 4>(F, fd.avx2, bid, lds); break;       // 14
-        }
+        switch (F.tx_size) { SVT_TX_CLASS0(SVT_FL_CASE, SVT_FL_DEFAULT) }
     } else if constexpr (CLS == 1) {
-        switch (F.tx_size) {
-        SVT_FL_CASE(3, 32, 32) SVT_FL_CASE(9, 16, 32) SVT_FL_CASE(10, 32, 16) SVT_FL_CASE(11, 32, 64) SVT_FL_CASE(12, 64, 32)
-        SVT_FL_CASE(15, 8, 32) SVT_FL_CASE(16, 32, 8) SVT_FL_CASE(17, 16, 64)
-        default: full_loop_body<64, 16>(F, fd.avx2, bid, lds); break;      // 18
-        }
+        switch (F.tx_size) { SVT_TX_CLASS1(SVT_FL_CASE, SVT_FL_DEFAULT) }
     } else {
         full_loop_body<64, 64>(F, fd.avx2, bid, lds);
     }
 #undef SVT_FL_CASE
+#undef SVT_FL_DEFAULT
 }
 
 }  // namespace svtdev

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "dev_common.h"
+#include "group_table.h"
 
 namespace svtdev {
 
@@ -81,17 +82,14 @@ struct OisGatherGroup {
     uint32_t bsize, nb_pitch, nblocks, wg_end;
 };
 struct OisGatherMulti { int32_t ngroups; OisGatherGroup g[OIS_GATHER_MAX_GROUPS]; };
+static_assert(sizeof(OisGatherMulti) <= 4000, "kernel arguments");
 __global__ __launch_bounds__(256) void ois_gather_multi_kernel(const uint8_t* __restrict__ pic, uint32_t stride, uint32_t width, uint32_t height,
                                                                const OisGatherMulti m) {
-    int gi = 0;
-    uint32_t start = 0;
-#pragma unroll 1
-    for (int i = 0; i < m.ngroups; i++) {
-        if (blockIdx.x >= m.g[i].wg_end) { gi = i + 1; start = m.g[i].wg_end; }
-    }
+    uint32_t bid;
+    const int gi = group_of(m, bid);
     if (gi >= m.ngroups) return;
     const OisGatherGroup& G = m.g[gi];
-    ois_gather_body(pic, stride, width, height, G.xy, G.bsize, G.above, G.left, G.nb_pitch, G.dc, G.nblocks, blockIdx.x - start);
+    ois_gather_body(pic, stride, width, height, G.xy, G.bsize, G.above, G.left, G.nb_pitch, G.dc, G.nblocks, bid);
 }
 
 // One launch for ALL candidates: pred_all holds ncand dense prediction batches back to back (a candidate whose bit
@@ -341,18 +339,15 @@ struct OisNdGroup {
     OisKinds kinds;
 };
 struct OisNdMulti { int32_t ngroups; OisNdGroup g[OIS_ND_MAX_GROUPS]; };
+static_assert(sizeof(OisNdMulti) <= 4000, "kernel arguments");
 __global__ __launch_bounds__(256) void ois_nd_multi_kernel(const uint8_t* __restrict__ pic, uint32_t stride, uint32_t width, uint32_t height,
                                                            const OisNdMulti m) {
-    int gi = 0;
-    uint32_t start = 0;
-#pragma unroll 1
-    for (int i = 0; i < m.ngroups; i++) {
-        if (blockIdx.x >= m.g[i].wg_end) { gi = i + 1; start = m.g[i].wg_end; }
-    }
+    uint32_t bid;
+    const int gi = group_of(m, bid);
     if (gi >= m.ngroups) return;
     const OisNdGroup& G = m.g[gi];
-    if (G.bsize < 16) ois_nd_body<8>(pic, stride, width, height, G.xy, G.bsize, G.kinds, G.dist, G.best_index, G.ncand, G.nblocks, blockIdx.x - start);
-    else ois_nd_body<16>(pic, stride, width, height, G.xy, G.bsize, G.kinds, G.dist, G.best_index, G.ncand, G.nblocks, blockIdx.x - start);
+    if (G.bsize < 16) ois_nd_body<8>(pic, stride, width, height, G.xy, G.bsize, G.kinds, G.dist, G.best_index, G.ncand, G.nblocks, bid);
+    else ois_nd_body<16>(pic, stride, width, height, G.xy, G.bsize, G.kinds, G.dist, G.best_index, G.ncand, G.nblocks, bid);
 }
 
 }  // namespace svtdev

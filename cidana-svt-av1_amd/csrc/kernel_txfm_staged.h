@@ -7,8 +7,10 @@
 // MODE 1: u8 src + pred -> coeff, qcoeff, dqcoeff (packed min(W,32)*min(H,32)), eob, sad,
 //         three_quad_energy  (the headline chain for sizes other than 32x32)
 #pragma once
+#include <initializer_list>
 #include <type_traits>
 
+#include "group_table.h"
 #include "kernel_txfm.h"
 
 namespace svtdev {
@@ -377,28 +379,25 @@ __device__ __forceinline__ uint4 add_clip(uint4 p, const short* res, int maxpix)
     return make_uint4(ow[0], ow[1], ow[2], ow[3]);
 }
 
-// ---- launch plumbing, not a transform step: here because both users of a group table include this header ----
-// Group-table launches (enc_frame_kernel, kernel_frame.h; full_loop_kernel, kernel_full_loop.h): a table in the kernel arguments (no
-// device-side descriptor memory: the call stays a pure enqueue and is graph-capturable) whose group i takes the workgroups up to
-// wg_end.  Returns the group of workgroup blockIdx.x (fd.ngroups when past the last) and its index bid inside that group.  Uniform:
-// scalar compares against the table.
-template <typename Desc>
-__device__ __forceinline__ int group_of(const Desc& fd, uint32_t& bid) {
-    int gi = 0;
-    uint32_t start = 0;
-#pragma unroll 1
-    for (int i = 0; i < fd.ngroups; i++) {
-        if (blockIdx.x >= fd.g[i].wg_end) { gi = i + 1; start = fd.g[i].wg_end; }
-    }
-    bid = blockIdx.x - start;
-    return gi;
-}
-// register class of a transform size in those launches (TxSize numbering of the reference, EbDefinitions.h:615-650): 0 both sides
-// <= 16 (TX_4X4 0, 8X8 1, 16X16 2, 4X8 5, 8X4 6, 8X16 7, 16X8 8, 4X16 13, 16X4 14), 2 64x64, 1 the rest.  A bit mask, not a table:
-// usable on the device with a run-time size.
+// Register classes of the group-table launches (enc_frame_kernel, kernel_frame.h; full_loop_kernel, kernel_full_loop.h): 0 both sides
+// <= 16, 1 a 32- or 64-sample side except 64x64, 2 64x64.  THE list of sizes per class, entries (TxSize number, W, H) in the
+// reference's numbering (EbDefinitions.h:615-650); tx_class_of, the kernels' LDS maxima and the case lists of their switches are
+// generated from it.  X takes every entry but the last, L the last one (a switch's default:).
+#define SVT_TX_CLASS0(X, L) X(0, 4, 4) X(1, 8, 8) X(2, 16, 16) X(5, 4, 8) X(6, 8, 4) X(7, 8, 16) X(8, 16, 8) X(13, 4, 16) L(14, 16, 4)
+#define SVT_TX_CLASS1(X, L) X(3, 32, 32) X(9, 16, 32) X(10, 32, 16) X(11, 32, 64) X(12, 64, 32) X(15, 8, 32) X(16, 32, 8) X(17, 16, 64) L(18, 64, 16)
+#define SVT_TX_BIT(N, W, H) | (1u << N)
+constexpr unsigned kTxClass0 = 0u SVT_TX_CLASS0(SVT_TX_BIT, SVT_TX_BIT), kTxClass1 = 0u SVT_TX_CLASS1(SVT_TX_BIT, SVT_TX_BIT), kTxClass2 = 1u << 4;
+#undef SVT_TX_BIT
+static_assert((kTxClass0 ^ kTxClass1 ^ kTxClass2) == (1u << 19) - 1 && !(kTxClass0 & kTxClass1), "each of the sizes 0 .. 18 lands in exactly one class");
+// bit masks, not a table: usable on the device with a run-time size
 __host__ __device__ constexpr int tx_class_of(int tx_size) {
-    constexpr unsigned small = (1u << 0) | (1u << 1) | (1u << 2) | (1u << 5) | (1u << 6) | (1u << 7) | (1u << 8) | (1u << 13) | (1u << 14);
-    return tx_size == 4 ? 2 : (((small >> tx_size) & 1u) ? 0 : 1);
+    return tx_size == 4 ? 2 : (((kTxClass0 >> tx_size) & 1u) ? 0 : 1);
+}
+// the largest of a list: cmax_of({SVT_TX_CLASS0(V, V)}) with V(N, W, H) = a size's value and a comma
+constexpr int cmax_of(std::initializer_list<int> v) {
+    int m = 0;
+    for (int x : v) m = cmax(m, x);
+    return m;
 }
 
 // PixT: sample type of src / pred in MODE 1 (uint8_t, or uint16_t for 10-bit).  xy != NULL: the blocks are

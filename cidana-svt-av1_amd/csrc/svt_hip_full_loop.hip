@@ -57,35 +57,25 @@ extern "C" int svt_hip_full_loop_frame(const svt_hip_full_loop_group* groups, in
     for (int ls = 0; ls < 3; ls++) qps[ls] = quant_params(zbin, round, quant, quant_shift, dequant, ls);
     // the 64x64 class first, the small sizes last: the long workgroups start early
     for (int cls = 2; cls >= 0; cls--) {
-        FullLoopDesc fd;
-        memset(&fd, 0, sizeof(fd));
-        fd.avx2 = flavour == SVT_HIP_FLAVOUR_AVX2;
-        uint32_t total = 0;
-        auto flush = [&]() -> int {
-            if (!fd.ngroups) return SVT_HIP_OK;
-            const int rc = cls == 2 ? full_loop_launch<2>(fd, total, s) : (cls == 1 ? full_loop_launch<1>(fd, total, s) : full_loop_launch<0>(fd, total, s));
-            fd.ngroups = 0;
-            total = 0;
-            return rc;
+        GroupTable<FullLoopDesc, FL_MAX_GROUPS> tab;
+        tab.desc.avx2 = flavour == SVT_HIP_FLAVOUR_AVX2;
+        auto launch = [&](const FullLoopDesc& fd, uint32_t total) -> int {
+            return cls == 2 ? full_loop_launch<2>(fd, total, s) : (cls == 1 ? full_loop_launch<1>(fd, total, s) : full_loop_launch<0>(fd, total, s));
         };
         for (int g = 0; g < ngroups; g++) {
             const svt_hip_full_loop_group& G = groups[g];
             if (G.nblocks == 0 || tx_class_of(G.tx_size) != cls) continue;
-            const int pels = kTxW[G.tx_size] * kTxH[G.tx_size];
-            const uint32_t per_wg = staged_blocks_per_wg(G.tx_size), wgs = (G.nblocks + per_wg - 1) / per_wg;
-            if (fd.ngroups == FL_MAX_GROUPS || (size_t)total + wgs > 0x7fffffffu)
-                if (int rc = flush()) return rc;
-            FullLoopGroupDev& D = fd.g[fd.ngroups++];
-            D.src = (const uint8_t*)G.d_src; D.pred = (const uint8_t*)G.d_pred; D.src_xy = G.d_src_xy; D.pred_xy = G.d_pred_xy;
-            D.iscan = G.d_iscan; D.dist = (unsigned long long*)G.d_dist; D.eob = G.d_eob; D.qcoeff = G.d_qcoeff; D.dqcoeff = G.d_dqcoeff;
-            D.src_stride = G.src_stride; D.pred_stride = G.pred_stride; D.nblocks = G.nblocks;
-            D.tx_size = G.tx_size; D.ntypes = G.ntypes;
-            memcpy(D.types, G.tx_types, sizeof(D.types));
-            D.qp = qps[pels > 1024 ? 2 : (pels > 256 ? 1 : 0)];
-            total += wgs;                                         // (< 2^31: checked above)
-            D.wg_end = total;
+            const uint32_t per_wg = staged_blocks_per_wg(G.tx_size);
+            FullLoopGroupDev* D = tab.add((G.nblocks + per_wg - 1) / per_wg, launch);
+            if (!D) return tab.rc;
+            D->src = (const uint8_t*)G.d_src; D->pred = (const uint8_t*)G.d_pred; D->src_xy = G.d_src_xy; D->pred_xy = G.d_pred_xy;
+            D->iscan = G.d_iscan; D->dist = (unsigned long long*)G.d_dist; D->eob = G.d_eob; D->qcoeff = G.d_qcoeff; D->dqcoeff = G.d_dqcoeff;
+            D->src_stride = G.src_stride; D->pred_stride = G.pred_stride; D->nblocks = G.nblocks;
+            D->tx_size = G.tx_size; D->ntypes = G.ntypes;
+            memcpy(D->types, G.tx_types, sizeof(D->types));
+            D->qp = qps[tx_log_scale(G.tx_size)];
         }
-        if (int rc = flush()) return rc;
+        if (int rc = tab.flush(launch)) return rc;
     }
     return SVT_HIP_OK;
 }

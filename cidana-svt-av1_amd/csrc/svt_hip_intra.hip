@@ -114,21 +114,15 @@ extern "C" int svt_hip_txb_init_levels_batch(const int32_t* d_coeff, size_t coef
 
 // ---- the frame call with its chroma-from-luma step and level maps (header: svt_hip_encode_recon_frame_ex) ----
 static int frame_levels_launch(const svt_hip_frame_group* groups, const svt_hip_frame_levels* levels, int ngroups, hipStream_t s) {
-    LevelsFrameDesc fd;
-    memset(&fd, 0, sizeof(fd));
-    uint32_t total = 0;
-    auto flush = [&]() -> int {
-        if (!fd.ngroups) return SVT_HIP_OK;
+    GroupTable<LevelsFrameDesc, LEVELS_MAX_GROUPS> tab;
+    auto launch = [&](const LevelsFrameDesc& fd, uint32_t total) -> int {
         hipLaunchKernelGGL(levels_frame_kernel, dim3(total), dim3(256), 0, s, fd);
-        fd.ngroups = 0; total = 0;
         return launch_status("levels_frame");
     };
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_frame_group& G = groups[g];
         const svt_hip_frame_levels& L = levels[g];
         if (!G.nblocks || !L.d_levels_buf) continue;
-        if (fd.ngroups == LEVELS_MAX_GROUPS) if (int rc = flush()) return rc;
-        LevelsGroupDev& D = fd.g[fd.ngroups];
         // get_txb_wide / get_txb_high: the packed coefficient block (a 64-sample side keeps its 32 low-frequency columns / rows)
         const uint32_t w = (uint32_t)(kTxW[G.tx_size] > 32 ? 32 : kTxW[G.tx_size]), h = (uint32_t)(kTxH[G.tx_size] > 32 ? 32 : kTxH[G.tx_size]);
         const uint32_t bytes = (w + 4) * (h + 6) + 16, ndw = bytes >> 2, dpr = (w + 4) >> 2;
@@ -136,14 +130,13 @@ static int frame_levels_launch(const svt_hip_frame_group* groups, const svt_hip_
         const uint32_t items = wide ? (ndw + 3) / 4 : ndw;
         uint32_t lpb = 1;
         while (lpb < items && lpb < 256) lpb <<= 1;
-        D.coeff = G.d_qcoeff; D.levels = L.d_levels_buf; D.levels_pitch = (uint32_t)L.levels_block_pitch; D.w = w; D.h = h; D.lpb = lpb; D.ndw = ndw;
-        D.row_magic = (uint32_t)(0x100000000ull / dpr) + 1u; D.nblocks = G.nblocks;
         const uint32_t slots = 256 / lpb;
-        total += (G.nblocks + slots - 1) / slots;
-        D.wg_end = total | (wide ? 0x80000000u : 0u);
-        fd.ngroups++;
+        LevelsGroupDev* D = tab.add((G.nblocks + slots - 1) / slots, launch);      // (nblocks < 2^31: checked by the caller)
+        if (!D) return tab.rc;
+        D->coeff = G.d_qcoeff; D->levels = L.d_levels_buf; D->levels_pitch = (uint32_t)L.levels_block_pitch; D->w = w; D->h = h; D->lpb = lpb; D->ndw = ndw;
+        D->row_magic = (uint32_t)(0x100000000ull / dpr) + 1u; D->nblocks = G.nblocks; D->wide = wide;
     }
-    return flush();
+    return tab.flush(launch);
 }
 
 extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, int ngroups, int first_chroma_group,
@@ -158,9 +151,7 @@ extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, 
     if ((is_16bit && bd != 8 && bd != 10 && bd != 12) || (!is_16bit && bd != 8)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
     // everything is validated before anything is enqueued
     if (int rc = frame_groups_check(groups, ngroups)) return rc;
-    CflFrameDesc cd;
-    memset(&cd, 0, sizeof(cd));
-    uint32_t cfl_total = 0;
+    GroupTable<CflFrameDesc, CFL_MAX_GROUPS> ctab;       // (ncfl <= CFL_MAX_GROUPS: one launch, after the luma pass)
     for (int g = 0; g < ncfl; g++) {
         const svt_hip_frame_cfl_group& C = cfl[g];
         if (C.nblocks == 0) continue;
@@ -169,16 +160,15 @@ extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, 
         if (!cfl_dim_ok(C.width) || !cfl_dim_ok(C.height)) return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: chroma block %ux%u", g, C.width, C.height);
         if (C.luma_stride < 2 * C.width || C.pred_stride_cb < C.width || C.pred_stride_cr < C.width)
             return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: stride smaller than the block", g);
-        CflGroupDev& D = cd.g[cd.ngroups++];
-        const uint32_t nchunks = (C.width / (C.width < 8 ? 4 : 8)) * C.height;
-        D.lpb = nchunks < 64 ? nchunks : 64;
-        D.luma = C.d_luma_recon; D.cb = C.d_pred_cb; D.cr = C.d_pred_cr; D.xy = C.d_xy; D.alpha_cb = C.d_alpha_q3_cb; D.alpha_cr = C.d_alpha_q3_cr;
-        D.luma_stride = C.luma_stride; D.cb_stride = C.pred_stride_cb; D.cr_stride = C.pred_stride_cr; D.nblocks = C.nblocks; D.w = C.width; D.h = C.height;
-        D.round_offset = (int32_t)(C.width * C.height / 2);
-        D.num_pel_log2 = __builtin_ctz(C.width) + __builtin_ctz(C.height);
-        const uint32_t slots = 256 / D.lpb;
-        cfl_total += (C.nblocks + slots - 1) / slots;
-        D.wg_end = cfl_total;
+        const uint32_t nchunks = (C.width / (C.width < 8 ? 4 : 8)) * C.height, lpb = nchunks < 64 ? nchunks : 64, slots = 256 / lpb;
+        const uint32_t wgs = (C.nblocks - 1) / slots + 1;
+        CflGroupDev* D = ctab.add(wgs);
+        if (!D) return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: too many blocks for one launch", g);
+        D->lpb = lpb;
+        D->luma = C.d_luma_recon; D->cb = C.d_pred_cb; D->cr = C.d_pred_cr; D->xy = C.d_xy; D->alpha_cb = C.d_alpha_q3_cb; D->alpha_cr = C.d_alpha_q3_cr;
+        D->luma_stride = C.luma_stride; D->cb_stride = C.pred_stride_cb; D->cr_stride = C.pred_stride_cr; D->nblocks = C.nblocks; D->w = C.width; D->h = C.height;
+        D->round_offset = (int32_t)(C.width * C.height / 2);
+        D->num_pel_log2 = __builtin_ctz(C.width) + __builtin_ctz(C.height);
     }
     if (levels)
         for (int g = 0; g < ngroups; g++) {
@@ -188,16 +178,19 @@ extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, 
             const size_t bytes = (size_t)(w + 4) * (h + 6) + 16;
             if (L.levels_block_pitch < bytes || (L.levels_block_pitch & 3) || ((uintptr_t)L.d_levels_buf & 3) || L.levels_block_pitch > 0xffffffffu)
                 return set_err(SVT_HIP_ERR_INVALID, "group %d: levels buffer %zu B per block (need >= %zu, multiple of 4, 4-byte aligned)", g, L.levels_block_pitch, bytes);
+            if (groups[g].nblocks > kMaxLaunchWgs) return set_err(SVT_HIP_ERR_INVALID, "group %d: too many blocks for one launch", g);
         }
     hipStream_t s = (hipStream_t)stream;
     // stream order carries the dependencies: luma reconstruction -> chroma-from-luma prediction -> chroma encode -> level maps
-    const int n_first = cd.ngroups ? first_chroma_group : ngroups;
+    const int n_first = ctab.size() ? first_chroma_group : ngroups;
     if (int rc = svt_hip_encode_recon_frame(groups, n_first, is_16bit, bd, zbin, round, quant, quant_shift, dequant, stream)) return rc;
-    if (cd.ngroups) {
+    if (ctab.size()) {
         const int hi = (1 << bd) - 1;
-        if (is_16bit) hipLaunchKernelGGL((cfl_frame_kernel<uint16_t>), dim3(cfl_total), dim3(256), 0, s, cd, hi);
-        else hipLaunchKernelGGL((cfl_frame_kernel<uint8_t>), dim3(cfl_total), dim3(256), 0, s, cd, hi);
-        if (int rc = launch_status("cfl_frame")) return rc;
+        if (int rc = ctab.flush([&](const CflFrameDesc& cd, uint32_t total) {
+                if (is_16bit) hipLaunchKernelGGL((cfl_frame_kernel<uint16_t>), dim3(total), dim3(256), 0, s, cd, hi);
+                else hipLaunchKernelGGL((cfl_frame_kernel<uint8_t>), dim3(total), dim3(256), 0, s, cd, hi);
+                return launch_status("cfl_frame");
+            })) return rc;
         if (int rc = svt_hip_encode_recon_frame(groups + n_first, ngroups - n_first, is_16bit, bd, zbin, round, quant, quant_shift, dequant, stream)) return rc;
     }
     if (levels) return frame_levels_launch(groups, levels, ngroups, s);
@@ -608,7 +601,7 @@ static int ois_search_impl(const uint8_t* d_pic, uint32_t stride, uint32_t width
                 const uint32_t slots = 256 / (2 * bsize);
                 if (phase == 1) {
                     gather->xy = d_xy; gather->above = d_above; gather->left = d_left; gather->dc = d_dc; gather->bsize = bsize;
-                    gather->nb_pitch = (uint32_t)pitch; gather->nblocks = (uint32_t)nblocks; gather->wg_end = (uint32_t)((nblocks + slots - 1) / slots);
+                    gather->nb_pitch = (uint32_t)pitch; gather->nblocks = (uint32_t)nblocks;
                     return SVT_HIP_OK;
                 }
                 if (phase == 0) {
@@ -654,7 +647,7 @@ static int ois_search_impl(const uint8_t* d_pic, uint32_t stride, uint32_t width
             const size_t shmem = (((size_t)nd_slots + (lpb > 64 ? 4 : 0)) * (size_t)ncand + 4) * sizeof(uint32_t);
             if (defer) {
                 defer->xy = d_xy; defer->dist = d_distortion; defer->best_index = d_best_index; defer->bsize = bsize; defer->ncand = (uint32_t)ncand;
-                defer->nblocks = (uint32_t)nblocks; defer->wg_end = nd_grid /* the caller turns it into a running end */; defer->kinds = kinds;
+                defer->nblocks = (uint32_t)nblocks; defer->kinds = kinds;
                 return SVT_HIP_OK;
             }
             if (cs == 8)
@@ -759,71 +752,58 @@ extern "C" int svt_hip_ois_search_frame(const uint8_t* d_pic, uint32_t stride, u
     // the chains leave no free units), so the side stream, its fork / join events and two ~ 20 us latency-bound launches are gone.
     // (svt_hip_tune("ois_no_nd_multi", 1): one non-directional launch per group, on the caller's stream.)
     hipStream_t s = (hipStream_t)stream;
-    OisNdMulti m;
-    memset(&m, 0, sizeof(m));
-    uint32_t total = 0;
-    size_t shmem = 0;
-    auto flush = [&]() -> int {
-        if (!m.ngroups) return SVT_HIP_OK;
-        // largest blocks first: their workgroups are the longest latency chains (64x64: one block per workgroup, two barriers)
-        for (int i = 1; i < m.ngroups; i++) {
-            const OisNdGroup v = m.g[i];
-            int j = i - 1;
-            while (j >= 0 && m.g[j].bsize < v.bsize) { m.g[j + 1] = m.g[j]; j--; }
-            m.g[j + 1] = v;
-        }
-        total = 0;
-        for (int i = 0; i < m.ngroups; i++) { total += m.g[i].wg_end; m.g[i].wg_end = total; }
+    // largest blocks first: their workgroups are the longest latency chains (64x64: one block per workgroup, two barriers)
+    GroupTable<OisNdMulti, OIS_ND_MAX_GROUPS, true> nd;
+    size_t shmem = 0;                           // of the launch: the largest of its groups
+    auto nd_launch = [&](const OisNdMulti& m, uint32_t total) -> int {
         hipLaunchKernelGGL(ois_nd_multi_kernel, dim3(total), dim3(256), shmem, s, d_pic, stride, width, height, m);
-        m.ngroups = 0; total = 0; shmem = 0;
+        shmem = 0;
         return launch_status("ois_nd_multi");
     };
     // the neighbour gathers of the groups that have directional candidates: one launch, first (arguments are validated here, before
     // anything is enqueued)
     const bool multi = !g_tune_ois_no_nd_multi;
     {
-        OisGatherMulti gm;
-        memset(&gm, 0, sizeof(gm));
-        uint32_t gtotal = 0;
-        auto gflush = [&]() -> int {
-            if (!gm.ngroups) return SVT_HIP_OK;
-            hipLaunchKernelGGL(ois_gather_multi_kernel, dim3(gtotal), dim3(256), 0, s, d_pic, stride, width, height, gm);
-            gm.ngroups = 0; gtotal = 0;
+        GroupTable<OisGatherMulti, OIS_GATHER_MAX_GROUPS> gather;
+        auto gather_launch = [&](const OisGatherMulti& gm, uint32_t total) -> int {
+            hipLaunchKernelGGL(ois_gather_multi_kernel, dim3(total), dim3(256), 0, s, d_pic, stride, width, height, gm);
             return launch_status("ois_gather_multi");
         };
         for (int g = 0; g < ngroups && multi; g++) {
             const svt_hip_ois_group& G = groups[g];
             if (G.nblocks == 0) continue;
-            OisGatherGroup gd;
+            OisGatherGroup gd = {};
             if (int rc = ois_search_impl(d_pic, stride, width, height, G.d_xy, G.bsize, G.modes, G.angle_deltas, G.ncand, G.d_distortion, G.d_best_index,
                                          G.d_work, G.work_bytes, G.nblocks, stream, nullptr, 1, &gd)) {
-                return gm.ngroups ? (gflush(), rc) : rc;
+                (void)gather.flush(gather_launch);
+                return rc;
             }
             if (gd.nblocks == 0) continue;
-            if (gm.ngroups == OIS_GATHER_MAX_GROUPS) if (int rc = gflush()) return rc;
-            gtotal += gd.wg_end;
-            gd.wg_end = gtotal;
-            gm.g[gm.ngroups++] = gd;
+            const uint32_t slots = 256 / (2 * gd.bsize);
+            OisGatherGroup* slot = gather.add((gd.nblocks + slots - 1) / slots, gather_launch);
+            if (!slot) return gather.rc;
+            *slot = gd;
         }
-        if (int rc = gflush()) return rc;
+        if (int rc = gather.flush(gather_launch)) return rc;
     }
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_ois_group& G = groups[g];
         if (G.nblocks == 0) continue;
-        OisNdGroup d;
+        OisNdGroup d = {};
         if (int rc = ois_search_impl(d_pic, stride, width, height, G.d_xy, G.bsize, G.modes, G.angle_deltas, G.ncand, G.d_distortion, G.d_best_index,
                                      G.d_work, G.work_bytes, G.nblocks, stream, multi ? &d : nullptr, multi ? 2 : 0)) {
-            (void)flush();                      // what was enqueued for the earlier groups stays complete
+            (void)nd.flush(nd_launch);          // what was enqueued for the earlier groups stays complete
             return rc;
         }
         if (g_tune_ois_no_nd_multi || d.nblocks == 0) continue;
-        if (m.ngroups == OIS_ND_MAX_GROUPS) if (int rc = flush()) return rc;
         const uint32_t cs = d.bsize < 16 ? 8 : 16, lpb = d.bsize * d.bsize / cs, nd_slots = 256 / lpb;
+        OisNdGroup* slot = nd.add((d.nblocks + nd_slots - 1) / nd_slots, nd_launch, d.bsize);
+        if (!slot) return nd.rc;
+        *slot = d;
         const size_t sh = (((size_t)nd_slots + (lpb > 64 ? 4 : 0)) * (size_t)d.ncand + 4) * sizeof(uint32_t);
         shmem = sh > shmem ? sh : shmem;
-        m.g[m.ngroups++] = d;                   // (wg_end = the group's own workgroup count until flush() orders the groups)
     }
-    return flush();
+    return nd.flush(nd_launch);
 }
 
 // one intra block: stage [lo, hi) of above / left around the origin, predict, copy the block back

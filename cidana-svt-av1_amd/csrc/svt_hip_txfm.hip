@@ -381,7 +381,7 @@ static int encode_recon_impl(const void* d_src_v, uint32_t src_stride, const voi
     }
     {   // every other size: the staged fused kernel (dense 8-bit batches, power-of-two quant_shift tables)
         const int pels = kTxW[tx_size] * kTxH[tx_size];
-        const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, pels > 1024 ? 2 : (pels > 256 ? 1 : 0));
+        const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, tx_log_scale(tx_size));
         const bool ok = qp.fast_ok && pels > 16 && !g_tune_no_enc_staged && ((d_coeff != nullptr) == (d_dqcoeff != nullptr)) &&
                         !qparams_negative(qp) && aligned16(d_qcoeff, d_coeff, d_dqcoeff) && (d_xy || aligned16(d_src, d_pred, d_recon));
         if (ok && tx_size == SVT_TX_64X64 && !g_tune_no_enc64) {
@@ -465,7 +465,7 @@ extern "C" int svt_hip_fwd_quant_planes_batch(const void* d_src, uint32_t src_st
     if (is_16bit && d_sad) return set_err(SVT_HIP_ERR_INVALID, "SAD is defined for 8-bit planes only (the reference searches on the 8-bit MSB plane)");
     if (nblocks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "nblocks too large");
     const int pels = kTxW[tx_size] * kTxH[tx_size];
-    const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, pels > 1024 ? 2 : (pels > 256 ? 1 : 0));
+    const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, tx_log_scale(tx_size));
     if (qparams_negative(qp)) return set_err(SVT_HIP_ERR_INVALID, "negative quantizer table entry");
     hipStream_t s = (hipStream_t)stream;
     if (tx_size == SVT_TX_32X32 && (tx_type == SVT_DCT_DCT || tx_type == SVT_IDTX) && qp.fast_ok && !d_energy && !g_tune_no_f32p &&
@@ -558,57 +558,41 @@ extern "C" int svt_hip_encode_recon_frame(const svt_hip_frame_group* groups, int
     for (int g = 0; g < ngroups; g++)
         if (mode == 1 && groups[g].nblocks && groups[g].tx_size > SVT_TX_64X64) mode = 2;      // the one-launch kernel holds the square sizes
     if (mode > 0) {
-        bool ok = true;
-        int per_class[4] = {0, 0, 0, 0};
+        bool ok = (is_16bit && bd == 10) || (!is_16bit && bd == 8);
         for (int g = 0; g < ngroups && ok; g++) {
             const svt_hip_frame_group& G = groups[g];
-            if (G.nblocks == 0) continue;
-            ok = !G.d_coeff && G.d_recon != G.d_src && (((uintptr_t)G.d_qcoeff) & 15) == 0;      // (type / size validated above)
-            per_class[mode == 1 ? 3 : tx_class_of(G.tx_size)]++;
+            if (G.nblocks) ok = !G.d_coeff && G.d_recon != G.d_src && (((uintptr_t)G.d_qcoeff) & 15) == 0;      // (type / size validated above)
         }
-        if ((is_16bit && bd != 10) || (!is_16bit && bd != 8)) ok = false;
-        for (int c = 0; c < 4; c++) ok = ok && per_class[c] <= FRAME_MAX_GROUPS;
-        FrameDesc fd[4];
-        uint32_t total[4] = {0, 0, 0, 0};
         if (ok) {
-            memset(fd, 0, sizeof(fd));
-            int order[256];
-            for (int i = 0; i < ngroups; i++) order[i] = i;
-            for (int i = 1; i < ngroups; i++) {          // largest blocks first: the long workgroups start early
-                const int v = order[i];
-                const int pv = kTxW[groups[v].tx_size] * kTxH[groups[v].tx_size];
-                int j = i - 1;
-                while (j >= 0 && kTxW[groups[order[j]].tx_size] * kTxH[groups[order[j]].tx_size] < pv) { order[j + 1] = order[j]; j--; }
-                order[j + 1] = v;
-            }
-            for (int k = 0; k < ngroups && ok; k++) {
-                const svt_hip_frame_group& G = groups[order[k]];
+            // one table per class (3: the one launch), its groups largest blocks first: the long workgroups start early.  Nothing is
+            // launched before every group has its slot: a class with no room for a group sends the call to the fan-out below.
+            GroupTable<FrameDesc, FRAME_MAX_GROUPS, true> tab[4];
+            for (int g = 0; g < ngroups; g++) {
+                const svt_hip_frame_group& G = groups[g];
                 if (G.nblocks == 0) continue;
-                const int pels = kTxW[G.tx_size] * kTxH[G.tx_size], c = mode == 1 ? 3 : tx_class_of(G.tx_size);
-                FrameGroupDev& D = fd[c].g[fd[c].ngroups];
-                D.qp = make_qparams(zbin, round, quant, quant_shift, dequant, pels > 1024 ? 2 : (pels > 256 ? 1 : 0));
-                ok = ok && D.qp.fast_ok && !qparams_negative(D.qp);
-                D.src = G.d_src; D.pred = G.d_pred; D.recon = G.d_recon; D.qcoeff = G.d_qcoeff; D.eob = G.d_eob; D.xy = G.d_xy; D.iscan = G.d_iscan;
-                D.src_stride = G.src_stride; D.pred_stride = G.pred_stride; D.recon_stride = G.recon_stride; D.nblocks = G.nblocks; D.tx_size = G.tx_size; D.tx_type = G.tx_type;
-                const uint32_t per_wg = frame_blocks_per_wg(G.tx_size);
-                total[c] += (G.nblocks + per_wg - 1) / per_wg;
-                D.wg_end = total[c];
-                fd[c].ngroups++;
+                const int c = mode == 1 ? 3 : tx_class_of(G.tx_size);
+                const uint32_t per_wg = frame_blocks_per_wg(G.tx_size), wgs = (G.nblocks - 1) / per_wg + 1;
+                const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, tx_log_scale(G.tx_size));
+                FrameGroupDev* D = qp.fast_ok && !qparams_negative(qp) ? tab[c].add(wgs, (uint64_t)(kTxW[G.tx_size] * kTxH[G.tx_size])) : nullptr;
+                if (!(ok = D != nullptr)) break;
+                D->qp = qp;
+                D->src = G.d_src; D->pred = G.d_pred; D->recon = G.d_recon; D->qcoeff = G.d_qcoeff; D->eob = G.d_eob; D->xy = G.d_xy; D->iscan = G.d_iscan;
+                D->src_stride = G.src_stride; D->pred_stride = G.pred_stride; D->recon_stride = G.recon_stride; D->nblocks = G.nblocks; D->tx_size = G.tx_size; D->tx_type = G.tx_type;
             }
-        }
-        if (ok) {
-            // (class launches: the 64x64 class first, the small sizes last)
-            hipStream_t hs = (hipStream_t)stream;
+            if (ok) {
+                hipStream_t hs = (hipStream_t)stream;
+                if (int rc = tab[3].flush([&](const FrameDesc& fd, uint32_t total) { return launch_enc_frame_one(&fd, total, is_16bit, hs); })) return rc;      // (svt_hip_frame.hip)
+                // (class launches: the 64x64 class first, the small sizes last)
 #define FRAME_LAUNCH(C)                                                                                                                         \
-            if (fd[C].ngroups) {                                                                                                                \
-                if (is_16bit) hipLaunchKernelGGL((enc_frame_kernel<uint16_t, 10, C>), dim3(total[C]), dim3(256), 0, hs, fd[C]);                 \
-                else hipLaunchKernelGGL((enc_frame_kernel<uint8_t, 8, C>), dim3(total[C]), dim3(256), 0, hs, fd[C]);                            \
-                if (int rc = launch_status("enc_frame")) return rc;                                                                             \
-            }
-            if (fd[3].ngroups) return launch_enc_frame_one(&fd[3], total[3], is_16bit, hs);      // (svt_hip_frame.hip)
-            FRAME_LAUNCH(2) FRAME_LAUNCH(1) FRAME_LAUNCH(0)
+                if (int rc = tab[C].flush([&](const FrameDesc& fd, uint32_t total) {                                                            \
+                        if (is_16bit) hipLaunchKernelGGL((enc_frame_kernel<uint16_t, 10, C>), dim3(total), dim3(256), 0, hs, fd);               \
+                        else hipLaunchKernelGGL((enc_frame_kernel<uint8_t, 8, C>), dim3(total), dim3(256), 0, hs, fd);                          \
+                        return launch_status("enc_frame");                                                                                      \
+                    })) return rc;
+                FRAME_LAUNCH(2) FRAME_LAUNCH(1) FRAME_LAUNCH(0)
 #undef FRAME_LAUNCH
-            return SVT_HIP_OK;
+                return SVT_HIP_OK;
+            }
         }
     }
     if (int rc = t_fan.ensure()) return rc;
@@ -623,14 +607,9 @@ extern "C" int svt_hip_encode_recon_frame(const svt_hip_frame_group* groups, int
     // largest groups first, round-robin: the long kernels start early and the small ones fill in beside them
     int order[256];
     const int ng = ngroups;                        // <= 256, checked with the arguments
-    for (int i = 0; i < ng; i++) order[i] = i;
-    for (int i = 1; i < ng; i++) {                 // insertion sort by work (pixels), descending
-        const int v = order[i];
-        const size_t wv = (size_t)groups[v].nblocks * kTxW[groups[v].tx_size] * kTxH[groups[v].tx_size];
-        int j = i - 1;
-        while (j >= 0 && (size_t)groups[order[j]].nblocks * kTxW[groups[order[j]].tx_size] * kTxH[groups[order[j]].tx_size] < wv) { order[j + 1] = order[j]; j--; }
-        order[j + 1] = v;
-    }
+    order_largest_first(order, ng, [&](int i) {      // by work (pixels); an empty group's size is not validated
+        return groups[i].nblocks ? (size_t)groups[i].nblocks * kTxW[groups[i].tx_size] * kTxH[groups[i].tx_size] : (size_t)0;
+    });
     for (int k = 0; k < ng && rc == SVT_HIP_OK; k++) {
         const svt_hip_frame_group& G = groups[order[k]];
         if (G.nblocks == 0) continue;
@@ -667,7 +646,7 @@ extern "C" int svt_hip_fwd_quant_batch(const int16_t* d_residual, size_t nblocks
         return set_err(SVT_HIP_ERR_INVALID, "NULL argument");
     if (!txfm_allowed(tx_size, tx_type)) return set_err(SVT_HIP_ERR_INVALID, "tx_size %d / tx_type %d not defined by the reference", tx_size, tx_type);
     const int w = kTxW[tx_size], h = kTxH[tx_size];
-    const int pels = w * h, ls = pels > 1024 ? 2 : (pels > 256 ? 1 : 0);
+    const int ls = tx_log_scale(tx_size);
     hipStream_t s = (hipStream_t)stream;
     const QParams qp = make_qparams(zbin, round, quant, quant_shift, dequant, ls);
     if (tx_size == SVT_TX_32X32 && bd == 8 && qp.fast_ok && ((uintptr_t)d_residual & 15) == 0 &&

@@ -426,3 +426,57 @@ def test_malloc_spread_allocates_usable_buffers_far_apart(dsp, pkg):
     assert len(ts) == 2 and ts[0].data_ptr() != ts[1].data_ptr() and ts[0].is_cuda
     ts[0].fill_(3); ts[1].fill_(5)
     assert int(ts[0].sum()) == 3 << 20 and int(ts[1].sum()) == 5 << 20
+
+
+def test_level_maps_of_more_groups_than_one_launch_holds(dsp, pkg):
+    """svt_hip_encode_recon_frame_ex with level maps for 49 luma groups: one more than the level launch's table holds
+    (LEVELS_MAX_GROUPS = 48), so the maps take a second launch whose table starts again from its group's own workgroup count.  48
+    groups of three 4x4 blocks and one of two 32x32 blocks; the level buffers of groups 7 and 48 are 4-byte aligned with a pitch that
+    is no multiple of 16 (4-byte stores), every other one is 16-byte aligned (16-byte stores).  Every block's levels against the
+    oracle's av1_txb_init_levels of the call's own qcoeff, itself against the oracle's forward chain."""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(13656)
+    W, H = 128, 64
+    src = rng.integers(0, 256, size=(H, W), dtype=np.uint8)
+    pred = np.clip(src.astype(np.int32) + rng.integers(-48, 49, size=src.shape), 0, 255).astype(np.uint8)
+    qrow = {k: v[60].copy() for k, v in pkg.tables.quant_tables(8).items()}
+    d_src, d_pred = torch.from_numpy(src).to(DEV), torch.from_numpy(pred).to(DEV)
+    d_recon = d_pred.clone()
+    cells = rng.permutation(256)[:144].reshape(48, 3)              # 4x4 cells of the left 64 x 64 samples, three per group
+    groups = []
+    for gi in range(49):
+        if gi == 20:
+            ts, side, xy = 3, 32, np.array([64, 96], np.uint32)
+        else:
+            c = cells[gi - (gi > 20)]
+            ts, side, xy = 0, 4, ((c % 16) * 4 | ((c // 16) * 4) << 16).astype(np.uint32)
+        n = xy.size
+        size = (side + 4) * (side + 6) + 16
+        narrow = gi in (7, 48)
+        pitch = size + 4 if narrow else (size + 15) // 16 * 16
+        raw = torch.full((n * pitch + 32,), 0x5a, dtype=torch.uint8, device=DEV)
+        off = (-raw.data_ptr()) % 16 + (4 if narrow else 0)
+        levels = raw[off:off + n * pitch].view(n, pitch)
+        assert levels.data_ptr() % 16 == (4 if narrow else 0) and (pitch % 16 != 0) == narrow
+        groups.append(dict(src=d_src, src_stride=W, pred=d_pred, pred_stride=W, recon=d_recon, recon_stride=W, tx_size=ts, tx_type=0,
+                           xy=torch.from_numpy(xy.view(np.int32)).to(DEV), iscan=torch.from_numpy(pkg.tables.scan_tables(ts, 0)[1]).to(DEV),
+                           qcoeff=torch.empty((n, side * side), dtype=torch.int32, device=DEV), eob=torch.zeros(n, dtype=torch.int16, device=DEV),
+                           levels=levels, raw=raw, side=side, size=size))
+    dsp.encode_recon_frame_ex(dsp.make_frame_groups(groups), qrow, len(groups), None, 0, dsp.make_frame_levels([g["levels"] for g in groups]))
+    torch.cuda.synchronize()
+    for gi, g in enumerate(groups):
+        side, size = g["side"], g["size"]
+        q, lv = g["qcoeff"].cpu().numpy(), g["levels"].cpu().numpy()
+        xy = g["xy"].cpu().numpy().view(np.uint32)
+        assert (lv[:, size:] == 0x5a).all(), gi                     # the slack of every block is untouched
+        for i in range(q.shape[0]):
+            x, y = int(xy[i] & 0xffff), int(xy[i] >> 16)
+            rc = np.zeros(1024, np.int32); rq = np.zeros(1024, np.int32); rdq = np.zeros(1024, np.int32); reob = np.zeros(1, np.uint16)
+            at = lambda p: ctypes.c_void_p(p.ctypes.data + y * W + x)
+            O.svt_oracle_fwd_quant_planes(at(src), W, at(pred), W, 0, 8, g["tx_size"], 0, ptr(qrow["zbin"]), ptr(qrow["round"]), ptr(qrow["quant"]),
+                                          ptr(qrow["quant_shift"]), ptr(qrow["dequant"]), ptr(rc), ptr(rq), ptr(rdq), ptr(reob), None, None)
+            assert np.array_equal(q[i], rq[:side * side]), (gi, i)
+            one = np.full(lv.shape[1], 0x5a, np.uint8)
+            O.svt_oracle_txb_init_levels(ptr(np.ascontiguousarray(q[i])), ctypes.c_int(side), ctypes.c_int(side), ctypes.c_void_p(one.ctypes.data + 2 * (side + 4)))
+            assert np.array_equal(lv[i], one), (gi, i)
+    assert any(g["qcoeff"].any().item() for g in groups)

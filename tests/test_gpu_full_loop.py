@@ -250,3 +250,33 @@ def test_argument_validation_launches_nothing(dsp):
         assert rc == -2, (i, rc)
         assert bool((first["dist"].view(torch.uint8) == SENT).all()) and bool((first["eob"].view(torch.uint8) == SENT).all()), i
     assert dsp.full_loop_frame([good()], qrow, 2) == -2                                              # flavour
+
+
+def test_more_groups_of_one_class_than_one_launch_holds(dsp):
+    """17 groups of 8x8 blocks, one transform type: one more than a launch's table holds (FL_MAX_GROUPS = 16), so the call takes a
+    second launch whose table starts again from its group's own workgroup count.  Sixteen groups of 5 blocks and one of 40 (two
+    workgroups of 32 blocks), distinct data per group; both distortion flavours and the eob against the CPU oracle."""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(13655)
+    s, t = 1, 0
+    qrow = qrow_of(110)
+    isc = svtlibs.scan_tables(s, t)[1]
+    groups, data = [], []
+    for gi in range(17):
+        n = 40 if gi == 3 else 5
+        sb = rng.integers(0, 256, size=(n, 8, 8), dtype=np.uint8)
+        pb = np.clip(sb.astype(np.int16) + rng.integers(-30, 31, size=(n, 8, 8)), 0, 255).astype(np.uint8)
+        groups.append(dict(src=torch.from_numpy(sb).to(DEV), pred=torch.from_numpy(pb).to(DEV), nblocks=n, tx_size=s, tx_types=[t],
+                           iscan=iscans(s, [t]), **outputs(n, s, 1, False)))
+        data.append((sb, pb))
+    run(dsp, groups, qrow, 0)
+    dist_c = [g["dist"].cpu().numpy().view(np.uint64).copy() for g in groups]
+    eob_c = [g["eob"].cpu().numpy().copy() for g in groups]
+    run(dsp, groups, qrow, 1)
+    for gi, (g, (sb, pb)) in enumerate(zip(groups, data)):
+        da_all, eob = g["dist"].cpu().numpy().view(np.uint64), g["eob"].cpu().numpy()
+        for b in range(g["nblocks"]):
+            dc, da, e, _, _ = oracle_chain(O, s, t, qrow, sb[b], pb[b], isc)
+            assert [int(v) for v in dist_c[gi][b, 0]] == dc, (gi, b)
+            assert [int(v) for v in da_all[b, 0]] == da, (gi, b)
+            assert int(eob_c[gi][b, 0]) == e and int(eob[b, 0]) == e, (gi, b)

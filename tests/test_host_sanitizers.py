@@ -79,3 +79,14 @@ def test_tsan_concurrent_readers_and_table_builders(tsan_exe, tmp_path):
 
 def test_tsan_frames_with_refused_threads(tsan_exe, tmp_path):
     assert "ok" in run(tsan_exe, ["frames", str(tmp_path)])
+
+
+@pytest.mark.parametrize("san_flags", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]], ids=["plain", "asan_ubsan"])
+def test_group_table_builder(tmp_path, san_flags):
+    """the host half of csrc/group_table.h (the builder of every whole-picture call's group table) as a stand-alone program with a
+    recording launcher: flush at a full table and at 2^31 - 1 workgroups, empty flush, stable largest-first order, running wg_end"""
+    exe = str(tmp_path / "group_table_host")
+    pr = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror"] + san_flags +
+                        [os.path.join(ROOT, "tests", "c", "group_table_host.cpp"), "-o", exe], capture_output=True, text=True)
+    assert pr.returncode == 0, pr.stderr[-4000:]
+    assert run(exe, []).strip() == "ok"
