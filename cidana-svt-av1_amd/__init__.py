@@ -164,7 +164,30 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_motion_estimate_frame_scratch_bytes.restype = c_size_t
     L.svt_hip_motion_estimate_frame.argtypes = [c_void_p] * 4 + [c_uint32] + [c_void_p] * 6 + [c_size_t, c_void_p]
     L.svt_hip_motion_estimate_frame.restype = c_int
+    L.svt_hip_coeff_rate_frame.argtypes = [c_void_p, c_int, c_void_p]
+    L.svt_hip_coeff_rate_frame.restype = c_int
+    L.svt_hip_coeff_cost_index.argtypes = [c_int, c_void_p, c_void_p]
+    L.svt_hip_coeff_cost_index.restype = c_int
     return L
+
+
+COEFF_COST_WORDS, EOB_COST_WORDS = 529, 22          # one LV_MAP_COEFF_COST / LV_MAP_EOB_COST as int32 words
+
+
+def coeff_cost_index(tx_size: int):
+    """(txs_ctx, eob_multi_size) of a transform size: which coeffFacBits[txs_ctx][plane] / eobFracBits[eob_multi_size][plane] entry
+    av1_cost_coeffs_txb reads (the mirror of svt_hip_coeff_cost_index: (txsize_sqr_map + txsize_sqr_up_map + 1) >> 1, txsize_log2_minus4)"""
+    lw, lh = TX_W[tx_size].bit_length() - 3, TX_H[tx_size].bit_length() - 3
+    return (min(lw, lh) + max(lw, lh) + 1) >> 1, (min(TX_W[tx_size], 32) * min(TX_H[tx_size], 32)).bit_length() - 5
+
+
+def coeff_cost_index_lib(tx_size: int):
+    """the same pair from the library's host helper (svt_hip_coeff_cost_index; no device needed)"""
+    a, b = c_int(-1), c_int(-1)
+    rc = load_library().svt_hip_coeff_cost_index(tx_size, ctypes.addressof(a), ctypes.addressof(b))
+    if rc != SVT_HIP_OK:
+        raise SvtHipError(f"svt_hip_coeff_cost_index = {rc}")
+    return a.value, b.value
 
 
 class MeFrameParams(ctypes.Structure):
@@ -1114,6 +1137,58 @@ class SvtHipDsp:
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         return self.lib.svt_hip_full_loop_frame(groups, n, flavour, tabs[0].ctypes.data, tabs[1].ctypes.data, tabs[2].ctypes.data,
                                                 tabs[3].ctypes.data, tabs[4].ctypes.data, self._stream())
+
+    # -- coefficient rate of quantised blocks: av1_cost_coeffs_txb / av1_cost_skip_txb per (block, transform type) ------------------
+    class CoeffRateGroup(ctypes.Structure):
+        _fields_ = [("tx_size", c_int32), ("ntypes", c_int32), ("tx_types", ctypes.c_uint8 * 16), ("nblocks", c_uint32),
+                    ("d_qcoeff", c_void_p), ("d_eob", c_void_p), ("d_iscan", c_void_p), ("d_txb_skip_ctx", c_void_p),
+                    ("d_dc_sign_ctx", c_void_p), ("d_type_bits", c_void_p), ("d_coeff_cost", c_void_p), ("d_eob_cost", c_void_p),
+                    ("d_bits", c_void_p)]
+
+    def make_coeff_rate_groups(self, groups):
+        """groups: list of dicts with tensors qcoeff (int32 [n, ntypes, NC]), eob (int16 [n, ntypes]) and iscan (int16 [ntypes, NC]) as in
+        the full-loop groups, txb_skip_ctx / dc_sign_ctx (uint8 [n]), optional type_bits (int32 [n, ntypes]), coeff_cost (int32 [529]),
+        eob_cost (int32 [22]), bits (int64 [n, ntypes]), plus nblocks, tx_size, tx_types.  -> ctypes array (keep the tensors alive!)"""
+        arr = (self.CoeffRateGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+            types = list(g["tx_types"])
+            tt = (ctypes.c_uint8 * 16)(*(types + [0] * (16 - len(types)))[:16])
+            arr[i] = self.CoeffRateGroup(g["tx_size"], g.get("ntypes", len(types)), tt, g["nblocks"], P("qcoeff"), P("eob"), P("iscan"),
+                                         P("txb_skip_ctx"), P("dc_sign_ctx"), P("type_bits"), P("coeff_cost"), P("eob_cost"), P("bits"))
+        return arr
+
+    def coeff_rate_frame(self, groups):
+        """svt_hip_coeff_rate_frame.  groups: a ctypes array from make_coeff_rate_groups, or the list of dicts itself; a dict without
+        "bits" gets a fresh int64 [nblocks, ntypes] tensor there (preallocate it to keep the call allocation-free, e.g. under graph
+        capture).  -> the library's return code"""
+        if isinstance(groups, list):
+            t = self.torch
+            for g in groups:
+                if g.get("bits") is None and g.get("qcoeff") is not None:
+                    g["bits"] = t.empty((g["nblocks"], g.get("ntypes", len(g["tx_types"]))), dtype=t.int64, device=g["qcoeff"].device)
+            keep = groups
+            groups = self.make_coeff_rate_groups(keep)
+            n = len(keep)
+        else:
+            n = len(groups)
+        return self.lib.svt_hip_coeff_rate_frame(groups, n, self._stream())
+
+    def coeff_rate(self, qcoeff, eob, tx_size, tx_types, txb_skip_ctx, dc_sign_ctx, coeff_cost, eob_cost, type_bits=None, iscan=None, bits=None):
+        """One group: qcoeff int32 [n, T, NC], eob int16 [n, T] (what full_loop returns), contexts uint8 [n], cost tables int32 [529] / [22]
+        on the device; iscan defaults to the reference's scans; bits: optional preallocated int64 [n, T].  -> bits"""
+        t = self.torch
+        n, T = qcoeff.shape[0], len(tx_types)
+        if iscan is None:
+            import numpy as np
+            iscan = t.from_numpy(np.stack([tables.scan_tables(tx_size, ty)[1] for ty in tx_types]).astype(np.int16)).to(qcoeff.device)
+        if bits is None:
+            bits = t.empty((n, T), dtype=t.int64, device=qcoeff.device)
+        assert bits.is_contiguous() and bits.numel() == n * T and bits.element_size() == 8
+        g = dict(qcoeff=qcoeff, eob=eob, iscan=iscan, txb_skip_ctx=txb_skip_ctx, dc_sign_ctx=dc_sign_ctx, type_bits=type_bits,
+                 coeff_cost=coeff_cost, eob_cost=eob_cost, bits=bits, nblocks=n, tx_size=tx_size, tx_types=tx_types)
+        self._check(self.coeff_rate_frame([g]), "svt_hip_coeff_rate_frame")
+        return bits
 
     # -- mode-decision fast loop, intra candidates: prediction -> distortion per (block, candidate) ------------------------------
     FAST_SAD, FAST_SSD = 0, 1

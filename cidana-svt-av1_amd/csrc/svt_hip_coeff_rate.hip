@@ -1,0 +1,85 @@
+// svt_hip_coeff_rate.hip — svt_hip_coeff_rate_frame: the coefficient rate of quantised blocks (coeff_rate_kernel, kernel_coeff_rate.h),
+// one launch per CR_MAX_GROUPS groups; svt_hip_coeff_cost_index, the host helper that names a size's cost tables.
+#include "host_common.h"
+#include "kernel_coeff_rate.h"
+
+using namespace svtdev;
+using namespace svthost;
+
+static int log2_of(int v) { int l = 0; while ((1 << l) < v) l++; return l; }
+static int packed_side(int v) { return v < 32 ? v : 32; }
+static uint64_t pairs_of(const svt_hip_coeff_rate_group& G) { return (uint64_t)G.nblocks * (uint64_t)G.ntypes; }
+// (block, type) pairs per wave-unit: 64 / min(quads, 64)
+static uint32_t pairs_per_unit(int tx_size) {
+    const int quads = packed_side(kTxW[tx_size]) * packed_side(kTxH[tx_size]) / 4;
+    return (uint32_t)(quads < 64 ? 64 / quads : 1);
+}
+// wave-units per wave: 1 until the group has 2048 workgroups of its own (8 per CU), then up to CR_ITERS, which spreads the staging of
+// the cost tables over more work
+static uint32_t coeff_rate_iters(uint64_t units) {
+    const uint64_t it = units / (uint64_t)(CR_WAVES * 2048);
+    return (uint32_t)(it < 1 ? 1 : (it > (uint64_t)CR_ITERS ? (uint64_t)CR_ITERS : it));
+}
+
+// txs_ctx = (txsize_sqr_map + txsize_sqr_up_map + 1) >> 1 (TX_4X4 = 0 .. TX_64X64 = 4) and txsize_log2_minus4, from the sides
+extern "C" int svt_hip_coeff_cost_index(int tx_size, int* txs_ctx, int* eob_multi_size) {
+    if (tx_size < 0 || tx_size >= SVT_TX_SIZES_ALL) return set_err(SVT_HIP_ERR_INVALID, "bad tx_size %d", tx_size);
+    const int lw = log2_of(kTxW[tx_size]), lh = log2_of(kTxH[tx_size]);
+    const int lo = (lw < lh ? lw : lh) - 2, hi = (lw > lh ? lw : lh) - 2;
+    if (txs_ctx) *txs_ctx = (lo + hi + 1) >> 1;
+    if (eob_multi_size) *eob_multi_size = log2_of(packed_side(kTxW[tx_size]) * packed_side(kTxH[tx_size])) - 4;
+    return SVT_HIP_OK;
+}
+
+static int coeff_rate_check(const svt_hip_coeff_rate_group* groups, int ngroups) {
+    if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
+    for (int g = 0; g < ngroups; g++) {
+        const svt_hip_coeff_rate_group& G = groups[g];
+        if (G.tx_size < 0 || G.tx_size >= SVT_TX_SIZES_ALL) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_size %d", g, G.tx_size);
+        if (G.ntypes < 1 || G.ntypes > CR_MAX_TYPES) return set_err(SVT_HIP_ERR_INVALID, "group %d: ntypes %d (1 .. 16)", g, G.ntypes);
+        unsigned seen = 0;
+        for (int t = 0; t < G.ntypes; t++) {
+            const int ty = G.tx_types[t];
+            if (!txfm_allowed(G.tx_size, ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d not defined for tx_size %d", g, ty, G.tx_size);
+            if (seen & (1u << ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d listed twice", g, ty);
+            seen |= 1u << ty;
+        }
+        if (G.nblocks == 0) continue;
+        if (pairs_of(G) > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "group %d: nblocks * ntypes too large", g);
+        if (!G.d_qcoeff || !G.d_eob || !G.d_iscan || !G.d_txb_skip_ctx || !G.d_dc_sign_ctx || !G.d_coeff_cost || !G.d_eob_cost || !G.d_bits)
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL member", g);
+        if (((uintptr_t)G.d_qcoeff & 15) || ((uintptr_t)G.d_iscan & 7) || ((uintptr_t)G.d_bits & 7) || ((uintptr_t)G.d_eob & 1) ||
+            ((uintptr_t)G.d_type_bits & 3) || ((uintptr_t)G.d_coeff_cost & 3) || ((uintptr_t)G.d_eob_cost & 3))
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: misaligned buffer (d_qcoeff 16 bytes, d_iscan / d_bits 8, the int32 tables 4, d_eob 2)", g);
+    }
+    return SVT_HIP_OK;
+}
+
+extern "C" int svt_hip_coeff_rate_frame(const svt_hip_coeff_rate_group* groups, int ngroups, void* stream) {
+    if (int rc = require_init()) return rc;
+    if (int rc = coeff_rate_check(groups, ngroups)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    GroupTable<CoeffRateDesc, CR_MAX_GROUPS> tab;
+    auto launch = [&](const CoeffRateDesc& fd, uint32_t total) -> int {
+        hipLaunchKernelGGL(coeff_rate_kernel, dim3(total), dim3(CR_THREADS), 0, s, fd);
+        return launch_status("coeff_rate");
+    };
+    for (int g = 0; g < ngroups; g++) {
+        const svt_hip_coeff_rate_group& G = groups[g];
+        if (G.nblocks == 0) continue;
+        const uint32_t ppu = pairs_per_unit(G.tx_size);
+        const uint64_t units = (pairs_of(G) + ppu - 1) / ppu;
+        const uint32_t iters = coeff_rate_iters(units), per_wg = (uint32_t)CR_WAVES * iters;
+        CoeffRateGroupDev* D = tab.add((uint32_t)((units + per_wg - 1) / per_wg), launch);
+        if (!D) return tab.rc;
+        const int w = kTxW[G.tx_size], h = kTxH[G.tx_size];
+        D->qcoeff = G.d_qcoeff; D->eob = G.d_eob; D->iscan = G.d_iscan; D->skip_ctx = G.d_txb_skip_ctx; D->dc_ctx = G.d_dc_sign_ctx;
+        D->type_bits = G.d_type_bits; D->coeff_cost = G.d_coeff_cost; D->eob_cost = G.d_eob_cost; D->bits = (unsigned long long*)G.d_bits;
+        D->nblocks = G.nblocks; D->ntypes = G.ntypes;
+        D->bwl = (uint8_t)log2_of(packed_side(w)); D->bhl = (uint8_t)log2_of(packed_side(h));
+        D->shape = w == h ? 0 : (w > h ? 1 : 2);
+        D->iters = (uint8_t)iters;
+        memcpy(D->types, G.tx_types, sizeof(D->types));
+    }
+    return tab.flush(launch);
+}

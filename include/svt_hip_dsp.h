@@ -628,8 +628,9 @@ int svt_hip_picture_full_distortion32_batch(const int32_t *d_coeff, size_t coeff
  *                                                                   eob 0: the cbf_zero kernel, {sum c^2, sum c^2}; flavour as in
  *                                                                   svt_hip_picture_full_distortion32_batch)
  *   dist[i] = RIGHT_SIGNED_SHIFT(dist[i] + three_quad_energy, (1 - av1_get_tx_scale(tx_size)) * 2)      (:829-835, :1062-1068)
- * coeff and dqcoeff never leave the device's registers unless d_qcoeff / d_dqcoeff ask for them.  Left to the caller: the rate
- * (entropy code), the skip of a non-DCT type whose eob is 0 (:1034) and the allowed type set (:952-984).
+ * coeff and dqcoeff never leave the device's registers unless d_qcoeff / d_dqcoeff ask for them.  The rate of the coefficients
+ * (Av1TuEstimateCoeffBits) is svt_hip_coeff_rate_frame below, which reads d_qcoeff / d_eob where this call leaves them.  Left to
+ * the caller: the skip of a non-DCT type whose eob is 0 (:1034) and the allowed type set (:952-984).
  * Blocks: d_*_xy[b] = x | y << 16 on a plane with the given row stride (in samples), or NULL: dense W * H samples per block (many
  * candidates of one source block each repeat its origin in d_src_xy).  d_iscan: ntypes consecutive iscans of min(W,32) * min(H,32)
  * entries in tx_types order (8-byte aligned); d_dist / d_qcoeff / d_dqcoeff 16-byte aligned.  One quantiser row set per call (the MD
@@ -650,6 +651,43 @@ typedef struct svt_hip_full_loop_group {
 int svt_hip_full_loop_frame(const svt_hip_full_loop_group *groups, int ngroups, int flavour,
                             const int16_t *zbin, const int16_t *round, const int16_t *quant,
                             const int16_t *quant_shift, const int16_t *dequant, void *stream);
+
+/* The coefficient rate of quantised blocks, what ProductFullLoopTxSearch gets from Av1TuEstimateCoeffBits (EbFullLoop.c:1070-1098):
+ * per (block, type) of a group
+ *   eob > 0   av1_cost_coeffs_txb (EbRateDistortionCost.c:412-519) WITHOUT its Av1TransformTypeRateEstimation term (:454-461), plus
+ *             d_type_bits[block][type] when that array is given (the caller's transform-type rate)
+ *   eob == 0  av1_cost_skip_txb (:401-410): txb_skip_cost[txb_skip_ctx][1]; no coefficient is read
+ * as the reference's int32 cost widened to uint64_t.  d_qcoeff / d_eob / d_iscan / tx_types are svt_hip_full_loop_group's, as that
+ * call writes and reads them, so the full loop feeds this call without a host copy.  The level map (av1_txb_init_levels), the
+ * coefficient contexts (av1_get_nz_map_contexts; the reference has only an SSE2 implementation of it, the kernel follows the AV1
+ * specification's get_nz_map_ctx) and get_br_ctx are computed on the device and never stored.
+ * Cost tables are the caller's data, device-resident: d_coeff_cost is ONE LV_MAP_COEFF_COST as its 529 int32 words in declaration
+ * order (EbMdRateEstimation.h:34-41: txb_skip_cost[13][2], base_eob_cost[4][3], base_cost[42][4], eob_extra_cost[22][2],
+ * dc_sign_cost[3][2], lps_cost[21][13]), d_eob_cost ONE LV_MAP_EOB_COST ([2][11]): coeffFacBits[txs_ctx][plane] and
+ * eobFracBits[eob_multi_size][plane] of the group's size, the two indices from svt_hip_coeff_cost_index (a host helper that needs
+ * no device).  Costs must keep a block's sum inside int32, as in the reference.
+ * Every argument, empty groups' tx_size / types included, is validated before the first launch (SVT_HIP_ERR_INVALID: a bad size, a
+ * type not defined for it or listed twice, a NULL member other than d_type_bits, nblocks * ntypes above 2^31 - 1, d_qcoeff not
+ * 16-byte, d_iscan / d_bits not 8-byte, an int32 table not 4-byte aligned).  The contexts are device data and are clamped there
+ * (d_txb_skip_ctx to 0 .. 12, d_dc_sign_ctx to 0 .. 2, an eob to the coefficient count): an out-of-range value gives an unspecified
+ * cost for its block and does not fault.  The call only enqueues work (one launch per 32 groups), allocates nothing and can be
+ * captured into a HIP graph. */
+typedef struct svt_hip_coeff_rate_group {
+    int32_t tx_size; int32_t ntypes; uint8_t tx_types[16];
+    uint32_t nblocks;
+    const int32_t *d_qcoeff;      /* [nblocks][ntypes][min(W,32)*min(H,32)]: svt_hip_full_loop_group.d_qcoeff as written */
+    const uint16_t *d_eob;        /* [nblocks][ntypes] */
+    const int16_t *d_iscan;       /* ntypes iscans, as in the full-loop group */
+    const uint8_t *d_txb_skip_ctx, *d_dc_sign_ctx;   /* [nblocks]; 0..12 and 0..2 */
+    const int32_t *d_type_bits;   /* optional [nblocks][ntypes], added where eob > 0 (the caller's transform-type rate); NULL: 0 */
+    const int32_t *d_coeff_cost;  /* 529 words, one LV_MAP_COEFF_COST */
+    const int32_t *d_eob_cost;    /* 22 words, one LV_MAP_EOB_COST */
+    uint64_t *d_bits;             /* [nblocks][ntypes] */
+} svt_hip_coeff_rate_group;
+int svt_hip_coeff_rate_frame(const svt_hip_coeff_rate_group *groups, int ngroups, void *stream);
+/* HOST: which coeffFacBits / eobFracBits entry a transform size reads: txs_ctx = (txsize_sqr_map + txsize_sqr_up_map + 1) >> 1 and
+ * eob_multi_size = txsize_log2_minus4 (either pointer may be NULL).  SVT_HIP_OK or SVT_HIP_ERR_INVALID (a bad tx_size). */
+int svt_hip_coeff_cost_index(int tx_size, int *txs_ctx, int *eob_multi_size);
 
 /* Open-loop intra search: open_loop_intra_search_sb, EbMotionEstimation.c:8694-8850,
  * for all blocks of ONE size of a picture (or of many pictures' worth of blocks) in one call.
