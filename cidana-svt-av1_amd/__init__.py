@@ -360,7 +360,7 @@ class SvtHipDsp:
     def pack64(self, coeff, tx_size, want_energy=True):
         t = self.torch
         n = coeff.shape[0]
-        energy = t.zeros(n, dtype=t.int64, device=coeff.device) if want_energy else None
+        energy = t.empty(n, dtype=t.int64, device=coeff.device) if want_energy else None
         self._check(self.lib.svt_hip_pack64_batch(self._p(coeff), self._p(energy) if want_energy else None, n, tx_size,
                                                    self._stream()), "svt_hip_pack64_batch")
         return energy
@@ -389,7 +389,7 @@ class SvtHipDsp:
         n, nc = coeff.shape
         q = t.empty_like(coeff)
         dq = t.empty_like(coeff)
-        eob = t.zeros(n, dtype=t.int16, device=coeff.device)
+        eob = t.empty(n, dtype=t.int16, device=coeff.device)
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         self._check(self.lib.svt_hip_quantize_b_batch(self._p(coeff), nc, skip_block, tabs[0].ctypes.data,
                                                        tabs[1].ctypes.data, tabs[2].ctypes.data, tabs[3].ctypes.data,
@@ -406,8 +406,8 @@ class SvtHipDsp:
         nc = min(TX_W[tx_size], 32) * min(TX_H[tx_size], 32)
         if outs is None:
             outs = (t.empty((n, nc), dtype=t.int32, device=src.device), t.empty((n, nc), dtype=t.int32, device=src.device),
-                    t.empty((n, nc), dtype=t.int32, device=src.device), t.zeros(n, dtype=t.int16, device=src.device),
-                    t.zeros(n, dtype=t.int32, device=src.device))
+                    t.empty((n, nc), dtype=t.int32, device=src.device), t.empty(n, dtype=t.int16, device=src.device),
+                    t.empty(n, dtype=t.int32, device=src.device))
         co, q, dq, eob, sad = outs
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         self._check(self.lib.svt_hip_fwd_quant_sad_batch(self._p(src), self._p(pred), n, tx_size, tx_type,
@@ -428,8 +428,8 @@ class SvtHipDsp:
         mk = lambda: t.empty((n, nc), dtype=t.int32, device=src.device)
         co, dq = (mk(), mk()) if keep_coeff else (None, None)
         q = outs[0] if outs else mk()
-        eob = outs[1] if outs else t.zeros(n, dtype=t.int16, device=src.device)
-        sad = t.zeros(n, dtype=t.int32, device=src.device) if want_sad else None
+        eob = outs[1] if outs else t.empty(n, dtype=t.int16, device=src.device)
+        sad = t.empty(n, dtype=t.int32, device=src.device) if want_sad else None
         recon = outs[2] if outs else t.empty_like(pred)
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         self._check(self.lib.svt_hip_encode_recon_batch(self._p(src), self._p(pred), n, tx_size, tx_type,
@@ -452,8 +452,8 @@ class SvtHipDsp:
         mk = lambda: t.empty((n, nc), dtype=t.int32, device=src.device)
         co, dq = (mk(), mk()) if keep_coeff else (None, None)
         q = mk()
-        eob = t.zeros(n, dtype=t.int16, device=src.device)
-        sad = t.zeros(n, dtype=t.int32, device=src.device) if want_sad else None
+        eob = t.empty(n, dtype=t.int16, device=src.device)
+        sad = t.empty(n, dtype=t.int32, device=src.device) if want_sad else None
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         self._check(self.lib.svt_hip_encode_recon_planes_batch(self._p(src), src_stride, self._p(pred), pred_stride, self._p(recon),
                                                                 recon_stride, self._p(xy), n, is16, bd, tx_size, tx_type,
@@ -470,7 +470,7 @@ class SvtHipDsp:
         """a, b: uint8 [n, H, W] dense -> int32 [n] (uint32 values)"""
         t = self.torch
         n, h, w = a.shape
-        out = t.zeros(n, dtype=t.int32, device=a.device)
+        out = t.empty(n, dtype=t.int32, device=a.device)
         self._check(self.lib.svt_hip_sad_batch(self._p(a), w, w * h, self._p(b), w, w * h, w, h, self._p(out), n,
                                                 self._stream()), "svt_hip_sad_batch")
         return out
@@ -478,7 +478,7 @@ class SvtHipDsp:
     def sse(self, a, b):
         t = self.torch
         n, h, w = a.shape
-        out = t.zeros(n, dtype=t.int64, device=a.device)
+        out = t.empty(n, dtype=t.int64, device=a.device)
         self._check(self.lib.svt_hip_sse_batch(self._p(a), w, w * h, self._p(b), w, w * h, w, h, self._p(out), n,
                                                 self._stream()), "svt_hip_sse_batch")
         return out
@@ -500,9 +500,9 @@ class SvtHipDsp:
         _, rh, rw = ref.shape
         rs = rw if ref_stride is None else ref_stride
         rraw = rw if ref_stride_raw is None else ref_stride_raw
-        best = t.zeros(n, dtype=t.int64, device=src.device)
-        x = t.zeros(n, dtype=t.int16, device=src.device)
-        y = t.zeros(n, dtype=t.int16, device=src.device)
+        best = t.empty(n, dtype=t.int64, device=src.device)
+        x = t.empty(n, dtype=t.int16, device=src.device)
+        y = t.empty(n, dtype=t.int16, device=src.device)
         self._check(self.lib.svt_hip_sad_search_batch(self._p(src), w, w * h, self._p(ref), rs, rraw, rw * rh, w, h,
                                                        search_w, search_h, self._p(best), self._p(x), self._p(y), n,
                                                        self._stream()), "svt_hip_sad_search_batch")
@@ -514,9 +514,9 @@ class SvtHipDsp:
         block and of the search window origin. -> best_sad int64, x int16, y int16"""
         t = self.torch
         n = src_offsets.shape[0]
-        best = t.zeros(n, dtype=t.int64, device=src_plane.device)
-        x = t.zeros(n, dtype=t.int16, device=src_plane.device)
-        y = t.zeros(n, dtype=t.int16, device=src_plane.device)
+        best = t.empty(n, dtype=t.int64, device=src_plane.device)
+        x = t.empty(n, dtype=t.int16, device=src_plane.device)
+        y = t.empty(n, dtype=t.int16, device=src_plane.device)
         self._check(self.lib.svt_hip_sad_search_planes_batch(self._p(src_plane), src_stride, self._p(src_offsets),
                                                               self._p(ref_plane), ref_stride,
                                                               ref_stride if ref_stride_raw is None else ref_stride_raw,
@@ -531,8 +531,8 @@ class SvtHipDsp:
         t = self.torch
         n = src_offsets.shape[0]
         if best_sad is None:
-            best_sad = t.full((n, 85), self.MAX_SAD_VALUE, dtype=t.int32, device=src_plane.device)
-            best_mv = t.zeros((n, 85), dtype=t.int32, device=src_plane.device)
+            best_sad = t.full((n, 85), self.MAX_SAD_VALUE, dtype=t.int32, device=src_plane.device)     # IN/OUT running bests: the caller initialises them
+            best_mv = t.zeros((n, 85), dtype=t.int32, device=src_plane.device)                          # IN/OUT
         self._check(self.lib.svt_hip_me_sb_search_planes_batch(self._p(src_plane), src_stride, self._p(src_offsets),
                                                                 self._p(ref_plane), ref_stride, self._p(ref_offsets),
                                                                 search_w, search_h,
@@ -546,7 +546,7 @@ class SvtHipDsp:
         """coeff, recon: int32 [n, height, width] dense -> int64 [n, 2] (uint64 values)"""
         t = self.torch
         n = coeff.shape[0]
-        out = t.zeros((n, 2), dtype=t.int64, device=coeff.device)
+        out = t.empty((n, 2), dtype=t.int64, device=coeff.device)
         self._check(self.lib.svt_hip_full_distortion32_batch(self._p(coeff), width, width * height,
                                                               self._p(recon) if recon is not None else None, width,
                                                               width * height, width, height, 1 if cbf_zero else 0,
@@ -632,12 +632,13 @@ class SvtHipDsp:
     def cfl_luma_subsampling_420(self, luma, luma_stride, width, height, xy=None, luma_block_pitch=0, n=None,
                                  subtract_average=False, q3=None):
         """luma: uint8 / int16(uint16 values) plane or dense blocks; width x height = LUMA block.
-        -> int16 [n, 32, 32] Q3 buffers in the reference's layout (rows CFL_BUF_LINE apart)"""
+        -> int16 [n, 32, 32] Q3 buffers in the reference's layout (rows CFL_BUF_LINE apart); the call writes the width / 2 x
+        height / 2 entries of each, the rest of a fresh buffer is zero"""
         t = self.torch
         if n is None:
             n = xy.shape[0]
         if q3 is None:
-            q3 = t.zeros((n, 32, 32), dtype=t.int16, device=luma.device)
+            q3 = t.zeros((n, 32, 32), dtype=t.int16, device=luma.device)      # partly written (width / 2 x height / 2 of each): zeros define the rest
         self._check(self.lib.svt_hip_cfl_luma_subsampling_420_batch(self._p(luma), luma_stride, luma_block_pitch,
                                                                      self._p(xy) if xy is not None else None,
                                                                      0 if luma.dtype == t.uint8 else 1, self._p(q3), 32, 1024,
@@ -716,8 +717,8 @@ class SvtHipDsp:
         n = src.shape[0]
         _, rh, rw = ref.shape
         if best_sad is None:
-            best_sad = t.full((n, 85), self.MAX_SAD_VALUE, dtype=t.int32, device=src.device)
-            best_mv = t.zeros((n, 85), dtype=t.int32, device=src.device)
+            best_sad = t.full((n, 85), self.MAX_SAD_VALUE, dtype=t.int32, device=src.device)     # IN/OUT running bests: the caller initialises them
+            best_mv = t.zeros((n, 85), dtype=t.int32, device=src.device)                          # IN/OUT
         self._check(self.lib.svt_hip_me_sb_search_batch(self._p(src), 64, 64 * 64, self._p(ref), rw, rw * rh, search_w,
                                                          search_h, self._p(origins) if origins is not None else None,
                                                          x_origin, y_origin, self._p(best_sad), self._p(best_mv), n,
@@ -936,8 +937,8 @@ class SvtHipDsp:
             spitch = rpitch = 0
         npu = self.ME_PUS_ALL if nsq else 85
         if best_sad is None:
-            best_sad = t.full((n, npu), self.MAX_SAD_VALUE, dtype=t.int32, device=src.device)
-            best_mv = t.zeros((n, npu), dtype=t.int32, device=src.device)
+            best_sad = t.full((n, npu), self.MAX_SAD_VALUE, dtype=t.int32, device=src.device)    # IN/OUT running bests: the caller initialises them
+            best_mv = t.zeros((n, npu), dtype=t.int32, device=src.device)                         # IN/OUT
         self._check(self.lib.svt_hip_me_fullpel_search_batch(
             self._p(src), src_stride, spitch, self._p(src_offsets) if src_offsets is not None else None, self._p(ref), ref_stride,
             rpitch, self._p(ref_offsets) if ref_offsets is not None else None, search_w, search_h,
@@ -977,8 +978,8 @@ class SvtHipDsp:
         n = src_offsets.numel()
         npu = self.ME_PUS_ALL if nsq else 85
         if best_sad is None:
-            best_sad = t.full((n, npu), self.MAX_SAD_VALUE, dtype=t.int32, device=src.device)
-            best_mv = t.zeros((n, npu), dtype=t.int32, device=src.device)
+            best_sad = t.full((n, npu), self.MAX_SAD_VALUE, dtype=t.int32, device=src.device)    # IN/OUT running bests: the caller initialises them
+            best_mv = t.zeros((n, npu), dtype=t.int32, device=src.device)                         # IN/OUT
         self._check(self.lib.svt_hip_me_fullpel_search_areas_batch(self._p(src), src_stride, self._p(src_offsets), self._p(ref), ref_stride,
                                                                    self._p(ref_offsets), self._p(areas), max_w, max_h, flavour, 1 if nsq else 0,
                                                                    self._p(best_sad), self._p(best_mv), best_sad.shape[1], n, self._stream()),
@@ -988,15 +989,15 @@ class SvtHipDsp:
     def me_bipred(self, src_pic00, src_stride, ref0_pic00, ref0_stride, ref1_pic00, ref1_stride, sb_origin, best_sad0, best_mv0, best_sad1=None,
                   best_mv1=None, npus=209, bipred_all_pus=True, sub_sad=True, out=None):
         """svt_hip_me_bipred_batch -> (bipred_sad int32 [n, pu_pitch] in storage order, results uint8 [n, npus, 24] = svt_hip_me_result
-        rows in raster PU order); `out`: such a pair to write into (its bipred_sad is zeroed first, as a fresh one is)"""
+        rows in raster PU order; the call writes every entry of both, bipred_sad = 0 where no bi-prediction is made); `out`: such a pair
+        to write into"""
         t = self.torch
         n = sb_origin.shape[0]
         pitch = best_sad0.shape[1]
         if out is not None:
             bip, res = out
-            bip.zero_()
         else:
-            bip = t.zeros((n, pitch), dtype=t.int32, device=sb_origin.device)
+            bip = t.empty((n, pitch), dtype=t.int32, device=sb_origin.device)
             res = t.empty((n, npus, ctypes.sizeof(self.MeResult)), dtype=t.uint8, device=sb_origin.device)      # (every row is written)
         two = best_sad1 is not None
         self._check(self.lib.svt_hip_me_bipred_batch(self._p(src_pic00), src_stride, self._p(ref0_pic00) if two else None, ref0_stride,
@@ -1073,9 +1074,9 @@ class SvtHipDsp:
         is16 = 0 if src.dtype == t.uint8 else 1
         co = t.empty((n, nc), dtype=t.int32, device=src.device)
         q = t.empty_like(co); dq = t.empty_like(co)
-        eob = t.zeros(n, dtype=t.int16, device=src.device)
-        sad = t.zeros(n, dtype=t.int32, device=src.device) if want_sad else None
-        en = t.zeros(n, dtype=t.int64, device=src.device) if want_energy else None
+        eob = t.empty(n, dtype=t.int16, device=src.device)
+        sad = t.empty(n, dtype=t.int32, device=src.device) if want_sad else None
+        en = t.empty(n, dtype=t.int64, device=src.device) if want_energy else None
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         self._check(self.lib.svt_hip_fwd_quant_planes_batch(self._p(src), src_stride, self._p(pred), pred_stride,
                                                              self._p(xy), n, is16, bd, tx_size, tx_type,
@@ -1095,7 +1096,7 @@ class SvtHipDsp:
         nc = TX_W[tx_size] * TX_H[tx_size]
         if outs is None:
             outs = (t.empty((n, nc), dtype=t.int32, device=residual.device), t.empty((n, nc), dtype=t.int32, device=residual.device),
-                    t.empty((n, nc), dtype=t.int32, device=residual.device), t.zeros(n, dtype=t.int16, device=residual.device))
+                    t.empty((n, nc), dtype=t.int32, device=residual.device), t.empty(n, dtype=t.int16, device=residual.device))
         co, q, dq, eob = outs
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         self._check(self.lib.svt_hip_fwd_quant_batch(self._p(residual), n, tx_size, tx_type, bd, tabs[0].ctypes.data,
@@ -1285,10 +1286,11 @@ class SvtHipDsp:
 
     def cdef_apply_frame(self, rec, skip, luma_strength, chroma_strength, width, height, bit_depth, base_qindex, dst=None):
         """svt_hip_cdef_apply_frame (av1_cdef_frame).  luma_strength / chroma_strength: int8 [(npics,) nfb], 0 .. 63 or -1 = leave the
-        filter block alone.  -> dst (Y, Cb, Cr), shaped as rec; only the picture area is written."""
+        filter block alone.  -> dst (Y, Cb, Cr), shaped as rec; only the picture area is written (the samples of a fresh dst outside it
+        are zero)."""
         t = self.torch
         if dst is None:
-            dst = tuple(t.zeros_like(x) for x in rec)
+            dst = tuple(t.zeros_like(x) for x in rec)      # partly written (the picture area of each plane): zeros define the rest
         p = self.make_cdef_pic(rec, skip, width, height, bit_depth, base_qindex, dst=dst)
         nfb = ((width + 63) // 64) * ((height + 63) // 64)
         for s in (luma_strength, chroma_strength):

@@ -113,6 +113,10 @@ __global__ __launch_bounds__(ME_THREADS) void me_bipred_kernel(
     const uint32_t sb = blockIdx.x;
     if (sb >= nsb) return;
     const size_t row = (size_t)sb * pu_pitch;
+    // every entry of the SB's bipred_sad row is defined after the call: 0 for PUs without a bi-prediction SAD and past the PU count
+    // (the body's own stores come after its barriers, as in me_frame_bipred_kernel)
+    if (bipred_sad)
+        for (uint32_t i = threadIdx.x; i < pu_pitch; i += ME_THREADS) bipred_sad[row + i] = 0u;
     me_bipred_body(src_pic, src_stride, ref0_pic, ref0_stride, ref1_pic, ref1_stride, sb_origin[2 * sb], sb_origin[2 * sb + 1], best_sad0 + row,
                    best_mv0 + row, best_sad1 ? best_sad1 + row : nullptr, best_mv1 ? best_mv1 + row : nullptr, npus, bipred_all_pus, sub_sad, map,
                    bipred_sad ? bipred_sad + row : nullptr, results + (size_t)sb * npus);

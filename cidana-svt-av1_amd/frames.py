@@ -32,7 +32,7 @@ class FramePass:
                  spread_outputs=False):
         """tx_types: {block side: transform type} (default DCT_DCT everywhere); rect_tx_sizes: rectangular TxSize ids (5 .. 18) that
         tile the luma plane too (DCT_DCT), e.g. pkg.TX_SIZE_NAMES.index("TX_16X8")"""
-        import torch
+        torch = dsp.torch                     # the module the SvtHipDsp allocates through
         self.dsp, self.torch = dsp, torch
         self.groups = []
         dev = next(iter(planes_src.values())).device
@@ -194,7 +194,7 @@ class PictureInput:
     left / top padding), pad_right / pad_bottom = extension to a multiple of the minimum CU size (8)."""
 
     def __init__(self, dsp, pkg, path, origin=(64 + 4, 64 + 4), min_cu=8, with_decimation=True, device="cuda:0"):
-        import torch
+        torch = dsp.torch
         self.dsp, self.t = dsp, torch
         self.rd = pkg.Y4mReader(dsp.lib, path)
         i = self.rd.info

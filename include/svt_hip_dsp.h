@@ -497,7 +497,9 @@ int svt_hip_me_fullpel_search_batch(const uint8_t *d_src, uint32_t src_stride, s
  *     puSearchIndexMap, EbMotionEstimation.h:178-315) and read the SAD / vector rows at the storage index of the same rectangle
  *     (svt_hip_me_pu_storage_index).  d_best_sad1 / d_best_mv1 NULL: P picture, one candidate.  bipred_all_pus = (cu8x8_mode ==
  *     CU_8x8_MODE_0 || pic_depth_mode <= PIC_ALL_C_DEPTH_MODE): otherwise only PUs 0 .. 20 are bi-predicted (:8297).  npus 85 or
- *     209.  me_nsq[] of the reference's rows is not produced (it is written by the sub-pel stage, which is outside this path). */
+ *     209.  me_nsq[] of the reference's rows is not produced (it is written by the sub-pel stage, which is outside this path).
+ *     Every entry of both outputs is written: all pu_pitch entries of an SB's d_bipred_sad row (may be NULL), 0 where no
+ *     bi-prediction is made (P pictures, PUs past 20 without bipred_all_pus, entries past the PU count), and all npus result rows. */
 typedef struct svt_hip_me_setup_params {
     int32_t picture_width, picture_height;        /* SequenceControlSet luma_width / luma_height: the search area's clip */
     int32_t ref_width, ref_height;                /* refPicPtr->width / height: the clip of the HME centre in CheckZeroZeroCenter */
@@ -739,7 +741,8 @@ int svt_hip_ois_search_frame(const uint8_t *d_pic, uint32_t stride, uint32_t wid
  * q3_line int16 apart (CFL_BUF_LINE = 32 in the reference), blocks q3_block_pitch int16 apart
  * (CFL_BUF_SQUARE = 1024 there).  subtract_average != 0 also applies subtract_average with the
  * encode pass's arguments (round_offset = w*h/2, num_pel_log2 = log2(w*h) of the chroma block) in
- * the same kernel.  Chroma sizes 4..32 in both dimensions. */
+ * the same kernel.  Chroma sizes 4..32 in both dimensions.  Only the width/2 x height/2 entries of a block's Q3 buffer are
+ * written; the rest of each row and the rows below keep what they held (the reference's pred_buf_q3 is not cleared either). */
 int svt_hip_cfl_luma_subsampling_420_batch(const void *d_luma, uint32_t luma_stride,
                                            size_t luma_block_pitch, const uint32_t *d_xy, int is_16bit,
                                            int16_t *d_q3, uint32_t q3_line, size_t q3_block_pitch,

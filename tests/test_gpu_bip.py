@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import TX_H, TX_W, ptr
 
 pytestmark = pytest.mark.gpu
@@ -102,7 +104,7 @@ def test_build_intra_predictors_random_batches_vs_oracle(dsp, is16):
         # destination: a picture, blocks on a grid with odd origins and a stride that is not a multiple of 4
         stride = 40 * (w + 3) + 1
         rows = (n + 39) // 40
-        pic = torch.zeros((rows * (h + 2) + 2, stride), dtype=torch.int16 if is16 else torch.uint8, device="cuda")
+        pic = poison.tensor((rows * (h + 2) + 2, stride), torch.int16 if is16 else torch.uint8, "cuda").zero_()
         offs = np.array([(1 + (i // 40) * (h + 2)) * stride + 1 + (i % 40) * (w + 3) for i in range(n)], np.uint32)
         dsp.build_intra_predictors(neigh_rows(list(tops), is16), neigh_rows(list(lefts), is16), dev(np.array(blks, np.uint8)), tx, bd=bd,
                                    dst=pic, dst_stride=stride, dst_offsets=dev(offs.view(np.int32)))
@@ -171,3 +173,6 @@ def test_ordered_batch_equals_plain_batch_and_order_is_sorted_by_kind(dsp, is16)
             assert sorted(tile.tolist()) == list(range(t0, min(n, t0 + 4096))), (tx, t0)
             ks = [kind(blks[i]) for i in tile]
             assert sum(1 for a, b in zip(ks, ks[1:]) if a != b) <= 12, (tx, t0)
+
+
+poison.add_second_fill(globals())

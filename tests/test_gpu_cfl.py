@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import ptr
 from test_gpu_parity import dev
 
@@ -43,7 +45,7 @@ def test_cfl_golden(dsp, w, h, bd):
     assert torch.equal(ac1, ac2)
     pred = g[key + "_pred"]
     ps = pred.shape[2]
-    dst = torch.zeros_like(_t(pred))
+    dst = poison.tensor(pred.shape, _t(pred).dtype, "cuda").zero_()
     dsp.cfl_predict(dev(np.ascontiguousarray(g[key + "_ac"])), _t(pred), ps, dst, ps, dev(g[key + "_alpha"]), bd, w, h)
     assert np.array_equal(_np(dst, dt), g[key + "_dst"])
 
@@ -55,7 +57,7 @@ def test_txb_init_levels_golden(dsp, w, h):
     n = coeff.shape[0]
     size = (w + 4) * (h + 6) + 16
     for pitch in ((size + 15) // 16 * 16, (size + 15) // 16 * 16 + 4):       # 16-byte stores / dword stores
-        buf = torch.full((n, pitch), 0x55, dtype=torch.uint8, device="cuda")
+        buf = poison.tensor((n, pitch), torch.uint8, "cuda").fill_(0x55)
         dsp.txb_init_levels(dev(coeff.reshape(n, -1)), w, h, buf)
         got = buf.cpu().numpy()
         assert np.array_equal(got[:, :size], g[f"lv_{w}x{h}_levels"])
@@ -105,7 +107,7 @@ def test_txb_init_levels_at_scale(dsp):
         coeff = rng.integers(-200, 201, size=(n, h * w)).astype(np.int32)
         coeff[::7] *= 1 << 16
         pitch = ((w + 4) * (h + 6) + 16 + 8 + 15) // 16 * 16      # 16-byte-aligned buffers; the slack is not touched
-        buf = torch.full((n, pitch), 0x77, dtype=torch.uint8, device="cuda")
+        buf = poison.tensor((n, pitch), torch.uint8, "cuda").fill_(0x77)
         dsp.txb_init_levels(dev(coeff), w, h, buf)
         got = buf.cpu().numpy()
         for i in range(0, n, 13):
@@ -128,3 +130,42 @@ def test_cfl_argument_errors(dsp):
     assert L.svt_hip_cfl_predict_batch(p, 32, 1024, p, 8, p, 8, None, p, 9, 8, 8, 0, 1, None) != 0                # 8-bit samples, bd 9
     assert L.svt_hip_txb_init_levels_batch(p, 16, p, 90, 4, 4, 1, None) != 0                                      # buffer < 96 B
     assert L.svt_hip_txb_init_levels_batch(p, 16, p, 96, 4, 4, 0, None) == 0                                      # empty batch
+
+
+@pytest.mark.parametrize("n", [1, 257])            # one block; one more than the 256 blocks the smallest size packs into a workgroup
+@pytest.mark.parametrize("w,h,bd", [(4, 4, 8), (32, 32, 8), (16, 8, 10)])
+def test_cfl_and_levels_tail_counts(dsp, w, h, bd, n):
+    """dense batches of n blocks: subsample + subtract average, predict into a fresh destination, level maps; oracle per block"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(8200 + 19 * n + w + bd)
+    dt = np.uint8 if bd == 8 else np.uint16
+    luma = rng.integers(0, 1 << bd, size=(n, 2 * h, 2 * w)).astype(dt)
+    pred = rng.integers(0, 1 << bd, size=(n, h, w)).astype(dt)
+    alpha = rng.integers(-16, 17, size=n).astype(np.int32)
+    q3buf = poison.tensor((n, 32, 32), torch.int16, "cuda")     # the call writes a block's w x h entries and nothing else (header)
+    ac = dsp.cfl_luma_subsampling_420(_t(luma), 2 * w, 2 * w, 2 * h, luma_block_pitch=4 * w * h, n=n, subtract_average=True, q3=q3buf)
+    dst = poison.tensor(pred.shape, _t(pred).dtype, "cuda")
+    dsp.cfl_predict(ac, _t(pred), w, dst, w, dev(alpha), bd, w, h)
+    got_ac, got = ac.cpu().numpy(), _np(dst, dt)
+    pat = poison.fill_value(torch.int16)
+    assert (got_ac[:, h:, :] == pat).all() and (got_ac[:, :, w:] == pat).all()
+    want = pred.copy()
+    for i in range(n):
+        q3 = np.zeros((32, 32), np.int16)
+        O.svt_oracle_cfl_luma_subsampling_420(ptr(luma[i]), c_int(bd > 8), c_int(2 * w), ptr(q3), c_int(2 * w), c_int(2 * h))
+        O.svt_oracle_subtract_average(ptr(q3), c_int(w), c_int(h), c_int(w * h // 2), c_int(int(np.log2(w * h))))
+        assert np.array_equal(got_ac[i, :h, :w], q3[:h, :w]), i
+        O.svt_oracle_cfl_predict(ptr(q3), ptr(want[i]), c_int(w), ptr(want[i]), c_int(w), c_int(int(alpha[i])), c_int(bd), c_int(w), c_int(h), c_int(bd > 8))
+    assert np.array_equal(got, want)
+    coeff = rng.integers(-200, 201, size=(n, h * w)).astype(np.int32)
+    coeff[n - 1] = 0
+    size = (w + 4) * (h + 6) + 16
+    lv = dsp.txb_init_levels(dev(coeff), w, h).cpu().numpy()
+    assert lv.shape == (n, size)
+    for i in range(n):
+        one = np.full(size, 0xEE, np.uint8)          # every byte of the buffer is written (header), by the oracle as well
+        O.svt_oracle_txb_init_levels(ptr(coeff[i]), c_int(w), c_int(h), ctypes.c_void_p(one.ctypes.data + 2 * (w + 4)))
+        assert np.array_equal(lv[i], one), i
+
+
+poison.add_second_fill(globals())

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import TX_H, TX_W, ptr
 
 pytestmark = pytest.mark.gpu

@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import TX_H, TX_W, ptr
 from test_gpu_parity import dev, make_pixels, oracle_chain
 
@@ -125,7 +127,7 @@ def test_encode_recon_on_planes(dsp, tx_size, tx_type, inplace):
     qrow = {k: v[80].copy() for k, v in qt.items()}
     _, iscan = svtlibs.scan_tables(tx_size, tx_type)
     d_pred = dev(pred)
-    d_recon = d_pred if inplace else torch.full_like(d_pred, 7)
+    d_recon = d_pred if inplace else poison.tensor(d_pred.shape, d_pred.dtype, d_pred.device).fill_(7)
     out = dsp.encode_recon_planes(dev(src), PW, d_pred, PW, d_recon, PW, dev(xy.view(np.int32)), tx_size, tx_type, qrow, dev(iscan),
                                   keep_coeff=True, want_sad=True)
     torch.cuda.synchronize()
@@ -163,7 +165,7 @@ def test_encode_recon_on_planes_10bit(dsp, tx_size, tx_type, inplace):
     qrow = {k: v[120].copy() for k, v in qt.items()}
     _, iscan = svtlibs.scan_tables(tx_size, tx_type)
     d_pred = dev(pred.view(np.int16))
-    d_recon = d_pred if inplace else torch.full_like(d_pred, 9)
+    d_recon = d_pred if inplace else poison.tensor(d_pred.shape, d_pred.dtype, d_pred.device).fill_(9)
     out = dsp.encode_recon_planes(dev(src.view(np.int16)), PW, d_pred, PW, d_recon, PW, dev(xy.view(np.int32)), tx_size, tx_type, qrow,
                                   dev(iscan), keep_coeff=True, bd=10)
     torch.cuda.synchronize()
@@ -227,3 +229,16 @@ def test_encode_recon_4x4_every_type_fused_equals_two_stage(dsp, tx_type):
         dsp.lib.svt_hip_tune(b"no_enc_staged", 0)
     for k in ("coeff", "qcoeff", "dqcoeff", "eob", "recon", "sad"):
         assert torch.equal(a[k], b[k]), k
+
+
+@pytest.mark.parametrize("n", [1, 257])            # 257: one more than enc4_kernel's 256 blocks per workgroup, no multiple of any other
+@pytest.mark.parametrize("tx_size,tx_type", [(0, 0), (1, 0), (3, 0), (3, 9), (4, 0), (13, 0)])
+@pytest.mark.parametrize("keep", [False, True])
+def test_encode_recon_tail_counts(dsp, tx_size, tx_type, n, keep):
+    rng = np.random.default_rng(8100 + 19 * n + tx_size)
+    src, pred = make_pixels(rng, n, TX_H[tx_size], TX_W[tx_size], "smooth")
+    src[n - 1] = pred[n - 1]                       # the last block: eob 0, sad 0, recon == pred must be written, not left over
+    check(dsp, src, pred, tx_size, tx_type, 60, keep)
+
+
+poison.add_second_fill(globals())

@@ -7,7 +7,9 @@ import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import ptr
 
 pytestmark = pytest.mark.gpu
@@ -454,13 +456,13 @@ def test_level_maps_of_more_groups_than_one_launch_holds(dsp, pkg):
         size = (side + 4) * (side + 6) + 16
         narrow = gi in (7, 48)
         pitch = size + 4 if narrow else (size + 15) // 16 * 16
-        raw = torch.full((n * pitch + 32,), 0x5a, dtype=torch.uint8, device=DEV)
+        raw = poison.tensor((n * pitch + 32,), torch.uint8, DEV).fill_(0x5a)
         off = (-raw.data_ptr()) % 16 + (4 if narrow else 0)
         levels = raw[off:off + n * pitch].view(n, pitch)
         assert levels.data_ptr() % 16 == (4 if narrow else 0) and (pitch % 16 != 0) == narrow
         groups.append(dict(src=d_src, src_stride=W, pred=d_pred, pred_stride=W, recon=d_recon, recon_stride=W, tx_size=ts, tx_type=0,
                            xy=torch.from_numpy(xy.view(np.int32)).to(DEV), iscan=torch.from_numpy(pkg.tables.scan_tables(ts, 0)[1]).to(DEV),
-                           qcoeff=torch.empty((n, side * side), dtype=torch.int32, device=DEV), eob=torch.zeros(n, dtype=torch.int16, device=DEV),
+                           qcoeff=poison.tensor((n, side * side), torch.int32, DEV), eob=poison.tensor((n,), torch.int16, DEV),
                            levels=levels, raw=raw, side=side, size=size))
     dsp.encode_recon_frame_ex(dsp.make_frame_groups(groups), qrow, len(groups), None, 0, dsp.make_frame_levels([g["levels"] for g in groups]))
     torch.cuda.synchronize()

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import ptr
 from test_gpu_parity import dev
 

@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import ptr
 
 pytestmark = pytest.mark.gpu
@@ -111,6 +113,7 @@ def test_hme_regions_in_one_launch_equal_per_region_calls(dsp):
         for r in range(4):
             b, c_each[r] = dsp.hme_level(src, W, ref00, stride, org, size, c_each[r], cs, prm[r])
             assert torch.equal(b, b_all[r]) and torch.equal(c_each[r], c_all[r]), (level, r)
+        poison.assert_written(b_all, c_all)
 
 
 def test_hme_argument_errors(dsp, pkg):
@@ -119,3 +122,29 @@ def test_hme_argument_errors(dsp, pkg):
     pic = torch.zeros((64, 64), dtype=torch.uint8, device="cuda")
     with pytest.raises(pkg.SvtHipError):
         dsp.hme_level(pic, 64, pic, 64, z, z, None, 0, p)          # zeroed parameter block
+
+
+def test_hme_tasks_outside_the_sb_size_range_get_the_documented_result(dsp):
+    """include/svt_hip_dsp.h: width 1 .. 64, height 2 .. 64; "an entry outside that range gets best_sad = 2^64 - 1 and mv = (0, 0)".
+    Four such tasks between two ordinary ones, which are searched as usual (oracle)"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(414)
+    W, H, pad = 128, 64, 72
+    stride = W + 2 * pad
+    ref = rng.integers(0, 256, (H + 2 * pad, stride), dtype=np.uint8); src = rng.integers(0, 256, (H, W), dtype=np.uint8)
+    hw, hh = np.array([16, 16], np.uint16), np.array([8, 8], np.uint16)
+    p = dsp.hme_level_params(2, hw, hh, 0, 0, int(hw.sum()), int(hh.sum()), 100, 100, pad, pad, W, H)
+    po = svtlibs.hme_params(2, hw, hh, 0, 0, 100, 100, pad, W, H)
+    org = np.array([(0, 0), (64, 0), (0, 0), (64, 0), (0, 0), (64, 0)], np.int16)
+    size = np.array([(64, 64), (0, 64), (64, 1), (65, 64), (64, 65), (64, 64)], np.int16)
+    d_src, d_ref = dev(src), dev(ref)
+    best, mv = dsp.hme_level(d_src, W, d_ref.view(-1)[pad * stride + pad:], stride, dev(org), dev(size), None, 0, p)
+    gb = best.cpu().numpy().view(np.uint64); gm = mv.cpu().numpy()
+    ref00 = ctypes.c_void_p(ref.ctypes.data + pad * stride + pad)
+    for i in range(6):
+        if i in (0, 5):
+            b = np.zeros(1, np.uint64); x = np.zeros(1, np.int16); y = np.zeros(1, np.int16)
+            O.svt_oracle_hme_level(ptr(src), W, ref00, stride, int(org[i, 0]), int(org[i, 1]), 64, 64, 0, 0, ctypes.byref(po), ptr(b), ptr(x), ptr(y))
+            assert (int(gb[i]), int(gm[i, 0]), int(gm[i, 1])) == (int(b[0]), int(x[0]), int(y[0])), i
+        else:
+            assert (int(gb[i]), int(gm[i, 0]), int(gm[i, 1])) == (2 ** 64 - 1, 0, 0), (i, size[i].tolist())

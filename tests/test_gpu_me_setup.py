@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import ptr
 
 pytestmark = pytest.mark.gpu

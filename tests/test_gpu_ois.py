@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import ptr
 from test_gpu_parity import dev
 from test_oracle_golden import ois_md_scan, ois_raster_idx
@@ -92,6 +94,7 @@ def test_ois_fold_variant(dsp, bsize):
             out.append(dsp.ois_search(plane[pad:, pad:], W + 2 * pad, W, H, _xy(blocks), bsize, modes, deltas))
     finally:
         dsp.lib.svt_hip_tune(b"ois_no_fold", 0)
+    poison.assert_written(out)
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
 
 
@@ -115,6 +118,7 @@ def test_ois_three_zones_in_one_launch_variant(dsp, bsize):
                 out.append(dsp.ois_search(plane[pad:, pad:], W + 2 * pad, W, H, _xy(blocks), bsize, m, d))
         finally:
             dsp.lib.svt_hip_tune(b"ois_no_dir3", 0)
+        poison.assert_written(out)
         assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
 
 
@@ -134,6 +138,7 @@ def test_ois_directional_angles_split_over_grid_variant(dsp, bsize):
             out.append(dsp.ois_search(plane, W + 24, W, H, _xy(blocks), bsize, modes, deltas))
     finally:
         dsp.lib.svt_hip_tune(b"dir_no_split", 0)
+    poison.assert_written(out)
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
 
 
@@ -155,6 +160,7 @@ def test_ois_fused_non_directional_variant(dsp, bsize, tl):
             out.append(dsp.ois_search(plane, W + 24, W, H, _xy(blocks), bsize, modes, deltas))
     finally:
         dsp.lib.svt_hip_tune(b"ois_no_nd", 0)
+    poison.assert_written(out)
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
 
 
@@ -198,6 +204,7 @@ def test_ois_search_frame_equals_per_size_calls(dsp):
         xy = _xy(blocks)
         groups.append((xy, bsize, modes, deltas))
         single.append(dsp.ois_search(plane, W + 16, W, H, xy, bsize, modes, deltas))
+    poison.assert_written(single)
     # six groups (more than one merged non-directional launch holds) and, second, one non-directional launch per group
     groups6 = groups + [groups[1], groups[3]]
     single6 = single + [single[1], single[3]]
@@ -212,3 +219,6 @@ def test_ois_search_frame_equals_per_size_calls(dsp):
                     assert torch.equal(single6[i][0], d2) and torch.equal(single6[i][1], b2), (knob, od, i)
     finally:
         dsp.lib.svt_hip_tune(b"ois_no_nd_multi", 0)
+
+
+poison.add_second_fill(globals())

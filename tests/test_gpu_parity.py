@@ -10,7 +10,9 @@ import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import TX_H, TX_SIZES, TX_TYPES, TX_W, ptr, txfm_allowed
 
 pytestmark = pytest.mark.gpu
@@ -544,3 +546,215 @@ def test_inverse_clamp_free_threshold(dsp, tx_size, bd):
             O.svt_oracle_inv_txfm2d_add_u8(ptr(co[i]), ptr(ref8[i]), w, 0, tx_size)
         dsp.inv_txfm2d_add(dev(co), d8, tx_size, 0, 8)
         assert np.array_equal(d8.cpu().numpy(), ref8)
+
+
+# ---------------------------------------------------------------------------------------
+# poisoned outputs (tests/poison.py) on the device, and the batch sizes at which a launch's last workgroup goes wrong:
+# one block, three blocks, and 257 = one more than the largest number of blocks any of these kernels gives a workgroup
+# (2 * F32_WAVES = 8 for the tuned 32x32 chain, 2 * E64_WAVES = 4 for 64x64, TX_WAVES * blocks-per-wave <= 256 for the
+# generic transform / quantiser kernels, 256 / lanes-per-block for the pixel kernels)
+# ---------------------------------------------------------------------------------------
+TAIL_COUNTS = [1, 3, 257]
+
+
+def test_wrapper_outputs_are_poisoned_and_fenced(dsp, poisoned_outputs):
+    """a wrapper call under the fixture: its output is the middle of a recorded, filled base and the guards hold"""
+    proxy = poisoned_outputs
+    assert dsp.torch is proxy
+    rng = np.random.default_rng(3)
+    a = rng.integers(0, 256, size=(3, 16, 16), dtype=np.uint8); b = rng.integers(0, 256, size=(3, 16, 16), dtype=np.uint8)
+    da, db = dev(a), dev(b)
+    before = len(proxy.records)
+    out = dsp.sad(da, db)
+    assert len(proxy.records) == before + 1
+    base, nbytes = proxy.records[-1]
+    assert nbytes == 3 * 4 and base.is_cuda and base.dtype == torch.uint8 and base.numel() == 2 * poison.GUARD + nbytes
+    assert base.data_ptr() + poison.GUARD == out.data_ptr() and out.is_contiguous() and out.dtype == torch.int32
+    torch.cuda.synchronize()
+    assert np.array_equal(out.cpu().numpy().view(np.uint32), np.abs(a.astype(np.int64) - b).sum(axis=(1, 2)).astype(np.uint32))
+    assert bool((base[:poison.GUARD] == proxy.fill_byte).all()) and bool((base[poison.GUARD + nbytes:] == proxy.fill_byte).all())
+    assert int(dsp.torch.empty(5, dtype=torch.int32, device=DEV)[4]) == poison.fill_value(torch.int32) == 0x5A5A5A5A
+    poison.check_guards()
+
+
+@pytest.mark.parametrize("n", TAIL_COUNTS)
+@pytest.mark.parametrize("tx_size,tx_type", [(0, 0), (1, 9), (3, 0), (3, 9), (4, 0), (9, 0)])
+def test_fused_chain_tail_counts(dsp, tx_size, tx_type, n):
+    w, h = TX_W[tx_size], TX_H[tx_size]
+    rng = np.random.default_rng(7000 + 19 * n + tx_size)
+    qrow = {k: v[60].copy() for k, v in svtlibs.quant_tables(8).items()}
+    _, iscan = svtlibs.scan_tables(tx_size, tx_type)
+    src, pred = make_pixels(rng, n, h, w, "smooth")
+    src[n - 1] = pred[n - 1]                       # the LAST block: zero residual, eob 0 and sad 0 must be written, not left over
+    co, q, dq, eob, sad = dsp.fwd_quant_sad(dev(src), dev(pred), tx_size, tx_type, qrow, dev(iscan))
+    rco, rq, rdq, reob, rsad = oracle_chain(src, pred, tx_size, tx_type, qrow)
+    assert np.array_equal(co.cpu().numpy(), rco) and np.array_equal(q.cpu().numpy(), rq) and np.array_equal(dq.cpu().numpy(), rdq)
+    assert np.array_equal(eob.cpu().numpy().view(np.uint16), reob) and reob[n - 1] == 0
+    assert np.array_equal(sad.cpu().numpy().view(np.uint32), rsad) and rsad[n - 1] == 0
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+@pytest.mark.parametrize("tx_size", [0, 3, 4])
+def test_fwd_quant_planes_tail_counts(dsp, tx_size, bd):
+    """one block (a plane of exactly one block) and five (more than the four blocks a 64x64 workgroup takes)"""
+    w, h = TX_W[tx_size], TX_H[tx_size]
+    rng = np.random.default_rng(7100 + tx_size + bd)
+    _plane_case(dsp, rng, bd, tx_size, 0, w, h, 80)
+    _plane_case(dsp, rng, bd, tx_size, 0, 5 * w, h, 80)
+
+
+@pytest.mark.parametrize("n", TAIL_COUNTS)
+@pytest.mark.parametrize("tx_size", [0, 2, 3, 4, 13])
+def test_fwd_inv_txfm2d_tail_counts(dsp, tx_size, n):
+    O = svtlibs.oracle()
+    w, h = TX_W[tx_size], TX_H[tx_size]
+    kw, kh = min(w, 32), min(h, 32)
+    rng = np.random.default_rng(7200 + 19 * n + tx_size)
+    for bd in (8, 10):
+        x = rng.integers(-(1 << bd) + 1, 1 << bd, size=(n, h, w)).astype(np.int16)
+        x[n - 1] = 0                               # the last block's coefficients are all zero: they must be written as zero
+        ref = np.zeros((n, w * h), np.int32)
+        for i in range(n):
+            O.svt_oracle_fwd_txfm2d(ptr(x[i]), ptr(ref[i]), ctypes.c_uint32(w), 0, tx_size, bd)
+        assert np.array_equal(dsp.fwd_txfm2d(dev(x), tx_size, 0, bd).cpu().numpy(), ref), (TX_SIZES[tx_size], bd)
+        packed = ref.copy()
+        for i in range(n):
+            O.svt_oracle_fwd_txfm2d_pack64(ptr(packed[i]), tx_size)
+        co = np.ascontiguousarray(packed[:, :kw * kh])
+        dst = rng.integers(0, 1 << bd, size=(n, h, w)).astype(np.uint16)
+        want = dst.copy()
+        for i in range(n):
+            O.svt_oracle_inv_txfm2d_add(ptr(co[i]), ptr(want[i]), w, 0, tx_size, bd)
+        d = dev(dst.view(np.int16))
+        dsp.inv_txfm2d_add(dev(co), d, tx_size, 0, bd)
+        assert np.array_equal(d.cpu().numpy().view(np.uint16), want), (TX_SIZES[tx_size], bd)
+        if bd == 8:
+            want8 = dst.astype(np.uint8)
+            for i in range(n):
+                O.svt_oracle_inv_txfm2d_add_u8(ptr(co[i]), ptr(want8[i]), w, 0, tx_size)
+            d8 = dev(dst.astype(np.uint8))
+            dsp.inv_txfm2d_add(dev(co), d8, tx_size, 0, 8)
+            assert np.array_equal(d8.cpu().numpy(), want8), TX_SIZES[tx_size]
+
+
+@pytest.mark.parametrize("n", [1, 65, 257])        # 4 lanes per 4x4 block: 64 blocks per workgroup
+@pytest.mark.parametrize("tx_size,log_scale", [(0, 0), (2, 0), (3, 1)])
+def test_quantize_b_tail_counts(dsp, tx_size, log_scale, n):
+    O = svtlibs.oracle()
+    scan, iscan = svtlibs.scan_tables(tx_size, 0)
+    nc = len(scan)
+    rng = np.random.default_rng(7300 + 19 * n + tx_size)
+    qrow = {k: v[100].copy() for k, v in svtlibs.quant_tables(8).items()}
+    co = rng.integers(-(1 << 15), (1 << 15) + 1, size=(n, nc)).astype(np.int32)
+    co[n - 1] = 0                                  # eob 0 in the last slot
+    q, dq, eob = dsp.quantize_b(dev(co), qrow, dev(iscan), log_scale)
+    rq = np.zeros_like(co); rdq = np.zeros_like(co); reob = np.zeros(n, np.uint16)
+    for i in range(n):
+        O.svt_oracle_quantize_b(ptr(co[i]), ctypes.c_ssize_t(nc), 0, ptr(qrow["zbin"]), ptr(qrow["round"]), ptr(qrow["quant"]),
+                                ptr(qrow["quant_shift"]), ptr(rq[i]), ptr(rdq[i]), ptr(qrow["dequant"]), ptr(reob[i:i + 1]), ptr(scan),
+                                ptr(iscan), log_scale, 0)
+    assert np.array_equal(q.cpu().numpy(), rq) and np.array_equal(dq.cpu().numpy(), rdq)
+    assert np.array_equal(eob.cpu().numpy().view(np.uint16), reob) and reob[n - 1] == 0
+    q, dq, eob = dsp.quantize_b(dev(co), qrow, dev(iscan), log_scale, skip_block=1)
+    assert not q.any() and not dq.any() and not eob.any()
+
+
+@pytest.mark.parametrize("n", TAIL_COUNTS)
+@pytest.mark.parametrize("tx_size,tx_type", [(1, 0), (3, 0), (3, 9)])
+def test_config2_fwd_quant_tail_counts(dsp, tx_size, tx_type, n):
+    O = svtlibs.oracle()
+    w, h = TX_W[tx_size], TX_H[tx_size]
+    rng = np.random.default_rng(7400 + 19 * n + tx_size + tx_type)
+    res = rng.integers(-255, 256, size=(n, h, w)).astype(np.int16)
+    res[n - 1] = 0
+    qrow = {k: v[100].copy() for k, v in svtlibs.quant_tables(8).items()}
+    scan, iscan = svtlibs.scan_tables(tx_size, tx_type)
+    co, q, dq, eob = (t.cpu().numpy() for t in dsp.fwd_quant(dev(res), tx_size, tx_type, qrow, dev(iscan)))
+    ls = 1 if w * h > 256 else 0
+    for i in range(n):
+        rc = np.zeros(w * h, np.int32); rq = np.zeros(w * h, np.int32); rdq = np.zeros(w * h, np.int32); reob = np.zeros(1, np.uint16)
+        O.svt_oracle_fwd_txfm2d(ptr(res[i]), ptr(rc), ctypes.c_uint32(w), tx_type, tx_size, 8)
+        O.svt_oracle_quantize_b(ptr(rc), ctypes.c_ssize_t(w * h), 0, ptr(qrow["zbin"]), ptr(qrow["round"]), ptr(qrow["quant"]),
+                                ptr(qrow["quant_shift"]), ptr(rq), ptr(rdq), ptr(qrow["dequant"]), ptr(reob), ptr(scan), ptr(iscan), ls, 0)
+        assert np.array_equal(co[i], rc) and np.array_equal(q[i], rq) and np.array_equal(dq[i], rdq), i
+        assert int(eob.view(np.uint16)[i]) == int(reob[0]), i
+
+
+@pytest.mark.parametrize("n", TAIL_COUNTS)
+@pytest.mark.parametrize("w,h", [(4, 4), (16, 16), (64, 64), (24, 16)])
+def test_sad_sse_residual_tail_counts(dsp, w, h, n):
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(7500 + 19 * n + w)
+    a = rng.integers(0, 256, size=(n, h, w), dtype=np.uint8)
+    b = rng.integers(0, 256, size=(n, h, w), dtype=np.uint8)
+    b[n - 1] = a[n - 1]                            # SAD 0 / SSE 0 in the last slot
+    sad = dsp.sad(dev(a), dev(b)).cpu().numpy().view(np.uint32)
+    sse = dsp.sse(dev(a), dev(b)).cpu().numpy().view(np.uint64)
+    res = dsp.residual(dev(a), dev(b)).cpu().numpy()
+    for i in range(n):
+        assert int(sad[i]) == O.svt_oracle_sad(ptr(a[i]), w, ptr(b[i]), w, h, w), i
+        assert int(sse[i]) == O.svt_oracle_sse(ptr(a[i]), w, ptr(b[i]), w, w, h), i
+    assert sad[n - 1] == 0 and sse[n - 1] == 0
+    assert np.array_equal(res, a.astype(np.int16) - b.astype(np.int16))
+
+
+@pytest.mark.parametrize("n", TAIL_COUNTS)
+@pytest.mark.parametrize("w,h,sw,sh", [(8, 8, 8, 8), (16, 16, 5, 3), (32, 32, 9, 6), (64, 64, 4, 4)])
+def test_sad_search_tail_counts(dsp, w, h, sw, sh, n):
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(7600 + 19 * n + w)
+    rw, rh = w + sw - 1, h + sh - 1
+    src = rng.integers(0, 256, size=(n, h, w), dtype=np.uint8)
+    ref = rng.integers(0, 256, size=(n, rh, rw), dtype=np.uint8)
+    ref[n - 1, :h, :w] = src[n - 1]                # the last block: best SAD 0 at (0, 0)
+    best, x, y = (t.cpu().numpy() for t in dsp.sad_search(dev(src), dev(ref), sw, sh))
+    for i in range(n):
+        rb = np.zeros(1, np.uint64); rx = np.zeros(1, np.int16); ry = np.zeros(1, np.int16)
+        O.svt_oracle_sad_loop(ptr(src[i]), w, ptr(ref[i]), rw, h, w, ptr(rb), ptr(rx), ptr(ry), rw, ctypes.c_int16(sw), ctypes.c_int16(sh))
+        assert (int(best[i]), int(x[i]), int(y[i])) == (int(rb[0]), int(rx[0]), int(ry[0])), f"block {i}"
+    assert (int(best[n - 1]), int(x[n - 1]), int(y[n - 1])) == (0, 0, 0)
+
+
+@pytest.mark.parametrize("n", TAIL_COUNTS)
+@pytest.mark.parametrize("w,h", [(4, 4), (32, 32), (8, 32)])
+def test_full_distortion32_tail_counts(dsp, w, h, n):
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(7700 + 19 * n + w)
+    c = rng.integers(-(1 << 18), 1 << 18, size=(n, h, w)).astype(np.int32)
+    r = rng.integers(-(1 << 18), 1 << 18, size=(n, h, w)).astype(np.int32)
+    c[n - 1] = 0; r[n - 1] = 0                     # both sums 0 in the last slot
+    got = dsp.full_distortion32(dev(c), dev(r), w, h).cpu().numpy().view(np.uint64)
+    got0 = dsp.full_distortion32(dev(c), None, w, h, cbf_zero=True).cpu().numpy().view(np.uint64)
+    for i in range(n):
+        out = np.zeros(2, np.uint64)
+        O.svt_oracle_full_distortion32(ptr(c[i]), w, ptr(r[i]), w, ptr(out), w, h)
+        assert (int(got[i, 0]), int(got[i, 1])) == (int(out[0]), int(out[1])), i
+        assert (int(got0[i, 0]), int(got0[i, 1])) == (int(out[1]), int(out[1])), i
+    assert not got[n - 1].any() and not got0[n - 1].any()
+
+
+@pytest.mark.parametrize("n", [1, 257])
+@pytest.mark.parametrize("tx_size", [0, 3, 4, 13])
+def test_intra_pred_tail_counts(dsp, tx_size, n):
+    O = svtlibs.oracle()
+    bw, bh = TX_W[tx_size], TX_H[tx_size]
+    rng = np.random.default_rng(7800 + n + tx_size)
+    for bd in (8, 10):
+        dt = np.uint8 if bd == 8 else np.uint16
+        a = rng.integers(0, 1 << bd, size=(n, 304)).astype(dt); l = rng.integers(0, 1 << bd, size=(n, 304)).astype(dt)
+        es = a.itemsize
+        for mode, zone, dx, dy in ((0, 0, 1, 1), (9, 0, 1, 1), (10, 1, DR_DERIV[45], 1), (11, 2, DR_DERIV[23], DR_DERIV[67])):
+            out = dsp.intra_pred(_as_dev(a), _as_dev(l), mode, bw, bh, bd, 0, 0, dx, dy).cpu().numpy()
+            out = out if bd == 8 else out.view(np.uint16)
+            ref = np.zeros((n, bh, bw), a.dtype)
+            for i in range(n):
+                pa = ctypes.c_void_p(a[i].ctypes.data + NB * es); pl = ctypes.c_void_p(l[i].ctypes.data + NB * es)
+                if zone and bd == 8:
+                    O.svt_oracle_dr_prediction(zone, ptr(ref[i]), ctypes.c_ssize_t(bw), bw, bh, pa, pl, 0, 0, dx, dy)
+                elif zone:
+                    O.svt_oracle_dr_prediction_hbd(zone, ptr(ref[i]), ctypes.c_ssize_t(bw), bw, bh, pa, pl, 0, 0, dx, dy, bd)
+                elif bd == 8:
+                    O.svt_oracle_intra_pred(mode, ptr(ref[i]), ctypes.c_ssize_t(bw), bw, bh, pa, pl)
+                else:
+                    O.svt_oracle_intra_pred_hbd(mode, ptr(ref[i]), ctypes.c_ssize_t(bw), bw, bh, pa, pl, bd)
+            assert np.array_equal(out, ref), (TX_SIZES[tx_size], mode, bd)

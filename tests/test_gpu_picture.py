@@ -8,7 +8,9 @@ import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import ptr
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +25,11 @@ def as_t(a):      # uint16 values travel as int16 tensors
     return dev(a.view(np.int16) if a.dtype == np.uint16 else a)
 
 
+def out_t(a):     # a buffer the call under test writes: fenced, holding a's samples
+    src = as_t(a)
+    return poison.tensor(src.shape, src.dtype, src.device).copy_(src)
+
+
 def back(t, dt):
     a = t.cpu().numpy()
     return a.view(np.uint16) if dt == np.uint16 else a
@@ -34,24 +41,24 @@ def test_import_and_decimation_equal_the_reference_fixture(dsp):
         w, h, ox, oy, pr, pb, is16, stride = (int(v) for v in g[f"pad{k}_prm"])
         exp = g[f"pad{k}_out"]
         dt = exp.dtype.type
-        buf = as_t(np.full_like(exp, 0x55))
+        buf = out_t(np.full_like(exp, 0x55))
         dsp.picture_import(as_t(np.ascontiguousarray(g[f"pad{k}_frame"]).reshape(-1)), w, h, (buf, None, None), ox, oy, pr, pb)
         assert np.array_equal(back(buf, dt), exp), k
         # the in-place border routine on a buffer that holds only the (extended) picture
         only = np.full_like(exp, 0x11)
         only[oy:oy + h + pb, ox:ox + w + pr] = exp[oy:oy + h + pb, ox:ox + w + pr]
-        b2 = as_t(only)
+        b2 = out_t(only)
         dsp.picture_pad(b2, w + pr, h + pb, ox, oy)
         got = back(b2, dt)
         assert np.array_equal(got[:, :w + pr + 2 * ox], exp[:, :w + pr + 2 * ox]), k
         assert (got[:, w + pr + 2 * ox:] == 0x11).all()
     for k in g["dec_cases"].tolist():
         w, h, stride, qo, so = (int(v) for v in g[f"dec{k}_prm"])
-        q, s = as_t(np.full_like(g[f"dec{k}_q"], 0x33)), as_t(np.full_like(g[f"dec{k}_s"], 0x33))
+        q, s = out_t(np.full_like(g[f"dec{k}_q"], 0x33)), out_t(np.full_like(g[f"dec{k}_s"], 0x33))
         luma = as_t(g[f"dec{k}_luma"])
         dsp.picture_decimate(luma, stride, w, h, q, (qo, qo), s, (so, so))
         assert np.array_equal(q.cpu().numpy(), g[f"dec{k}_q"]) and np.array_equal(s.cpu().numpy(), g[f"dec{k}_s"]), k
-        s2 = as_t(np.full_like(g[f"dec{k}_s"], 0x33))
+        s2 = out_t(np.full_like(g[f"dec{k}_s"], 0x33))
         dsp.picture_decimate(luma, stride, w, h, None, (0, 0), s2, (so, so))        # sixteenth alone
         assert np.array_equal(s2.cpu().numpy(), g[f"dec{k}_s"]), k
 
@@ -78,7 +85,7 @@ def test_import_three_planes_vs_oracle_random_geometry(dsp, is16):
             O.svt_oracle_pad_input_picture(ctypes.c_void_p(e.ctypes.data + (poy * stride + pox) * es), stride, pw, ph, ppr, ppb, es)
             O.svt_oracle_generate_padding(ptr(e), stride, pw + ppr, ph + ppb, pox, poy, es)
             planes_np.append(e)
-        bufs = [as_t(np.full_like(e, 0x22)) for e in planes_np]
+        bufs = [out_t(np.full_like(e, 0x22)) for e in planes_np]
         dsp.picture_import(as_t(np.concatenate(frame)), w, h, tuple(bufs), ox, oy, pr, pb)
         for i in range(3):
             assert np.array_equal(back(bufs[i], dt), planes_np[i]), (trial, i, w, h, ox, oy)
@@ -97,7 +104,7 @@ def test_decimation_vs_oracle_1080p(dsp):
         O.svt_oracle_decimation_2d(ptr(luma), stride, w, h, ctypes.c_void_p(e.ctypes.data + o * ds + o), ds, step)
         O.svt_oracle_generate_padding(ptr(e), ds, dw, dh, o, o, 1)
         exp.append(e)
-    q, s = dev(np.full_like(exp[0], 0x44)), dev(np.full_like(exp[1], 0x44))
+    q, s = out_t(np.full_like(exp[0], 0x44)), out_t(np.full_like(exp[1], 0x44))
     dsp.picture_decimate(dev(luma), stride, w, h, q, (34, 34), s, (17, 17))
     assert np.array_equal(q.cpu().numpy(), exp[0]) and np.array_equal(s.cpu().numpy(), exp[1])
 
@@ -110,7 +117,7 @@ def test_luma8_plane_vs_oracle(dsp):
         src = rng.integers(0, 1024, (h, w + 7)).astype(np.uint16)
         exp = np.full((h, w + 9), 0x66, np.uint8)
         O.svt_oracle_unpack8(ptr(src), w + 7, ptr(exp), w + 9, w, h)
-        out = dev(np.full((h, w + 9), 0x66, np.uint8))
+        out = out_t(np.full((h, w + 9), 0x66, np.uint8))
         dsp.picture_luma8(as_t(src), out, w, h, 10)
         assert np.array_equal(out.cpu().numpy(), exp), (w, h)
 
@@ -174,3 +181,6 @@ def test_y4m_file_through_picture_input(dsp, pkg, tmp_path, bd):
         n += 1
     pi.close()
     assert n == nf
+
+
+poison.add_second_fill(globals())

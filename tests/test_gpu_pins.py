@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from svtlibs import TX_H, TX_SIZES, TX_TYPES, TX_W, ptr, txfm_allowed
 
 pytestmark = pytest.mark.gpu

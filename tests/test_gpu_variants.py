@@ -4,7 +4,9 @@ import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
+from poison import poisoned_outputs  # noqa: F401
 from test_gpu_parity import dev, make_pixels
 
 pytestmark = pytest.mark.gpu
@@ -20,10 +22,15 @@ def _tune(dsp, key, value):
 
 
 def _eq(a, b):
+    poison.assert_written(a, b)          # an entry that neither kernel wrote must not pass as equal
+    return _same(a, b)
+
+
+def _same(a, b):
     if isinstance(a, dict):
-        return all(_eq(a[k], b[k]) for k in a)
+        return all(_same(a[k], b[k]) for k in a)
     if isinstance(a, (tuple, list)):
-        return all(_eq(x, y) for x, y in zip(a, b))
+        return all(_same(x, y) for x, y in zip(a, b))
     if a is None or b is None:
         return a is b
     return torch.equal(a, b)
