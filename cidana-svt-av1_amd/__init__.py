@@ -168,6 +168,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_coeff_rate_frame.restype = c_int
     L.svt_hip_coeff_cost_index.argtypes = [c_int, c_void_p, c_void_p]
     L.svt_hip_coeff_cost_index.restype = c_int
+    L.svt_hip_tx_decide_frame.argtypes = [c_void_p, c_int, c_void_p]
+    L.svt_hip_tx_decide_frame.restype = c_int
+    L.svt_hip_tx_search_scratch_bytes.argtypes = [c_void_p, c_int]
+    L.svt_hip_tx_search_scratch_bytes.restype = c_size_t
+    L.svt_hip_tx_search_frame.argtypes = [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_void_p, c_size_t, c_void_p]
+    L.svt_hip_tx_search_frame.restype = c_int
+    L.svt_hip_tx_type_rate_index.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
+    L.svt_hip_tx_type_rate_index.restype = c_int
     return L
 
 
@@ -188,6 +196,16 @@ def coeff_cost_index_lib(tx_size: int):
     if rc != SVT_HIP_OK:
         raise SvtHipError(f"svt_hip_coeff_cost_index = {rc}")
     return a.value, b.value
+
+
+def tx_type_rate_index(tx_size: int, is_inter: bool, reduced_tx_set_used: bool = False):
+    """svt_hip_tx_type_rate_index (no device needed) -> (coded, ext_tx_set, square_tx_size): which row of intraTxTypeFacBits[ext_tx_set]
+    [square_tx_size][intra_dir] / interTxTypeFacBits[ext_tx_set][square_tx_size] holds the transform-type rate; coded False: the term is 0"""
+    a, b = c_int(-1), c_int(-1)
+    rc = load_library().svt_hip_tx_type_rate_index(tx_size, int(bool(is_inter)), int(bool(reduced_tx_set_used)), ctypes.addressof(a), ctypes.addressof(b))
+    if rc < 0:
+        raise SvtHipError(f"svt_hip_tx_type_rate_index = {rc}")
+    return bool(rc), a.value, b.value
 
 
 class MeFrameParams(ctypes.Structure):
@@ -1191,6 +1209,104 @@ class SvtHipDsp:
         self._check(self.coeff_rate_frame([g]), "svt_hip_coeff_rate_frame")
         return bits
 
+    # -- transform-type decision: RD cost, best type and the winner's coefficients per block ----------------------------------------
+    class TxDecision(ctypes.Structure):
+        _fields_ = [("cost", ctypes.c_uint64), ("dist", ctypes.c_uint64 * 2), ("bits", ctypes.c_uint64), ("eob", ctypes.c_uint16),
+                    ("tx_type", ctypes.c_uint8), ("type_index", ctypes.c_uint8), ("has_coeff", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3)]
+
+    class TxDecideGroup(ctypes.Structure):
+        _fields_ = [("tx_size", c_int32), ("ntypes", c_int32), ("tx_types", ctypes.c_uint8 * 16), ("nblocks", c_uint32), ("lambda_", c_uint32),
+                    ("d_dist", c_void_p), ("d_eob", c_void_p), ("d_bits", c_void_p), ("d_qcoeff", c_void_p), ("d_dqcoeff", c_void_p),
+                    ("d_decision", c_void_p), ("d_best_qcoeff", c_void_p), ("d_best_dqcoeff", c_void_p)]
+
+    class TxSearchGroup(ctypes.Structure):
+        pass                                                              # (a nested class body does not see FullLoopGroup)
+
+    TxSearchGroup._fields_ = [("fl", FullLoopGroup), ("d_txb_skip_ctx", c_void_p), ("d_dc_sign_ctx", c_void_p), ("d_type_bits", c_void_p),
+                              ("d_coeff_cost", c_void_p), ("d_eob_cost", c_void_p), ("lambda_", c_uint32), ("d_decision", c_void_p),
+                              ("d_best_qcoeff", c_void_p), ("d_best_dqcoeff", c_void_p)]
+
+    TX_DECISION_DTYPE = [("cost", "<u8"), ("dist", "<u8", (2,)), ("bits", "<u8"), ("eob", "<u2"), ("tx_type", "u1"), ("type_index", "u1"),
+                         ("has_coeff", "u1"), ("pad", "u1", (3,))]        # numpy view of a downloaded uint8 [n, 40] decision tensor
+
+    def make_tx_decide_groups(self, groups):
+        """groups: list of dicts with tensors dist (int64 [n, T, 2]), eob (int16 [n, T]), bits (int64 [n, T]), optional qcoeff / dqcoeff
+        (int32 [n, T, NC]), decision (uint8 [n, 40]: TxDecision records), optional best_qcoeff / best_dqcoeff (int32 [n, NC]), plus
+        nblocks, tx_size, tx_types, lambda.  -> ctypes array (keep the tensors alive!)"""
+        arr = (self.TxDecideGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+            types = list(g["tx_types"])
+            tt = (ctypes.c_uint8 * 16)(*(types + [0] * (16 - len(types)))[:16])
+            arr[i] = self.TxDecideGroup(g["tx_size"], g.get("ntypes", len(types)), tt, g["nblocks"], g.get("lambda", 0), P("dist"), P("eob"),
+                                        P("bits"), P("qcoeff"), P("dqcoeff"), P("decision"), P("best_qcoeff"), P("best_dqcoeff"))
+        return arr
+
+    def tx_decide_frame(self, groups):
+        """svt_hip_tx_decide_frame.  groups: a ctypes array from make_tx_decide_groups, or the list of dicts itself; a dict without
+        "decision" gets a fresh uint8 [nblocks, 40] tensor there (preallocate it to keep the call allocation-free, e.g. under graph
+        capture).  -> the library's return code"""
+        if isinstance(groups, list):
+            t = self.torch
+            for g in groups:
+                if g.get("decision") is None and g.get("dist") is not None:
+                    g["decision"] = t.empty((g["nblocks"], ctypes.sizeof(self.TxDecision)), dtype=t.uint8, device=g["dist"].device)
+            keep = groups
+            groups = self.make_tx_decide_groups(keep)
+            n = len(keep)
+        else:
+            n = len(groups)
+        return self.lib.svt_hip_tx_decide_frame(groups, n, self._stream())
+
+    def tx_decide(self, dist, eob, bits, tx_size, tx_types, lam, qcoeff=None, dqcoeff=None, decision=None, best_qcoeff=None, best_dqcoeff=None):
+        """One group: dist int64 [n, T, 2], eob int16 [n, T] (full_loop's), bits int64 [n, T] (coeff_rate's), optional qcoeff / dqcoeff
+        int32 [n, T, NC].  Outputs not given are allocated: decision uint8 [n, 40], best_qcoeff / best_dqcoeff int32 [n, NC] for every
+        coefficient input given.  -> decision, best_qcoeff | None, best_dqcoeff | None"""
+        t = self.torch
+        n, nc = dist.shape[0], min(TX_W[tx_size], 32) * min(TX_H[tx_size], 32)
+        if decision is None:
+            decision = t.empty((n, ctypes.sizeof(self.TxDecision)), dtype=t.uint8, device=dist.device)
+        if best_qcoeff is None and qcoeff is not None:
+            best_qcoeff = t.empty((n, nc), dtype=t.int32, device=dist.device)
+        if best_dqcoeff is None and dqcoeff is not None:
+            best_dqcoeff = t.empty((n, nc), dtype=t.int32, device=dist.device)
+        g = {"dist": dist, "eob": eob, "bits": bits, "qcoeff": qcoeff, "dqcoeff": dqcoeff, "decision": decision, "best_qcoeff": best_qcoeff,
+             "best_dqcoeff": best_dqcoeff, "nblocks": n, "tx_size": tx_size, "tx_types": tx_types, "lambda": lam}
+        self._check(self.tx_decide_frame([g]), "svt_hip_tx_decide_frame")
+        return decision, best_qcoeff, best_dqcoeff
+
+    def make_tx_search_groups(self, groups):
+        """groups: list of dicts: a full-loop group's keys (make_full_loop_groups; dist / eob / qcoeff / dqcoeff may be absent: scratch),
+        txb_skip_ctx / dc_sign_ctx (uint8 [n]), optional type_bits (int32 [n, T]), coeff_cost (int32 [529]), eob_cost (int32 [22]), lambda,
+        decision (uint8 [n, 40]), optional best_qcoeff / best_dqcoeff (int32 [n, NC]).  -> ctypes array (keep the tensors alive!)"""
+        fl = self.make_full_loop_groups(groups)
+        arr = (self.TxSearchGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+            arr[i] = self.TxSearchGroup(fl[i], P("txb_skip_ctx"), P("dc_sign_ctx"), P("type_bits"), P("coeff_cost"), P("eob_cost"),
+                                        g.get("lambda", 0), P("decision"), P("best_qcoeff"), P("best_dqcoeff"))
+        return arr
+
+    def tx_search_scratch_bytes(self, groups):
+        """svt_hip_tx_search_scratch_bytes of a ctypes array from make_tx_search_groups or of the list of dicts (0: bad parameters)"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_tx_search_groups(groups)
+        return self.lib.svt_hip_tx_search_scratch_bytes(groups, n)
+
+    def tx_search_frame(self, groups, qrow, scratch, flavour=1):
+        """svt_hip_tx_search_frame: full loop -> coefficient rate -> decide in one call.  groups: a ctypes array from
+        make_tx_search_groups or the list of dicts; scratch: a uint8 device tensor of at least tx_search_scratch_bytes(groups) bytes (None
+        where that is 0).  -> the library's return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            keep = groups
+            groups = self.make_tx_search_groups(keep)
+        tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
+        return self.lib.svt_hip_tx_search_frame(groups, n, flavour, tabs[0].ctypes.data, tabs[1].ctypes.data, tabs[2].ctypes.data,
+                                                tabs[3].ctypes.data, tabs[4].ctypes.data, self._p(scratch) if scratch is not None else None,
+                                                scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+
     # -- mode-decision fast loop, intra candidates: prediction -> distortion per (block, candidate) ------------------------------
     FAST_SAD, FAST_SSD = 0, 1
 
@@ -1357,3 +1473,6 @@ class SvtHipDsp:
         g = dict(src=src, pred=pred, nblocks=n, tx_size=tx_size, tx_types=tx_types, iscan=iscan, dist=dist, eob=eob, qcoeff=q, dqcoeff=dq)
         self._check(self.full_loop_frame([g], qrow, flavour), "svt_hip_full_loop_frame")
         return dist, eob, q, dq
+
+
+TxDecision, TxDecideGroup, TxSearchGroup = SvtHipDsp.TxDecision, SvtHipDsp.TxDecideGroup, SvtHipDsp.TxSearchGroup

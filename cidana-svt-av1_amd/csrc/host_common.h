@@ -81,9 +81,28 @@ inline int tx_log_scale(int tx_size) {
     return pels > 1024 ? 2 : (pels > 256 ? 1 : 0);
 }
 bool txfm_allowed(int tx_size, int tx_type);
+// size, count and type list of a (transform size, type list) group, as the full-loop, rate and decide calls all require them (empty
+// groups included): a size of the 19, 1 .. 16 types, each defined for the size, none listed twice
+inline int group_types_check(int g, int tx_size, int ntypes, const uint8_t* types) {
+    if (tx_size < 0 || tx_size >= SVT_TX_SIZES_ALL) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_size %d", g, tx_size);
+    if (ntypes < 1 || ntypes > 16) return set_err(SVT_HIP_ERR_INVALID, "group %d: ntypes %d (1 .. 16)", g, ntypes);
+    unsigned seen = 0;
+    for (int t = 0; t < ntypes; t++) {
+        const int ty = types[t];
+        if (!txfm_allowed(tx_size, ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d not defined for tx_size %d", g, ty, tx_size);
+        if (seen & (1u << ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d listed twice", g, ty);
+        seen |= 1u << ty;
+    }
+    return SVT_HIP_OK;
+}
 int frame_groups_check(const svt_hip_frame_group* groups, int ngroups);      // svt_hip_txfm.hip
 svtdev::QParams quant_params(const int16_t* zbin, const int16_t* round, const int16_t* quant, const int16_t* quant_shift,
                              const int16_t* dequant, int log_scale);                  // svt_hip_txfm.hip (make_qparams)
+// the argument checks of svt_hip_full_loop_frame and svt_hip_coeff_rate_frame (svt_hip_full_loop.hip, svt_hip_coeff_rate.hip):
+// svt_hip_tx_search_frame runs them on all its stages before the first launch
+int full_loop_check(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const int16_t* zbin, const int16_t* round,
+                    const int16_t* quant, const int16_t* quant_shift, const int16_t* dequant);
+int coeff_rate_check(const svt_hip_coeff_rate_group* groups, int ngroups);
 
 #define TX_SWITCH(tx_size, CALL)                                                                  \
     switch (tx_size) {                                                                            \

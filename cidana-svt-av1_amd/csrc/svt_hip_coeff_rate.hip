@@ -31,19 +31,11 @@ extern "C" int svt_hip_coeff_cost_index(int tx_size, int* txs_ctx, int* eob_mult
     return SVT_HIP_OK;
 }
 
-static int coeff_rate_check(const svt_hip_coeff_rate_group* groups, int ngroups) {
+int svthost::coeff_rate_check(const svt_hip_coeff_rate_group* groups, int ngroups) {
     if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_coeff_rate_group& G = groups[g];
-        if (G.tx_size < 0 || G.tx_size >= SVT_TX_SIZES_ALL) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_size %d", g, G.tx_size);
-        if (G.ntypes < 1 || G.ntypes > CR_MAX_TYPES) return set_err(SVT_HIP_ERR_INVALID, "group %d: ntypes %d (1 .. 16)", g, G.ntypes);
-        unsigned seen = 0;
-        for (int t = 0; t < G.ntypes; t++) {
-            const int ty = G.tx_types[t];
-            if (!txfm_allowed(G.tx_size, ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d not defined for tx_size %d", g, ty, G.tx_size);
-            if (seen & (1u << ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d listed twice", g, ty);
-            seen |= 1u << ty;
-        }
+        if (int rc = group_types_check(g, G.tx_size, G.ntypes, G.tx_types)) return rc;
         if (G.nblocks == 0) continue;
         if (pairs_of(G) > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "group %d: nblocks * ntypes too large", g);
         if (!G.d_qcoeff || !G.d_eob || !G.d_iscan || !G.d_txb_skip_ctx || !G.d_dc_sign_ctx || !G.d_coeff_cost || !G.d_eob_cost || !G.d_bits)

@@ -6,8 +6,8 @@
 using namespace svtdev;
 using namespace svthost;
 
-static int full_loop_check(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const int16_t* zbin, const int16_t* round,
-                           const int16_t* quant, const int16_t* quant_shift, const int16_t* dequant) {
+int svthost::full_loop_check(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const int16_t* zbin, const int16_t* round,
+                             const int16_t* quant, const int16_t* quant_shift, const int16_t* dequant) {
     if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
     if (flavour != SVT_HIP_FLAVOUR_C && flavour != SVT_HIP_FLAVOUR_AVX2) return set_err(SVT_HIP_ERR_INVALID, "flavour %d", flavour);
     if (!zbin || !round || !quant || !quant_shift || !dequant) return set_err(SVT_HIP_ERR_INVALID, "NULL quantiser table");
@@ -21,15 +21,7 @@ static int full_loop_check(const svt_hip_full_loop_group* groups, int ngroups, i
             return set_err(SVT_HIP_ERR_INVALID, "quantiser table outside the one-product quantiser's range (log_scale %d)", ls);
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_full_loop_group& G = groups[g];
-        if (G.tx_size < 0 || G.tx_size >= SVT_TX_SIZES_ALL) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_size %d", g, G.tx_size);
-        if (G.ntypes < 1 || G.ntypes > FL_MAX_TYPES) return set_err(SVT_HIP_ERR_INVALID, "group %d: ntypes %d (1 .. 16)", g, G.ntypes);
-        unsigned seen = 0;
-        for (int t = 0; t < G.ntypes; t++) {
-            const int ty = G.tx_types[t];
-            if (!txfm_allowed(G.tx_size, ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d not defined for tx_size %d", g, ty, G.tx_size);
-            if (seen & (1u << ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d listed twice", g, ty);
-            seen |= 1u << ty;
-        }
+        if (int rc = group_types_check(g, G.tx_size, G.ntypes, G.tx_types)) return rc;
         if (G.nblocks == 0) continue;
         if (G.nblocks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "group %d: nblocks too large", g);
         if (!G.d_src || !G.d_pred || !G.d_iscan || !G.d_dist || !G.d_eob) return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL member", g);

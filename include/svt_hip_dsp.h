@@ -691,6 +691,71 @@ int svt_hip_coeff_rate_frame(const svt_hip_coeff_rate_group *groups, int ngroups
  * eob_multi_size = txsize_log2_minus4 (either pointer may be NULL).  SVT_HIP_OK or SVT_HIP_ERR_INVALID (a bad tx_size). */
 int svt_hip_coeff_cost_index(int tx_size, int *txs_ctx, int *eob_multi_size);
 
+/* The end of ProductFullLoopTxSearch (EbFullLoop.c:927-1124; encode_pass_tx_search :1127-1323 is the same loop): the RD cost of every
+ * (block, type), the best type of every block and that type's coefficients, from the tables the two calls above write.  Per block,
+ * for i = 0 .. ntypes - 1 in the list's order, in uint64 arithmetic that wraps as the reference's does:
+ *   type i is skipped when d_eob[i] == 0 and tx_types[i] != DCT_DCT                                   (:1034)
+ *   cost_i = ((d_bits[i] * lambda + 256) >> 9) + d_dist[i][DIST_CALC_RESIDUAL] * 128                    (av1_tu_calc_cost_luma,
+ *            EbRateDistortionCost.c:2120-2194: RDCOST, EbRateDistortionCost.h:73, with LUMA_WEIGHT 1, AV1_COST_PRECISION 0 and
+ *            AV1_PROB_COST_SHIFT 9; its zero-cbf branch is compiled to UINT64_MAX, :2176-2191)
+ *   the winner is the first i with cost_i < best, best starting at UINT64_MAX                           (:940, :1102)
+ * A block without a candidate (every eob 0 in a list without DCT_DCT, or every cost UINT64_MAX) gets cost UINT64_MAX, tx_type
+ * DCT_DCT (the reference's initial best_tx_type), type_index 0xFF and zeros elsewhere.  d_best_qcoeff / d_best_dqcoeff, when given,
+ * receive the winner's min(W,32) * min(H,32) coefficients; a winner whose eob is 0, or no winner, gives zeros and its input is not
+ * read.  Only the winner's position, which is below ntypes by construction, addresses memory from device data.
+ * Every argument, empty groups' tx_size / types included, is validated before the first launch (SVT_HIP_ERR_INVALID: a bad size, a
+ * type not defined for it or listed twice, nblocks * ntypes above 2^31 - 1, a NULL d_dist / d_eob / d_bits / d_decision, a d_best_*
+ * without its input or equal to it, d_dist or a coefficient array not 16-byte, d_bits / d_decision not 8-byte, d_eob not 2-byte
+ * aligned).  The call only enqueues work (one launch per 32 groups), allocates nothing and can be captured into a HIP graph. */
+typedef struct svt_hip_tx_decision {        /* one per block; sizeof 40, 8-byte aligned */
+    uint64_t cost;       /* the winner's y_full_cost; UINT64_MAX when there is no candidate */
+    uint64_t dist[2];    /* the winner's {DIST_CALC_RESIDUAL, DIST_CALC_PREDICTION} as given */
+    uint64_t bits;       /* the winner's d_bits entry */
+    uint16_t eob;        /* the winner's eob */
+    uint8_t  tx_type;    /* best_tx_type (DCT_DCT when there is no candidate, the reference's initial value) */
+    uint8_t  type_index; /* its position in tx_types; 0xFF: no candidate */
+    uint8_t  has_coeff;  /* eob != 0 (the bit av1_tu_calc_cost_luma ors into y_has_coeff) */
+    uint8_t  pad[3];     /* written as 0 */
+} svt_hip_tx_decision;
+typedef struct svt_hip_tx_decide_group {
+    int32_t tx_size; int32_t ntypes; uint8_t tx_types[16];   /* as svt_hip_coeff_rate_group: defined for the size, distinct */
+    uint32_t nblocks;
+    uint32_t lambda;                       /* ModeDecisionContext_t.full_lambda (uint32 in the reference) */
+    const uint64_t *d_dist;                /* [nblocks][ntypes][2], the full loop's, 16-byte aligned */
+    const uint16_t *d_eob;                 /* [nblocks][ntypes] */
+    const uint64_t *d_bits;                /* [nblocks][ntypes], the rate call's (type bits already inside) */
+    const int32_t *d_qcoeff, *d_dqcoeff;   /* optional [nblocks][ntypes][NC], NC = min(W,32)*min(H,32), 16-byte aligned */
+    svt_hip_tx_decision *d_decision;       /* [nblocks] */
+    int32_t *d_best_qcoeff, *d_best_dqcoeff; /* optional [nblocks][NC]: the winner's coefficients; each needs its input */
+} svt_hip_tx_decide_group;
+int svt_hip_tx_decide_frame(const svt_hip_tx_decide_group *groups, int ngroups, void *stream);
+
+/* The whole transform-type search in one call: svt_hip_full_loop_frame -> svt_hip_coeff_rate_frame -> svt_hip_tx_decide_frame
+ * enqueued on `stream`, whose order carries the dependencies (host composition, no kernel of its own).  fl is the full-loop group;
+ * its d_dist / d_eob / d_qcoeff / d_dqcoeff may be NULL, the array then lives in d_scratch, as d_bits always does.  Carved per
+ * non-empty group in group order, every piece rounded up to 16 bytes: dist, eob, bits, qcoeff (each only when not supplied) and
+ * dqcoeff (only when not supplied and d_best_dqcoeff asks for it).  svt_hip_tx_search_scratch_bytes returns their sum, a HOST
+ * computation that needs no device: 0 for bad parameters (a NULL list, a bad size / count / type, nblocks * ntypes above 2^31 - 1)
+ * and for a call without a non-empty group, which needs no scratch.  All three stages' arguments are validated before the first
+ * launch (SVT_HIP_ERR_INVALID, as the three calls; also a scratch that is NULL, not 16-byte aligned or too small). */
+typedef struct svt_hip_tx_search_group {
+    svt_hip_full_loop_group fl;            /* d_dist / d_eob / d_qcoeff / d_dqcoeff may be NULL: they then live in the scratch */
+    const uint8_t *d_txb_skip_ctx, *d_dc_sign_ctx; const int32_t *d_type_bits;   /* as svt_hip_coeff_rate_group */
+    const int32_t *d_coeff_cost, *d_eob_cost;
+    uint32_t lambda;
+    svt_hip_tx_decision *d_decision; int32_t *d_best_qcoeff, *d_best_dqcoeff;    /* as svt_hip_tx_decide_group */
+} svt_hip_tx_search_group;
+size_t svt_hip_tx_search_scratch_bytes(const svt_hip_tx_search_group *groups, int ngroups);   /* 0: bad parameters */
+int svt_hip_tx_search_frame(const svt_hip_tx_search_group *groups, int ngroups, int flavour, const int16_t *zbin, const int16_t *round,
+                            const int16_t *quant, const int16_t *quant_shift, const int16_t *dequant,
+                            void *d_scratch, size_t scratch_bytes, void *stream);
+/* HOST: which row of the caller's transform-type rate tables feeds d_type_bits (Av1TransformTypeRateEstimation,
+ * EbRateDistortionCost.c:155-191): *ext_tx_set = get_ext_tx_set(tx_size, is_inter, reduced_tx_set_used) and *square_tx_size =
+ * txsize_sqr_map[tx_size] index intraTxTypeFacBits[ext_tx_set][square_tx_size][intra_dir][tx_type] (is_inter 0) or
+ * interTxTypeFacBits[ext_tx_set][square_tx_size][tx_type] (either pointer may be NULL).  Returns 1 when a type is coded
+ * (get_ext_tx_types > 1 and ext_tx_set > 0), 0 when the term is 0, SVT_HIP_ERR_INVALID for a bad tx_size. */
+int svt_hip_tx_type_rate_index(int tx_size, int is_inter, int reduced_tx_set_used, int *ext_tx_set, int *square_tx_size);
+
 /* Open-loop intra search: open_loop_intra_search_sb, EbMotionEstimation.c:8694-8850,
  * for all blocks of ONE size of a picture (or of many pictures' worth of blocks) in one call.
  * d_pic points at picture sample (0, 0) (buffer_y + origin_y * stride_y + origin_x), width x height are
