@@ -176,6 +176,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_tx_search_frame.restype = c_int
     L.svt_hip_tx_type_rate_index.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
     L.svt_hip_tx_type_rate_index.restype = c_int
+    L.svt_hip_cfl_search_scratch_bytes.argtypes = [c_void_p, c_int]
+    L.svt_hip_cfl_search_scratch_bytes.restype = c_size_t
+    L.svt_hip_cfl_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_cfl_search_frame.restype = c_int
+    L.svt_hip_cfl_decide_frame.argtypes = [c_void_p, c_int, c_void_p]
+    L.svt_hip_cfl_decide_frame.restype = c_int
+    L.svt_hip_cfl_pick_scratch_bytes.argtypes = [c_void_p, c_int]
+    L.svt_hip_cfl_pick_scratch_bytes.restype = c_size_t
+    L.svt_hip_cfl_pick_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_cfl_pick_frame.restype = c_int
     return L
 
 
@@ -1307,6 +1317,132 @@ class SvtHipDsp:
                                                 tabs[3].ctypes.data, tabs[4].ctypes.data, self._p(scratch) if scratch is not None else None,
                                                 scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
 
+    # -- CfL alpha search of mode decision: the (block, plane, alpha) table, cfl_rd_pick_alpha's walk, and both in one call ---------
+    CFL_NALPHA = 33
+
+    class QRows(ctypes.Structure):
+        _fields_ = [(k, c_void_p) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
+
+    class CflSearchGroup(ctypes.Structure):
+        _fields_ = [("d_luma_recon", c_void_p), ("luma_stride", c_uint32), ("d_src", c_void_p * 2), ("src_stride", c_uint32 * 2),
+                    ("d_pred", c_void_p * 2), ("pred_stride", c_uint32 * 2), ("d_xy", c_void_p), ("nblocks", c_uint32),
+                    ("tx_size", c_int32), ("tx_type", c_int32), ("d_iscan", c_void_p), ("d_txb_skip_ctx", c_void_p * 2),
+                    ("d_dc_sign_ctx", c_void_p * 2), ("d_coeff_cost", c_void_p), ("d_eob_cost", c_void_p), ("d_dist", c_void_p),
+                    ("d_bits", c_void_p), ("d_eob", c_void_p)]
+
+    class CflDecision(ctypes.Structure):
+        _fields_ = [("best_rd", ctypes.c_int64), ("dc_rd", ctypes.c_int64), ("alpha_q3", c_int32 * 2), ("uv_mode", ctypes.c_uint8),
+                    ("cfl_alpha_idx", ctypes.c_uint8), ("cfl_alpha_signs", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 5)]
+
+    class CflDecideGroup(ctypes.Structure):
+        _fields_ = [("nblocks", c_uint32), ("lambda_", c_uint32), ("d_dist", c_void_p), ("d_bits", c_void_p), ("d_alpha_rate", c_void_p),
+                    ("d_cfl_mode_bits", c_void_p), ("d_dc_mode_bits", c_void_p), ("d_decision", c_void_p), ("d_alpha_q3_cb", c_void_p),
+                    ("d_alpha_q3_cr", c_void_p)]
+
+    class CflPickGroup(ctypes.Structure):
+        pass                                                              # (a nested class body does not see CflSearchGroup)
+
+    CflPickGroup._fields_ = [("search", CflSearchGroup), ("lambda_", c_uint32), ("d_alpha_rate", c_void_p), ("d_cfl_mode_bits", c_void_p),
+                             ("d_dc_mode_bits", c_void_p), ("d_decision", c_void_p), ("d_alpha_q3_cb", c_void_p), ("d_alpha_q3_cr", c_void_p)]
+
+    CFL_DECISION_DTYPE = [("best_rd", "<i8"), ("dc_rd", "<i8"), ("alpha_q3", "<i4", (2,)), ("uv_mode", "u1"), ("cfl_alpha_idx", "u1"),
+                          ("cfl_alpha_signs", "u1"), ("pad", "u1", (5,))]    # numpy view of a downloaded uint8 [n, 32] decision tensor
+
+    def _qrows(self, qrow):
+        """-> (QRows, the int16 arrays it points into: keep them alive over the call)"""
+        tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
+        return self.QRows(*[x.ctypes.data for x in tabs]), tabs
+
+    def make_cfl_search_groups(self, groups):
+        """groups: list of dicts with tensors luma (uint8 plane, sample (0,0)), src / pred ((Cb, Cr) uint8 planes), xy (int32 chroma
+        origins x | y << 16), iscan (int16 [NC]), txb_skip_ctx / dc_sign_ctx ((Cb, Cr) uint8 [n]), coeff_cost (int32 [529]), eob_cost
+        (int32 [22]), dist (int64 [n, 2, 33, 2]), bits (int64 [n, 2, 33]), eob (int16 [n, 2, 33]), plus luma_stride, src_stride /
+        pred_stride (pairs), nblocks, tx_size, tx_type (default DCT_DCT).  -> ctypes array (keep the tensors alive!)"""
+        arr = (self.CflSearchGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+            P2 = lambda k: (c_void_p * 2)(*[x.data_ptr() if x is not None else None for x in (g.get(k) or (None, None))])
+            S2 = lambda k: (c_uint32 * 2)(*(g.get(k) or (0, 0)))
+            arr[i] = self.CflSearchGroup(P("luma"), g.get("luma_stride", 0), P2("src"), S2("src_stride"), P2("pred"), S2("pred_stride"),
+                                         P("xy"), g["nblocks"], g["tx_size"], g.get("tx_type", DCT_DCT), P("iscan"), P2("txb_skip_ctx"),
+                                         P2("dc_sign_ctx"), P("coeff_cost"), P("eob_cost"), P("dist"), P("bits"), P("eob"))
+        return arr
+
+    def cfl_search_scratch_bytes(self, groups):
+        """svt_hip_cfl_search_scratch_bytes of a ctypes array from make_cfl_search_groups or of the list of dicts (0: bad parameters)"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_cfl_search_groups(groups)
+        return self.lib.svt_hip_cfl_search_scratch_bytes(groups, n)
+
+    def cfl_search_frame(self, groups, qrow_cb, qrow_cr, scratch, flavour=1):
+        """svt_hip_cfl_search_frame.  groups: a ctypes array from make_cfl_search_groups or the list of dicts; qrow_cb / qrow_cr: the
+        planes' quantiser rows; scratch: a uint8 device tensor of at least cfl_search_scratch_bytes(groups) bytes (None where that is
+        0).  -> the library's return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            keep = groups
+            groups = self.make_cfl_search_groups(keep)
+        qb, kb = self._qrows(qrow_cb)
+        qr, kr = self._qrows(qrow_cr)
+        return self.lib.svt_hip_cfl_search_frame(groups, n, flavour, ctypes.addressof(qb), ctypes.addressof(qr),
+                                                 self._p(scratch) if scratch is not None else None,
+                                                 scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+
+    def make_cfl_decide_groups(self, groups):
+        """groups: list of dicts with tensors dist (int64 [n, 2, 33, 2]), bits (int64 [n, 2, 33]), alpha_rate (int32 [8, 2, 16]),
+        cfl_mode_bits / dc_mode_bits (int32 [n]), decision (uint8 [n, 32]: CflDecision records), optional alpha_q3_cb / alpha_q3_cr
+        (int32 [n]), plus nblocks, lambda.  -> ctypes array (keep the tensors alive!)"""
+        arr = (self.CflDecideGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+            arr[i] = self.CflDecideGroup(g["nblocks"], g.get("lambda", 0), P("dist"), P("bits"), P("alpha_rate"), P("cfl_mode_bits"),
+                                         P("dc_mode_bits"), P("decision"), P("alpha_q3_cb"), P("alpha_q3_cr"))
+        return arr
+
+    def cfl_decide_frame(self, groups):
+        """svt_hip_cfl_decide_frame.  groups: a ctypes array from make_cfl_decide_groups, or the list of dicts itself; a dict without
+        "decision" gets a fresh uint8 [nblocks, 32] tensor there (preallocate it to keep the call allocation-free).  -> return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            t = self.torch
+            for g in groups:
+                if g.get("decision") is None and g.get("dist") is not None:
+                    g["decision"] = t.empty((g["nblocks"], ctypes.sizeof(self.CflDecision)), dtype=t.uint8, device=g["dist"].device)
+            keep = groups
+            groups = self.make_cfl_decide_groups(keep)
+        return self.lib.svt_hip_cfl_decide_frame(groups, n, self._stream())
+
+    def make_cfl_pick_groups(self, groups):
+        """groups: list of dicts: a search group's keys (dist / bits / eob may be absent: scratch) and a decide group's (alpha_rate,
+        cfl_mode_bits, dc_mode_bits, decision, optional alpha_q3_cb / alpha_q3_cr, lambda).  -> ctypes array (keep the tensors alive!)"""
+        sg = self.make_cfl_search_groups(groups)
+        arr = (self.CflPickGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+            arr[i] = self.CflPickGroup(sg[i], g.get("lambda", 0), P("alpha_rate"), P("cfl_mode_bits"), P("dc_mode_bits"), P("decision"),
+                                       P("alpha_q3_cb"), P("alpha_q3_cr"))
+        return arr
+
+    def cfl_pick_scratch_bytes(self, groups):
+        """svt_hip_cfl_pick_scratch_bytes of a ctypes array from make_cfl_pick_groups or of the list of dicts (0: bad parameters)"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_cfl_pick_groups(groups)
+        return self.lib.svt_hip_cfl_pick_scratch_bytes(groups, n)
+
+    def cfl_pick_frame(self, groups, qrow_cb, qrow_cr, scratch, flavour=1):
+        """svt_hip_cfl_pick_frame: search -> decide in one call; arguments as cfl_search_frame.  -> the library's return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            keep = groups
+            groups = self.make_cfl_pick_groups(keep)
+        qb, kb = self._qrows(qrow_cb)
+        qr, kr = self._qrows(qrow_cr)
+        return self.lib.svt_hip_cfl_pick_frame(groups, n, flavour, ctypes.addressof(qb), ctypes.addressof(qr),
+                                               self._p(scratch) if scratch is not None else None,
+                                               scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+
     # -- mode-decision fast loop, intra candidates: prediction -> distortion per (block, candidate) ------------------------------
     FAST_SAD, FAST_SSD = 0, 1
 
@@ -1476,3 +1612,5 @@ class SvtHipDsp:
 
 
 TxDecision, TxDecideGroup, TxSearchGroup = SvtHipDsp.TxDecision, SvtHipDsp.TxDecideGroup, SvtHipDsp.TxSearchGroup
+QRows, CflSearchGroup, CflDecision, CflDecideGroup, CflPickGroup = (SvtHipDsp.QRows, SvtHipDsp.CflSearchGroup, SvtHipDsp.CflDecision,
+                                                                    SvtHipDsp.CflDecideGroup, SvtHipDsp.CflPickGroup)

@@ -27,6 +27,27 @@ struct QParams {
     int32_t round2[2];
 };
 
+// (the CfL kernels, kernel_cfl.h and kernel_cfl_search.h) one (possibly unaligned) 16- / 8-byte global access: a plain memcpy from a 1- or 2-byte-aligned pointer is split
+// into dwordx2 / dword pieces by the compiler
+typedef unsigned cfl_v4u __attribute__((ext_vector_type(4), aligned(1)));
+typedef unsigned cfl_v2u __attribute__((ext_vector_type(2), aligned(1)));
+template <int BYTES, typename T>
+__device__ __forceinline__ void cfl_ld(T* dst, const void* src) {
+    static_assert(BYTES == 32 || BYTES == 16 || BYTES == 8, "chunk");
+    if constexpr (BYTES == 32) {
+        const cfl_v4u a = reinterpret_cast<const cfl_v4u*>(src)[0], b = reinterpret_cast<const cfl_v4u*>(src)[1];
+        __builtin_memcpy(dst, &a, 16); __builtin_memcpy(reinterpret_cast<char*>(dst) + 16, &b, 16);
+    } else if constexpr (BYTES == 16) { const cfl_v4u a = *reinterpret_cast<const cfl_v4u*>(src); __builtin_memcpy(dst, &a, 16); }
+    else { const cfl_v2u a = *reinterpret_cast<const cfl_v2u*>(src); __builtin_memcpy(dst, &a, 8); }
+}
+template <int BYTES, typename T>
+__device__ __forceinline__ void cfl_st(void* dst, const T* src) {
+    static_assert(BYTES == 16 || BYTES == 8 || BYTES == 4, "chunk");
+    if constexpr (BYTES == 16) { cfl_v4u a; __builtin_memcpy(&a, src, 16); *reinterpret_cast<cfl_v4u*>(dst) = a; }
+    else if constexpr (BYTES == 8) { cfl_v2u a; __builtin_memcpy(&a, src, 8); *reinterpret_cast<cfl_v2u*>(dst) = a; }
+    else { unsigned a; __builtin_memcpy(&a, src, 4); __builtin_memcpy(dst, &a, 4); }
+}
+
 // Orders this wave's LDS traffic: LDS instructions of one wave execute in
 // issue order, so a compiler-level fence is all that is needed between a
 // phase that writes a tile and a phase in which OTHER lanes of the same wave

@@ -66,12 +66,83 @@ template <> struct FullLoopClass<2> {
     static constexpr int THREADS = 128;                   // 64x64: two waves of one block each
     static constexpr int LDS = FullLoopLds<64, 64>::BYTES;
 };
+// One candidate of a wave whose staging image (source, prediction) is in place: the forward transform of the type, then the row
+// pass's outputs quantised in registers.  Shared by full_loop_body and cfl_search_body (kernel_cfl_search.h).  bs = the block's
+// staging image, tile = its transpose tile, is = the type's iscan; store(s, q, d) receives the four quantised / dequantised
+// coefficients 4 s .. 4 s + 3 of row l (l < KH).  Out, valid in every lane of the block: e the eob, sc = sum c^2, sr the residual sum
+// of the flavour, en three_quad_energy.  Reads the staging image, writes and reads the tile: the caller owes a fence before either
+// is overwritten.
+template <int W, int H, typename Store>
+__device__ __forceinline__ void full_loop_candidate(const char* bs, int32_t* tile, int l, int tx_type, const int16_t* is, const QParams& qp,
+                                                    int avx2, Store&& store, int& e, unsigned long long& sc, unsigned long long& sr,
+                                                    unsigned long long& en) {
+    using S = StagedGeom<W, H>;
+    using G = TxGeom<W, H>;
+    constexpr int KW = S::KW, KH = S::KH;
+    const int vk = kVKind[tx_type], hk = kHKind[tx_type];
+    {
+        int x[H];
+        fwd_col_pass<W, H, uint8_t, true>(bs, l, vk, x);
+        if (l < W) fwd1d<H, fwd_cos_col(W, H)>(vk, x);
+        fwd_col_store<W, H>(tile, l, hk, x);
+    }
+    wave_lds_fence();
+    // ---- row pass, then quantise / distortion / eob in registers: lane l holds coefficient row l ----
+    sc = 0; sr = 0;
+    uint32_t lo0 = 0, lo1 = 0, lo2 = 0, lo3 = 0, hi = 0;
+    e = 0;
+    int y[W];
+    if (l < H) {
+#pragma unroll
+        for (int c = 0; c < W; c++) y[c] = tile[l * G::PITCH + c];
+        fwd1d<W, fwd_cos_row(W, H)>(hk, y);
+    }
+    en = fwd_row_scale<W, H>(l, y);
+    if (l < KH) {
+        const int16_t* isr = is + l * KW;
+#pragma unroll
+        for (int s = 0; s < KW / 4; s++) {
+            int q[4], d[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int c = y[4 * s + j];
+                quant_one<2>(c, (l == 0 && s == 0 && j == 0) ? 0 : 1, qp, q[j], d[j]);      // host-checked power-of-two quant_shift
+                const long long cc = c, df = (long long)c - d[j];
+                sc += (unsigned long long)(cc * cc);
+                if (avx2) {
+                    const long long dl = (int)(uint32_t)df;
+                    const unsigned long long sq = (unsigned long long)(dl * dl);
+                    hi += (uint32_t)(sq >> 32);
+                    if (j == 0) lo0 += (uint32_t)sq; else if (j == 1) lo1 += (uint32_t)sq; else if (j == 2) lo2 += (uint32_t)sq; else lo3 += (uint32_t)sq;
+                } else {
+                    sr += (unsigned long long)(df * df);
+                }
+            }
+            const uint2 iv = *reinterpret_cast<const uint2*>(isr + 4 * s);
+            e = max(e, max(max(q[0] ? (int)(iv.x & 0xffffu) + 1 : 0, q[1] ? (int)(iv.x >> 16) + 1 : 0),
+                           max(q[2] ? (int)(iv.y & 0xffffu) + 1 : 0, q[3] ? (int)(iv.y >> 16) + 1 : 0)));
+            store(s, q, d);
+        }
+    }
+    // ---- reduce over the block's lanes ----
+    e = group_max<G::LPB>(e);
+    sc = group_sum64<G::LPB>(sc);
+    if (W > 32 || H > 32) en = group_sum64<G::LPB>(en);
+    if (avx2) {
+        lo0 = group_sum<G::LPB>(lo0); lo1 = group_sum<G::LPB>(lo1); lo2 = group_sum<G::LPB>(lo2); lo3 = group_sum<G::LPB>(lo3);
+        hi = group_sum<G::LPB>(hi);
+        sr = ((unsigned long long)hi << 32) + lo0 + lo1 + lo2 + lo3;
+    } else {
+        sr = group_sum64<G::LPB>(sr);
+    }
+}
+
 template <int W, int H>
 __device__ __forceinline__ void full_loop_body(const FullLoopGroupDev& F, int avx2, uint32_t bid, char* lds) {
     using S = StagedGeom<W, H>;
     using G = TxGeom<W, H>;
     using I = StagedIn<W, H, 1>;
-    constexpr int KW = S::KW, KH = S::KH, NC = S::NC;
+    constexpr int KW = S::KW, NC = S::NC;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (wave >= S::WAVES) return;                         // (inside a larger workgroup of the class: the spare waves have nothing to do)
     char* wl = lds + wave * FullLoopLds<W, H>::WAVE;
@@ -94,65 +165,14 @@ __device__ __forceinline__ void full_loop_body(const FullLoopGroupDev& F, int av
 
 #pragma unroll 1
     for (int t = 0; t < F.ntypes; t++) {
-        const int tx_type = F.types[t];
-        const int vk = kVKind[tx_type], hk = kHKind[tx_type];
-        {
-            int x[H];
-            fwd_col_pass<W, H, uint8_t, true>(wl + sub * (I::BB + I::PADI), l, vk, x);
-            if (l < W) fwd1d<H, fwd_cos_col(W, H)>(vk, x);
-            fwd_col_store<W, H>(tile, l, hk, x);
-        }
-        wave_lds_fence();
-        // ---- row pass, then quantise / distortion / eob in registers: lane l holds coefficient row l ----
-        unsigned long long sc = 0, sr = 0;
-        uint32_t lo0 = 0, lo1 = 0, lo2 = 0, lo3 = 0, hi = 0;
-        int e = 0;
-        int y[W];
-        if (l < H) {
-#pragma unroll
-            for (int c = 0; c < W; c++) y[c] = tile[l * G::PITCH + c];
-            fwd1d<W, fwd_cos_row(W, H)>(hk, y);
-        }
-        unsigned long long en = fwd_row_scale<W, H>(l, y);
-        if (l < KH) {
-            const int16_t* is = F.iscan + t * NC + l * KW;
-            const size_t o = ((size_t)blk * F.ntypes + t) * NC + (size_t)l * KW;
-#pragma unroll
-            for (int s = 0; s < KW / 4; s++) {
-                int q[4], d[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int c = y[4 * s + j];
-                    quant_one<2>(c, (l == 0 && s == 0 && j == 0) ? 0 : 1, F.qp, q[j], d[j]);      // host-checked power-of-two quant_shift
-                    const long long cc = c, df = (long long)c - d[j];
-                    sc += (unsigned long long)(cc * cc);
-                    if (avx2) {
-                        const long long dl = (int)(uint32_t)df;
-                        const unsigned long long sq = (unsigned long long)(dl * dl);
-                        hi += (uint32_t)(sq >> 32);
-                        if (j == 0) lo0 += (uint32_t)sq; else if (j == 1) lo1 += (uint32_t)sq; else if (j == 2) lo2 += (uint32_t)sq; else lo3 += (uint32_t)sq;
-                    } else {
-                        sr += (unsigned long long)(df * df);
-                    }
-                }
-                const uint2 iv = *reinterpret_cast<const uint2*>(is + 4 * s);
-                e = max(e, max(max(q[0] ? (int)(iv.x & 0xffffu) + 1 : 0, q[1] ? (int)(iv.x >> 16) + 1 : 0),
-                               max(q[2] ? (int)(iv.y & 0xffffu) + 1 : 0, q[3] ? (int)(iv.y >> 16) + 1 : 0)));
+        const size_t o = ((size_t)blk * F.ntypes + t) * NC + (size_t)l * KW;
+        unsigned long long sc, sr, en;
+        int e;
+        full_loop_candidate<W, H>(wl + sub * (I::BB + I::PADI), tile, l, F.types[t], F.iscan + t * NC, F.qp, avx2,
+            [&](int s, const int (&q)[4], const int (&d)[4]) {
                 if (valid && F.qcoeff) *reinterpret_cast<int4*>(F.qcoeff + o + 4 * s) = make_int4(q[0], q[1], q[2], q[3]);
                 if (valid && F.dqcoeff) *reinterpret_cast<int4*>(F.dqcoeff + o + 4 * s) = make_int4(d[0], d[1], d[2], d[3]);
-            }
-        }
-        // ---- reduce over the block's lanes ----
-        e = group_max<G::LPB>(e);
-        sc = group_sum64<G::LPB>(sc);
-        if (W > 32 || H > 32) en = group_sum64<G::LPB>(en);
-        if (avx2) {
-            lo0 = group_sum<G::LPB>(lo0); lo1 = group_sum<G::LPB>(lo1); lo2 = group_sum<G::LPB>(lo2); lo3 = group_sum<G::LPB>(lo3);
-            hi = group_sum<G::LPB>(hi);
-            sr = ((unsigned long long)hi << 32) + lo0 + lo1 + lo2 + lo3;
-        } else {
-            sr = group_sum64<G::LPB>(sr);
-        }
+            }, e, sc, sr, en);
         if (valid && l == 0) {
             unsigned long long d0 = (e == 0 ? sc : sr) + en, d1 = sc + en;
             if (DSH > 0) { d0 >>= DSH; d1 >>= DSH; }

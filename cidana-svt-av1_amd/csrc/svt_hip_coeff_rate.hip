@@ -47,10 +47,7 @@ int svthost::coeff_rate_check(const svt_hip_coeff_rate_group* groups, int ngroup
     return SVT_HIP_OK;
 }
 
-extern "C" int svt_hip_coeff_rate_frame(const svt_hip_coeff_rate_group* groups, int ngroups, void* stream) {
-    if (int rc = require_init()) return rc;
-    if (int rc = coeff_rate_check(groups, ngroups)) return rc;
-    hipStream_t s = (hipStream_t)stream;
+int svthost::coeff_rate_enqueue(const svt_hip_coeff_rate_group* groups, int ngroups, hipStream_t s) {
     GroupTable<CoeffRateDesc, CR_MAX_GROUPS> tab;
     auto launch = [&](const CoeffRateDesc& fd, uint32_t total) -> int {
         hipLaunchKernelGGL(coeff_rate_kernel, dim3(total), dim3(CR_THREADS), 0, s, fd);
@@ -74,4 +71,10 @@ extern "C" int svt_hip_coeff_rate_frame(const svt_hip_coeff_rate_group* groups, 
         memcpy(D->types, G.tx_types, sizeof(D->types));
     }
     return tab.flush(launch);
+}
+
+extern "C" int svt_hip_coeff_rate_frame(const svt_hip_coeff_rate_group* groups, int ngroups, void* stream) {
+    if (int rc = require_init()) return rc;
+    if (int rc = coeff_rate_check(groups, ngroups)) return rc;
+    return coeff_rate_enqueue(groups, ngroups, (hipStream_t)stream);
 }

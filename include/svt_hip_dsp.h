@@ -756,6 +756,123 @@ int svt_hip_tx_search_frame(const svt_hip_tx_search_group *groups, int ngroups, 
  * (get_ext_tx_types > 1 and ext_tx_set > 0), 0 when the term is 0, SVT_HIP_ERR_INVALID for a bad tx_size. */
 int svt_hip_tx_type_rate_index(int tx_size, int is_inter, int reduced_tx_set_used, int *ext_tx_set, int *square_tx_size);
 
+/* The CfL alpha search of mode decision: CflPrediction (EbProductCodingLoop.c:1746-1860) without its luma inverse transform, that is
+ * cfl_rd_pick_alpha (:1577-1737) and the AV1CostCalcCfl (:1395-1572) runs under it, for many chroma-size groups in one call.  From
+ * the luma reconstruction and the DC chroma predictions to per-block alpha_q3_cb / alpha_q3_cr, which svt_hip_frame_cfl_group
+ * (svt_hip_encode_recon_frame_ex) and svt_hip_cfl_predict_batch take as they are, without a host round trip.  8-bit samples only,
+ * as the reference's mode decision (BIT_INCREMENT_8BIT).
+ *
+ * svt_hip_cfl_search_frame: THE TABLE.  Per chroma block, once: ac = cfl_luma_subsampling_420_lbd_c of the 2W x 2H luma area at
+ * (2x, 2y), subtract_average with round_offset W * H / 2 and num_pel_log2 log2(W * H) (:1774-1789).  Then per plane (0 Cb, 1 Cr) and
+ * per candidate a of SVT_HIP_CFL_NALPHA:
+ *   pred = cfl_predict_lbd(ac, dc_pred, alpha_q3(a), 8); residual = src - pred; av1_estimate_transform(DEFAULT_SHAPE) (no CfL size is
+ *   32x32: FullLoop_R's PF_N2_32X32 branch, EbFullLoop.c:1529-1710, is never taken); the production quantiser with THAT PLANE's rows
+ *   (u_* / v_*, :559-579: they differ as soon as the picture has chroma delta-q; quant_shift a power of two, as the full loop);
+ *   eob = count_non_zero_coeffs; d_dist = picture_full_distortion32_bits (the cbf-zero kernel at eob 0, flavour as
+ *   svt_hip_full_loop_frame), both entries >> 2 (chromaShift, :1803 of CuFullDistortionFastTuMode_R, EbFullLoop.c:1715-1873; no
+ *   three_quad_energy); d_bits = av1_cost_coeffs_txb for eob > 0, else av1_cost_skip_txb (Av1TuEstimateCoeffBits, PLANE_TYPE_UV).
+ * Sizes: the nine chroma sizes the reference can reach (TX_4X4, 8X8, 16X16, 4X8, 8X4, 8X16, 16X8, 4X16, 16X4); any other tx_size, or
+ * a tx_type not defined for the size, is SVT_HIP_ERR_INVALID.  The reference always uses DCT_DCT here (EbModeDecision.c:1976).
+ * Two launches: the search kernel (one per 16 groups), which never stores a prediction or a dqcoeff, leaves every candidate's qcoeff
+ * and context bytes in d_scratch, where svt_hip_coeff_rate_frame's kernel reads (block, plane, a) as a block with one type.
+ * svt_hip_cfl_search_scratch_bytes (HOST, no device needed) is, per non-empty group in group order, nblocks * 66 * W * H * 4 bytes of
+ * qcoeff and twice nblocks * 66 context bytes rounded up to 16; 0 for bad parameters (a NULL list, a bad size or type, nblocks * 66
+ * above 2^31 - 1) and for a call without a non-empty group.
+ * Divergences from the reference.  The first two have no effect on a decision; the third can have one:
+ *   - the table always holds all 66 entries; the reference's walk skips some (`if (c > 2 && progress < c) break`), but an entry is a
+ *     pure function of (block, plane, a);
+ *   - AV1CostCalcCfl's "To check DC" test (cfl_alpha_idx 0 and cfl_alpha_signs 0, :1436 / :1511) is also met by the walk's Cr,
+ *     CFL_SIGN_NEG, c = 0 step, which the reference therefore costs at alpha_q3 0 and not -1.  The table's entry [1][1] is the honest
+ *     alpha_q3 -1; svt_hip_cfl_decide_frame reads entry [1][0] at that step, as the reference does;
+ *   - QUANTISER ROWS.  Of each int16[8] row of svt_hip_qrows only entry [0] (the DC coefficient) and entry [1] (every other
+ *     coefficient) are read, as the reference's C quantiser (highbd_quantize_b_helper_c) reads them.  The reference's production AVX2
+ *     quantiser reads the lanes: coefficient 0 from [0], coefficient 1 from [1], and every coefficient from the third on from [2 .. 7].
+ *     For a row that is {dc, ac, ac, ac, ac, ac, ac, ac} the two agree, and so does this call.  av1_build_quantizer does not build
+ *     such a row for v_quant: it fills v_quant[q][2 .. 7] from u_quant[q][1] (EbModeDecisionConfigurationProcess.c:511; every other u /
+ *     v row repeats its own [1]).  So in a picture with u_ac_delta_q != v_ac_delta_q the reference encoder quantises the Cr
+ *     coefficients from the third on with Cb's AC multiplier and Cr's zbin / round / quant_shift / dequant, while this call uses
+ *     Cr's own multiplier v_quant[q][1].  Then the Cr half of the table (qcoeff, d_eob, d_dist, d_bits) can differ from what the
+ *     reference encoder computes, and with it the picked alpha or the CfL / DC choice.  With u_ac_delta_q == v_ac_delta_q (this
+ *     reference never sets a chroma delta: all are 0) v_quant[q][2 .. 7] equals v_quant[q][1] and the call is bit-exact with the AVX2
+ *     path, whatever the DC deltas; that is the case tests/golden/cfl_search.npz pins.  svt_hip_full_loop_frame reads its rows the
+ *     same way.
+ * Every argument, empty groups' tx_size / tx_type included, is validated before the first launch (SVT_HIP_ERR_INVALID: a NULL member,
+ * d_dist not 16-byte, d_iscan / d_bits not 8-byte, d_xy not 4-byte, d_eob not 2-byte aligned, a stride below the block width (luma:
+ * twice), a NULL or non-power-of-two quantiser row, a scratch that is NULL, not 16-byte aligned or too small).  Contexts are
+ * device data and clamped as in svt_hip_coeff_rate_frame.  The calls only enqueue work on `stream`, allocate nothing and can be
+ * captured into a HIP graph. */
+#define SVT_HIP_CFL_NALPHA 33   /* a = 0: alpha_q3 0;  a = 1 + 16 * (sign - 1) + c: sign 1 = CFL_SIGN_NEG, 2 = CFL_SIGN_POS, alpha_q3 = -/+ (c + 1), c = 0 .. 15 */
+typedef struct svt_hip_qrows { const int16_t *zbin, *round, *quant, *quant_shift, *dequant; } svt_hip_qrows;   /* HOST int16[8] rows; only [0] (DC) and [1] (AC) are read: see QUANTISER ROWS above */
+typedef struct svt_hip_cfl_search_group {
+    const uint8_t *d_luma_recon; uint32_t luma_stride;        /* sample (0,0) of the luma reconstruction; block at (2x, 2y) */
+    const uint8_t *d_src[2];  uint32_t src_stride[2];         /* Cb, Cr source planes */
+    const uint8_t *d_pred[2]; uint32_t pred_stride[2];        /* Cb, Cr DC predictions; only read */
+    const uint32_t *d_xy;     uint32_t nblocks;               /* chroma origins x | y << 16 */
+    int32_t tx_size, tx_type;                                 /* chroma transform block = chroma block (txb_count 1) */
+    const int16_t *d_iscan;
+    const uint8_t *d_txb_skip_ctx[2], *d_dc_sign_ctx[2];      /* [nblocks] per plane: cb_/cr_txb_skip_context, _dc_sign_context */
+    const int32_t *d_coeff_cost, *d_eob_cost;                 /* the PLANE_TYPE_UV tables, as svt_hip_coeff_rate_group */
+    uint64_t *d_dist;   /* [nblocks][2 planes][33][2]  {DIST_CALC_RESIDUAL, DIST_CALC_PREDICTION} >> 2 */
+    uint64_t *d_bits;   /* [nblocks][2][33] */
+    uint16_t *d_eob;    /* [nblocks][2][33] */
+} svt_hip_cfl_search_group;
+size_t svt_hip_cfl_search_scratch_bytes(const svt_hip_cfl_search_group *groups, int ngroups);   /* HOST; 0: bad parameters or nothing to do */
+int svt_hip_cfl_search_frame(const svt_hip_cfl_search_group *groups, int ngroups, int flavour,
+                             const svt_hip_qrows *q_cb, const svt_hip_qrows *q_cr,
+                             void *d_scratch, size_t scratch_bytes, void *stream);
+
+/* svt_hip_cfl_decide_frame: cfl_rd_pick_alpha's walk (:1587-1735) over the search call's tables, to the letter, one record per block.
+ * RDCOST(lambda, R, D) = ((R * lambda + 256) >> 9) + D * 128 in uint64 arithmetic (EbRateDistortionCost.h:73), held and compared as
+ * int64_t; sums of costs wrap as two's complement.
+ *   alpha zero     per plane, best_rd_uv[PLANE_SIGN_TO_JOINT_SIGN(plane, CFL_SIGN_ZERO, i)][plane] = RDCOST(bits[plane][0] +
+ *                  alpha_rate[js][plane][0], dist[plane][0][RESIDUAL]) for i = CFL_SIGN_NEG, CFL_SIGN_POS;
+ *   the walk       per plane, per pn_sign, c = 0 .. 15 until `c > 2 && progress < c`: entry a = 1 + 16 * (pn_sign - 1) + c (entry 0 at
+ *                  Cr, CFL_SIGN_NEG, c = 0: see above) costed under the three joint signs of i = 0 .. 2; a cost >= the joint sign's
+ *                  best is rejected (a tie keeps the earlier candidate), an accepted one sets flag = 2 and, once the other plane has
+ *                  a cost for the joint sign, competes with mode_rd + the other plane's best against best_rd (again >= rejects);
+ *   against DC     dc_rd = RDCOST(bits[0][0] + bits[1][0], dist[0][0] + dist[1][0]) + RDCOST(d_dc_mode_bits, 0); dc_rd <= best_rd
+ *                  picks UV_DC_PRED with index 0, signs 0; else UV_CFL_PRED with ind = (best_c[js][U] << 4) + best_c[js][V] and the
+ *                  `best_joint_sign < 0` branch as written (ind 0, signs 0).
+ * The two `coeffBits == INT64_MAX` breaks of the reference cannot fire (a rate is an int32 widened) and have no counterpart.
+ * alpha_q3 = cfl_idx_to_alpha of the result; a UV_DC_PRED winner has 0 in both, and alpha 0 leaves a prediction unchanged in
+ * cfl_predict, so a caller can send every block on.  Only the block index addresses memory from device data.
+ * Validated before the launch (SVT_HIP_ERR_INVALID): a NULL member other than d_alpha_q3_*, nblocks * 66 above 2^31 - 1, d_dist not
+ * 16-byte, d_bits / d_decision not 8-byte, an int32 array not 4-byte aligned.  One launch per 32 groups; enqueue only. */
+typedef struct svt_hip_cfl_decision {     /* sizeof 32, 8-byte aligned */
+    int64_t  best_rd;                     /* the CfL side's best_rd; INT64_MAX when no joint sign completed */
+    int64_t  dc_rd;                       /* RDCOST(lambda, bits[0][0] + bits[1][0], dist[0][0] + dist[1][0]) + RDCOST(lambda, dc_mode_bits, 0) */
+    int32_t  alpha_q3[2];                 /* cfl_idx_to_alpha of the result for Cb, Cr; 0, 0 for UV_DC_PRED */
+    uint8_t  uv_mode;                     /* 0 UV_DC_PRED, 13 UV_CFL_PRED */
+    uint8_t  cfl_alpha_idx, cfl_alpha_signs;
+    uint8_t  pad[5];                      /* written as 0 */
+} svt_hip_cfl_decision;
+typedef struct svt_hip_cfl_decide_group {
+    uint32_t nblocks; uint32_t lambda;                      /* full_lambda */
+    const uint64_t *d_dist, *d_bits;                        /* the search call's tables */
+    const int32_t *d_alpha_rate;                            /* cflAlphaFacBits[8][2][16], 256 words */
+    const int32_t *d_cfl_mode_bits, *d_dc_mode_bits;        /* [nblocks]: intraUVmodeFacBits[CFL_ALLOWED][intra_luma_mode][UV_CFL_PRED] / [UV_DC_PRED] */
+    svt_hip_cfl_decision *d_decision;                       /* [nblocks] */
+    int32_t *d_alpha_q3_cb, *d_alpha_q3_cr;                 /* optional [nblocks]: what svt_hip_frame_cfl_group takes */
+} svt_hip_cfl_decide_group;
+int svt_hip_cfl_decide_frame(const svt_hip_cfl_decide_group *groups, int ngroups, void *stream);
+
+/* Search then decide on `stream`, whose order carries the dependency (host composition, as svt_hip_tx_search_frame).  search.d_dist /
+ * d_bits / d_eob may be NULL: the table then lives in d_scratch.  Carved first, per non-empty group in group order: dist (nblocks *
+ * 66 * 16 bytes), bits (* 8) and eob (* 2), each only when not supplied and rounded up to 16 bytes; then the search call's own
+ * scratch.  svt_hip_cfl_pick_scratch_bytes returns the sum (HOST; 0: bad parameters or nothing to do).  Both stages' arguments are
+ * validated before the first launch. */
+typedef struct svt_hip_cfl_pick_group {
+    svt_hip_cfl_search_group search;
+    uint32_t lambda;
+    const int32_t *d_alpha_rate, *d_cfl_mode_bits, *d_dc_mode_bits;
+    svt_hip_cfl_decision *d_decision;
+    int32_t *d_alpha_q3_cb, *d_alpha_q3_cr;
+} svt_hip_cfl_pick_group;
+size_t svt_hip_cfl_pick_scratch_bytes(const svt_hip_cfl_pick_group *groups, int ngroups);
+int svt_hip_cfl_pick_frame(const svt_hip_cfl_pick_group *groups, int ngroups, int flavour,
+                           const svt_hip_qrows *q_cb, const svt_hip_qrows *q_cr,
+                           void *d_scratch, size_t scratch_bytes, void *stream);
+
 /* Open-loop intra search: open_loop_intra_search_sb, EbMotionEstimation.c:8694-8850,
  * for all blocks of ONE size of a picture (or of many pictures' worth of blocks) in one call.
  * d_pic points at picture sample (0, 0) (buffer_y + origin_y * stride_y + origin_x), width x height are
