@@ -13,10 +13,9 @@
 
 #include "dev_common.h"
 #include "group_table.h"
+#include "ois_plan.h"          // OIS_NB_ORIGIN, OIS_MAX_CAND, OIS_K_*, OisKinds: shared with the host's plan
 
 namespace svtdev {
-
-constexpr int OIS_NB_ORIGIN = 16;      // == NB_ORIGIN of kernel_intra.h (position p of an edge at index 16 + p)
 
 __device__ __forceinline__ void ois_gather_body(const uint8_t* __restrict__ pic, uint32_t stride, uint32_t width,
                                                 uint32_t height, const uint32_t* __restrict__ xy, uint32_t bsize,
@@ -98,7 +97,6 @@ __global__ __launch_bounds__(256) void ois_gather_multi_kernel(const uint8_t* __
 // contiguous run of dist[block][0 .. ncand) (candidates in fold_mask were already summed by intra_dir_kernel's SAD mode
 // and are only picked up), and the best index (first strict minimum below 64*64*255,
 // EbMotionEstimation.c:8756, 8800-8803) is taken from the same LDS row - no second pass over the matrix.
-constexpr int OIS_MAX_CAND = 61;       // MAX_OIS_CANDIDATES, EbCodingUnit.h:43
 __global__ __launch_bounds__(256) void ois_sad_kernel(const uint8_t* __restrict__ pic, uint32_t stride, const uint32_t* __restrict__ xy,
                                                       uint32_t bsize, const uint8_t* __restrict__ pred_all, size_t pred_cand_pitch,
                                                       const uint8_t* __restrict__ dc, unsigned long long const_mask,
@@ -175,12 +173,6 @@ __global__ __launch_bounds__(256) void ois_sad_kernel(const uint8_t* __restrict_
 // first strict minimum.  With a list that has no directional candidate (every 32x32 / 64x64 list, EbMotionEstimation.c:8747)
 // this is the whole open-loop search in ONE launch - no neighbour arrays, no prediction scratch.
 // ---------------------------------------------------------------------------
-enum { OIS_K_DC = 0, OIS_K_V, OIS_K_H, OIS_K_SMOOTH, OIS_K_SMOOTH_V, OIS_K_SMOOTH_H, OIS_K_PAETH, OIS_K_FOLDED };
-struct OisKinds {
-    uint8_t k[OIS_MAX_CAND + 3];             // kind of candidate c; [OIS_MAX_CAND + 2] = the list has folded candidates
-    uint8_t n_nd, nd_c[15], nd_kind[15];     // the candidates ois_nd_kernel computes itself, in list order (host-built: the kernel's loop
-};                                           // then runs 7 times, not 45 with a scalar load and a branch per folded candidate)
-
 __device__ constexpr uint8_t kOisSmWeights[128] = {          // sm_weight_arrays (ASM_AVX2/EbIntraPrediction_AVX2.h:19-38), index [bs + i]
     0, 0, 255, 128, 255, 149, 85, 64, 255, 197, 146, 105, 73, 50, 37, 32,
     255, 225, 196, 170, 145, 123, 102, 84, 68, 54, 43, 33, 26, 20, 17, 16,

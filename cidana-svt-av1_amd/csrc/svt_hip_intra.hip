@@ -5,12 +5,23 @@
 #include "kernel_intra.h"
 #include "kernel_bip.h"
 #include "kernel_ois.h"
+#include "ois_plan.h"
 
 using namespace svtdev;
 using namespace svthost;
 
 // ---- K11 chroma-from-luma helpers + av1_txb_init_levels ----
-static bool cfl_dim_ok(uint32_t v) { return v == 4 || v == 8 || v == 16 || v == 32; }
+// f(T{}) with the sample type, for the uint8_t / uint16_t launch pairs
+template <typename F> static void by_sample(int is_16bit, F&& f) { if (is_16bit) f(uint16_t{}); else f(uint8_t{}); }
+
+static bool tx_side_ok(uint32_t v) { return v == 4 || v == 8 || v == 16 || v == 32 || v == 64; }
+static bool cfl_dim_ok(uint32_t v) { return v != 64 && tx_side_ok(v); }
+// a lane takes a chunk of 4 (4-wide blocks) or 8 samples of a row; at most 64 lanes per block, slots blocks per workgroup
+struct CflLanes { uint32_t nchunks, lpb, slots; };
+static CflLanes cfl_lanes(uint32_t w, uint32_t h) {
+    const uint32_t nchunks = (w / (w < 8 ? 4 : 8)) * h, lpb = nchunks < 64 ? nchunks : 64;
+    return {nchunks, lpb, 256 / lpb};
+}
 
 static int cfl_ac_launch(int in_mode, const void* d_luma, uint32_t luma_stride, size_t luma_block_pitch, const uint32_t* d_xy,
                          int16_t* d_q3, uint32_t q3_line, size_t q3_block_pitch, uint32_t w, uint32_t h, int subtract,
@@ -21,8 +32,7 @@ static int cfl_ac_launch(int in_mode, const void* d_luma, uint32_t luma_stride, 
     if (!cfl_dim_ok(w) || !cfl_dim_ok(h)) return set_err(SVT_HIP_ERR_INVALID, "chroma block %ux%u", w, h);
     if (q3_line < w || q3_block_pitch < (size_t)q3_line * (h - 1) + w) return set_err(SVT_HIP_ERR_INVALID, "q3 layout: line %u, block pitch %zu", q3_line, q3_block_pitch);
     if (num_pel_log2 < 0 || num_pel_log2 > 31) return set_err(SVT_HIP_ERR_INVALID, "num_pel_log2 %d", num_pel_log2);
-    const uint32_t nchunks = (w / (w < 8 ? 4 : 8)) * h;
-    const uint32_t lpb = nchunks < 64 ? nchunks : 64;
+    const uint32_t lpb = cfl_lanes(w, h).lpb;
     const size_t lanes = nblocks * lpb;
     const size_t grid = (lanes + 255) / 256;
     if (grid > 0x7fffffffu || nblocks > 0x7fffffffu / 64) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
@@ -62,25 +72,35 @@ extern "C" int svt_hip_cfl_predict_batch(const int16_t* d_ac_q3, uint32_t q3_lin
     if (nblocks == 0) return SVT_HIP_OK;
     if (!d_ac_q3 || !d_pred || !d_dst || !d_alpha_q3) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
     if (!cfl_dim_ok(width) || !cfl_dim_ok(height)) return set_err(SVT_HIP_ERR_INVALID, "chroma block %ux%u", width, height);
-    if ((is_16bit && bit_depth != 8 && bit_depth != 10 && bit_depth != 12) || (!is_16bit && bit_depth != 8))
-        return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bit_depth);
+    if (!sample_depth_ok(is_16bit, bit_depth)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bit_depth);
     if (q3_line < width || pred_stride < width || dst_stride < width) return set_err(SVT_HIP_ERR_INVALID, "stride smaller than the block");
-    const uint32_t nchunks = (width / (width < 8 ? 4 : 8)) * height;
+    const uint32_t nchunks = cfl_lanes(width, height).nchunks;
     uint32_t sh = 0;
     while ((1u << sh) < nchunks) sh++;
     const size_t grid = ((nblocks << sh) + 255) / 256;
     if (grid > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
     const int hi = (1 << bit_depth) - 1;
-    if (is_16bit)
-        hipLaunchKernelGGL((cfl_predict_kernel<uint16_t>), dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_ac_q3, q3_line,
-                           q3_block_pitch, (const uint16_t*)d_pred, pred_stride, (uint16_t*)d_dst, dst_stride, d_xy, d_alpha_q3, hi,
-                           width, height, sh, (uint32_t)nblocks);
-    else
-        hipLaunchKernelGGL((cfl_predict_kernel<uint8_t>), dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_ac_q3, q3_line,
-                           q3_block_pitch, (const uint8_t*)d_pred, pred_stride, (uint8_t*)d_dst, dst_stride, d_xy, d_alpha_q3, hi,
-                           width, height, sh, (uint32_t)nblocks);
+    by_sample(is_16bit, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((cfl_predict_kernel<T>), dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_ac_q3, q3_line, q3_block_pitch, (const T*)d_pred,
+                           pred_stride, (T*)d_dst, dst_stride, d_xy, d_alpha_q3, hi, width, height, sh, (uint32_t)nblocks);
+    });
     return launch_status("cfl_predict");
 }
+
+// The level map of a w x h coefficient block: (w + TX_PAD_HOR) * (h + TX_PAD_VER) + TX_PAD_END bytes = ndw dwords, written by lpb lanes
+// per block (a dword each, or 16 bytes when pitch and pointer allow: wide), slots blocks per workgroup; row_magic divides by a row's dwords
+struct LevelsGeom { uint32_t bytes, ndw, lpb, slots, row_magic; bool wide; };
+static LevelsGeom levels_geom(uint32_t w, uint32_t h, size_t pitch, const void* ptr) {
+    const uint32_t bytes = (w + 4) * (h + 6) + 16, ndw = bytes >> 2;
+    const bool wide = (pitch & 15) == 0 && ((uintptr_t)ptr & 15) == 0;
+    const uint32_t items = wide ? (ndw + 3) / 4 : ndw;
+    uint32_t lpb = 1;
+    while (lpb < items && lpb < 256) lpb <<= 1;
+    return {bytes, ndw, lpb, 256 / lpb, (uint32_t)(0x100000000ull / ((w + 4) >> 2)) + 1u, wide};
+}
+// get_txb_wide / get_txb_high: a side of the packed coefficient block (a 64-sample side keeps its 32 low-frequency columns / rows)
+static uint32_t txb_side(int v) { return v > 32 ? 32u : (uint32_t)v; }
 
 extern "C" int svt_hip_txb_init_levels_batch(const int32_t* d_coeff, size_t coeff_block_pitch, uint8_t* d_levels_buf,
                                              size_t levels_block_pitch, uint32_t width, uint32_t height, size_t nblocks,
@@ -88,27 +108,15 @@ extern "C" int svt_hip_txb_init_levels_batch(const int32_t* d_coeff, size_t coef
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
     if (!d_coeff || !d_levels_buf) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    auto ok = [](uint32_t v) { return v == 4 || v == 8 || v == 16 || v == 32 || v == 64; };
-    if (!ok(width) || !ok(height)) return set_err(SVT_HIP_ERR_INVALID, "block %ux%u", width, height);
-    const uint32_t bytes = (width + 4) * (height + 6) + 16;      // (W + TX_PAD_HOR) * (H + TX_PAD_VER) + TX_PAD_END
-    if (levels_block_pitch < bytes || (levels_block_pitch & 3) || ((uintptr_t)d_levels_buf & 3))
-        return set_err(SVT_HIP_ERR_INVALID, "levels buffer: %zu B per block (need >= %u, multiple of 4, 4-byte aligned)", levels_block_pitch, bytes);
+    if (!tx_side_ok(width) || !tx_side_ok(height)) return set_err(SVT_HIP_ERR_INVALID, "block %ux%u", width, height);
+    const LevelsGeom lg = levels_geom(width, height, levels_block_pitch, d_levels_buf);
+    if (levels_block_pitch < lg.bytes || (levels_block_pitch & 3) || ((uintptr_t)d_levels_buf & 3))
+        return set_err(SVT_HIP_ERR_INVALID, "levels buffer: %zu B per block (need >= %u, multiple of 4, 4-byte aligned)", levels_block_pitch, lg.bytes);
     if (coeff_block_pitch < (size_t)width * height) return set_err(SVT_HIP_ERR_INVALID, "coeff_block_pitch %zu", coeff_block_pitch);
-    const uint32_t ndw = bytes >> 2, dpr = (width + 4) >> 2;
-    const bool wide = (levels_block_pitch & 15) == 0 && ((uintptr_t)d_levels_buf & 15) == 0;
-    const uint32_t items = wide ? (ndw + 3) / 4 : ndw;
-    uint32_t lpb = 1;
-    while (lpb < items && lpb < 256) lpb <<= 1;
-    const uint32_t slots = 256 / lpb;
-    const size_t grid = (nblocks + slots - 1) / slots;
+    const size_t grid = (nblocks + lg.slots - 1) / lg.slots;
     if (grid > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
-    const uint32_t row_magic = (uint32_t)(0x100000000ull / dpr) + 1u;
-    if (wide)
-        hipLaunchKernelGGL(txb_init_levels_kernel<true>, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_coeff, coeff_block_pitch,
-                           d_levels_buf, levels_block_pitch, width, height, lpb, ndw, row_magic, (uint32_t)nblocks);
-    else
-        hipLaunchKernelGGL(txb_init_levels_kernel<false>, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_coeff, coeff_block_pitch,
-                           d_levels_buf, levels_block_pitch, width, height, lpb, ndw, row_magic, (uint32_t)nblocks);
+    hipLaunchKernelGGL(lg.wide ? txb_init_levels_kernel<true> : txb_init_levels_kernel<false>, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_coeff,
+                       coeff_block_pitch, d_levels_buf, levels_block_pitch, width, height, lg.lpb, lg.ndw, lg.row_magic, (uint32_t)nblocks);
     return launch_status("txb_init_levels");
 }
 
@@ -123,18 +131,12 @@ static int frame_levels_launch(const svt_hip_frame_group* groups, const svt_hip_
         const svt_hip_frame_group& G = groups[g];
         const svt_hip_frame_levels& L = levels[g];
         if (!G.nblocks || !L.d_levels_buf) continue;
-        // get_txb_wide / get_txb_high: the packed coefficient block (a 64-sample side keeps its 32 low-frequency columns / rows)
-        const uint32_t w = (uint32_t)(kTxW[G.tx_size] > 32 ? 32 : kTxW[G.tx_size]), h = (uint32_t)(kTxH[G.tx_size] > 32 ? 32 : kTxH[G.tx_size]);
-        const uint32_t bytes = (w + 4) * (h + 6) + 16, ndw = bytes >> 2, dpr = (w + 4) >> 2;
-        const bool wide = (L.levels_block_pitch & 15) == 0 && ((uintptr_t)L.d_levels_buf & 15) == 0;
-        const uint32_t items = wide ? (ndw + 3) / 4 : ndw;
-        uint32_t lpb = 1;
-        while (lpb < items && lpb < 256) lpb <<= 1;
-        const uint32_t slots = 256 / lpb;
-        LevelsGroupDev* D = tab.add((G.nblocks + slots - 1) / slots, launch);      // (nblocks < 2^31: checked by the caller)
+        const uint32_t w = txb_side(kTxW[G.tx_size]), h = txb_side(kTxH[G.tx_size]);
+        const LevelsGeom lg = levels_geom(w, h, L.levels_block_pitch, L.d_levels_buf);
+        LevelsGroupDev* D = tab.add((G.nblocks + lg.slots - 1) / lg.slots, launch);      // (nblocks < 2^31: checked by the caller)
         if (!D) return tab.rc;
-        D->coeff = G.d_qcoeff; D->levels = L.d_levels_buf; D->levels_pitch = (uint32_t)L.levels_block_pitch; D->w = w; D->h = h; D->lpb = lpb; D->ndw = ndw;
-        D->row_magic = (uint32_t)(0x100000000ull / dpr) + 1u; D->nblocks = G.nblocks; D->wide = wide;
+        D->coeff = G.d_qcoeff; D->levels = L.d_levels_buf; D->levels_pitch = (uint32_t)L.levels_block_pitch; D->w = w; D->h = h; D->lpb = lg.lpb; D->ndw = lg.ndw;
+        D->row_magic = lg.row_magic; D->nblocks = G.nblocks; D->wide = lg.wide;
     }
     return tab.flush(launch);
 }
@@ -148,7 +150,7 @@ extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, 
     if (ngroups > 256) return set_err(SVT_HIP_ERR_INVALID, "more than 256 groups in one call");
     if (ncfl > CFL_MAX_GROUPS) return set_err(SVT_HIP_ERR_INVALID, "%d chroma-from-luma groups (at most %d: one per chroma transform size)", ncfl, CFL_MAX_GROUPS);
     if (ncfl && (first_chroma_group < 0 || first_chroma_group > ngroups)) return set_err(SVT_HIP_ERR_INVALID, "first_chroma_group %d of %d", first_chroma_group, ngroups);
-    if ((is_16bit && bd != 8 && bd != 10 && bd != 12) || (!is_16bit && bd != 8)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
+    if (!sample_depth_ok(is_16bit, bd)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
     // everything is validated before anything is enqueued
     if (int rc = frame_groups_check(groups, ngroups)) return rc;
     GroupTable<CflFrameDesc, CFL_MAX_GROUPS> ctab;       // (ncfl <= CFL_MAX_GROUPS: one launch, after the luma pass)
@@ -160,11 +162,10 @@ extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, 
         if (!cfl_dim_ok(C.width) || !cfl_dim_ok(C.height)) return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: chroma block %ux%u", g, C.width, C.height);
         if (C.luma_stride < 2 * C.width || C.pred_stride_cb < C.width || C.pred_stride_cr < C.width)
             return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: stride smaller than the block", g);
-        const uint32_t nchunks = (C.width / (C.width < 8 ? 4 : 8)) * C.height, lpb = nchunks < 64 ? nchunks : 64, slots = 256 / lpb;
-        const uint32_t wgs = (C.nblocks - 1) / slots + 1;
-        CflGroupDev* D = ctab.add(wgs);
+        const CflLanes lanes = cfl_lanes(C.width, C.height);
+        CflGroupDev* D = ctab.add((C.nblocks - 1) / lanes.slots + 1);
         if (!D) return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: too many blocks for one launch", g);
-        D->lpb = lpb;
+        D->lpb = lanes.lpb;
         D->luma = C.d_luma_recon; D->cb = C.d_pred_cb; D->cr = C.d_pred_cr; D->xy = C.d_xy; D->alpha_cb = C.d_alpha_q3_cb; D->alpha_cr = C.d_alpha_q3_cr;
         D->luma_stride = C.luma_stride; D->cb_stride = C.pred_stride_cb; D->cr_stride = C.pred_stride_cr; D->nblocks = C.nblocks; D->w = C.width; D->h = C.height;
         D->round_offset = (int32_t)(C.width * C.height / 2);
@@ -174,8 +175,7 @@ extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, 
         for (int g = 0; g < ngroups; g++) {
             const svt_hip_frame_levels& L = levels[g];
             if (!groups[g].nblocks || !L.d_levels_buf) continue;
-            const uint32_t w = (uint32_t)(kTxW[groups[g].tx_size] > 32 ? 32 : kTxW[groups[g].tx_size]), h = (uint32_t)(kTxH[groups[g].tx_size] > 32 ? 32 : kTxH[groups[g].tx_size]);
-            const size_t bytes = (size_t)(w + 4) * (h + 6) + 16;
+            const size_t bytes = levels_geom(txb_side(kTxW[groups[g].tx_size]), txb_side(kTxH[groups[g].tx_size]), L.levels_block_pitch, L.d_levels_buf).bytes;
             if (L.levels_block_pitch < bytes || (L.levels_block_pitch & 3) || ((uintptr_t)L.d_levels_buf & 3) || L.levels_block_pitch > 0xffffffffu)
                 return set_err(SVT_HIP_ERR_INVALID, "group %d: levels buffer %zu B per block (need >= %zu, multiple of 4, 4-byte aligned)", g, L.levels_block_pitch, bytes);
             if (groups[g].nblocks > kMaxLaunchWgs) return set_err(SVT_HIP_ERR_INVALID, "group %d: too many blocks for one launch", g);
@@ -187,8 +187,7 @@ extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, 
     if (ctab.size()) {
         const int hi = (1 << bd) - 1;
         if (int rc = ctab.flush([&](const CflFrameDesc& cd, uint32_t total) {
-                if (is_16bit) hipLaunchKernelGGL((cfl_frame_kernel<uint16_t>), dim3(total), dim3(256), 0, s, cd, hi);
-                else hipLaunchKernelGGL((cfl_frame_kernel<uint8_t>), dim3(total), dim3(256), 0, s, cd, hi);
+                by_sample(is_16bit, [&](auto t) { hipLaunchKernelGGL((cfl_frame_kernel<decltype(t)>), dim3(total), dim3(256), 0, s, cd, hi); });
                 return launch_status("cfl_frame");
             })) return rc;
         if (int rc = svt_hip_encode_recon_frame(groups + n_first, ngroups - n_first, is_16bit, bd, zbin, round, quant, quant_shift, dequant, stream)) return rc;
@@ -198,25 +197,29 @@ extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, 
 }
 
 static bool intra_size_ok(int bw, int bh) {
-    auto ok1 = [](int v) { return v == 4 || v == 8 || v == 16 || v == 32 || v == 64; };
-    if (!ok1(bw) || !ok1(bh)) return false;
+    if (!tx_side_ok((uint32_t)bw) || !tx_side_ok((uint32_t)bh)) return false;
     const int m = bw > bh ? bw : bh, mn = bw < bh ? bw : bh;
     return m <= 4 * mn;     // the 19 TX sizes
 }
 
-static int intra_pred_impl(void* d_dst, int32_t dst_stride, size_t dst_block_pitch,
-                           const uint32_t* d_dst_offsets, const void* d_above, const void* d_left,
-                           int32_t nb_pitch, int mode, int bw, int bh, int upsample_above,
-                           int upsample_left, int dx, int dy, int is_16bit, int bd, size_t nblocks,
-                           void* stream, const DirMulti* multi);
-
-extern "C" int svt_hip_intra_pred_batch(void* d_dst, int32_t dst_stride, size_t dst_block_pitch,
-                                        const uint32_t* d_dst_offsets, const void* d_above, const void* d_left,
-                                        int32_t nb_pitch, int mode, int bw, int bh, int upsample_above,
-                                        int upsample_left, int dx, int dy, int is_16bit, int bd, size_t nblocks,
-                                        void* stream) {
-    return intra_pred_impl(d_dst, dst_stride, dst_block_pitch, d_dst_offsets, d_above, d_left, nb_pitch, mode, bw, bh,
-                           upsample_above, upsample_left, dx, dy, is_16bit, bd, nblocks, stream, nullptr);
+// zone 2's per-angle tables of the left-edge terms, see DirMulti
+static void dir_z2_tables(DirMulti& d) {
+    d.z2_tab = 1;
+    for (int a = 0; a < d.n; a++)
+        for (int k = 0; k < 16; k++) {
+            const int ys = -(int)d.dy[a] * (k + 1);
+            const uint32_t sh = ((uint32_t)ys & 63u) >> 1;
+            d.z2_w2[a][k] = (32u - sh) | (sh << 16);
+            d.z2_ol[a][k] = 4 * (ys >> 6);
+        }
+}
+// angles per workgroup (chunk) and the parts over grid.y: all n angles in one part when the batch alone gives `want` workgroups, else
+// split (each part re-stages the edges).  No angles: no part.
+static void dir_angle_split(int n, size_t grid, size_t want, int& chunk, uint32_t& grid_y) {
+    size_t parts = (g_tune_dir_no_split || grid >= want) ? 1 : (want + grid - 1) / grid;
+    if (parts > (size_t)n) parts = (size_t)n;
+    chunk = n ? (int)((n + parts - 1) / parts) : 1;
+    grid_y = n ? (uint32_t)((n + chunk - 1) / chunk) : 0;
 }
 
 // multi (directional modes only): several (dx, dy) of the same zone in one launch on edges staged once, see DirMulti
@@ -230,7 +233,7 @@ static int intra_pred_impl(void* d_dst, int32_t dst_stride, size_t dst_block_pit
     if (!d_dst || !d_above || !d_left) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
     if (mode < 0 || mode >= SVT_INTRA_MODES) return set_err(SVT_HIP_ERR_INVALID, "intra mode %d", mode);
     if (!intra_size_ok(bw, bh)) return set_err(SVT_HIP_ERR_INVALID, "block %dx%d is not an AV1 transform size", bw, bh);
-    if ((is_16bit && bd != 10 && bd != 12 && bd != 8) || (!is_16bit && bd != 8)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
+    if (!sample_depth_ok(is_16bit, bd)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
     if ((upsample_above | upsample_left) & ~1) return set_err(SVT_HIP_ERR_INVALID, "upsample flags");
     if (mode >= SVT_INTRA_Z1) {
         if (dx <= 0 || dy <= 0) return set_err(SVT_HIP_ERR_INVALID, "dx/dy must be positive");
@@ -259,26 +262,11 @@ static int intra_pred_impl(void* d_dst, int32_t dst_stride, size_t dst_block_pit
         DirMulti dm;
         if (multi) dm = *multi; else dm.n = 0;
         dm.z2_tab = 0;
-        if (dm.n > 0 && mode == SVT_INTRA_Z2 && bw == ppl && (upsample_above | upsample_left) == 0) {     // see DirMulti
-            dm.z2_tab = 1;
-            for (int a = 0; a < dm.n; a++)
-                for (int k = 0; k < 16; k++) {
-                    const int ys = -(int)dm.dy[a] * (k + 1);
-                    const uint32_t sh = ((uint32_t)ys & 63u) >> 1;
-                    dm.z2_w2[a][k] = (32u - sh) | (sh << 16);
-                    dm.z2_ol[a][k] = 4 * (ys >> 6);
-                }
-        }
+        if (dm.n > 0 && mode == SVT_INTRA_Z2 && bw == ppl && (upsample_above | upsample_left) == 0) dir_z2_tables(dm);     // see DirMulti
         // angles per workgroup: all of them when the batch alone gives every CU a few workgroups, else split over grid.y (each part re-stages the edges)
         uint32_t gy = 1;
-        dm.chunk = dm.n > 0 ? dm.n : 1;
-        if (dm.n > 1 && !g_tune_dir_no_split) {
-            const size_t want = (size_t)g_tune_dir_split_target * (size_t)g_num_cu;
-            size_t parts = grid >= want ? 1 : (want + grid - 1) / grid;
-            if (parts > (size_t)dm.n) parts = (size_t)dm.n;
-            dm.chunk = (int)((dm.n + parts - 1) / parts);
-            gy = (uint32_t)((dm.n + dm.chunk - 1) / dm.chunk);
-        }
+        dm.chunk = 1;
+        if (dm.n > 0) dir_angle_split(dm.n, grid, (size_t)g_tune_dir_split_target * (size_t)g_num_cu, dm.chunk, gy);
 #define IDL(T, M, P, TB)                                                                                                     \
     hipLaunchKernelGGL((intra_dir_kernel<T, M, P, TB>), dim3((uint32_t)grid, gy), dim3(256), shmem, s, (T*)d_dst, dst_stride, \
                        dst_block_pitch, d_dst_offsets, (const T*)d_above, (const T*)d_left, nb_pitch, bw, bh,               \
@@ -324,6 +312,15 @@ static int intra_pred_impl(void* d_dst, int32_t dst_stride, size_t dst_block_pit
     return launch_status("intra_pred");
 }
 
+extern "C" int svt_hip_intra_pred_batch(void* d_dst, int32_t dst_stride, size_t dst_block_pitch,
+                                        const uint32_t* d_dst_offsets, const void* d_above, const void* d_left,
+                                        int32_t nb_pitch, int mode, int bw, int bh, int upsample_above,
+                                        int upsample_left, int dx, int dy, int is_16bit, int bd, size_t nblocks,
+                                        void* stream) {
+    return intra_pred_impl(d_dst, dst_stride, dst_block_pitch, d_dst_offsets, d_above, d_left, nb_pitch, mode, bw, bh,
+                           upsample_above, upsample_left, dx, dy, is_16bit, bd, nblocks, stream, nullptr);
+}
+
 extern "C" int svt_hip_filter_intra_edge_batch(void* d_edges, int32_t nb_pitch, int sz, int strength, int is_16bit,
                                                size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
@@ -332,10 +329,9 @@ extern "C" int svt_hip_filter_intra_edge_batch(void* d_edges, int32_t nb_pitch, 
     if (sz < 1 || sz > 129 || strength < 0 || strength > 3 || nb_pitch < NB_ORIGIN + sz)
         return set_err(SVT_HIP_ERR_INVALID, "edge sz %d strength %d pitch %d", sz, strength, nb_pitch);
     hipStream_t s = (hipStream_t)stream;
-    if (is_16bit)
-        hipLaunchKernelGGL((filter_edge_kernel<uint16_t>), dim3((uint32_t)nblocks), dim3(256), 0, s, (uint16_t*)d_edges, nb_pitch, NB_ORIGIN, sz, strength, (uint32_t)nblocks);
-    else
-        hipLaunchKernelGGL((filter_edge_kernel<uint8_t>), dim3((uint32_t)nblocks), dim3(256), 0, s, (uint8_t*)d_edges, nb_pitch, NB_ORIGIN, sz, strength, (uint32_t)nblocks);
+    by_sample(is_16bit, [&](auto t) {
+        hipLaunchKernelGGL((filter_edge_kernel<decltype(t)>), dim3((uint32_t)nblocks), dim3(256), 0, s, (decltype(t)*)d_edges, nb_pitch, NB_ORIGIN, sz, strength, (uint32_t)nblocks);
+    });
     return launch_status("filter_intra_edge");
 }
 extern "C" int svt_hip_upsample_intra_edge_batch(void* d_edges, int32_t nb_pitch, int sz, int is_16bit, int bd,
@@ -345,15 +341,12 @@ extern "C" int svt_hip_upsample_intra_edge_batch(void* d_edges, int32_t nb_pitch
     if (!d_edges) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
     if (sz < 1 || sz > 16 || nb_pitch < NB_ORIGIN + 2 * sz) return set_err(SVT_HIP_ERR_INVALID, "upsample sz %d pitch %d", sz, nb_pitch);
     hipStream_t s = (hipStream_t)stream;
-    if (is_16bit)
-        hipLaunchKernelGGL((upsample_edge_kernel<uint16_t>), dim3((uint32_t)nblocks), dim3(64), 0, s, (uint16_t*)d_edges, nb_pitch, NB_ORIGIN, sz, bd, (uint32_t)nblocks);
-    else
-        hipLaunchKernelGGL((upsample_edge_kernel<uint8_t>), dim3((uint32_t)nblocks), dim3(64), 0, s, (uint8_t*)d_edges, nb_pitch, NB_ORIGIN, sz, 8, (uint32_t)nblocks);
+    by_sample(is_16bit, [&](auto t) {
+        hipLaunchKernelGGL((upsample_edge_kernel<decltype(t)>), dim3((uint32_t)nblocks), dim3(64), 0, s, (decltype(t)*)d_edges, nb_pitch, NB_ORIGIN, sz, is_16bit ? bd : 8, (uint32_t)nblocks);
+    });
     return launch_status("upsample_intra_edge");
 }
 
-// ===========================================================================
-// (A) drop-in entry points: host pointers, one block, synchronous
 // ---- build_intra_predictors{,_high} for a batch (EbIntraPrediction.c:3667-4076), see kernel_bip.h ----
 namespace svtdev {
 // ---- ordering pass: block indices grouped by kind inside TILES of BIP_ORDER_TILE consecutive blocks (a counting sort over the
@@ -406,12 +399,11 @@ template <int W, int H>
 static int bip_launch(void* d_dst, int32_t dst_stride, size_t dst_block_pitch, const uint32_t* d_dst_offsets, const void* d_top_neigh,
                       const void* d_left_neigh, int32_t neigh_pitch, const svt_hip_intra_blk* d_blocks, const uint32_t* d_order, int is_16bit,
                       int bd, size_t nblocks, uint32_t grid, hipStream_t s) {
-    if (is_16bit)
-        hipLaunchKernelGGL((bip_kernel<uint16_t, W, H>), dim3(grid), dim3(64 * BIP_WAVES), 0, s, (uint16_t*)d_dst, dst_stride, dst_block_pitch, d_dst_offsets,
-                           (const uint16_t*)d_top_neigh, (const uint16_t*)d_left_neigh, neigh_pitch, (const BipBlk*)d_blocks, d_order, bd, (uint32_t)nblocks);
-    else
-        hipLaunchKernelGGL((bip_kernel<uint8_t, W, H>), dim3(grid), dim3(64 * BIP_WAVES), 0, s, (uint8_t*)d_dst, dst_stride, dst_block_pitch, d_dst_offsets,
-                           (const uint8_t*)d_top_neigh, (const uint8_t*)d_left_neigh, neigh_pitch, (const BipBlk*)d_blocks, d_order, bd, (uint32_t)nblocks);
+    by_sample(is_16bit, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL((bip_kernel<T, W, H>), dim3(grid), dim3(64 * BIP_WAVES), 0, s, (T*)d_dst, dst_stride, dst_block_pitch, d_dst_offsets,
+                           (const T*)d_top_neigh, (const T*)d_left_neigh, neigh_pitch, (const BipBlk*)d_blocks, d_order, bd, (uint32_t)nblocks);
+    });
     return launch_status("build_intra_predictors");
 }
 static int bip_impl(void* d_dst, int32_t dst_stride, size_t dst_block_pitch, const uint32_t* d_dst_offsets, const void* d_top_neigh,
@@ -421,7 +413,7 @@ static int bip_impl(void* d_dst, int32_t dst_stride, size_t dst_block_pitch, con
     if (nblocks == 0) return SVT_HIP_OK;
     if (!d_dst || !d_top_neigh || !d_left_neigh || !d_blocks) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
     if (tx_size < 0 || tx_size >= SVT_TX_SIZES_ALL) return set_err(SVT_HIP_ERR_INVALID, "tx_size %d", tx_size);
-    if ((is_16bit && bd != 10 && bd != 12 && bd != 8) || (!is_16bit && bd != 8)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
+    if (!sample_depth_ok(is_16bit, bd)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
     const int w = kTxW[tx_size], h = kTxH[tx_size];
     if (neigh_pitch < 1 + 2 * (w > h ? w : h)) return set_err(SVT_HIP_ERR_INVALID, "neigh_pitch %d < %d", neigh_pitch, 1 + 2 * (w > h ? w : h));
     if (dst_stride < w) return set_err(SVT_HIP_ERR_INVALID, "dst_stride %d < width %d", dst_stride, w);
@@ -467,277 +459,138 @@ extern "C" int svt_hip_intra_order_blocks_batch(const svt_hip_intra_blk* d_block
     return launch_status("intra_order_blocks");
 }
 
-// ---- open-loop intra search ----
-static size_t ois_nb_pitch(uint32_t bsize) { return (size_t)NB_ORIGIN + 4 * bsize + 16; }     // multiple of 16
-static size_t ois_align(size_t v) { return (v + 255) & ~(size_t)255; }
+// ---- open-loop intra search: check, plan (ois_plan.h), enqueue ----
+static_assert(sizeof(DirMulti::dx) == kDirMaxAngles * sizeof(int16_t) && sizeof(DirMultiLite::dx) == sizeof(DirMulti::dx) && OIS_NB_ORIGIN == NB_ORIGIN, "ois_plan.h");
+extern "C" size_t svt_hip_ois_work_bytes(uint32_t bsize, int ncand, size_t nblocks) { return ois_work_layout(bsize, ncand, nblocks).total; }
 
-extern "C" size_t svt_hip_ois_work_bytes(uint32_t bsize, int ncand, size_t nblocks) {
-    if ((bsize != 8 && bsize != 16 && bsize != 32 && bsize != 64) || ncand <= 0 || ncand > 61) return 0;
-    return 2 * ois_align(nblocks * ois_nb_pitch(bsize)) + ois_align(nblocks) + (size_t)ncand * ois_align(nblocks * (size_t)bsize * bsize);
+struct OisPic { const uint8_t* pic; uint32_t stride, width, height; hipStream_t s; };
+struct OisJob {            // one group, checked: its plan, its arrays, its work buffer carved (ois_work_layout)
+    OisPlan plan;
+    const uint32_t* xy; uint32_t* dist; int8_t* best; uint8_t *above, *left, *dc, *pred; size_t cand_pitch, nblocks;
+};
+
+static int ois_job(OisJob& J, const OisPic& P, const svt_hip_ois_group& G) {
+    if (!P.pic || !G.d_xy || !G.d_distortion || !G.d_best_index || !G.d_work || !G.modes || !G.angle_deltas) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
+    if (int rc = ois_plan(J.plan, G.bsize, G.modes, G.angle_deltas, G.ncand, {g_tune_ois_no_fold != 0, g_tune_ois_no_nd != 0, g_tune_ois_no_dir3 != 0}))
+        return set_err(rc, "%s", J.plan.err);
+    if (P.width == 0 || P.height == 0 || P.width > 0xffffu || P.height > 0xffffu || P.stride < P.width)
+        return set_err(SVT_HIP_ERR_INVALID, "picture %ux%u stride %u", P.width, P.height, P.stride);
+    const OisWorkLayout L = ois_work_layout(G.bsize, G.ncand, G.nblocks);
+    if (G.work_bytes < L.total) return set_err(SVT_HIP_ERR_INVALID, "work buffer: %zu B, need %zu", G.work_bytes, L.total);
+    if (G.nblocks > 0x7fffffffu / 256) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
+    uint8_t* w = (uint8_t*)G.d_work;
+    J.xy = G.d_xy; J.dist = G.d_distortion; J.best = G.d_best_index; J.nblocks = G.nblocks;
+    J.above = w + L.above; J.left = w + L.left; J.dc = w + L.dc; J.pred = w + L.pred; J.cand_pitch = L.cand_pitch;
+    return SVT_HIP_OK;
 }
 
-// dr_intra_derivative (AV1 spec 7.11.2.4; reference EbIntraPrediction.c:299), non-zero entries
-static int ois_dr_derivative(int angle) {
-    static const uint16_t at[][2] = {{3, 1023}, {6, 547}, {9, 372}, {14, 273}, {17, 215}, {20, 178}, {23, 151}, {26, 132},
-                                     {29, 116}, {32, 102}, {36, 90}, {39, 80}, {42, 71}, {45, 64}, {48, 57}, {51, 51},
-                                     {54, 45}, {58, 40}, {61, 35}, {64, 31}, {67, 27}, {70, 23}, {73, 19}, {76, 15},
-                                     {81, 11}, {84, 7}, {87, 3}};
-    for (const auto& e : at)
-        if (e[0] == angle) return e[1];
-    return 0;
+static int ois_gather_enqueue(const OisPic& P, const OisJob& J) {
+    hipLaunchKernelGGL(ois_gather_kernel, dim3(ois_wgs(J.nblocks, ois_gather_slots(J.plan.bsize))), dim3(256), 0, P.s, P.pic, P.stride, P.width, P.height,
+                       J.xy, J.plan.bsize, J.above, J.left, (uint32_t)ois_nb_pitch(J.plan.bsize), J.dc, (uint32_t)J.nblocks);
+    return launch_status("ois_gather");
+}
+
+// the angles of a directional launch (S null: none); dense: each prediction to its candidate's batch in J.pred (summed as well when the
+// plan folds), else sums only
+template <typename Z>
+static void ois_dir_multi(Z& z, const OisPic& P, const OisJob& J, const OisDirSeg* S, bool dense) {
+    z.n = 0; z.batch_pitch = dense ? J.cand_pitch : 0;
+    z.sad_pic = P.pic; z.sad_stride = P.stride; z.sad_xy = J.xy; z.sad_dist = dense && !J.plan.fold ? nullptr : J.dist; z.sad_ncand = (uint32_t)J.plan.ncand;
+    if (!S) return;
+    z.n = S->n; memcpy(z.dx, S->dx, sizeof(S->dx)); memcpy(z.dy, S->dy, sizeof(S->dy)); memcpy(z.slot, S->slot, sizeof(S->slot));
+}
+static int ois_seg_enqueue(const OisPic& P, const OisJob& J, const OisDirSeg& S, bool dense) {
+    const int b = (int)J.plan.bsize;
+    DirMulti z;
+    ois_dir_multi(z, P, J, &S, dense);
+    return intra_pred_impl(dense ? (void*)J.pred : (void*)J.dist /* unused in SAD mode */, b, (size_t)b * b, nullptr, J.above, J.left, (int32_t)ois_nb_pitch(b),
+                           SVT_INTRA_Z1 + S.zone, b, b, 0, 0, 1, 1, 0, 8, J.nblocks, P.s, &z);
 }
 
 // the directional candidates of the three zones in ONE launch (ois_dir3_kernel): 8x8 / 16x16 SAD mode
-static int ois_dir3_launch(const uint8_t* d_above, const uint8_t* d_left, size_t pitch, uint32_t bsize, size_t nblocks, const DirMulti zone[3],
-                           hipStream_t s) {
-    const size_t per_block = bsize;                              // one lane per row
-    const size_t grid = (per_block * nblocks + 255) / 256;
+static int ois_dir3_enqueue(const OisPic& P, const OisJob& J) {
+    const uint32_t bsize = J.plan.bsize;                         // = lanes per block: one lane per row
+    const size_t grid = ((size_t)bsize * J.nblocks + 255) / 256;
     const int lim = NB_ORIGIN + (int)(2 * bsize - 1), n_pad = lim + 16 + 3;
-    const size_t slots = 256 / per_block;
-    const size_t shmem = slots * (size_t)dir_slot_stride((n_pad + 10) & ~7, (uint32_t)per_block) * 4 + 2 * 64 * 4;
+    const size_t shmem = (size_t)(256 / bsize) * dir_slot_stride((n_pad + 10) & ~7, bsize) * 4 + 2 * 64 * 4;
+    const OisDirSeg* of[3] = {};                                 // at most one segment per zone (OisPlan::dir3)
+    for (int i = 0; i < J.plan.nseg; i++) of[J.plan.seg[i].zone] = &J.plan.seg[i];
     DirOis3 m;
     memset(&m, 0, sizeof(m));
-    auto lite = [](DirMultiLite& d, const DirMulti& z) {
-        d.n = z.n; memcpy(d.dx, z.dx, sizeof(d.dx)); memcpy(d.dy, z.dy, sizeof(d.dy)); memcpy(d.slot, z.slot, sizeof(d.slot));
-        d.batch_pitch = 0; d.sad_pic = z.sad_pic; d.sad_stride = z.sad_stride; d.sad_xy = z.sad_xy; d.sad_dist = z.sad_dist; d.sad_ncand = z.sad_ncand; d.z2_tab = 0;
-    };
-    lite(m.z1, zone[0]); lite(m.z3, zone[2]);
-    m.z2 = zone[1];
-    m.z2.z2_tab = 1;
-    for (int a = 0; a < m.z2.n; a++)
-        for (int k = 0; k < 16; k++) {
-            const int ys = -(int)m.z2.dy[a] * (k + 1);
-            const uint32_t sh = ((uint32_t)ys & 63u) >> 1;
-            m.z2.z2_w2[a][k] = (32u - sh) | (sh << 16);
-            m.z2.z2_ol[a][k] = 4 * (ys >> 6);
-        }
+    ois_dir_multi(m.z1, P, J, of[0], false); ois_dir_multi(m.z2, P, J, of[1], false); ois_dir_multi(m.z3, P, J, of[2], false);
+    dir_z2_tables(m.z2);
     // angles per workgroup, per zone: as separate launches each zone wants dir_split_target (4) workgroups per CU before it stops
     // spreading its angles over grid.y; with the three zones in one launch the sum counts - swept 1 .. 8 on the 1080p search
     // (gpurun_out r03_f): 1 is best for 8x8 (0.0526 against 0.0567 ms at 4) and 16x16 (0.0443 against 0.0471)
-    const int nz[3] = {m.z1.n, m.z2.n, m.z3.n};
-    int chunk[3];
     uint32_t gy[3];
-    const size_t want = (size_t)g_num_cu;
-    for (int z = 0; z < 3; z++) {
-        size_t parts = (g_tune_dir_no_split || grid >= want) ? 1 : (want + grid - 1) / grid;
-        if (parts > (size_t)(nz[z] ? nz[z] : 1)) parts = (size_t)(nz[z] ? nz[z] : 1);
-        chunk[z] = nz[z] ? (int)((nz[z] + parts - 1) / parts) : 1;
-        gy[z] = nz[z] ? (uint32_t)((nz[z] + chunk[z] - 1) / chunk[z]) : 0;
-    }
-    m.z1.chunk = chunk[0]; m.z2.chunk = chunk[1]; m.z3.chunk = chunk[2];
+    dir_angle_split(m.z1.n, grid, (size_t)g_num_cu, m.z1.chunk, gy[0]);
+    dir_angle_split(m.z2.n, grid, (size_t)g_num_cu, m.z2.chunk, gy[1]);
+    dir_angle_split(m.z3.n, grid, (size_t)g_num_cu, m.z3.chunk, gy[2]);
     m.y_end[0] = gy[0]; m.y_end[1] = gy[0] + gy[1];
-    const uint32_t gyt = gy[0] + gy[1] + gy[2];
-    if (bsize == 8)
-        hipLaunchKernelGGL(ois_dir3_kernel<8>, dim3((uint32_t)grid, gyt), dim3(256), shmem, s, d_above, d_left, (int32_t)pitch, (int)bsize, lim, n_pad, (uint32_t)nblocks, m);
-    else
-        hipLaunchKernelGGL(ois_dir3_kernel<16>, dim3((uint32_t)grid, gyt), dim3(256), shmem, s, d_above, d_left, (int32_t)pitch, (int)bsize, lim, n_pad, (uint32_t)nblocks, m);
+    hipLaunchKernelGGL(bsize == 8 ? ois_dir3_kernel<8> : ois_dir3_kernel<16>, dim3((uint32_t)grid, gy[0] + gy[1] + gy[2]), dim3(256), shmem, P.s, J.above, J.left,
+                       (int32_t)ois_nb_pitch(bsize), (int)bsize, lim, n_pad, (uint32_t)J.nblocks, m);
     return launch_status("ois_dir3");
 }
 
-// `defer` (svt_hip_ois_search_frame): the non-directional launch of the group is not enqueued but described in *defer (nblocks != 0),
-// so that the caller can run every group's in ONE launch (ois_nd_multi_kernel) after the chains it depends on
-static int ois_search_impl(const uint8_t* d_pic, uint32_t stride, uint32_t width, uint32_t height,
-                           const uint32_t* d_xy, uint32_t bsize, const uint8_t* modes, const int8_t* angle_deltas,
-                           int ncand, uint32_t* d_distortion, int8_t* d_best_index, void* d_work,
-                           size_t work_bytes, size_t nblocks, void* stream, OisNdGroup* defer, int phase = 0, OisGatherGroup* gather = nullptr) {
-    // phase 0: everything; 1: enqueue nothing, describe the group's neighbour gather in *gather (nblocks != 0) if it takes the fused
-    // path; 2: the gather has been done by the caller (fused path), enqueue the rest
-    if (defer) defer->nblocks = 0;
-    if (gather) gather->nblocks = 0;
-    if (int rc = require_init()) return rc;
-    if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_pic || !d_xy || !d_distortion || !d_best_index || !d_work || !modes || !angle_deltas) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (bsize != 8 && bsize != 16 && bsize != 32 && bsize != 64) return set_err(SVT_HIP_ERR_INVALID, "block size %u", bsize);
-    if (ncand <= 0 || ncand > 61) return set_err(SVT_HIP_ERR_INVALID, "%d candidates (1..61, MAX_OIS_CANDIDATES)", ncand);
-    if (width == 0 || height == 0 || width > 0xffffu || height > 0xffffu || stride < width) return set_err(SVT_HIP_ERR_INVALID, "picture %ux%u stride %u", width, height, stride);
-    if (work_bytes < svt_hip_ois_work_bytes(bsize, ncand, nblocks)) return set_err(SVT_HIP_ERR_INVALID, "work buffer: %zu B, need %zu", work_bytes, svt_hip_ois_work_bytes(bsize, ncand, nblocks));
-    if (nblocks > 0x7fffffffu / 256) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
-    static const int mode_angle[13] = {0, 90, 180, 45, 135, 113, 157, 203, 67, 0, 0, 0, 0};      // mode_to_angle_map, EbCodingUnit.h:129
-    for (int c = 0; c < ncand; c++) {
-        if (modes[c] > 12) return set_err(SVT_HIP_ERR_INVALID, "candidate %d: prediction mode %u", c, modes[c]);
-        if (modes[c] >= 1 && modes[c] <= 8) {
-            const int a = mode_angle[modes[c]] + 3 * angle_deltas[c];
-            if (a <= 0 || a >= 270) return set_err(SVT_HIP_ERR_INVALID, "candidate %d: angle %d", c, a);
-            if (a != 90 && a != 180) {
-                const int d1 = a < 90 ? a : (a < 180 ? 180 - a : 270 - a), d2 = a < 180 && a > 90 ? a - 90 : d1;
-                if (!ois_dr_derivative(d1) || !ois_dr_derivative(d2)) return set_err(SVT_HIP_ERR_INVALID, "candidate %d: angle %d has no derivative", c, a);
-            }
-        }
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const size_t pitch = ois_nb_pitch(bsize);
-    char* w = (char*)d_work;
-    // ---- fused form: the directional candidates (angles other than 90 / 180) sum their SADs inside intra_dir_kernel (blocks of
-    // at most 64 lanes: 8x8, 16x16), everything else - DC, V, H, SMOOTH*, PAETH - is predicted and summed inside ois_nd_kernel
-    // straight from the picture; no prediction ever goes to memory.  Lists without directional candidates (all 32x32 / 64x64
-    // lists) are ONE launch.
-    {
-        OisKinds kinds;
-        memset(&kinds, 0, sizeof(kinds));
-        bool any_dir = false, nd_fits = true;             // nd_fits: the kernel's own list (7 distinct kinds; a list may repeat them)
-        for (int c = 0; c < ncand; c++) {
-            const int m = modes[c];
-            int k;
-            if (m == 0) k = OIS_K_DC;
-            else if (m <= 8) {
-                const int a = mode_angle[m] + 3 * angle_deltas[c];
-                k = a == 90 ? OIS_K_V : (a == 180 ? OIS_K_H : OIS_K_FOLDED);
-                any_dir = any_dir || k == OIS_K_FOLDED;
-            } else k = m == 9 ? OIS_K_SMOOTH : (m == 10 ? OIS_K_SMOOTH_V : (m == 11 ? OIS_K_SMOOTH_H : OIS_K_PAETH));
-            kinds.k[c] = (uint8_t)k;
-            if (k != OIS_K_FOLDED) {
-                if (kinds.n_nd >= sizeof(kinds.nd_c)) nd_fits = false;
-                else { kinds.nd_c[kinds.n_nd] = (uint8_t)c; kinds.nd_kind[kinds.n_nd] = (uint8_t)k; kinds.n_nd++; }
-            }
-        }
-        kinds.k[OIS_MAX_CAND + 2] = any_dir ? 1 : 0;              // ois_nd_kernel: rows of dist hold folded sums to pick up
-        const bool can_fold = bsize <= 16 && !g_tune_ois_no_fold;
-        if (!g_tune_ois_no_nd && nd_fits && (!any_dir || can_fold)) {
-            if (any_dir) {
-                uint8_t* d_above = (uint8_t*)w;
-                uint8_t* d_left = d_above + ois_align(nblocks * pitch);
-                uint8_t* d_dc = d_left + ois_align(nblocks * pitch);
-                // (no clearing of the neighbour arrays: the directional kernels stage positions [-2, 2 * bsize) only, all written by the gather)
-                const uint32_t slots = 256 / (2 * bsize);
-                if (phase == 1) {
-                    gather->xy = d_xy; gather->above = d_above; gather->left = d_left; gather->dc = d_dc; gather->bsize = bsize;
-                    gather->nb_pitch = (uint32_t)pitch; gather->nblocks = (uint32_t)nblocks;
-                    return SVT_HIP_OK;
-                }
-                if (phase == 0) {
-                    hipLaunchKernelGGL(ois_gather_kernel, dim3((uint32_t)((nblocks + slots - 1) / slots)), dim3(256), 0, st, d_pic, stride, width,
-                                       height, d_xy, bsize, d_above, d_left, (uint32_t)pitch, d_dc, (uint32_t)nblocks);
-                    if (int rc = launch_status("ois_gather")) return rc;
-                }
-                DirMulti zone[3];
-                for (auto& z : zone) {
-                    z.n = 0; z.batch_pitch = 0;
-                    z.sad_pic = d_pic; z.sad_stride = stride; z.sad_xy = d_xy; z.sad_dist = d_distortion; z.sad_ncand = (uint32_t)ncand;
-                }
-                bool flushed = false;                             // a zone with more than 20 angles went out on its own
-                auto flush = [&](int zi) -> int {
-                    DirMulti& z = zone[zi];
-                    if (!z.n) return SVT_HIP_OK;
-                    flushed = true;
-                    const int rc = intra_pred_impl(d_distortion /* unused in SAD mode */, (int32_t)bsize, (size_t)bsize * bsize, nullptr, d_above, d_left,
-                                                   (int32_t)pitch, SVT_INTRA_Z1 + zi, (int)bsize, (int)bsize, 0, 0, 1, 1, 0, 8, nblocks, stream, &z);
-                    z.n = 0;
-                    return rc;
-                };
-                for (int c = 0; c < ncand; c++) {
-                    if (kinds.k[c] != OIS_K_FOLDED) continue;
-                    const int a = mode_angle[modes[c]] + 3 * angle_deltas[c];
-                    const int zi = a < 90 ? 0 : (a < 180 ? 1 : 2);
-                    DirMulti& z = zone[zi];
-                    if (z.n == 20) if (int rc = flush(zi)) return rc;
-                    z.dx[z.n] = (int16_t)(zi == 0 ? ois_dr_derivative(a) : (zi == 1 ? ois_dr_derivative(180 - a) : 1));
-                    z.dy[z.n] = (int16_t)(zi == 0 ? 1 : (zi == 1 ? ois_dr_derivative(a - 90) : ois_dr_derivative(270 - a)));
-                    z.slot[z.n] = (uint8_t)c;
-                    z.n++;
-                }
-                if (!flushed && !g_tune_ois_no_dir3 && (zone[0].n > 0) + (zone[1].n > 0) + (zone[2].n > 0) >= 2) {
-                    if (int rc = ois_dir3_launch(d_above, d_left, pitch, bsize, nblocks, zone, st)) return rc;
-                } else
-                    for (int zi = 0; zi < 3; zi++) if (int rc = flush(zi)) return rc;
-            }
-            if (phase == 1) return SVT_HIP_OK;
-            const uint32_t cs = bsize < 16 ? 8 : 16, lpb = bsize * bsize / cs;
-            const uint32_t nd_slots = 256 / lpb;
-            const uint32_t nd_grid = (uint32_t)((nblocks + nd_slots - 1) / nd_slots);
-            const size_t shmem = (((size_t)nd_slots + (lpb > 64 ? 4 : 0)) * (size_t)ncand + 4) * sizeof(uint32_t);
-            if (defer) {
-                defer->xy = d_xy; defer->dist = d_distortion; defer->best_index = d_best_index; defer->bsize = bsize; defer->ncand = (uint32_t)ncand;
-                defer->nblocks = (uint32_t)nblocks; defer->kinds = kinds;
-                return SVT_HIP_OK;
-            }
-            if (cs == 8)
-                hipLaunchKernelGGL(ois_nd_kernel<8>, dim3(nd_grid), dim3(256), shmem, st, d_pic, stride, width, height, d_xy, bsize, kinds, d_distortion,
-                                   d_best_index, (uint32_t)ncand, (uint32_t)nblocks);
-            else
-                hipLaunchKernelGGL(ois_nd_kernel<16>, dim3(nd_grid), dim3(256), shmem, st, d_pic, stride, width, height, d_xy, bsize, kinds, d_distortion,
-                                   d_best_index, (uint32_t)ncand, (uint32_t)nblocks);
-            return launch_status("ois_nd");
-        }
-    }
-    if (phase == 1) return SVT_HIP_OK;                    // (the general path below gathers for itself, in phase 2)
-    uint8_t* d_above = (uint8_t*)w;
-    uint8_t* d_left = d_above + ois_align(nblocks * pitch);
-    uint8_t* d_dc = d_left + ois_align(nblocks * pitch);
-    uint8_t* d_pred = d_dc + ois_align(nblocks);
-    if (hipMemsetAsync(d_above, 0, 2 * ois_align(nblocks * pitch), st) != hipSuccess) return set_err(SVT_HIP_ERR_RUNTIME, "hipMemsetAsync");
-    {
-        const uint32_t slots = 256 / (2 * bsize);
-        hipLaunchKernelGGL(ois_gather_kernel, dim3((uint32_t)((nblocks + slots - 1) / slots)), dim3(256), 0, st, d_pic, stride, width,
-                           height, d_xy, bsize, d_above, d_left, (uint32_t)pitch, d_dc, (uint32_t)nblocks);
-        if (int rc = launch_status("ois_gather")) return rc;
-    }
-    // every candidate's prediction into its own dense batch, then ONE SAD launch over (block, candidate).  The
-    // directional candidates of one zone (up to 19) share one launch (DirMulti): 9 prediction launches for the
-    // reference's 45-candidate list instead of 44.
-    const size_t cand_pitch = ois_align(nblocks * (size_t)bsize * bsize);
-    unsigned long long const_mask = 0;
-    DirMulti zone[3];
-    // 8x8 / 16x16 (a block's lanes share a wave): the directional kernels compare each angle's prediction with the source
-    // block themselves (DirMulti SAD mode) - no prediction scratch round trip for 38 of the 45 candidates
-    const bool fold = bsize <= 16 && !g_tune_ois_no_fold;
-    unsigned long long fold_mask = 0;
-    for (auto& z : zone) {
-        z.n = 0; z.batch_pitch = cand_pitch;
-        z.sad_pic = d_pic; z.sad_stride = stride; z.sad_xy = d_xy; z.sad_dist = fold ? d_distortion : nullptr; z.sad_ncand = (uint32_t)ncand;
-    }
-    for (int c = 0; c < ncand; c++) {
-        const int m = modes[c];
-        if (m == 0) { const_mask |= 1ull << c; continue; }     // DC_PRED under the availability rule: constant prediction
-        int mode = -1;
-        if (m >= 1 && m <= 8) {                                               // dr_predictor, EbIntraPrediction.c:3352-3383
-            const int a = mode_angle[m] + 3 * angle_deltas[c];
-            if (a == 90) mode = SVT_INTRA_V;
-            else if (a == 180) mode = SVT_INTRA_H;
-            else {
-                const int zi = a < 90 ? 0 : (a < 180 ? 1 : 2);
-                DirMulti& z = zone[zi];
-                if (z.n == 20) {                                              // flush a full group (longer candidate lists)
-                    if (int rc = intra_pred_impl(d_pred, (int32_t)bsize, (size_t)bsize * bsize, nullptr, d_above, d_left, (int32_t)pitch,
-                                                 SVT_INTRA_Z1 + zi, (int)bsize, (int)bsize, 0, 0, 1, 1, 0, 8, nblocks, stream, &z))
-                        return rc;
-                    z.n = 0;
-                }
-                z.dx[z.n] = (int16_t)(zi == 0 ? ois_dr_derivative(a) : (zi == 1 ? ois_dr_derivative(180 - a) : 1));
-                z.dy[z.n] = (int16_t)(zi == 0 ? 1 : (zi == 1 ? ois_dr_derivative(a - 90) : ois_dr_derivative(270 - a)));
-                z.slot[z.n] = (uint8_t)c;
-                z.n++;
-                if (fold) fold_mask |= 1ull << c;
-                continue;
-            }
-        } else {
-            mode = m == 9 ? SVT_INTRA_SMOOTH : m == 10 ? SVT_INTRA_SMOOTH_V : m == 11 ? SVT_INTRA_SMOOTH_H : SVT_INTRA_PAETH;
-        }
-        if (int rc = svt_hip_intra_pred_batch(d_pred + (size_t)c * cand_pitch, (int32_t)bsize, (size_t)bsize * bsize, nullptr, d_above,
-                                              d_left, (int32_t)pitch, mode, (int)bsize, (int)bsize, 0, 0, 1, 1, 0, 8, nblocks, stream))
+// OIS_PATH_FUSED after the gather: the directional candidates sum their SADs into dist, the three zones in one launch or segment by segment
+// (no clearing of the neighbour arrays: the directional kernels stage positions [-2, 2 * bsize) only, all written by the gather)
+static int ois_chain_enqueue(const OisPic& P, const OisJob& J) {
+    if (J.plan.dir3) return ois_dir3_enqueue(P, J);
+    for (int i = 0; i < J.plan.nseg; i++)
+        if (int rc = ois_seg_enqueue(P, J, J.plan.seg[i], false)) return rc;
+    return SVT_HIP_OK;
+}
+
+// OIS_PATH_GENERAL: every candidate's prediction into its own dense batch, then ONE SAD launch over (block, candidate).  The directional
+// candidates of a segment share one launch (DirMulti): 9 prediction launches for the reference's 45-candidate list instead of 44.  With plan.fold
+// (8x8 / 16x16: a block's lanes share a wave) they are compared with the source block there: no scratch round trip for 38 of the 45 candidates.
+static int ois_general_enqueue(const OisPic& P, const OisJob& J) {
+    const OisPlan& plan = J.plan;
+    const int b = (int)plan.bsize;
+    if (hipMemsetAsync(J.above, 0, (size_t)(J.dc - J.above), P.s) != hipSuccess) return set_err(SVT_HIP_ERR_RUNTIME, "hipMemsetAsync");
+    if (int rc = ois_gather_enqueue(P, J)) return rc;
+    int si = 0;
+    for (int c = 0; c <= plan.ncand; c++) {                // (c = ncand: the segments still open at the end of the list)
+        for (; si < plan.nseg && plan.seg[si].before == c; si++)
+            if (int rc = ois_seg_enqueue(P, J, plan.seg[si], true)) return rc;
+        const int mode = c < plan.ncand ? ois_dense_mode(plan.kinds.k[c]) : -1;
+        if (mode < 0) continue;
+        if (int rc = svt_hip_intra_pred_batch(J.pred + (size_t)c * J.cand_pitch, b, (size_t)b * b, nullptr, J.above, J.left, (int32_t)ois_nb_pitch(b), mode,
+                                              b, b, 0, 0, 1, 1, 0, 8, J.nblocks, P.s))
             return rc;
     }
-    for (int zi = 0; zi < 3; zi++)
-        if (zone[zi].n)
-            if (int rc = intra_pred_impl(d_pred, (int32_t)bsize, (size_t)bsize * bsize, nullptr, d_above, d_left, (int32_t)pitch,
-                                         SVT_INTRA_Z1 + zi, (int)bsize, (int)bsize, 0, 0, 1, 1, 0, 8, nblocks, stream, &zone[zi]))
-                return rc;
-    {
-        const uint32_t lpb = bsize * bsize / (bsize < 16 ? 8 : 16);
-        const uint32_t sad_slots = 256 / lpb;
-        const uint32_t sad_grid = (uint32_t)((nblocks + sad_slots - 1) / sad_slots);
-        const size_t shmem = ((size_t)sad_slots + (lpb > 64 ? 4 : 0)) * (size_t)ncand * sizeof(uint32_t);
-        hipLaunchKernelGGL(ois_sad_kernel, dim3(sad_grid), dim3(256), shmem, st, d_pic, stride, d_xy, bsize, d_pred, cand_pitch,
-                           d_dc, const_mask, fold_mask, d_distortion, d_best_index, (uint32_t)ncand, (uint32_t)nblocks);
-    }
+    const OisLanes g = ois_lanes(plan.bsize, plan.ncand);
+    hipLaunchKernelGGL(ois_sad_kernel, dim3(ois_wgs(J.nblocks, g.slots)), dim3(256), g.shmem, P.s, P.pic, P.stride, J.xy,
+                       plan.bsize, J.pred, J.cand_pitch, J.dc, (unsigned long long)plan.const_mask, (unsigned long long)plan.fold_mask, J.dist, J.best,
+                       (uint32_t)plan.ncand, (uint32_t)J.nblocks);
     return launch_status("ois_sad");
+}
+
+// A whole group on its own.  The last launch of the fused paths: everything but the directional candidates - DC, V, H, SMOOTH*, PAETH -
+// predicted and summed straight from the picture, the folded sums picked up, each block's best index taken; no prediction goes to memory
+static int ois_enqueue(const OisPic& P, const OisJob& J) {
+    if (J.plan.path == OIS_PATH_GENERAL) return ois_general_enqueue(P, J);
+    if (J.plan.path == OIS_PATH_FUSED) {
+        if (int rc = ois_gather_enqueue(P, J)) return rc;
+        if (int rc = ois_chain_enqueue(P, J)) return rc;
+    }
+    const OisLanes g = ois_lanes(J.plan.bsize, J.plan.ncand, 4);
+    hipLaunchKernelGGL(g.cs == 8 ? ois_nd_kernel<8> : ois_nd_kernel<16>, dim3(ois_wgs(J.nblocks, g.slots)), dim3(256), g.shmem, P.s, P.pic, P.stride, P.width, P.height,
+                       J.xy, J.plan.bsize, J.plan.kinds, J.dist, J.best, (uint32_t)J.plan.ncand, (uint32_t)J.nblocks);
+    return launch_status("ois_nd");
 }
 
 extern "C" int svt_hip_ois_search_batch(const uint8_t* d_pic, uint32_t stride, uint32_t width, uint32_t height,
                                         const uint32_t* d_xy, uint32_t bsize, const uint8_t* modes, const int8_t* angle_deltas,
                                         int ncand, uint32_t* d_distortion, int8_t* d_best_index, void* d_work,
                                         size_t work_bytes, size_t nblocks, void* stream) {
-    return ois_search_impl(d_pic, stride, width, height, d_xy, bsize, modes, angle_deltas, ncand, d_distortion, d_best_index, d_work, work_bytes,
-                           nblocks, stream, nullptr);
+    if (int rc = require_init()) return rc;
+    if (nblocks == 0) return SVT_HIP_OK;
+    const OisPic P = {d_pic, stride, width, height, (hipStream_t)stream};
+    const svt_hip_ois_group G = {d_xy, bsize, modes, angle_deltas, ncand, d_distortion, d_best_index, d_work, work_bytes, nblocks};
+    OisJob J;
+    if (int rc = ois_job(J, P, G)) return rc;
+    return ois_enqueue(P, J);
 }
 
 extern "C" int svt_hip_ois_search_frame(const uint8_t* d_pic, uint32_t stride, uint32_t width, uint32_t height,
@@ -745,67 +598,62 @@ extern "C" int svt_hip_ois_search_frame(const uint8_t* d_pic, uint32_t stride, u
     if (int rc = require_init()) return rc;
     if (ngroups == 0) return SVT_HIP_OK;
     if (!groups || ngroups < 0 || ngroups > 64) return set_err(SVT_HIP_ERR_INVALID, "group list");
-    // Every group's chain (neighbour gather, the three directional zones in one launch) goes out on the caller's stream, one after
-    // the other - each fills the GPU - and the non-directional launch of EVERY group, which also takes each block's best index,
-    // follows as ONE launch (ois_nd_multi_kernel).  Round 2 ran the single-launch groups (every 32x32 / 64x64 list) on a side stream;
-    // they did not hide behind the chains (the call cost 0.134 ms per 1080p picture against 0.140 for the four groups in sequence:
-    // the chains leave no free units), so the side stream, its fork / join events and two ~ 20 us latency-bound launches are gone.
-    // (svt_hip_tune("ois_no_nd_multi", 1): one non-directional launch per group, on the caller's stream.)
-    hipStream_t s = (hipStream_t)stream;
+    // every group is checked and planned before anything is enqueued
+    const OisPic P = {d_pic, stride, width, height, (hipStream_t)stream};
+    OisJob jobs[64];
+    int njobs = 0;
+    for (int g = 0; g < ngroups; g++) {
+        if (groups[g].nblocks == 0) continue;
+        if (int rc = ois_job(jobs[njobs++], P, groups[g])) return rc;
+    }
+    // Every group's chain (neighbour gather, the directional launches) goes out on the caller's stream, one after the other - each fills
+    // the GPU - and the non-directional launch of EVERY group, which also takes each block's best index, follows as ONE launch
+    // (ois_nd_multi_kernel; a side stream for the single-launch groups did not hide them behind the chains).
+    // svt_hip_tune("ois_no_nd_multi", 1): every group as svt_hip_ois_search_batch runs it.
+    if (g_tune_ois_no_nd_multi) {
+        for (int j = 0; j < njobs; j++)
+            if (int rc = ois_enqueue(P, jobs[j])) return rc;
+        return SVT_HIP_OK;
+    }
+    // the neighbour gathers of the groups that have directional candidates: one launch, first
+    GroupTable<OisGatherMulti, OIS_GATHER_MAX_GROUPS> gather;
+    auto gather_launch = [&](const OisGatherMulti& gm, uint32_t total) -> int {
+        hipLaunchKernelGGL(ois_gather_multi_kernel, dim3(total), dim3(256), 0, P.s, d_pic, stride, width, height, gm);
+        return launch_status("ois_gather_multi");
+    };
+    for (int j = 0; j < njobs; j++) {
+        const OisJob& J = jobs[j];
+        if (J.plan.path != OIS_PATH_FUSED) continue;
+        OisGatherGroup* D = gather.add(ois_wgs(J.nblocks, ois_gather_slots(J.plan.bsize)), gather_launch);
+        if (!D) return gather.rc;
+        D->xy = J.xy; D->above = J.above; D->left = J.left; D->dc = J.dc; D->bsize = J.plan.bsize;
+        D->nb_pitch = (uint32_t)ois_nb_pitch(J.plan.bsize); D->nblocks = (uint32_t)J.nblocks;
+    }
+    if (int rc = gather.flush(gather_launch)) return rc;
     // largest blocks first: their workgroups are the longest latency chains (64x64: one block per workgroup, two barriers)
     GroupTable<OisNdMulti, OIS_ND_MAX_GROUPS, true> nd;
     size_t shmem = 0;                           // of the launch: the largest of its groups
     auto nd_launch = [&](const OisNdMulti& m, uint32_t total) -> int {
-        hipLaunchKernelGGL(ois_nd_multi_kernel, dim3(total), dim3(256), shmem, s, d_pic, stride, width, height, m);
+        hipLaunchKernelGGL(ois_nd_multi_kernel, dim3(total), dim3(256), shmem, P.s, d_pic, stride, width, height, m);
         shmem = 0;
         return launch_status("ois_nd_multi");
     };
-    // the neighbour gathers of the groups that have directional candidates: one launch, first (arguments are validated here, before
-    // anything is enqueued)
-    const bool multi = !g_tune_ois_no_nd_multi;
-    {
-        GroupTable<OisGatherMulti, OIS_GATHER_MAX_GROUPS> gather;
-        auto gather_launch = [&](const OisGatherMulti& gm, uint32_t total) -> int {
-            hipLaunchKernelGGL(ois_gather_multi_kernel, dim3(total), dim3(256), 0, s, d_pic, stride, width, height, gm);
-            return launch_status("ois_gather_multi");
-        };
-        for (int g = 0; g < ngroups && multi; g++) {
-            const svt_hip_ois_group& G = groups[g];
-            if (G.nblocks == 0) continue;
-            OisGatherGroup gd = {};
-            if (int rc = ois_search_impl(d_pic, stride, width, height, G.d_xy, G.bsize, G.modes, G.angle_deltas, G.ncand, G.d_distortion, G.d_best_index,
-                                         G.d_work, G.work_bytes, G.nblocks, stream, nullptr, 1, &gd)) {
-                (void)gather.flush(gather_launch);
-                return rc;
-            }
-            if (gd.nblocks == 0) continue;
-            const uint32_t slots = 256 / (2 * gd.bsize);
-            OisGatherGroup* slot = gather.add((gd.nblocks + slots - 1) / slots, gather_launch);
-            if (!slot) return gather.rc;
-            *slot = gd;
-        }
-        if (int rc = gather.flush(gather_launch)) return rc;
-    }
-    for (int g = 0; g < ngroups; g++) {
-        const svt_hip_ois_group& G = groups[g];
-        if (G.nblocks == 0) continue;
-        OisNdGroup d = {};
-        if (int rc = ois_search_impl(d_pic, stride, width, height, G.d_xy, G.bsize, G.modes, G.angle_deltas, G.ncand, G.d_distortion, G.d_best_index,
-                                     G.d_work, G.work_bytes, G.nblocks, stream, multi ? &d : nullptr, multi ? 2 : 0)) {
-            (void)nd.flush(nd_launch);          // what was enqueued for the earlier groups stays complete
-            return rc;
-        }
-        if (g_tune_ois_no_nd_multi || d.nblocks == 0) continue;
-        const uint32_t cs = d.bsize < 16 ? 8 : 16, lpb = d.bsize * d.bsize / cs, nd_slots = 256 / lpb;
-        OisNdGroup* slot = nd.add((d.nblocks + nd_slots - 1) / nd_slots, nd_launch, d.bsize);
-        if (!slot) return nd.rc;
-        *slot = d;
-        const size_t sh = (((size_t)nd_slots + (lpb > 64 ? 4 : 0)) * (size_t)d.ncand + 4) * sizeof(uint32_t);
-        shmem = sh > shmem ? sh : shmem;
+    for (int j = 0; j < njobs; j++) {
+        const OisJob& J = jobs[j];
+        if (J.plan.path == OIS_PATH_GENERAL) { if (int rc = ois_general_enqueue(P, J)) return rc; continue; }
+        if (J.plan.path == OIS_PATH_FUSED) if (int rc = ois_chain_enqueue(P, J)) return rc;
+        const OisLanes g = ois_lanes(J.plan.bsize, J.plan.ncand, 4);
+        OisNdGroup* D = nd.add(ois_wgs(J.nblocks, g.slots), nd_launch, J.plan.bsize);
+        if (!D) return nd.rc;
+        D->xy = J.xy; D->dist = J.dist; D->best_index = J.best; D->bsize = J.plan.bsize; D->ncand = (uint32_t)J.plan.ncand;
+        D->nblocks = (uint32_t)J.nblocks; D->kinds = J.plan.kinds;
+        shmem = g.shmem > shmem ? g.shmem : shmem;
     }
     return nd.flush(nd_launch);
 }
 
+// ===========================================================================
+// (A) drop-in entry points: host pointers, one block, synchronous
 // one intra block: stage [lo, hi) of above / left around the origin, predict, copy the block back
 static void dropin_intra(int mode, int bw, int bh, void* dst, ptrdiff_t stride, const void* above, const void* left,
                          int a_lo, int a_hi, int l_lo, int l_hi, int ua, int ul, int dx, int dy, int is16, int bd,

@@ -897,7 +897,8 @@ int svt_hip_ois_search_batch(const uint8_t *d_pic, uint32_t stride, uint32_t wid
 /* The open-loop intra search of a whole PICTURE in one call: one group per block size (what svt_hip_ois_search_batch takes),
  * run concurrently on the library's internal streams (forked from / joined into `stream`; the call only enqueues).  The four
  * sizes of open_loop_intra_search_sb (EbMotionEstimation.c:8694) are independent, so the picture costs its slowest size, not
- * their sum. */
+ * their sum.  Every group (ngroups <= 64; a group with nblocks == 0 is skipped) is checked before the first launch: when the
+ * call returns an argument error it has enqueued nothing, under either setting of "ois_no_nd_multi". */
 typedef struct svt_hip_ois_group {
     const uint32_t *d_xy;                 /* block origins x | y << 16 */
     uint32_t bsize;                       /* 8, 16, 32, 64 */

@@ -2,6 +2,7 @@
 open_loop_intra_search_sb (tests/golden/ois.npz, made by oracle/ref_ois.c) and against oracle/ois.c on a whole
 picture."""
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -219,6 +220,93 @@ def test_ois_search_frame_equals_per_size_calls(dsp):
                     assert torch.equal(single6[i][0], d2) and torch.equal(single6[i][1], b2), (knob, od, i)
     finally:
         dsp.lib.svt_hip_tune(b"ois_no_nd_multi", 0)
+
+
+# ---- the branches of the host plan (csrc/ois_plan.h) that the reference's own lists never reach, against oracle/ois.c ----
+_Z1_DELTAS = [(3, d) for d in (-14, -13, -12, -3, -2, -1, 0, 1, 2, 3, 12, 13, 14)] + [(8, d) for d in range(-3, 4)]     # 20 angles below 90
+LIST_SPLIT_ZONE = [(0, 0), (1, 0), (4, 0), (7, 0)] + _Z1_DELTAS + [(3, 0), (8, 0), (3, 1)]         # 23 in zone 1: segments of 20 and 3
+LIST_16_ND = [(m, 0) for m in (0, 9, 10, 11, 12, 1, 0, 9, 10, 11, 12, 1, 0, 9, 10, 11)] + [(3, -1), (6, 2)]
+LIST_DIR_BIG = [(0, 0), (3, 0), (4, 1), (7, -1), (12, 0)]
+_PLAN_W, _PLAN_H, _PLAN_PAD = 96, 72, 32                    # 72 is no multiple of 64: partial superblocks
+
+
+@functools.lru_cache(maxsize=None)
+def _plan_case(bsize, cands):
+    """the 96x72 picture in its padded plane, every block of one size (all four borders), and the oracle's answer per block"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(7000 + bsize)
+    W, H, pad = _PLAN_W, _PLAN_H, _PLAN_PAD
+    buf = rng.integers(0, 256, size=(H + 2 * pad, W + 2 * pad), dtype=np.uint8)
+    buf[pad + 16:pad + 40, pad + 24:pad + 72] = 90           # flat area: ties, first strict minimum
+    stride = buf.shape[1]
+    blocks = [(x, y) for y in range(0, H - bsize + 1, bsize) for x in range(0, W - bsize + 1, bsize)]
+    modes = np.array([m for m, _ in cands], np.uint8); deltas = np.array([d for _, d in cands], np.int8)
+    n = len(cands)
+    pic = ctypes.c_void_p(buf.ctypes.data + pad * stride + pad)
+    dist = np.zeros((len(blocks), n), np.int64); best = np.zeros(len(blocks), np.int8)
+    ds = np.zeros(61, np.uint32)
+    for i, (x, y) in enumerate(blocks):
+        best[i] = O.svt_oracle_ois_block(pic, c_int(stride), c_int(W), c_int(H), c_int(x), c_int(y), c_int(bsize), c_int(n), ptr(modes), ptr(deltas), ptr(ds))
+        dist[i] = ds[:n]
+    dist.setflags(write=False); best.setflags(write=False)
+    return buf, blocks, modes, deltas, dist, best
+
+
+def _check_plan_case(dsp, bsize, cands, knob=None):
+    buf, blocks, modes, deltas, want_dist, want_best = _plan_case(bsize, tuple(cands))
+    pad = _PLAN_PAD
+    plane = dev(buf)
+    try:
+        if knob:
+            assert dsp.lib.svt_hip_tune(knob, 1) == 0
+        dist, best = dsp.ois_search(plane[pad:, pad:], buf.shape[1], _PLAN_W, _PLAN_H, _xy(blocks), bsize, modes, deltas)
+    finally:
+        if knob:
+            dsp.lib.svt_hip_tune(knob, 0)
+    assert np.array_equal(dist.cpu().numpy().astype(np.int64), want_dist), (bsize, knob)
+    assert np.array_equal(best.cpu().numpy(), want_best), (bsize, knob)
+
+
+@pytest.mark.parametrize("knob", [None, b"ois_no_nd"], ids=["fused_per_zone", "general_fold"])
+@pytest.mark.parametrize("bsize", [8, 16])
+def test_ois_zone_split_into_segments(dsp, bsize, knob):
+    """23 candidates in zone 1: a directional launch holds 20 angles, so the zone goes out as 20 + 3.  Default knobs: the fused path, per
+    zone because one zone is split; ois_no_nd: the general path, where the full segment is enqueued between the dense predictions"""
+    _check_plan_case(dsp, bsize, LIST_SPLIT_ZONE, knob)
+
+
+def test_ois_more_non_directional_candidates_than_the_fused_list(dsp):
+    """16 non-directional candidates (the fused kernel's list holds 15) and two directional ones: the general path with fold"""
+    _check_plan_case(dsp, 8, LIST_16_ND)
+
+
+@pytest.mark.parametrize("bsize", [32, 64])
+def test_ois_directional_candidates_at_32_and_64(dsp, bsize):
+    """blocks of more than 64 lanes cannot fold: the general path, every prediction through scratch"""
+    _check_plan_case(dsp, bsize, LIST_DIR_BIG)
+
+
+@pytest.mark.parametrize("no_nd_multi", [0, 1])
+def test_ois_search_frame_enqueues_nothing_on_a_bad_group(dsp, no_nd_multi):
+    """every group is checked before the first launch: a bad second group leaves the first group's outputs untouched"""
+    buf, blocks, modes, deltas, _, _ = _plan_case(8, tuple(LIST_SPLIT_ZONE))
+    pad, n, nc = _PLAN_PAD, len(blocks), len(modes)
+    plane = dev(buf)
+    xy = _xy(blocks)
+    dist = poison.tensor((n, nc), torch.int32, xy.device); best = poison.tensor((n,), torch.int8, xy.device)
+    wb = dsp.lib.svt_hip_ois_work_bytes(8, nc, n)
+    work = torch.empty(wb, dtype=torch.uint8, device=xy.device)
+    good = dsp.OisGroup(xy.data_ptr(), 8, modes.ctypes.data, deltas.ctypes.data, nc, dist.data_ptr(), best.data_ptr(), work.data_ptr(), wb, n)
+    arr = (dsp.OisGroup * 2)(good, good)
+    arr[1].bsize = 12
+    try:
+        assert dsp.lib.svt_hip_tune(b"ois_no_nd_multi", no_nd_multi) == 0
+        rc = dsp.lib.svt_hip_ois_search_frame(plane[pad:, pad:].data_ptr(), buf.shape[1], _PLAN_W, _PLAN_H, arr, 2, dsp._stream())
+    finally:
+        dsp.lib.svt_hip_tune(b"ois_no_nd_multi", 0)
+    assert rc != 0
+    torch.cuda.synchronize()
+    assert bool((dist == poison.fill_value(torch.int32)).all()) and bool((best == poison.fill_value(torch.int8)).all())
 
 
 poison.add_second_fill(globals())

@@ -90,3 +90,16 @@ def test_group_table_builder(tmp_path, san_flags):
                         [os.path.join(ROOT, "tests", "c", "group_table_host.cpp"), "-o", exe], capture_output=True, text=True)
     assert pr.returncode == 0, pr.stderr[-4000:]
     assert run(exe, []).strip() == "ok"
+
+
+@pytest.mark.parametrize("san_flags", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]], ids=["plain", "asan_ubsan"])
+def test_ois_plan(tmp_path, san_flags):
+    """csrc/ois_plan.h (what the open-loop intra search derives from a candidate list before it enqueues) as a stand-alone program:
+    every candidate placed exactly once on every list of svt_hip_ois_candidates under the 8 knob settings, the path rules, the
+    derivatives, zones split into segments of 20, the refusals, the work-buffer layout against the formula"""
+    exe = str(tmp_path / "ois_plan_host")
+    pr = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror"] + san_flags +
+                        [os.path.join(ROOT, "tests", "c", "ois_plan_host.cpp"), os.path.join(PKG, "csrc", "host_tables.cpp"), "-o", exe],
+                        capture_output=True, text=True)
+    assert pr.returncode == 0, pr.stderr[-4000:]
+    assert run(exe, []).strip() == "ok"
