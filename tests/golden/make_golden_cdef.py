@@ -20,6 +20,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.path.join(HERE, "cdef.npz")
 REF = os.path.join(ROOT, "oracle", "_ref", "libsvtref.so")
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import svtlibs      # noqa: E402
 
 BSTRIDE, VBORDER, HBORDER = 144, 3, 8              # CDEF_BSTRIDE (MAX_SB_SIZE_LOG2 7), CDEF_VBORDER, CDEF_HBORDER
 INBUF = BSTRIDE * (128 + 2 * VBORDER)              # CDEF_INBUF_SIZE
@@ -40,19 +42,19 @@ def ptr(a):
 
 
 _lib = None
+SLOTS = {s: s + "_c" for s in ("cdef_find_dir", "cdef_filter_block", "copy_rect8_8bit_to_16bit", "dist_8x8_16bit", "mse_4x4_16bit")}
 
 
 def ref_lib():
-    """libsvtref.so with the five CDEF dispatch globals pointed at the reference's C functions; None when it is not built"""
+    """libsvtref.so with the five CDEF dispatch globals pointed at the reference's C functions; None when it is not built.  The
+    slots are pointed on every call (svtlibs.ref_with_slots: whatever refilled them since the last call does not matter)"""
     global _lib
-    if _lib is None and os.path.exists(REF):
-        L = ctypes.CDLL(REF)
-        for slot in ("cdef_find_dir", "cdef_filter_block", "copy_rect8_8bit_to_16bit", "dist_8x8_16bit", "mse_4x4_16bit"):
-            ctypes.c_void_p.in_dll(L, slot).value = ctypes.cast(getattr(L, slot + "_c"), ctypes.c_void_p).value
-        L.compute_cdef_dist.restype = ctypes.c_uint64
-        L.dist_8x8_16bit_c.restype = ctypes.c_uint64
-        L.cdef_find_dir_c.restype = ctypes.c_int32
-        _lib = L
+    first = _lib is None
+    _lib = svtlibs.ref_with_slots(SLOTS, _lib)
+    if first and _lib is not None:
+        _lib.compute_cdef_dist.restype = ctypes.c_uint64
+        _lib.dist_8x8_16bit_c.restype = ctypes.c_uint64
+        _lib.cdef_find_dir_c.restype = ctypes.c_int32
     return _lib
 
 

@@ -267,24 +267,11 @@ def np_decide(z, dist):
 # ---------------------------------------------------------------------------------------------------------------------------
 # the reference
 # ---------------------------------------------------------------------------------------------------------------------------
-_ref = None
-
-
 def ref_lib():
     """libsvtref.so ready for the whole chain, None when it is not built.  The ref_* pin functions refill the dispatch globals on first
-    use, so av1_txb_init_levels and av1_get_nz_map_contexts (make_golden_coeff_rate.ref_lib points them) are pointed AGAIN after the
-    first ref_estimate_transform call; otherwise av1_cost_coeffs_txb jumps through NULL."""
-    global _ref
-    if _ref is None:
-        L = mgc.ref_lib()
-        if L is None:
-            return None
-        x, co, e = np.zeros((4, 64), np.int16), np.zeros(16 + 64, np.int32), np.zeros(1, np.uint64)
-        assert L.ref_estimate_transform(ptr(x), ctypes.c_uint32(64), ptr(co), c_int(0), c_int(0), c_int(0), ptr(e)) == 0
-        ctypes.c_void_p.in_dll(L, "av1_txb_init_levels").value = ctypes.cast(L.av1_txb_init_levels_c, ctypes.c_void_p).value
-        ctypes.c_void_p.in_dll(L, "av1_get_nz_map_contexts").value = ctypes.cast(mgc._keep[-1], ctypes.c_void_p).value
-        _ref = L
-    return _ref
+    use; make_golden_coeff_rate.ref_lib (svtlibs.ref_with_slots) has that refill run before it points av1_txb_init_levels and
+    av1_get_nz_map_contexts, and points them on every call, so av1_cost_coeffs_txb never jumps through NULL."""
+    return mgc.ref_lib()
 
 
 def ref_qrows(L, qindex):

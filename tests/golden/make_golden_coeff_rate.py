@@ -210,21 +210,21 @@ def _nz_map_callback(levels, scan, eob, tx_size, cls, out):
 
 def ref_lib():
     """libsvtref.so with av1_txb_init_levels pointed at the reference's C function and av1_get_nz_map_contexts at the callback above;
-    None when it is not built"""
+    None when it is not built.  The slots are pointed on every call (svtlibs.ref_with_slots: whatever refilled them since the last
+    call does not matter)"""
     global _lib
-    if _lib is None and os.path.exists(REF):
-        L = ctypes.CDLL(REF)
-        ctypes.c_void_p.in_dll(L, "av1_txb_init_levels").value = ctypes.cast(L.av1_txb_init_levels_c, ctypes.c_void_p).value
-        cb = NZ_CB(_nz_map_callback)
-        _keep.append(cb)
-        ctypes.c_void_p.in_dll(L, "av1_get_nz_map_contexts").value = ctypes.cast(cb, ctypes.c_void_p).value
+    if not _keep:
+        _keep.append(NZ_CB(_nz_map_callback))
+    first = _lib is None
+    _lib = svtlibs.ref_with_slots({"av1_txb_init_levels": "av1_txb_init_levels_c", "av1_get_nz_map_contexts": _keep[0]}, _lib)
+    if first and _lib is not None:
+        L = _lib
         L.av1_cost_coeffs_txb.restype = ctypes.c_uint64
         L.av1_cost_coeffs_txb.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint16, ctypes.c_int, ctypes.c_uint8, ctypes.c_int16,
                                           ctypes.c_int16, ctypes.c_uint8]
         L.ref_get_scan.restype = ctypes.POINTER(ctypes.c_int16)
         lib_off = np.frombuffer(ctypes.string_at(ctypes.addressof(ctypes.c_char.in_dll(L, "av1_nz_map_ctx_offset")), 19 * 25), np.int8)
         assert np.array_equal(lib_off.reshape(19, 5, 5), NZ_MAP_CTX_OFFSET), "Coeff_Base_Ctx_Offset differs from the reference's table"
-        _lib = L
     return _lib
 
 

@@ -41,8 +41,12 @@ CASES = [
     ("b_edge_off", "edge", dict(slice_type=0, pic_depth_mode=2, enable_hme_flag=0, search_area_width=24, search_area_height=12)),
     ("b_edge_samepoc", "edge", dict(slice_type=0, pic_depth_mode=2, ref1_poc=8)),
     ("p_edge_narrow", "edge", dict(slice_type=1, pic_depth_mode=0, temporal_layer_index=0, search_area_width=8, search_area_height=7)),
+    # the branches that no other case carries through the picture call: bi-prediction of PUs 0 .. 20 only, its full-row SAD, no
+    # CheckZeroZeroCenter; the 525 % level-0 multiplier (the level-0 area clipped by the 1/16 picture's padding)
+    ("b_edge_cu8x8_fullsad_nozz", "edge", dict(slice_type=0, pic_depth_mode=2, cu8x8_mode=1, fractional_search_method=1, is_used_as_reference_flag=0)),
+    ("b_full_hl5_base", "full", dict(slice_type=0, pic_depth_mode=0, hierarchical_levels=5, temporal_layer_index=0)),
 ]
-REGENERATED_IN_TESTS = ("b_full_avx2", "p_edge_narrow")
+REGENERATED_IN_TESTS = ("b_full_avx2", "p_edge_narrow", "b_edge_cu8x8_fullsad_nozz")
 
 
 def ptr(a):
@@ -150,9 +154,18 @@ def check_conditions(g):
             for l in range(nl):
                 narrow |= area_width(prm[i], int(g[name + "_area_origin"][i, l, 0])) < 8
         assert (g[name + "_best_sad"][:, :nl, :npus] < 128 * 128 * 255).all()                     # every PU of every searched list found a vector
-        assert p[23] == 0 and (g[name + "_results"][:, :npus, 10] == (1 if nl == 1 else 3)).all()     # cu8x8_mode 0: every PU is bi-predicted
+        if name == "b_edge_cu8x8_fullsad_nozz":           # cu8x8_mode 1 with 85 PUs: PUs 0 .. 20 are bi-predicted, the 8x8 PUs 21 .. 84 are not
+            assert (p[23], p[24], p[12], npus, nl) == (1, 1, 0, 85, 2)
+            assert (g[name + "_results"][:, :21, 10] == 3).all() and (g[name + "_results"][:, 21:85, 10] == 2).all()
+            assert (g[name + "_bipred_sad"][:, :21] != 0).any()
+            seen |= {("cu8x8", 1), ("fullsad", 1), ("nozz", 1)}
+        else:
+            assert p[23] == 0 and (g[name + "_results"][:, :npus, 10] == (1 if nl == 1 else 3)).all()     # cu8x8_mode 0: every PU is bi-predicted
+        if p[8] and p[9] and (p[7], p[6]) == (5, 0):
+            seen.add(("multiplier", 525))
     need = {("slice", 0), ("slice", 1), ("hme", "full"), ("hme", "l0"), ("hme", "off"), ("regions", 1, 1), ("regions", 2, 2), ("pus", 85), ("pus", 209),
-            ("flavour", 0, "full"), ("flavour", 0, "edge"), ("flavour", 1, "full"), ("samepoc", "base")}
+            ("flavour", 0, "full"), ("flavour", 0, "edge"), ("flavour", 1, "full"), ("samepoc", "base"), ("cu8x8", 1), ("fullsad", 1), ("nozz", 1),
+            ("multiplier", 525)}
     assert need <= seen, sorted(need - seen)
     assert ("flavour", 1, "edge") not in seen             # the reference's AVX2 HME kernels are undefined on partial SB columns
     assert narrow, "no search area clipped to fewer than 8 columns"
@@ -191,7 +204,7 @@ def main():
     check_conditions(d)
     np.savez_compressed(OUT, **d)
     size = os.path.getsize(OUT)
-    assert size < (1 << 20), size
+    assert size < (512 << 10), size
     print(f"wrote {OUT}: {size} bytes, {len(CASES)} cases")
 
 

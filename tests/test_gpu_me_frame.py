@@ -1,15 +1,21 @@
 """GPU: svt_hip_motion_estimate_frame - MotionEstimateLcu for every SB of a picture in one call (HME levels, best region,
 CheckZeroZeroCenter and the search area in one fused launch, then the search and the bi-prediction) - against the reference's OWN
 MotionEstimateLcu on every SB of the fixture's pictures (tests/golden/me_frame.npz), against the composed stage calls on a larger
-picture, on a stack of pictures under a captured graph, and on the arguments it must refuse.  Every comparison is an equality."""
+picture, on a stack of pictures under a captured graph, and on the arguments it must refuse; across its parameter space (random
+parameter sets, svtlibs.me_frame_draws) against the oracle's MotionEstimateLcu, which tests/test_oracle_vs_ref.py pins to the
+reference on the same draws; on a stack whose pitch is above one padded picture; at the limits of what it accepts.  Every output is
+allocated poisoned (tests/poison.py): an entry the three launches never wrote fails the comparison.  Every comparison is an equality."""
+import ctypes
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import poison
 import svtlibs
 import test_gpu_me_setup as stage
+from poison import poisoned_outputs  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -133,6 +139,10 @@ def test_the_call_equals_the_composed_stage_calls_on_a_640x360_picture(dsp, pkg,
     if nl == 2:
         assert np.array_equal(got["bipred_sad"], want["bipred_sad"])
     assert (got["best_mv"][:, 0, 0] != 0).any()
+    # two device results were compared: an entry that neither wrote would have compared equal
+    fill = np.uint32(poison.fill_value(torch.int32) & 0xffffffff)
+    for k in ("best_sad", "best_mv", "bipred_sad"):
+        assert not (got[k] == fill).any(), k
 
 
 def test_the_avx2_flavour_is_refused_where_the_references_hme_kernels_are_undefined(dsp, pkg):
@@ -164,3 +174,133 @@ def test_nothing_happens_on_an_empty_stack(dsp, pkg):
     torch.cuda.synchronize()
     for k in KEYS:
         assert int((out[k] != 0x55).sum()) == 0, k
+
+
+def assert_equals_the_oracle(got, nl, want, what):
+    """want: svtlibs.me_frame_oracle_run.  area_origin and the result rows of the searched lists; bipred_sad and results whole"""
+    for k in ("best_sad", "best_mv", "area_origin"):
+        assert np.array_equal(got[k][:, :nl], want[k][:, :nl]), (what, k, np.argwhere(got[k][:, :nl] != want[k][:, :nl])[:4].tolist())
+    for k in ("results", "bipred_sad"):
+        assert np.array_equal(got[k], want[k]), (what, k, np.argwhere(got[k] != want[k])[:4].tolist())
+
+
+@pytest.mark.parametrize("seed", svtlibs.ME_FRAME_SEEDS)
+def test_random_parameter_sets_equal_the_oracles_motion_estimate_lcu_on_every_sb(dsp, pkg, seed):
+    """one call per draw on the whole picture (at most 24 SBs) against svt_oracle_me_lcu_ex per SB on the CPU: slice type, 85 / 209
+    PUs, hierarchical_levels 0 .. 5 with every temporal layer, every subset of the HME levels and HME off, 1 x 1 / 2 x 2 / 1 x 2 / 2 x 1
+    regions, equal and unequal per-region HME areas, search areas 7 .. 64 wide and 5 .. 64 high, CheckZeroZeroCenter on / off, cu8x8_mode,
+    the sub-sampled / full-row bi-prediction SAD, equal / unequal reference POCs, the AVX2 flavour on whole-SB pictures"""
+    for d, want in enumerate(svtlibs.me_frame_oracle_runs(seed)):
+        got, nl = run_frame(dsp, pkg, want["prm"][0], want["pics"])
+        assert_equals_the_oracle(got, nl, want, (seed, d, want["W"], want["H"], want["kw"]))
+
+
+def test_the_random_parameter_sets_reach_the_branches_they_are_for():
+    svtlibs.me_frame_generator_coverage()
+    svtlibs.me_frame_oracle_coverage()
+
+
+def guarded_stack(dsp, lumas, guard):
+    """a stack whose pitch is TWO padded pictures: picture i of level k at [i, 0], a plane of `guard` at [i, 1]"""
+    pyr = [svtlibs.me_pyramid(l) for l in lumas]
+    planes = []
+    for k in range(3):
+        a = np.full((len(lumas), 2) + pyr[0][0][k].shape, guard, np.uint8)
+        for i, p in enumerate(pyr):
+            a[i, 0] = p[0][k]
+        planes.append(torch.from_numpy(a).cuda()[:, 0])
+    return dsp.me_pyramid(planes, [(g[1], g[2]) for g in pyr[0][1]])
+
+
+def test_a_stack_of_three_p_pictures_at_a_pitch_above_one_picture_equals_three_single_calls(dsp, pkg):
+    W, H = 200, 136
+    kw = dict(slice_type=1, pic_depth_mode=0, search_area_width=24, search_area_height=9, regions_w=2, regions_h=1)
+    rng = np.random.default_rng(31360)
+    triples = []
+    for i in range(3):
+        base = svtlibs.smooth_picture(rng, H + 96, W + 96)
+        dx, dy = (int(v) for v in rng.integers(-20, 21, 2))
+        triples.append((base[48:48 + H, 48:48 + W].copy(), base[48 + dy:48 + dy + H, 48 + dx:48 + dx + W].copy(), np.zeros((H, W), np.uint8)))
+    wants = [svtlibs.me_frame_oracle_run(W, H, kw, t) for t in triples]
+    assert not np.array_equal(wants[0]["best_mv"], wants[1]["best_mv"]) and not np.array_equal(wants[1]["best_mv"], wants[2]["best_mv"])
+    singles = []
+    for t, want in zip(triples, wants):
+        got, nl = run_frame(dsp, pkg, want["prm"][0], t)
+        assert_equals_the_oracle(got, nl, want, "single")
+        singles.append(got)
+    params = pkg.MeFrameParams.from_lcu_prm(wants[0]["prm"][0])
+    src, ref0 = (guarded_stack(dsp, [t[i] for t in triples], 0xC3 - 0x40 * i) for i in range(2))
+    one_picture = [int(src.stride[k]) * wants[0]["pyr"][0][k].shape[0] for k in range(3)]
+    assert all(int(src.pitch[k]) == 2 * one_picture[k] for k in range(3))
+    out = dsp.motion_estimate_frame(src, ref0, None, params, 3)
+    torch.cuda.synchronize()
+    got = as_arrays(dsp, out, 1)
+    nsb = len(wants[0]["prm"])
+    for i in range(3):
+        for k in KEYS:
+            assert np.array_equal(got[k][i * nsb:(i + 1) * nsb], singles[i][k]), (i, k)
+
+
+def frame_outputs(pkg, params, device):
+    """poisoned outputs of one picture, as the wrapper would allocate them"""
+    nsb = ((params.picture_width + 63) // 64) * ((params.picture_height + 63) // 64)
+    nl = 1 if params.slice_type == 1 else 2
+    return {"best_sad": poison.tensor((nsb, nl, 209), torch.int32, device), "best_mv": poison.tensor((nsb, nl, 209), torch.int32, device),
+            "area_origin": poison.tensor((nsb, nl, 2), torch.int16, device), "bipred_sad": poison.tensor((nsb, 209), torch.int32, device),
+            "results": poison.tensor((nsb, 209, 24), torch.uint8, device)}
+
+
+# (what, keywords of svtlibs.me_lcu_params on the 200 x 136 B picture, refused by svt_hip_motion_estimate_frame_scratch_bytes already?, scratch)
+REFUSED = [
+    ("enable_hme_flag with no level on", dict(hme_l0=0, hme_l1=0, hme_l2=0), True, "exact"),
+    ("a 1 x 2 grid with same-POC references above the base layer", dict(regions_w=1, regions_h=2, ref1_poc=8, temporal_layer_index=1), True, "exact"),
+    ("a 2 x 1 grid with same-POC references above the base layer", dict(regions_w=2, regions_h=1, ref1_poc=8, temporal_layer_index=2, hme_l0=0, hme_l1=0), True, "exact"),
+    ("a 65 x 64 area: 72 x 64 points > 4096", dict(search_area_width=65, search_area_height=64), True, "exact"),
+    ("a 4096 x 1 area: 4096 points, but the window is above 58 KiB of LDS", dict(search_area_width=4096, search_area_height=1), True, "exact"),
+    ("a width that is no multiple of 8", dict(width=204), True, "exact"),
+    ("temporal_layer_index > hierarchical_levels", dict(hierarchical_levels=2, temporal_layer_index=3), True, "exact"),
+    ("3 regions", dict(regions_w=3), True, "exact"),
+    ("scratch one byte short", dict(), False, "short"),
+    ("scratch misaligned", dict(), False, "misaligned"),
+]
+
+
+def test_refused_parameter_sets_return_an_error_and_leave_the_outputs_untouched(dsp, pkg):
+    W, H = 200, 136
+    pics = svtlibs.me_frame_limit_run("area_512x8")["pics"]
+    pyr = [device_pyramid(dsp, p)[0] for p in pics]
+    geo = svtlibs.me_pyramid(np.zeros((H, W), np.uint8))[1]
+    lib = pkg.load_library()
+    fill = poison.fill_value(torch.uint8)
+    for what, kw, plan_level, scratch_kind in REFUSED:
+        kw = dict(kw)
+        params = pkg.MeFrameParams.from_lcu_prm(svtlibs.me_lcu_params(kw.pop("width", W), H, 0, 0, geo, slice_type=0, **kw))
+        need = lib.svt_hip_motion_estimate_frame_scratch_bytes(ctypes.addressof(params), 1)
+        assert (need == 0) == plan_level, (what, need)
+        out = frame_outputs(pkg, params, dsp.device)
+        if scratch_kind == "short":
+            scratch = poison.tensor(need - 1, torch.uint8, dsp.device)
+        elif scratch_kind == "misaligned":
+            scratch = poison.tensor(need + 16, torch.uint8, dsp.device)[1:1 + need]
+            assert scratch.data_ptr() % 16 == 1
+        else:
+            scratch = poison.tensor(4096, torch.uint8, dsp.device)
+        with pytest.raises(pkg.SvtHipError):
+            dsp.motion_estimate_frame(pyr[0], pyr[1], pyr[2], params, 1, out=out, scratch=scratch)
+        torch.cuda.synchronize()
+        for k, t in list(out.items()) + [("scratch", scratch)]:
+            if k != "_scratch":
+                assert int((t.contiguous().view(torch.uint8) != fill).sum()) == 0, (what, k)
+        if not plan_level:                                            # with the scratch it asks for, the same call is accepted
+            dsp.motion_estimate_frame(pyr[0], pyr[1], pyr[2], params, 1, out=out, scratch=poison.tensor(need, torch.uint8, dsp.device))
+            torch.cuda.synchronize()
+            assert int((out["best_sad"] == poison.fill_value(torch.int32)).sum()) == 0, what
+
+
+@pytest.mark.parametrize("name", sorted(svtlibs.ME_FRAME_ACCEPTED_LIMITS))
+def test_the_largest_accepted_search_areas_equal_the_oracle(dsp, pkg, name):
+    """64 x 64 with 209 PUs (4096 points, the largest square) and 512 x 8 (clipped by the picture's right side for every SB) on the
+    200 x 136 picture; tests/test_oracle_vs_ref.py shows the oracle equal to the reference on both"""
+    want = svtlibs.me_frame_limit_run(name)
+    got, nl = run_frame(dsp, pkg, want["prm"][0], want["pics"])
+    assert_equals_the_oracle(got, nl, want, name)

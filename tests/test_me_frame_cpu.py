@@ -26,14 +26,48 @@ def package():
 
 def test_fixture_holds_the_cases_the_picture_call_must_cover():
     g = np.load(GOLD)
-    assert os.path.getsize(GOLD) < (1 << 20)
-    mg.check_conditions(g)                  # P / B, HME full / level 0 only / off, 1x1 / 2x2 regions, 85 / 209 PUs, same POC, narrow area
+    assert os.path.getsize(GOLD) < (512 << 10)
+    mg.check_conditions(g)                  # P / B, HME full / level 0 only / off, 1x1 / 2x2 regions, 85 / 209 PUs, same POC, narrow area,
+    #                                         cu8x8_mode 1 (PUs 21 .. 84 not bi-predicted), full-row SAD, no zero-centre check, 525 %
     # sources and references are stored once per picture size; the pyramids are rebuilt from them
     assert sorted(k for k in g if k.startswith("pic_")) == sorted(f"pic_{p}_{i}" for p in mg.SIZES for i in range(3))
     pics = mg.pictures()
     for p in mg.SIZES:
         for i in range(3):
             assert np.array_equal(g[f"pic_{p}_{i}"], pics[p][i])
+
+
+def test_the_randomised_draws_cover_every_listed_value_and_redraw_at_most_a_quarter():
+    """svtlibs.me_frame_draws, shared by tests/test_oracle_vs_ref.py (oracle against the reference) and tests/test_gpu_me_frame.py (the
+    picture call against the oracle): every listed value of every dimension at least twice over the seeds in use, at most 25 % of the
+    draws outside the domain - decided by me_frame_outside_domain alone, which agrees with what the picture call refuses"""
+    seen, stats = svtlibs.me_frame_generator_coverage()
+    assert stats["drawn"] >= len(svtlibs.ME_FRAME_SEEDS) * svtlibs.ME_FRAME_DRAWS_PER_SEED and sum(seen["W"].values()) == 24
+    assert max(r["prm"].shape[0] for s in svtlibs.ME_FRAME_SEEDS for r in svtlibs.me_frame_oracle_runs(s)) <= 24      # SBs per picture
+    # the rules name exactly what svt_hip_motion_estimate_frame_scratch_bytes refuses (a host computation, no device)
+    pkg = package()
+    lib = pkg.load_library()
+    geo = svtlibs.me_pyramid(np.zeros((192, 256), np.uint8))[1]
+    outside = [(200, dict(enable_hme_flag=1, hme_l0=0, hme_l1=0, hme_l2=0)),
+               (256, dict(slice_type=0, regions_w=1, regions_h=2, ref1_poc=8, temporal_layer_index=1)),
+               (256, dict(slice_type=0, regions_w=2, regions_h=1, ref1_poc=8, temporal_layer_index=2, hme_l0=0)),
+               (200, dict(asm_type=1))]
+    inside = [(256, dict(slice_type=0, regions_w=1, regions_h=2, ref1_poc=8, temporal_layer_index=0)),
+              (256, dict(slice_type=0, regions_w=1, regions_h=2, ref1_poc=8, temporal_layer_index=1, hme_l2=0)),
+              (256, dict(slice_type=1, regions_w=2, regions_h=1, ref1_poc=8, temporal_layer_index=1)),
+              (256, dict(asm_type=1)), (200, dict(asm_type=1, hme_l0=0))]
+    for want, sets in ((True, outside), (False, inside)):
+        for W, kw in sets:
+            full = dict(svtlibs.ME_LCU_DEFAULTS); full.update(kw)
+            assert (svtlibs.me_frame_outside_domain(W, 192, full) is not None) == want, kw
+            p = pkg.MeFrameParams.from_lcu_prm(svtlibs.me_lcu_params(W, 192, 0, 0, geo, **kw))
+            assert (lib.svt_hip_motion_estimate_frame_scratch_bytes(ctypes.addressof(p), 1) == 0) == want, kw
+
+
+def test_the_randomised_draws_reach_the_branches_they_are_for():
+    """from the oracle's outputs: an area clipped below 8 columns, a non-zero vector, cu8x8_mode 1 with PUs 21 .. 84 not bi-predicted, and
+    the 70 % / 350 % / 525 % level-0 multipliers with level 0 on"""
+    svtlibs.me_frame_oracle_coverage()
 
 
 def test_regenerating_two_cases_reproduces_the_fixture():

@@ -630,3 +630,35 @@ def test_motion_estimate_lcu_vs_reference_randomized(seed):
                 ncase += 1
                 nnarrow += int(0 < areas[0, 2] < 8) + int(0 < areas[1, 2] < 8)
     assert ncase > 150 and nnarrow > 0            # search areas clipped below 8 columns (the single-search-point form) did occur
+
+
+def test_motion_estimate_lcu_vs_reference_on_the_picture_calls_draws():
+    """the same comparison on svtlibs.me_frame_draws, the draws tests/test_gpu_me_frame.py sends through svt_hip_motion_estimate_frame:
+    hierarchical_levels 0 .. 5 with every temporal layer (the 70 % .. 525 % level-0 multipliers), 1 x 2 / 2 x 1 region grids, unequal
+    per-region HME areas at all three levels, every subset of the levels, 64-wide / 64-high search areas, 8-wide and 8-high partial
+    SBs.  The chain reference -> oracle (here) -> picture call (there) needs no fixture."""
+    svtlibs.me_frame_generator_coverage()
+    ncase = nnarrow = 0
+    for seed in svtlibs.ME_FRAME_SEEDS:
+        for d, b in enumerate(svtlibs.me_frame_oracle_runs(seed)):
+            for i, prm in enumerate(b["prm"]):
+                a = svtlibs.run_me_lcu(R.ref_motion_estimate_lcu, prm, *b["pyr"])
+                for k in a:
+                    assert np.array_equal(a[k], b[k][i]), (seed, d, (b["W"], b["H"]), tuple(prm[2:4]), b["kw"], k, np.argwhere(a[k] != b[k][i])[:4].tolist())
+                ncase += 1
+                nnarrow += int(0 < b["areas"][i, 0, 2] < 8) + int(0 < b["areas"][i, 1, 2] < 8)
+    assert ncase > 150 and nnarrow > 0
+    svtlibs.me_frame_oracle_coverage()
+
+
+@pytest.mark.parametrize("name", sorted(svtlibs.ME_FRAME_ACCEPTED_LIMITS))
+def test_motion_estimate_lcu_vs_reference_on_the_largest_search_areas(name):
+    """the two largest areas svt_hip_motion_estimate_frame accepts (svtlibs.ME_FRAME_ACCEPTED_LIMITS): the reference is defined there
+    (every read stays inside the padded pictures) and the oracle equals it, so the GPU test may compare the picture call with the oracle"""
+    b = svtlibs.me_frame_limit_run(name)
+    for i, prm in enumerate(b["prm"]):
+        a = svtlibs.run_me_lcu(R.ref_motion_estimate_lcu, prm, *b["pyr"])
+        for k in a:
+            assert np.array_equal(a[k], b[k][i]), (name, tuple(prm[2:4]), k, np.argwhere(a[k] != b[k][i])[:4].tolist())
+    if name == "area_512x8":
+        assert (b["areas"][:, :, 2] < 512).all() and (b["areas"][:, :, 2] >= 8).any()      # clipped by the picture's right side everywhere
