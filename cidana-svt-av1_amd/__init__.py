@@ -14,6 +14,7 @@ The directory name contains '-', so import it through
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 from ctypes import c_int, c_int16, c_int32, c_size_t, c_uint32, c_void_p
@@ -186,6 +187,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_cfl_pick_scratch_bytes.restype = c_size_t
     L.svt_hip_cfl_pick_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     L.svt_hip_cfl_pick_frame.restype = c_int
+    L.svt_hip_picture_stats_frame.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]
+    L.svt_hip_picture_stats_frame.restype = c_int
     return L
 
 
@@ -252,6 +255,27 @@ class MePyramid(ctypes.Structure):
     """svt_hip_me_pyramid: the padded full / quarter / sixteenth luma buffers of one picture (or of a stack of pictures)"""
     _fields_ = [("d_plane", c_void_p * 3), ("stride", c_uint32 * 3), ("origin_x", c_uint32 * 3), ("origin_y", c_uint32 * 3),
                 ("pitch", ctypes.c_uint64 * 3)]
+
+
+class PicStatsPlanes(ctypes.Structure):
+    """svt_hip_pic_stats_planes: the padded luma, Cb, Cr and 1/16 luma buffers of one picture (or of a stack of pictures)"""
+    _fields_ = [("d_plane", c_void_p * 4), ("stride", c_uint32 * 4), ("origin_x", c_uint32 * 4), ("origin_y", c_uint32 * 4),
+                ("pitch", ctypes.c_uint64 * 4)]
+
+
+class PicStatsParams(ctypes.Structure):
+    """svt_hip_pic_stats_params"""
+    _fields_ = [(n, c_int32) for n in ("picture_width", "picture_height", "block_mean_calc_prec", "regions_per_width", "regions_per_height")]
+
+
+class PicStatsOut(ctypes.Structure):
+    """svt_hip_pic_stats_out: the eight device outputs of svt_hip_picture_stats_frame"""
+    _fields_ = [(n, c_void_p) for n in ("d_y_mean", "d_variance", "d_cb_mean", "d_cr_mean", "d_pic_avg_variance", "d_histogram",
+                                        "d_avg_intensity_region", "d_avg_intensity")]
+
+
+PicStatsResult = collections.namedtuple("PicStatsResult", ("y_mean", "variance", "cb_mean", "cr_mean", "pic_avg_variance", "histogram",
+                                                           "avg_intensity_region", "avg_intensity"))
 
 
 class Y4mInfo(ctypes.Structure):
@@ -1089,6 +1113,43 @@ class SvtHipDsp:
                                                            self._p(out["area_origin"]), self._p(out["bipred_sad"]), self._p(out["results"]),
                                                            self._p(scratch), scratch.numel(), self._stream()), "svt_hip_motion_estimate_frame")
         out["_scratch"] = scratch
+        return out
+
+    # -- GatheringPictureStatistics for a whole picture: one call, two launches --------------------------------------------
+    PicStatsPlanes = PicStatsPlanes
+    PicStatsParams = PicStatsParams
+    PicStatsOut = PicStatsOut
+    PicStatsResult = PicStatsResult
+    BLOCK_MEAN_PREC_FULL, BLOCK_MEAN_PREC_SUB = 0, 1
+
+    def pic_stats_planes(self, planes, origins):
+        """planes: the padded luma, Cb, Cr and 1/16 luma buffers, 2-D uint8 tensors [rows, stride] (one picture) or 3-D [pictures, rows,
+        stride] (a stack).  origins: (x, y) of sample (0, 0) in each; the chroma origins are the luma origin >> 1"""
+        p = PicStatsPlanes()
+        for k, (t, o) in enumerate(zip(planes, origins)):
+            p.d_plane[k] = t.data_ptr()
+            p.stride[k], p.origin_x[k], p.origin_y[k] = t.stride(-2), int(o[0]), int(o[1])
+            p.pitch[k] = t.stride(0) if t.dim() == 3 else 0
+        p._keep = planes
+        return p
+
+    def picture_stats_frame(self, planes, width, height, block_mean_calc_prec=1, regions=(4, 4), n_pictures=1, out=None):
+        """svt_hip_picture_stats_frame.  planes: PicStatsPlanes (pic_stats_planes); regions: (per width, per height).  -> PicStatsResult of
+        device tensors, s = n_pictures * SBs: y_mean uint8 [s, 85], variance int16 [s, 85] (uint16 values), cb_mean, cr_mean uint8 [s, 21],
+        pic_avg_variance int16 [n] (uint16 values), histogram int32 [n, rw, rh, 3, 256], avg_intensity_region uint8 [n, rw, rh, 3],
+        avg_intensity uint8 [n, 3].  `out`: the result of an earlier call to write into (the call allocates nothing itself)."""
+        t = self.torch
+        prm = PicStatsParams(int(width), int(height), int(block_mean_calc_prec), int(regions[0]), int(regions[1]))
+        if out is None:
+            n = max(1, n_pictures)
+            s = n * max(1, ((width + 63) // 64) * ((height + 63) // 64))
+            rw, rh = (min(max(int(r), 1), 4) for r in regions)
+            e = lambda shape, dt: t.empty(shape, dtype=dt, device=self.device)
+            out = PicStatsResult(e((s, 85), t.uint8), e((s, 85), t.int16), e((s, 21), t.uint8), e((s, 21), t.uint8), e((n,), t.int16),
+                                 e((n, rw, rh, 3, 256), t.int32), e((n, rw, rh, 3), t.uint8), e((n, 3), t.uint8))
+        o = PicStatsOut(*[x.data_ptr() for x in out])
+        self._check(self.lib.svt_hip_picture_stats_frame(ctypes.addressof(planes), ctypes.addressof(prm), n_pictures, ctypes.addressof(o),
+                                                         self._stream()), "svt_hip_picture_stats_frame")
         return out
 
     # -- general fused chain on planes ------------------------------------------------------

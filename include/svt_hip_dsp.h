@@ -1334,6 +1334,75 @@ int svt_hip_picture_decimate(const uint8_t *d_luma, uint32_t luma_stride, uint32
                              uint32_t q_stride, uint32_t q_origin_x, uint32_t q_origin_y, uint8_t *d_sixteenth,
                              uint32_t s_stride, uint32_t s_origin_x, uint32_t s_origin_y, void *stream);
 
+/* ---- GatheringPictureStatistics for a whole picture (EbPictureAnalysisProcess.c:4759-4812; runs between decimation and ME) -----
+ * svt_hip_picture_stats_frame computes, for one picture or a stack of n_pictures under one parameter set, what rate control, the
+ * mode-decision configuration and scene-change detection read of the picture-analysis stage: the 85 luma block means and variances
+ * and the 21 Cb / Cr block means of every 64x64 SB (ComputePictureSpatialStatistics :4631), pic_avg_variance (:4686-4689), the
+ * per-region 256-bin histograms of the 1/16 luma and of the chroma planes (:4146-4284, CalculateHistogram :201-225) and the
+ * average intensities (:4191, :4255, :4746-4748).  Two launches whatever n_pictures is (SB statistics + histograms; the
+ * per-picture sums); nothing is allocated, nothing returns to the host, no buffer has to be zeroed, the call only enqueues and
+ * can be captured into a HIP graph.  No atomics: the result is deterministic.
+ *
+ * Planes, all 8-bit (the reference analyses the 8-bit planes of a 10-bit input too), 4:2:0: k = 0 the padded luma, 1 / 2 the padded
+ * Cb / Cr, 3 the padded 1/16 luma (svt_hip_picture_decimate).  As in svt_hip_me_pyramid d_plane[k] is the START of the buffer,
+ * sample (0, 0) sits at (origin_x[k], origin_y[k]), rows are stride[k] bytes apart, picture i of a stack lies pitch[k] * i bytes
+ * further.  The chroma origin is the luma origin >> 1 (origin_x[1] = origin_x[2] = origin_x[0] >> 1, likewise y).  The luma padding
+ * must be at least 64 samples on every side: a partial SB reads its full 64x64 from the padding, as the reference does.
+ *
+ * Luma 8x8 blocks (ComputeBlockMeanComputeVariance :2066-3084), S = sum of samples, Q = sum of squares:
+ *   block_mean_calc_prec 1 (BLOCK_MEAN_PREC_SUB, what the encoder sets, EbResourceCoordinationProcess.c:599): rows 0, 2, 4, 6 only,
+ *     mean = S << 3, meansq = Q << 11 (compute_interm_var_four8x8_avx2_intrin); 0 (BLOCK_MEAN_PREC_FULL): all rows, mean = S << 2,
+ *     meansq = Q << 10.  16x16, 32x32, 64x64: (a + b + c + d) >> 2 of the four children, mean and meansq separately, level by level
+ *     (:2843-2896).  y_mean = mean >> 8, variance = (uint16)((meansq - mean * mean) >> 16) in 64-bit arithmetic (:2899-3082).
+ * Chroma (ComputeChromaBlockMean :1770-2058): only for complete SBs (origin + 64 <= picture side both ways, is_complete_sb); all 21
+ *   entries of both planes are 0 for the others (ZeroOutChromaBlockMean :1706).  The sixteen 8x8 chroma means by the same SUB / FULL
+ *   formula, their tree to 32x32 and 64x64.  DIVERGENCE KEPT ON PURPOSE: the reference's 64x64 line reads
+ *   (m32[0] + m32[1] + m32[3] + m32[3]) >> 2 (:2006-2007: entry 2 is never added, entry 3 twice), and so does this call.
+ * Histograms: a region is side / regions wide, the last takes the remainder; bins start at 1.  Luma: the 1/16 picture
+ *   ((w >> 2) x (h >> 2)), every sample, each bin << 4 after counting, region average (sum + (area >> 1)) / area.  Chroma: the full
+ *   plane, region origin ((ox + r * regionW) >> 1, (oy + r * regionH) >> 1) with the luma origin and region size, area
+ *   (regionW' >> 1) x (regionH' >> 1), every 4th sample of every 4th row, bins and sum << 4, region average
+ *   (sum + (A >> 3)) / (A >> 2) with A the region's luma area.  Every average is cast to uint8 as the reference casts it.
+ *   Picture averages: :4746-4748, the lines of every scd_mode but SCD_MODE_0.  The SCD_MODE_0 branch (:4718-4743) is outside this
+ *   call: it indexes buffer_y without the picture origin, so it averages the padding.
+ *
+ * Outputs, all on the device, every entry written; SB index s = picture * nsb + sb_y * nsbx + sb_x (nsbx = (width + 63) / 64), rw /
+ * rh = regions_per_width / _height:
+ *   d_y_mean               uint8  [s][85]                  ME_TIER_ZERO_PU_* order (EbMotionEstimationContext.h:50-135): 0 = 64x64,
+ *   d_variance             uint16 [s][85]                  1-4 = 32x32, 5-20 = 16x16, 21-84 = 8x8, each in raster order
+ *   d_cb_mean, d_cr_mean   uint8  [s][21]                  the same order: 5-20 are the 8x8 chroma blocks
+ *   d_pic_avg_variance     uint16 [picture]                sum of the SBs' 64x64 variances / nsb
+ *   d_histogram            uint32 [picture][rw][rh][3][256] picture_histogram[region w][region h][plane]
+ *   d_avg_intensity_region uint8  [picture][rw][rh][3]     average_intensity_per_region
+ *   d_avg_intensity        uint8  [picture][3]             average_intensity
+ *
+ * Every argument is checked before the first launch (SVT_HIP_ERR_INVALID): NULL planes or outputs, misaligned 16- / 32-bit outputs, sides that
+ * are not multiples of 8 or exceed 16384, a precision other than 0 / 1, a region count outside 1 .. 4 or larger than the 1/16
+ * picture's side (the reference divides by a zero area there), luma padding below 64 on any side, a chroma origin that is not
+ * the luma origin >> 1, strides or pitches too small, more than 65535 pictures.  n_pictures = 0 is a successful no-op. */
+enum { SVT_HIP_BLOCK_MEAN_PREC_FULL = 0, SVT_HIP_BLOCK_MEAN_PREC_SUB = 1 };           /* EB_BLOCK_MEAN_PREC */
+enum { SVT_HIP_PIC_STATS_LUMA = 0, SVT_HIP_PIC_STATS_CB = 1, SVT_HIP_PIC_STATS_CR = 2, SVT_HIP_PIC_STATS_SIXTEENTH = 3 };
+typedef struct svt_hip_pic_stats_planes {
+    const uint8_t *d_plane[4];
+    uint32_t stride[4], origin_x[4], origin_y[4];
+    uint64_t pitch[4];                                /* between the pictures of a stack (ignored for n_pictures 1) */
+} svt_hip_pic_stats_planes;
+typedef struct svt_hip_pic_stats_params {
+    int32_t picture_width, picture_height;            /* luma; multiples of 8, at most 16384 */
+    int32_t block_mean_calc_prec;                     /* SVT_HIP_BLOCK_MEAN_PREC_FULL / _SUB */
+    int32_t regions_per_width, regions_per_height;    /* picture_analysis_number_of_regions_per_width / _height, 1 .. 4 */
+} svt_hip_pic_stats_params;
+typedef struct svt_hip_pic_stats_out {
+    uint8_t *d_y_mean;
+    uint16_t *d_variance;
+    uint8_t *d_cb_mean, *d_cr_mean;
+    uint16_t *d_pic_avg_variance;
+    uint32_t *d_histogram;
+    uint8_t *d_avg_intensity_region, *d_avg_intensity;
+} svt_hip_pic_stats_out;
+int svt_hip_picture_stats_frame(const svt_hip_pic_stats_planes *planes, const svt_hip_pic_stats_params *params,
+                                uint32_t n_pictures, const svt_hip_pic_stats_out *out, void *stream);
+
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
  * aom_dsp_rtcd.h it implements (svt_hip_rtcd_slot_count() entries: the 19 av1_fwd_txfm2d_WxH, the 19

@@ -1,0 +1,126 @@
+"""CPU: the C ABI of svt_hip_picture_stats_frame as the header declares it and the Python mirror binds it, and the golden fixture of
+GatheringPictureStatistics (tests/golden/picture_stats.npz, written by tests/golden/make_golden_picture_stats.py: every leaf but two is
+the reference's own function, the glue is the generator's, see there)."""
+import ctypes
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "picture_stats.npz")
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import make_golden_picture_stats as mg  # noqa: E402
+
+HAVE_REF = os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libsvtref.so"))
+INVALID, NO_DEVICE = -2, -1
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(GOLD)
+
+
+def test_fixture_loads_and_meets_the_conditions(gold):
+    mg.check_conditions(gold)
+    assert np.array_equal(gold["cases"], np.array(mg.CASES, np.int32))
+    for ci in range(len(mg.CASES)):
+        for content in mg.CONTENTS:
+            y, cb, cr = mg.frame_of(gold, ci, content)
+            for a, b in zip((y, cb, cr), mg.make_frame(ci, content)):
+                assert np.array_equal(a, b), (ci, content)                             # the frames are the generator's
+    assert os.path.getsize(GOLD) < 1 << 20
+
+
+def test_the_restatement_equals_the_fixture(gold):
+    z = mg.generate(mg.np_picture_stats)
+    assert sorted(z) == sorted(gold.files)
+    for k, v in z.items():
+        assert v.dtype == gold[k].dtype and np.array_equal(v, gold[k]), k
+
+
+def test_hand_computed_blocks():
+    """an SB of 255s: mean * mean = 4 261 478 400 is above int32 and the variance is 0; a 0 / 255 checkerboard: the largest variance;
+    the chroma 64x64 entry takes the fourth 32x32 mean twice and the third never"""
+    y = np.full((64, 64), 255, np.uint8)
+    cb = np.zeros((32, 32), np.uint8)
+    cb[:16, :16], cb[:16, 16:], cb[16:, :16], cb[16:, 16:] = 8, 16, 200, 40
+    cr = np.full((32, 32), 7, np.uint8)
+    for prec in (mg.FULL, mg.SUB):
+        o = mg.np_picture_stats(y, cb, cr, prec, 1, 1)
+        assert (o["y_mean"] == 255).all() and not o["variance"].any() and int(o["pic_avg_variance"][0]) == 0
+        assert o["cb_mean"][0, 1:5].tolist() == [8, 16, 200, 40] and int(o["cb_mean"][0, 0]) == (8 + 16 + 40 + 40) >> 2
+        assert (o["cr_mean"] == 7).all()
+        # the luma histogram is of the 16 x 16 1/16 picture: bin 255 holds (1 + 256) << 4, every other bin 1 << 4
+        assert int(o["histogram"][0, 0, 0, 255]) == 257 << 4 and int(o["histogram"][0, 0, 0, 0]) == 16
+        # chroma: every 4th sample of every 4th row of 32 x 32 = 64 samples, 16 per quadrant
+        assert [int(o["histogram"][0, 0, 1, v]) for v in (8, 16, 200, 40)] == [17 << 4] * 4
+        assert o["avg"].tolist() == [255, (8 + 16 + 200 + 40) // 4, 7] and o["avg_region"][0, 0].tolist() == o["avg"].tolist()
+    yy, xx = np.mgrid[0:64, 0:64]
+    o = mg.np_picture_stats((((xx + yy) & 1) * 255).astype(np.uint8), cb, cr, mg.FULL, 1, 1)
+    assert (o["variance"] == 16256).all()
+
+
+@pytest.mark.skipif(not HAVE_REF, reason="needs the reference build (oracle/_ref)")
+def test_the_reference_regenerates_the_fixture_and_the_sub_restatement_equals_the_avx2_leaf(gold):
+    R = mg.ref_lib()
+    mg.check_sub_restatement(R, np.random.default_rng(0x5056), 2000)
+    z = mg.generate(lambda *a: mg.ref_picture_stats(R, *a))
+    assert sorted(z) == sorted(gold.files)
+    for k, v in z.items():
+        assert v.dtype == gold[k].dtype and np.array_equal(v, gold[k]), k
+    # the planes: Decimation2D and generate_padding against the restatement's slicing and edge replication
+    y, cb, cr = mg.make_frame(0, "random")
+    for (a, oa), (b, ob) in zip(mg.ref_planes(R, y, cb, cr), mg.np_planes(y, cb, cr)):
+        assert oa == ob and np.array_equal(a, b)
+
+
+def test_header_declares_the_entry_and_the_mirror_sets_argtypes_and_restype(pkg):
+    hdr = open(os.path.join(ROOT, "include", "svt_hip_dsp.h")).read()
+    assert "int svt_hip_picture_stats_frame(const svt_hip_pic_stats_planes *planes, const svt_hip_pic_stats_params *params," in hdr
+    for cite in (":4759-4812", ":2066-3084", ":1770-2058", ":1706", ":2006-2007", ":4146-4284", ":201-225", ":4746-4748", ":4718-4743",
+                 "EbResourceCoordinationProcess.c:599", "EbMotionEstimationContext.h:50-135"):
+        assert cite in hdr, cite
+    lib = pkg.load_library()
+    f = lib.svt_hip_picture_stats_frame
+    assert f.argtypes is not None and len(f.argtypes) == 5 and f.restype is ctypes.c_int
+    assert pkg.SvtHipDsp.BLOCK_MEAN_PREC_FULL == mg.FULL == 0 and pkg.SvtHipDsp.BLOCK_MEAN_PREC_SUB == mg.SUB == 1
+    assert pkg.PicStatsResult._fields == ("y_mean", "variance", "cb_mean", "cr_mean", "pic_avg_variance", "histogram", "avg_intensity_region",
+                                          "avg_intensity")
+
+
+def test_struct_layouts_match_the_header(pkg):
+    structs = (("svt_hip_pic_stats_planes", pkg.PicStatsPlanes), ("svt_hip_pic_stats_params", pkg.PicStatsParams), ("svt_hip_pic_stats_out", pkg.PicStatsOut))
+    args, want = [], []
+    for cname, S in structs:
+        fields = [n for n, _ in S._fields_]
+        args += [f"sizeof({cname})"] + [f"offsetof({cname}, {n})" for n in fields]
+        want += [ctypes.sizeof(S)] + [getattr(S, n).offset for n in fields]
+    code = ('#include <stddef.h>\n#include <stdio.h>\n#include "svt_hip_dsp.h"\nint main(void){printf("%zu"' + ' " %zu"' * (len(args) - 1) + ", " +
+            ", ".join(args) + ");return 0;}\n")
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(code)
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        out = [int(v) for v in subprocess.check_output([os.path.join(d, "t")]).decode().split()]
+    assert out == want
+
+
+def test_the_call_without_a_device_or_with_null_arguments(pkg):
+    """NULL structs: SVT_HIP_ERR_INVALID (-2) on a machine with a device, SVT_HIP_ERR_NO_DEVICE (-1) without one, as the sibling calls
+    answer (the device is looked for first); the call never returns a result"""
+    import torch
+    lib = pkg.load_library()
+    bad = INVALID if torch.cuda.is_available() else NO_DEVICE
+    prm = pkg.PicStatsParams(64, 64, 1, 4, 4)
+    assert lib.svt_hip_picture_stats_frame(None, ctypes.addressof(prm), 1, None, None) == bad
+    assert lib.svt_hip_picture_stats_frame(None, None, 0, None, None) == bad
+
+
+def test_both_kernels_are_in_the_built_library():
+    """so that tests/test_kernel_resources.py, which holds every kernel of the library to no scratch, covers them"""
+    lib = os.path.join(ROOT, "cidana-svt-av1_amd", "libsvt_hip_dsp.so")
+    data = open(lib, "rb").read()
+    assert b"picture_stats_kernel" in data and b"picture_stats_sum_kernel" in data

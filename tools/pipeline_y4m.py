@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """The hot path end to end on a y4m file (every row of SURVEY 8(f) working on the others' outputs), per frame:
    picture input    file -> pinned -> HBM -> padded planes + 1/4 and 1/16 luma pictures   (frames.PictureInput, n4)
+   picture stats    (--picture-stats, 8-bit clips) block means / variances, histograms, average intensities   (svt_hip_picture_stats_frame)
    HME 0 / 1 / 2    every 64x64 SB against the previous picture's pyramid, vectors stay on the device   (svt_hip_hme_level_batch, n1)
    ME set-up        best HME region, CheckZeroZeroCenter, per-SB search area clipped as MotionEstimateLcu does   (svt_hip_me_setup_batch, n1)
    full-pel ME      209 PUs per SB over its own (up to 64x64) area, one launch   (svt_hip_me_fullpel_search_areas_batch, a11)
@@ -49,15 +50,19 @@ def synthetic_clip(path, w, h, nf, seed=3, pan=(3, 1), bd=8):
 
 
 class Pipeline:
-    def __init__(self, dsp, path, qindex=100, use_graph=False, me_frame=False):
+    def __init__(self, dsp, path, qindex=100, use_graph=False, me_frame=False, picture_stats=False):
         self.dsp = dsp
         self.me_frame = me_frame
+        self.picture_stats, self.stats_out = picture_stats, None
         self.use_graph, self.graph, self.graph_out, self.count = use_graph, None, None, 0
         self.pi = frames.PictureInput(dsp, pkg, path, origin=(68, 68))
         pi = self.pi
         # a 10-bit clip: the analysis stages read the 8-bit plane (the samples' top 8 bits, as in the reference), the encode pass the
         # 16-bit samples at bd 10
         dev = pi.planes[0].device
+        if picture_stats and pi.is16:
+            pi.close()
+            raise pkg.SvtHipError("picture_stats reads 8-bit chroma planes, which PictureInput keeps for 8-bit clips only")
         self.W, self.H, self.pad = pi.W, pi.H, pi.ox
         W, H = self.W, self.H
         sbs = [(x, y) for y in range(0, H, 64) for x in range(0, W, 64)]
@@ -120,6 +125,14 @@ class Pipeline:
         out = {}
         y = pi.luma8 if pi.is16 else planes[0]             # the plane HME / ME / the intra search read
         pic = y[self.pad:, self.pad:]
+        if self.picture_stats:
+            # GatheringPictureStatistics on the planes the import and the decimation just wrote (SUB precision, 4 x 4 regions: the encoder's)
+            p2, p4 = self.pad >> 1, self.pad >> 2
+            st = self.stats_out = dsp.picture_stats_frame(dsp.pic_stats_planes([y, planes[1], planes[2], pi.sixteenth],
+                                                                               [(self.pad, self.pad), (p2, p2), (p2, p2), (p4, p4)]),
+                                                          self.W, self.H, out=self.stats_out)
+            for k, v in st._asdict().items():
+                out["stats_" + k] = v
         # open-loop intra search on the source picture
         out["ois"] = dsp.ois_search_frame(pic, y.stride(0), self.W, self.H, self.ois_groups)
         if self.prev is not None and self.me_frame:
@@ -217,6 +230,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="capture the per-picture analysis into a HIP graph and replay it")
     ap.add_argument("--me-frame", action="store_true", help="HME, ME set-up and the search through svt_hip_motion_estimate_frame (one call, "
                     "three launches); a stage-call pass runs first and the digests both paths share must be equal")
+    ap.add_argument("--picture-stats", action="store_true", help="GatheringPictureStatistics between the input and HME "
+                    "(svt_hip_picture_stats_frame: one call, two launches); 8-bit clips")
     a = ap.parse_args()
     dsp = pkg.SvtHipDsp(0)
     tmp = None
@@ -228,7 +243,7 @@ def main():
         synthetic_clip(path, w, h, a.frames, bd=a.bd)
     results = []
     for rep in range(2):                                  # the second pass is timed (page cache, allocator, first-launch costs settled)
-        p = Pipeline(dsp, path, use_graph=a.graph, me_frame=a.me_frame and rep == 1)
+        p = Pipeline(dsp, path, use_graph=a.graph, me_frame=a.me_frame and rep == 1, picture_stats=a.picture_stats)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         n, last = 0, None
