@@ -155,6 +155,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_full_loop_frame.restype = c_int
     L.svt_hip_intra_fast_loop_frame.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p]
     L.svt_hip_intra_fast_loop_frame.restype = c_int
+    L.svt_hip_fast_pick_frame.argtypes = [c_void_p, c_int, c_int, c_void_p]
+    L.svt_hip_fast_pick_frame.restype = c_int
+    L.svt_hip_intra_fast_search_scratch_bytes.argtypes = [c_void_p, c_int]
+    L.svt_hip_intra_fast_search_scratch_bytes.restype = c_size_t
+    L.svt_hip_intra_fast_search_frame.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_intra_fast_search_frame.restype = c_int
     L.svt_hip_md_intra_candidates.argtypes = [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_void_p, c_void_p]
     L.svt_hip_md_intra_candidates.restype = c_int
     L.svt_hip_cdef_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
@@ -1553,6 +1559,138 @@ class SvtHipDsp:
                  modes=modes, deltas=deltas, dist=dist, pred=pred)
         self._check(self.intra_fast_loop_frame([g], metric, flavour), "svt_hip_intra_fast_loop_frame")
         return dist, pred
+
+    # -- the end of the fast loop: fast cost, the N best, their order, the survivors' predictions gathered --------------------------
+    MAX_NFL = 40
+    FAST_RATE_TABLES = (("yModeFacBits", (5, 5, 14)), ("mbModeFacBits", (4, 14)), ("intraUVmodeFacBits", (2, 13, 15)),
+                        ("angleDeltaFacBits", (8, 8)), ("skipModeFacBits", (3, 3)), ("intraInterFacBits", (4, 2)))       # svt_hip_fast_rates
+    FAST_RATE_WORDS = 877
+    FAST_PICK_BLK_DTYPE = [("top_mode", "u1"), ("left_mode", "u1"), ("skip_mode_ctx", "u1"), ("is_inter_ctx", "u1"), ("has_chroma", "u1"),
+                           ("pad", "u1", (3,))]                              # svt_hip_fast_pick_blk
+
+    class FastPickGroup(ctypes.Structure):
+        _fields_ = [("tx_size", c_int32), ("bsize", c_int32), ("bsize_uv", c_int32), ("nblocks", c_uint32),
+                    ("ncand", c_int32), ("modes", ctypes.c_uint8 * 64), ("angle_deltas", ctypes.c_int8 * 64),
+                    ("uv_modes", ctypes.c_uint8 * 64), ("uv_angle_deltas", ctypes.c_int8 * 64),
+                    ("use_angle_delta", c_int32), ("nfl", c_int32), ("slice_is_intra", c_int32), ("lambda_", c_uint32),
+                    ("ac_dequant_q3", c_int16), ("intrabc_bits", c_uint32),
+                    ("d_dist", c_void_p), ("d_dist_cb", c_void_p), ("d_dist_cr", c_void_p), ("d_blk", c_void_p), ("d_rates", c_void_p),
+                    ("d_pred", c_void_p), ("d_src_xy", c_void_p), ("d_cand", c_void_p), ("d_sorted", c_void_p), ("d_cost", c_void_p),
+                    ("d_rate", c_void_p), ("d_ref_fast_cost", c_void_p), ("d_all_cost", c_void_p), ("d_pred_out", c_void_p),
+                    ("d_src_xy_out", c_void_p)]
+
+    class IntraFastSearchGroup(ctypes.Structure):
+        pass                                                              # (a nested class body does not see its siblings)
+
+    IntraFastSearchGroup._fields_ = [("luma", FastLoopGroup), ("use_chroma", c_int32), ("cb", FastLoopGroup), ("cr", FastLoopGroup),
+                                     ("pick", FastPickGroup)]
+    FAST_PICK_OUTPUTS = ("cand", "sorted", "cost", "rate", "ref_fast_cost", "all_cost", "pred_out", "src_xy_out")
+
+    @staticmethod
+    def pack_fast_rates(tables):
+        """dict of the six int32 tables (FAST_RATE_TABLES shapes) -> int32 [877] in svt_hip_fast_rates order"""
+        import numpy as np
+        parts = []
+        for name, shape in SvtHipDsp.FAST_RATE_TABLES:
+            a = np.asarray(tables[name], np.int32)
+            assert a.shape == shape, (name, a.shape)
+            parts.append(a.reshape(-1))
+        return np.concatenate(parts)
+
+    def _fast_pick_struct(self, g):
+        P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+        pad = lambda k, ct: (ct * 64)(*(list(g.get(k, []))[:64] + [0] * (64 - len(list(g.get(k, []))[:64]))))
+        modes = list(g.get("modes", []))
+        return self.FastPickGroup(g.get("tx_size", 0), g.get("bsize", 0), g.get("bsize_uv", 0), g.get("nblocks", 0), g.get("ncand", len(modes)),
+                                  pad("modes", ctypes.c_uint8), pad("deltas", ctypes.c_int8), pad("uv_modes", ctypes.c_uint8),
+                                  pad("uv_deltas", ctypes.c_int8), int(g.get("use_angle_delta", 0)), g.get("nfl", 0),
+                                  int(g.get("slice_is_intra", 0)), g.get("lambda", 0), g.get("ac_dequant_q3", 0), g.get("intrabc_bits", 0),
+                                  P("dist"), P("dist_cb"), P("dist_cr"), P("blk"), P("rates"), P("pred"), P("src_xy"), P("cand"), P("sorted"),
+                                  P("cost"), P("rate"), P("ref_fast_cost"), P("all_cost"), P("pred_out"), P("src_xy_out"))
+
+    def make_fast_pick_groups(self, groups):
+        """groups: list of dicts with tensors dist (int64 [n, ncand], the fast loop's), optional dist_cb / dist_cr, blk (uint8 [n, 8]:
+        FAST_PICK_BLK_DTYPE records), rates (int32 [877]: pack_fast_rates), optional pred (uint8 [n, ncand, H, W]) and src_xy (int32 [n]),
+        the outputs cand / sorted (uint8 [n, N]), cost (int64 [n, N]), rate (int32 [n, N, 2]), ref_fast_cost (int64 [n]), optional all_cost
+        (int64 [n, ncand]), pred_out (uint8 [n, N, H, W]), src_xy_out (int32 [n, N]) with N = min(nfl, ncand), plus tx_size, bsize, bsize_uv,
+        nblocks, modes, deltas, uv_modes, uv_deltas (host lists), use_angle_delta, nfl, slice_is_intra, lambda, ac_dequant_q3,
+        intrabc_bits.  -> ctypes array (keep the tensors alive!)"""
+        arr = (self.FastPickGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            arr[i] = self._fast_pick_struct(g)
+        return arr
+
+    def fast_pick_frame(self, groups, metric):
+        """svt_hip_fast_pick_frame.  groups: a ctypes array from make_fast_pick_groups or the list of dicts -> the library's return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_fast_pick_groups(groups)
+        return self.lib.svt_hip_fast_pick_frame(groups, n, metric, self._stream())
+
+    def fast_pick(self, dist, blk, rates, tx_size, bsize, bsize_uv, modes, deltas, uv_modes, uv_deltas, nfl, lam, metric, use_angle_delta=True,
+                  slice_is_intra=True, ac_dequant_q3=0, intrabc_bits=0, dist_cb=None, dist_cr=None, pred=None, src_xy=None, want_all_cost=False):
+        """One group; the outputs are allocated here.  -> dict of cand, sorted, cost, rate, ref_fast_cost and, when asked for or their input
+        is given, all_cost, pred_out, src_xy_out"""
+        t = self.torch
+        n, nc = dist.shape[0], len(modes)
+        N = max(1, min(nfl, nc))
+        w, h = (TX_W[tx_size], TX_H[tx_size]) if 0 <= tx_size < 19 else (4, 4)
+        d = dist.device
+        g = dict(dist=dist, dist_cb=dist_cb, dist_cr=dist_cr, blk=blk, rates=rates, pred=pred, src_xy=src_xy, tx_size=tx_size, bsize=bsize,
+                 bsize_uv=bsize_uv, nblocks=n, modes=modes, deltas=deltas, uv_modes=uv_modes, uv_deltas=uv_deltas, nfl=nfl,
+                 use_angle_delta=use_angle_delta, slice_is_intra=slice_is_intra, ac_dequant_q3=ac_dequant_q3, intrabc_bits=intrabc_bits,
+                 cand=t.empty((n, N), dtype=t.uint8, device=d), sorted=t.empty((n, N), dtype=t.uint8, device=d),
+                 cost=t.empty((n, N), dtype=t.int64, device=d), rate=t.empty((n, N, 2), dtype=t.int32, device=d),
+                 ref_fast_cost=t.empty((n,), dtype=t.int64, device=d))
+        g["lambda"] = lam
+        if want_all_cost:
+            g["all_cost"] = t.empty((n, nc), dtype=t.int64, device=d)
+        if pred is not None:
+            g["pred_out"] = t.empty((n, N, h, w), dtype=t.uint8, device=d)
+        if src_xy is not None:
+            g["src_xy_out"] = t.empty((n, N), dtype=t.int32, device=d)
+        self._check(self.fast_pick_frame([g], metric), "svt_hip_fast_pick_frame")
+        return {k: g[k] for k in self.FAST_PICK_OUTPUTS if g.get(k) is not None}
+
+    def make_intra_fast_search_groups(self, groups):
+        """groups: list of dicts {"luma": a fast-loop group dict (make_fast_loop_groups; dist / pred may be absent: scratch), optional "cb" /
+        "cr": fast-loop group dicts of the chroma planes (dist may be absent), "pick": a fast-pick group dict (its size, list, dist*, pred
+        come from the fast-loop groups)}.  -> ctypes array (keep the tensors alive!)"""
+        arr = (self.IntraFastSearchGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            arr[i].luma = self.make_fast_loop_groups([g["luma"]])[0]
+            arr[i].use_chroma = int(g.get("cb") is not None)
+            if g.get("cb") is not None:
+                arr[i].cb = self.make_fast_loop_groups([g["cb"]])[0]
+                arr[i].cr = self.make_fast_loop_groups([g["cr"]])[0]
+            arr[i].pick = self._fast_pick_struct(g["pick"])
+        return arr
+
+    def intra_fast_search_scratch_bytes(self, groups):
+        """svt_hip_intra_fast_search_scratch_bytes of a ctypes array from make_intra_fast_search_groups or of the list of dicts"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_intra_fast_search_groups(groups)
+        return self.lib.svt_hip_intra_fast_search_scratch_bytes(groups, n)
+
+    def intra_fast_search_frame(self, groups, metric, scratch, flavour=1):
+        """svt_hip_intra_fast_search_frame: fast loop (luma, Cb, Cr) -> pick in one call.  scratch: a uint8 device tensor of at least
+        intra_fast_search_scratch_bytes(groups) bytes (None where that is 0).  -> the library's return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_intra_fast_search_groups(groups)
+        return self.lib.svt_hip_intra_fast_search_frame(groups, n, metric, flavour, self._p(scratch) if scratch is not None else None,
+                                                        scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+
+    def intra_fast_search(self, luma, pick, metric, cb=None, cr=None, flavour=1):
+        """One group with the per-candidate arrays in a scratch allocated here: luma / cb / cr fast-loop group dicts without dist / pred, pick
+        a fast-pick group dict with its outputs.  -> the pick dict"""
+        t = self.torch
+        g = [dict(luma=luma, cb=cb, cr=cr, pick=pick)]
+        need = self.intra_fast_search_scratch_bytes(g)
+        scratch = t.empty((need,), dtype=t.uint8, device=pick["cand"].device) if need else None
+        self._check(self.intra_fast_search_frame(g, metric, scratch, flavour), "svt_hip_intra_fast_search_frame")
+        return pick
 
     class CdefPic(ctypes.Structure):
         """svt_hip_cdef_pic"""

@@ -103,6 +103,8 @@ svtdev::QParams quant_params(const int16_t* zbin, const int16_t* round, const in
 int full_loop_check(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const int16_t* zbin, const int16_t* round,
                     const int16_t* quant, const int16_t* quant_shift, const int16_t* dequant);
 int coeff_rate_check(const svt_hip_coeff_rate_group* groups, int ngroups);
+// the argument check of svt_hip_intra_fast_loop_frame (svt_hip_fast_loop.hip): svt_hip_intra_fast_search_frame runs it before its first launch
+int fast_loop_check(const svt_hip_fast_loop_group* groups, int ngroups, int metric, int flavour);
 // the launches of svt_hip_coeff_rate_frame for groups that coeff_rate_check accepted (svt_hip_cfl_search_frame's rate stage: nothing is
 // validated again after its first launch)
 int coeff_rate_enqueue(const svt_hip_coeff_rate_group* groups, int ngroups, hipStream_t s);

@@ -8,7 +8,7 @@ using namespace svthost;
 
 static_assert(sizeof(svt_hip_intra_blk) == sizeof(BipBlk), "svt_hip_intra_blk layout");
 
-static int fast_loop_check(const svt_hip_fast_loop_group* groups, int ngroups, int metric, int flavour) {
+int svthost::fast_loop_check(const svt_hip_fast_loop_group* groups, int ngroups, int metric, int flavour) {
     if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
     if (metric != SVT_HIP_FAST_SAD && metric != SVT_HIP_FAST_SSD) return set_err(SVT_HIP_ERR_INVALID, "metric %d", metric);
     if (flavour != SVT_HIP_FLAVOUR_C && flavour != SVT_HIP_FLAVOUR_AVX2) return set_err(SVT_HIP_ERR_INVALID, "flavour %d", flavour);

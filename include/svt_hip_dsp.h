@@ -1050,6 +1050,112 @@ typedef struct svt_hip_fast_loop_group {
 } svt_hip_fast_loop_group;
 int svt_hip_intra_fast_loop_frame(const svt_hip_fast_loop_group *groups, int ngroups, int metric, int flavour, void *stream);
 
+/* The end of the fast loop for an all-intra candidate list, on the device: the fast cost of every (block, candidate), the buffer walk
+ * that keeps the N best, the two index arrays, and the gather of the survivors' predictions into the layout the full loop reads.
+ * svt_hip_intra_fast_loop_frame writes its inputs, svt_hip_full_loop_frame / svt_hip_tx_search_frame read its outputs as they lie.
+ * What is reproduced (all of it restated from the reference and NOT pinned to a compiled reference: see DESIGN.md 4.31):
+ *   cost     av1_intra_fast_cost (EbRateDistortionCost.c:531-729), the non-intrabc branch (:598-728): the mode / skip-mode / is-inter /
+ *            angle-delta / uv-mode bits out of d_rates (MdRateEstimationContext_s, EbMdRateEstimation.h:59, 93-103, in the reference's
+ *            declaration shapes), intra_mode_context / size_group_lookup / num_pels_log2_lookup (EbDefinitions.h:1213, 1311, 1315),
+ *            RDCOST (EbRateDistortionCost.h:71-75) = ((rate * lambda + 256) >> 9) + dist * 128 in uint64.  SVT_HIP_FAST_SSD takes the
+ *            branch at :687-716: model_rd_from_sse -> av1_model_rd_from_var_lapndz -> model_rd_norm (EbInterPrediction.c:3311-3438).
+ *   walk     perform_fast_loop (EbProductCodingLoop.c:1152-1365) as md_encode_block calls it (:3103-3131): n = min(ncand, nfl) full-loop
+ *            slots, n + 1 buffers when ncand > n (one scratch), the candidates taken from the LAST list entry down to entry 0, each
+ *            into the buffer the re-scan (:1331-1356, strict >, stops at the first empty buffer) found, the last one emptied (:1361).
+ *   order    sort_fast_loop_candidates (EbModeDecision.c:436-489): best_candidate_index_array = the buffers in buffer order, the empty
+ *            one last; ref_fast_cost; sorted_candidate_index_array.
+ * Quirks kept, because AV1PerformFullLoop (:1919-1923) and get_skip_tx_search_flag (:1866-1878) consume exactly these values:
+ *   - the rates are summed in uint32; fast_luma_rate / fast_chroma_rate (d_rate) are stored BEFORE the SSD model's rates are added;
+ *     the SSD chroma call writes the model's rate OVER chromaRate (:704-710), so the chroma mode bits drop out of the SSD cost;
+ *   - ref_fast_cost starts at MAX_MODE_COST (13616969489728 * 8) and is the minimum over buffers 0 .. n-1 BY BUFFER INDEX (:472-476):
+ *     the scratch buffer may be among them, a real candidate in buffer n is then left out;
+ *   - the sorted array is bubble-swapped on the costs of BUFFERS i and j, not of the entries being swapped (:480-488);
+ *   - the candidate's use_angle_delta is the block-size flag AND "luma mode is directional" (:2444, :2490): the uv angle-delta bits
+ *     are counted only under a directional luma mode.  The group's use_angle_delta is the block-size flag (bsize >= BLOCK_8X8).
+ *   - UV_CFL_PRED (13) is costed as UV_DC_PRED (:606); cfl_allowed = W <= 32 && H <= 32 (:601).
+ * has_chroma gates the uv rate bits only (blk_geom->has_uv && is_chroma_reference(mi_row, mi_col, bsize, 1, 1), :666-667); the chroma
+ * distortions d_dist_cb + d_dist_cr are added for every block when given (the reference adds them when has_uv under CHROMA_MODE_0:
+ * give zeros for blocks without chroma; NULL = 0, any other chroma level).  Context bytes are device data and are clamped on the
+ * device (modes to 12, skip_mode_ctx to 2, is_inter_ctx to 3): an out-of-range byte gives an unspecified cost for its block, nothing
+ * else.  A cost equal to MAX_CU_COST (UINT64_MAX >> 1) or above cannot be told from an empty buffer in the reference: the block's
+ * results are then unspecified (the stores stay inside the block's rows).
+ * Outputs, n = min(nfl, ncand), [nblocks][n] unless stated: d_cand = the list index of the candidate in full-loop slot k
+ * (best_candidate_index_array order); d_sorted = sorted_candidate_index_array[k] as the SLOT that holds that buffer (the reference's
+ * value is a buffer index; slots are what this interface exposes); d_cost = the candidate's fast cost; d_rate [..][2] = fast_luma_rate,
+ * fast_chroma_rate; d_ref_fast_cost [nblocks]; optional d_all_cost [nblocks][ncand] = every candidate's cost; optional d_pred_out
+ * [nblocks][n][H][W] (needs d_pred, the fast loop's [nblocks][ncand][H][W]) = the d_pred of a svt_hip_full_loop_group of nblocks * n
+ * blocks; optional d_src_xy_out [nblocks][n] (needs d_src_xy) = the block's origin repeated, that group's d_src_xy.
+ * Validation, every group before the first launch (SVT_HIP_ERR_INVALID, nothing launched): metric; tx_size 0 .. 18; bsize / bsize_uv
+ * 0 .. 21; ncand 1 .. 64; nfl 1 .. 40; a mode above 12, a uv mode above 13, a delta outside -3 .. 3; ac_dequant_q3 < 0; and for non-empty
+ * groups NULL d_dist / d_blk / d_rates / d_cand / d_sorted / d_cost / d_rate / d_ref_fast_cost, d_pred_out without d_pred,
+ * d_src_xy_out without d_src_xy, d_pred_out == d_pred, misalignment (d_pred / d_pred_out 16 bytes; the 8-byte arrays and d_blk 8;
+ * d_rates / d_rate / d_src_xy* 4), nblocks * ncand above 2^31 - 1.  One launch per non-empty group, the group in the kernel arguments; the call
+ * only enqueues (no allocation, no synchronisation) and can be captured into a HIP graph.
+ * Left to the caller: inter candidates (the first, src-to-src loop and the inter-before-intra swap), the intrabc branch
+ * (:556-597; intrabc_bits is intrabcFacBits[0] when the picture allows intrabc, else 0), and product_full_mode_decision. */
+#define SVT_HIP_MAX_NFL 40
+typedef struct svt_hip_fast_pick_blk {
+    uint8_t top_mode, left_mode;         /* intra_luma_top_mode / intra_luma_left_mode, 0 .. 12 */
+    uint8_t skip_mode_ctx;               /* cu_ptr->skip_flag_context, 0 .. 2 */
+    uint8_t is_inter_ctx;                /* cu_ptr->is_inter_ctx, 0 .. 3 */
+    uint8_t has_chroma;                  /* blk_geom->has_uv && is_chroma_reference(...) */
+    uint8_t pad[3];
+} svt_hip_fast_pick_blk;
+typedef struct svt_hip_fast_rates {      /* the int32 tables of MdRateEstimationContext_s the intra fast cost reads */
+    int32_t yModeFacBits[5][5][14];
+    int32_t mbModeFacBits[4][14];
+    int32_t intraUVmodeFacBits[2][13][15];
+    int32_t angleDeltaFacBits[8][8];
+    int32_t skipModeFacBits[3][3];
+    int32_t intraInterFacBits[4][2];
+} svt_hip_fast_rates;
+typedef struct svt_hip_fast_pick_group {
+    int32_t tx_size;                     /* 0 .. 18: the block, as in svt_hip_fast_loop_group */
+    int32_t bsize, bsize_uv;             /* AV1 block_size order, 0 .. 21 */
+    uint32_t nblocks;
+    int32_t ncand; uint8_t modes[64]; int8_t angle_deltas[64];          /* HOST-side list, as svt_hip_fast_loop_group */
+    uint8_t uv_modes[64]; int8_t uv_angle_deltas[64];                   /* 0 .. 13 (UV_CFL_PRED = 13), -3 .. 3 */
+    int32_t use_angle_delta;             /* bsize >= BLOCK_8X8 */
+    int32_t nfl;                         /* full_recon_search_count, 1 .. SVT_HIP_MAX_NFL */
+    int32_t slice_is_intra;
+    uint32_t lambda;                     /* fast_lambda (SAD) / full_lambda (SSD) */
+    int16_t ac_dequant_q3;               /* y_dequant_Q3[qindex][1]; SSD only */
+    uint32_t intrabc_bits;
+    const uint64_t *d_dist, *d_dist_cb, *d_dist_cr;                     /* [nblocks][ncand]; cb / cr optional */
+    const svt_hip_fast_pick_blk *d_blk;  /* [nblocks] */
+    const svt_hip_fast_rates *d_rates;
+    const uint8_t *d_pred;               /* optional [nblocks][ncand][H][W] */
+    const uint32_t *d_src_xy;            /* optional [nblocks] */
+    uint8_t *d_cand, *d_sorted;          /* [nblocks][n] */
+    uint64_t *d_cost;                    /* [nblocks][n] */
+    uint32_t *d_rate;                    /* [nblocks][n][2] */
+    uint64_t *d_ref_fast_cost;           /* [nblocks] */
+    uint64_t *d_all_cost;                /* optional [nblocks][ncand] */
+    uint8_t *d_pred_out;                 /* optional [nblocks][n][H][W] */
+    uint32_t *d_src_xy_out;              /* optional [nblocks][n] */
+} svt_hip_fast_pick_group;
+int svt_hip_fast_pick_frame(const svt_hip_fast_pick_group *groups, int ngroups, int metric, void *stream);
+
+/* The whole intra fast search in one call: svt_hip_intra_fast_loop_frame (luma, then the Cb and Cr groups when use_chroma) ->
+ * svt_hip_fast_pick_frame on `stream`, whose order carries the dependency.  Host composition: it has no kernel of its own.  The
+ * pick's tx_size, nblocks, ncand, modes, angle_deltas, d_dist*, d_pred and d_src_xy are taken from the fast-loop groups (what `pick`
+ * holds there is ignored; a luma group with a dense source, d_src_xy NULL, leaves the pick's own d_src_xy in place); cb / cr carry the chroma size and the uv candidates as intra modes, with luma's nblocks and ncand.  Arrays
+ * the caller does not keep live in d_scratch (16-byte aligned), carved per non-empty group in group order, each piece rounded up to
+ * 16 bytes: luma.d_dist when NULL (nblocks * ncand * 8), cb.d_dist and cr.d_dist likewise when use_chroma, luma.d_pred when NULL and
+ * pick.d_pred_out asks for it (nblocks * ncand * W * H).  svt_hip_intra_fast_search_scratch_bytes returns their sum, a HOST
+ * computation that needs no device (0: bad parameters, or nothing needed).  Every stage's arguments are validated before the first
+ * launch; a scratch that is NULL, misaligned or too small returns SVT_HIP_ERR_INVALID.  Every candidate's prediction is still stored;
+ * regenerating only the winners' is out of scope. */
+typedef struct svt_hip_intra_fast_search_group {
+    svt_hip_fast_loop_group luma;
+    int32_t use_chroma;                  /* non-zero: cb and cr are fast-loop groups of the chroma planes */
+    svt_hip_fast_loop_group cb, cr;
+    svt_hip_fast_pick_group pick;
+} svt_hip_intra_fast_search_group;
+size_t svt_hip_intra_fast_search_scratch_bytes(const svt_hip_intra_fast_search_group *groups, int ngroups);
+int svt_hip_intra_fast_search_frame(const svt_hip_intra_fast_search_group *groups, int ngroups, int metric, int flavour,
+                                    void *d_scratch, size_t scratch_bytes, void *stream);
+
 /* CDEF for whole 4:2:0 pictures: the strength search and the apply.  One descriptor serves both calls: a picture (or a stack of
  * npics pictures of one geometry, *_pitch samples / skip_pitch bytes apart) of width x height luma samples, both multiples of 8 as the
  * reference's padded pictures are; planes of uint8 (bit_depth 8) or uint16 (bit_depth 10; coeff_shift = bit_depth - 8) samples with

@@ -1,0 +1,244 @@
+"""CPU: the fixture of svt_hip_fast_pick_frame (tests/golden/fast_pick.npz, written by tests/golden/make_golden_fast_pick.py: the
+reference's loops restated in Python integers, UNPINNED but for has_chroma, see there), its numpy restatement, the properties of the
+buffer walk that do not depend on how it is written, the C ABI of the three entry points and the new kernel's resources."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "fast_pick.npz")
+LIB = os.path.join(ROOT, "cidana-svt-av1_amd", "libsvt_hip_dsp.so")
+LLVM = "/opt/rocm/lib/llvm/bin"
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import make_golden_fast_pick as mg  # noqa: E402
+
+INVALID, NO_DEVICE = -2, -1
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(GOLD)
+
+
+def test_fixture_loads_and_meets_the_conditions(gold):
+    mg.check_conditions(gold)
+    assert [str(n) for n in gold["names"]] == mg.CASE_NAMES
+    assert os.path.getsize(GOLD) < 1 << 20
+    lams = {mg.case_of(gold, ci)[0]["lambda"] for ci in range(mg.NCASES)}
+    assert lams == set(mg.LAMBDAS)
+
+
+def test_the_restatement_equals_the_fixture(gold):
+    z = mg.generate(mg.np_fast_pick)
+    assert sorted(z) == sorted(gold.files)
+    for k, v in z.items():
+        assert v.dtype == gold[k].dtype and np.array_equal(v, gold[k]), k
+
+
+def test_has_chroma_of_the_fixture_is_is_chroma_reference(gold):
+    """the fixture's has_chroma bytes never exceed is_chroma_reference at the stored mi position (has_uv can only clear them; blocks 0
+    and 1 are forced), and the helper equals the reference's function where the compiled reference is there"""
+    for ci in range(mg.NCASES):
+        P, _, _, _, blk, _, _ = mg.case_of(gold, ci)
+        mi = gold[f"c{ci}_mi"]
+        for b in range(2, len(blk)):
+            assert int(blk["has_chroma"][b]) <= mg.np_is_chroma_reference(int(mi[b, 0]), int(mi[b, 1]), P["bsize"])
+    assert mg.np_is_chroma_reference(0, 0, 0) == 0 and mg.np_is_chroma_reference(1, 1, 0) == 1 and mg.np_is_chroma_reference(0, 0, 3) == 1
+    assert mg.np_is_chroma_reference(1, 0, 16) == 0 and mg.np_is_chroma_reference(0, 1, 16) == 1          # 4x16: only the column counts
+    if os.path.exists(mg.REF):
+        assert mg.check_is_chroma_reference()
+
+
+def test_distinct_costs_keep_exactly_the_n_smallest():
+    """independent of the buffer walk: with distinct costs the survivors are the n smallest, whatever their order"""
+    rng = np.random.default_rng(31)
+    for C, nfl in ((61, 3), (61, 12), (61, 40), (13, 5), (2, 1), (64, 40), (41, 40)):
+        cost = np.stack([rng.permutation(100000)[:C] for _ in range(50)]).astype(np.uint64)
+        cand, srt, ref = mg.np_walk(cost, nfl)
+        n = min(nfl, C)
+        for b in range(len(cost)):
+            assert set(cand[b].tolist()) == set(np.argsort(cost[b])[:n].tolist()), (C, nfl, b)
+            assert sorted(srt[b].tolist()) == list(range(n))
+            assert mg.ref_walk([int(v) for v in cost[b]], nfl) == (cand[b].tolist(), srt[b].tolist(), int(ref[b]))
+
+
+def test_without_a_scratch_buffer_the_list_is_reversed():
+    rng = np.random.default_rng(32)
+    for C, nfl in ((13, 13), (13, 40), (1, 3), (5, 5), (40, 40)):
+        cost = rng.integers(0, 1 << 30, (20, C)).astype(np.uint64)
+        cand, srt, ref = mg.np_walk(cost, nfl)
+        assert (cand == np.arange(C - 1, -1, -1)[None, :]).all()
+        assert np.array_equal(ref, np.minimum(cost.min(axis=1), np.uint64(mg.MAX_MODE_COST)))
+
+
+def test_ref_fast_cost_leaves_out_the_candidate_in_the_last_buffer():
+    """3 candidates, nfl 2: 3 buffers, one scratch.  Costs in list order (5, 9, 7): entry 2 (7) goes to buffer 0, entry 1 (9) to buffer 1,
+    entry 0 (5) to buffer 2; the highest is buffer 1, which is emptied.  Buffers 0 .. 1 by index hold 7 and MAX_CU_COST: ref_fast_cost is
+    7, the true minimum 5 sits in buffer 2.  The bubble pass compares buffers 0 and 1 (7 against MAX_CU_COST): no swap."""
+    cand, srt, ref = mg.ref_walk([5, 9, 7], 2)
+    assert cand == [2, 0] and srt == [0, 1] and ref == 7
+    c2, s2, r2 = mg.np_walk(np.array([[5, 9, 7]], np.uint64), 2)
+    assert c2.tolist() == [cand] and s2.tolist() == [srt] and r2.tolist() == [ref]
+    # and a swap decided by buffers, not entries: costs (1, 9, 3, 8), nfl 3: buffers 8, 3, (9 -> emptied), 1; best = buffers 0, 1, 3;
+    # pass (0, 1): 3 < 8 swaps; pass (0, 2): buffer 2 is MAX_CU_COST, no swap although the entry there (buffer 3, cost 1) is the best
+    cand, srt, ref = mg.ref_walk([1, 9, 3, 8], 3)
+    assert cand == [3, 2, 0] and srt == [1, 0, 2] and ref == 3
+
+
+def test_model_rd_edges():
+    assert mg.ref_model_rd(0, 6, 1336) == (0, 0)
+    # the clamp: a small SSE under a large quantiser
+    qstep = 1336 >> 3
+    x = ((qstep * qstep) << 16) // 1
+    assert x > mg.MAX_XSQ_Q10
+    r, d, xq = mg.ref_model_rd_norm(mg.MAX_XSQ_Q10)
+    assert xq == 102 and (r, d) == (0, 1023)                    # the table's last interval: rate 0, all of the variance is distortion
+    assert mg.ref_model_rd(1, 6, 1336) == (0, ((1 * 1023 + 512) >> 10) << 4)
+    # the other end: xsq 0 .. 3 fall into interval 0, 65536 interpolated towards 6086
+    assert mg.ref_model_rd_norm(0) == (65536, 0, 0)
+    assert mg.ref_model_rd_norm(3) == ((65536 * 256 + 6086 * 768) >> 10, 0, 0)
+    assert mg.ref_model_rd_norm(4)[2] == 1
+    # a large SSE under the smallest quantiser reaches xsq 0
+    rate, dist = mg.ref_model_rd(64 * 255 * 255, 6, 8)
+    assert rate == ((65536 << 6) + 1) >> 1 and dist == 0
+    # vectorised = scalar over a sweep
+    rng = np.random.default_rng(33)
+    sse = np.concatenate([np.arange(0, 64), rng.integers(0, 1 << 24, 4000)]).astype(np.uint64)
+    for n_log2, q in ((4, 4), (6, 156), (12, 1336), (14, 8)):
+        r, d = mg.np_model_rd(sse, n_log2, q)
+        for i in range(0, len(sse), 7):
+            assert (int(r[i]), int(d[i])) == mg.ref_model_rd(int(sse[i]), n_log2, q)
+
+
+def test_rate_table_shapes_against_the_header():
+    hdr = open(os.path.join(ROOT, "include", "svt_hip_dsp.h")).read()
+    for name, shape in mg.RATE_TABLES:
+        assert f"int32_t {name}" + "".join(f"[{d}]" for d in shape) + ";" in hdr, name
+    assert sum(int(np.prod(s)) for _, s in mg.RATE_TABLES) == 877
+
+
+def test_library_exports_and_mirror(pkg):
+    lib = pkg.load_library()
+    hdr = open(os.path.join(ROOT, "include", "svt_hip_dsp.h")).read()
+    for n, nargs, ret, cret in (("svt_hip_fast_pick_frame", 4, ctypes.c_int, "int"), ("svt_hip_intra_fast_search_frame", 7, ctypes.c_int, "int"),
+                                ("svt_hip_intra_fast_search_scratch_bytes", 2, ctypes.c_size_t, "size_t")):
+        assert f"{cret} {n}(" in hdr
+        f = getattr(lib, n)
+        assert f.argtypes is not None and len(f.argtypes) == nargs and f.restype is ret, n
+    assert pkg.SvtHipDsp.FAST_RATE_WORDS == 877 and tuple(pkg.SvtHipDsp.FAST_RATE_TABLES) == tuple(mg.RATE_TABLES)
+    assert np.dtype(pkg.SvtHipDsp.FAST_PICK_BLK_DTYPE) == mg.BLK_DTYPE
+
+
+def test_struct_layout_against_the_header(pkg, tmp_path):
+    """sizeof / offsetof from a program compiled against the header, against the ctypes mirror"""
+    cc = shutil.which("g++") or shutil.which("c++")
+    if cc is None:
+        pytest.skip("no host C++ compiler")
+    S = pkg.SvtHipDsp
+    fields = [("svt_hip_fast_pick_group", S.FastPickGroup, ("nblocks", "uv_modes", "nfl", "ac_dequant_q3", "intrabc_bits", "d_dist", "d_src_xy_out")),
+              ("svt_hip_intra_fast_search_group", S.IntraFastSearchGroup, ("use_chroma", "cb", "cr", "pick"))]
+    rename = {"lambda_": "lambda"}
+    body = "".join(f'printf("%zu ", sizeof({c}));' + "".join(f'printf("%zu ", offsetof({c}, {rename.get(f, f)}));' for f in fs) for c, _, fs in fields)
+    src = tmp_path / "t.cpp"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "svt_hip_dsp.h"\nint main() {' + body + "return 0; }\n")
+    subprocess.check_call([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "t")])
+    got = [int(v) for v in subprocess.check_output([str(tmp_path / "t")]).decode().split()]
+    want = []
+    for _, ct, fs in fields:
+        want += [ctypes.sizeof(ct)] + [getattr(ct, f).offset for f in fs]
+    assert got == want
+
+
+def search_groups(pkg, specs):
+    """an IntraFastSearchGroup array from (tx_size, ncand, nblocks, use_chroma, supplied) with supplied a set of "dist", "pred", "cb", "cr",
+    "pred_out": a supplied pointer is any non-NULL value, the scratch computation reads no memory"""
+    arr = (pkg.SvtHipDsp.IntraFastSearchGroup * max(len(specs), 1))()
+    for i, (s, ncand, n, chroma, have) in enumerate(specs):
+        g = arr[i]
+        for fl in (g.luma, g.cb, g.cr):
+            fl.tx_size, fl.ncand, fl.nblocks = s, ncand, n
+        g.use_chroma = chroma
+        g.luma.d_dist = 0x1000 if "dist" in have else None
+        g.luma.d_pred = 0x1000 if "pred" in have else None
+        g.cb.d_dist = 0x1000 if "cb" in have else None
+        g.cr.d_dist = 0x1000 if "cr" in have else None
+        g.pick.d_pred_out = 0x1000 if "pred_out" in have else None
+    return arr
+
+
+def test_scratch_bytes_on_hand_computed_cases(pkg):
+    lib = pkg.load_library()
+    sb = lambda specs, n=None: lib.svt_hip_intra_fast_search_scratch_bytes(search_groups(pkg, specs), len(specs) if n is None else n)
+    # 4x4, 13 candidates, 5 blocks = 65 pairs, nothing supplied, no gather: only luma dist, 520 -> 528
+    assert sb([(0, 13, 5, 0, set())]) == 528
+    # with the gather asked for: the predictions as well, 65 * 16 = 1040
+    assert sb([(0, 13, 5, 0, {"pred_out"})]) == 528 + 1040
+    # chroma planes: two more dist arrays; cb supplied: one more
+    assert sb([(0, 13, 5, 1, {"pred_out"})]) == 3 * 528 + 1040
+    assert sb([(0, 13, 5, 1, {"pred_out", "cb"})]) == 2 * 528 + 1040
+    # everything supplied
+    assert sb([(0, 13, 5, 1, {"dist", "pred", "cb", "cr", "pred_out"})]) == 0
+    # a supplied d_pred without a gather, and no d_pred without a gather: nothing for the predictions
+    assert sb([(0, 13, 5, 0, {"dist", "pred"})]) == 0 and sb([(0, 13, 5, 0, {"dist"})]) == 0
+    # 8x8, 61 candidates, 3 blocks: 183 pairs: 1464 -> 1472, pred 183 * 64 = 11712; two groups add up, an empty one adds nothing
+    assert sb([(1, 61, 3, 0, {"pred_out"})]) == 1472 + 11712
+    assert sb([(0, 13, 5, 0, {"pred_out"}), (1, 61, 0, 1, set()), (1, 61, 3, 0, {"pred_out"})]) == 528 + 1040 + 1472 + 11712
+    assert sb([]) == 0
+    # the Python computation over a sweep
+    rng = np.random.default_rng(34)
+    for _ in range(40):
+        s, ncand, n, chroma = int(rng.integers(0, 19)), int(rng.integers(1, 65)), int(rng.integers(0, 50)), int(rng.integers(0, 2))
+        have = {k for k in ("dist", "pred", "cb", "cr", "pred_out") if rng.integers(0, 2)}
+        a16 = lambda v: (v + 15) // 16 * 16
+        want = 0
+        if n:
+            want += 0 if "dist" in have else a16(n * ncand * 8)
+            want += sum(a16(n * ncand * 8) for k in ("cb", "cr") if chroma and k not in have)
+            want += a16(n * ncand * mg.TX_W[s] * mg.TX_H[s]) if "pred_out" in have and "pred" not in have else 0
+        assert sb([(s, ncand, n, chroma, have)]) == want, (s, ncand, n, chroma, have)
+    # bad parameters: 0
+    assert sb([(19, 13, 5, 0, set())]) == 0 and sb([(-1, 13, 5, 0, set())]) == 0
+    assert sb([(0, 0, 5, 0, set())]) == 0 and sb([(0, 65, 5, 0, set())]) == 0
+    assert sb([(0, 64, 0x4000000, 0, set())]) == 0                           # nblocks * ncand = 2^32 / 2
+    assert sb([(0, 13, 5, 0, set()), (19, 13, 0, 0, set())]) == 0            # an empty group's size counts
+    bad = search_groups(pkg, [(0, 13, 5, 1, set())])
+    bad[0].cb.nblocks = 4                                                    # the chroma groups follow luma
+    assert lib.svt_hip_intra_fast_search_scratch_bytes(bad, 1) == 0
+    assert lib.svt_hip_intra_fast_search_scratch_bytes(None, 1) == 0 and lib.svt_hip_intra_fast_search_scratch_bytes(None, -1) == 0
+
+
+def test_frame_calls_without_a_device_or_with_bad_arguments(pkg):
+    import torch
+    lib = pkg.load_library()
+    have = torch.cuda.is_available()
+    bad = INVALID if have else NO_DEVICE
+    assert lib.svt_hip_fast_pick_frame(None, 1, 0, None) == bad
+    assert lib.svt_hip_fast_pick_frame(None, 0, 0, None) == (0 if have else NO_DEVICE)
+    assert lib.svt_hip_intra_fast_search_frame(None, 1, 0, 1, None, 0, None) == bad
+    g = search_groups(pkg, [(0, 13, 5, 0, set())])
+    assert lib.svt_hip_intra_fast_search_frame(g, 1, 0, 1, None, 0, None) == bad          # a group that needs a scratch, none given
+
+
+@pytest.mark.skipif(not (os.path.exists(os.path.join(LLVM, "llvm-objdump")) and os.path.exists(LIB)), reason="needs the built library and ROCm's llvm tools")
+def test_the_kernel_has_no_scratch_and_fits_eight_waves(tmp_path):
+    shutil.copy(LIB, tmp_path / "lib.so")
+    subprocess.run([os.path.join(LLVM, "llvm-objdump"), "--offloading", "lib.so"], cwd=tmp_path, check=True, capture_output=True)
+    found = []
+    for f in sorted(os.listdir(tmp_path)):
+        if "gfx950" not in f:
+            continue
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", f], cwd=tmp_path, check=True, capture_output=True, text=True).stdout
+        for blk in notes.split("- .agpr_count:")[1:]:
+            g = lambda k: re.search(r"\." + k + r":\s+(\S+)", blk)
+            if "fast_pick_kernel" in g("name").group(1):
+                found.append((int(g("private_segment_fixed_size").group(1)), int(g("vgpr_count").group(1)) + int(re.match(r"\s*(\d+)", blk).group(1)),
+                              int(g("group_segment_fixed_size").group(1))))
+    assert len(found) == 1, found
+    scratch, regs, lds = found[0]
+    assert scratch == 0 and regs <= 64 and lds <= 8192, found            # 8 waves / SIMD of the 512-entry file; 8 KiB of the CU's 160
