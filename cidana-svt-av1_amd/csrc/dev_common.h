@@ -3,29 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-namespace svtdev {
+#include "quant_params.h"
 
-// Quantizer scalars for one launch: index 0 = DC (coefficient 0), 1 = AC.
-// Derived on the host from the reference's five int16[8] tables
-// (EbFullLoop.c:239-296): zbin/round already ROUND_POWER_OF_TWO'ed by
-// log_scale; quant_m = quant + 65536 (so ((t*quant)>>16)+t == (t*quant_m)>>16).
-struct QParams {
-    int32_t zbin[2];
-    int32_t round[2];
-    uint32_t quant_m[2];
-    int32_t quant_shift[2];
-    int32_t dequant[2];
-    int32_t log_scale;
-    // POW2 fast path (host-checked): quant_shift = 2^k, so the two-step reference
-    // formula collapses to  aq = (t1 * quant_m) >> fast_sh  with fast_sh = 32 - log_scale - k
-    int32_t fast_sh[2];
-    int32_t fast_ok;
-    // the same collapse as ONE multiply: with quant_hi = quant_m << (31 - fast_sh) (fits 32 bits: quant_m < 2^17, fast_sh >= 16),
-    // aq = mulhi_u32(2 * t1, quant_hi) = floor(t1 * quant_m / 2^fast_sh) exactly; zbin2 / round2 are the doubled thresholds
-    uint32_t quant_hi[2];
-    int32_t zbin2[2];
-    int32_t round2[2];
-};
+namespace svtdev {
 
 // (the CfL kernels, kernel_cfl.h and kernel_cfl_search.h) one (possibly unaligned) 16- / 8-byte global access: a plain memcpy from a 1- or 2-byte-aligned pointer is split
 // into dwordx2 / dword pieces by the compiler

@@ -14,6 +14,7 @@
 #include "../../include/svt_hip_dsp.h"
 #include "group_table.h"
 #include "host_err.h"
+#include "md_plan.h"
 
 namespace svthost {
 static_assert(kGroupTooLarge == SVT_HIP_ERR_INVALID, "group_table.h");
@@ -59,7 +60,7 @@ extern int g_tune_inv32_var;
 int require_init();
 int launch_status(const char* what);
 }  // namespace svthost
-namespace svtdev { struct FrameDesc; struct QParams; struct MePuMap; }
+namespace svtdev { struct FrameDesc; struct MePuMap; }
 namespace svthost {
 // svt_hip_pixel.hip: the LDS row pitch of the motion search's reference window, and the raster PU order of the me_results rows
 // (shared with svt_hip_me_frame.hip)
@@ -68,46 +69,18 @@ const svtdev::MePuMap& me_pu_map();
 // svt_hip_frame.hip: the one-launch form of svt_hip_encode_recon_frame (its kernel lives in a translation unit of its own)
 int launch_enc_frame_one(const svtdev::FrameDesc* fd, uint32_t total_wgs, int is_16bit, hipStream_t s);
 
-extern const int kTxW[SVT_TX_SIZES_ALL];
-extern const int kTxH[SVT_TX_SIZES_ALL];
 // blocks per workgroup of a staged body (enc_staged_body, full_loop_body): StagedGeom<W, H>::WAVES waves of TxGeom<W, H>::BPW blocks
 inline uint32_t staged_blocks_per_wg(int tx_size) {
     const int w = kTxW[tx_size], h = kTxH[tx_size], m = w > h ? w : h;
     return (uint32_t)((w * h >= 4096 ? 2 : 4) * (64 / m));
 }
-// the quantiser's log_scale of a transform size (av1_get_tx_scale): 1 above 256 pixels, 2 above 1024
-inline int tx_log_scale(int tx_size) {
-    const int pels = kTxW[tx_size] * kTxH[tx_size];
-    return pels > 1024 ? 2 : (pels > 256 ? 1 : 0);
-}
-bool txfm_allowed(int tx_size, int tx_type);
-// size, count and type list of a (transform size, type list) group, as the full-loop, rate and decide calls all require them (empty
-// groups included): a size of the 19, 1 .. 16 types, each defined for the size, none listed twice
-inline int group_types_check(int g, int tx_size, int ntypes, const uint8_t* types) {
-    if (tx_size < 0 || tx_size >= SVT_TX_SIZES_ALL) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_size %d", g, tx_size);
-    if (ntypes < 1 || ntypes > 16) return set_err(SVT_HIP_ERR_INVALID, "group %d: ntypes %d (1 .. 16)", g, ntypes);
-    unsigned seen = 0;
-    for (int t = 0; t < ntypes; t++) {
-        const int ty = types[t];
-        if (!txfm_allowed(tx_size, ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d not defined for tx_size %d", g, ty, tx_size);
-        if (seen & (1u << ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d listed twice", g, ty);
-        seen |= 1u << ty;
-    }
-    return SVT_HIP_OK;
-}
 int frame_groups_check(const svt_hip_frame_group* groups, int ngroups);      // svt_hip_txfm.hip
-svtdev::QParams quant_params(const int16_t* zbin, const int16_t* round, const int16_t* quant, const int16_t* quant_shift,
-                             const int16_t* dequant, int log_scale);                  // svt_hip_txfm.hip (make_qparams)
-// the argument checks of svt_hip_full_loop_frame and svt_hip_coeff_rate_frame (svt_hip_full_loop.hip, svt_hip_coeff_rate.hip):
-// svt_hip_tx_search_frame runs them on all its stages before the first launch
-int full_loop_check(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const int16_t* zbin, const int16_t* round,
-                    const int16_t* quant, const int16_t* quant_shift, const int16_t* dequant);
-int coeff_rate_check(const svt_hip_coeff_rate_group* groups, int ngroups);
-// the argument check of svt_hip_intra_fast_loop_frame (svt_hip_fast_loop.hip): svt_hip_intra_fast_search_frame runs it before its first launch
-int fast_loop_check(const svt_hip_fast_loop_group* groups, int ngroups, int metric, int flavour);
-// the launches of svt_hip_coeff_rate_frame for groups that coeff_rate_check accepted (svt_hip_cfl_search_frame's rate stage: nothing is
-// validated again after its first launch)
-int coeff_rate_enqueue(const svt_hip_coeff_rate_group* groups, int ngroups, hipStream_t s);
+// The launches of the mode-decision stages for groups their *_check (md_plan.h) accepted: the group-table fill and the launches, nothing
+// validated.  Every public entry point is require_init, check, enqueue; the composed calls (svt_hip_tx_search_frame,
+// svt_hip_intra_fast_search_frame, svt_hip_cfl_search_frame, svt_hip_cfl_pick_frame) check every stage, then enqueue every stage.
+int full_loop_enqueue(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const svt_hip_qrows& q, hipStream_t s);      // svt_hip_full_loop.hip
+int coeff_rate_enqueue(const svt_hip_coeff_rate_group* groups, int ngroups, hipStream_t s);                                       // svt_hip_coeff_rate.hip
+int fast_loop_enqueue(const svt_hip_fast_loop_group* groups, int ngroups, int metric, int flavour, hipStream_t s);                // svt_hip_fast_loop.hip
 
 #define TX_SWITCH(tx_size, CALL)                                                                  \
     switch (tx_size) {                                                                            \

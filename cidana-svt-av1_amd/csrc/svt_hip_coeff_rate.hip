@@ -1,17 +1,16 @@
 // svt_hip_coeff_rate.hip — svt_hip_coeff_rate_frame: the coefficient rate of quantised blocks (coeff_rate_kernel, kernel_coeff_rate.h),
-// one launch per CR_MAX_GROUPS groups; svt_hip_coeff_cost_index, the host helper that names a size's cost tables.
+// one launch per CR_MAX_GROUPS groups; svt_hip_coeff_cost_index, the host helper that names a size's cost tables.  What is left here: the
+// launch geometry, the group-table fill and the launch (coeff_rate_enqueue); the argument check is md_plan.h's.
 #include "host_common.h"
 #include "kernel_coeff_rate.h"
 
 using namespace svtdev;
 using namespace svthost;
 
-static int log2_of(int v) { int l = 0; while ((1 << l) < v) l++; return l; }
-static int packed_side(int v) { return v < 32 ? v : 32; }
 static uint64_t pairs_of(const svt_hip_coeff_rate_group& G) { return (uint64_t)G.nblocks * (uint64_t)G.ntypes; }
 // (block, type) pairs per wave-unit: 64 / min(quads, 64)
 static uint32_t pairs_per_unit(int tx_size) {
-    const int quads = packed_side(kTxW[tx_size]) * packed_side(kTxH[tx_size]) / 4;
+    const int quads = coeffs_of(tx_size) / 4;
     return (uint32_t)(quads < 64 ? 64 / quads : 1);
 }
 // wave-units per wave: 1 until the group has 2048 workgroups of its own (8 per CU), then up to CR_ITERS, which spreads the staging of
@@ -27,23 +26,7 @@ extern "C" int svt_hip_coeff_cost_index(int tx_size, int* txs_ctx, int* eob_mult
     const int lw = log2_of(kTxW[tx_size]), lh = log2_of(kTxH[tx_size]);
     const int lo = (lw < lh ? lw : lh) - 2, hi = (lw > lh ? lw : lh) - 2;
     if (txs_ctx) *txs_ctx = (lo + hi + 1) >> 1;
-    if (eob_multi_size) *eob_multi_size = log2_of(packed_side(kTxW[tx_size]) * packed_side(kTxH[tx_size])) - 4;
-    return SVT_HIP_OK;
-}
-
-int svthost::coeff_rate_check(const svt_hip_coeff_rate_group* groups, int ngroups) {
-    if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
-    for (int g = 0; g < ngroups; g++) {
-        const svt_hip_coeff_rate_group& G = groups[g];
-        if (int rc = group_types_check(g, G.tx_size, G.ntypes, G.tx_types)) return rc;
-        if (G.nblocks == 0) continue;
-        if (pairs_of(G) > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "group %d: nblocks * ntypes too large", g);
-        if (!G.d_qcoeff || !G.d_eob || !G.d_iscan || !G.d_txb_skip_ctx || !G.d_dc_sign_ctx || !G.d_coeff_cost || !G.d_eob_cost || !G.d_bits)
-            return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL member", g);
-        if (((uintptr_t)G.d_qcoeff & 15) || ((uintptr_t)G.d_iscan & 7) || ((uintptr_t)G.d_bits & 7) || ((uintptr_t)G.d_eob & 1) ||
-            ((uintptr_t)G.d_type_bits & 3) || ((uintptr_t)G.d_coeff_cost & 3) || ((uintptr_t)G.d_eob_cost & 3))
-            return set_err(SVT_HIP_ERR_INVALID, "group %d: misaligned buffer (d_qcoeff 16 bytes, d_iscan / d_bits 8, the int32 tables 4, d_eob 2)", g);
-    }
+    if (eob_multi_size) *eob_multi_size = log2_of(coeffs_of(tx_size)) - 4;
     return SVT_HIP_OK;
 }
 

@@ -54,19 +54,6 @@ int launch_status(const char* what) {
     return SVT_HIP_OK;
 }
 
-const int kTxW[SVT_TX_SIZES_ALL] = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64};
-const int kTxH[SVT_TX_SIZES_ALL] = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16};
-
-// is_txfm_allowed (test/TxfmCommon.h:172-181; av1_estimate_transform's switch)
-bool txfm_allowed(int tx_size, int tx_type) {
-    if (tx_size < 0 || tx_size >= SVT_TX_SIZES_ALL || tx_type < 0 || tx_type >= SVT_TX_TYPES) return false;
-    const int m = kTxW[tx_size] > kTxH[tx_size] ? kTxW[tx_size] : kTxH[tx_size];
-    if (m == 64) return tx_type == SVT_DCT_DCT;
-    if (m == 32) return tx_type == SVT_DCT_DCT || tx_type == SVT_IDTX;
-    return true;
-}
-
-
 thread_local ThreadCtx t_ctx;
 
 [[noreturn]] void die(const char* fn) {

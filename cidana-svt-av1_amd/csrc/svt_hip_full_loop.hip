@@ -1,37 +1,11 @@
 // svt_hip_full_loop.hip — svt_hip_full_loop_frame: the fused luma mode-decision full loop (full_loop_kernel, kernel_full_loop.h), one
-// launch per register class and per FL_MAX_GROUPS groups.
+// launch per register class and per FL_MAX_GROUPS groups.  What is left here: the group-table fill and the launches (full_loop_enqueue);
+// the argument check is md_plan.h's.
 #include "host_common.h"
 #include "kernel_full_loop.h"
 
 using namespace svtdev;
 using namespace svthost;
-
-int svthost::full_loop_check(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const int16_t* zbin, const int16_t* round,
-                             const int16_t* quant, const int16_t* quant_shift, const int16_t* dequant) {
-    if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
-    if (flavour != SVT_HIP_FLAVOUR_C && flavour != SVT_HIP_FLAVOUR_AVX2) return set_err(SVT_HIP_ERR_INVALID, "flavour %d", flavour);
-    if (!zbin || !round || !quant || !quant_shift || !dequant) return set_err(SVT_HIP_ERR_INVALID, "NULL quantiser table");
-    for (int i = 0; i < 2; i++) {
-        const int qs = quant_shift[i];
-        if (qs <= 0 || (qs & (qs - 1))) return set_err(SVT_HIP_ERR_INVALID, "quant_shift[%d] = %d is not a power of two", i, qs);
-        if (dequant[i] < 0 || round[i] < 0) return set_err(SVT_HIP_ERR_INVALID, "negative quantiser table entry");
-    }
-    for (int ls = 0; ls < 3; ls++)
-        if (!quant_params(zbin, round, quant, quant_shift, dequant, ls).fast_ok)
-            return set_err(SVT_HIP_ERR_INVALID, "quantiser table outside the one-product quantiser's range (log_scale %d)", ls);
-    for (int g = 0; g < ngroups; g++) {
-        const svt_hip_full_loop_group& G = groups[g];
-        if (int rc = group_types_check(g, G.tx_size, G.ntypes, G.tx_types)) return rc;
-        if (G.nblocks == 0) continue;
-        if (G.nblocks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "group %d: nblocks too large", g);
-        if (!G.d_src || !G.d_pred || !G.d_iscan || !G.d_dist || !G.d_eob) return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL member", g);
-        if (((uintptr_t)G.d_iscan & 7) || ((uintptr_t)G.d_dist & 15) || ((uintptr_t)G.d_qcoeff & 15) || ((uintptr_t)G.d_dqcoeff & 15))
-            return set_err(SVT_HIP_ERR_INVALID, "group %d: misaligned buffer (d_iscan 8 bytes, d_dist / d_qcoeff / d_dqcoeff 16 bytes)", g);
-        if ((G.d_src_xy && G.src_stride < (uint32_t)kTxW[G.tx_size]) || (G.d_pred_xy && G.pred_stride < (uint32_t)kTxW[G.tx_size]))
-            return set_err(SVT_HIP_ERR_INVALID, "group %d: plane stride below the block width", g);
-    }
-    return SVT_HIP_OK;
-}
 
 template <int CLS>
 static int full_loop_launch(const FullLoopDesc& fd, uint32_t wgs, hipStream_t s) {
@@ -39,14 +13,9 @@ static int full_loop_launch(const FullLoopDesc& fd, uint32_t wgs, hipStream_t s)
     return launch_status("full_loop");
 }
 
-extern "C" int svt_hip_full_loop_frame(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const int16_t* zbin,
-                                       const int16_t* round, const int16_t* quant, const int16_t* quant_shift, const int16_t* dequant,
-                                       void* stream) {
-    if (int rc = require_init()) return rc;
-    if (int rc = full_loop_check(groups, ngroups, flavour, zbin, round, quant, quant_shift, dequant)) return rc;
-    hipStream_t s = (hipStream_t)stream;
+int svthost::full_loop_enqueue(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const svt_hip_qrows& q, hipStream_t s) {
     QParams qps[3];
-    for (int ls = 0; ls < 3; ls++) qps[ls] = quant_params(zbin, round, quant, quant_shift, dequant, ls);
+    for (int ls = 0; ls < 3; ls++) qps[ls] = make_qparams(q, ls);
     // the 64x64 class first, the small sizes last: the long workgroups start early
     for (int cls = 2; cls >= 0; cls--) {
         GroupTable<FullLoopDesc, FL_MAX_GROUPS> tab;
@@ -70,4 +39,13 @@ extern "C" int svt_hip_full_loop_frame(const svt_hip_full_loop_group* groups, in
         if (int rc = tab.flush(launch)) return rc;
     }
     return SVT_HIP_OK;
+}
+
+extern "C" int svt_hip_full_loop_frame(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const int16_t* zbin,
+                                       const int16_t* round, const int16_t* quant, const int16_t* quant_shift, const int16_t* dequant,
+                                       void* stream) {
+    const svt_hip_qrows q = {zbin, round, quant, quant_shift, dequant};
+    if (int rc = require_init()) return rc;
+    if (int rc = full_loop_check(groups, ngroups, flavour, q)) return rc;
+    return full_loop_enqueue(groups, ngroups, flavour, q, (hipStream_t)stream);
 }

@@ -13,33 +13,6 @@ using namespace svthost;
 
 namespace {
 
-int rpot(int v, int n) { return n == 0 ? v : ((v + (1 << (n - 1))) >> n); }
-
-QParams make_qparams(const int16_t* zbin, const int16_t* round, const int16_t* quant,
-                     const int16_t* quant_shift, const int16_t* dequant, int log_scale) {
-    QParams qp;
-    for (int i = 0; i < 2; i++) {
-        qp.zbin[i] = rpot(zbin[i], log_scale);       // EbFullLoop.c:248-249
-        qp.round[i] = rpot(round[i], log_scale);     // :277
-        qp.quant_m[i] = (uint32_t)((int)quant[i] + 65536);
-        qp.quant_shift[i] = quant_shift[i];
-        qp.dequant[i] = dequant[i];
-    }
-    qp.log_scale = log_scale;
-    qp.fast_ok = 1;
-    for (int i = 0; i < 2; i++) {
-        const int qs = quant_shift[i];
-        int k = -1;
-        if (qs > 0 && (qs & (qs - 1)) == 0) { k = 0; while ((1 << k) != qs) k++; }
-        const int sh = 32 - log_scale - k;
-        qp.fast_sh[i] = sh;
-        if (k < 0 || sh < 16 || sh > 31 || dequant[i] < 0 || qp.round[i] < 0 || qp.quant_m[i] >= (1u << 17)) qp.fast_ok = 0;
-        qp.quant_hi[i] = (sh >= 16 && sh <= 31) ? qp.quant_m[i] << (31 - sh) : 0u;
-        qp.zbin2[i] = 2 * qp.zbin[i];
-        qp.round2[i] = 2 * qp.round[i];
-    }
-    return qp;
-}
 // a negative quant_shift, dequant or (rounded) round entry: outside the 24-bit arithmetic of the fused kernels (dev_common.h
 // quant_one<1 / 2>).  Each caller decides what that means: an error, or another kernel.
 bool qparams_negative(const QParams& qp) {
@@ -161,12 +134,6 @@ int launch_inv(const int32_t* in, void* dst, int is16, int32_t stride, size_t pi
     return launch_status("inv_txfm2d_add");
 }
 }  // namespace
-
-// the quantiser scalars for the other translation units (svt_hip_full_loop.hip)
-svtdev::QParams svthost::quant_params(const int16_t* zbin, const int16_t* round, const int16_t* quant, const int16_t* quant_shift,
-                                      const int16_t* dequant, int log_scale) {
-    return make_qparams(zbin, round, quant, quant_shift, dequant, log_scale);
-}
 
 // ===========================================================================
 // (B) batched API

@@ -103,3 +103,17 @@ def test_ois_plan(tmp_path, san_flags):
                         capture_output=True, text=True)
     assert pr.returncode == 0, pr.stderr[-4000:]
     assert run(exe, []).strip() == "ok"
+
+
+@pytest.mark.parametrize("san_flags", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]], ids=["plain", "asan_ubsan"])
+def test_md_plan(tmp_path, san_flags):
+    """csrc/md_plan.h (what the mode-decision calls decide on the host before they enqueue) as a stand-alone program: for the four
+    composed calls the scratch size against the header's formula, every piece inside a scratch of exactly that size, aligned, in the
+    documented order and overlapping nothing, supplied arrays passed through, the derived stage groups consistent and accepted by their
+    stages' checks; for the seven stage checks a valid group accepted and every clause refusing its one changed field"""
+    exe = str(tmp_path / "md_plan_host")
+    pr = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror"] + san_flags +
+                        [os.path.join(ROOT, "tests", "c", "md_plan_host.cpp"), os.path.join(PKG, "csrc", "host_tables.cpp"),
+                         os.path.join(PKG, "csrc", "host_err.cpp"), "-o", exe], capture_output=True, text=True)
+    assert pr.returncode == 0, pr.stderr[-4000:]
+    assert run(exe, []).strip() == "ok"
