@@ -1053,7 +1053,10 @@ int svt_hip_intra_fast_loop_frame(const svt_hip_fast_loop_group *groups, int ngr
 /* The end of the fast loop for an all-intra candidate list, on the device: the fast cost of every (block, candidate), the buffer walk
  * that keeps the N best, the two index arrays, and the gather of the survivors' predictions into the layout the full loop reads.
  * svt_hip_intra_fast_loop_frame writes its inputs, svt_hip_full_loop_frame / svt_hip_tx_search_frame read its outputs as they lie.
- * What is reproduced (all of it restated from the reference and NOT pinned to a compiled reference: see DESIGN.md 4.31):
+ * What is reproduced.  Each piece is pinned to the reference's own compiled function (oracle/ref_md.c): cost to
+ * av1_intra_fast_cost and model_rd_from_sse called directly, order to sort_fast_loop_candidates called directly, and cost, walk and order
+ * together to inject_intra_candidates -> perform_fast_loop -> sort_fast_loop_candidates run whole on blocks of a picture
+ * (tests/golden/fast_search_ref.npz).  Inter candidates, the first (src-to-src) loop and the intrabc branch remain the caller's.
  *   cost     av1_intra_fast_cost (EbRateDistortionCost.c:531-729), the non-intrabc branch (:598-728): the mode / skip-mode / is-inter /
  *            angle-delta / uv-mode bits out of d_rates (MdRateEstimationContext_s, EbMdRateEstimation.h:59, 93-103, in the reference's
  *            declaration shapes), intra_mode_context / size_group_lookup / num_pels_log2_lookup (EbDefinitions.h:1213, 1311, 1315),

@@ -11,8 +11,8 @@ Per transform size, per block, per candidate of the list (8-bit):
   ssd_avx2         square sizes only: spatial_full_distortion_kernel{4x4,8x8,16_mx_n}_ssse3_intrin with the call site's argument
                    order (area_width = bheight, area_height = bwidth) - the wrapped-byte SSD the encoder runs
 
-Layout, per size s (key prefix f"s{s}_"): modes uint8 [C], deltas int8 [C] (the 61-entry list of inject_intra_candidates at
-intra_pred_mode 0 wherever the size has angle deltas, else 13 entries); top, left uint8 [NB, 176] (element 15 = the corner, 16 =
+Layout, per size s (key prefix f"s{s}_"): modes uint8 [C], deltas int8 [C] (the list the reference's own inject_intra_candidates gives
+at intra_pred_mode 0, through oracle/ref_md.c: 61 entries wherever the size has angle deltas, else 13); top, left uint8 [NB, 176] (element 15 = the corner, 16 =
 above[0] / left[0]); blk uint8 [NB, 8] (svt_hip_intra_blk: mode / angle_delta 0, filt_type, disable_edge_filter, n_top_px,
 n_topright_px, n_left_px, n_bottomleft_px); src uint8 [NB, H, W]; sad, ssd_c uint64 [NB, C]; ssd_avx2 uint64 [NB, C] (square sizes).
 Blocks cycle through six availability patterns (all, none, top only, left only, partial top-right, partial bottom-left), both
@@ -33,8 +33,40 @@ NB = 12
 SEED = 1152
 
 
+def ref_geometries(R):
+    """the distinct block geometries of the reference's table (build_blk_geom(0): 64x64 superblocks) through oracle/ref_md.c:
+    {(bwidth, bheight, sq_size, bsize, has_uv): first table index}"""
+    out, info, idx = {}, np.zeros(8, np.int32), 0
+    while R.ref_md_geom_info(idx, ptr(info)) == 0:
+        out.setdefault(tuple(int(v) for v in info[:5]), idx)
+        idx += 1
+    return out
+
+
+def ref_inject_list(R, idx, intra_pred_mode, is16, chroma_level=1):
+    """the reference's own inject_intra_candidates on table entry idx -> int32 [n, 7]: mode, angle delta, uv mode, uv delta, the two
+    directional flags, use_angle_delta"""
+    lst = np.zeros((64, 7), np.int32)
+    n = R.ref_md_inject_intra(idx, intra_pred_mode, int(is16), chroma_level, ptr(lst))
+    assert 0 < n <= 64
+    return lst[:n]
+
+
+def ref_cand_list(R, s):
+    """inject_intra_candidates' own luma list at intra_pred_mode 0, 8-bit, of every table geometry of the transform size's shape (they
+    agree: at level 0 nothing depends on sq_size), asserted equal to the restatement cand_list"""
+    w, h = TX_W[s], TX_H[s]
+    lists = [ref_inject_list(R, idx, 0, False) for g, idx in sorted(ref_geometries(R).items()) if g[:2] == (w, h)]
+    assert lists and all(np.array_equal(l[:, :2], lists[0][:, :2]) for l in lists), s
+    modes, deltas = lists[0][:, 0].astype(np.uint8), lists[0][:, 1].astype(np.int8)
+    rm, rd = cand_list(s)
+    assert np.array_equal(modes, rm) and np.array_equal(deltas, rd), s
+    return modes, deltas
+
+
 def cand_list(s):
-    """inject_intra_candidates' luma list at intra_pred_mode 0, 8-bit: 7 deltas unless the block is 4x4, 4x8 or 8x4"""
+    """inject_intra_candidates' luma list at intra_pred_mode 0, 8-bit, restated (what runs where the reference is absent; ref_cand_list
+    asserts it equal to the reference's own): 7 deltas unless the block is 4x4, 4x8 or 8x4"""
     w, h = TX_W[s], TX_H[s]
     nd = 1 if (w, h) in ((4, 4), (4, 8), (8, 4)) else 7
     modes, deltas = [], []
@@ -79,7 +111,7 @@ def main():
     for s in range(19):
         w, h = TX_W[s], TX_H[s]
         rng = np.random.default_rng(SEED + s)
-        modes, deltas = cand_list(s)
+        modes, deltas = ref_cand_list(R, s) if hasattr(R, "ref_md_inject_intra") else cand_list(s)          # a build from before oracle/ref_md.c
         C = len(modes)
         blks, tops, lefts, srcs = [], [], [], []
         sad = np.zeros((NB, C), np.uint64); ssd_c = np.zeros((NB, C), np.uint64); ssd_a = np.zeros((NB, C), np.uint64)

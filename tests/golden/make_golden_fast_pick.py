@@ -1,20 +1,24 @@
 """Writes tests/golden/fast_pick.npz: inputs and expected outputs of svt_hip_fast_pick_frame (fast cost of every intra candidate, the
 buffer walk that keeps the N best, the two index arrays).
 
-What is pinned to what.  UNPINNED: the compiled reference subset (oracle/Makefile) holds EbRateDistortionCost.c but none of
-EbEntropyCoding.c (av1_allow_intrabc), EbInterPrediction.c (model_rd_from_sse), EbModeDecision.c (sort_fast_loop_candidates) or
-EbProductCodingLoop.c (perform_fast_loop), so av1_intra_fast_cost loads and jumps to NULL on its first line: it is never called here.
-Everything below is the reference's code RESTATED in Python integers, next to the line numbers it follows (the precedent:
-make_golden_fast_loop.py's inject_intra_candidates, make_golden_picture_stats.py's two SSE2 leaves):
+What is pinned to what.  Everything below is the reference's code RESTATED in Python integers, next to the line numbers it follows, and
+is what runs where the compiled reference is absent:
 
   ref_model_rd        model_rd_from_sse -> av1_model_rd_from_var_lapndz -> model_rd_norm, EbInterPrediction.c:3311-3438
   ref_intra_fast_cost av1_intra_fast_cost, EbRateDistortionCost.c:598-728 (the non-intrabc branch); RDCOST, EbRateDistortionCost.h:71-75
-  ref_walk            perform_fast_loop, EbProductCodingLoop.c:1225-1363, as md_encode_block calls it (:3103-3131), then
-                      sort_fast_loop_candidates, EbModeDecision.c:436-489
-  ref_fast_pick       the three over the blocks of a case
+  ref_walk_buffers    perform_fast_loop's second loop, EbProductCodingLoop.c:1225-1363, as md_encode_block calls it (:3103-3131)
+  ref_sort            sort_fast_loop_candidates, EbModeDecision.c:436-489
+  ref_fast_pick       the four over the blocks of a case
 
-The one PINNED piece: has_chroma = has_uv && is_chroma_reference(mi_row, mi_col, bsize, 1, 1) (EbRateDistortionCost.c:33-40, pure and
-callable): where oracle/_ref/libsvtref.so exists, main() asserts np_is_chroma_reference against it for every block size and parity.
+Where oracle/_ref/libsvtref.so exists (oracle/ref_md.c holds the harness), main() and tests/test_fast_pick_cpu.py take, for every block
+and candidate of all 28 cases, the cost and the two rates from the reference's own av1_intra_fast_cost (lib_fast_costs), the SSD pieces
+from its model_rd_from_sse (lib_model_rd) and the two index arrays and ref_fast_cost from its sort_fast_loop_candidates on the walk's
+buffers (lib_sort), and assert ref_intra_fast_cost, ref_model_rd, ref_sort, np_fast_pick and every stored output equal to them
+(check_case_against_reference); model_rd_edges() adds the model's edges.  has_chroma = has_uv && is_chroma_reference(mi_row, mi_col,
+bsize, 1, 1) (EbRateDistortionCost.c:33-40) is asserted against the reference's function for every block size and parity.  The buffer
+walk between cost and order is pinned by tests/golden/fast_search_ref.npz (make_golden_fast_search_ref.py): whole blocks through the
+reference's inject_intra_candidates -> perform_fast_loop -> sort_fast_loop_candidates, which ref_fast_pick and np_fast_pick must
+reproduce.  What remains a restatement because it is the caller's: inter candidates, the first (src-to-src) loop, the intrabc branch.
 
 np_fast_pick is the vectorised restatement the tests import: the costs in numpy uint64, and the walk in the form the kernel runs it
 (ranks of the costs, "first buffer of the largest rank" for the re-scan, one rotation per bubble pass); main() asserts that it equals
@@ -153,9 +157,8 @@ def ref_intra_fast_cost(P, R, blk, c, luma, chroma):
     return cost, fast_luma_rate, fast_chroma_rate
 
 
-def ref_walk(costs, nfl):
-    """the second loop of perform_fast_loop and sort_fast_loop_candidates on one block's costs (list index order)
-    -> cand[n], sorted as slots [n], ref_fast_cost"""
+def ref_walk_buffers(costs, nfl):
+    """the second loop of perform_fast_loop on one block's costs (list index order) -> fast_cost[nbuf], cand_of[nbuf], n"""
     ncand = len(costs)
     n = min(ncand, nfl)                                        # EbProductCodingLoop.c:3105
     scratch = ncand > n                                        # :3127
@@ -180,6 +183,12 @@ def ref_walk(costs, nfl):
         idx -= 1
     if scratch:
         fast_cost[hi] = MAX_CU_COST                            # :1361
+    return fast_cost, cand_of, n
+
+
+def ref_sort(fast_cost, n):
+    """sort_fast_loop_candidates on the buffers' costs, all candidates intra -> best[nbuf], sorted[n] (buffer indices), ref_fast_cost"""
+    nbuf = len(fast_cost)
     best = [0] * nbuf                                          # EbModeDecision.c:447-456
     start, end = 0, nbuf - 1
     for b in range(nbuf):
@@ -198,8 +207,21 @@ def ref_walk(costs, nfl):
         for j in range(i + 1, n):
             if fast_cost[j] < fast_cost[i]:
                 srt[i], srt[j] = srt[j], srt[i]
+    return best, srt, ref_fast_cost
+
+
+def slots_of(best, srt, cand_of, n):
+    """the interface's form of the two arrays: cand[k] = the list index in slot k, sorted[k] = the SLOT of buffer srt[k]"""
     slot_of = {b: k for k, b in enumerate(best)}
-    return [cand_of[best[k]] for k in range(n)], [slot_of[b] for b in srt], ref_fast_cost
+    return [cand_of[best[k]] for k in range(n)], [slot_of[b] for b in srt]
+
+
+def ref_walk(costs, nfl):
+    """perform_fast_loop's second loop and sort_fast_loop_candidates on one block's costs -> cand[n], sorted as slots [n], ref_fast_cost"""
+    fast_cost, cand_of, n = ref_walk_buffers(costs, nfl)
+    best, srt, ref_fast_cost = ref_sort(fast_cost, n)
+    cand, slots = slots_of(best, srt, cand_of, n)
+    return cand, slots, ref_fast_cost
 
 
 def rates_dict(packed):
@@ -344,6 +366,133 @@ def np_fast_pick(P, dist, dist_cb, dist_cr, blk, rates):
 def np_gather(cand, pred):
     """pred [B, C, ...] -> [B, n, ...]: the survivors in slot order"""
     return np.take_along_axis(pred, cand.astype(np.int64).reshape(cand.shape + (1,) * (pred.ndim - 2)), axis=1)
+
+
+# ---- the compiled reference (oracle/ref_md.c) ----------------------------------------------------------------------------------------
+def plain_ref_lib():
+    """libsvtref.so as any build of it is (is_chroma_reference), or None where it is not built"""
+    if not os.path.exists(REF):
+        return None
+    L = ctypes.CDLL(REF)
+    L.is_chroma_reference.restype = ctypes.c_int32
+    L.is_chroma_reference.argtypes = [ctypes.c_int32] * 5
+    return L
+
+
+def ref_lib():
+    """libsvtref.so with the ref_md_* entries typed; None where it is not built, or is a build from before oracle/ref_md.c that could
+    not be remade (the reference's sources are not there)"""
+    L = plain_ref_lib()
+    if L is None or not hasattr(L, "ref_md_fast_search"):
+        return None
+    vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32
+    L.ref_md_intra_fast_cost.argtypes = [vp, vp, u64, vp, i32, vp, vp, vp, vp, vp]
+    L.ref_md_model_rd_from_sse.argtypes = [i32, i32, u64, vp, vp]
+    L.ref_md_model_rd_from_sse.restype = None
+    L.ref_md_sort.argtypes = [i32, vp, i32, vp, vp, vp]
+    return L
+
+
+def _p(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def lib_model_rd(L, sse, bsize, quantizer):
+    """(b) model_rd_from_sse(bsize, quantizer, sse) -> (rate, dist)"""
+    r, d = np.zeros(1, np.uint32), np.zeros(1, np.uint64)
+    L.ref_md_model_rd_from_sse(bsize, quantizer, int(sse), _p(r), _p(d))
+    return int(r[0]), int(d[0])
+
+
+def lib_sort(L, fast_cost, n):
+    """(c) sort_fast_loop_candidates on the buffers' costs -> best[nbuf], sorted[n], ref_fast_cost"""
+    costs = np.array(fast_cost, np.uint64)
+    best, srt, ref = np.zeros(MAX_NFL + 2, np.uint8), np.zeros(MAX_NFL, np.uint8), np.zeros(1, np.uint64)
+    assert L.ref_md_sort(len(costs), _p(costs), n, _p(best), _p(srt), _p(ref)) == 0
+    return best[:len(costs)].tolist(), srt[:n].tolist(), int(ref[0])
+
+
+def cand_records(P, C):
+    """[C, 7] candidates as inject_intra_candidates leaves them (EbModeDecision.c:2439-2458): mode, delta, uv mode, uv delta, the two
+    directional flags, use_angle_delta = the block-size flag AND directional luma"""
+    m, uvm = np.asarray(P["modes"][:C], np.int32), np.asarray(P["uv_modes"][:C], np.int32)
+    d, uvd = np.asarray(P["deltas"][:C], np.int32), np.asarray(P["uv_deltas"][:C], np.int32)
+    lum, uv = ((m >= 1) & (m <= 8)).astype(np.int32), ((uvm >= 1) & (uvm <= 8)).astype(np.int32)
+    return np.ascontiguousarray(np.stack([m, d, uvm, uvd, lum, uv, lum * int(bool(P["use_angle_delta"]))], axis=1).astype(np.int32))
+
+
+def lib_fast_costs(L, P, dist, dist_cb, dist_cr, blk, rates, mi):
+    """(a) av1_intra_fast_cost on every block and candidate -> cost uint64 [B, C], rate uint32 [B, C, 2].  has_chroma is reached the
+    reference's way: blk_geom->has_uv = has_chroma, and a mode-info position at which is_chroma_reference holds (the fixture's own,
+    or (1, 1) where the fixture forces has_chroma on a block whose drawn position has none)."""
+    B, C = dist.shape
+    w, h = TX_W[P["tx_size"]], TX_H[P["tx_size"]]
+    cand = cand_records(P, C)
+    pic = np.array([P["slice_is_intra"], int(P["intrabc_bits"] != 0), P["intrabc_bits"] & 0x7FFFFFFF, 60, P["ac_dequant_q3"], int(P["metric"] == SSD)], np.int32)
+    assert P["intrabc_bits"] < (1 << 31)
+    rates = np.ascontiguousarray(rates, np.int32)
+    cost, rate = np.zeros((B, C), np.uint64), np.zeros((B, C, 2), np.uint32)
+    for b in range(B):
+        r, c = int(mi[b][0]), int(mi[b][1])
+        if blk[b]["has_chroma"] and not np_is_chroma_reference(r, c, P["bsize"]):
+            r, c = r | 1, c | 1
+        rec = np.array([blk[b]["top_mode"], blk[b]["left_mode"], blk[b]["skip_mode_ctx"], blk[b]["is_inter_ctx"], r, c, w, h, blk[b]["has_chroma"]], np.int32)
+        luma = np.ascontiguousarray(dist[b], np.uint64)
+        chroma = np.zeros(C, np.uint64)
+        for x in (dist_cb, dist_cr):
+            if x is not None:
+                chroma = chroma + np.asarray(x[b], np.uint64)
+        assert L.ref_md_intra_fast_cost(_p(rec), _p(pic), P["lambda"], _p(rates), C, _p(cand), _p(luma), _p(chroma), _p(cost[b]), _p(rate[b])) == 0
+    return cost, rate
+
+
+def lib_fast_pick(L, P, dist, dist_cb, dist_cr, blk, rates, mi):
+    """every output of the call with the costs and rates from (a) and the order from (c); the buffer walk between them is ref_walk_buffers
+    (perform_fast_loop itself is pinned through tests/golden/fast_search_ref.npz)"""
+    cost, rate = lib_fast_costs(L, P, dist, dist_cb, dist_cr, blk, rates, mi)
+    return lib_pick_of(L, P, cost, rate), rate
+
+
+def lib_pick_of(L, P, cost, rate):
+    B, C = cost.shape
+    n = min(P["nfl"], C)
+    out = dict(cand=np.zeros((B, n), np.uint8), sorted=np.zeros((B, n), np.uint8), cost=np.zeros((B, n), np.uint64),
+               rate=np.zeros((B, n, 2), np.uint32), ref_fast_cost=np.zeros(B, np.uint64), all_cost=cost)
+    for b in range(B):
+        costs = [int(v) for v in cost[b]]
+        fast_cost, cand_of, n_ = ref_walk_buffers(costs, P["nfl"])
+        best, srt, ref = lib_sort(L, fast_cost, n_)
+        assert (best, srt, ref) == ref_sort(fast_cost, n_), b
+        cand, slots = slots_of(best, srt, cand_of, n_)
+        out["cand"][b], out["sorted"][b], out["ref_fast_cost"][b] = cand, slots, ref
+        out["cost"][b] = [costs[c] for c in cand]
+        out["rate"][b] = rate[b][cand]
+    return out
+
+
+def check_case_against_reference(L, z, ci):
+    """the restatements against the compiled reference on fixture case ci: every block's and candidate's cost and rates through (a),
+    the SSD model of every luma and chroma distortion through (b), the order through (c), and with them every stored output"""
+    P, dist, cb, cr, blk, rates, want = case_of(z, ci)
+    mi = z[f"c{ci}_mi"]
+    got, rate_all = lib_fast_pick(L, P, dist, cb, cr, blk, rates, mi)
+    for k in OUTPUTS:
+        assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), (CASE_NAMES[ci], k)
+    R = rates_dict(rates)
+    for b in range(dist.shape[0]):
+        rec = {k: int(blk[b][k]) for k in ("top_mode", "left_mode", "skip_mode_ctx", "is_inter_ctx", "has_chroma")}
+        for c in range(dist.shape[1]):
+            chroma = (int(cb[b, c]) if cb is not None else 0) + (int(cr[b, c]) if cr is not None else 0)
+            res = ref_intra_fast_cost(P, R, rec, c, int(dist[b, c]), chroma)
+            assert res == (int(got["all_cost"][b, c]), int(rate_all[b, c, 0]), int(rate_all[b, c, 1])), (CASE_NAMES[ci], b, c)
+    if P["metric"] == SSD:
+        for vals, bs in ((dist, P["bsize"]), (cb, P["bsize_uv"]), (cr, P["bsize_uv"])):
+            if vals is not None:
+                for sse in np.unique(vals):
+                    assert ref_model_rd(int(sse), NUM_PELS_LOG2[bs], P["ac_dequant_q3"]) == lib_model_rd(L, sse, bs, P["ac_dequant_q3"]), (CASE_NAMES[ci], int(sse))
+    np_out = np_fast_pick(P, dist, cb, cr, blk, rates)
+    for k in OUTPUTS:
+        assert np.array_equal(np_out[k], got[k]), (CASE_NAMES[ci], k)
 
 
 # ---- the cases --------------------------------------------------------------------------------------------------------------------
@@ -492,13 +641,11 @@ def check_conditions(z):
     assert ties > 3 and quirk > 0 and unsorted_ > 3 and no_scratch > 2 and both_chroma > 10, (ties, quirk, unsorted_, no_scratch, both_chroma)
 
 
-def check_is_chroma_reference():
+def check_is_chroma_reference(L=None):
     """np_is_chroma_reference against the reference's own function; False where libsvtref.so is not built"""
-    if not os.path.exists(REF):
+    L = L or plain_ref_lib()
+    if L is None:
         return False
-    L = ctypes.CDLL(REF)
-    L.is_chroma_reference.restype = ctypes.c_int32
-    L.is_chroma_reference.argtypes = [ctypes.c_int32] * 5
     for bsize in range(22):
         for r in range(4):
             for c in range(4):
@@ -508,16 +655,58 @@ def check_is_chroma_reference():
     return True
 
 
+def model_rd_edges():
+    """(sse, n_log2 as a block size, quantizer) at the model's edges: sse 0 and 1, the MAX_XSQ_Q10 clamp from both sides, every xq bucket
+    edge from both sides, quantisers 8 and 1336, n_log2 4 (BLOCK_4X4) and 14 (BLOCK_128X128)"""
+    out = []
+    for bsize in (0, 15):
+        n_log2 = NUM_PELS_LOG2[bsize]
+        for q in (8, 1336):
+            num = ((q >> 3) ** 2) << (n_log2 + 10)
+            sses = {0, 1, 2, 3}
+            for xsq in list(XSQ_IQ_Q10) + [MAX_XSQ_Q10, MAX_XSQ_Q10 + 1]:
+                for t in (xsq - 1, xsq, xsq + 1):
+                    if t > 0:
+                        sse = num // t                           # xsq = (num + sse / 2) / sse is t or next to it
+                        sses.update(v for v in (sse - 1, sse, sse + 1) if v >= 0)
+            out += [(v, bsize, q) for v in sorted(sses)]
+    return out
+
+
+def check_model_rd_edges(L=None):
+    """ref_model_rd and np_model_rd on model_rd_edges(), against each other and, where L is given, against model_rd_from_sse itself
+    -> the xq buckets reached"""
+    seen = set()
+    for sse, bsize, q in model_rd_edges():
+        want = ref_model_rd(sse, NUM_PELS_LOG2[bsize], q)
+        if L is not None:
+            assert lib_model_rd(L, sse, bsize, q) == want, (sse, bsize, q)
+        r, d = np_model_rd(np.array([sse], np.uint64), NUM_PELS_LOG2[bsize], q)
+        assert (int(r[0]), int(d[0])) == want, (sse, bsize, q)
+        if sse:
+            xsq = min(((((q >> 3) ** 2) << (NUM_PELS_LOG2[bsize] + 10)) + (sse >> 1)) // sse, MAX_XSQ_Q10)
+            seen.add(ref_model_rd_norm(xsq)[2])
+    return seen
+
+
 def main():
-    pinned = check_is_chroma_reference()
+    L = ref_lib()
     z = generate(ref_fast_pick)
     v = generate(np_fast_pick)
     assert sorted(z) == sorted(v)
     for k in z:
         assert z[k].dtype == v[k].dtype and np.array_equal(z[k], v[k]), k
     np.savez_compressed(OUT, **z)
-    check_conditions(np.load(OUT))
-    print(f"wrote {OUT}: {NCASES} cases, {os.path.getsize(OUT)} bytes; has_chroma pinned to is_chroma_reference: {pinned}; the rest UNPINNED")
+    z = np.load(OUT)
+    check_conditions(z)
+    pinned = "the reference is absent: restatements only"
+    if L is not None:
+        check_is_chroma_reference(L)
+        for ci in range(NCASES):
+            check_case_against_reference(L, z, ci)
+        buckets = check_model_rd_edges(L)
+        pinned = f"all {NCASES} cases equal av1_intra_fast_cost, model_rd_from_sse ({len(buckets)} xq buckets at the edges) and sort_fast_loop_candidates"
+    print(f"wrote {OUT}: {NCASES} cases, {os.path.getsize(OUT)} bytes; {pinned}")
 
 
 if __name__ == "__main__":

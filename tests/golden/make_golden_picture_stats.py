@@ -11,10 +11,11 @@ line numbers it follows: the trees (:2843-2896, :1992-2007), the variance line (
 (:1706) and the chroma 64x64 line as the reference has it, (m32[0] + m32[1] + m32[3] + m32[3]) >> 2 (:2006-2007), the region
 arithmetic (:4162-4191, :4222-4255) and the averages (:4746-4748, the lines of every scd_mode but SCD_MODE_0).
 
-UNPINNED: two leaves are not in the library (the compiled subset has no ASM_SSE2/EbComputeMean_Intrinsic_SSE2.c) and are restated
-here from that file: the SUB chroma mean compute_sub_mean8x8_sse2_intrin (:52-76: the sum of rows 0, 2, 4, 6, << 3) as sub_mean8x8,
-and the FULL mean of squares compute_mean_of_squared_values8x8_sse2_intrin (:80-118: the sum of squares of all rows, << 10) as
-mean_sq8x8.  sub_mean8x8 is checked against the mean lane of the AVX2 leaf on the same data (check_sub_restatement).
+The two SSE2 leaves of ASM_SSE2/EbComputeMean_Intrinsic_SSE2.c are the reference's own as well, through oracle/ref_md.c's
+ref_md_mean8x8: the SUB chroma mean compute_sub_mean8x8_sse2_intrin (:52-76: the sum of rows 0, 2, 4, 6, << 3) and the FULL mean of
+squares compute_mean_of_squared_values8x8_sse2_intrin (:80-118: the sum of squares of all rows, << 10).  ref_picture_stats calls them
+(ref_sub_mean8x8, ref_mean_sq8x8) and asserts the plain formulas sub_mean8x8 / mean_sq8x8, which np_picture_stats follows, equal to
+them on every block it visits; check_sub_restatement does the same on random and extreme blocks.
 
 np_picture_stats is the numpy restatement tests use where the reference is not built (and compare with it where it is).
 
@@ -101,7 +102,7 @@ def ref_planes(R, y, cb, cr):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the two leaves that are not in the library, restated (UNPINNED, see the docstring)
+# the two SSE2 leaves as plain formulas (what np_picture_stats follows), and the reference's own through oracle/ref_md.c
 # ---------------------------------------------------------------------------------------------------------------------------
 def sub_mean8x8(buf, y, x):
     """compute_sub_mean8x8_sse2_intrin (EbComputeMean_Intrinsic_SSE2.c:52-76)"""
@@ -112,6 +113,28 @@ def mean_sq8x8(buf, y, x):
     """compute_mean_of_squared_values8x8_sse2_intrin (:80-118)"""
     b = buf[y:y + 8, x:x + 8].astype(np.int64)
     return int((b * b).sum()) << 10
+
+
+def has_sse2_leaves(R):
+    """False for a build of libsvtref.so from before the two leaves joined it (one that could not be remade: no reference sources)"""
+    return R is not None and hasattr(R, "ref_md_mean8x8")
+
+
+def ref_sub_mean8x8(R, buf, y, x):
+    """the reference's leaf, asserted equal to the plain formula; the formula alone where the library has no such entry"""
+    if not has_sse2_leaves(R):
+        return sub_mean8x8(buf, y, x)
+    v = int(R.ref_md_mean8x8(_at(buf, y, x), buf.strides[0], 0))
+    assert v == sub_mean8x8(buf, y, x), (y, x)
+    return v
+
+
+def ref_mean_sq8x8(R, buf, y, x):
+    if not has_sse2_leaves(R):
+        return mean_sq8x8(buf, y, x)
+    v = int(R.ref_md_mean8x8(_at(buf, y, x), buf.strides[0], 1))
+    assert v == mean_sq8x8(buf, y, x), (y, x)
+    return v
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -127,6 +150,9 @@ def ref_lib():
     R.compute_interm_var_four8x8_avx2_intrin.argtypes = [ctypes.c_void_p, ctypes.c_uint16, ctypes.c_void_p, ctypes.c_void_p]
     R.CalculateHistogram.restype = None
     R.CalculateHistogram.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_void_p, ctypes.c_void_p]
+    if has_sse2_leaves(R):
+        R.ref_md_mean8x8.restype = ctypes.c_uint64
+        R.ref_md_mean8x8.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
     return R
 
 
@@ -172,7 +198,7 @@ def ref_picture_stats(R, y, cb, cr, prec, rw, rh):
             else:
                 for bx in range(8):
                     mean[by * 8 + bx] = int(R.compute_mean8x8_avx2_intrin(_at(luma, oy + sy + 8 * by, ox + sx + 8 * bx), luma.strides[0], 8, 8))
-                    msq[by * 8 + bx] = mean_sq8x8(luma, oy + sy + 8 * by, ox + sx + 8 * bx)
+                    msq[by * 8 + bx] = ref_mean_sq8x8(R, luma, oy + sy + 8 * by, ox + sx + 8 * bx)
         M, Q = tree(mean, 8), tree(msq, 8)
         for e in range(85):
             out["y_mean"][sb, e] = (M[e] >> 8) & 0xff                                    # MEAN_PRECISION (:2899-2989)
@@ -182,7 +208,7 @@ def ref_picture_stats(R, y, cb, cr, prec, rw, rh):
             cy, cx = (oy + sy) >> 1, (ox + sx) >> 1      # :4658
             for name, pl in (("cb_mean", pcb), ("cr_mean", pcr)):
                 if prec == SUB:
-                    m16 = [sub_mean8x8(pl, cy + 8 * r, cx + 8 * c) for r in range(4) for c in range(4)]
+                    m16 = [ref_sub_mean8x8(R, pl, cy + 8 * r, cx + 8 * c) for r in range(4) for c in range(4)]
                 else:
                     m16 = [int(R.compute_mean8x8_avx2_intrin(_at(pl, cy + 8 * r, cx + 8 * c), pl.strides[0], 8, 8)) for r in range(4) for c in range(4)]
                 m32 = tree(m16, 4)[1:5]
@@ -216,8 +242,8 @@ def ref_picture_stats(R, y, cb, cr, prec, rw, rh):
 
 
 def check_sub_restatement(R, rng, n=2000):
-    """sub_mean8x8 against the mean lane of compute_interm_var_four8x8_avx2_intrin, and the plain formulas of the header against both of
-    its lanes, on random, all-255, 0 / 255 and near-flat blocks"""
+    """sub_mean8x8 and mean_sq8x8 against the reference's two SSE2 leaves (ref_md_mean8x8) and against the lanes of
+    compute_interm_var_four8x8_avx2_intrin, on random, all-255, all-0, 0 / 255 and near-flat blocks"""
     m4, q4 = np.zeros(4, np.uint64), np.zeros(4, np.uint64)
     for i in range(n):
         kind = i % 4
@@ -226,9 +252,24 @@ def check_sub_restatement(R, rng, n=2000):
         R.compute_interm_var_four8x8_avx2_intrin(ptr(a), a.strides[0], ptr(m4), ptr(q4))
         for k in range(4):
             b = a[0:8:2, 8 * k:8 * k + 8].astype(np.int64)
-            assert sub_mean8x8(a, 0, 8 * k) == int(m4[k]) == int(b.sum()) << 3
+            assert ref_sub_mean8x8(R, a, 0, 8 * k) == int(m4[k]) == int(b.sum()) << 3
+            assert ref_mean_sq8x8(R, a, 0, 8 * k) == int((a[:, 8 * k:8 * k + 8].astype(np.int64) ** 2).sum()) << 10
             assert int(q4[k]) == int((b * b).sum()) << 11
             assert int(R.compute_mean8x8_avx2_intrin(_at(a, 0, 8 * k), a.strides[0], 8, 8)) == int(a[:, 8 * k:8 * k + 8].astype(np.int64).sum()) << 2
+
+
+def check_sse2_leaves(R, rng, n=2000):
+    """the plain formulas against the reference's two SSE2 leaves on n random 8x8 blocks (at a random offset of a wider buffer, so the
+    stride counts) plus all-0 and all-255"""
+    assert has_sse2_leaves(R), "libsvtref.so has no ref_md_mean8x8: rebuild it (make -C oracle ref)"
+    blocks = [rng.integers(0, 256, (8, 24)).astype(np.uint8) for _ in range(n)] + [np.zeros((8, 24), np.uint8), np.full((8, 24), 255, np.uint8)]
+    for i, a in enumerate(blocks):
+        x = i % 17
+        ref_sub_mean8x8(R, a, 0, x)
+        ref_mean_sq8x8(R, a, 0, x)
+    assert ref_sub_mean8x8(R, blocks[-1], 0, 0) == (255 * 32) << 3 and ref_mean_sq8x8(R, blocks[-1], 0, 0) == (255 * 255 * 64) << 10
+    assert ref_sub_mean8x8(R, blocks[-2], 0, 0) == 0 and ref_mean_sq8x8(R, blocks[-2], 0, 0) == 0
+    return len(blocks)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -349,8 +390,9 @@ def check_conditions(g):
 
 def main():
     R = ref_lib()
-    assert R is not None, "oracle/_ref/libsvtref.so is not built"
+    assert has_sse2_leaves(R), "oracle/_ref/libsvtref.so is not built, or is a build without oracle/ref_md.c"
     check_sub_restatement(R, np.random.default_rng(0x5054), 20000)
+    check_sse2_leaves(R, np.random.default_rng(0x5055), 20000)
     z = generate(lambda *a: ref_picture_stats(R, *a))
     rest = generate(np_picture_stats)
     for k, v in z.items():

@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+import sys
+
 import svtlibs
 from svtlibs import TX_H, TX_W, ptr
 
@@ -15,6 +17,11 @@ GOLD = os.path.join(ROOT, "tests", "golden", "fast_loop.npz")
 # AV1 block_size (BLOCK_4X4 = 0 .. BLOCK_64X16 = 21) -> (width, height)
 BSIZE_WH = [(4, 4), (4, 8), (8, 4), (8, 8), (8, 16), (16, 8), (16, 16), (16, 32), (32, 16), (32, 32), (32, 64), (64, 32), (64, 64),
             (64, 128), (128, 64), (128, 128), (4, 16), (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
+
+
+HAVE_REF = svtlibs.ref() is not None and hasattr(svtlibs.ref(), "ref_md_inject_intra")
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import make_golden_fast_loop as mgl  # noqa: E402
 
 
 def wrapped_ssd(src, pred):
@@ -106,3 +113,27 @@ def test_md_intra_candidates_c_abi_equals_python(pkg):
     assert lib.svt_hip_md_intra_candidates(16, 16, 16, 6, 4, 0, ptr(m), ptr(d)) < 0
     assert lib.svt_hip_md_intra_candidates(16, 16, 16, 22, 0, 0, ptr(m), ptr(d)) < 0
     assert lib.svt_hip_md_intra_candidates(16, 16, 16, 6, 0, 0, None, None) < 0
+
+
+@pytest.mark.skipif(not HAVE_REF, reason="needs the reference build with oracle/ref_md.c in it (oracle/_ref)")
+def test_md_intra_candidates_equal_the_reference_inject_intra_candidates(pkg):
+    """svt_hip_md_intra_candidates (C ABI) and its Python mirror against the reference's own inject_intra_candidates (oracle/ref_md.c) on
+    every distinct geometry of the reference's block table (width, height, sq_size, bsize, has_uv), intra_pred_mode 0 .. 3, 8- and
+    10-bit; and the list's other fields as the fast cost relies on them"""
+    R = svtlibs.ref()
+    lib = pkg.load_library()
+    geoms = mgl.ref_geometries(R)
+    assert {g[:2] for g in geoms} >= {(TX_W[s], TX_H[s]) for s in range(19)} and len({g[2] for g in geoms}) == 5
+    for (w, h, sq, bs, has_uv), idx in sorted(geoms.items()):
+        for ipm in range(4):
+            for is16 in (0, 1):
+                lst = mgl.ref_inject_list(R, idx, ipm, is16)
+                m = np.zeros(64, np.uint8); d = np.zeros(64, np.int8)
+                n = lib.svt_hip_md_intra_candidates(w, h, sq, bs, ipm, is16, ptr(m), ptr(d))
+                assert n == len(lst) and np.array_equal(m[:n], lst[:, 0]) and np.array_equal(d[:n], lst[:, 1]), (w, h, sq, bs, ipm, is16)
+                pm, pd = pkg.SvtHipDsp.md_intra_candidates(w, h, sq, bs, ipm, bool(is16))
+                assert np.array_equal(pm, lst[:, 0]) and np.array_equal(pd, lst[:, 1]), (w, h, sq, bs, ipm, is16)
+                # what svt_hip_fast_pick_frame's header states about the candidates
+                lum = (lst[:, 0] >= 1) & (lst[:, 0] <= 8)
+                assert np.array_equal(lst[:, 4], lum) and np.array_equal(lst[:, 5], (lst[:, 2] >= 1) & (lst[:, 2] <= 8))
+                assert np.array_equal(lst[:, 6], lum & (bs >= 3)) and not lst[:, 3].any()

@@ -1,6 +1,12 @@
 """CPU: the fixture of svt_hip_fast_pick_frame (tests/golden/fast_pick.npz, written by tests/golden/make_golden_fast_pick.py: the
-reference's loops restated in Python integers, UNPINNED but for has_chroma, see there), its numpy restatement, the properties of the
-buffer walk that do not depend on how it is written, the C ABI of the three entry points and the new kernel's resources."""
+reference's loops restated in Python integers), its numpy restatement, the properties of the buffer walk that do not depend on how it
+is written, the C ABI of the three entry points and the new kernel's resources.
+
+What is pinned to the compiled reference (oracle/ref_md.c in oracle/_ref/libsvtref.so; those tests skip where it is not built): every
+cost and rate of every fixture case to av1_intra_fast_cost, the SSD model to model_rd_from_sse, the two index arrays and ref_fast_cost to
+sort_fast_loop_candidates, has_chroma to is_chroma_reference.  The buffer walk is pinned through tests/golden/fast_search_ref.npz, whole
+blocks through the reference's inject_intra_candidates -> perform_fast_loop -> sort_fast_loop_candidates: the restatements, chained after
+that fixture's own distortions, must reproduce every output (this needs no reference at test time: the fixture travels)."""
 import ctypes
 import os
 import re
@@ -17,8 +23,11 @@ LIB = os.path.join(ROOT, "cidana-svt-av1_amd", "libsvt_hip_dsp.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import make_golden_fast_pick as mg  # noqa: E402
+import make_golden_fast_search_ref as ms  # noqa: E402
 
 INVALID, NO_DEVICE = -2, -1
+HAVE_REF = mg.ref_lib() is not None
+needs_ref = pytest.mark.skipif(not HAVE_REF, reason="needs the reference build with oracle/ref_md.c in it (oracle/_ref)")
 
 
 @pytest.fixture(scope="module")
@@ -39,6 +48,73 @@ def test_the_restatement_equals_the_fixture(gold):
     assert sorted(z) == sorted(gold.files)
     for k, v in z.items():
         assert v.dtype == gold[k].dtype and np.array_equal(v, gold[k]), k
+
+
+@needs_ref
+@pytest.mark.parametrize("ci", range(mg.NCASES), ids=mg.CASE_NAMES)
+def test_the_restatements_equal_the_compiled_reference(gold, ci):
+    """every block and candidate of the case: ref_intra_fast_cost against av1_intra_fast_cost (cost, fast_luma_rate, fast_chroma_rate),
+    ref_model_rd against model_rd_from_sse on every luma and chroma distortion of an SSD case, ref_sort against
+    sort_fast_loop_candidates on the walk's buffers, and with them np_fast_pick and every stored output"""
+    mg.check_case_against_reference(mg.ref_lib(), gold, ci)
+
+
+@needs_ref
+def test_the_picture_that_allows_intrabc_adds_its_bits():
+    """EbRateDistortionCost.c:679-680: with av1_allow_intrabc true and use_intrabc 0, intrabcFacBits[0] goes into the luma rate"""
+    L = mg.ref_lib()
+    z = np.load(GOLD)
+    ci = mg.CASE_NAMES.index("8x8_sad_nfl12")
+    P, dist, cb, cr, blk, rates, _ = mg.case_of(z, ci)
+    assert P["intrabc_bits"] == 977
+    with_bits, r1 = mg.lib_fast_costs(L, P, dist, cb, cr, blk, rates, z[f"c{ci}_mi"])
+    without, r0 = mg.lib_fast_costs(L, dict(P, intrabc_bits=0), dist, cb, cr, blk, rates, z[f"c{ci}_mi"])
+    assert np.array_equal(r1[:, :, 0], r0[:, :, 0] + np.uint32(977)) and np.array_equal(r1[:, :, 1], r0[:, :, 1]) and (with_bits > without).all()
+
+
+@pytest.fixture(scope="module")
+def search_gold():
+    return np.load(ms.OUT)
+
+
+def test_search_fixture_meets_its_coverage_conditions(search_gold):
+    """tests/golden/fast_search_ref.npz, the reference's whole function: tied costs among a block's survivors, a ref_fast_cost that is not
+    the true minimum, both has_chroma values, slice types and metrics, with and without a scratch buffer, nfl 1, 3, 12 and 40, blocks
+    on the picture's top and left edges and at all four mi parities"""
+    assert [str(n) for n in search_gold["names"]] == ms.CASE_NAMES
+    c = ms.check_coverage(search_gold)
+    print(c)
+    assert os.path.getsize(ms.OUT) < os.path.getsize(os.path.join(ROOT, "tests", "golden", "real_picture.npz"))
+    for ci in range(ms.NCASES):
+        P, blk, _, extra, want = ms.case_of(search_gold, ci)
+        assert want["cand"].shape == (ms.NB, P["nfl"]) or want["all_cost"].shape[1] < P["nfl"]
+        assert P["metric"] == mg.SAD or mg.TX_W[P["tx_size"]] == mg.TX_H[P["tx_size"]]          # SSD on square sizes only
+        assert ((blk["has_chroma"] == 1) | (np.minimum(mg.TX_W[P["tx_size"]], mg.TX_H[P["tx_size"]]) == 4)).all()
+    sizes = {(mg.TX_W[ms.case_of(search_gold, ci)[0]["tx_size"]], mg.TX_H[ms.case_of(search_gold, ci)[0]["tx_size"]]) for ci in range(ms.NCASES)}
+    assert sizes == {(4, 4), (8, 8), (4, 16), (16, 4), (32, 32), (64, 64)}
+    assert {len(ms.case_of(search_gold, ci)[0]["modes"]) for ci in range(ms.NCASES)} == {5, 13, 61}
+
+
+@pytest.mark.parametrize("ci", range(ms.NCASES), ids=ms.CASE_NAMES)
+def test_the_restatements_reproduce_the_reference_whole_function(search_gold, ci):
+    """ref_fast_pick (the loops in Python integers) and np_fast_pick (what the GPU tests compare with), chained after the fixture's own
+    luma_fast_distortion, against every output of inject_intra_candidates -> perform_fast_loop -> sort_fast_loop_candidates"""
+    P, blk, rates, _, want = ms.case_of(search_gold, ci)
+    for fn in (mg.ref_fast_pick, mg.np_fast_pick):
+        got = fn(P, want["dist"], None, None, blk, rates)
+        for k in mg.OUTPUTS:
+            assert got[k].dtype == want[k].dtype and np.array_equal(got[k], want[k]), (fn.__name__, k)
+
+
+@needs_ref
+def test_the_reference_regenerates_the_search_fixture(search_gold):
+    L, O = mg.ref_lib(), ms.oracle()
+    pictures = search_gold["pictures"]
+    for ci in range(ms.NCASES):
+        c = ms.make_case(L, O, ci, pictures)
+        for k in ms.OUTPUTS:
+            assert np.array_equal(c["out"][k], search_gold[f"c{ci}_{k}"]), (ms.CASE_NAMES[ci], k)
+        assert np.array_equal(c["iblk"], search_gold[f"c{ci}_iblk"]) and np.array_equal(c["blk"].view(np.uint8).reshape(-1, 8), search_gold[f"c{ci}_blk"])
 
 
 def test_has_chroma_of_the_fixture_is_is_chroma_reference(gold):
@@ -92,6 +168,12 @@ def test_ref_fast_cost_leaves_out_the_candidate_in_the_last_buffer():
 
 
 def test_model_rd_edges():
+    """the model's edges in the restatements, and against model_rd_from_sse itself where the reference is built: sse 0 and 1, the
+    MAX_XSQ_Q10 clamp from both sides, every xq bucket edge, quantisers 8 and 1336, n_log2 4 and 14"""
+    edges = mg.model_rd_edges()
+    assert {(b, q) for _, b, q in edges} == {(0, 8), (0, 1336), (15, 8), (15, 1336)} and mg.NUM_PELS_LOG2[0] == 4 and mg.NUM_PELS_LOG2[15] == 14
+    assert {0, 1} <= {s for s, _, _ in edges}
+    assert mg.check_model_rd_edges(mg.ref_lib()) == set(range(103))          # every interval of the tables, the clamp's (102) included
     assert mg.ref_model_rd(0, 6, 1336) == (0, 0)
     # the clamp: a small SSE under a large quantiser
     qstep = 1336 >> 3

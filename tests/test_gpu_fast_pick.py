@@ -1,7 +1,11 @@
 """GPU: svt_hip_fast_pick_frame (fast cost, the N best, their order and the survivors' predictions per block) against the fixture
-(tests/golden/fast_pick.npz: the reference's loops restated, UNPINNED but for has_chroma) and its numpy restatement, and
-svt_hip_intra_fast_search_frame (fast loop -> pick in one call) against the calls enqueued by hand, as the stage in front of
-svt_hip_tx_search_frame.  Every output is compared for equality in a poisoned, fenced buffer."""
+(tests/golden/fast_pick.npz: the reference's loops restated; on the CPU every cost and rate of it is pinned to the compiled
+av1_intra_fast_cost, the SSD model to model_rd_from_sse, the order to sort_fast_loop_candidates, has_chroma to is_chroma_reference) and
+its numpy restatement, and svt_hip_intra_fast_search_frame (fast loop -> pick in one call) against what the reference's own
+inject_intra_candidates -> perform_fast_loop -> sort_fast_loop_candidates produced on whole blocks (tests/golden/fast_search_ref.npz, no
+restatement in between), against the calls enqueued by hand, and as the stage in front of svt_hip_tx_search_frame.  Still the caller's,
+and restated nowhere here: inter candidates, the first (src-to-src) loop and the intrabc branch.  Every output is compared for equality
+in a poisoned, fenced buffer."""
 import os
 import sys
 
@@ -22,6 +26,7 @@ FAST_LOOP = os.path.join(ROOT, "tests", "golden", "fast_loop.npz")
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import make_golden_coeff_rate as mgc  # noqa: E402
 import make_golden_fast_pick as mg  # noqa: E402
+import make_golden_fast_search_ref as ms  # noqa: E402
 
 INVALID = -2
 PITCH = 1 + 2 * 64 + 15                                                     # fast_loop.npz keeps 15 samples in front of the corner
@@ -375,6 +380,63 @@ def test_search_frame_equals_the_calls_by_hand_and_the_restatement(dsp, metric):
         want["pred_out"] = mg.np_gather(want["cand"], L["pred"].cpu().numpy())
         want["src_xy_out"] = np.repeat(luma["src_xy"].cpu().numpy().view(np.uint32)[:, None], want["cand"].shape[1], axis=1)
         check([dict(pk, tx_size=s)], [want])
+
+
+def reference_search_groups(z, metric):
+    """the cases of fast_search_ref.npz of one metric as search groups (every per-candidate array kept, every output poisoned), and what the
+    reference's whole function produced for them"""
+    groups, wants = [], []
+    for ci in range(ms.NCASES):
+        P, blk, rates, extra, want = ms.case_of(z, ci)
+        if P["metric"] != metric:
+            continue
+        n, C, s = len(blk), len(P["modes"]), P["tx_size"]
+        xy = (extra["xy"][:, 0].astype(np.uint32) | extra["xy"][:, 1].astype(np.uint32) << 16).astype(np.uint32)
+        luma = dict(src=dev(extra["src"]), src_stride=extra["src"].shape[1], src_xy=dev(xy), top=dev(extra["top"]), left=dev(extra["left"]), blocks=dev(extra["iblk"]),
+                    nblocks=n, tx_size=s, modes=[int(v) for v in P["modes"]], deltas=[int(v) for v in P["deltas"]],
+                    dist=poison.tensor((n, C), torch.int64, DEV), pred=poison.tensor((n, C, TX_H[s], TX_W[s]), torch.uint8, DEV))
+        groups.append(dict(luma=luma, cb=None, cr=None, pick=pick_dict(P, blk, rates, n, C)))
+        wants.append(dict(want, src_xy_out=np.repeat(xy[:, None], want["cand"].shape[1], axis=1)))
+    return groups, wants
+
+
+def check_against_the_reference(groups, wants):
+    for g, w in zip(groups, wants):
+        s = g["luma"]["tx_size"]
+        poison.assert_written([g["pick"][k] for k in PICK_OUTS] + [g["luma"]["dist"], g["luma"]["pred"]])
+        assert np.array_equal(g["luma"]["dist"].cpu().numpy().view(np.uint64), w["dist"]), s          # luma_fast_distortion of every candidate
+        check([dict(g["pick"], tx_size=s)], [{k: w[k] for k in PICK_OUTS}])
+        # the gathered predictions are the fast loop's own of the surviving candidates
+        assert np.array_equal(mg.np_gather(w["cand"], g["luma"]["pred"].cpu().numpy()), w["pred_out"]), s
+
+
+@pytest.mark.parametrize("metric", [SAD, SSD])
+def test_search_frame_equals_the_reference_whole_function(dsp, metric):
+    """svt_hip_intra_fast_search_frame on tests/golden/fast_search_ref.npz, every case of the metric as the groups of one call: d_cand,
+    d_sorted (as slots), d_cost, d_rate, d_ref_fast_cost, d_all_cost, the luma distortions and the gathered predictions must equal what
+    the reference's inject_intra_candidates -> perform_fast_loop (ProductMdFastPuPrediction -> av1_predict_intra_block, the AVX2 table
+    entries, av1_intra_fast_cost) -> sort_fast_loop_candidates left in its buffers.  Integers, no tolerance.  Eagerly, then captured into
+    a graph and replayed once over re-poisoned outputs."""
+    groups, wants = reference_search_groups(np.load(ms.OUT), metric)
+    assert len(groups) >= 4
+    assert dsp.intra_fast_search_scratch_bytes(groups) == 0
+    arr = dsp.make_intra_fast_search_groups(groups)
+    assert dsp.intra_fast_search_frame(arr, metric, None, 1) == 0, dsp.lib.svt_hip_last_error()
+    torch.cuda.synchronize()
+    check_against_the_reference(groups, wants)
+    graph = torch.cuda.CUDAGraph()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        with torch.cuda.graph(graph, stream=side):
+            assert dsp.intra_fast_search_frame(arr, metric, None, 1) == 0, dsp.lib.svt_hip_last_error()
+    torch.cuda.current_stream().wait_stream(side)
+    for g in groups:
+        for t in [g["pick"][k] for k in PICK_OUTS] + [g["luma"]["dist"], g["luma"]["pred"]]:
+            t.view(torch.uint8).fill_(poison.fill_value(torch.uint8))
+    graph.replay()
+    torch.cuda.synchronize()
+    check_against_the_reference(groups, wants)
 
 
 def test_search_frame_rejects_a_small_scratch_and_bad_stage_arguments(dsp):

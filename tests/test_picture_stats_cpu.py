@@ -78,6 +78,13 @@ def test_the_reference_regenerates_the_fixture_and_the_sub_restatement_equals_th
         assert oa == ob and np.array_equal(a, b)
 
 
+@pytest.mark.skipif(not (HAVE_REF and mg.has_sse2_leaves(mg.ref_lib())), reason="needs the reference build with oracle/ref_md.c in it (oracle/_ref)")
+def test_the_two_sse2_mean_leaves_equal_the_reference():
+    """sub_mean8x8 / mean_sq8x8, the formulas np_picture_stats follows, against compute_sub_mean8x8_sse2_intrin and
+    compute_mean_of_squared_values8x8_sse2_intrin themselves: 2 000 random 8x8 blocks, all-0 and all-255"""
+    assert mg.check_sse2_leaves(mg.ref_lib(), np.random.default_rng(0x5057), 2000) == 2002
+
+
 def test_header_declares_the_entry_and_the_mirror_sets_argtypes_and_restype(pkg):
     hdr = open(os.path.join(ROOT, "include", "svt_hip_dsp.h")).read()
     assert "int svt_hip_picture_stats_frame(const svt_hip_pic_stats_planes *planes, const svt_hip_pic_stats_params *params," in hdr
