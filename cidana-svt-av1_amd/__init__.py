@@ -195,6 +195,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_cfl_pick_frame.restype = c_int
     L.svt_hip_picture_stats_frame.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]
     L.svt_hip_picture_stats_frame.restype = c_int
+    L.svt_hip_inter_pred_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p]
+    L.svt_hip_inter_pred_frame.restype = c_int
     return L
 
 
@@ -282,6 +284,30 @@ class PicStatsOut(ctypes.Structure):
 
 PicStatsResult = collections.namedtuple("PicStatsResult", ("y_mean", "variance", "cb_mean", "cr_mean", "pic_avg_variance", "histogram",
                                                            "avg_intensity_region", "avg_intensity"))
+
+
+class InterBlk(ctypes.Structure):
+    """svt_hip_inter_blk: one (block, candidate) of svt_hip_inter_pred_frame (16 bytes; inter_blk_dtype() is its numpy twin)"""
+    _fields_ = [("x", ctypes.c_uint16), ("y", ctypes.c_uint16), ("mv", (ctypes.c_int16 * 2) * 2), ("pred_direction", ctypes.c_uint8),
+                ("filter_x", ctypes.c_uint8), ("filter_y", ctypes.c_uint8), ("pad", ctypes.c_uint8)]
+
+
+class InterPredGroup(ctypes.Structure):
+    """svt_hip_inter_pred_group"""
+    _fields_ = [("d_ref", c_void_p * 2), ("ref_stride", c_uint32), ("ss", c_int32), ("bwidth", c_int32), ("bheight", c_int32),
+                ("nblocks", c_uint32), ("d_blk", c_void_p), ("d_pred", c_void_p), ("pred_stride", c_uint32), ("d_src", c_void_p),
+                ("src_stride", c_uint32), ("d_dist", c_void_p)]
+
+
+UNI_PRED_LIST_0, UNI_PRED_LIST_1, BI_PRED = 0, 1, 2
+INTER_PRED_MAX_GROUPS = 48
+
+
+def inter_blk_dtype():
+    """numpy dtype of svt_hip_inter_blk"""
+    import numpy as np
+    return np.dtype([("x", np.uint16), ("y", np.uint16), ("mv", np.int16, (2, 2)), ("pred_direction", np.uint8), ("filter_x", np.uint8),
+                     ("filter_y", np.uint8), ("pad", np.uint8)])
 
 
 class Y4mInfo(ctypes.Structure):
@@ -1626,6 +1652,29 @@ class SvtHipDsp:
         if isinstance(groups, list):
             groups = self.make_fast_pick_groups(groups)
         return self.lib.svt_hip_fast_pick_frame(groups, n, metric, self._stream())
+
+    def make_inter_pred_groups(self, groups):
+        """groups: list of dicts with ref0 (and ref1 for list-1 / bi-predicted blocks): tensors whose first element is sample (0, 0) of
+        the PICTURE in the list's padded plane (a view plane[oy:, ox:]), ref_stride (samples), ss, bwidth, bheight (luma), blk (uint8
+        [n, 16]: inter_blk_dtype records), optional pred (dense [n, h, w], or a plane view with pred_stride), optional src (a view at the
+        picture's sample (0, 0)) with src_stride and dist (int64 [n]).  -> ctypes array (keep the tensors alive!)"""
+        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
+        arr = (InterPredGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            a = arr[i]
+            a.d_ref[0], a.d_ref[1] = P(g, "ref0"), P(g, "ref1")
+            a.ref_stride, a.ss, a.bwidth, a.bheight = g.get("ref_stride", 0), g.get("ss", 0), g.get("bwidth", 0), g.get("bheight", 0)
+            a.nblocks = g["nblocks"] if "nblocks" in g else (g["blk"].shape[0] if g.get("blk") is not None else 0)
+            a.d_blk, a.d_pred, a.pred_stride = P(g, "blk"), P(g, "pred"), g.get("pred_stride", 0)
+            a.d_src, a.src_stride, a.d_dist = P(g, "src"), g.get("src_stride", 0), P(g, "dist")
+        return arr
+
+    def inter_pred_frame(self, groups, pic_width, pic_height, bd=8, metric=0):
+        """svt_hip_inter_pred_frame.  groups: a ctypes array from make_inter_pred_groups or the list of dicts -> the library's return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_inter_pred_groups(groups)
+        return self.lib.svt_hip_inter_pred_frame(groups, n, pic_width, pic_height, bd, metric, self._stream())
 
     def fast_pick(self, dist, blk, rates, tx_size, bsize, bsize_uv, modes, deltas, uv_modes, uv_deltas, nfl, lam, metric, use_angle_delta=True,
                   slice_is_intra=True, ac_dequant_q3=0, intrabc_bits=0, dist_cb=None, dist_cr=None, pred=None, src_xy=None, want_all_cost=False):

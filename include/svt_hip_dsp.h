@@ -1512,6 +1512,72 @@ typedef struct svt_hip_pic_stats_out {
 int svt_hip_picture_stats_frame(const svt_hip_pic_stats_planes *planes, const svt_hip_pic_stats_params *params,
                                 uint32_t n_pictures, const svt_hip_pic_stats_out *out, void *stream);
 
+/* ---- AV1 inter prediction for whole pictures (av1_inter_prediction / av1_inter_prediction_hbd, EbInterPrediction.c:1024, :2093) -----
+ * svt_hip_inter_pred_frame turns motion vectors into predictions: translational prediction of one plane for many (plane, block size)
+ * groups per call, one launch per SVT_HIP_INTER_PRED_MAX_GROUPS non-empty groups.  Samples are uint8 (bd 8) or uint16 (bd 10); strides
+ * are in samples.  The call only enqueues (no allocation, no synchronisation) and can be captured into a HIP graph.
+ *
+ * Per block (svt_hip_inter_blk, device memory, one per (block, candidate)), in the reference's order:
+ *   clamp      clamp_mv_to_umv_border_sb (:80-102) per list: the vector is scaled by 1 << (1 - ss) and cast to int16 first, then
+ *              clamped to [mb_to_left_edge * (1 << (1 - ss)) - ((4 + bw) << 4), mb_to_right_edge * (1 << (1 - ss)) + ((4 + bw) << 4) - 16]
+ *              (rows likewise), bw / bh the PLANE's block size, the edges from the block's luma origin, its size in mode-info units
+ *              and mi_cols = pic_width / 4, mi_rows = pic_height / 4 (EbAdaptiveMotionVectorPrediction.c:1169-1172).
+ *   address    luma: (x, y); chroma: (((x >> 3) << 3) / 2, ((y >> 3) << 3) / 2) (:1310); plus the clamped vector >> 4.
+ *   filters    av1_get_interp_filter_params_with_block_size per direction: a plane dimension <= 4 takes the 4-tap tables (REGULAR
+ *              and SHARP sub_pel_filters_4, SMOOTH sub_pel_filters_4smooth); filter_x and filter_y may differ.
+ *   convolve   the convolve[subpel_x != 0][subpel_y != 0][compound] entry with get_conv_params_no_round (round_0 3; round_1 11, or 7
+ *              for BI_PRED), use_jnt_comp_avg 0: all sixteen _c entries, 8-bit and highbd.
+ *   BI_PRED    list 0 through the jnt entry (do_average 0), list 1 with do_average 1: ((c0 + c1) >> 1) minus the round offset,
+ *              rounded by 4 bits and clipped.  List 0's intermediate lives in registers only.
+ * The prediction is the dst_ptr contents after the call(s) of the plane; the block's x / y also place it in a strided d_pred and
+ * in d_src (x, y for luma, the chroma address above for chroma).
+ *
+ * Fused distortion (d_src and d_dist both set): the prediction against the source block at the block's own origin, SVT_HIP_FAST_SAD
+ * or SVT_HIP_FAST_SSD with their C-flavour definitions above, summed while the prediction is on chip; d_pred may be NULL then.
+ *
+ * BORDER CONTRACT (trusted, as for motion estimation): d_ref[l] points at sample (0, 0) of the PICTURE in list l's plane and the
+ * plane carries, on every side, at least bw + 8 (bh + 8 above and below) plane samples of border for a luma group and bw + 10
+ * (bh + 10) for a chroma group.  Derivation, per direction in plane samples, P the plane's side, p the block's position: the clamp
+ * leaves p + (mv >> 4) in [-(bw + 4), P + 3] whatever x and the vector are (the vector's whole part is at least
+ * -p - (4 + bw) and at most P - bw - p + (4 + bw) - 1); the 8-tap window reaches 3 samples before and
+ * bw - 1 + 4 after that, so samples -(bw + 7) .. P + bw + 6 are read: bw + 7 on either side, for every phase (a full-pel block's
+ * window is staged too when its wave filters).  Chroma floors the origin to the 8-grid (at most 2 plane samples lower than the
+ * position the clamp was derived for): bw + 9.  The contract rounds both up.  x and y are multiples of 4, as every AV1 block origin
+ * is (the edges are taken from x >> 2: an origin off that grid would reach up to 3 samples further on the far side).  x / y beyond pic - bwidth / - bheight are read as
+ * that bound; pred_direction above 2 as 2, a filter above 3 as 3: such a block's prediction is unspecified, its accesses stay inside
+ * the windows above and the block's own output.  d_ref[1] may be NULL only when no block of the group has pred_direction 1 or 2
+ * (device data: not checked, unspecified otherwise).
+ *
+ * Validated before the first launch (SVT_HIP_ERR_INVALID, nothing launched): bd 8 / 10; metric; picture sides non-zero multiples of
+ * 8 up to 16384; per group ss 0 / 1, bwidth and bheight in {4, 8, 16, 32, 64} (chroma: both >= 8) and not above the picture,
+ * d_blk and d_ref[0] set, at least one of d_pred / (d_src, d_dist), d_src and d_dist together, d_dist 8-byte, d_blk 4-byte and a
+ * dense d_pred 16-byte aligned, pred_stride 0 or >= the plane block's width, nblocks within one launch.  Not built: see DESIGN.md
+ * section 7 (OBMC, warped / global motion, masked and distance-weighted compound, scaled references, intrabc, sub-8x8 chroma, bd 12). */
+enum { SVT_HIP_UNI_PRED_LIST_0 = 0, SVT_HIP_UNI_PRED_LIST_1 = 1, SVT_HIP_BI_PRED = 2 };    /* EbDefinitions.h:2061-2063 */
+#define SVT_HIP_INTER_PRED_MAX_GROUPS 48
+typedef struct svt_hip_inter_blk {       /* sizeof 16 */
+    uint16_t x, y;                       /* luma origin of the block in the picture: pu_origin_x / _y */
+    int16_t mv[2][2];                    /* [list][0 = x, 1 = y], 1/8 luma sample, as MvUnit_t */
+    uint8_t pred_direction;              /* SVT_HIP_UNI_PRED_LIST_0 / _1 / SVT_HIP_BI_PRED */
+    uint8_t filter_x, filter_y;          /* InterpFilter 0 .. 3: av1_extract_interp_filter(interp_filters, 1) / (.., 0) */
+    uint8_t pad;
+} svt_hip_inter_blk;
+typedef struct svt_hip_inter_pred_group {
+    const void *d_ref[2];                /* sample (0, 0) of the picture in each list's plane; the border lies at negative offsets */
+    uint32_t ref_stride;
+    int32_t ss;                          /* 0: a luma plane; 1: a chroma plane of 4:2:0 */
+    int32_t bwidth, bheight;             /* LUMA block size; the plane's block is (bwidth >> ss) x (bheight >> ss) */
+    uint32_t nblocks;
+    const svt_hip_inter_blk *d_blk;      /* [nblocks] */
+    void *d_pred;                        /* optional when the distortion is asked for */
+    uint32_t pred_stride;                /* 0: dense [nblocks][h][w] (what svt_hip_full_loop_group.d_pred reads); else a plane, block at its origin */
+    const void *d_src;                   /* optional source plane, sample (0, 0) of the picture, for the fused distortion */
+    uint32_t src_stride;
+    uint64_t *d_dist;                    /* optional [nblocks] */
+} svt_hip_inter_pred_group;
+int svt_hip_inter_pred_frame(const svt_hip_inter_pred_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd,
+                             int metric, void *stream);
+
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
  * aom_dsp_rtcd.h it implements (svt_hip_rtcd_slot_count() entries: the 19 av1_fwd_txfm2d_WxH, the 19

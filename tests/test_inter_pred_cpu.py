@@ -1,0 +1,141 @@
+"""CPU: the golden fixture of AV1 inter prediction (tests/golden/inter_pred.npz, written by tests/golden/make_golden_inter_pred.py: the
+leaves are the reference's sixteen compiled convolve entries and av1_get_interp_filter_params_with_block_size, the glue is the
+generator's, see there), the numpy restatement against it and against the compiled path, the device tap tables against the recorded
+reference data, and the C ABI of svt_hip_inter_pred_frame as the header declares it and the Python mirror binds it."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = os.path.join(ROOT, "tests", "golden", "inter_pred.npz")
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import make_golden_inter_pred as mg  # noqa: E402
+
+HAVE_REF = os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libsvtref.so"))
+INVALID, NO_DEVICE = -2, -1
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return np.load(GOLD)
+
+
+def test_fixture_loads_and_meets_the_conditions(gold):
+    """clips at 0 and at the maximum, all sixteen entries, all six tap tables, every plane block shape; the planes are the generator's"""
+    st = mg.check_conditions(gold, gold["taps"])
+    assert st["clip0"] > 0 and st["clipmax"] > 0
+    crc = [mg.planes_crc(mg.planes_of(bd, c)) for bd in (8, 10) for c in mg.CONTENTS]
+    assert np.array_equal(gold["planes_crc"], np.array(crc, np.uint32))
+    assert os.path.getsize(GOLD) < 1 << 20
+    dirs = set()
+    for gi in range(len(gold["groups"])):
+        dirs |= set(int(v) for v in mg.blocks_of(gold, gi)["pred_direction"])
+    assert dirs == {mg.LIST0, mg.LIST1, mg.BI}
+    assert any(int(r[5]) for r in gold["groups"])                                      # BI_PRED with both lists on one plane
+
+
+def test_the_restatement_equals_the_fixture(gold):
+    z = mg.generate(mg.np_predictor(gold["taps"]))
+    assert sorted(list(z) + ["taps"]) == sorted(gold.files)
+    for k, v in z.items():
+        assert v.dtype == gold[k].dtype and np.array_equal(v, gold[k]), k
+
+
+def test_the_single_body_of_the_kernel_equals_the_fixture(gold):
+    """hr = (sum fx p + 4) >> 3, V = sum fy hr, (V + 1024) >> 11 or (((c0 + c1) >> 1) + 8) >> 4 with c = (V + 64) >> 7: what
+    csrc/kernel_inter_pred.h runs for all sixteen entries"""
+    z = mg.generate(mg.np_predictor(gold["taps"], unified=True))
+    for k, v in z.items():
+        assert np.array_equal(v, gold[k]), k
+
+
+def test_hand_computed_clamp_and_addressing():
+    # luma 8x8 at x = 16 in a 104-wide picture: mb_to_left = -128, mb_to_right = (26 - 2 - 4) * 32 = 640 (1/8 sample);
+    # the window is (4 + 8) << 4 = 192: [-256 - 192, 1280 + 176] in 1/16 sample
+    assert mg.clamp_mv(5, 16, 8, 8, 104, 0) == 10
+    assert mg.clamp_mv(-1000, 16, 8, 8, 104, 0) == -448 and mg.clamp_mv(1000, 16, 8, 8, 104, 0) == 1456
+    assert mg.clamp_mv(20001, 16, 8, 8, 104, 0) == -448                                # 40002 wraps to -25534 before the clamp
+    # its chroma (4 wide): the vector is not doubled, the edges are not doubled, the window is (4 + 4) << 4 = 128
+    assert mg.clamp_mv(5, 16, 8, 4, 104, 1) == 5
+    assert mg.clamp_mv(-1000, 16, 8, 4, 104, 1) == -128 - 128 and mg.clamp_mv(1000, 16, 8, 4, 104, 1) == 640 + 112
+    b = np.zeros((), mg.BLK_DTYPE)
+    b["x"], b["y"] = 12, 20
+    assert mg.block_glue(b, 0, 8, 8)[:2] == (12, 20) and mg.block_glue(b, 1, 8, 8)[:2] == (4, 8)
+    assert [mg.table_index(f, 4) for f in range(4)] == [4, 5, 4, 3] and [mg.table_index(f, 8) for f in range(4)] == [0, 1, 2, 3]
+
+
+@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref/libsvtref.so is built from the reference tree, which is not on this machine")
+def test_the_reference_regenerates_the_fixture_and_equals_the_restatements_on_random_cases(gold):
+    R = mg.ref_lib()
+    assert R is not None
+    taps = mg.record_taps(R)
+    assert np.array_equal(taps, gold["taps"])
+    stats = mg.new_stats()
+    z = mg.generate(mg.ref_predictor(R, stats))
+    assert sorted(stats["entries"]) == mg.ALL_ENTRIES and stats["tables"] == set(range(6))
+    for k, v in z.items():
+        assert v.dtype == gold[k].dtype and np.array_equal(v, gold[k]), k
+    mg.check_unified(R, taps, n=400)
+
+
+def test_the_device_tap_tables_equal_the_recorded_reference_data(gold):
+    text = open(os.path.join(ROOT, "cidana-svt-av1_amd", "csrc", "kernel_inter_pred.h")).read()
+    body = text[text.index("// INTER-TAPS-BEGIN"):text.index("// INTER-TAPS-END")]
+    body = body[body.index("= {"):]
+    vals = np.array([int(v) for v in re.findall(r"-?\d+", body)], np.int16)
+    assert vals.size == 6 * 16 * 8
+    assert np.array_equal(vals.reshape(6, 16, 8), gold["taps"])
+    assert (gold["taps"].sum(axis=2) == 128).all()                                     # what lets the offsets cancel
+    t = gold["taps"][:, 1:]                                                            # taps of a filter that runs: a signed byte holds them
+    assert t.min() >= -24 and t.max() <= 126
+
+
+def test_header_declares_the_entry_and_the_mirror_binds_it(pkg):
+    hdr = open(os.path.join(ROOT, "include", "svt_hip_dsp.h")).read()
+    assert "int svt_hip_inter_pred_frame(const svt_hip_inter_pred_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd," in hdr
+    for cite in ("EbInterPrediction.c:1024", ":2093", ":80-102", "EbAdaptiveMotionVectorPrediction.c:1169-1172", ":1310", "BORDER CONTRACT"):
+        assert cite in hdr, cite
+    lib = pkg.load_library()
+    f = lib.svt_hip_inter_pred_frame
+    assert f.argtypes is not None and len(f.argtypes) == 7 and f.restype is ctypes.c_int
+    assert (pkg.UNI_PRED_LIST_0, pkg.UNI_PRED_LIST_1, pkg.BI_PRED) == (mg.LIST0, mg.LIST1, mg.BI) == (0, 1, 2)
+    assert pkg.inter_blk_dtype() == mg.BLK_DTYPE and ctypes.sizeof(pkg.InterBlk) == 16
+    assert f"#define SVT_HIP_INTER_PRED_MAX_GROUPS {pkg.INTER_PRED_MAX_GROUPS}" in hdr
+
+
+def test_struct_layouts_match_the_header(pkg):
+    structs = (("svt_hip_inter_blk", pkg.InterBlk), ("svt_hip_inter_pred_group", pkg.InterPredGroup))
+    args, want = [], []
+    for cname, S in structs:
+        fields = [n for n, _ in S._fields_]
+        args += [f"sizeof({cname})"] + [f"offsetof({cname}, {n})" for n in fields]
+        want += [ctypes.sizeof(S)] + [getattr(S, n).offset for n in fields]
+    code = ('#include <stddef.h>\n#include <stdio.h>\n#include "svt_hip_dsp.h"\nint main(void){printf("%zu"' + ' " %zu"' * (len(args) - 1) + ", " +
+            ", ".join(args) + ");return 0;}\n")
+    with tempfile.TemporaryDirectory() as d:
+        open(os.path.join(d, "t.c"), "w").write(code)
+        subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), os.path.join(d, "t.c"), "-o", os.path.join(d, "t")])
+        out = [int(v) for v in subprocess.check_output([os.path.join(d, "t")]).decode().split()]
+    assert out == want
+
+
+def test_the_call_without_a_device_or_with_a_null_list(pkg):
+    """SVT_HIP_ERR_INVALID (-2) on a machine with a device, SVT_HIP_ERR_NO_DEVICE (-1) without one, as the sibling calls answer (the
+    device is looked for first)"""
+    import torch
+    lib = pkg.load_library()
+    bad = INVALID if torch.cuda.is_available() else NO_DEVICE
+    assert lib.svt_hip_inter_pred_frame(None, 1, 104, 72, 8, 0, None) == bad
+    assert lib.svt_hip_inter_pred_frame(None, 1, 104, 72, 12, 0, None) == bad
+
+
+def test_the_kernels_are_in_the_built_library():
+    """so that tests/test_kernel_resources.py, which holds every kernel of the library to no scratch, covers them"""
+    data = open(os.path.join(ROOT, "cidana-svt-av1_amd", "libsvt_hip_dsp.so"), "rb").read()
+    assert data.count(b"inter_pred_kernel") >= 2 and b"svt_hip_inter_pred_frame" in data
