@@ -197,6 +197,14 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_picture_stats_frame.restype = c_int
     L.svt_hip_inter_pred_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p]
     L.svt_hip_inter_pred_frame.restype = c_int
+    L.svt_hip_interp_sse_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p]
+    L.svt_hip_interp_sse_frame.restype = c_int
+    L.svt_hip_interp_decide_frame.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
+    L.svt_hip_interp_decide_frame.restype = c_int
+    L.svt_hip_interp_search_scratch_bytes.argtypes = [c_void_p, c_int, c_int]
+    L.svt_hip_interp_search_scratch_bytes.restype = c_size_t
+    L.svt_hip_interp_search_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_interp_search_frame.restype = c_int
     return L
 
 
@@ -301,6 +309,44 @@ class InterPredGroup(ctypes.Structure):
 
 UNI_PRED_LIST_0, UNI_PRED_LIST_1, BI_PRED = 0, 1, 2
 INTER_PRED_MAX_GROUPS = 48
+
+
+class InterpSseGroup(ctypes.Structure):
+    """svt_hip_interp_sse_group"""
+    _fields_ = [("d_ref", (c_void_p * 3) * 2), ("ref_stride", c_uint32 * 3), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3),
+                ("bwidth", c_int32), ("bheight", c_int32), ("nblocks", c_uint32), ("d_blk", c_void_p), ("d_sse", c_void_p)]
+
+
+class InterpDecision(ctypes.Structure):
+    """svt_hip_interp_decision (32 bytes; interp_decision_dtype() is its numpy twin)"""
+    _fields_ = [("interp_filters", c_uint32), ("switchable_rate", c_int32), ("rd", ctypes.c_int64), ("skip_sse_sb", ctypes.c_int64),
+                ("skip_txfm_sb", c_int32), ("pad", c_uint32)]
+
+
+class InterpParams(ctypes.Structure):
+    """svt_hip_interp_params"""
+    _fields_ = [("full_lambda", c_uint32), ("ac_dequant_q3", c_int32), ("d_rates", c_void_p), ("use_uv", c_int32), ("mode", c_int32)]
+
+
+class InterpDecideGroup(ctypes.Structure):
+    """svt_hip_interp_decide_group"""
+    _fields_ = [("bwidth", c_int32), ("bheight", c_int32), ("nblocks", c_uint32), ("d_sse", c_void_p), ("d_ctx", c_void_p),
+                ("d_searchable", c_void_p), ("d_decision", c_void_p), ("d_blk", c_void_p), ("d_blk_out", c_void_p)]
+
+
+class InterpSearchGroup(ctypes.Structure):
+    """svt_hip_interp_search_group"""
+    _fields_ = [("sse", InterpSseGroup), ("d_ctx", c_void_p), ("d_searchable", c_void_p), ("d_decision", c_void_p), ("d_blk_out", c_void_p)]
+
+
+INTERP_DUAL_FAST, INTERP_FULL, INTERP_SINGLE = 0, 1, 2
+
+
+def interp_decision_dtype():
+    """numpy dtype of svt_hip_interp_decision"""
+    import numpy as np
+    return np.dtype([("interp_filters", np.uint32), ("switchable_rate", np.int32), ("rd", np.int64), ("skip_sse_sb", np.int64),
+                     ("skip_txfm_sb", np.int32), ("pad", np.uint32)])
 
 
 def inter_blk_dtype():
@@ -1675,6 +1721,92 @@ class SvtHipDsp:
         if isinstance(groups, list):
             groups = self.make_inter_pred_groups(groups)
         return self.lib.svt_hip_inter_pred_frame(groups, n, pic_width, pic_height, bd, metric, self._stream())
+
+    # -- interpolation filter search: the nine-pair SSE table, the reference's walk, both in one call -------------------------------
+    def _interp_sse_struct(self, a, g):
+        P = lambda t: self._p(t) if t is not None else None
+        for l, key in enumerate(("ref0", "ref1")):
+            planes = g.get(key) or ()
+            for p in range(3):
+                a.d_ref[l][p] = P(planes[p]) if p < len(planes) else None
+        src = g.get("src") or ()
+        for p in range(3):
+            a.d_src[p] = P(src[p]) if p < len(src) else None
+            a.ref_stride[p] = list(g.get("ref_stride", ()))[p] if p < len(g.get("ref_stride", ())) else 0
+            a.src_stride[p] = list(g.get("src_stride", ()))[p] if p < len(g.get("src_stride", ())) else 0
+        a.bwidth, a.bheight = g.get("bwidth", 0), g.get("bheight", 0)
+        a.nblocks = g["nblocks"] if "nblocks" in g else (g["blk"].shape[0] if g.get("blk") is not None else 0)
+        a.d_blk, a.d_sse = P(g.get("blk")), P(g.get("sse"))
+
+    def make_interp_sse_groups(self, groups):
+        """groups: list of dicts with ref0 / ref1: lists of the Y, Cb, Cr tensors of a list whose first element is sample (0, 0) of the
+        PICTURE in the padded plane (ref1 optional; Y alone without use_uv), ref_stride (three numbers, samples), src / src_stride
+        likewise, bwidth, bheight (luma), blk (uint8 [n, 16]: inter_blk_dtype records), sse (int32 [n, planes, 9]).  -> ctypes array
+        (keep the tensors alive!)"""
+        arr = (InterpSseGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            self._interp_sse_struct(arr[i], g)
+        return arr
+
+    def interp_sse_frame(self, groups, pic_width, pic_height, use_uv, bd=8):
+        """svt_hip_interp_sse_frame.  groups: a ctypes array from make_interp_sse_groups or the list of dicts -> the return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_interp_sse_groups(groups)
+        return self.lib.svt_hip_interp_sse_frame(groups, n, pic_width, pic_height, bd, int(use_uv), self._stream())
+
+    def make_interp_params(self, full_lambda, ac_dequant_q3, rates, use_uv, mode):
+        """svt_hip_interp_params; rates: int32 [16, 3] device tensor (switchable_interp_FacBitss; keep it alive!)"""
+        return InterpParams(full_lambda, ac_dequant_q3, self._p(rates) if rates is not None else None, int(use_uv), mode)
+
+    def make_interp_decide_groups(self, groups):
+        """groups: list of dicts with bwidth, bheight, sse (int32 [n, planes, 9]), ctx (uint8 [n, 2]), searchable (uint8 [n]), decision
+        (uint8 [n, 32]: interp_decision_dtype records), optional blk and blk_out (uint8 [n, 16]).  -> ctypes array"""
+        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
+        arr = (InterpDecideGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            n = g["nblocks"] if "nblocks" in g else (g["decision"].shape[0] if g.get("decision") is not None else 0)
+            arr[i] = InterpDecideGroup(g.get("bwidth", 0), g.get("bheight", 0), n, P(g, "sse"), P(g, "ctx"), P(g, "searchable"),
+                                       P(g, "decision"), P(g, "blk"), P(g, "blk_out"))
+        return arr
+
+    def interp_decide_frame(self, groups, params):
+        """svt_hip_interp_decide_frame.  params: make_interp_params' (or None) -> the return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_interp_decide_groups(groups)
+        return self.lib.svt_hip_interp_decide_frame(groups, n, ctypes.byref(params) if params is not None else None, self._stream())
+
+    def make_interp_search_groups(self, groups):
+        """groups: make_interp_sse_groups' dicts (sse optional: the table then lives in the scratch) plus ctx, searchable, decision and the
+        optional blk_out.  -> ctypes array"""
+        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
+        arr = (InterpSearchGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            self._interp_sse_struct(arr[i].sse, g)
+            arr[i].d_ctx, arr[i].d_searchable, arr[i].d_decision, arr[i].d_blk_out = P(g, "ctx"), P(g, "searchable"), P(g, "decision"), P(g, "blk_out")
+        return arr
+
+    def interp_search_scratch_bytes(self, groups, use_uv):
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_interp_search_groups(groups)
+        return self.lib.svt_hip_interp_search_scratch_bytes(groups, n, int(use_uv))
+
+    def interp_search_frame(self, groups, pic_width, pic_height, params, scratch=None, bd=8):
+        """svt_hip_interp_search_frame.  scratch: a uint8 device tensor of interp_search_scratch_bytes, allocated here when None and
+        needed (the tensor is returned beside the code so that it outlives the enqueued work) -> (return code, scratch)"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_interp_search_groups(groups)
+        if scratch is None and params is not None:
+            need = self.lib.svt_hip_interp_search_scratch_bytes(groups, n, params.use_uv)
+            if need:
+                scratch = self.torch.empty((need,), dtype=self.torch.uint8, device=self.device)
+        rc = self.lib.svt_hip_interp_search_frame(groups, n, pic_width, pic_height, bd, ctypes.byref(params) if params is not None else None,
+                                                  self._p(scratch) if scratch is not None else None, scratch.numel() if scratch is not None else 0,
+                                                  self._stream())
+        return rc, scratch
 
     def fast_pick(self, dist, blk, rates, tx_size, bsize, bsize_uv, modes, deltas, uv_modes, uv_deltas, nfl, lam, metric, use_angle_delta=True,
                   slice_is_intra=True, ac_dequant_q3=0, intrabc_bits=0, dist_cb=None, dist_cr=None, pred=None, src_xy=None, want_all_cost=False):

@@ -1578,6 +1578,97 @@ typedef struct svt_hip_inter_pred_group {
 int svt_hip_inter_pred_frame(const svt_hip_inter_pred_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd,
                              int metric, void *stream);
 
+/* ---- Interpolation filter search of mode decision (interpolation_filter_search, EbInterPrediction.c:3578-3917) ---------------------
+ * For an inter candidate the reference predicts the block with up to nine (vertical, horizontal) filter pairs out of {REGULAR, SMOOTH,
+ * SHARP}, takes the SSE of every prediction against the source, models rate and distortion from it and keeps the first strict minimum
+ * of the RD cost.  Three calls: the table, the walk, and both in one.  8-bit samples only (bd != 8 is refused: DESIGN.md section 7).
+ *
+ * svt_hip_interp_sse_frame: THE TABLE.  Per block record (the svt_hip_inter_blk of svt_hip_inter_pred_frame; filter_x / filter_y are
+ * ignored) and plane (Y alone, or Y, Cb, Cr with use_uv), d_sse[block][plane][i], i = 0 .. 8, is the SSE (highbd_variance64_c, :3231,
+ * truncated to 32 bits as highbd_8_variance does) between the source block and the prediction svt_hip_inter_pred_frame writes for that
+ * plane with filter pair i.  Pair i is filter_sets[i] (:3573) through av1_make_interp_filters(y_filter, x_filter): the VERTICAL filter
+ * is i / 3 (filter_y), the horizontal one i % 3 (filter_x).  Everything else is svt_hip_inter_pred_frame's and is stated there: the
+ * clamp, the luma / chroma addressing, the 4-tap tables of a plane dimension <= 4 (the chroma of 8-wide blocks), BI_PRED through the two
+ * jnt entries, the BORDER CONTRACT (luma borders for d_ref[l][0], chroma borders for d_ref[l][1 .. 2]), the rules for x / y and for
+ * out-of-range device bytes.  d_ref[1][p] may be NULL only when no block of the group has pred_direction 1 or 2.  All nine pairs are
+ * always computed; per list the (w + 7) x (h + 7) window is staged once and three horizontal passes feed nine vertical ones; no
+ * prediction leaves the chip.  One launch per SVT_HIP_INTER_PRED_MAX_GROUPS (group, plane) entries; nothing is zeroed by the caller.
+ * Validated before the first launch (SVT_HIP_ERR_INVALID, nothing launched): bd 8; picture sides as svt_hip_inter_pred_frame; bwidth and
+ * bheight in {8, 16, 32, 64} and not above the picture; d_blk (4-byte aligned), d_sse (4-byte aligned), d_ref[0][0], d_src[0] set and,
+ * with use_uv, d_ref[0][1 .. 2] and d_src[1 .. 2]; nblocks within one launch (the luma tiling's workgroups).
+ *
+ * svt_hip_interp_decide_frame: THE WALK, to the letter, one svt_hip_interp_decision per block.  Per pair i, model_rd_for_sb (:3440-3529):
+ * per plane model_rd_from_sse(sse, num_pels_log2 of the PLANE block, ac_dequant_q3 >> 3), ac_dequant_q3 = y_dequant_Q3[qindex][1], the
+ * LUMA AC value for all three planes (:3507-3516); rate and distortion summed in uint64, the rate cast to int32; skip_txfm_sb =
+ * total_sse == 0, skip_sse_sb = total_sse << 4.  rs = d_rates[ctx[0]][i / 3] + d_rates[ctx[1]][i % 3] (av1_get_switchable_rate, :3184:
+ * dir 0 reads the vertical filter; d_rates is switchable_interp_FacBitss, int32 [16][3]; d_ctx[block][dir] is
+ * av1_get_pred_context_switchable_interp, the caller's, read as min(ctx, 15)).  rd = RDCOST(full_lambda, rs + rate, dist) = (((uint64)
+ * (int32)(rs + rate) * full_lambda + 256) >> 9) + dist * 128 held as int64 (:3305).  Pair 0 first (:3621-3661); a later pair replaces
+ * the best only when its rd is strictly below, and switchable_rate, skip_txfm_sb and skip_sse_sb follow the winner.  Pairs tried:
+ *   SVT_HIP_INTERP_DUAL_FAST  :3672-3825: 1, 2, then best + 3 and best + 6, best the winner among 0 .. 2;
+ *   SVT_HIP_INTERP_FULL       :3828 with enable_dual_filter: 1 .. 8;
+ *   SVT_HIP_INTERP_SINGLE     :3828 without: 4, 8.
+ * interp_filters = y_filter | x_filter << 16 of the winner.  A block whose d_searchable byte is 0 (av1_is_interp_needed, the caller's)
+ * gets the :3909-3911 result: interp_filters 0 and pair 0's rd, rate and skip values.  d_blk_out (optional, with d_blk): the block's
+ * record with filter_x / filter_y set from the winner, ready for svt_hip_inter_pred_frame (the reference's :4470); d_blk_out may equal
+ * d_blk (a thread reads its record before it writes it) but must not overlap it otherwise.  Only the block index addresses memory from
+ * device data.  Validated before the launch: params and d_rates set, mode 0 .. 2, ac_dequant_q3 0 .. 32767; per group the sides as
+ * above, d_sse (4-byte), d_ctx, d_searchable, d_decision (8-byte) set, d_blk with d_blk_out (4-byte each).
+ *
+ * svt_hip_interp_search_frame: both on `stream`, whose order carries the dependency.  sse.d_sse may be NULL: the table then lives in
+ * d_scratch, per non-empty group in group order nblocks * planes * 36 bytes rounded up to 16; svt_hip_interp_search_scratch_bytes (HOST)
+ * returns the sum (0: bad parameters or nothing to carve).  d_scratch 16-byte aligned.  Both stages are validated before the first
+ * launch.  All calls only enqueue, allocate nothing and can be captured into a HIP graph. */
+enum { SVT_HIP_INTERP_DUAL_FAST = 0, SVT_HIP_INTERP_FULL = 1, SVT_HIP_INTERP_SINGLE = 2 };
+typedef struct svt_hip_interp_sse_group {
+    const uint8_t *d_ref[2][3];          /* [list][Y, Cb, Cr]: sample (0, 0) of the picture in each plane */
+    uint32_t ref_stride[3];              /* Y, Cb, Cr; both lists */
+    const uint8_t *d_src[3];             /* source planes, sample (0, 0) of the picture */
+    uint32_t src_stride[3];
+    int32_t bwidth, bheight;             /* LUMA block size */
+    uint32_t nblocks;
+    const svt_hip_inter_blk *d_blk;      /* [nblocks] */
+    uint32_t *d_sse;                     /* [nblocks][use_uv ? 3 : 1][9] */
+} svt_hip_interp_sse_group;
+int svt_hip_interp_sse_frame(const svt_hip_interp_sse_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd,
+                             int use_uv, void *stream);
+
+typedef struct svt_hip_interp_decision { /* sizeof 32, 8-byte aligned */
+    uint32_t interp_filters;             /* y_filter | x_filter << 16 */
+    int32_t  switchable_rate;
+    int64_t  rd;
+    int64_t  skip_sse_sb;
+    int32_t  skip_txfm_sb;
+    uint32_t pad;                        /* written as 0 */
+} svt_hip_interp_decision;
+typedef struct svt_hip_interp_params {
+    uint32_t full_lambda;
+    int32_t ac_dequant_q3;               /* y_dequant_Q3[qindex][1] */
+    const int32_t *d_rates;              /* switchable_interp_FacBitss: int32 [16][3], device */
+    int32_t use_uv, mode;                /* mode: SVT_HIP_INTERP_DUAL_FAST / _FULL / _SINGLE */
+} svt_hip_interp_params;
+typedef struct svt_hip_interp_decide_group {
+    int32_t bwidth, bheight;             /* LUMA block size */
+    uint32_t nblocks;
+    const uint32_t *d_sse;               /* [nblocks][use_uv ? 3 : 1][9] */
+    const uint8_t *d_ctx;                /* [nblocks][2] */
+    const uint8_t *d_searchable;         /* [nblocks] */
+    svt_hip_interp_decision *d_decision; /* [nblocks] */
+    const svt_hip_inter_blk *d_blk;      /* optional, with d_blk_out */
+    svt_hip_inter_blk *d_blk_out;        /* optional [nblocks] */
+} svt_hip_interp_decide_group;
+int svt_hip_interp_decide_frame(const svt_hip_interp_decide_group *groups, int ngroups, const svt_hip_interp_params *params, void *stream);
+
+typedef struct svt_hip_interp_search_group {
+    svt_hip_interp_sse_group sse;        /* sse.d_sse may be NULL */
+    const uint8_t *d_ctx, *d_searchable;
+    svt_hip_interp_decision *d_decision;
+    svt_hip_inter_blk *d_blk_out;        /* optional; may equal sse.d_blk */
+} svt_hip_interp_search_group;
+size_t svt_hip_interp_search_scratch_bytes(const svt_hip_interp_search_group *groups, int ngroups, int use_uv);   /* HOST */
+int svt_hip_interp_search_frame(const svt_hip_interp_search_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd,
+                                const svt_hip_interp_params *params, void *d_scratch, size_t scratch_bytes, void *stream);
+
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
  * aom_dsp_rtcd.h it implements (svt_hip_rtcd_slot_count() entries: the 19 av1_fwd_txfm2d_WxH, the 19
