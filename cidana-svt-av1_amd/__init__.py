@@ -205,6 +205,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_interp_search_scratch_bytes.restype = c_size_t
     L.svt_hip_interp_search_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
     L.svt_hip_interp_search_frame.restype = c_int
+    L.svt_hip_inter_fast_pick_frame.argtypes = [c_void_p, c_int, c_int, c_void_p]
+    L.svt_hip_inter_fast_pick_frame.restype = c_int
+    L.svt_hip_inter_fast_search_scratch_bytes.argtypes = [c_void_p, c_int]
+    L.svt_hip_inter_fast_search_scratch_bytes.restype = c_size_t
+    L.svt_hip_inter_fast_search_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_inter_fast_search_frame.restype = c_int
     return L
 
 
@@ -340,6 +346,80 @@ class InterpSearchGroup(ctypes.Structure):
 
 
 INTERP_DUAL_FAST, INTERP_FULL, INTERP_SINGLE = 0, 1, 2
+
+
+class InterCand(ctypes.Structure):
+    """svt_hip_inter_cand: what only the fast cost reads of an inter candidate (16 bytes; inter_cand_dtype() is its numpy twin)"""
+    _fields_ = [("pred_mv", (ctypes.c_int16 * 2) * 2), ("mode_ctx", ctypes.c_int16), ("pred_mode", ctypes.c_uint8),
+                ("ref_frame_type", ctypes.c_uint8), ("drl_index", ctypes.c_uint8), ("ref_mv_count", ctypes.c_uint8), ("drl_ctx", ctypes.c_uint8),
+                ("flags", ctypes.c_uint8)]
+
+
+class InterFastBlk(ctypes.Structure):
+    """svt_hip_inter_fast_blk: the block's context bytes (16 bytes; inter_fast_blk_dtype() is its numpy twin)"""
+    _fields_ = [(n, ctypes.c_uint8) for n in ("skip_flag_context", "is_inter_ctx", "reference_mode_context", "compoud_reference_type_context",
+                                              "comp_ref_p", "comp_ref_p1", "comp_ref_p2", "comp_bwdref_p", "comp_bwdref_p1")] + \
+               [("single_ref_p", ctypes.c_uint8 * 6), ("has_uv", ctypes.c_uint8)]
+
+
+INTER_FAST_RATE_TABLES = (("skipModeFacBits", (3, 3)), ("newMvModeFacBits", (6, 3)), ("zeroMvModeFacBits", (2, 3)), ("refMvModeFacBits", (6, 3)),
+                          ("drlModeFacBits", (3, 3)), ("interCompoundModeFacBits", (8, 9)), ("singleRefFacBits", (3, 6, 3)),
+                          ("compRefTypeFacBits", (5, 3)), ("compRefFacBits", (3, 3, 3)), ("compBwdRefFacBits", (3, 2, 3)),
+                          ("compInterFacBits", (5, 3)), ("motionModeFacBits", (22, 3)), ("motionModeFacBits1", (22, 2)),
+                          ("intraInterFacBits", (4, 2)), ("nmv_vec_cost", (4,)))      # svt_hip_inter_fast_rates
+INTER_FAST_RATE_WORDS = 383
+MV_VALS = 32767
+
+
+class InterFastRates(ctypes.Structure):
+    """svt_hip_inter_fast_rates"""
+    _fields_ = [("skipModeFacBits", (c_int32 * 3) * 3), ("newMvModeFacBits", (c_int32 * 3) * 6), ("zeroMvModeFacBits", (c_int32 * 3) * 2),
+                ("refMvModeFacBits", (c_int32 * 3) * 6), ("drlModeFacBits", (c_int32 * 3) * 3), ("interCompoundModeFacBits", (c_int32 * 9) * 8),
+                ("singleRefFacBits", ((c_int32 * 3) * 6) * 3), ("compRefTypeFacBits", (c_int32 * 3) * 5), ("compRefFacBits", ((c_int32 * 3) * 3) * 3),
+                ("compBwdRefFacBits", ((c_int32 * 3) * 2) * 3), ("compInterFacBits", (c_int32 * 3) * 5), ("motionModeFacBits", (c_int32 * 3) * 22),
+                ("motionModeFacBits1", (c_int32 * 2) * 22), ("intraInterFacBits", (c_int32 * 2) * 4), ("nmv_vec_cost", c_int32 * 4)]
+
+
+class InterFastPickGroup(ctypes.Structure):
+    """svt_hip_inter_fast_pick_group"""
+    _fields_ = [("bsize", c_int32), ("bsize_uv", c_int32), ("nblocks", c_uint32), ("ninter", c_int32), ("nintra", c_int32), ("nfl", c_int32),
+                ("lambda_", c_uint32), ("ac_dequant_q3", ctypes.c_int16), ("reference_mode_select", c_int32), ("switchable_motion_mode", c_int32)] + \
+               [(n, c_void_p) for n in ("d_blk", "d_cand_in", "d_ctx", "d_rates", "d_mv_cost", "d_dist", "d_dist_cb", "d_dist_cr", "d_intra_cost",
+                                        "d_intra_rate", "d_cand", "d_sorted", "d_cost", "d_rate", "d_ref_fast_cost", "d_all_cost", "d_blk_out",
+                                        "d_cand_out", "d_src_xy_out")]
+
+
+class InterFastSearchGroup(ctypes.Structure):
+    """svt_hip_inter_fast_search_group"""
+    _fields_ = [("pick", InterFastPickGroup), ("bwidth", c_int32), ("bheight", c_int32), ("use_chroma", c_int32), ("d_ref", (c_void_p * 3) * 2),
+                ("ref_stride", c_uint32 * 3), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3), ("d_pred_out", c_void_p * 3),
+                ("d_intra_pred", c_void_p)]
+
+
+def inter_cand_dtype():
+    """numpy dtype of svt_hip_inter_cand"""
+    import numpy as np
+    return np.dtype([("pred_mv", np.int16, (2, 2)), ("mode_ctx", np.int16), ("pred_mode", np.uint8), ("ref_frame_type", np.uint8),
+                     ("drl_index", np.uint8), ("ref_mv_count", np.uint8), ("drl_ctx", np.uint8), ("flags", np.uint8)])
+
+
+def inter_fast_blk_dtype():
+    """numpy dtype of svt_hip_inter_fast_blk"""
+    import numpy as np
+    return np.dtype([(n, np.uint8) for n in ("skip_flag_context", "is_inter_ctx", "reference_mode_context", "compoud_reference_type_context",
+                                             "comp_ref_p", "comp_ref_p1", "comp_ref_p2", "comp_bwdref_p", "comp_bwdref_p1")] +
+                    [("single_ref_p", np.uint8, (6,)), ("has_uv", np.uint8)])
+
+
+def pack_inter_fast_rates(tables):
+    """dict of the fifteen int32 tables (INTER_FAST_RATE_TABLES shapes) -> int32 [383] in svt_hip_inter_fast_rates order"""
+    import numpy as np
+    parts = []
+    for name, shape in INTER_FAST_RATE_TABLES:
+        a = np.asarray(tables[name], np.int32)
+        assert a.shape == shape, (name, a.shape)
+        parts.append(a.reshape(-1))
+    return np.concatenate(parts)
 
 
 def interp_decision_dtype():
@@ -1806,6 +1886,82 @@ class SvtHipDsp:
         rc = self.lib.svt_hip_interp_search_frame(groups, n, pic_width, pic_height, bd, ctypes.byref(params) if params is not None else None,
                                                   self._p(scratch) if scratch is not None else None, scratch.numel() if scratch is not None else 0,
                                                   self._stream())
+        return rc, scratch
+
+    # -- the fast loop for inter candidates: fast cost, the N best of the combined list, the survivors' records; the one-call search ---------
+    INTER_FAST_PICK_OUTPUTS = ("cand", "sorted", "cost", "rate", "ref_fast_cost", "all_cost", "blk_out", "cand_out", "src_xy_out")
+
+    def _inter_fast_pick_struct(self, a, g):
+        P = lambda k: self._p(g[k]) if g.get(k) is not None else None
+        a.bsize, a.bsize_uv, a.ninter, a.nintra, a.nfl = g.get("bsize", 0), g.get("bsize_uv", 0), g.get("ninter", 0), g.get("nintra", 0), g.get("nfl", 0)
+        a.nblocks = g["nblocks"] if "nblocks" in g else (g["ctx"].shape[0] if g.get("ctx") is not None else 0)
+        a.lambda_, a.ac_dequant_q3 = g.get("lambda", 0), g.get("ac_dequant_q3", 0)
+        a.reference_mode_select, a.switchable_motion_mode = int(g.get("reference_mode_select", 0)), int(g.get("switchable_motion_mode", 0))
+        a.d_blk, a.d_cand_in, a.d_ctx, a.d_rates, a.d_mv_cost = P("blk"), P("cand_in"), P("ctx"), P("rates"), P("mv_cost")
+        a.d_dist, a.d_dist_cb, a.d_dist_cr, a.d_intra_cost, a.d_intra_rate = P("dist"), P("dist_cb"), P("dist_cr"), P("intra_cost"), P("intra_rate")
+        a.d_cand, a.d_sorted, a.d_cost, a.d_rate, a.d_ref_fast_cost = P("cand"), P("sorted"), P("cost"), P("rate"), P("ref_fast_cost")
+        a.d_all_cost, a.d_blk_out, a.d_cand_out, a.d_src_xy_out = P("all_cost"), P("blk_out"), P("cand_out"), P("src_xy_out")
+
+    def make_inter_fast_pick_groups(self, groups):
+        """groups: list of dicts with tensors blk (uint8 [n, ninter, 16]: inter_blk_dtype records), cand_in (uint8 [n, ninter, 16]:
+        inter_cand_dtype), ctx (uint8 [n, 16]: inter_fast_blk_dtype), rates (int32 [383]: pack_inter_fast_rates), mv_cost (int32 [2, 32767]),
+        dist (int64 [n, ninter]; optional dist_cb / dist_cr), intra_cost (int64 [n, nintra], with nintra > 0), optional intra_rate (int32
+        [n, nintra, 2]); the outputs cand / sorted (uint8 [n, N]), cost (int64 [n, N]), rate (int32 [n, N, 2]), ref_fast_cost (int64 [n]),
+        blk_out (uint8 [n, N, 16]) and the optional all_cost (int64 [n, ninter]), cand_out (uint8 [n, N, 16]), src_xy_out (int32 [n, N]),
+        N = min(nfl, ninter + nintra); plus bsize, bsize_uv, ninter, nintra, nfl, lambda, ac_dequant_q3, reference_mode_select,
+        switchable_motion_mode.  -> ctypes array (keep the tensors alive!)"""
+        arr = (InterFastPickGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            self._inter_fast_pick_struct(arr[i], g)
+        return arr
+
+    def inter_fast_pick_frame(self, groups, metric):
+        """svt_hip_inter_fast_pick_frame.  groups: a ctypes array from make_inter_fast_pick_groups or the list of dicts -> the return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_inter_fast_pick_groups(groups)
+        return self.lib.svt_hip_inter_fast_pick_frame(groups, n, metric, self._stream())
+
+    def make_inter_fast_search_groups(self, groups):
+        """groups: make_inter_fast_pick_groups' dicts (dist / dist_cb / dist_cr optional: scratch) plus bwidth, bheight, use_chroma, ref0 /
+        ref1 (lists of the Y, Cb, Cr tensors whose first element is sample (0, 0) of the picture), ref_stride, src, src_stride (three
+        each), pred_out (list of dense [n, N, h, w] tensors, Y required), optional intra_pred ([n, nintra, H, W]).  -> ctypes array"""
+        P = lambda t: self._p(t) if t is not None else None
+        arr = (InterFastSearchGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            a = arr[i]
+            self._inter_fast_pick_struct(a.pick, g)
+            a.bwidth, a.bheight, a.use_chroma = g.get("bwidth", 0), g.get("bheight", 0), int(g.get("use_chroma", 0))
+            for p in range(3):
+                for l, key in enumerate(("ref0", "ref1")):
+                    planes = g.get(key) or ()
+                    a.d_ref[l][p] = P(planes[p]) if p < len(planes) else None
+                src, out = g.get("src") or (), g.get("pred_out") or ()
+                a.d_src[p] = P(src[p]) if p < len(src) else None
+                a.d_pred_out[p] = P(out[p]) if p < len(out) else None
+                a.ref_stride[p] = list(g.get("ref_stride", ()))[p] if p < len(g.get("ref_stride", ())) else 0
+                a.src_stride[p] = list(g.get("src_stride", ()))[p] if p < len(g.get("src_stride", ())) else 0
+            a.d_intra_pred = P(g.get("intra_pred"))
+        return arr
+
+    def inter_fast_search_scratch_bytes(self, groups):
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_inter_fast_search_groups(groups)
+        return self.lib.svt_hip_inter_fast_search_scratch_bytes(groups, n)
+
+    def inter_fast_search_frame(self, groups, pic_width, pic_height, metric, scratch=None, bd=8):
+        """svt_hip_inter_fast_search_frame.  scratch: a uint8 device tensor of inter_fast_search_scratch_bytes, allocated here when None
+        and needed (returned beside the code so that it outlives the enqueued work) -> (return code, scratch)"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_inter_fast_search_groups(groups)
+        if scratch is None:
+            need = self.lib.svt_hip_inter_fast_search_scratch_bytes(groups, n)
+            if need:
+                scratch = self.torch.empty((need,), dtype=self.torch.uint8, device=self.device)
+        rc = self.lib.svt_hip_inter_fast_search_frame(groups, n, pic_width, pic_height, bd, metric, self._p(scratch) if scratch is not None else None,
+                                                      scratch.numel() if scratch is not None else 0, self._stream())
         return rc, scratch
 
     def fast_pick(self, dist, blk, rates, tx_size, bsize, bsize_uv, modes, deltas, uv_modes, uv_deltas, nfl, lam, metric, use_angle_delta=True,

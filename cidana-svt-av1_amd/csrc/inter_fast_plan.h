@@ -1,0 +1,132 @@
+// inter_fast_plan.h — the inter fast search planned on the host: the argument check of svt_hip_inter_fast_pick_frame, the pick's blocks
+// per wave, and for svt_hip_inter_fast_search_frame ONE walk over its groups that sizes its scratch, carves it and derives the groups of
+// its stages (distortion-only prediction, pick, the survivors' prediction, the intra gather).  svt_hip_inter_fast.hip checks and plans
+// here, then enqueues.  Plain C++17, no HIP header: a CPU program can include it (tests/c/inter_fast_plan_host.cpp).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "inter_plan.h"
+#include "md_plan.h"
+
+namespace svthost {
+
+constexpr int kIfpMaxBpw = 4;                               // IFP_MAX_BPW (kernel_inter_fast_pick.h)
+// block_size_wide / block_size_high (EbDefinitions.h): the luma block of a bsize
+constexpr uint8_t kBsizeW[22] = {4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64, 128, 128, 4, 16, 8, 32, 16, 64};
+constexpr uint8_t kBsizeH[22] = {4, 8, 4, 8, 16, 8, 16, 32, 16, 32, 64, 32, 64, 128, 64, 128, 16, 4, 32, 8, 64, 16};
+
+inline int inter_fast_n(const svt_hip_inter_fast_pick_group& G) { const int nc = G.ninter + G.nintra; return G.nfl < nc ? G.nfl : nc; }
+
+// blocks per wave: one until every wave slot of the device (32 per CU) has a block, then up to kIfpMaxBpw
+inline int inter_fast_pick_bpw(uint32_t nblocks, int num_cu) {
+    const uint32_t slots = (uint32_t)(num_cu > 0 ? num_cu : 256) * 32u, b = nblocks / slots;
+    return b < 1 ? 1 : (b > (uint32_t)kIfpMaxBpw ? kIfpMaxBpw : (int)b);
+}
+
+// every group of a pick call before the first launch, empty groups' sizes and counts included
+inline int inter_fast_pick_check(const svt_hip_inter_fast_pick_group* groups, int ngroups, int metric) {
+    if (int rc = group_list_check(groups, ngroups)) return rc;
+    if (int rc = metric_check(metric)) return rc;
+    for (int g = 0; g < ngroups; g++) {
+        const svt_hip_inter_fast_pick_group& G = groups[g];
+        if (G.bsize < 0 || G.bsize > 21 || G.bsize_uv < 0 || G.bsize_uv > 21)
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: bsize %d / bsize_uv %d (0 .. 21)", g, G.bsize, G.bsize_uv);
+        if (G.ninter < 1 || G.ninter > 64 || G.nintra < 0 || G.nintra > 63 || G.ninter + G.nintra > SVT_HIP_FAST_LOOP_MAX_CANDIDATES)
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: ninter %d (1 .. 64), nintra %d (0 .. 63), together at most 64", g, G.ninter, G.nintra);
+        if (G.nfl < 1 || G.nfl > SVT_HIP_MAX_NFL) return set_err(SVT_HIP_ERR_INVALID, "group %d: nfl %d (1 .. %d)", g, G.nfl, SVT_HIP_MAX_NFL);
+        if (G.ac_dequant_q3 < 0) return set_err(SVT_HIP_ERR_INVALID, "group %d: ac_dequant_q3 %d", g, G.ac_dequant_q3);
+        if (G.nblocks == 0) continue;
+        if (int rc = pairs_check(g, G.nblocks, (uint64_t)(G.ninter + G.nintra), "nblocks * ncand")) return rc;
+        if (!G.d_blk || !G.d_cand_in || !G.d_ctx || !G.d_rates || !G.d_mv_cost || !G.d_dist || !G.d_cand || !G.d_sorted || !G.d_cost || !G.d_rate ||
+            !G.d_ref_fast_cost || !G.d_blk_out)
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL member", g);
+        if (G.nintra > 0 && !G.d_intra_cost) return set_err(SVT_HIP_ERR_INVALID, "group %d: nintra %d without d_intra_cost", g, G.nintra);
+        if (((uintptr_t)G.d_dist & 7) || ((uintptr_t)G.d_dist_cb & 7) || ((uintptr_t)G.d_dist_cr & 7) || ((uintptr_t)G.d_intra_cost & 7) ||
+            ((uintptr_t)G.d_cost & 7) || ((uintptr_t)G.d_ref_fast_cost & 7) || ((uintptr_t)G.d_all_cost & 7) || ((uintptr_t)G.d_blk & 3) ||
+            ((uintptr_t)G.d_blk_out & 3) || ((uintptr_t)G.d_cand_in & 3) || ((uintptr_t)G.d_cand_out & 3) || ((uintptr_t)G.d_ctx & 3) ||
+            ((uintptr_t)G.d_rates & 3) || ((uintptr_t)G.d_mv_cost & 3) || ((uintptr_t)G.d_rate & 3) || ((uintptr_t)G.d_intra_rate & 3) ||
+            ((uintptr_t)G.d_src_xy_out & 3))
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: misaligned buffer (the 8-byte arrays 8, the records, tables and 4-byte arrays 4)", g);
+    }
+    return SVT_HIP_OK;
+}
+
+// ---- svt_hip_inter_fast_search_frame: scratch and stage groups ---------------------------------------------------------------------------
+struct InterFastGather {                                    // step 4 of one group: the intra survivors' luma predictions
+    const uint8_t* d_cand; const void* d_intra_pred; void* d_pred_out;
+    uint32_t nblocks, n, ninter, nintra, quads;             // quads: 16-byte pieces of a luma block
+};
+struct InterFastStages {
+    std::vector<svt_hip_inter_pred_group> dist;             // step 1: Y, then Cb and Cr of the groups with chroma
+    std::vector<svt_hip_inter_fast_pick_group> pick;        // step 2
+    std::vector<svt_hip_inter_pred_group> pred;             // step 3
+    std::vector<InterFastGather> gather;                    // step 4
+};
+// The walk (md_plan.h's Carver): checks what the carving needs of each group, carves, and with `st` derives the four stages' groups.
+// bytes_per_sample (1: bd 8, 2: bd 10) sizes the intra gather only; plan_stages takes a plain function, hence the two wrappers below.
+inline int inter_fast_search_walk_bd(const svt_hip_inter_fast_search_group* groups, int ngroups, int bytes_per_sample, Carver& sc, InterFastStages* st) {
+    if (int rc = group_list_check(groups, ngroups)) return rc;
+    for (int g = 0; g < ngroups; g++) {
+        const svt_hip_inter_fast_search_group& G = groups[g];
+        svt_hip_inter_fast_pick_group P = G.pick;
+        if (P.ninter < 1 || P.ninter > 64 || P.nintra < 0 || P.nintra > 63 || P.ninter + P.nintra > SVT_HIP_FAST_LOOP_MAX_CANDIDATES)
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: ninter %d (1 .. 64), nintra %d (0 .. 63), together at most 64", g, P.ninter, P.nintra);
+        if (P.nfl < 1 || P.nfl > SVT_HIP_MAX_NFL) return set_err(SVT_HIP_ERR_INVALID, "group %d: nfl %d (1 .. %d)", g, P.nfl, SVT_HIP_MAX_NFL);
+        if (int rc = pairs_check(g, P.nblocks, (uint64_t)(P.ninter + P.nintra), "nblocks * ncand")) return rc;
+        if (P.bsize < 0 || P.bsize > 21 || kBsizeW[P.bsize] != G.bwidth || kBsizeH[P.bsize] != G.bheight)
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: bsize %d is not the %d x %d block", g, P.bsize, G.bwidth, G.bheight);
+        const size_t pairs = (size_t)P.nblocks * (size_t)P.ninter;
+        uint64_t *dy = (uint64_t*)P.d_dist, *dcb = (uint64_t*)P.d_dist_cb, *dcr = (uint64_t*)P.d_dist_cr;
+        if (pairs) {
+            if (!dy) sc.piece(dy, pairs * 8);
+            if (G.use_chroma && !dcb) sc.piece(dcb, pairs * 8);
+            if (G.use_chroma && !dcr) sc.piece(dcr, pairs * 8);
+        }
+        if (!st) continue;
+        if (!G.use_chroma) dcb = dcr = nullptr;
+        P.d_dist = dy; P.d_dist_cb = dcb; P.d_dist_cr = dcr;
+        st->pick.push_back(P);
+        if (P.nblocks == 0) continue;
+        const int n = inter_fast_n(P);
+        if (!G.d_pred_out[0]) return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL d_pred_out[0]", g);
+        uint64_t* dists[3] = {dy, dcb, dcr};
+        for (int p = 0; p < (G.use_chroma ? 3 : 1); p++) {
+            svt_hip_inter_pred_group D{};
+            D.d_ref[0] = G.d_ref[0][p]; D.d_ref[1] = G.d_ref[1][p]; D.ref_stride = G.ref_stride[p]; D.ss = p ? 1 : 0;
+            D.bwidth = G.bwidth; D.bheight = G.bheight; D.nblocks = (uint32_t)pairs; D.d_blk = P.d_blk;
+            D.d_src = G.d_src[p]; D.src_stride = G.src_stride[p]; D.d_dist = dists[p];
+            if (!D.d_src) return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL d_src[%d]", g, p);
+            st->dist.push_back(D);
+            if (!G.d_pred_out[p]) continue;
+            svt_hip_inter_pred_group R = D;
+            R.nblocks = P.nblocks * (uint32_t)n; R.d_blk = P.d_blk_out; R.d_pred = G.d_pred_out[p]; R.pred_stride = 0;
+            R.d_src = nullptr; R.d_dist = nullptr;
+            st->pred.push_back(R);
+        }
+        if (G.d_intra_pred && P.nintra > 0) {
+            if (((uintptr_t)G.d_intra_pred & 15)) return set_err(SVT_HIP_ERR_INVALID, "group %d: d_intra_pred not 16-byte aligned", g);
+            if (G.d_intra_pred == G.d_pred_out[0]) return set_err(SVT_HIP_ERR_INVALID, "group %d: d_intra_pred is d_pred_out[0]", g);
+            InterFastGather T{P.d_cand, G.d_intra_pred, G.d_pred_out[0], P.nblocks, (uint32_t)n, (uint32_t)P.ninter, (uint32_t)P.nintra,
+                              (uint32_t)(G.bwidth * G.bheight * bytes_per_sample / 16)};
+            st->gather.push_back(T);
+        }
+    }
+    return SVT_HIP_OK;
+}
+inline int inter_fast_search_walk8(const svt_hip_inter_fast_search_group* g, int n, Carver& sc, InterFastStages* st) { return inter_fast_search_walk_bd(g, n, 1, sc, st); }
+inline int inter_fast_search_walk16(const svt_hip_inter_fast_search_group* g, int n, Carver& sc, InterFastStages* st) { return inter_fast_search_walk_bd(g, n, 2, sc, st); }
+
+// Everything the call checks before its first launch: bd, the scratch, then every stage's own check on the derived groups.
+inline int inter_fast_search_plan(const svt_hip_inter_fast_search_group* groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd,
+                                  int metric, void* d_scratch, size_t scratch_bytes, InterFastStages* st) {
+    if (bd != 8 && bd != 10) return set_err(SVT_HIP_ERR_INVALID, "bd %d (8 or 10)", bd);
+    if (int rc = plan_stages(bd == 8 ? inter_fast_search_walk8 : inter_fast_search_walk16, groups, ngroups, d_scratch, scratch_bytes, st)) return rc;
+    if (int rc = inter_pred_check(st->dist.data(), (int)st->dist.size(), pic_width, pic_height, bd, metric)) return rc;
+    if (int rc = inter_fast_pick_check(st->pick.data(), (int)st->pick.size(), metric)) return rc;
+    return inter_pred_check(st->pred.data(), (int)st->pred.size(), pic_width, pic_height, bd, metric);
+}
+
+}  // namespace svthost

@@ -1094,7 +1094,7 @@ int svt_hip_intra_fast_loop_frame(const svt_hip_fast_loop_group *groups, int ngr
  * d_src_xy_out without d_src_xy, d_pred_out == d_pred, misalignment (d_pred / d_pred_out 16 bytes; the 8-byte arrays and d_blk 8;
  * d_rates / d_rate / d_src_xy* 4), nblocks * ncand above 2^31 - 1.  One launch per non-empty group, the group in the kernel arguments; the call
  * only enqueues (no allocation, no synchronisation) and can be captured into a HIP graph.
- * Left to the caller: inter candidates (the first, src-to-src loop and the inter-before-intra swap), the intrabc branch
+ * Left to the caller here: inter candidates (svt_hip_inter_fast_pick_frame below costs them and walks the combined list), the intrabc branch
  * (:556-597; intrabc_bits is intrabcFacBits[0] when the picture allows intrabc, else 0), and product_full_mode_decision. */
 #define SVT_HIP_MAX_NFL 40
 typedef struct svt_hip_fast_pick_blk {
@@ -1668,6 +1668,143 @@ typedef struct svt_hip_interp_search_group {
 size_t svt_hip_interp_search_scratch_bytes(const svt_hip_interp_search_group *groups, int ngroups, int use_uv);   /* HOST */
 int svt_hip_interp_search_frame(const svt_hip_interp_search_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd,
                                 const svt_hip_interp_params *params, void *d_scratch, size_t scratch_bytes, void *stream);
+
+/* ---- The fast loop for inter candidates: fast cost, the N best over the block's combined list, the survivors' records ----------------
+ * svt_hip_inter_fast_pick_frame is svt_hip_fast_pick_frame for the list ProductGenerateMdCandidatesCu builds for a P or B picture:
+ * per block `ninter` inter candidates followed by `nintra` intra candidates (the order in which fast_candidate_array is filled),
+ * ncand = ninter + nintra <= 64.  svt_hip_inter_pred_frame (distortion only) writes its d_dist*, svt_hip_fast_pick_frame's d_all_cost
+ * with slice_is_intra 0 is the intended d_intra_cost; its d_blk_out is a svt_hip_inter_pred_frame d_blk of nblocks * n records.
+ * Everything that depends on MVP generation arrives as bytes (mode_ctx, ref_mv_count, drl_ctx, the predicted vectors), the split
+ * d_ctx / d_searchable make in the interpolation search.  is_compound is pred_direction == SVT_HIP_BI_PRED: every injector of
+ * EbModeDecision.c sets the two together (its twenty assignments of is_compound, :538 .. :2345, each beside prediction_direction[0]:
+ * is_compound 0 with UNI_PRED_LIST_0 / _1, is_compound 1 with BI_PRED).
+ * What is reproduced, to the letter:
+ *   cost     av1_inter_fast_cost (EbRateDistortionCost.c:971-1318) with EstimateRefFramesNumBits (:741-947) and Av1ModeContextAnalyzer
+ *            (:951-969, compound_mode_ctx_map_2); rf[] = av1_set_ref_frame(ref_frame_type) (EbAdaptiveMotionVectorPrediction.c:214-258).
+ *            Reference bits :781-942 (compInterFacBits only under reference_mode_select and min(bw, bh) >= 8, the luma block of bsize);
+ *            mode bits :1037-1057 (NEWMV / GLOBALMV / NEARESTMV cascade, or the compound table at the mapped context); the two DRL
+ *            loops with their breaks :1058-1088; the MV rate :1090-1198, each av1_mv_bit_cost (:91-95) = (joint + comp[0][row diff] +
+ *            comp[1][col diff]) * 108 rounded by 7 bits, d_mv_cost indexed from its centre entry MV_MAX = 16383
+ *            (EbMdRateEstimation.c:363-366); motion-mode bits :1203-1229 out of motionModeFacBits1 (allowed == OBMC) or
+ *            motionModeFacBits; intraInterFacBits[is_inter_ctx][1] :1250; then SAD RDCOST(lambda, rate, luma + chroma) or the two
+ *            model_rd_from_sse calls :1260-1294 (quantiser ac_dequant_q3, bsize and bsize_uv).
+ *   walk     the second loop of perform_fast_loop (EbProductCodingLoop.c:1225-1363) over the combined list from the last entry down,
+ *            as svt_hip_fast_pick_frame states it.  Every candidate has distortion_ready 0 (only inject_intra_candidates_ois sets it),
+ *            so the first, src-to-src loop (:1180-1222) does nothing and stays out of scope.
+ *   order    sort_fast_loop_candidates (EbModeDecision.c:436-489) INCLUDING the "inter then intra" pass (:458-469).
+ * Quirks kept:
+ *   - lumaRate is summed in uint32 (:1251); fast_luma_rate / fast_chroma_rate (d_rate) are stored BEFORE the SSD model's rates are
+ *     added (:1257-1258); chromaRate is 0 for inter and under SSD the model's chroma rate is written over it (:1276-1283);
+ *   - merge_flag: skipModeFacBits[ctx][1] replaces the rate when it is strictly below it, in the SAD (:1310-1315) and the SSD branch
+ *     (:1288-1293); d_rate keeps the unreplaced values;
+ *   - the single-reference bits read ref_frame_type itself, the compound ones rf[] (:830-941); the single candidate's MV list is
+ *     "pred_direction == 0 ? 0 : 1" (:1175); the mode context of a candidate whose rf[1] is a frame goes through
+ *     compound_mode_ctx_map_2 whatever is_compound says (:960);
+ *   - has_uv enters no number: the reference reads it only to print a warning (:1301).  The chroma distortions are added when given;
+ *   - the :458-469 pass is no stable partition: for position i it swaps with the first later inter entry only while entry i is
+ *     intra, so [A, B, c] (capitals intra) becomes [c, B, A].  Inter entries keep their order (DESIGN.md 4.34 has the closed form);
+ *   - ref_fast_cost and the sorted array keep the by-buffer-index quirks stated for svt_hip_fast_pick_frame.
+ * Context bytes are device data and are clamped before they index (skip ctx to 2, is_inter_ctx to 3, reference_mode_context and
+ * compoud_reference_type_context to 4, the reference contexts to 2, newmv ctx to 5, refmv ctx to 5, the compound context to 7,
+ * pred_mode to 13 .. 24, ref_frame_type to 1 .. 28, drl contexts to 2, motion_mode to its table, MV differences to +-16383): an
+ * out-of-range byte gives an unspecified cost for its block and nothing else.  Costs at or above MAX_CU_COST are outside the domain,
+ * as for the intra pick.  Only the block index and the winners' list positions address memory from device data.
+ * Outputs, n = min(nfl, ninter + nintra), [nblocks][n] unless stated: d_cand (index into the combined list; >= ninter: intra), d_sorted
+ * (slots), d_cost, d_rate [..][2], d_ref_fast_cost [nblocks], optional d_all_cost [nblocks][ninter] (the inter candidates' costs),
+ * d_blk_out (the survivor's svt_hip_inter_blk; an intra slot gets the x / y of the block's first record, zero vectors, list 0,
+ * filter 0, so a prediction call over the array stays inside that call's contract), optional d_cand_out (the survivor's
+ * svt_hip_inter_cand, zeros in an intra slot), optional d_src_xy_out (x | y << 16 of the block's first record, repeated).
+ * Validation, every group before the first launch (SVT_HIP_ERR_INVALID, nothing launched): metric; bsize / bsize_uv 0 .. 21; ninter
+ * 1 .. 64, nintra 0 .. 63, their sum at most 64; nfl 1 .. 40; ac_dequant_q3 < 0; and for non-empty groups NULL d_blk / d_cand_in / d_ctx /
+ * d_rates / d_mv_cost / d_dist / d_cand / d_sorted / d_cost / d_rate / d_ref_fast_cost / d_blk_out, d_intra_cost NULL with nintra > 0,
+ * misalignment (the 8-byte arrays 8; d_blk, d_blk_out, d_cand_in, d_cand_out, d_ctx, d_rates, d_mv_cost, d_rate, d_intra_rate,
+ * d_src_xy_out 4), nblocks * ncand above 2^31 - 1.  One launch per non-empty group; enqueue only, graph-capturable, nothing zeroed by the caller.
+ *
+ * svt_hip_inter_fast_search_frame: the one-call form, host composition on `stream`: (1) svt_hip_inter_pred_frame distortion-only over
+ * the [nblocks][ninter] records on Y, and on Cb and Cr when use_chroma, into pick.d_dist* (d_scratch when NULL: per non-empty group
+ * in group order Y, Cb, Cr, nblocks * ninter * 8 bytes each rounded up to 16; svt_hip_inter_fast_search_scratch_bytes, HOST, returns
+ * the sum, 0 for bad parameters or nothing to carve); (2) the pick; (3) svt_hip_inter_pred_frame over pick.d_blk_out into the dense
+ * d_pred_out[p] [nblocks][n][h][w] (p = 0 required; 1, 2 optional with use_chroma), what svt_hip_full_loop_group.d_pred reads; (4) with
+ * d_intra_pred ([nblocks][nintra][H][W] luma samples of the call's depth) the intra survivors' luma slots are copied from it, ordered
+ * after (3).  Without d_intra_pred an intra slot holds the benign record's prediction: the caller owns those slots.  The [nblocks]
+ * [ninter][H][W] prediction array never exists.  bd 8 / 10 (the pick reads no samples); chroma follows svt_hip_inter_pred_frame's own
+ * check.  Every stage is validated before the first launch; a scratch that is NULL, misaligned or too small is refused. */
+typedef struct svt_hip_inter_cand {      /* sizeof 16: what only the cost reads of a candidate */
+    int16_t pred_mv[2][2];               /* [list][0 = x, 1 = y]: motion_vector_pred_x / _y, the units of svt_hip_inter_blk.mv */
+    int16_t mode_ctx;                    /* cu_ptr->inter_mode_ctx[ref_frame_type], raw */
+    uint8_t pred_mode;                   /* PredictionMode: NEARESTMV 13 .. NEW_NEWMV 24 */
+    uint8_t ref_frame_type;              /* 1 .. 28 */
+    uint8_t drl_index;
+    uint8_t ref_mv_count;                /* xd->ref_mv_count[ref_frame_type] */
+    uint8_t drl_ctx;                     /* av1_drl_ctx(ref_mv_stack, idx) << 2 * idx, idx 0 .. 2 */
+    uint8_t flags;                       /* merge_flag | motion_mode << 1 | motion_mode_allowed(...) << 3 (0 SIMPLE, 1 OBMC, 2 WARPED) */
+} svt_hip_inter_cand;
+typedef struct svt_hip_inter_fast_blk {  /* sizeof 16: the block's context bytes */
+    uint8_t skip_flag_context, is_inter_ctx, reference_mode_context, compoud_reference_type_context;
+    uint8_t comp_ref_p, comp_ref_p1, comp_ref_p2, comp_bwdref_p, comp_bwdref_p1;       /* av1_get_pred_context_* */
+    uint8_t single_ref_p[6];             /* av1_get_pred_context_single_ref_p1 .. _p6 */
+    uint8_t has_uv;
+} svt_hip_inter_fast_blk;
+typedef struct svt_hip_inter_fast_rates { /* the int32 tables of MdRateEstimationContext_s the inter fast cost reads */
+    int32_t skipModeFacBits[3][3];
+    int32_t newMvModeFacBits[6][3];
+    int32_t zeroMvModeFacBits[2][3];
+    int32_t refMvModeFacBits[6][3];
+    int32_t drlModeFacBits[3][3];
+    int32_t interCompoundModeFacBits[8][9];
+    int32_t singleRefFacBits[3][6][3];
+    int32_t compRefTypeFacBits[5][3];
+    int32_t compRefFacBits[3][3][3];
+    int32_t compBwdRefFacBits[3][2][3];
+    int32_t compInterFacBits[5][3];
+    int32_t motionModeFacBits[22][3];
+    int32_t motionModeFacBits1[22][2];
+    int32_t intraInterFacBits[4][2];
+    int32_t nmv_vec_cost[4];
+} svt_hip_inter_fast_rates;
+#define SVT_HIP_MV_VALS 32767            /* MV_VALS; the centre entry is MV_MAX = 16383 */
+typedef struct svt_hip_inter_fast_pick_group {
+    int32_t bsize, bsize_uv;             /* AV1 block_size order, 0 .. 21 */
+    uint32_t nblocks;
+    int32_t ninter, nintra;              /* per block: ninter inter candidates, then nintra intra candidates */
+    int32_t nfl;                         /* full_recon_search_count, 1 .. SVT_HIP_MAX_NFL */
+    uint32_t lambda;                     /* fast_lambda (SAD) / full_lambda (SSD) */
+    int16_t ac_dequant_q3;               /* y_dequant_Q3[qindex][1]; SSD only */
+    int32_t reference_mode_select;       /* reference_mode == REFERENCE_MODE_SELECT */
+    int32_t switchable_motion_mode;
+    const svt_hip_inter_blk *d_blk;      /* [nblocks][ninter] */
+    const svt_hip_inter_cand *d_cand_in; /* [nblocks][ninter] */
+    const svt_hip_inter_fast_blk *d_ctx; /* [nblocks] */
+    const svt_hip_inter_fast_rates *d_rates;
+    const int32_t *d_mv_cost;            /* [2][SVT_HIP_MV_VALS]: nmv_costs or nmv_costs_hp, whichever nmvcoststack points into */
+    const uint64_t *d_dist, *d_dist_cb, *d_dist_cr;                     /* [nblocks][ninter]; cb / cr optional */
+    const uint64_t *d_intra_cost;        /* [nblocks][nintra]; required when nintra > 0 */
+    const uint32_t *d_intra_rate;        /* optional [nblocks][nintra][2]; NULL: read as 0 */
+    uint8_t *d_cand, *d_sorted;          /* [nblocks][n] */
+    uint64_t *d_cost;                    /* [nblocks][n] */
+    uint32_t *d_rate;                    /* [nblocks][n][2] */
+    uint64_t *d_ref_fast_cost;           /* [nblocks] */
+    uint64_t *d_all_cost;                /* optional [nblocks][ninter] */
+    svt_hip_inter_blk *d_blk_out;        /* [nblocks][n] */
+    svt_hip_inter_cand *d_cand_out;      /* optional [nblocks][n] */
+    uint32_t *d_src_xy_out;              /* optional [nblocks][n] */
+} svt_hip_inter_fast_pick_group;
+int svt_hip_inter_fast_pick_frame(const svt_hip_inter_fast_pick_group *groups, int ngroups, int metric, void *stream);
+
+typedef struct svt_hip_inter_fast_search_group {
+    svt_hip_inter_fast_pick_group pick;  /* d_dist* may be NULL: scratch */
+    int32_t bwidth, bheight;             /* LUMA block size, as svt_hip_inter_pred_group */
+    int32_t use_chroma;                  /* non-zero: Cb and Cr distortions and (optionally) predictions */
+    const void *d_ref[2][3];             /* [list][Y, Cb, Cr], as svt_hip_inter_pred_group.d_ref */
+    uint32_t ref_stride[3];
+    const void *d_src[3];                /* source planes, sample (0, 0) of the picture */
+    uint32_t src_stride[3];
+    void *d_pred_out[3];                 /* dense [nblocks][n][h][w] per plane; [0] required, [1] / [2] optional with use_chroma */
+    const void *d_intra_pred;            /* optional [nblocks][nintra][H][W] luma */
+} svt_hip_inter_fast_search_group;
+size_t svt_hip_inter_fast_search_scratch_bytes(const svt_hip_inter_fast_search_group *groups, int ngroups);   /* HOST */
+int svt_hip_inter_fast_search_frame(const svt_hip_inter_fast_search_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height,
+                                    int bd, int metric, void *d_scratch, size_t scratch_bytes, void *stream);
 
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
