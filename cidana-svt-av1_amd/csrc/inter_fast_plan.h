@@ -1,7 +1,8 @@
-// inter_fast_plan.h — the inter fast search planned on the host: the argument check of svt_hip_inter_fast_pick_frame, the pick's blocks
-// per wave, and for svt_hip_inter_fast_search_frame ONE walk over its groups that sizes its scratch, carves it and derives the groups of
-// its stages (distortion-only prediction, pick, the survivors' prediction, the intra gather).  svt_hip_inter_fast.hip checks and plans
-// here, then enqueues.  Plain C++17, no HIP header: a CPU program can include it (tests/c/inter_fast_plan_host.cpp).
+// inter_fast_plan.h — the inter fast search planned on the host: the argument check of svt_hip_inter_fast_pick_frame (its counts and
+// blocks per wave are md_plan.h's fast_n, fast_nbuf, pick_bpw), and for svt_hip_inter_fast_search_frame ONE walk over its groups that
+// sizes its scratch, carves it and derives the groups of its stages (distortion-only prediction, pick, the survivors' prediction, the
+// intra gather).  svt_hip_inter_fast.hip checks and plans here, then enqueues.  Plain C++17, no HIP header: a CPU program can include
+// it (tests/c/inter_fast_plan_host.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -13,17 +14,12 @@
 
 namespace svthost {
 
-constexpr int kIfpMaxBpw = 4;                               // IFP_MAX_BPW (kernel_inter_fast_pick.h)
-// block_size_wide / block_size_high (EbDefinitions.h): the luma block of a bsize
-constexpr uint8_t kBsizeW[22] = {4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64, 128, 128, 4, 16, 8, 32, 16, 64};
-constexpr uint8_t kBsizeH[22] = {4, 8, 4, 8, 16, 8, 16, 32, 16, 32, 64, 32, 64, 128, 64, 128, 16, 4, 32, 8, 64, 16};
-
-inline int inter_fast_n(const svt_hip_inter_fast_pick_group& G) { const int nc = G.ninter + G.nintra; return G.nfl < nc ? G.nfl : nc; }
-
-// blocks per wave: one until every wave slot of the device (32 per CU) has a block, then up to kIfpMaxBpw
-inline int inter_fast_pick_bpw(uint32_t nblocks, int num_cu) {
-    const uint32_t slots = (uint32_t)(num_cu > 0 ? num_cu : 256) * 32u, b = nblocks / slots;
-    return b < 1 ? 1 : (b > (uint32_t)kIfpMaxBpw ? kIfpMaxBpw : (int)b);
+// the shape of a combined list, as the pick and the search both require it (empty groups included)
+inline int inter_fast_list_check(int g, int ninter, int nintra, int nfl) {
+    if (ninter < 1 || ninter > 64 || nintra < 0 || nintra > 63 || ninter + nintra > SVT_HIP_FAST_LOOP_MAX_CANDIDATES)
+        return set_err(SVT_HIP_ERR_INVALID, "group %d: ninter %d (1 .. 64), nintra %d (0 .. 63), together at most 64", g, ninter, nintra);
+    if (nfl < 1 || nfl > SVT_HIP_MAX_NFL) return set_err(SVT_HIP_ERR_INVALID, "group %d: nfl %d (1 .. %d)", g, nfl, SVT_HIP_MAX_NFL);
+    return SVT_HIP_OK;
 }
 
 // every group of a pick call before the first launch, empty groups' sizes and counts included
@@ -34,9 +30,7 @@ inline int inter_fast_pick_check(const svt_hip_inter_fast_pick_group* groups, in
         const svt_hip_inter_fast_pick_group& G = groups[g];
         if (G.bsize < 0 || G.bsize > 21 || G.bsize_uv < 0 || G.bsize_uv > 21)
             return set_err(SVT_HIP_ERR_INVALID, "group %d: bsize %d / bsize_uv %d (0 .. 21)", g, G.bsize, G.bsize_uv);
-        if (G.ninter < 1 || G.ninter > 64 || G.nintra < 0 || G.nintra > 63 || G.ninter + G.nintra > SVT_HIP_FAST_LOOP_MAX_CANDIDATES)
-            return set_err(SVT_HIP_ERR_INVALID, "group %d: ninter %d (1 .. 64), nintra %d (0 .. 63), together at most 64", g, G.ninter, G.nintra);
-        if (G.nfl < 1 || G.nfl > SVT_HIP_MAX_NFL) return set_err(SVT_HIP_ERR_INVALID, "group %d: nfl %d (1 .. %d)", g, G.nfl, SVT_HIP_MAX_NFL);
+        if (int rc = inter_fast_list_check(g, G.ninter, G.nintra, G.nfl)) return rc;
         if (G.ac_dequant_q3 < 0) return set_err(SVT_HIP_ERR_INVALID, "group %d: ac_dequant_q3 %d", g, G.ac_dequant_q3);
         if (G.nblocks == 0) continue;
         if (int rc = pairs_check(g, G.nblocks, (uint64_t)(G.ninter + G.nintra), "nblocks * ncand")) return rc;
@@ -72,9 +66,7 @@ inline int inter_fast_search_walk_bd(const svt_hip_inter_fast_search_group* grou
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_inter_fast_search_group& G = groups[g];
         svt_hip_inter_fast_pick_group P = G.pick;
-        if (P.ninter < 1 || P.ninter > 64 || P.nintra < 0 || P.nintra > 63 || P.ninter + P.nintra > SVT_HIP_FAST_LOOP_MAX_CANDIDATES)
-            return set_err(SVT_HIP_ERR_INVALID, "group %d: ninter %d (1 .. 64), nintra %d (0 .. 63), together at most 64", g, P.ninter, P.nintra);
-        if (P.nfl < 1 || P.nfl > SVT_HIP_MAX_NFL) return set_err(SVT_HIP_ERR_INVALID, "group %d: nfl %d (1 .. %d)", g, P.nfl, SVT_HIP_MAX_NFL);
+        if (int rc = inter_fast_list_check(g, P.ninter, P.nintra, P.nfl)) return rc;
         if (int rc = pairs_check(g, P.nblocks, (uint64_t)(P.ninter + P.nintra), "nblocks * ncand")) return rc;
         if (P.bsize < 0 || P.bsize > 21 || kBsizeW[P.bsize] != G.bwidth || kBsizeH[P.bsize] != G.bheight)
             return set_err(SVT_HIP_ERR_INVALID, "group %d: bsize %d is not the %d x %d block", g, P.bsize, G.bwidth, G.bheight);
@@ -90,7 +82,7 @@ inline int inter_fast_search_walk_bd(const svt_hip_inter_fast_search_group* grou
         P.d_dist = dy; P.d_dist_cb = dcb; P.d_dist_cr = dcr;
         st->pick.push_back(P);
         if (P.nblocks == 0) continue;
-        const int n = inter_fast_n(P);
+        const int n = fast_n(P.nfl, P.ninter + P.nintra);
         if (!G.d_pred_out[0]) return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL d_pred_out[0]", g);
         uint64_t* dists[3] = {dy, dcb, dcr};
         for (int p = 0; p < (G.use_chroma ? 3 : 1); p++) {

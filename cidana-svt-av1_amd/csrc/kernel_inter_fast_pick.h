@@ -1,17 +1,12 @@
 // kernel_inter_fast_pick.h — inter_pick_kernel: the end of the fast loop for the combined list of a P / B picture (ninter inter
 // candidates, then nintra intra candidates).  Per block: av1_inter_fast_cost (EbRateDistortionCost.c:971-1318, with
 // EstimateRefFramesNumBits :741-947 and Av1ModeContextAnalyzer :951-969) of every inter candidate, the intra candidates' costs as given,
-// the buffer walk of perform_fast_loop (EbProductCodingLoop.c:1225-1363), sort_fast_loop_candidates (EbModeDecision.c:436-489) with its
-// inter-before-intra pass, and the survivors' records.  It reads what inter_pred_kernel writes (dist) and writes what it reads (blk).
-//
-// One wave per block, bpw blocks per wave one after the other, IFP_WAVES waves per workgroup; the 383 words of rate tables are staged in
-// LDS once per workgroup (the only workgroup barrier).  The MV cost table (2 x 32767 words) stays in global memory: a candidate reads at
-// most four of its words.  Phases per block, fenced per wave:
+// the buffer walk and the sorted array (fast_walk, fast_sorted: kernel_fast_walk.h, which also states the mapping of a block to a
+// wave), the inter-before-intra pass of sort_fast_loop_candidates (EbModeDecision.c:458-469), and the survivors' records.  It reads
+// what inter_pred_kernel writes (dist) and writes what it reads (blk).  The 383 words of rate tables are staged in LDS; the MV cost
+// table (2 x 32767 words) stays in global memory: a candidate reads at most four of its words.  What is this kernel's own:
 //   cost     lane = candidate of the combined list.  Inter lanes: the two 16-byte records, the rates out of the LDS tables (every
-//            context byte clamped first), cost, luma rate -> the wave's LDS rows.  Intra lanes: d_intra_cost / d_intra_rate.  Then the
-//            candidate's RANK as in fast_pick_kernel: equal costs share a rank, 127 = MAX_CU_COST.
-//   walk     lane = buffer: fast_pick_kernel's walk, restated (kernel_fast_pick.h explains it; that kernel is left untouched, so the
-//            walk has a second statement here rather than a shared function).
+//            context byte clamped first), cost, luma rate -> the wave's LDS rows.  Intra lanes: d_intra_cost / d_intra_rate.
 //   order    positions 0 .. n-1 of best_candidate_index_array are the held buffers in buffer order.  The :458-469 pass is, with M the
 //            set of positions that hold an inter entry, K = |M| and p_k the k-th member of M: for k = 0 .. K-1 in order, exchange
 //            positions k and p_k (DESIGN.md 4.34 derives it).  So destination d < K takes the entry of p_d; d >= K outside M keeps its
@@ -19,15 +14,10 @@
 //            chain on the 64-bit mask alone (no cross-lane traffic, at most n short steps); the inverse map goes through one LDS row.
 //            The sorted array is bubble-swapped on BUFFER costs and does not see the pass.
 #pragma once
-#include "dev_common.h"
-#include "model_rd.h"
+#include "kernel_fast_walk.h"
 
 namespace svtdev {
 
-constexpr int IFP_THREADS = 256, IFP_WAVES = IFP_THREADS / 64;
-constexpr int IFP_MAX_BPW = 4;                             // blocks per wave, at most
-constexpr int IFP_EMPTY = 127;                             // the rank of MAX_CU_COST
-constexpr unsigned long long IFP_MAX_CU_COST = ~0ull >> 1, IFP_MAX_MODE_COST = 13616969489728ull * 8ull;
 constexpr int IFP_MV_MAX = 16383, IFP_MV_VALS = 2 * IFP_MV_MAX + 1;
 // svt_hip_inter_fast_rates as words
 constexpr int IFP_SKIP = 0, IFP_NEWMV = IFP_SKIP + 3 * 3, IFP_ZEROMV = IFP_NEWMV + 6 * 3, IFP_REFMV = IFP_ZEROMV + 2 * 3,
@@ -65,7 +55,7 @@ struct InterFastPickDev {
     uint8_t ninter, nintra, n, nbuf, ssd, bsize, nlog2_y, nlog2_uv;
     uint8_t comp_inter;                                    // reference_mode_select && min(bw, bh) >= 8
     uint8_t switchable_motion_mode;
-    uint8_t bpw;                                           // blocks per wave, 1 .. IFP_MAX_BPW
+    uint8_t bpw;                                           // blocks per wave, 1 .. FW_MAX_BPW
 };
 
 // av1_mv_bit_cost (:91-95) with MV_COST_WEIGHT 108; the differences clamped to the table
@@ -76,21 +66,19 @@ __device__ __forceinline__ uint32_t ifp_mv_bits(const int32_t* mv_cost, const in
     return (uint32_t)((c * 108 + 64) >> 7);
 }
 
-__global__ __launch_bounds__(IFP_THREADS) void inter_pick_kernel(const InterFastPickDev F) {
+__global__ __launch_bounds__(FW_THREADS) void inter_pick_kernel(const InterFastPickDev F) {
     __shared__ int32_t s_rates[IFP_RATE_WORDS];
-    __shared__ unsigned long long s_cost[IFP_WAVES][64];
-    __shared__ uint32_t s_lr[IFP_WAVES][64], s_cr[IFP_WAVES][64];
-    __shared__ uint8_t s_dest[IFP_WAVES][64];
-    for (int i = threadIdx.x; i < IFP_RATE_WORDS; i += IFP_THREADS) s_rates[i] = F.rates[i];
+    __shared__ unsigned long long s_cost[FW_WAVES][64];
+    __shared__ uint32_t s_lr[FW_WAVES][64], s_cr[FW_WAVES][64];
+    __shared__ uint8_t s_dest[FW_WAVES][64];
+    for (int i = threadIdx.x; i < IFP_RATE_WORDS; i += FW_THREADS) s_rates[i] = F.rates[i];
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ninter = F.ninter, ncand = F.ninter + F.nintra, n = F.n, nbuf = F.nbuf;
-    const bool scratch = nbuf > n;
-    const unsigned long long below = (1ull << lane) - 1ull;
 
 #pragma unroll 1
     for (int j = 0; j < F.bpw; j++) {
-        const uint32_t blk = (blockIdx.x * IFP_WAVES + (uint32_t)wave) * F.bpw + (uint32_t)j;
+        const uint32_t blk = (blockIdx.x * FW_WAVES + (uint32_t)wave) * F.bpw + (uint32_t)j;
         if (blk >= F.nblocks) break;                                             // wave-uniform
         wave_lds_fence();                                                        // the previous block's LDS reads before these writes
         // ---- cost: lane = candidate ----
@@ -198,16 +186,9 @@ __global__ __launch_bounds__(IFP_THREADS) void inter_pick_kernel(const InterFast
             unsigned long long chroma = 0;
             if (F.dist_cb) chroma += F.dist_cb[at];
             if (F.dist_cr) chroma += F.dist_cr[at];
-            uint32_t rate = lr;
-            unsigned long long d = luma + chroma;
-            if (F.ssd) {
-                uint32_t r1, r2;
-                unsigned long long d1, d2;
-                fp_model_rd(luma, F.nlog2_y, F.qstep, r1, d1);
-                fp_model_rd(chroma, F.nlog2_uv, F.qstep, r2, d2);
-                rate = lr + r1 + r2;
-                d = d1 + d2;
-            }
+            uint32_t rate;
+            unsigned long long d;
+            fast_cost_tail(F.ssd, luma, chroma, lr, 0u, F.nlog2_y, F.nlog2_uv, F.qstep, rate, d);
             unsigned long long r64 = rate;
             if (flags & 1u) {                                                    // merge_flag
                 const unsigned long long skip1 = (unsigned long long)(long long)s_rates[IFP_SKIP + skip_ctx * 3 + 1];
@@ -222,52 +203,11 @@ __global__ __launch_bounds__(IFP_THREADS) void inter_pick_kernel(const InterFast
         }
         s_cost[wave][lane] = cost; s_lr[wave][lane] = lr; s_cr[wave][lane] = cr; s_dest[wave][lane] = (uint8_t)lane;
         wave_lds_fence();
-        int rank = 0;
-#pragma unroll 8
-        for (int c = 0; c < ncand; c++) rank += s_cost[wave][c] < cost;
-
-        // ---- walk: lane = buffer (kernel_fast_pick.h) ----
-        int bcand = lane < nbuf ? ncand - 1 - lane : 0;
-        int brank = __shfl(rank, bcand, 64);
-        if (lane >= nbuf) brank = IFP_EMPTY;
-        int empty = 64;                                                          // the buffer emptied at :1361
-        if (scratch) {
-            unsigned long long bits = lane < nbuf ? 1ull << brank : 0ull;
-#pragma unroll
-            for (int x = 32; x >= 1; x >>= 1) {
-                const uint32_t lo = __shfl_xor((uint32_t)bits, x, 64), hw = __shfl_xor((uint32_t)(bits >> 32), x, 64);
-                bits |= ((unsigned long long)hw << 32) | lo;
-            }
-            unsigned long long held_ranks = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(bits >> 32)) << 32) |
-                                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)bits);
-#pragma unroll 1
-            for (int c = ncand - nbuf - 1;; c--) {
-                const int top = 63 - __builtin_clzll(held_ranks);
-                const unsigned long long eq = __ballot(brank == top);            // (lanes from nbuf up hold IFP_EMPTY)
-                const int hi = __builtin_ctzll(eq);
-                if (c < 0) {
-                    if (lane == hi) brank = IFP_EMPTY;                           // :1361
-                    empty = hi;
-                    break;
-                }
-                const int rc = __builtin_amdgcn_readlane(rank, c);
-                if ((eq & (eq - 1ull)) == 0) held_ranks &= ~(1ull << top);       // the only buffer of that rank is overwritten
-                held_ranks |= 1ull << rc;
-                if (lane == hi) { brank = rc; bcand = c; }
-            }
-        }
-        const bool held = lane < nbuf && brank != IFP_EMPTY;
+        // ---- walk: lane = buffer ----
+        const FastWalk w = fast_walk(s_cost[wave], cost, ncand, n, nbuf, lane, F.ref_fast_cost + blk);
+        const bool held = w.held;
+        const int bcand = w.bcand, empty = w.empty;
         const int pos = lane - (lane > empty ? 1 : 0);                           // best_candidate_index_array: the empty buffer goes last
-        const unsigned long long bcost = s_cost[wave][bcand];
-        // ref_fast_cost: buffers 0 .. n-1 by buffer index
-        unsigned long long ref = lane < n ? (brank == IFP_EMPTY ? IFP_MAX_CU_COST : bcost) : ~0ull;
-#pragma unroll
-        for (int x = 32; x >= 1; x >>= 1) {
-            const uint32_t lo = __shfl_xor((uint32_t)ref, x, 64), hw = __shfl_xor((uint32_t)(ref >> 32), x, 64);
-            const unsigned long long o = ((unsigned long long)hw << 32) | lo;
-            ref = o < ref ? o : ref;
-        }
-        if (lane == 0) F.ref_fast_cost[blk] = ref < IFP_MAX_MODE_COST ? ref : IFP_MAX_MODE_COST;
         // ---- order: the inter-before-intra pass over positions 0 .. n-1 ----
         const unsigned long long inter_lanes = __ballot(held && bcand < ninter);
         // the mask by position: the emptied buffer's bit (clear) taken out
@@ -282,25 +222,13 @@ __global__ __launch_bounds__(IFP_THREADS) void inter_pick_kernel(const InterFast
         wave_lds_fence();
         int slot = pos;
         if (held) slot = bcand < ninter ? __popcll(M & ((1ull << pos) - 1ull)) : s_dest[wave][pos];
-        // sorted_candidate_index_array, as slots: position i starts as slot i
-        int sval = lane;
-#pragma unroll 1
-        for (int i = 0; i + 1 < n; i++) {
-            const int ri = __builtin_amdgcn_readlane(brank, i);
-            const bool in_j = lane > i && lane < n && brank < ri;
-            const unsigned long long J = __ballot(in_j);
-            if (J) {
-                const unsigned long long jb = J & below;
-                const int from = in_j ? (jb ? 63 - __builtin_clzll(jb) : i) : (lane == i ? 63 - __builtin_clzll(J) : lane);
-                sval = __shfl(sval, from, 64);
-            }
-        }
+        const int sval = fast_sorted(w.brank, n, lane);
         const size_t row = (size_t)blk * n;
         const uint32_t xy = F.blk[(size_t)blk * ninter * 4];                      // x | y << 16 of the block's first record
         if (held && slot < n) {
             const size_t o = row + slot;
             F.cand_out[o] = (uint8_t)bcand;
-            F.cost[o] = bcost;
+            F.cost[o] = w.bcost;
             F.rate[2 * o] = s_lr[wave][bcand];
             F.rate[2 * o + 1] = s_cr[wave][bcand];
             ifp_rec rec = {xy, 0u, 0u, 0u}, crec = {0u, 0u, 0u, 0u};             // an intra slot: zero vectors, list 0, filter 0

@@ -17,6 +17,8 @@ namespace svthost {
 // ---- sizes ------------------------------------------------------------------------------------------------------------------------
 extern const int kTxW[SVT_TX_SIZES_ALL], kTxH[SVT_TX_SIZES_ALL];      // host_tables.cpp
 bool txfm_allowed(int tx_size, int tx_type);                           // host_tables.cpp
+// of a block size 0 .. 21: size_group_lookup, num_pels_log2_lookup, block_size_wide, block_size_high (host_tables.cpp)
+extern const uint8_t kSizeGroup[22], kNumPelsLog2[22], kBsizeW[22], kBsizeH[22];
 inline int log2_of(int v) { int l = 0; while ((1 << l) < v) l++; return l; }
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 // a side as the coefficient arrays hold it (a 64-sample side packs to 32), and the coefficients of a block: min(W,32) * min(H,32)
@@ -25,6 +27,16 @@ inline int coeffs_of(int tx_size) { return packed_side(kTxW[tx_size]) * packed_s
 // the quantiser's log_scale of a transform size (av1_get_tx_scale): 1 above 256 pixels, 2 above 1024
 inline int tx_log_scale(int tx_size) { const int pels = kTxW[tx_size] * kTxH[tx_size]; return pels > 1024 ? 2 : (pels > 256 ? 1 : 0); }
 constexpr int kCflCands = 2 * SVT_HIP_CFL_NALPHA;      // per block: two planes of SVT_HIP_CFL_NALPHA
+// the end of the fast loop (fast pick, inter fast pick): the survivors of a list of ncand, the buffers the walk uses for them (one more
+// as a scratch when the list is longer), and the blocks a wave takes: one until every wave slot of the device (32 per CU; 256 CUs when
+// no device is known) has a block, then up to kPickMaxBpw, which spreads the staging of the rate tables over more blocks
+constexpr int kPickMaxBpw = 4;                         // FW_MAX_BPW (kernel_fast_walk.h)
+inline int fast_n(int nfl, int ncand) { return nfl < ncand ? nfl : ncand; }
+inline int fast_nbuf(int n, int ncand) { return ncand > n ? n + 1 : n; }
+inline int pick_bpw(uint32_t nblocks, int num_cu) {
+    const uint32_t slots = (uint32_t)(num_cu > 0 ? num_cu : 256) * 32u, b = nblocks / slots;
+    return b < 1 ? 1 : (b > (uint32_t)kPickMaxBpw ? kPickMaxBpw : (int)b);
+}
 inline svtdev::QParams make_qparams(const svt_hip_qrows& q, int log_scale) { return svtdev::make_qparams(q.zbin, q.round, q.quant, q.quant_shift, q.dequant, log_scale); }
 
 // ---- the clauses the checks share ---------------------------------------------------------------------------------------------------

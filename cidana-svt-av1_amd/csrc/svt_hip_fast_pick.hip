@@ -1,8 +1,8 @@
 // svt_hip_fast_pick.hip — svt_hip_fast_pick_frame: fast cost, the N best and their order per block, the survivors' predictions gathered
 // (fast_pick_kernel, kernel_fast_pick.h), one launch per non-empty group; svt_hip_intra_fast_search_frame, the whole intra fast search
 // as host composition: fast loop (luma, Cb, Cr) -> pick on one stream, the arrays the caller does not keep in a scratch.
-// What is left here: the pick's blocks per wave, kernel arguments and launches (fast_pick_enqueue) and the entry points; the checks, the
-// scratch layout and the stages' groups are md_plan.h's.
+// What is left here: the pick's kernel arguments and launches (fast_pick_enqueue) and the entry points; the checks, the scratch layout,
+// the stages' groups and the pick's counts (fast_n, fast_nbuf, pick_bpw) are md_plan.h's.
 #include "host_common.h"
 #include "kernel_fast_pick.h"
 
@@ -15,17 +15,7 @@ static_assert(offsetof(svt_hip_fast_rates, mbModeFacBits) == FP_MB * 4 && offset
               offsetof(svt_hip_fast_rates, angleDeltaFacBits) == FP_ANG * 4 && offsetof(svt_hip_fast_rates, skipModeFacBits) == FP_SKIP * 4 &&
               offsetof(svt_hip_fast_rates, intraInterFacBits) == FP_II * 4, "svt_hip_fast_rates layout");
 static_assert(sizeof(FastPickDev) <= 4000, "kernel arguments");
-
-// size_group_lookup / num_pels_log2_lookup (EbDefinitions.h:1311, 1315)
-static const uint8_t kSizeGroup[22] = {0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3, 3, 3, 3, 0, 0, 1, 1, 2, 2};
-static const uint8_t kNumPelsLog2[22] = {4, 5, 5, 6, 7, 7, 8, 9, 9, 10, 11, 11, 12, 13, 13, 14, 6, 6, 8, 8, 10, 10};
-
-// blocks per wave: one until every wave slot of the device (32 per CU) has a block, then up to FP_MAX_BPW, which spreads the staging of the
-// rate tables over more blocks
-static int fast_pick_bpw(uint32_t nblocks) {
-    const uint32_t slots = (uint32_t)(g_num_cu > 0 ? g_num_cu : 256) * 32u, b = nblocks / slots;
-    return b < 1 ? 1 : (b > (uint32_t)FP_MAX_BPW ? FP_MAX_BPW : (int)b);
-}
+static_assert(kPickMaxBpw == FW_MAX_BPW, "md_plan.h / kernel_fast_walk.h: both pick kernels take pick_bpw's blocks per wave");
 
 static int fast_pick_enqueue(const svt_hip_fast_pick_group* groups, int ngroups, int metric, hipStream_t s) {
     for (int g = 0; g < ngroups; g++) {
@@ -44,15 +34,15 @@ static int fast_pick_enqueue(const svt_hip_fast_pick_group* groups, int ngroups,
             const int um = G.uv_modes[c] == 13 ? 0 : G.uv_modes[c];              // UV_CFL_PRED is costed as UV_DC_PRED
             D.cand[c] = (uint16_t)(G.modes[c] | ((G.angle_deltas[c] + 3) << 4) | (um << 8) | ((G.uv_angle_deltas[c] + 3) << 12));
         }
-        const int n = G.nfl < G.ncand ? G.nfl : G.ncand;
-        D.ncand = (uint8_t)G.ncand; D.n = (uint8_t)n; D.nbuf = (uint8_t)(G.ncand > n ? n + 1 : n);
+        const int n = fast_n(G.nfl, G.ncand);
+        D.ncand = (uint8_t)G.ncand; D.n = (uint8_t)n; D.nbuf = (uint8_t)fast_nbuf(n, G.ncand);
         D.ssd = metric == SVT_HIP_FAST_SSD; D.slice_is_intra = G.slice_is_intra != 0; D.use_angle_delta = G.use_angle_delta != 0;
         D.cfl_allowed = w <= 32 && h <= 32; D.size_group = kSizeGroup[G.bsize];
         D.nlog2_y = kNumPelsLog2[G.bsize]; D.nlog2_uv = kNumPelsLog2[G.bsize_uv];
         D.ql = (uint8_t)(log2_of(w * h) - 4);
-        D.bpw = (uint8_t)fast_pick_bpw(G.nblocks);
-        const uint32_t per_wg = (uint32_t)(FP_WAVES * D.bpw), wgs = (G.nblocks + per_wg - 1) / per_wg;
-        hipLaunchKernelGGL(fast_pick_kernel, dim3(wgs), dim3(FP_THREADS), 0, s, D);
+        D.bpw = (uint8_t)pick_bpw(G.nblocks, g_num_cu);
+        const uint32_t per_wg = (uint32_t)(FW_WAVES * D.bpw), wgs = (G.nblocks + per_wg - 1) / per_wg;
+        hipLaunchKernelGGL(fast_pick_kernel, dim3(wgs), dim3(FW_THREADS), 0, s, D);
         if (int rc = launch_status("fast_pick")) return rc;
     }
     return SVT_HIP_OK;

@@ -26,11 +26,8 @@ static_assert(offsetof(svt_hip_inter_fast_rates, newMvModeFacBits) == IFP_NEWMV 
               offsetof(svt_hip_inter_fast_rates, motionModeFacBits) == IFP_MM * 4 && offsetof(svt_hip_inter_fast_rates, motionModeFacBits1) == IFP_MM1 * 4 &&
               offsetof(svt_hip_inter_fast_rates, intraInterFacBits) == IFP_II * 4 && offsetof(svt_hip_inter_fast_rates, nmv_vec_cost) == IFP_JOINT * 4,
               "svt_hip_inter_fast_rates layout");
-static_assert(SVT_HIP_MV_VALS == IFP_MV_VALS && kIfpMaxBpw == IFP_MAX_BPW, "svt_hip_dsp.h / inter_fast_plan.h");
+static_assert(SVT_HIP_MV_VALS == IFP_MV_VALS, "svt_hip_dsp.h");
 static_assert(sizeof(InterFastPickDev) <= 4000, "kernel arguments");
-
-// num_pels_log2_lookup (EbDefinitions.h:1315)
-static const uint8_t kNumPelsLog2[22] = {4, 5, 5, 6, 7, 7, 8, 9, 9, 10, 11, 11, 12, 13, 13, 14, 6, 6, 8, 8, 10, 10};
 
 static int inter_fast_pick_enqueue(const svt_hip_inter_fast_pick_group* groups, int ngroups, int metric, hipStream_t s) {
     for (int g = 0; g < ngroups; g++) {
@@ -46,15 +43,15 @@ static int inter_fast_pick_enqueue(const svt_hip_inter_fast_pick_group* groups, 
         D.ref_fast_cost = (unsigned long long*)G.d_ref_fast_cost; D.all_cost = (unsigned long long*)G.d_all_cost;
         D.blk_out = (uint32_t*)G.d_blk_out; D.cand_rec_out = (uint32_t*)G.d_cand_out; D.src_xy_out = G.d_src_xy_out;
         D.nblocks = G.nblocks; D.lambda = G.lambda; D.qstep = (uint32_t)(G.ac_dequant_q3 >> 3);
-        const int n = inter_fast_n(G), ncand = G.ninter + G.nintra;
-        D.ninter = (uint8_t)G.ninter; D.nintra = (uint8_t)G.nintra; D.n = (uint8_t)n; D.nbuf = (uint8_t)(ncand > n ? n + 1 : n);
+        const int ncand = G.ninter + G.nintra, n = fast_n(G.nfl, ncand);
+        D.ninter = (uint8_t)G.ninter; D.nintra = (uint8_t)G.nintra; D.n = (uint8_t)n; D.nbuf = (uint8_t)fast_nbuf(n, ncand);
         D.ssd = metric == SVT_HIP_FAST_SSD; D.bsize = (uint8_t)G.bsize;
         D.nlog2_y = kNumPelsLog2[G.bsize]; D.nlog2_uv = kNumPelsLog2[G.bsize_uv];
         D.comp_inter = G.reference_mode_select != 0 && (kBsizeW[G.bsize] < kBsizeH[G.bsize] ? kBsizeW[G.bsize] : kBsizeH[G.bsize]) >= 8;
         D.switchable_motion_mode = G.switchable_motion_mode != 0;
-        D.bpw = (uint8_t)inter_fast_pick_bpw(G.nblocks, g_num_cu);
-        const uint32_t per_wg = (uint32_t)(IFP_WAVES * D.bpw), wgs = (G.nblocks + per_wg - 1) / per_wg;
-        hipLaunchKernelGGL(inter_pick_kernel, dim3(wgs), dim3(IFP_THREADS), 0, s, D);
+        D.bpw = (uint8_t)pick_bpw(G.nblocks, g_num_cu);
+        const uint32_t per_wg = (uint32_t)(FW_WAVES * D.bpw), wgs = (G.nblocks + per_wg - 1) / per_wg;
+        hipLaunchKernelGGL(inter_pick_kernel, dim3(wgs), dim3(FW_THREADS), 0, s, D);
         if (int rc = launch_status("inter_fast_pick")) return rc;
     }
     return SVT_HIP_OK;

@@ -634,6 +634,16 @@ int main() {
     CHECK(kTxW[SVT_TX_64X64] == 64 && kTxH[SVT_TX_4X16] == 16 && kTxW[SVT_TX_16X4] == 16 && coeffs_of(SVT_TX_64X64) == 1024 && coeffs_of(SVT_TX_16X64) == 512);
     CHECK(!txfm_allowed(-1, 0) && !txfm_allowed(SVT_TX_SIZES_ALL, 0));
     CHECK(align16(0) == 0 && align16(1) == 16 && align16(16) == 16 && align16(17) == 32 && log2_of(1) == 0 && log2_of(1024) == 10);
+    // ---- the end of the fast loop: survivors, buffers, blocks per wave ----
+    CHECK(fast_n(3, 8) == 3 && fast_n(40, 64) == 40 && fast_n(2, 64) == 2 && fast_n(12, 3) == 3);
+    CHECK(fast_nbuf(3, 8) == 4 && fast_nbuf(40, 64) == 41 && fast_nbuf(3, 3) == 3 && fast_nbuf(1, 1) == 1 && fast_nbuf(1, 2) == 2);
+    // 256 compute units hold 8192 waves: one block a wave up to 16383 blocks, then nblocks / 8192, at most four
+    CHECK(pick_bpw(1, 256) == 1 && pick_bpw(8192, 256) == 1 && pick_bpw(16383, 256) == 1);
+    CHECK(pick_bpw(16384, 256) == 2 && pick_bpw(24575, 256) == 2 && pick_bpw(24576, 256) == 3);
+    CHECK(pick_bpw(32768, 256) == 4 && pick_bpw(1u << 30, 256) == kPickMaxBpw);
+    CHECK(pick_bpw(64, 1) == 2 && pick_bpw(63, 1) == 1);
+    CHECK(pick_bpw(16384, 0) == 2 && pick_bpw(16384, -1) == 2);                  // no device known: 256 units
+    for (int b = 0; b < 22; b++) CHECK((1 << kNumPelsLog2[b]) == kBsizeW[b] * kBsizeH[b] && kSizeGroup[b] <= 3);
     {                                                             // the carver: in order, rounded up, NULL without a base
         alignas(16) char buf[64];
         Carver c{buf}, z{nullptr};

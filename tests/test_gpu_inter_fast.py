@@ -153,7 +153,7 @@ def test_pick_one_group_per_call(dsp, nb):
 
 
 def test_pick_groups_large_enough_for_several_blocks_per_wave(dsp):
-    """the plan (inter_fast_pick_bpw, tests/c/inter_fast_plan_host.cpp) gives a wave 2 and 4 blocks once a group has that many times the
+    """the plan (pick_bpw of csrc/md_plan.h, tests/c/md_plan_host.cpp) gives a wave 2 and 4 blocks once a group has that many times the
     device's wave slots (32 per CU): a mixed (5, 3, 3) and a (3, 9, 4) group of the fixture repeated to just above those counts, cost only"""
     slots = torch.cuda.get_device_properties(0).multi_processor_count * 32
     groups, wants = [], []

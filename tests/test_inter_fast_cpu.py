@@ -273,8 +273,8 @@ def test_ctypes_mirrors_match_sizeof(tmp_path):
     import __graft_entry__ as ge
     pkg = ge.load_package()
     exe = str(tmp_path / "inter_fast_plan_host")
-    pr = subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "c", "inter_fast_plan_host.cpp"), os.path.join(PKG, "csrc", "host_err.cpp"),
-                         "-o", exe], capture_output=True, text=True)
+    pr = subprocess.run(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "c", "inter_fast_plan_host.cpp"), os.path.join(PKG, "csrc", "host_tables.cpp"),
+                         os.path.join(PKG, "csrc", "host_err.cpp"), "-o", exe], capture_output=True, text=True)
     assert pr.returncode == 0, pr.stderr[-4000:]
     out = subprocess.run([exe, "sizes"], capture_output=True, text=True, timeout=60)
     assert out.returncode == 0

@@ -13,11 +13,12 @@ PKG = os.path.join(ROOT, "cidana-svt-av1_amd")
 def test_inter_fast_plan(tmp_path, san_flags):
     """every clause of inter_fast_pick_check and of the search's plan refuses its one changed field (counts, nfl, bsize, NULL and
     misaligned members, d_intra_cost with nintra > 0, the 31-bit bound, bd, scratch) and accepts the neighbour of each bound; the scratch
-    size and carving and the four stages' groups of a mixed list against hand-computed values; the blocks-per-wave choice"""
+    size and carving and the four stages' groups of a mixed list against hand-computed values (the blocks-per-wave choice is
+    md_plan.h's and is checked with it, tests/c/md_plan_host.cpp)"""
     exe = str(tmp_path / "inter_fast_plan_host")
     pr = subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-Werror"] + san_flags +
-                        [os.path.join(ROOT, "tests", "c", "inter_fast_plan_host.cpp"), os.path.join(PKG, "csrc", "host_err.cpp"), "-o", exe],
-                        capture_output=True, text=True)
+                        [os.path.join(ROOT, "tests", "c", "inter_fast_plan_host.cpp"), os.path.join(PKG, "csrc", "host_tables.cpp"),
+                         os.path.join(PKG, "csrc", "host_err.cpp"), "-o", exe], capture_output=True, text=True)
     assert pr.returncode == 0, pr.stderr[-4000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", UBSAN_OPTIONS="print_stacktrace=1")
     out = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)

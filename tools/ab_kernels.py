@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """A/B of two builds of the library on the same box, interleaved: tools/ab/lib_a.so against tools/ab/lib_b.so (tools/make_ab_lib.sh).
-usage: ab_kernels.py <workload> [<workload> ...]      workloads: enc8 enc16 enc32 enc64 inv8 inv16 inv32 fq8 fq16 fwd8 fwd16 (dense 8-bit batches),
+usage: ab_kernels.py [--out=FILE.json] <workload> [<workload> ...]      workloads: enc8 enc16 enc32 enc64 inv8 inv16 inv32 fq8 fq16 fwd8 fwd16 (dense 8-bit batches),
        fqp8 fqp16 (fwd_quant_planes on a 8192x4096 plane; fqp32h: a 10-bit plane), encp32 encp32h (encode_recon_planes, 8- / 10-bit plane), fl8 fl16 fl32 fl64 (full_loop, dense, AVX2 flavour, DCT_DCT) and fl8x16 fl16x16
        (every allowed type), c4 (one 1080p frame, five sizes, svt_hip_encode_recon_frame), ois8 ois16 (open-loop intra search of a 1080p
-       picture), bip, me85 me209
-Prints per workload the minimum and median of 6 interleaved rounds per library and whether the two libraries' outputs are equal."""
+       picture), bip, me85 me209, fpick ifpick (svt_hip_fast_pick_frame with gather on 61 candidates, svt_hip_inter_fast_pick_frame on 48 inter
+       candidates: the 8x8 blocks of a 1080p picture, nfl 12)
+Prints per workload the minimum and median of 6 interleaved rounds per library, the spread of a's own rounds (minimum to median) and
+whether b's median lies within it of a's, and whether the two libraries' outputs are equal; --out also writes the rows to a file."""
 import json
 import os
 import sys
@@ -161,6 +163,46 @@ def workload(name, d):
         blk[:, 4] = 16; blk[:, 5] = 16; blk[:, 6] = 16; blk[:, 7] = 16
         out = torch.empty((n, 16, 16), dtype=torch.uint8, device=dev)
         return (lambda: d.build_intra_predictors(top, left, blk, 2, dst=out, dst_stride=16)), n, 330
+    if name in ("fpick", "ifpick"):      # the two kernels that end the fast loop, on the 8x8 blocks of a 1080p picture, nfl 12, SAD
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        import bench_fast_pick as bf
+        rng = np.random.default_rng(17031)
+        D = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        E = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+        nb_x, nb_y, nfl = bf.PIC_W // 8, (bf.PIC_H + 7) // 8, 12
+        n = nb_x * nb_y
+        sad = lambda shape: D(rng.integers(0, 64 * 256, shape).astype(np.int64))
+        outs = dict(cand=E((n, nfl), torch.uint8), sorted=E((n, nfl), torch.uint8), cost=E((n, nfl), torch.int64), rate=E((n, nfl, 2), torch.int32),
+                    ref_fast_cost=E((n,), torch.int64))
+        if name == "fpick":              # svt_hip_fast_pick_frame: tools/bench_fast_pick.py's 61-candidate list, tables and context records; with gather
+            modes, deltas = bf.candidate_list()
+            C = len(modes)
+            bsize, bsize_uv = bf.mg.bsizes_of_tx(1)
+            pblk = np.zeros(n, bf.mg.BLK_DTYPE)
+            pblk["top_mode"], pblk["left_mode"], pblk["has_chroma"] = rng.integers(0, 13, n), rng.integers(0, 13, n), 1
+            xy = (np.arange(n, dtype=np.uint32) % nb_x * 8 | (np.arange(n, dtype=np.uint32) // nb_x * 8) << 16).view(np.int32)
+            outs.update(pred_out=E((n, nfl, 8, 8), torch.uint8), src_xy_out=E((n, nfl), torch.int32))
+            g_ = dict(outs, tx_size=1, bsize=bsize, bsize_uv=bsize_uv, nblocks=n, modes=modes, deltas=deltas, uv_modes=[0] * C, uv_deltas=[0] * C,
+                      use_angle_delta=1, nfl=nfl, slice_is_intra=1, blk=D(pblk.view(np.uint8).reshape(-1, 8)), rates=D(bf.mg.make_rates("rand", rng)),
+                      dist=sad((n, C)), pred=D(rng.integers(0, 256, (n, C, 8, 8), dtype=np.uint8)), src_xy=D(xy))
+            g_["lambda"] = bf.LAMBDA
+            arr, call, bpu = d.make_fast_pick_groups([g_]), d.fast_pick_frame, C * 8 + 8 + 2 * nfl * 64 + nfl * 22 + 8
+        else:                            # svt_hip_inter_fast_pick_frame: tools/bench_inter_fast_search.py's records and tables, 48 inter candidates
+            import bench_inter_fast_search as bi
+            ni = 48
+            blk, cand, ctx = bi.make_records(rng, 8, nb_x, nb_y, ni)
+            outs.update(blk_out=E((n, nfl, 16), torch.uint8))
+            g_ = dict(outs, bsize=3, bsize_uv=0, ninter=ni, nintra=0, nfl=nfl, ac_dequant_q3=0, reference_mode_select=1, switchable_motion_mode=1, nblocks=n,
+                      blk=D(blk.view(np.uint8).reshape(n, ni, 16)), cand_in=D(cand.view(np.uint8).reshape(n, ni, 16)), ctx=D(ctx.view(np.uint8).reshape(n, 16)),
+                      rates=D(bi.mg.pack_rates(bi.mg.make_rates(0))), mv_cost=D(bi.mg.make_mv_cost()), dist=sad((n, ni)), dist_cb=sad((n, ni)), dist_cr=sad((n, ni)))
+            g_["lambda"] = bi.LAMBDA
+            arr, call, bpu = d.make_inter_fast_pick_groups([g_]), d.inter_fast_pick_frame, ni * 56 + 16 + nfl * 34 + 8
+
+        def run(keep=(g_, arr)):         # (the group array points into the tensors)
+            assert call(arr, 0) == 0, d.lib.svt_hip_last_error()
+        # every output weighted by position: a survivor in another slot changes the digest
+        weighted = lambda t: (t.reshape(-1).to(torch.int64) * (torch.arange(t.numel(), device=dev) % 65521 + 1)).sum()
+        return run, n, bpu, (lambda: [weighted(outs[k]) for k in sorted(outs)]), 2000
     if name in ("me85", "me209"):
         n = 2040
         src = torch.randint(0, 256, (n, 64, 64), dtype=torch.uint8, device=dev, generator=g); ref = torch.randint(0, 256, (n, 127, 128), dtype=torch.uint8, device=dev, generator=g)
@@ -170,24 +212,33 @@ def workload(name, d):
 
 def main():
     libs = {t: load(t) for t in ("a", "b")}
-    for name in sys.argv[1:]:
+    out = [a[6:] for a in sys.argv[1:] if a.startswith("--out=")]
+    rows = []
+    for name in [a for a in sys.argv[1:] if not a.startswith("--out=")]:
         fns, outs = {}, {}
         for t in ("a", "b"):
             w = workload(name, libs[t])
             fns[t], units, bpu = w[:3]
+            iters = w[4] if len(w) > 4 else 8        # calls per timed window: a workload of a fraction of a millisecond asks for more
             r = fns[t]()
             outs[t] = digest(w[3]() if len(w) > 3 else r)
         times = {"a": [], "b": []}
         for rnd in range(6):
             for t in ("a", "b"):
-                times[t].append(timeit(fns[t]))
-        row = {"workload": name, "units": units, "equal_outputs": outs["a"] == outs["b"]}
+                times[t].append(timeit(fns[t], iters))
+        row = {"workload": name, "units": units, "calls_per_window": iters, "equal_outputs": outs["a"] == outs["b"]}
         for t in ("a", "b"):
             v = sorted(times[t])
             med = (v[2] + v[3]) / 2
-            row[t] = {"ms_min": round(v[0], 4), "ms_med": round(med, 4), "frac_hbm_at_med": round(bpu * units / med / 1e6 / 8000, 4)}
+            row[t] = {"ms_min": round(v[0], 5), "ms_med": round(med, 5), "frac_hbm_at_med": round(bpu * units / med / 1e6 / 8000, 4)}
         row["b_over_a_speed"] = round(row["a"]["ms_med"] / row["b"]["ms_med"], 4)
+        # what a's own rounds differ by, minimum to median, and whether b's median is within that of a's
+        row["a_spread_min_to_med_ms"] = round(row["a"]["ms_med"] - row["a"]["ms_min"], 5)
+        row["b_med_within_a_spread"] = bool(row["b"]["ms_med"] <= row["a"]["ms_med"] + row["a_spread_min_to_med_ms"])
+        rows.append(row)
         print(json.dumps(row), flush=True)
+    if out:
+        json.dump(dict(device=torch.cuda.get_device_name(0), rounds=6, rows=rows), open(out[0], "w"), indent=1)
 
 
 if __name__ == "__main__":
