@@ -211,6 +211,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_inter_fast_search_scratch_bytes.restype = c_size_t
     L.svt_hip_inter_fast_search_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p, c_size_t, c_void_p]
     L.svt_hip_inter_fast_search_frame.restype = c_int
+    L.svt_hip_md_decide_frame.argtypes = [c_void_p, c_int, c_void_p]
+    L.svt_hip_md_decide_frame.restype = c_int
+    L.svt_hip_md_search_scratch_bytes.argtypes = [c_void_p, c_int]
+    L.svt_hip_md_search_scratch_bytes.restype = c_size_t
+    L.svt_hip_md_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_md_search_frame.restype = c_int
     return L
 
 
@@ -394,6 +400,80 @@ class InterFastSearchGroup(ctypes.Structure):
     _fields_ = [("pick", InterFastPickGroup), ("bwidth", c_int32), ("bheight", c_int32), ("use_chroma", c_int32), ("d_ref", (c_void_p * 3) * 2),
                 ("ref_stride", c_uint32 * 3), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3), ("d_pred_out", c_void_p * 3),
                 ("d_intra_pred", c_void_p)]
+
+
+class MdBlk(ctypes.Structure):
+    """svt_hip_md_blk: the block's bytes the full cost reads (4 bytes; md_blk_dtype() is its numpy twin)"""
+    _fields_ = [("skip_flag_context", ctypes.c_uint8), ("has_uv", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2)]
+
+
+MD_RATE_TABLES = (("skipModeFacBits", (3, 3)), ("intraUVmodeFacBits", (2, 13, 15)), ("cflAlphaFacBits", (8, 2, 16)))      # svt_hip_md_rates
+MD_RATE_WORDS = 655
+MD_NO_INTRA = 0xFF
+
+
+class MdRates(ctypes.Structure):
+    """svt_hip_md_rates"""
+    _fields_ = [("skipModeFacBits", (c_int32 * 3) * 3), ("intraUVmodeFacBits", ((c_int32 * 15) * 13) * 2), ("cflAlphaFacBits", ((c_int32 * 16) * 2) * 8)]
+
+
+class MdDecision(ctypes.Structure):
+    """svt_hip_md_decision (72 bytes; md_decision_dtype() is its numpy twin)"""
+    _fields_ = [("cost", ctypes.c_uint64), ("cost_luma", ctypes.c_uint64), ("merge_cost", ctypes.c_uint64), ("skip_cost", ctypes.c_uint64),
+                ("full_lambda_rate", ctypes.c_uint64), ("full_distortion", c_uint32), ("eob", ctypes.c_uint16 * 3)] + \
+               [(n, ctypes.c_uint8) for n in ("slot", "cand", "count", "is_intra", "skip_flag", "merge_flag", "y_has_coeff", "u_has_coeff",
+                                              "v_has_coeff", "block_has_coeff", "tx_type", "best_intra_mode", "uv_mode", "cfl_alpha_idx",
+                                              "cfl_alpha_signs")] + [("pad", ctypes.c_uint8 * 7)]
+
+
+class MdDecideGroup(ctypes.Structure):
+    """svt_hip_md_decide_group"""
+    _fields_ = [("bsize", c_int32), ("nblocks", c_uint32), ("n", c_int32), ("ninter", c_int32), ("nintra", c_int32), ("lambda_", c_uint32),
+                ("slice_is_intra", c_int32), ("full_loop_escape", c_int32), ("modes", ctypes.c_uint8 * 64)] + \
+               [(n, c_void_p) for n in ("d_luma", "d_dist_cb", "d_dist_cr", "d_bits_cb", "d_bits_cr", "d_eob_cb", "d_eob_cr", "d_rate", "d_cand",
+                                        "d_cand_out", "d_cfl", "d_blk", "d_rates", "d_decision", "d_full_cost")] + \
+               [(n, c_void_p * 3) for n in ("d_pred", "d_best_pred", "d_qcoeff", "d_dqcoeff", "d_best_qcoeff", "d_best_dqcoeff")] + \
+               [("d_inter_blk", c_void_p), ("d_best_inter_blk", c_void_p)]
+
+
+def md_blk_dtype():
+    """numpy dtype of svt_hip_md_blk"""
+    import numpy as np
+    return np.dtype([("skip_flag_context", np.uint8), ("has_uv", np.uint8), ("pad", np.uint8, (2,))])
+
+
+def md_decision_dtype():
+    """numpy dtype of svt_hip_md_decision"""
+    import numpy as np
+    return np.dtype([("cost", "<u8"), ("cost_luma", "<u8"), ("merge_cost", "<u8"), ("skip_cost", "<u8"), ("full_lambda_rate", "<u8"),
+                     ("full_distortion", "<u4"), ("eob", "<u2", (3,))] +
+                    [(n, np.uint8) for n in ("slot", "cand", "count", "is_intra", "skip_flag", "merge_flag", "y_has_coeff", "u_has_coeff",
+                                             "v_has_coeff", "block_has_coeff", "tx_type", "best_intra_mode", "uv_mode", "cfl_alpha_idx",
+                                             "cfl_alpha_signs")] + [("pad", np.uint8, (7,))])
+
+
+def pack_md_rates(tables):
+    """dict of the three int32 tables (MD_RATE_TABLES shapes) -> int32 [655] in svt_hip_md_rates order"""
+    import numpy as np
+    parts = []
+    for name, shape in MD_RATE_TABLES:
+        a = np.asarray(tables[name], np.int32)
+        assert a.shape == shape, (name, a.shape)
+        parts.append(a.reshape(-1))
+    return np.concatenate(parts)
+
+
+BSIZE_W = (4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64, 128, 128, 4, 16, 8, 32, 16, 64)      # block_size_wide / _high, AV1 block_size order
+BSIZE_H = (4, 8, 4, 8, 16, 8, 16, 32, 16, 32, 64, 32, 64, 128, 64, 128, 16, 4, 32, 8, 64, 16)
+
+
+def md_plane_sizes(bsize):
+    """per plane (Y, Cb, Cr; 4:2:0, a chroma side at least 4) of a block size: (width, height, coefficients of its one transform block)"""
+    out = []
+    for p in range(3):
+        w, h = (BSIZE_W[bsize], BSIZE_H[bsize]) if p == 0 else (max(BSIZE_W[bsize] // 2, 4), max(BSIZE_H[bsize] // 2, 4))
+        out.append((w, h, min(w, 32) * min(h, 32)))
+    return out
 
 
 def inter_cand_dtype():
@@ -1964,6 +2044,95 @@ class SvtHipDsp:
                                                       scratch.numel() if scratch is not None else 0, self._stream())
         return rc, scratch
 
+    # -- the join of mode decision: full cost, early exit, best candidate and the winner's arrays per block ------------------------------
+    MD_GATHERS = ("pred", "best_pred", "qcoeff", "dqcoeff", "best_qcoeff", "best_dqcoeff")
+
+    def _md_decide_struct(self, a, g):
+        """fills one MdDecideGroup from a dict (see make_md_decide_groups)"""
+        P = lambda t: self._p(t) if t is not None else None
+        a.bsize, a.nblocks, a.n = g["bsize"], g["nblocks"], g["n"]
+        a.ninter, a.nintra, a.lambda_ = g.get("ninter", 0), g.get("nintra", 0), g.get("lambda", 0)
+        a.slice_is_intra, a.full_loop_escape = int(g.get("slice_is_intra", 0)), g.get("full_loop_escape", 0)
+        modes = [int(m) for m in g.get("modes", ())][:64]
+        a.modes = (ctypes.c_uint8 * 64)(*(modes + [0] * (64 - len(modes))))
+        for k in ("luma", "dist_cb", "dist_cr", "bits_cb", "bits_cr", "eob_cb", "eob_cr", "rate", "cand", "cand_out", "cfl", "blk", "rates",
+                  "decision", "full_cost", "inter_blk", "best_inter_blk"):
+            setattr(a, "d_" + k, P(g.get(k)))
+        for k in self.MD_GATHERS:
+            planes = g.get(k) or ()
+            for p in range(3):
+                getattr(a, "d_" + k)[p] = P(planes[p]) if p < len(planes) else None
+
+    def make_md_decide_groups(self, groups):
+        """groups: list of dicts with tensors luma (uint8 [nb, n, 40]: TxDecision records), optional dist_cb / dist_cr (int64 [nb, n, 2]),
+        bits_cb / bits_cr (int64 [nb, n]), eob_cb / eob_cr (int16 [nb, n]), rate (int32 [nb, n, 2]), cand (uint8 [nb, n]), cand_out (uint8
+        [nb, n, 16]: inter_cand_dtype, with ninter > 0), optional cfl (uint8 [nb, n, 32]: CflDecision), blk (uint8 [nb, 4]: md_blk_dtype),
+        rates (int32 [655]: pack_md_rates), decision (uint8 [nb, 72]: md_decision_dtype), optional full_cost (int64 [nb, n]); the optional
+        gathers pred / qcoeff / dqcoeff (lists of up to three tensors [nb, n, ...] for Y, Cb, Cr; None for a plane not given) with best_pred /
+        best_qcoeff / best_dqcoeff ([nb, ...]), inter_blk (uint8 [nb, n, 16]) with best_inter_blk (uint8 [nb, 16]); plus bsize, nblocks, n,
+        ninter, nintra, modes, lambda, slice_is_intra, full_loop_escape.  -> ctypes array (keep the tensors alive!)"""
+        arr = (MdDecideGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            self._md_decide_struct(arr[i], g)
+        return arr
+
+    def md_decide_frame(self, groups):
+        """svt_hip_md_decide_frame.  groups: a ctypes array from make_md_decide_groups or the list of dicts -> the return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_md_decide_groups(groups)
+        return self.lib.svt_hip_md_decide_frame(groups, n, self._stream())
+
+    def make_md_search_groups(self, groups):
+        """groups: list of dicts {"md": a make_md_decide_groups dict (its stage inputs luma, the chroma arrays, qcoeff and dqcoeff are set by
+        the call), "luma": a make_tx_search_groups dict over the nb * n survivors (decision / best_qcoeff / best_dqcoeff optional: scratch),
+        optional "cb" / "cr": make_full_loop_groups dicts with one type (dist / eob / qcoeff / dqcoeff optional: scratch) and then
+        txb_skip_ctx_c / dc_sign_ctx_c (two uint8 [nb * n] tensors each), coeff_cost_uv (int32 [529]), eob_cost_uv (int32 [22]), optional
+        bits_c (two int64 [nb, n] tensors)}.  -> ctypes array (keep the tensors alive!)"""
+        P = lambda t: self._p(t) if t is not None else None
+        arr = (MdSearchGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            a = arr[i]
+            self._md_decide_struct(a.md, g["md"])
+            a.luma = self.make_tx_search_groups([g["luma"]])[0]
+            a.use_chroma = int(g.get("cb") is not None)
+            if a.use_chroma:
+                fl = self.make_full_loop_groups([g["cb"], g["cr"]])
+                a.cb, a.cr = fl[0], fl[1]
+                for p in range(2):
+                    a.d_txb_skip_ctx_c[p], a.d_dc_sign_ctx_c[p] = P(g["txb_skip_ctx_c"][p]), P(g["dc_sign_ctx_c"][p])
+                    a.d_bits_c[p] = P(g["bits_c"][p]) if g.get("bits_c") is not None else None
+                a.d_coeff_cost_uv, a.d_eob_cost_uv = P(g.get("coeff_cost_uv")), P(g.get("eob_cost_uv"))
+        return arr
+
+    def md_search_scratch_bytes(self, groups):
+        """svt_hip_md_search_scratch_bytes of a ctypes array from make_md_search_groups or of the list of dicts (0: bad parameters)"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_md_search_groups(groups)
+        return self.lib.svt_hip_md_search_scratch_bytes(groups, n)
+
+    def md_search_frame(self, groups, qrow_luma, qrow_chroma, scratch, flavour=1):
+        """svt_hip_md_search_frame: luma transform-type search -> chroma full loop and rate -> decide in one call.  groups: a ctypes array
+        from make_md_search_groups or the list of dicts; qrow_luma / qrow_chroma: quantiser row sets as full_loop_frame takes them
+        (qrow_chroma None without chroma); scratch: a uint8 device tensor of at least md_search_scratch_bytes(groups) bytes (None where
+        that is 0).  -> the library's return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_md_search_groups(groups)
+        keep, rows = [], []
+        for qrow in (qrow_luma, qrow_chroma):
+            if qrow is None:
+                rows.append(None)
+                continue
+            tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
+            keep.append(tabs)
+            rows.append(self.QRows(*[tb.ctypes.data for tb in tabs]))
+        return self.lib.svt_hip_md_search_frame(groups, n, flavour, ctypes.addressof(rows[0]) if rows[0] is not None else None,
+                                                ctypes.addressof(rows[1]) if rows[1] is not None else None,
+                                                self._p(scratch) if scratch is not None else None,
+                                                scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+
     def fast_pick(self, dist, blk, rates, tx_size, bsize, bsize_uv, modes, deltas, uv_modes, uv_deltas, nfl, lam, metric, use_angle_delta=True,
                   slice_is_intra=True, ac_dequant_q3=0, intrabc_bits=0, dist_cb=None, dist_cr=None, pred=None, src_xy=None, want_all_cost=False):
         """One group; the outputs are allocated here.  -> dict of cand, sorted, cost, rate, ref_fast_cost and, when asked for or their input
@@ -2150,3 +2319,10 @@ class SvtHipDsp:
 TxDecision, TxDecideGroup, TxSearchGroup = SvtHipDsp.TxDecision, SvtHipDsp.TxDecideGroup, SvtHipDsp.TxSearchGroup
 QRows, CflSearchGroup, CflDecision, CflDecideGroup, CflPickGroup = (SvtHipDsp.QRows, SvtHipDsp.CflSearchGroup, SvtHipDsp.CflDecision,
                                                                     SvtHipDsp.CflDecideGroup, SvtHipDsp.CflPickGroup)
+
+
+class MdSearchGroup(ctypes.Structure):
+    """svt_hip_md_search_group"""
+    _fields_ = [("md", MdDecideGroup), ("luma", TxSearchGroup), ("use_chroma", c_int32), ("cb", SvtHipDsp.FullLoopGroup), ("cr", SvtHipDsp.FullLoopGroup),
+                ("d_txb_skip_ctx_c", c_void_p * 2), ("d_dc_sign_ctx_c", c_void_p * 2), ("d_coeff_cost_uv", c_void_p), ("d_eob_cost_uv", c_void_p),
+                ("d_bits_c", c_void_p * 2)]

@@ -77,10 +77,11 @@ inline uint32_t staged_blocks_per_wg(int tx_size) {
 int frame_groups_check(const svt_hip_frame_group* groups, int ngroups);      // svt_hip_txfm.hip
 // The launches of the mode-decision stages for groups their *_check (md_plan.h) accepted: the group-table fill and the launches, nothing
 // validated.  Every public entry point is require_init, check, enqueue; the composed calls (svt_hip_tx_search_frame,
-// svt_hip_intra_fast_search_frame, svt_hip_cfl_search_frame, svt_hip_cfl_pick_frame) check every stage, then enqueue every stage.
+// svt_hip_intra_fast_search_frame, svt_hip_cfl_search_frame, svt_hip_cfl_pick_frame, svt_hip_md_search_frame) check every stage, then enqueue every stage.
 int full_loop_enqueue(const svt_hip_full_loop_group* groups, int ngroups, int flavour, const svt_hip_qrows& q, hipStream_t s);      // svt_hip_full_loop.hip
 int coeff_rate_enqueue(const svt_hip_coeff_rate_group* groups, int ngroups, hipStream_t s);                                       // svt_hip_coeff_rate.hip
 int fast_loop_enqueue(const svt_hip_fast_loop_group* groups, int ngroups, int metric, int flavour, hipStream_t s);                // svt_hip_fast_loop.hip
+int tx_decide_enqueue(const svt_hip_tx_decide_group* groups, int ngroups, hipStream_t s);                                         // svt_hip_tx_decide.hip
 
 #define TX_SWITCH(tx_size, CALL)                                                                  \
     switch (tx_size) {                                                                            \

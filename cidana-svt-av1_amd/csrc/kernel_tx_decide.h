@@ -25,14 +25,13 @@
 #pragma once
 #include "dev_common.h"
 #include "group_table.h"
+#include "kernel_winner_gather.h"
 
 namespace svtdev {
 
 constexpr int TD_MAX_GROUPS = 32;          // per launch: what fits the kernel arguments
 constexpr int TD_MAX_TYPES = 16;
 constexpr int TD_THREADS = 256, TD_WAVES = TD_THREADS / 64;
-constexpr int TD_UNIT_QUADS_LOG2 = 9;      // quads (16 bytes) of one array a wave-unit gathers, at most
-constexpr int TD_GATHER = (1 << TD_UNIT_QUADS_LOG2) / 64;
 constexpr int TD_COST_WORDS = 64 * (TD_MAX_TYPES + 1);     // a wave's cost tile: up to 64 rows of ntypes + 1
 
 struct TxDecideGroupDev {
@@ -55,30 +54,6 @@ struct TxDecideDesc {
     TxDecideGroupDev g[TD_MAX_GROUPS];
 };
 static_assert(sizeof(TxDecideDesc) <= 4000, "kernel arguments");
-
-// one array's gather for a wave-unit: blocks blk0 .. blk0 + nb - 1, winner positions in src (lane b: block b's, -1: zeros)
-__device__ __forceinline__ void td_gather(const int32_t* __restrict__ in, int32_t* __restrict__ out, uint32_t blk0, int nb, int ntypes, int nql,
-                                          int ngather, int lane, int src) {
-    int4 v[TD_GATHER];
-    const int qmask = (1 << nql) - 1;
-#pragma unroll
-    for (int g = 0; g < TD_GATHER; g++) {
-        if (g < ngather) {
-            const int q = g * 64 + lane, jb = q >> nql;                      // jb < 64
-            const int w = __shfl(src, jb, 64);
-            v[g] = make_int4(0, 0, 0, 0);
-            if (jb < nb && w >= 0)
-                v[g] = *reinterpret_cast<const int4*>(in + ((((size_t)(blk0 + jb) * ntypes + w) << nql) + (q & qmask)) * 4);
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < TD_GATHER; g++) {
-        if (g < ngather) {
-            const int q = g * 64 + lane, jb = q >> nql;
-            if (jb < nb) *reinterpret_cast<int4*>(out + ((((size_t)(blk0 + jb)) << nql) + (q & qmask)) * 4) = v[g];
-        }
-    }
-}
 
 __global__ __launch_bounds__(TD_THREADS) void tx_decide_kernel(const TxDecideDesc fd) {
     __shared__ unsigned long long cost_all[TD_WAVES * TD_COST_WORDS];

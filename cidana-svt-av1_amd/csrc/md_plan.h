@@ -1,6 +1,6 @@
 // md_plan.h — what the mode-decision calls settle on the host before they touch a device: the size helpers, the argument check of each
-// of the seven stages (full loop, coefficient rate, transform-type decide, fast loop, fast pick, CfL search, CfL decide) and, for each
-// of the four calls composed of them, ONE walk over its groups that sizes its scratch, carves it and derives its stages' groups.
+// of the eight stages (full loop, coefficient rate, transform-type decide, fast loop, fast pick, CfL search, CfL decide, mode-decision
+// decide) and, for each of the five calls composed of them, ONE walk over its groups that sizes its scratch, carves it and derives its stages' groups.
 // The svt_hip_*.hip files check and plan here, then enqueue.  Plain C++17, no HIP header: a CPU program can include it
 // (tests/c/md_plan_host.cpp).
 #pragma once
@@ -233,6 +233,69 @@ inline int cfl_decide_check(const svt_hip_cfl_decide_group* groups, int ngroups)
     }
     return SVT_HIP_OK;
 }
+// The decide of mode decision (svt_hip_md_decide_frame).  Its geometry comes from the block size alone: per plane (Y, Cb, Cr; 4:2:0, a
+// chroma side at least 4) the samples of a prediction and the coefficients of the plane's one transform block.
+struct MdGeom { int w[3], h[3], pred_bytes[3], ncoeff[3]; };
+inline MdGeom md_geom(int bsize) {
+    MdGeom m;
+    for (int p = 0; p < 3; p++) {
+        const int w = p ? (kBsizeW[bsize] / 2 < 4 ? 4 : kBsizeW[bsize] / 2) : kBsizeW[bsize], h = p ? (kBsizeH[bsize] / 2 < 4 ? 4 : kBsizeH[bsize] / 2) : kBsizeH[bsize];
+        m.w[p] = w; m.h[p] = h; m.pred_bytes[p] = w * h; m.ncoeff[p] = packed_side(w) * packed_side(h);
+    }
+    return m;
+}
+inline bool md_bsize_ok(int bsize) { return bsize >= 0 && bsize <= 21 && (bsize < 13 || bsize > 15); }
+// log2 blocks per wave-unit: the largest gather of the size (luma's prediction or coefficients) at most 2^9 quads, the unit's costs
+// (rows of n + 1 words) inside the wave's tile of kMdTileWords, 64 blocks (one owning lane each) at most
+constexpr int kMdTileWords = 64 * 17;                  // MD_COST_WORDS (kernel_md_decide.h)
+inline int md_decide_bpul(int bsize, int n) {
+    const MdGeom m = md_geom(bsize);
+    const int py = log2_of(m.pred_bytes[0]) - 4, cy = log2_of(m.ncoeff[0]) - 2;
+    int bpul = 9 - (py > cy ? py : cy);
+    if (bpul > 6) bpul = 6;
+    while ((n + 1) << bpul > kMdTileWords) bpul--;
+    return bpul;
+}
+// the scalars of a group, as the decide and the composed search require them of every group, empty ones included
+inline int md_scalars_check(int g, const svt_hip_md_decide_group& G) {
+    if (!md_bsize_ok(G.bsize)) return set_err(SVT_HIP_ERR_INVALID, "group %d: bsize %d (0 .. 21 without the 128-wide 13 .. 15)", g, G.bsize);
+    if (G.n < 1 || G.n > SVT_HIP_MAX_NFL) return set_err(SVT_HIP_ERR_INVALID, "group %d: n %d (1 .. %d)", g, G.n, SVT_HIP_MAX_NFL);
+    if (G.ninter < 0 || G.nintra < 0 || G.ninter + G.nintra < 1 || G.ninter + G.nintra > SVT_HIP_FAST_LOOP_MAX_CANDIDATES)
+        return set_err(SVT_HIP_ERR_INVALID, "group %d: ninter %d + nintra %d (1 .. 64 candidates)", g, G.ninter, G.nintra);
+    for (int c = 0; c < G.nintra; c++)
+        if (G.modes[c] > 12) return set_err(SVT_HIP_ERR_INVALID, "group %d: intra candidate %d: mode %d", g, c, G.modes[c]);
+    if (G.full_loop_escape < 0 || G.full_loop_escape > 2) return set_err(SVT_HIP_ERR_INVALID, "group %d: full_loop_escape %d (0 .. 2)", g, G.full_loop_escape);
+    return pairs_check(g, G.nblocks, (uint64_t)G.n, "nblocks * n");
+}
+inline int md_decide_check(const svt_hip_md_decide_group* groups, int ngroups) {
+    if (int rc = group_list_check(groups, ngroups)) return rc;
+    for (int g = 0; g < ngroups; g++) {
+        const svt_hip_md_decide_group& G = groups[g];
+        if (int rc = md_scalars_check(g, G)) return rc;
+        if (G.nblocks == 0) continue;
+        if (!G.d_luma || !G.d_rate || !G.d_cand || !G.d_blk || !G.d_rates || !G.d_decision) return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL member", g);
+        if (G.ninter > 0 && !G.d_cand_out) return set_err(SVT_HIP_ERR_INVALID, "group %d: d_cand_out is required with ninter > 0", g);
+        const int nchroma = !!G.d_dist_cb + !!G.d_dist_cr + !!G.d_bits_cb + !!G.d_bits_cr + !!G.d_eob_cb + !!G.d_eob_cr;
+        if (nchroma != 0 && nchroma != 6) return set_err(SVT_HIP_ERR_INVALID, "group %d: the six chroma arrays are given all or none (Cb without Cr)", g);
+        uintptr_t a16 = (uintptr_t)G.d_inter_blk | (uintptr_t)G.d_best_inter_blk;
+        if (G.d_best_inter_blk && (!G.d_inter_blk || G.d_best_inter_blk == G.d_inter_blk))
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: d_best_inter_blk without its input or equal to it", g);
+        for (int p = 0; p < 3; p++) {
+            const void* in[3] = {G.d_pred[p], G.d_qcoeff[p], G.d_dqcoeff[p]};
+            const void* out[3] = {G.d_best_pred[p], G.d_best_qcoeff[p], G.d_best_dqcoeff[p]};
+            for (int a = 0; a < 3; a++) {
+                if (out[a] && (!in[a] || out[a] == in[a])) return set_err(SVT_HIP_ERR_INVALID, "group %d: plane %d: a gather without its input or equal to it", g, p);
+                a16 |= (uintptr_t)in[a] | (uintptr_t)out[a];
+            }
+        }
+        const uintptr_t a8 = (uintptr_t)G.d_luma | (uintptr_t)G.d_dist_cb | (uintptr_t)G.d_dist_cr | (uintptr_t)G.d_bits_cb | (uintptr_t)G.d_bits_cr |
+                             (uintptr_t)G.d_cfl | (uintptr_t)G.d_decision | (uintptr_t)G.d_full_cost;
+        const uintptr_t a4 = (uintptr_t)G.d_rate | (uintptr_t)G.d_rates | (uintptr_t)G.d_blk | (uintptr_t)G.d_cand_out;
+        if ((a16 & 15) || (a8 & 7) || (a4 & 3) || (((uintptr_t)G.d_eob_cb | (uintptr_t)G.d_eob_cr) & 1))
+            return set_err(SVT_HIP_ERR_INVALID, "group %d: misaligned buffer (prediction, coefficient and inter-record arrays 16 bytes, records and uint64 arrays 8, d_rate / d_rates / d_blk / d_cand_out 4, eobs 2)", g);
+    }
+    return SVT_HIP_OK;
+}
 
 // ---- the composed calls: scratch and stage groups ------------------------------------------------------------------------------------------
 // Hands out the pieces of a scratch in the order they are asked for, each rounded up to 16 bytes.  Without a base it only adds them up
@@ -242,6 +305,9 @@ struct Carver {
     char* base;
     size_t used = 0;
     template <typename T> void piece(T*& p, size_t bytes) { p = base ? (T*)(base + used) : nullptr; used += align16(bytes); }
+    // a piece that a later part of the same walk asks only "is it there?" of: while sizing it is not NULL either (the Carver's own address,
+    // which nothing dereferences: a sizing walk derives no stage groups)
+    template <typename T> void piece_present(T*& p, size_t bytes) { piece(p, bytes); if (!base) p = (T*)this; }
 };
 // A walk checks what the carving needs of each group (sizes and counts), carves, and with `st` appends the groups of the call's stages.
 // plan_stages: the walk without a base sizes the scratch, the scratch is accepted or refused, and only then the walk runs over it.
@@ -372,5 +438,74 @@ inline int cfl_pick_walk(const svt_hip_cfl_pick_group* groups, int ngroups, Carv
     if (int rc = cfl_search_walk(sg.data(), ngroups, sc, st)) return rc;
     if (st) st->sg = std::move(sg);
     return SVT_HIP_OK;
+}
+
+// svt_hip_md_search_frame: luma transform-type search -> (Cb, Cr full loop -> coefficient rate) -> decide.  Per non-empty group the
+// luma record, luma's best coefficients when a gather asks for them, then per chroma plane dist, eob, bits, qcoeff and (when its gather
+// asks) dqcoeff, each only when not supplied; after all groups the luma search's own pieces (tx_search_walk).
+struct MdSearchStages {
+    TxSearchStages tx;
+    std::vector<svt_hip_full_loop_group> flc; std::vector<svt_hip_coeff_rate_group> crc;        // Cb, Cr of the groups with chroma
+    std::vector<svt_hip_md_decide_group> md;
+};
+inline int md_search_walk(const svt_hip_md_search_group* groups, int ngroups, Carver& sc, MdSearchStages* st) {
+    if (int rc = group_list_check(groups, ngroups)) return rc;
+    std::vector<svt_hip_tx_search_group> luma;
+    for (int g = 0; g < ngroups; g++) {
+        const svt_hip_md_search_group& G = groups[g];
+        svt_hip_md_decide_group M = G.md;
+        svt_hip_tx_search_group L = G.luma;
+        if (int rc = md_scalars_check(g, M)) return rc;
+        const uint32_t pairs = M.nblocks * (uint32_t)M.n;                           // (md_scalars_check: below 2^31)
+        if (int rc = group_types_check(g, L.fl.tx_size, L.fl.ntypes, L.fl.tx_types)) return rc;
+        bool dct = false;
+        for (int t = 0; t < L.fl.ntypes; t++) dct |= L.fl.tx_types[t] == SVT_DCT_DCT;
+        if (!dct) return set_err(SVT_HIP_ERR_INVALID, "group %d: the luma type list has no DCT_DCT", g);
+        const MdGeom m = md_geom(M.bsize);
+        if (kTxW[L.fl.tx_size] != m.w[0] || kTxH[L.fl.tx_size] != m.h[0]) return set_err(SVT_HIP_ERR_INVALID, "group %d: luma tx_size %d is not the block size's", g, L.fl.tx_size);
+        if (L.fl.nblocks != pairs) return set_err(SVT_HIP_ERR_INVALID, "group %d: luma nblocks %u is not md.nblocks * md.n", g, L.fl.nblocks);
+        svt_hip_full_loop_group C[2] = {G.cb, G.cr};
+        uint64_t* cbits[2] = {G.d_bits_c[0], G.d_bits_c[1]};
+        if (G.use_chroma)
+            for (int p = 0; p < 2; p++) {
+                if (int rc = group_types_check(g, C[p].tx_size, C[p].ntypes, C[p].tx_types)) return rc;
+                if (C[p].ntypes != 1 || C[p].nblocks != pairs || kTxW[C[p].tx_size] != m.w[1 + p] || kTxH[C[p].tx_size] != m.h[1 + p])
+                    return set_err(SVT_HIP_ERR_INVALID, "group %d: chroma plane %d: ntypes %d (1), nblocks %u (md.nblocks * md.n) or a tx_size %d that is not the block size's", g, p, C[p].ntypes, C[p].nblocks, C[p].tx_size);
+            }
+        if (pairs) {
+            if (!L.d_decision) sc.piece(L.d_decision, (size_t)pairs * sizeof(svt_hip_tx_decision));
+            if (!L.d_best_qcoeff && M.d_best_qcoeff[0]) sc.piece(L.d_best_qcoeff, (size_t)pairs * (size_t)m.ncoeff[0] * sizeof(int32_t));
+            // (tx_search_walk below keeps the luma dqcoeff exactly when d_best_dqcoeff is there, while sizing too)
+            if (!L.d_best_dqcoeff && M.d_best_dqcoeff[0]) sc.piece_present(L.d_best_dqcoeff, (size_t)pairs * (size_t)m.ncoeff[0] * sizeof(int32_t));
+            if (G.use_chroma)
+                for (int p = 0; p < 2; p++) {
+                    const size_t coeff_bytes = (size_t)pairs * (size_t)m.ncoeff[1 + p] * sizeof(int32_t);
+                    if (!C[p].d_dist) sc.piece(C[p].d_dist, (size_t)pairs * 16);
+                    if (!C[p].d_eob) sc.piece(C[p].d_eob, (size_t)pairs * 2);
+                    if (!cbits[p]) sc.piece(cbits[p], (size_t)pairs * 8);
+                    if (!C[p].d_qcoeff) sc.piece(C[p].d_qcoeff, coeff_bytes);
+                    if (!C[p].d_dqcoeff && M.d_best_dqcoeff[1 + p]) sc.piece(C[p].d_dqcoeff, coeff_bytes);
+                }
+        }
+        luma.push_back(L);
+        if (!st) continue;
+        M.d_luma = L.d_decision; M.d_qcoeff[0] = L.d_best_qcoeff; M.d_dqcoeff[0] = L.d_best_dqcoeff;
+        M.d_dist_cb = M.d_dist_cr = M.d_bits_cb = M.d_bits_cr = nullptr; M.d_eob_cb = M.d_eob_cr = nullptr;
+        M.d_qcoeff[1] = M.d_qcoeff[2] = M.d_dqcoeff[1] = M.d_dqcoeff[2] = nullptr;
+        if (G.use_chroma) {
+            M.d_dist_cb = C[0].d_dist; M.d_dist_cr = C[1].d_dist; M.d_eob_cb = C[0].d_eob; M.d_eob_cr = C[1].d_eob;
+            M.d_bits_cb = cbits[0]; M.d_bits_cr = cbits[1];
+            for (int p = 0; p < 2; p++) {
+                M.d_qcoeff[1 + p] = C[p].d_qcoeff; M.d_dqcoeff[1 + p] = C[p].d_dqcoeff;
+                svt_hip_coeff_rate_group R{};
+                R.tx_size = C[p].tx_size; R.ntypes = 1; R.tx_types[0] = C[p].tx_types[0]; R.nblocks = pairs;
+                R.d_qcoeff = C[p].d_qcoeff; R.d_eob = C[p].d_eob; R.d_iscan = C[p].d_iscan; R.d_txb_skip_ctx = G.d_txb_skip_ctx_c[p];
+                R.d_dc_sign_ctx = G.d_dc_sign_ctx_c[p]; R.d_coeff_cost = G.d_coeff_cost_uv; R.d_eob_cost = G.d_eob_cost_uv; R.d_bits = cbits[p];
+                st->flc.push_back(C[p]); st->crc.push_back(R);
+            }
+        }
+        st->md.push_back(M);
+    }
+    return tx_search_walk(luma.data(), ngroups, sc, st ? &st->tx : nullptr);
 }
 }  // namespace svthost

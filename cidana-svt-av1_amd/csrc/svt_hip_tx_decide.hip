@@ -14,7 +14,7 @@ static_assert(sizeof(svt_hip_tx_decision) == 40 && alignof(svt_hip_tx_decision) 
 // log2 blocks per wave-unit: 2^TD_UNIT_QUADS_LOG2 quads of gather, 64 blocks (one owning lane each) at most
 static int tx_decide_bpul(int nql) { return TD_UNIT_QUADS_LOG2 - nql < 6 ? TD_UNIT_QUADS_LOG2 - nql : 6; }
 
-static int tx_decide_enqueue(const svt_hip_tx_decide_group* groups, int ngroups, hipStream_t s) {
+int svthost::tx_decide_enqueue(const svt_hip_tx_decide_group* groups, int ngroups, hipStream_t s) {
     GroupTable<TxDecideDesc, TD_MAX_GROUPS> tab;
     auto launch = [&](const TxDecideDesc& fd, uint32_t total) -> int {
         hipLaunchKernelGGL(tx_decide_kernel, dim3(total), dim3(TD_THREADS), 0, s, fd);

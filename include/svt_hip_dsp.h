@@ -1095,7 +1095,8 @@ int svt_hip_intra_fast_loop_frame(const svt_hip_fast_loop_group *groups, int ngr
  * d_rates / d_rate / d_src_xy* 4), nblocks * ncand above 2^31 - 1.  One launch per non-empty group, the group in the kernel arguments; the call
  * only enqueues (no allocation, no synchronisation) and can be captured into a HIP graph.
  * Left to the caller here: inter candidates (svt_hip_inter_fast_pick_frame below costs them and walks the combined list), the intrabc branch
- * (:556-597; intrabc_bits is intrabcFacBits[0] when the picture allows intrabc, else 0), and product_full_mode_decision. */
+ * (:556-597; intrabc_bits is intrabcFacBits[0] when the picture allows intrabc, else 0).  product_full_mode_decision over the survivors is
+ * svt_hip_md_decide_frame below. */
 #define SVT_HIP_MAX_NFL 40
 typedef struct svt_hip_fast_pick_blk {
     uint8_t top_mode, left_mode;         /* intra_luma_top_mode / intra_luma_left_mode, 0 .. 12 */
@@ -1805,6 +1806,133 @@ typedef struct svt_hip_inter_fast_search_group {
 size_t svt_hip_inter_fast_search_scratch_bytes(const svt_hip_inter_fast_search_group *groups, int ngroups);   /* HOST */
 int svt_hip_inter_fast_search_frame(const svt_hip_inter_fast_search_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height,
                                     int bd, int metric, void *d_scratch, size_t scratch_bytes, void *stream);
+
+/* The join of mode decision: the rest of AV1PerformFullLoop (EbProductCodingLoop.c:1877-2184) after the survivors' transform search,
+ * and product_full_mode_decision (EbModeDecision.c:2653-2690): every survivor's full cost, the full loop's early exit and the best
+ * candidate of every block, with the winner's prediction, coefficients and inter record gathered, for many groups in one launch.
+ * A group is nblocks blocks of one block size, each with n full-loop slots in best_candidate_index_array order, which is what
+ * svt_hip_fast_pick_frame / svt_hip_inter_fast_pick_frame write (n = min(nfl, ncand)).  Per (block, slot), in uint64 arithmetic
+ * that wraps as the reference's does, RDCOST(R, D) = ((R * lambda + 256) >> 9) + D * 128 (EbRateDistortionCost.h:73):
+ *   inputs    luma: d_luma's dist[2], bits, eob, has_coeff, tx_type (its cost is not read).  Cb, Cr: the given dist / bits / eob of
+ *             svt_hip_full_loop_frame with ntypes 1 and svt_hip_coeff_rate_frame (FullLoop_R + CuFullDistortionFastTuMode_R,
+ *             EbFullLoop.c:1529-1873), used when the arrays are given AND the block's has_uv is set, else zero distortion, bits and
+ *             eob.  u_has_coeff / v_has_coeff are eob != 0 (av1_tu_calc_cost, EbRateDistortionCost.c:2103-2110), block_has_coeff the
+ *             OR of the three.  A slot is intra iff d_cand >= ninter, its intra_luma_mode / pred_mode modes[d_cand - ninter].
+ *   cost      Av1FullCost (EbRateDistortionCost.c:1456-1534): rate = fast_luma_rate + chroma rate + the three planes' bits, chroma
+ *             rate = fast_chroma_rate and, for an intra slot of a has_uv block whose d_cfl record says UV_CFL_PRED (:1493-1506),
+ *             + (cflAlphaFacBits[signs][0][idx >> 4] + cflAlphaFacBits[signs][1][idx & 15], summed as int32) + intraUVmodeFacBits
+ *             [isCflAllowed][mode][UV_CFL_PRED] - intraUVmodeFacBits[isCflAllowed][mode][UV_DC_PRED], the -= on the uint64 as written;
+ *             full_cost = RDCOST(rate, D), D = the three planes' dist[DIST_CALC_RESIDUAL]; full_lambda_rate = full_cost - D (D, not
+ *             D * 128: as written, :1529); full_cost_luma = RDCOST(fast_luma_rate + luma bits, luma dist).
+ *             Av1MergeSkipFullCost (:1551-1692) for an inter slot whose d_cand_out flags & 1 (merge_flag; av1_inter_full_cost,
+ *             :1761-1811): merge_cost = RDCOST(fast_luma_rate + fast_chroma_rate + bits, D), skip_cost = RDCOST(skipModeFacBits
+ *             [skip_flag_context][1], the three planes' dist[DIST_CALC_PREDICTION]); skip_cost <= merge_cost picks skip (a tie is skip);
+ *             full_lambda_rate = the picked cost - the picked side's distortion.
+ *   escape    on a non-I slice, walking the slots in order, slot k ends the loop when (intra || full_loop_escape == 2) &&
+ *             best_inter_luma_zero_coeff == 0 (:1935-1941); that variable starts at 1 and, only with full_loop_escape != 0, becomes
+ *             the y_has_coeff of an inter slot whose full cost is strictly below bestfullCost, which starts at 0xFFFFFFFF: 32 bits,
+ *             so an inter cost of 2^32 - 1 or more never updates it (:1909, :2170-2181; a quirk, kept).  count = k, at least 1.
+ *   decision  over the first count slots: the first strict minimum of the full cost from UINT64_MAX (slot 0 when no cost is below
+ *             it: lowestCostIndex starts at best_candidate_index_array[0], :2674); best_intra_mode = the pred_mode of the first
+ *             strict minimum among the intra slots, 0xFF when none was evaluated (the reference leaves its caller's value).
+ * The decision's uv_mode / cfl_alpha_idx / cfl_alpha_signs are the winner's d_cfl record's when it is an intra slot of a has_uv
+ * block and d_cfl is given, else 0: a candidate's own uv mode stays with the caller.  cost_luma is 0 for a merge winner (its cost
+ * function does not set it); merge_cost / skip_cost are 0 unless the winner is a merge slot.
+ * d_full_cost, when given, receives every slot's cost, those at or past the escape included (count says which were evaluated).
+ * Gathers of the winner, each needing its input: d_best_pred[p] from the dense 8-bit [nblocks][n][h][w] d_pred[p] (p = 0 luma bw x
+ * bh, 1 / 2 chroma max(bw / 2, 4) x max(bh / 2, 4)); d_best_qcoeff[p] / d_best_dqcoeff[p] from [nblocks][n][NC_p], NC_p = min(w, 32) *
+ * min(h, 32) of the plane; d_best_inter_blk from d_inter_blk [nblocks][n].  A plane whose winner has eob 0 stores zero coefficients and
+ * its input is not read.  Only the block index and the winner's slot, below n by construction, address memory from device data.
+ * Context bytes are device data and clamped (skip ctx to 2, CfL signs to 7, the idx nibbles to 15 by construction, the list index
+ * to 63, an intra mode to 12): an out-of-range byte gives an unspecified cost for its block and nothing else.
+ * One transform block per plane is assumed: bsize 13, 14, 15 (128 wide or high, txb_count 2 or 4, EbUtility.c:861) are refused.
+ * Validation, every group (empty ones' scalars included) before the first launch (SVT_HIP_ERR_INVALID): bsize outside 0 .. 21 or
+ * 13 .. 15; n outside 1 .. 40; ninter < 0, nintra < 0, ninter + nintra outside 1 .. 64; an intra mode above 12; full_loop_escape
+ * outside 0 .. 2; and for non-empty groups nblocks * n above 2^31 - 1; NULL d_luma / d_rate / d_cand / d_blk / d_rates / d_decision;
+ * NULL d_cand_out with ninter > 0; some but not all of the six chroma arrays; a gather without its input or equal to it;
+ * misalignment (records and uint64 arrays 8 bytes, d_inter_blk / d_best_inter_blk and the prediction and coefficient arrays 16,
+ * d_rate / d_rates / d_blk / d_cand_out 4, the eobs 2).  One launch per 10 groups; the call only enqueues, allocates nothing and can be captured
+ * into a HIP graph. */
+typedef struct svt_hip_md_blk { uint8_t skip_flag_context, has_uv, pad[2]; } svt_hip_md_blk;     /* sizeof 4 */
+typedef struct svt_hip_md_rates {         /* the int32 tables of MdRateEstimationContext_s the full cost reads, its declaration shapes */
+    int32_t skipModeFacBits[3][3];
+    int32_t intraUVmodeFacBits[2][13][15];
+    int32_t cflAlphaFacBits[8][2][16];
+} svt_hip_md_rates;
+typedef struct svt_hip_md_decision {      /* one per block; sizeof 72, 8-byte aligned */
+    uint64_t cost;                        /* the winner's full cost */
+    uint64_t cost_luma;                   /* its full_cost_luma (0: merge winner) */
+    uint64_t merge_cost, skip_cost;       /* full_cost_merge / full_cost_skip (0: the winner is no merge slot) */
+    uint64_t full_lambda_rate;
+    uint32_t full_distortion;             /* (uint32_t)luma dist[DIST_CALC_RESIDUAL], :2144 */
+    uint16_t eob[3];                      /* Y, Cb, Cr */
+    uint8_t  slot;                        /* the winner's full-loop slot, below count */
+    uint8_t  cand;                        /* its d_cand entry: the index into the candidate list */
+    uint8_t  count;                       /* the effective full_recon_search_count, 1 .. n */
+    uint8_t  is_intra, skip_flag, merge_flag;
+    uint8_t  y_has_coeff, u_has_coeff, v_has_coeff, block_has_coeff;
+    uint8_t  tx_type;                     /* the luma record's */
+    uint8_t  best_intra_mode;             /* 0xFF: no intra slot evaluated */
+    uint8_t  uv_mode, cfl_alpha_idx, cfl_alpha_signs;
+    uint8_t  pad[7];                      /* written as 0 */
+} svt_hip_md_decision;
+#define SVT_HIP_MD_NO_INTRA 0xFF
+typedef struct svt_hip_md_decide_group {
+    int32_t bsize;                        /* AV1 block_size order, 0 .. 21 without 13 .. 15; isCflAllowed = bw <= 32 && bh <= 32 */
+    uint32_t nblocks;
+    int32_t n;                            /* slots per block, 1 .. SVT_HIP_MAX_NFL */
+    int32_t ninter, nintra;               /* of the candidate list d_cand indexes */
+    uint32_t lambda;                      /* full_lambda */
+    int32_t slice_is_intra;               /* slice_type == I_SLICE: no escape */
+    int32_t full_loop_escape;             /* 0, 1, 2 */
+    uint8_t modes[64];                    /* the intra list, as the pick groups carry it; [0 .. nintra) read */
+    const svt_hip_tx_decision *d_luma;    /* [nblocks][n] */
+    const uint64_t *d_dist_cb, *d_dist_cr;   /* optional [nblocks][n][2]; the six chroma arrays all or none */
+    const uint64_t *d_bits_cb, *d_bits_cr;   /* [nblocks][n] */
+    const uint16_t *d_eob_cb, *d_eob_cr;     /* [nblocks][n] */
+    const uint32_t *d_rate;               /* [nblocks][n][2]: fast_luma_rate, fast_chroma_rate */
+    const uint8_t *d_cand;                /* [nblocks][n] */
+    const svt_hip_inter_cand *d_cand_out; /* [nblocks][n]; required when ninter > 0 */
+    const svt_hip_cfl_decision *d_cfl;    /* optional [nblocks][n] */
+    const svt_hip_md_blk *d_blk;          /* [nblocks] */
+    const svt_hip_md_rates *d_rates;
+    svt_hip_md_decision *d_decision;      /* [nblocks] */
+    uint64_t *d_full_cost;                /* optional [nblocks][n] */
+    const uint8_t *d_pred[3]; uint8_t *d_best_pred[3];                 /* optional gathers, see above */
+    const int32_t *d_qcoeff[3], *d_dqcoeff[3]; int32_t *d_best_qcoeff[3], *d_best_dqcoeff[3];
+    const svt_hip_inter_blk *d_inter_blk; svt_hip_inter_blk *d_best_inter_blk;
+} svt_hip_md_decide_group;
+int svt_hip_md_decide_frame(const svt_hip_md_decide_group *groups, int ngroups, void *stream);
+
+/* The one-call form, host composition on `stream`, whose order carries the dependencies (no kernel of its own, as
+ * svt_hip_tx_search_frame): (1) svt_hip_tx_search_frame over the nblocks * n luma survivor predictions (group `luma`, whose
+ * fl.nblocks must be md.nblocks * md.n); (2) with use_chroma, svt_hip_full_loop_frame over `cb` and `cr` (ntypes 1:
+ * transform_type[PLANE_TYPE_UV] at txsize_uv; nblocks as luma's) and svt_hip_coeff_rate_frame on them with the PLANE_TYPE_UV tables;
+ * (3) the decide.  Both chroma planes are quantised with q_chroma: FullLoop_R indexes both planes' rows with cbQp (EbFullLoop.c:1625,
+ * :1686), and the Cr rows equal the Cb rows in a picture without chroma delta q, the only kind this reference makes.
+ * The stages' outputs are the decide's inputs: md.d_luma, the six chroma arrays, d_qcoeff[] and d_dqcoeff[] are SET BY THE CALL from
+ * luma.d_decision / d_best_qcoeff / d_best_dqcoeff, cb / cr .d_dist / d_eob / d_qcoeff / d_dqcoeff and d_bits_c[]; what the caller put
+ * into those members of md is ignored.  Any of these stage arrays may be NULL and then lives in d_scratch (the luma record and the
+ * chroma dist / eob / bits / qcoeff always; luma's best_qcoeff / best_dqcoeff and chroma's dqcoeff only when the matching md.d_best_*
+ * asks for them).  Carved per non-empty group in group order, every piece rounded up to 16 bytes: the luma record, luma best_qcoeff,
+ * luma best_dqcoeff, then per plane Cb, Cr: dist, eob, bits, qcoeff, dqcoeff; after all groups the luma search's own scratch
+ * (svt_hip_tx_search_scratch_bytes of the luma groups).  svt_hip_md_search_scratch_bytes returns the sum, a HOST computation that
+ * needs no device: 0 for bad parameters and for a call without a non-empty group.
+ * A luma type list without DCT_DCT is refused: a no-candidate record (type_index 0xFF) then cannot occur.  Every stage's arguments
+ * are validated before the first launch (SVT_HIP_ERR_INVALID, as the stages' own calls; also luma / cb / cr nblocks other than
+ * md.nblocks * md.n, a chroma ntypes other than 1, a scratch that is NULL, not 16-byte aligned or too small). */
+typedef struct svt_hip_md_search_group {
+    svt_hip_md_decide_group md;
+    svt_hip_tx_search_group luma;
+    int32_t use_chroma;
+    svt_hip_full_loop_group cb, cr;
+    const uint8_t *d_txb_skip_ctx_c[2], *d_dc_sign_ctx_c[2];     /* [nblocks * n] per plane, as svt_hip_coeff_rate_group */
+    const int32_t *d_coeff_cost_uv, *d_eob_cost_uv;              /* the PLANE_TYPE_UV tables */
+    uint64_t *d_bits_c[2];                                       /* optional [nblocks][n]: scratch when NULL */
+} svt_hip_md_search_group;
+size_t svt_hip_md_search_scratch_bytes(const svt_hip_md_search_group *groups, int ngroups);     /* HOST; 0: bad parameters or nothing to carve */
+int svt_hip_md_search_frame(const svt_hip_md_search_group *groups, int ngroups, int flavour, const svt_hip_qrows *q_luma,
+                            const svt_hip_qrows *q_chroma, void *d_scratch, size_t scratch_bytes, void *stream);
 
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
