@@ -60,8 +60,8 @@ struct InterFastStages {
     std::vector<InterFastGather> gather;                    // step 4
 };
 // The walk (md_plan.h's Carver): checks what the carving needs of each group, carves, and with `st` derives the four stages' groups.
-// bytes_per_sample (1: bd 8, 2: bd 10) sizes the intra gather only; plan_stages takes a plain function, hence the two wrappers below.
-inline int inter_fast_search_walk_bd(const svt_hip_inter_fast_search_group* groups, int ngroups, int bytes_per_sample, Carver& sc, InterFastStages* st) {
+// bytes_per_sample (1: bd 8, 2: bd 10) sizes the intra gather only: the carved pieces are distortions, the same for either depth.
+inline int inter_fast_search_walk(int bytes_per_sample, const svt_hip_inter_fast_search_group* groups, int ngroups, Carver& sc, InterFastStages* st) {
     if (int rc = group_list_check(groups, ngroups)) return rc;
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_inter_fast_search_group& G = groups[g];
@@ -108,14 +108,16 @@ inline int inter_fast_search_walk_bd(const svt_hip_inter_fast_search_group* grou
     }
     return SVT_HIP_OK;
 }
-inline int inter_fast_search_walk8(const svt_hip_inter_fast_search_group* g, int n, Carver& sc, InterFastStages* st) { return inter_fast_search_walk_bd(g, n, 1, sc, st); }
-inline int inter_fast_search_walk16(const svt_hip_inter_fast_search_group* g, int n, Carver& sc, InterFastStages* st) { return inter_fast_search_walk_bd(g, n, 2, sc, st); }
+inline size_t inter_fast_search_scratch_bytes(const svt_hip_inter_fast_search_group* groups, int ngroups, int bytes_per_sample = 1) {
+    return scratch_bytes_of([=](auto* g, int n, Carver& sc, InterFastStages* st) { return inter_fast_search_walk(bytes_per_sample, g, n, sc, st); }, groups, ngroups);
+}
 
 // Everything the call checks before its first launch: bd, the scratch, then every stage's own check on the derived groups.
 inline int inter_fast_search_plan(const svt_hip_inter_fast_search_group* groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd,
                                   int metric, void* d_scratch, size_t scratch_bytes, InterFastStages* st) {
     if (bd != 8 && bd != 10) return set_err(SVT_HIP_ERR_INVALID, "bd %d (8 or 10)", bd);
-    if (int rc = plan_stages(bd == 8 ? inter_fast_search_walk8 : inter_fast_search_walk16, groups, ngroups, d_scratch, scratch_bytes, st)) return rc;
+    const auto walk = [bd](auto* g, int n, Carver& sc, InterFastStages* s) { return inter_fast_search_walk(bd == 8 ? 1 : 2, g, n, sc, s); };
+    if (int rc = plan_stages(walk, groups, ngroups, d_scratch, scratch_bytes, st)) return rc;
     if (int rc = inter_pred_check(st->dist.data(), (int)st->dist.size(), pic_width, pic_height, bd, metric)) return rc;
     if (int rc = inter_fast_pick_check(st->pick.data(), (int)st->pick.size(), metric)) return rc;
     return inter_pred_check(st->pred.data(), (int)st->pred.size(), pic_width, pic_height, bd, metric);

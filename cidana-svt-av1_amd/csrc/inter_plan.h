@@ -1,7 +1,7 @@
 // inter_plan.h — svt_hip_inter_pred_frame planned on the host: the argument checks, the tiling of a (plane, block size) group over the
 // waves of a workgroup, and the launch list, all derived before the first launch.  svt_hip_inter_pred.hip checks, plans, then enqueues
 // from the plan.  Plain C++17, no HIP header: a CPU program can include it (tests/c/inter_plan_host.cpp).  InterGeom is the one
-// statement of the tiling: inter_pred_kernel (kernel_inter_pred.h) derives the same numbers from the same two logarithms.
+// statement of the tiling: the kernels' ip_lane and ip_block (kernel_inter_steps.h) derive the same numbers from the same two logarithms.
 #pragma once
 #include <stdint.h>
 
@@ -76,6 +76,13 @@ namespace svthost {
 constexpr uint32_t kInterMaxSide = 16384;                   // picture sides (the clamp's 1/16-sample arithmetic stays far inside 32 bits)
 
 inline int inter_log2_side(int v) { return v == 4 ? 2 : v == 8 ? 3 : v == 16 ? 4 : v == 32 ? 5 : v == 64 ? 6 : -1; }
+// the two clauses every call of the family states (interp_plan.h too): the picture's sides, and the workgroups that `per_wg` blocks a
+// workgroup make of a group (64 bits: nblocks goes up to 2^32 - 1, the checks compare the count with kMaxLaunchWgs)
+inline int inter_picture_check(uint32_t pic_width, uint32_t pic_height) {
+    const bool bad = pic_width == 0 || pic_height == 0 || (pic_width & 7) || (pic_height & 7) || pic_width > kInterMaxSide || pic_height > kInterMaxSide;
+    return bad ? set_err(SVT_HIP_ERR_INVALID, "picture %u x %u: both sides must be multiples of 8, 8 .. %u", pic_width, pic_height, kInterMaxSide) : SVT_HIP_OK;
+}
+inline uint64_t inter_wgs(uint32_t nblocks, int per_wg) { return ((uint64_t)nblocks + (uint64_t)per_wg - 1) / (uint64_t)per_wg; }
 
 struct InterGroupPlan {
     int src;                 // index into the caller's list
@@ -89,8 +96,7 @@ inline int inter_pred_check(const svt_hip_inter_pred_group* groups, int ngroups,
     if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
     if (bd != 8 && bd != 10) return set_err(SVT_HIP_ERR_INVALID, "bd %d (8 or 10)", bd);
     if (metric != SVT_HIP_FAST_SAD && metric != SVT_HIP_FAST_SSD) return set_err(SVT_HIP_ERR_INVALID, "metric %d", metric);
-    if (pic_width == 0 || pic_height == 0 || (pic_width & 7) || (pic_height & 7) || pic_width > kInterMaxSide || pic_height > kInterMaxSide)
-        return set_err(SVT_HIP_ERR_INVALID, "picture %u x %u: both sides must be multiples of 8, 8 .. %u", pic_width, pic_height, kInterMaxSide);
+    if (int rc = inter_picture_check(pic_width, pic_height)) return rc;
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_inter_pred_group& G = groups[g];
         if (G.ss != 0 && G.ss != 1) return set_err(SVT_HIP_ERR_INVALID, "group %d: ss %d (0 luma, 1 chroma of 4:2:0)", g, G.ss);
@@ -107,7 +113,7 @@ inline int inter_pred_check(const svt_hip_inter_pred_group* groups, int ngroups,
             return set_err(SVT_HIP_ERR_INVALID, "group %d: misaligned buffer (d_dist 8 bytes, d_blk 4 bytes, a dense d_pred 16 bytes)", g);
         if (G.d_pred && G.pred_stride != 0 && G.pred_stride < pw) return set_err(SVT_HIP_ERR_INVALID, "group %d: pred_stride %u below the block width %u", g, G.pred_stride, pw);
         const svtdev::InterGeom ge = svtdev::inter_geom(lw - G.ss, lh - G.ss);
-        if (((uint64_t)G.nblocks + ge.blocks_per_wg - 1) / ge.blocks_per_wg > kMaxLaunchWgs) return set_err(SVT_HIP_ERR_INVALID, "group %d: nblocks %u too large", g, G.nblocks);
+        if (inter_wgs(G.nblocks, ge.blocks_per_wg) > kMaxLaunchWgs) return set_err(SVT_HIP_ERR_INVALID, "group %d: nblocks %u too large", g, G.nblocks);
     }
     return SVT_HIP_OK;
 }
@@ -124,7 +130,7 @@ inline int inter_pred_plan(const svt_hip_inter_pred_group* groups, int ngroups, 
         P.lw = inter_log2_side(G.bwidth) - G.ss;
         P.lh = inter_log2_side(G.bheight) - G.ss;
         P.geom = svtdev::inter_geom(P.lw, P.lh);
-        P.wgs = (uint32_t)(((uint64_t)G.nblocks + P.geom.blocks_per_wg - 1) / P.geom.blocks_per_wg);
+        P.wgs = (uint32_t)inter_wgs(G.nblocks, P.geom.blocks_per_wg);
     }
     return n;
 }

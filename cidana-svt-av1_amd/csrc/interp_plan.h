@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "inter_plan.h"
+#include "md_plan.h"
 
 namespace svtdev {
 constexpr int IS_NPAIR = 9;                                  // filter_sets (EbInterPrediction.c:3573)
@@ -58,17 +59,16 @@ namespace svthost {
 inline int interp_side_ok(int v) { return v == 8 || v == 16 || v == 32 || v == 64; }
 inline int interp_planes(int use_uv) { return use_uv ? 3 : 1; }
 inline size_t interp_sse_bytes(uint32_t nblocks, int use_uv) {       // a group's table, rounded up to the scratch's 16-byte grain
-    return (((size_t)nblocks * (size_t)interp_planes(use_uv) * svtdev::IS_NPAIR * sizeof(uint32_t)) + 15) & ~(size_t)15;
+    return align16((size_t)nblocks * (size_t)interp_planes(use_uv) * svtdev::IS_NPAIR * sizeof(uint32_t));
 }
 
 // Every group of an SSE call before the first launch.  allow_null_sse: the one-call search carves the table from its scratch.
 inline int interp_sse_check(const svt_hip_interp_sse_group* groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd, int use_uv,
                             bool allow_null_sse = false) {
-    if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
+    if (int rc = group_list_check(groups, ngroups)) return rc;
     if (bd != 8) return set_err(SVT_HIP_ERR_INVALID, "bd %d (the filter search is pinned for 8-bit only)", bd);
     if (use_uv != 0 && use_uv != 1) return set_err(SVT_HIP_ERR_INVALID, "use_uv %d", use_uv);
-    if (pic_width == 0 || pic_height == 0 || (pic_width & 7) || (pic_height & 7) || pic_width > kInterMaxSide || pic_height > kInterMaxSide)
-        return set_err(SVT_HIP_ERR_INVALID, "picture %u x %u: both sides must be multiples of 8, 8 .. %u", pic_width, pic_height, kInterMaxSide);
+    if (int rc = inter_picture_check(pic_width, pic_height)) return rc;
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_interp_sse_group& G = groups[g];
         if (!interp_side_ok(G.bwidth) || !interp_side_ok(G.bheight))
@@ -80,14 +80,14 @@ inline int interp_sse_check(const svt_hip_interp_sse_group* groups, int ngroups,
         for (int p = 0; p < interp_planes(use_uv); p++)
             if (!G.d_ref[0][p] || !G.d_src[p]) return set_err(SVT_HIP_ERR_INVALID, "group %d: NULL d_ref[0][%d] or d_src[%d]", g, p, p);
         const svtdev::InterGeom ge = svtdev::inter_geom(inter_log2_side(G.bwidth), inter_log2_side(G.bheight));
-        if (((uint64_t)G.nblocks + ge.blocks_per_wg - 1) / ge.blocks_per_wg > kMaxLaunchWgs) return set_err(SVT_HIP_ERR_INVALID, "group %d: nblocks %u too large", g, G.nblocks);
+        if (inter_wgs(G.nblocks, ge.blocks_per_wg) > kMaxLaunchWgs) return set_err(SVT_HIP_ERR_INVALID, "group %d: nblocks %u too large", g, G.nblocks);
     }
     return SVT_HIP_OK;
 }
 
 // from_search: an empty group of the one-call search has no table to point at.
 inline int interp_decide_check(const svt_hip_interp_decide_group* groups, int ngroups, const svt_hip_interp_params* params, bool from_search = false) {
-    if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
+    if (int rc = group_list_check(groups, ngroups)) return rc;
     if (!params || !params->d_rates || ((uintptr_t)params->d_rates & 3)) return set_err(SVT_HIP_ERR_INVALID, "NULL params or d_rates (4-byte aligned)");
     if (params->mode < SVT_HIP_INTERP_DUAL_FAST || params->mode > SVT_HIP_INTERP_SINGLE) return set_err(SVT_HIP_ERR_INVALID, "mode %d", params->mode);
     if (params->use_uv != 0 && params->use_uv != 1) return set_err(SVT_HIP_ERR_INVALID, "use_uv %d", params->use_uv);
@@ -119,7 +119,7 @@ inline int interp_sse_enqueue(const svt_hip_interp_sse_group* groups, int ngroup
         for (int p = 0; p < planes; p++) {
             const int ss = p ? 1 : 0, lw = inter_log2_side(G.bwidth) - ss, lh = inter_log2_side(G.bheight) - ss;
             const svtdev::InterGeom ge = svtdev::inter_geom(lw, lh);
-            svtdev::InterpSseGroupDev* D = tab.add((uint32_t)(((uint64_t)G.nblocks + ge.blocks_per_wg - 1) / ge.blocks_per_wg), launch);
+            svtdev::InterpSseGroupDev* D = tab.add((uint32_t)inter_wgs(G.nblocks, ge.blocks_per_wg), launch);
             if (!D) return tab.rc;
             D->ref[0] = G.d_ref[0][p]; D->ref[1] = G.d_ref[1][p]; D->src = G.d_src[p]; D->blk = G.d_blk;
             D->sse = G.d_sse + p * svtdev::IS_NPAIR;
@@ -140,7 +140,7 @@ inline int interp_decide_enqueue(const svt_hip_interp_decide_group* groups, int 
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_interp_decide_group& G = groups[g];
         if (G.nblocks == 0) continue;
-        svtdev::InterpDecideGroupDev* D = tab.add((uint32_t)(((uint64_t)G.nblocks + svtdev::ID_THREADS - 1) / svtdev::ID_THREADS), launch);
+        svtdev::InterpDecideGroupDev* D = tab.add((uint32_t)inter_wgs(G.nblocks, svtdev::ID_THREADS), launch);
         if (!D) return tab.rc;
         D->sse = G.d_sse; D->ctx = G.d_ctx; D->searchable = G.d_searchable; D->decision = (unsigned long long*)G.d_decision;
         D->blk = G.d_blk; D->blk_out = G.d_blk_out; D->nblocks = G.nblocks;
@@ -150,44 +150,35 @@ inline int interp_decide_enqueue(const svt_hip_interp_decide_group* groups, int 
 }
 
 // ---- the one-call search: scratch and the two stages' groups ----
-// bytes the call carves: per non-empty group without a table of its own, in group order, interp_sse_bytes.  0: bad parameters or
-// nothing to carve.
-inline size_t interp_search_scratch_bytes(const svt_hip_interp_search_group* groups, int ngroups, int use_uv) {
-    if (ngroups <= 0 || !groups || (use_uv != 0 && use_uv != 1)) return 0;
-    size_t total = 0;
-    for (int g = 0; g < ngroups; g++)
-        if (groups[g].sse.nblocks && !groups[g].sse.d_sse) total += interp_sse_bytes(groups[g].sse.nblocks, use_uv);
-    return total;
-}
-
-struct InterpStages {
-    std::vector<svt_hip_interp_sse_group> sg;
-    std::vector<svt_hip_interp_decide_group> dg;
-};
-
-// Fills both stages' groups, the tables the caller does not keep carved from d_scratch.  The stages' own checks run on the result.
-inline int interp_search_plan(const svt_hip_interp_search_group* groups, int ngroups, const svt_hip_interp_params* params, void* d_scratch,
-                              size_t scratch_bytes, InterpStages* st) {
-    if (ngroups < 0 || (ngroups > 0 && !groups)) return set_err(SVT_HIP_ERR_INVALID, "NULL group list");
-    if (!params || (params->use_uv != 0 && params->use_uv != 1)) return set_err(SVT_HIP_ERR_INVALID, "NULL params or use_uv");
-    const size_t need = interp_search_scratch_bytes(groups, ngroups, params->use_uv);
-    if (need && (!d_scratch || ((uintptr_t)d_scratch & 15) || scratch_bytes < need))
-        return set_err(SVT_HIP_ERR_INVALID, "scratch NULL, not 16-byte aligned or below the %zu bytes of svt_hip_interp_search_scratch_bytes", need);
-    st->sg.resize((size_t)ngroups);
-    st->dg.resize((size_t)ngroups);
-    char* at = (char*)d_scratch;
+struct InterpStages { std::vector<svt_hip_interp_sse_group> sg; std::vector<svt_hip_interp_decide_group> dg; };      // an entry per group, empty ones included
+// The walk (md_plan.h's Carver): per non-empty group without a table of its own, in group order, its table of interp_sse_bytes; with
+// `st` both stages' groups.  The stages' own checks run on the result.
+inline int interp_search_walk(int use_uv, const svt_hip_interp_search_group* groups, int ngroups, Carver& sc, InterpStages* st) {
+    if (int rc = group_list_check(groups, ngroups)) return rc;
+    if (use_uv != 0 && use_uv != 1) return set_err(SVT_HIP_ERR_INVALID, "use_uv %d", use_uv);
+    if (st) { st->sg.resize((size_t)ngroups); st->dg.resize((size_t)ngroups); }
     for (int g = 0; g < ngroups; g++) {
         const svt_hip_interp_search_group& G = groups[g];
-        svt_hip_interp_sse_group& S = st->sg[(size_t)g] = G.sse;
-        if (S.nblocks && !S.d_sse) {
-            S.d_sse = (uint32_t*)at;
-            at += interp_sse_bytes(S.nblocks, params->use_uv);
-        }
-        svt_hip_interp_decide_group& D = st->dg[(size_t)g] = svt_hip_interp_decide_group{};
+        svt_hip_interp_sse_group S = G.sse;
+        if (S.nblocks && !S.d_sse) sc.piece(S.d_sse, interp_sse_bytes(S.nblocks, use_uv));
+        if (!st) continue;
+        svt_hip_interp_decide_group D{};
         D.bwidth = S.bwidth; D.bheight = S.bheight; D.nblocks = S.nblocks; D.d_sse = S.d_sse; D.d_ctx = G.d_ctx; D.d_searchable = G.d_searchable;
         D.d_decision = G.d_decision; D.d_blk = S.d_blk; D.d_blk_out = G.d_blk_out;
+        st->sg[(size_t)g] = S; st->dg[(size_t)g] = D;
     }
     return SVT_HIP_OK;
+}
+inline size_t interp_search_scratch_bytes(const svt_hip_interp_search_group* groups, int ngroups, int use_uv) {      // 0: bad parameters or nothing to carve
+    return scratch_bytes_of([=](auto* g, int n, Carver& sc, InterpStages* st) { return interp_search_walk(use_uv, g, n, sc, st); }, groups, ngroups);
+}
+// The group list, the parameters, then the scratch: sized, accepted or refused, carved (plan_stages).
+inline int interp_search_plan(const svt_hip_interp_search_group* groups, int ngroups, const svt_hip_interp_params* params, void* d_scratch,
+                              size_t scratch_bytes, InterpStages* st) {
+    if (int rc = group_list_check(groups, ngroups)) return rc;
+    if (!params) return set_err(SVT_HIP_ERR_INVALID, "NULL params");
+    const auto walk = [params](auto* g, int n, Carver& sc, InterpStages* s) { return interp_search_walk(params->use_uv, g, n, sc, s); };
+    return plan_stages(walk, groups, ngroups, d_scratch, scratch_bytes, st);
 }
 
 }  // namespace svthost

@@ -17,78 +17,13 @@
 // Work split (inter_plan.h, InterGeom): a lane owns 4 samples of a row of a tile of at most 16 x 16; small blocks share a wave.  Per list
 // a slot's lanes stage its (tw + 7) x (th + 7) window into LDS as uint16 (every load of a batch of 8 issued before the first LDS write),
 // run the first pass over its th + 7 rows into int16 rows in LDS, and the second pass into registers.  List 0's result stays in four
-// registers while list 1 goes through the same LDS: the compound intermediate never reaches memory.
+// registers while list 1 goes through the same LDS: the compound intermediate never reaches memory.  The tap tables, the clamp, the
+// lane geometry, a round's block, the window and the first pass are kernel_inter_steps.h's, shared with interp_sse_kernel.
 #pragma once
-#include "dev_common.h"
 #include "group_table.h"
-#include "inter_plan.h"
+#include "kernel_inter_steps.h"
 
 namespace svtdev {
-
-// The sub-pel kernels, this project's statement of AV1's interpolation filters (AV1 spec 7.11.3.4; the reference's copies are
-// sub_pel_filters_8 / _8smooth / _8sharp, bilinear_filters, sub_pel_filters_4 / _4smooth, EbInterPrediction.c:106-127, :878-922).
-// Rows: InterpFilter 0 .. 3 (REGULAR, SMOOTH, SHARP, BILINEAR), then the two 4-tap tables a dimension <= 4 takes instead (REGULAR and
-// SHARP -> 4, SMOOTH -> 5).  tests/test_inter_pred_cpu.py reads the rows between the two marker lines and compares them with the
-// tables recorded from the compiled reference (tests/golden/inter_pred.npz).
-// INTER-TAPS-BEGIN
-static __device__ const int16_t kInterTaps[6][16][8] __attribute__((aligned(16))) = {
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 2, -6, 126, 8, -2, 0, 0}, {0, 2, -10, 122, 18, -4, 0, 0}, {0, 2, -12, 116, 28, -8, 2, 0},
-     {0, 2, -14, 110, 38, -10, 2, 0}, {0, 2, -14, 102, 48, -12, 2, 0}, {0, 2, -16, 94, 58, -12, 2, 0}, {0, 2, -14, 84, 66, -12, 2, 0},
-     {0, 2, -14, 76, 76, -14, 2, 0}, {0, 2, -12, 66, 84, -14, 2, 0}, {0, 2, -12, 58, 94, -16, 2, 0}, {0, 2, -12, 48, 102, -14, 2, 0},
-     {0, 2, -10, 38, 110, -14, 2, 0}, {0, 2, -8, 28, 116, -12, 2, 0}, {0, 0, -4, 18, 122, -10, 2, 0}, {0, 0, -2, 8, 126, -6, 2, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 2, 28, 62, 34, 2, 0, 0}, {0, 0, 26, 62, 36, 4, 0, 0}, {0, 0, 22, 62, 40, 4, 0, 0},
-     {0, 0, 20, 60, 42, 6, 0, 0}, {0, 0, 18, 58, 44, 8, 0, 0}, {0, 0, 16, 56, 46, 10, 0, 0}, {0, -2, 16, 54, 48, 12, 0, 0},
-     {0, -2, 14, 52, 52, 14, -2, 0}, {0, 0, 12, 48, 54, 16, -2, 0}, {0, 0, 10, 46, 56, 16, 0, 0}, {0, 0, 8, 44, 58, 18, 0, 0},
-     {0, 0, 6, 42, 60, 20, 0, 0}, {0, 0, 4, 40, 62, 22, 0, 0}, {0, 0, 4, 36, 62, 26, 0, 0}, {0, 0, 2, 34, 62, 28, 2, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {-2, 2, -6, 126, 8, -2, 2, 0}, {-2, 6, -12, 124, 16, -6, 4, -2}, {-2, 8, -18, 120, 26, -10, 6, -2},
-     {-4, 10, -22, 116, 38, -14, 6, -2}, {-4, 10, -22, 108, 48, -18, 8, -2}, {-4, 10, -24, 100, 60, -20, 8, -2}, {-4, 10, -24, 90, 70, -22, 10, -2},
-     {-4, 12, -24, 80, 80, -24, 12, -4}, {-2, 10, -22, 70, 90, -24, 10, -4}, {-2, 8, -20, 60, 100, -24, 10, -4}, {-2, 8, -18, 48, 108, -22, 10, -4},
-     {-2, 6, -14, 38, 116, -22, 10, -4}, {-2, 6, -10, 26, 120, -18, 8, -2}, {-2, 4, -6, 16, 124, -12, 6, -2}, {0, 2, -2, 8, 126, -6, 2, -2}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, 0, 120, 8, 0, 0, 0}, {0, 0, 0, 112, 16, 0, 0, 0}, {0, 0, 0, 104, 24, 0, 0, 0},
-     {0, 0, 0, 96, 32, 0, 0, 0}, {0, 0, 0, 88, 40, 0, 0, 0}, {0, 0, 0, 80, 48, 0, 0, 0}, {0, 0, 0, 72, 56, 0, 0, 0},
-     {0, 0, 0, 64, 64, 0, 0, 0}, {0, 0, 0, 56, 72, 0, 0, 0}, {0, 0, 0, 48, 80, 0, 0, 0}, {0, 0, 0, 40, 88, 0, 0, 0},
-     {0, 0, 0, 32, 96, 0, 0, 0}, {0, 0, 0, 24, 104, 0, 0, 0}, {0, 0, 0, 16, 112, 0, 0, 0}, {0, 0, 0, 8, 120, 0, 0, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, -4, 126, 8, -2, 0, 0}, {0, 0, -8, 122, 18, -4, 0, 0}, {0, 0, -10, 116, 28, -6, 0, 0},
-     {0, 0, -12, 110, 38, -8, 0, 0}, {0, 0, -12, 102, 48, -10, 0, 0}, {0, 0, -14, 94, 58, -10, 0, 0}, {0, 0, -12, 84, 66, -10, 0, 0},
-     {0, 0, -12, 76, 76, -12, 0, 0}, {0, 0, -10, 66, 84, -12, 0, 0}, {0, 0, -10, 58, 94, -14, 0, 0}, {0, 0, -10, 48, 102, -12, 0, 0},
-     {0, 0, -8, 38, 110, -12, 0, 0}, {0, 0, -6, 28, 116, -10, 0, 0}, {0, 0, -4, 18, 122, -8, 0, 0}, {0, 0, -2, 8, 126, -4, 0, 0}},
-    {{0, 0, 0, 128, 0, 0, 0, 0}, {0, 0, 30, 62, 34, 2, 0, 0}, {0, 0, 26, 62, 36, 4, 0, 0}, {0, 0, 22, 62, 40, 4, 0, 0},
-     {0, 0, 20, 60, 42, 6, 0, 0}, {0, 0, 18, 58, 44, 8, 0, 0}, {0, 0, 16, 56, 46, 10, 0, 0}, {0, 0, 14, 54, 48, 12, 0, 0},
-     {0, 0, 12, 52, 52, 12, 0, 0}, {0, 0, 12, 48, 54, 14, 0, 0}, {0, 0, 10, 46, 56, 16, 0, 0}, {0, 0, 8, 44, 58, 18, 0, 0},
-     {0, 0, 6, 42, 60, 20, 0, 0}, {0, 0, 4, 40, 62, 22, 0, 0}, {0, 0, 4, 36, 62, 26, 0, 0}, {0, 0, 2, 34, 62, 30, 0, 0}},
-};
-// INTER-TAPS-END
-
-typedef unsigned ip_u1 __attribute__((aligned(1)));
-typedef unsigned ip_v2u __attribute__((ext_vector_type(2), aligned(1)));
-typedef unsigned ip_v4a4 __attribute__((ext_vector_type(4), aligned(4)));       // a block record: d_blk is 4-byte aligned
-
-// av1_get_interp_filter_params_with_block_size (:940-949): the table of InterpFilter f (clamped to 0 .. 3) for a plane dimension
-__device__ __forceinline__ int ip_table(int f, bool small) {
-    f = f > 3 ? 3 : f;
-    return !small || f == 3 ? f : (f == 1 ? 5 : 4);
-}
-
-// One list's vector for one direction, as clamp_mv_to_umv_border_sb (:80-102) leaves it: 1/16 plane sample.  org = the block's LUMA
-// origin, lsize = its LUMA side, psize = the plane's, pic = the picture's luma side.
-__device__ __forceinline__ int ip_clamp_mv(int mv, int org, int lsize, int psize, int pic, int ss) {
-    const int mi = org >> 2;
-    const int to_lo = -(mi * 32), to_hi = ((pic >> 2) - (lsize >> 2) - mi) * 32;       // mb_to_left / _right_edge, EbAdaptiveMotionVectorPrediction.c:1169-1172
-    const int sc = 1 << (1 - ss);
-    const int spel_lo = (4 + psize) << 4, spel_hi = spel_lo - 16;                       // AOM_INTERP_EXTEND = 4, SUBPEL_BITS = 4
-    const int v = (int16_t)(mv * sc);
-    const int lo = to_lo * sc - spel_lo, hi = to_hi * sc + spel_hi;
-    return (int16_t)(v < lo ? lo : (v > hi ? hi : v));
-}
-
-struct IpTaps { int f[8]; };
-__device__ __forceinline__ IpTaps ip_load_taps(int table, int phase) {
-    const uint4 r = *reinterpret_cast<const uint4*>(&kInterTaps[table][phase][0]);
-    IpTaps t;
-    t.f[0] = (int16_t)(r.x & 0xffff); t.f[1] = (int)r.x >> 16; t.f[2] = (int16_t)(r.y & 0xffff); t.f[3] = (int)r.y >> 16;
-    t.f[4] = (int16_t)(r.z & 0xffff); t.f[5] = (int)r.z >> 16; t.f[6] = (int16_t)(r.w & 0xffff); t.f[7] = (int)r.w >> 16;
-    return t;
-}
 
 template <typename PIX>
 __global__ __launch_bounds__(IP_THREADS) void inter_pred_kernel(const InterPredDesc fd) {
@@ -101,14 +36,10 @@ __global__ __launch_bounds__(IP_THREADS) void inter_pred_kernel(const InterPredD
     if (gi >= fd.ngroups) return;
     const InterPredGroupDev& D = fd.g[gi];
     const InterGeom ge = inter_geom(D.lw, D.lh);
-    const int ss = D.ss, w = 1 << D.lw, h = 1 << D.lh, tw = 1 << ge.ltw, th = 1 << ge.lth;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int L = 1 << ge.llanes, slot = lane >> ge.llanes, li = lane & (L - 1);
-    const int row = li >> (ge.ltw - 2), col4 = (li & ((tw >> 2) - 1)) << 2;
-    const int PW = tw + 8, wd = tw + 7, ws = wd * (th + 7);
-    const uint32_t recip = 65536u / (uint32_t)wd + 1;          // e / wd == (e * recip) >> 16 for e < ws <= 529
-    uint16_t* const win = &s_win[wave][slot * PW * (th + 7)];
-    int16_t* const hrb = &s_hr[wave][slot * tw * (th + 7)];
+    const IpLane T = ip_lane(ge, D.ss, D.lw, D.lh);
+    const int w = T.w, h = T.h, tw = T.tw, lane = T.lane, wave = T.wave, row = T.row, col4 = T.col4;
+    uint16_t* const win = &s_win[wave][T.slot * T.PW * (T.th + 7)];
+    int16_t* const hrb = &s_hr[wave][T.slot * tw * (T.th + 7)];
     const int maxv = (1 << fd.bd) - 1;
     const bool want_dist = D.dist != nullptr;
 
@@ -117,29 +48,12 @@ __global__ __launch_bounds__(IP_THREADS) void inter_pred_kernel(const InterPredD
     bool active = false;
 #pragma unroll 1
     for (int r = 0; r < ge.rounds; r++) {
-        const uint32_t t = (uint32_t)(r * IP_WAVES + wave) * ge.slots + slot;           // tile of the workgroup
-        const uint32_t b = bid * ge.blocks_per_wg + (ge.rounds > 1 ? 0 : t >> ge.ltpb);
-        const int ti = t & ((1 << ge.ltpb) - 1);
-        const int tx = (ti & ((w >> ge.ltw) - 1)) << ge.ltw, ty = (ti >> (D.lw - ge.ltw)) << ge.lth;
-        active = b < D.nblocks;
-        blk_of_lane = b;
-
-        // ---- the block: clamp, addressing, filters (device bytes clamped: an out-of-range one changes the prediction, never the window) ----
-        ip_v4a4 raw = {0, 0, 0, 0};
-        if (active) raw = *reinterpret_cast<const ip_v4a4*>(D.blk + b);
-        int bx = raw.x & 0xffff, by = raw.x >> 16;
-        bx = min(bx, (int)fd.pic_w - (w << ss));
-        by = min(by, (int)fd.pic_h - (h << ss));
-        const int dir = min((int)(raw.w & 0xff), 2);
-        const int fxi = (raw.w >> 8) & 0xff, fyi = (raw.w >> 16) & 0xff;
-        const int tabx = ip_table(fxi, w <= 4), taby = ip_table(fyi, h <= 4);
-        const int px = ss ? ((bx >> 3) << 3) >> 1 : bx, py = ss ? ((by >> 3) << 3) >> 1 : by;      // :1282, :1310
-        const bool use0 = active && dir != 1, use1 = active && dir != 0;
-        const int qx0 = ip_clamp_mv((int16_t)(raw.y & 0xffff), bx, w << ss, w, fd.pic_w, ss);
-        const int qy0 = ip_clamp_mv((int)raw.y >> 16, by, h << ss, h, fd.pic_h, ss);
-        const int qx1 = ip_clamp_mv((int16_t)(raw.z & 0xffff), bx, w << ss, w, fd.pic_w, ss);
-        const int qy1 = ip_clamp_mv((int)raw.z >> 16, by, h << ss, h, fd.pic_h, ss);
-        const bool frac = (use0 && ((qx0 | qy0) & 15)) || (use1 && ((qx1 | qy1) & 15));
+        const IpBlock B = ip_block(ge, T, r, bid, D.blk, D.nblocks, fd.pic_w, fd.pic_h);
+        active = B.active;
+        blk_of_lane = B.b;
+        const int tabx = ip_table((B.w3 >> 8) & 0xff, w <= 4), taby = ip_table((B.w3 >> 16) & 0xff, h <= 4);      // filter_x, filter_y
+        const int dir = B.dir, px = B.px, py = B.py, tx = B.tx, ty = B.ty;
+        const bool frac = (B.use0 && ((B.qx0 | B.qy0) & 15)) || (B.use1 && ((B.qx1 | B.qy1) & 15));
         const bool filter_wave = __any(frac);
 
         // one list into V (named registers: the two calls below are the unrolled loop over the lists)
@@ -156,49 +70,9 @@ __global__ __launch_bounds__(IP_THREADS) void inter_pred_kernel(const InterPredD
                 }
                 return;
             }
-            // ---- stage the window: rows -3 .. th + 3, columns -3 .. tw + 3 ----
-            const PIX* const wbase = ref - 3ll * D.ref_stride - 3;
-#pragma unroll 1
-            for (int e0 = li; e0 < ws; e0 += 8 * L) {
-                PIX v[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int e = e0 + k * L;
-                    const int rr = (int)(((uint32_t)e * recip) >> 16), cc = e - rr * wd;
-                    v[k] = use_l && e < ws ? wbase[(long long)rr * D.ref_stride + cc] : (PIX)0;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int e = e0 + k * L;
-                    const int rr = (int)(((uint32_t)e * recip) >> 16), cc = e - rr * wd;
-                    if (e < ws) win[rr * PW + cc] = v[k];
-                }
-            }
-            wave_lds_fence();
-            // ---- first pass: th + 7 rows of tw, four outputs of a row per lane and step ----
-            {
-                const IpTaps fx = ip_load_taps(tabx, qxl & 15);
-#pragma unroll 1
-                for (int hrow = row; hrow < th + 7; hrow += th) {
-                    const uint2* p = reinterpret_cast<const uint2*>(&win[hrow * PW + col4]);
-                    const uint2 a = p[0], bq = p[1], c = p[2];
-                    const int s[12] = {(int)(a.x & 0xffff), (int)(a.x >> 16), (int)(a.y & 0xffff), (int)(a.y >> 16),
-                                       (int)(bq.x & 0xffff), (int)(bq.x >> 16), (int)(bq.y & 0xffff), (int)(bq.y >> 16),
-                                       (int)(c.x & 0xffff), (int)(c.x >> 16), (int)(c.y & 0xffff), (int)(c.y >> 16)};
-                    int o[4];
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        int acc = 4;
-#pragma unroll
-                        for (int k = 0; k < 8; k++) acc += fx.f[k] * s[j + k];
-                        o[j] = acc >> 3;
-                    }
-                    uint2 pk;
-                    pk.x = (uint32_t)(o[0] & 0xffff) | ((uint32_t)o[1] << 16);
-                    pk.y = (uint32_t)(o[2] & 0xffff) | ((uint32_t)o[3] << 16);
-                    *reinterpret_cast<uint2*>(&hrb[hrow * tw + col4]) = pk;
-                }
-            }
+            // ---- the window, then the first pass over it (kernel_inter_steps.h) ----
+            ip_stage_window(T, win, ref - 3ll * D.ref_stride - 3, D.ref_stride, use_l);
+            ip_first_pass(T, win, hrb, ip_load_taps(tabx, qxl & 15));
             wave_lds_fence();
             // ---- second pass: this lane's four samples ----
             {
@@ -215,8 +89,8 @@ __global__ __launch_bounds__(IP_THREADS) void inter_pred_kernel(const InterPredD
             wave_lds_fence();                       // list 1 stages over list 0's window
         };
         int V0[4] = {0, 0, 0, 0}, V1[4] = {0, 0, 0, 0};
-        one_list(V0, use0, qx0, qy0, D.ref[0]);
-        one_list(V1, use1, qx1, qy1, D.ref[1]);
+        one_list(V0, B.use0, B.qx0, B.qy0, D.ref[0]);
+        one_list(V1, B.use1, B.qx1, B.qy1, D.ref[1]);
 
         // ---- rounding (:175-178, :313-328), store, distortion ----
         int o[4];
@@ -229,7 +103,7 @@ __global__ __launch_bounds__(IP_THREADS) void inter_pred_kernel(const InterPredD
         }
         if (active && D.pred) {
             PIX* dst = reinterpret_cast<PIX*>(D.pred);
-            if (D.pred_stride == 0) dst += (size_t)b * (size_t)(w * h) + (size_t)((ty + row) * w + tx + col4);
+            if (D.pred_stride == 0) dst += (size_t)B.b * (size_t)(w * h) + (size_t)((ty + row) * w + tx + col4);
             else dst += (size_t)(py + ty + row) * D.pred_stride + (size_t)(px + tx + col4);
             if constexpr (sizeof(PIX) == 1) {
                 *reinterpret_cast<ip_u1*>(dst) = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24);

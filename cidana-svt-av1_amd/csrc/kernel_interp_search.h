@@ -1,8 +1,9 @@
 // kernel_interp_search.h — the interpolation filter search of mode decision (interpolation_filter_search, EbInterPrediction.c:3578-3917).
 //
 // interp_sse_kernel: for a block record and a plane, the SSE against the source of the nine predictions inter_pred_kernel
-// (kernel_inter_pred.h) would write with filter pair i = 3 * filter_y + filter_x, filter_sets[i] of :3573.  Same tiling (InterGeom), same
-// clamp, addressing, tap tables and arithmetic (hr, V and the two rounding lines stated there); what differs is what is shared.  Per list
+// (kernel_inter_pred.h) would write with filter pair i = 3 * filter_y + filter_x, filter_sets[i] of :3573.  The tiling, the clamp, the
+// addressing, the tap tables, the window and the first pass are the text that kernel runs (kernel_inter_steps.h), the second pass and
+// the two rounding lines the arithmetic stated there (hr, V); what differs is how often each step runs.  Per list
 // a slot's lanes stage the (tw + 7) x (th + 7) window into LDS ONCE, run the THREE horizontal passes into three sets of int16 rows, and
 // each lane runs the NINE vertical passes over its four samples: the eight rows of a horizontal set are read once and feed the three
 // vertical filters.  A full-pel direction takes phase 0, {0, 0, 0, 128, 0, 0, 0, 0} in every table, which is the copy exactly, so the wave
@@ -14,8 +15,9 @@
 // interp_decide_kernel: the walk over that table, a thread a block, as svt_hip_dsp.h states it line by line.  model_rd_from_sse is
 // fp_model_rd (model_rd.h, shared with fast_pick_kernel), included, not restated.
 #pragma once
+#include "group_table.h"
 #include "interp_plan.h"
-#include "kernel_inter_pred.h"
+#include "kernel_inter_steps.h"
 #include "model_rd.h"
 
 namespace svtdev {
@@ -30,14 +32,10 @@ __global__ __launch_bounds__(IP_THREADS) void interp_sse_kernel(const InterpSseD
     if (gi >= fd.ngroups) return;
     const InterpSseGroupDev& D = fd.g[gi];
     const InterGeom ge = inter_geom(D.lw, D.lh);
-    const int ss = D.ss, w = 1 << D.lw, h = 1 << D.lh, tw = 1 << ge.ltw, th = 1 << ge.lth;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int L = 1 << ge.llanes, slot = lane >> ge.llanes, li = lane & (L - 1);
-    const int row = li >> (ge.ltw - 2), col4 = (li & ((tw >> 2) - 1)) << 2;
-    const int PW = tw + 8, wd = tw + 7, ws = wd * (th + 7);
-    const uint32_t recip = 65536u / (uint32_t)wd + 1;          // e / wd == (e * recip) >> 16 for e < ws <= 529
-    uint16_t* const win = &s_win[wave][slot * PW * (th + 7)];
-    int16_t* const hrb = &s_hr[wave][slot * tw * (th + 7)];   // filter f's rows: hrb + f * IP_LDS_HR
+    const IpLane T = ip_lane(ge, D.ss, D.lw, D.lh);
+    const int w = T.w, h = T.h, tw = T.tw, lane = T.lane, wave = T.wave, row = T.row, col4 = T.col4;
+    uint16_t* const win = &s_win[wave][T.slot * T.PW * (T.th + 7)];
+    int16_t* const hrb = &s_hr[wave][T.slot * tw * (T.th + 7)];   // filter f's rows: hrb + f * IP_LDS_HR
 
     uint32_t sse[IS_NPAIR];
 #pragma unroll
@@ -46,26 +44,10 @@ __global__ __launch_bounds__(IP_THREADS) void interp_sse_kernel(const InterpSseD
     bool active = false;
 #pragma unroll 1
     for (int r = 0; r < ge.rounds; r++) {
-        const uint32_t t = (uint32_t)(r * IP_WAVES + wave) * ge.slots + slot;           // tile of the workgroup
-        const uint32_t b = bid * ge.blocks_per_wg + (ge.rounds > 1 ? 0 : t >> ge.ltpb);
-        const int ti = t & ((1 << ge.ltpb) - 1);
-        const int tx = (ti & ((w >> ge.ltw) - 1)) << ge.ltw, ty = (ti >> (D.lw - ge.ltw)) << ge.lth;
-        active = b < D.nblocks;
-        blk_of_lane = b;
-
-        // ---- the block: clamp and addressing, as inter_pred_kernel ----
-        ip_v4a4 raw = {0, 0, 0, 0};
-        if (active) raw = *reinterpret_cast<const ip_v4a4*>(D.blk + b);
-        int bx = raw.x & 0xffff, by = raw.x >> 16;
-        bx = min(bx, (int)fd.pic_w - (w << ss));
-        by = min(by, (int)fd.pic_h - (h << ss));
-        const int dir = min((int)(raw.w & 0xff), 2);
-        const int px = ss ? ((bx >> 3) << 3) >> 1 : bx, py = ss ? ((by >> 3) << 3) >> 1 : by;
-        const bool use0 = active && dir != 1, use1 = active && dir != 0;
-        const int qx0 = ip_clamp_mv((int16_t)(raw.y & 0xffff), bx, w << ss, w, fd.pic_w, ss);
-        const int qy0 = ip_clamp_mv((int)raw.y >> 16, by, h << ss, h, fd.pic_h, ss);
-        const int qx1 = ip_clamp_mv((int16_t)(raw.z & 0xffff), bx, w << ss, w, fd.pic_w, ss);
-        const int qy1 = ip_clamp_mv((int)raw.z >> 16, by, h << ss, h, fd.pic_h, ss);
+        const IpBlock B = ip_block(ge, T, r, bid, D.blk, D.nblocks, fd.pic_w, fd.pic_h);
+        active = B.active;
+        blk_of_lane = B.b;
+        const int dir = B.dir, px = B.px, py = B.py, tx = B.tx, ty = B.ty;
 
         // the lane's four source samples
         int sp[4] = {0, 0, 0, 0};
@@ -83,50 +65,10 @@ __global__ __launch_bounds__(IP_THREADS) void interp_sse_kernel(const InterpSseD
             if (!__any(use_l)) return;
             const long long org = (long long)(py + ty + (qyl >> 4)) * (long long)D.ref_stride + (px + tx + (qxl >> 4));
             const uint8_t* const wbase = plane + (use_l ? org - 3ll * D.ref_stride - 3 : 0);
-            // ---- stage the window once: rows -3 .. th + 3, columns -3 .. tw + 3 ----
+            // ---- the window once, then the three first passes over it, one per horizontal filter (kernel_inter_steps.h) ----
+            ip_stage_window(T, win, wbase, D.ref_stride, use_l);
 #pragma unroll 1
-            for (int e0 = li; e0 < ws; e0 += 8 * L) {
-                uint8_t v[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int e = e0 + k * L;
-                    const int rr = (int)(((uint32_t)e * recip) >> 16), cc = e - rr * wd;
-                    v[k] = use_l && e < ws ? wbase[(long long)rr * D.ref_stride + cc] : (uint8_t)0;
-                }
-#pragma unroll
-                for (int k = 0; k < 8; k++) {
-                    const int e = e0 + k * L;
-                    const int rr = (int)(((uint32_t)e * recip) >> 16), cc = e - rr * wd;
-                    if (e < ws) win[rr * PW + cc] = v[k];
-                }
-            }
-            wave_lds_fence();
-            // ---- three first passes: th + 7 rows of tw per horizontal filter ----
-#pragma unroll 1
-            for (int f = 0; f < 3; f++) {
-                const IpTaps fx = ip_load_taps(ip_table(f, w <= 4), qxl & 15);
-                int16_t* const hf = hrb + f * IP_LDS_HR;
-#pragma unroll 1
-                for (int hrow = row; hrow < th + 7; hrow += th) {
-                    const uint2* p = reinterpret_cast<const uint2*>(&win[hrow * PW + col4]);
-                    const uint2 a = p[0], bq = p[1], c = p[2];
-                    const int s[12] = {(int)(a.x & 0xffff), (int)(a.x >> 16), (int)(a.y & 0xffff), (int)(a.y >> 16),
-                                       (int)(bq.x & 0xffff), (int)(bq.x >> 16), (int)(bq.y & 0xffff), (int)(bq.y >> 16),
-                                       (int)(c.x & 0xffff), (int)(c.x >> 16), (int)(c.y & 0xffff), (int)(c.y >> 16)};
-                    int o[4];
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        int acc = 4;
-#pragma unroll
-                        for (int k = 0; k < 8; k++) acc += fx.f[k] * s[j + k];
-                        o[j] = acc >> 3;
-                    }
-                    uint2 pk;
-                    pk.x = (uint32_t)(o[0] & 0xffff) | ((uint32_t)o[1] << 16);
-                    pk.y = (uint32_t)(o[2] & 0xffff) | ((uint32_t)o[3] << 16);
-                    *reinterpret_cast<uint2*>(&hf[hrow * tw + col4]) = pk;
-                }
-            }
+            for (int f = 0; f < 3; f++) ip_first_pass(T, win, hrb + f * IP_LDS_HR, ip_load_taps(ip_table(f, w <= 4), qxl & 15));
             wave_lds_fence();
             // ---- nine second passes: a horizontal set's eight rows feed the three vertical filters ----
             IpTaps fy[3];
@@ -170,8 +112,8 @@ __global__ __launch_bounds__(IP_THREADS) void interp_sse_kernel(const InterpSseD
             }
             wave_lds_fence();                       // the next list, or the next round, stages over these rows
         };
-        one_list(0, use0, qx0, qy0, D.ref[0]);
-        one_list(1, use1, qx1, qy1, D.ref[1]);
+        one_list(0, B.use0, B.qx0, B.qy0, D.ref[0]);
+        one_list(1, B.use1, B.qx1, B.qy1, D.ref[1]);
     }
 
     // ---- the nine sums: at most 1024 samples of a block per wave, 1024 * 255^2 < 2^32; a 64 x 64 block: 4096 * 255^2 < 2^32 ----

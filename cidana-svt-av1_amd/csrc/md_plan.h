@@ -310,16 +310,17 @@ struct Carver {
     template <typename T> void piece_present(T*& p, size_t bytes) { piece(p, bytes); if (!base) p = (T*)this; }
 };
 // A walk checks what the carving needs of each group (sizes and counts), carves, and with `st` appends the groups of the call's stages.
-// plan_stages: the walk without a base sizes the scratch, the scratch is accepted or refused, and only then the walk runs over it.
-template <typename G, typename St>
-size_t scratch_bytes_of(int (*walk)(const G*, int, Carver&, St*), const G* groups, int ngroups) {
+// plan_stages: the walk without a base sizes the scratch, the scratch is accepted or refused, and only then the walk runs over it.  The
+// walk is any callable int(const G*, int, Carver&, St*): a function, or a lambda that binds what else the call's walk depends on.
+template <typename Walk, typename G>
+size_t scratch_bytes_of(Walk&& walk, const G* groups, int ngroups) {
     Carver size{nullptr};
     return walk(groups, ngroups, size, nullptr) == SVT_HIP_OK ? size.used : 0;
 }
-template <typename G, typename St>
-int plan_stages(int (*walk)(const G*, int, Carver&, St*), const G* groups, int ngroups, void* d_scratch, size_t scratch_bytes, St* st) {
+template <typename Walk, typename G, typename St>
+int plan_stages(Walk&& walk, const G* groups, int ngroups, void* d_scratch, size_t scratch_bytes, St* st) {
     Carver size{nullptr};
-    if (int rc = walk(groups, ngroups, size, nullptr)) return rc;
+    if (int rc = walk(groups, ngroups, size, (St*)nullptr)) return rc;
     if (size.used && (!d_scratch || ((uintptr_t)d_scratch & 15) || scratch_bytes < size.used))
         return set_err(SVT_HIP_ERR_INVALID, "scratch NULL, not 16-byte aligned or below the call's *_scratch_bytes()");
     Carver carve{(char*)d_scratch};

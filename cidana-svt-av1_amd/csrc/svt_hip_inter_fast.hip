@@ -65,7 +65,7 @@ extern "C" int svt_hip_inter_fast_pick_frame(const svt_hip_inter_fast_pick_group
 
 // ---- the whole inter fast search -----------------------------------------------------------------------------------------------------
 extern "C" size_t svt_hip_inter_fast_search_scratch_bytes(const svt_hip_inter_fast_search_group* groups, int ngroups) {
-    return scratch_bytes_of(inter_fast_search_walk8, groups, ngroups);       // (the carved pieces are distortions: the same for either depth)
+    return inter_fast_search_scratch_bytes(groups, ngroups);
 }
 
 extern "C" int svt_hip_inter_fast_search_frame(const svt_hip_inter_fast_search_group* groups, int ngroups, uint32_t pic_width, uint32_t pic_height,

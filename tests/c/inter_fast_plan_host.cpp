@@ -148,8 +148,8 @@ static int search_plan() {
     v[2].pick.d_dist = nullptr;
     // hand-computed: group 0 three pieces of 10 * 5 * 8 = 400 bytes (already a multiple of 16); group 3 two pieces of 1 * 3 * 8 = 24 -> 32
     const size_t want = 3 * 400 + 2 * 32;
-    CHECK(scratch_bytes_of(inter_fast_search_walk8, v.data(), (int)v.size()) == want);
-    CHECK(scratch_bytes_of(inter_fast_search_walk16, v.data(), (int)v.size()) == want);
+    CHECK(inter_fast_search_scratch_bytes(v.data(), (int)v.size(), 1) == want);
+    CHECK(inter_fast_search_scratch_bytes(v.data(), (int)v.size(), 2) == want);
     InterFastStages st;
     CHECK(splan(v, &st) == SVT_HIP_OK);
     CHECK(st.pick.size() == 4 && st.dist.size() == 3 + 1 + 3 && st.pred.size() == 3 + 1 + 3 && st.gather.size() == 2);
@@ -185,7 +185,7 @@ static int search_plan() {
     CHECK(splan(v, nullptr, 128, 64, 8, 0, g_scratch + 8, sizeof(g_scratch) - 8) == INVALID);
     {
         std::vector<svt_hip_inter_fast_search_group> u = {sgroup(16, 16, 6, 3, 10, 5, 3, 3, 1)};
-        CHECK(scratch_bytes_of(inter_fast_search_walk8, u.data(), 1) == 0);
+        CHECK(inter_fast_search_scratch_bytes(u.data(), 1) == 0);
         CHECK(splan(u, nullptr, 128, 64, 8, 0, nullptr, 0) == SVT_HIP_OK);
         u[0].use_chroma = 0; u[0].pick.d_dist_cb = nullptr; u[0].pick.d_dist_cr = nullptr;
         for (int p = 1; p < 3; p++) { u[0].d_ref[0][p] = u[0].d_ref[1][p] = u[0].d_src[p] = u[0].d_pred_out[p] = nullptr; }
@@ -228,7 +228,7 @@ static int search_plan() {
     }
     CHECK(inter_fast_search_plan(nullptr, 0, 128, 64, 8, 0, nullptr, 0, &st) == SVT_HIP_OK);
     CHECK(inter_fast_search_plan(nullptr, 1, 128, 64, 8, 0, nullptr, 0, &st) == INVALID);
-    CHECK(scratch_bytes_of(inter_fast_search_walk8, (const svt_hip_inter_fast_search_group*)nullptr, 1) == 0);
+    CHECK(inter_fast_search_scratch_bytes(nullptr, 1) == 0);
     return 0;
 }
 

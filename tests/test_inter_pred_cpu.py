@@ -85,7 +85,7 @@ def test_the_reference_regenerates_the_fixture_and_equals_the_restatements_on_ra
 
 
 def test_the_device_tap_tables_equal_the_recorded_reference_data(gold):
-    text = open(os.path.join(ROOT, "cidana-svt-av1_amd", "csrc", "kernel_inter_pred.h")).read()
+    text = open(os.path.join(ROOT, "cidana-svt-av1_amd", "csrc", "kernel_inter_steps.h")).read()
     body = text[text.index("// INTER-TAPS-BEGIN"):text.index("// INTER-TAPS-END")]
     body = body[body.index("= {"):]
     vals = np.array([int(v) for v in re.findall(r"-?\d+", body)], np.int16)

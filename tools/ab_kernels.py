@@ -4,7 +4,8 @@ usage: ab_kernels.py [--out=FILE.json] <workload> [<workload> ...]      workload
        fqp8 fqp16 (fwd_quant_planes on a 8192x4096 plane; fqp32h: a 10-bit plane), encp32 encp32h (encode_recon_planes, 8- / 10-bit plane), fl8 fl16 fl32 fl64 (full_loop, dense, AVX2 flavour, DCT_DCT) and fl8x16 fl16x16
        (every allowed type), c4 (one 1080p frame, five sizes, svt_hip_encode_recon_frame), ois8 ois16 (open-loop intra search of a 1080p
        picture), bip, me85 me209, fpick ifpick (svt_hip_fast_pick_frame with gather on 61 candidates, svt_hip_inter_fast_pick_frame on 48 inter
-       candidates: the 8x8 blocks of a 1080p picture, nfl 12)
+       candidates: the 8x8 blocks of a 1080p picture, nfl 12), ipred isse (svt_hip_inter_pred_frame, prediction stored and SSD, and
+       svt_hip_interp_sse_frame with use_uv 1: the 16x16 luma blocks of a 1080p picture, fractional vectors, single reference and BI_PRED mixed)
 Prints per workload the minimum and median of 6 interleaved rounds per library, the spread of a's own rounds (minimum to median) and
 whether b's median lies within it of a's, and whether the two libraries' outputs are equal; --out also writes the rows to a file."""
 import json
@@ -201,6 +202,44 @@ def workload(name, d):
         def run(keep=(g_, arr)):         # (the group array points into the tensors)
             assert call(arr, 0) == 0, d.lib.svt_hip_last_error()
         # every output weighted by position: a survivor in another slot changes the digest
+        weighted = lambda t: (t.reshape(-1).to(torch.int64) * (torch.arange(t.numel(), device=dev) % 65521 + 1)).sum()
+        return run, n, bpu, (lambda: [weighted(outs[k]) for k in sorted(outs)]), 2000
+    if name in ("ipred", "isse"):        # the two kernels that run the sub-pel convolve, on the 16x16 luma blocks of a 1080p picture, 8-bit
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        rng = np.random.default_rng(19031)
+        D = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        W, H, bs = 1920, 1080, 16
+        nx, ny = W // bs, H // bs
+        n = nx * ny
+
+        def planes(pads):                # padded planes; the views start at the picture's sample (0, 0)
+            full = [torch.randint(0, 256, (H // s + 2 * p, W // s + 2 * p), dtype=torch.uint8, device=dev, generator=g) for s, p in pads]
+            return full, [t[p:, p:] for t, (s, p) in zip(full, pads)], [t.shape[1] for t in full]
+
+        def mixed(r):                    # fractional vectors; list 0, list 1 and BI_PRED blocks share waves
+            r["pred_direction"] = rng.integers(0, 3, n)
+            return D(r.view(np.uint8).reshape(n, 16))
+        if name == "ipred":              # svt_hip_inter_pred_frame: tools/bench_inter_pred.py's records; prediction stored and SSD
+            import bench_inter_pred as bp
+            keep, (ref0, ref1, src), (stride, _, _) = planes([(1, bp.PAD)] * 3)
+            outs = dict(pred=torch.empty((n, bs, bs), dtype=torch.uint8, device=dev), dist=torch.empty((n,), dtype=torch.int64, device=dev))
+            g_ = dict(outs, ref0=ref0, ref1=ref1, ref_stride=stride, ss=0, bwidth=bs, bheight=bs, nblocks=n,
+                      blk=mixed(bp.make_records(pkg, rng, bs, nx, ny, "sr_2d")), src=src, src_stride=stride)
+            arr = d.make_inter_pred_groups([g_])
+            call, bpu = (lambda: d.inter_pred_frame(arr, W, H, 8, 1)), 3 * bs * bs + 16 + 8
+        else:                            # svt_hip_interp_sse_frame, use_uv 1: tools/bench_interp_search.py's records on the same blocks
+            import bench_interp_search as bs_
+            pads = [(1, bs_.PAD), (2, bs_.PAD_C), (2, bs_.PAD_C)]
+            (k0, ref0, strides), (k1, ref1, _), (k2, src, _) = planes(pads), planes(pads), planes(pads)
+            keep = (k0, k1, k2)
+            outs = dict(sse=torch.empty((n, 3, 9), dtype=torch.int32, device=dev))
+            g_ = dict(outs, ref0=ref0, ref1=ref1, ref_stride=strides, src=src, src_stride=strides, bwidth=bs, bheight=bs, nblocks=n,
+                      blk=mixed(bs_.make_records(pkg, rng, bs, nx, ny, 1, 0)))
+            arr = d.make_interp_sse_groups([g_])
+            call, bpu = (lambda: d.interp_sse_frame(arr, W, H, 1)), 3 * (bs * bs * 3 // 2) + 16 + 108
+
+        def run(keep=(keep, g_, arr)):       # (the group array points into the tensors)
+            assert call() == 0, d.lib.svt_hip_last_error()
         weighted = lambda t: (t.reshape(-1).to(torch.int64) * (torch.arange(t.numel(), device=dev) % 65521 + 1)).sum()
         return run, n, bpu, (lambda: [weighted(outs[k]) for k in sorted(outs)]), 2000
     if name in ("me85", "me209"):

@@ -42,6 +42,21 @@ SIZES = (8, 16, 32, 64)
 SAD, SSD = 0, 1
 
 
+def make_records(pkg, rng, bs, nx, ny, kind, cands=1):
+    """inter_blk_dtype records of the nx x ny grid of bs x bs blocks, `cands` per position: vectors within +-16 samples, full-pel for
+    sr_full and with both fractions non-zero otherwise, BI_PRED for bi_2d and list 0 otherwise, random filters"""
+    n = nx * ny * cands
+    r = np.zeros(n, pkg.inter_blk_dtype())
+    pos = np.arange(n) // cands
+    r["x"], r["y"] = (pos % nx) * bs, (pos // nx) * bs
+    whole = rng.integers(-16, 17, (n, 2, 2)) * 8
+    frac = rng.integers(1, 8, (n, 2, 2)) if kind != "sr_full" else 0
+    r["mv"] = whole + frac
+    r["pred_direction"] = pkg.BI_PRED if kind == "bi_2d" else pkg.UNI_PRED_LIST_0
+    r["filter_x"], r["filter_y"] = rng.integers(0, 3, n), rng.integers(0, 3, n)
+    return r
+
+
 def window(fn, min_s=0.2):
     """seconds per call: calls back to back in a window of >= min_s, HIP events, synchronised around"""
     reps = 1
@@ -94,16 +109,7 @@ def main():
         n = nx * ny
         px = bs * bs
 
-        def records(kind):
-            r = np.zeros(n, pkg.inter_blk_dtype())
-            r["x"], r["y"] = (np.arange(n) % nx) * bs, (np.arange(n) // nx) * bs
-            whole = rng.integers(-16, 17, (n, 2, 2)) * 8
-            frac = rng.integers(1, 8, (n, 2, 2)) if kind != "sr_full" else 0
-            r["mv"] = whole + frac
-            r["pred_direction"] = pkg.BI_PRED if kind == "bi_2d" else pkg.UNI_PRED_LIST_0
-            r["filter_x"], r["filter_y"] = rng.integers(0, 3, n), rng.integers(0, 3, n)
-            return D(r.view(np.uint8).reshape(n, 16))
-
+        records = lambda kind: D(make_records(pkg, rng, bs, nx, ny, kind).view(np.uint8).reshape(n, 16))
         pred = E((n, bs, bs), torch.uint8)
         dist, dist2 = E((n,), torch.int64), E((n,), torch.int64)
         sad32 = E((n,), torch.int32)
@@ -177,13 +183,7 @@ def main():
         dist = E((n,), torch.int64)
         arrs = {}
         for kind in ("sr_2d", "sr_full", "bi_2d"):
-            r = np.zeros(n, pkg.inter_blk_dtype())
-            pos = np.arange(n) // CANDS
-            r["x"], r["y"] = (pos % nx) * bs, (pos // nx) * bs
-            r["mv"] = rng.integers(-16, 17, (n, 2, 2)) * 8 + (rng.integers(1, 8, (n, 2, 2)) if kind != "sr_full" else 0)
-            r["pred_direction"] = pkg.BI_PRED if kind == "bi_2d" else pkg.UNI_PRED_LIST_0
-            r["filter_x"], r["filter_y"] = rng.integers(0, 3, n), rng.integers(0, 3, n)
-            blk = D(r.view(np.uint8).reshape(n, 16))
+            blk = D(make_records(pkg, rng, bs, nx, ny, kind, CANDS).view(np.uint8).reshape(n, 16))
             keep.append(blk)
             g = dict(ref0=ref0, ref1=ref1, ref_stride=stride, ss=0, bwidth=bs, bheight=bs, nblocks=n, blk=blk)
             arrs[kind] = dsp.make_inter_pred_groups([dict(g, pred=pred)])

@@ -37,6 +37,18 @@ SIZES = (8, 16, 64)
 SSD = 1
 
 
+def make_records(pkg, rng, bs, nx, ny, cands, direction):
+    """inter_blk_dtype records of the nx x ny grid of bs x bs blocks, `cands` per position: vectors within +-16 samples with both
+    fractions non-zero, every block of `direction`; the filter bytes stay 0 (the search tries all nine pairs)"""
+    n = nx * ny * cands
+    r = np.zeros(n, pkg.inter_blk_dtype())
+    pos = np.arange(n) // cands
+    r["x"], r["y"] = (pos % nx) * bs, (pos // nx) * bs
+    r["mv"] = rng.integers(-16, 17, (n, 2, 2)) * 8 + rng.integers(1, 8, (n, 2, 2))
+    r["pred_direction"] = direction
+    return r
+
+
 def window(fn, min_s=0.2):
     """seconds per call: calls back to back in a window of >= min_s, HIP events, synchronised around"""
     reps = 1
@@ -94,11 +106,7 @@ def main():
             n = nx * ny * cands
             px = bs * bs
             for direction, dname in ((pkg.UNI_PRED_LIST_0, "single"), (pkg.BI_PRED, "bi")):
-                r = np.zeros(n, pkg.inter_blk_dtype())
-                pos = np.arange(n) // cands
-                r["x"], r["y"] = (pos % nx) * bs, (pos // nx) * bs
-                r["mv"] = rng.integers(-16, 17, (n, 2, 2)) * 8 + rng.integers(1, 8, (n, 2, 2))
-                r["pred_direction"] = direction
+                r = make_records(pkg, rng, bs, nx, ny, cands, direction)
                 blk = D(r.view(np.uint8).reshape(n, 16))
                 r9 = np.repeat(r, 9)                                         # the composed path's records: [block][pair]
                 r9["filter_y"], r9["filter_x"] = np.tile(np.arange(9) // 3, n), np.tile(np.arange(9) % 3, n)
