@@ -213,6 +213,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_inter_fast_search_frame.restype = c_int
     L.svt_hip_md_decide_frame.argtypes = [c_void_p, c_int, c_void_p]
     L.svt_hip_md_decide_frame.restype = c_int
+    L.svt_hip_blk_geom_mds.argtypes = [c_uint32, c_void_p]
+    L.svt_hip_blk_geom_mds.restype = c_int
+    L.svt_hip_partition_decide_frame.argtypes = [c_void_p, c_void_p]
+    L.svt_hip_partition_decide_frame.restype = c_int
     L.svt_hip_md_search_scratch_bytes.argtypes = [c_void_p, c_int]
     L.svt_hip_md_search_scratch_bytes.restype = c_size_t
     L.svt_hip_md_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
@@ -450,6 +454,49 @@ def md_decision_dtype():
                     [(n, np.uint8) for n in ("slot", "cand", "count", "is_intra", "skip_flag", "merge_flag", "y_has_coeff", "u_has_coeff",
                                              "v_has_coeff", "block_has_coeff", "tx_type", "best_intra_mode", "uv_mode", "cfl_alpha_idx",
                                              "cfl_alpha_signs")] + [("pad", np.uint8, (7,))])
+
+
+SB_BLOCKS, SB_SQUARES, SB_MAX_FINAL = 1101, 341, 256      # a 64x64 superblock: blocks in md scan, squares, the most blocks it can code
+PART_NO_SRC = 0xFFFFFFFF
+PARTITION_SPLIT = 3
+PARTITION_BITS_SHAPE = (20, 11)                            # partitionFacBits
+
+
+class BlkGeom(ctypes.Structure):
+    """svt_hip_blk_geom (16 bytes)"""
+    _fields_ = [("sqi_mds", ctypes.c_uint16)] + [(n, ctypes.c_uint8) for n in ("bsize", "shape", "depth", "nsi", "totns", "d1i", "origin_x", "origin_y",
+                                                                             "bwidth", "bheight", "sq_size", "is_last_quadrant", "has_uv", "pad")]
+
+
+class PartitionArgs(ctypes.Structure):
+    """svt_hip_partition_args"""
+    _fields_ = [(n, c_uint32) for n in ("nsb", "nleaves", "nsrc", "lambda_", "pic_width", "pic_height")] + [("slice_is_intra", c_int32), ("pad", c_int32)] + \
+               [(n, c_void_p) for n in ("d_sb", "d_leaf", "d_decision", "d_cost", "d_partition_bits", "d_sq", "d_final_count", "d_final", "d_final_decision")]
+
+
+def part_leaf_dtype():
+    """numpy dtype of svt_hip_part_leaf (12 bytes)"""
+    import numpy as np
+    return np.dtype([("mds_idx", "<u2"), ("split_flag", "u1"), ("tot_d1_blocks", "u1"), ("left_partition", "i1"), ("above_partition", "i1"),
+                     ("pad", "u1", (2,)), ("src", "<u4")])
+
+
+def part_sb_dtype():
+    """numpy dtype of svt_hip_part_sb (12 bytes)"""
+    import numpy as np
+    return np.dtype([("leaf_first", "<u4"), ("leaf_count", "<u2"), ("origin_x", "<u2"), ("origin_y", "<u2"), ("pad", "<u2")])
+
+
+def part_sq_dtype():
+    """numpy dtype of svt_hip_part_sq (16 bytes)"""
+    import numpy as np
+    return np.dtype([("cost", "<u8"), ("best_d1_blk", "<u2"), ("part", "u1"), ("split_flag", "u1"), ("tested", "u1"), ("pad", "u1", (3,))])
+
+
+def part_final_dtype():
+    """numpy dtype of svt_hip_part_final (12 bytes)"""
+    import numpy as np
+    return np.dtype([("mds_idx", "<u2"), ("x", "<u2"), ("y", "<u2"), ("bsize", "u1"), ("part", "u1"), ("src", "<u4")])
 
 
 def pack_md_rates(tables):
@@ -2082,6 +2129,37 @@ class SvtHipDsp:
         if isinstance(groups, list):
             groups = self.make_md_decide_groups(groups)
         return self.lib.svt_hip_md_decide_frame(groups, n, self._stream())
+
+    # -- the partition decision: d1 / d2 per superblock and the final block list -------------------------------------------------------
+    def blk_geom_mds(self, mds_idx):
+        """svt_hip_blk_geom_mds -> dict of the block's geometry (a host table; raises for an index outside 0 .. 1100)"""
+        g = BlkGeom()
+        self._check(self.lib.svt_hip_blk_geom_mds(int(mds_idx), ctypes.byref(g)), f"svt_hip_blk_geom_mds({mds_idx})")
+        return {n: int(getattr(g, n)) for n, _ in BlkGeom._fields_ if n != "pad"}
+
+    def make_partition_args(self, a):
+        """a: dict with tensors sb (uint8 [nsb, 12]: part_sb_dtype), leaf (uint8 [nleaves, 12]: part_leaf_dtype; None with no leaf), exactly one
+        of decision (uint8 [nsrc, 72]: md_decision_dtype) / cost (int64 [nsrc]), partition_bits (int32 [20, 11]), sq (uint8 [nsb, 341, 16]:
+        part_sq_dtype), final_count (int32 [nsb]), final (uint8 [nsb, 256, 12]: part_final_dtype), optional final_decision (uint8 [nsb, 256,
+        72]); plus lambda, pic_width, pic_height, slice_is_intra and optionally nsb / nleaves / nsrc (else the tensors' first dimensions).
+        -> PartitionArgs (keep the tensors alive!)"""
+        P = lambda t: self._p(t) if t is not None else None
+        A = PartitionArgs()
+        src = a.get("decision") if a.get("decision") is not None else a.get("cost")
+        A.nsb = a["nsb"] if "nsb" in a else a["sb"].shape[0]
+        A.nleaves = a["nleaves"] if "nleaves" in a else (a["leaf"].shape[0] if a.get("leaf") is not None else 0)
+        A.nsrc = a["nsrc"] if "nsrc" in a else (src.shape[0] if src is not None else 0)
+        A.lambda_, A.pic_width, A.pic_height = a.get("lambda", 0), a.get("pic_width", 0), a.get("pic_height", 0)
+        A.slice_is_intra = int(a.get("slice_is_intra", 0))
+        for k in ("sb", "leaf", "decision", "cost", "partition_bits", "sq", "final_count", "final", "final_decision"):
+            setattr(A, "d_" + k, P(a.get(k)))
+        return A
+
+    def partition_decide_frame(self, args):
+        """svt_hip_partition_decide_frame.  args: a PartitionArgs from make_partition_args or the dict -> the return code"""
+        if isinstance(args, dict):
+            args = self.make_partition_args(args)
+        return self.lib.svt_hip_partition_decide_frame(ctypes.byref(args), self._stream())
 
     def make_md_search_groups(self, groups):
         """groups: list of dicts {"md": a make_md_decide_groups dict (its stage inputs luma, the chroma arrays, qcoeff and dqcoeff are set by

@@ -1934,6 +1934,103 @@ size_t svt_hip_md_search_scratch_bytes(const svt_hip_md_search_group *groups, in
 int svt_hip_md_search_frame(const svt_hip_md_search_group *groups, int ngroups, int flavour, const svt_hip_qrows *q_luma,
                             const svt_hip_qrows *q_chroma, void *d_scratch, size_t scratch_bytes, void *stream);
 
+/* The partition decision of a picture: the d1 (shape) and d2 (depth) decisions that mode_decision_sb (EbProductCodingLoop.c:3375-3502)
+ * makes around md_encode_block, and the block list the encode pass derives from them (EbCodingLoop.c:2571-2589, :3618-3621), for nsb
+ * 64x64 superblocks in one launch.  It consumes the cost svt_hip_md_decide_frame stores first in its record (md_local_cu_unit[].cost).
+ * A superblock has 1 101 blocks in md-scan order (mds) under 341 squares (EbUtility.c:782-917, build_blk_geom(0)); svt_hip_blk_geom_mds
+ * gives a block's geometry on the host.  Per superblock, in uint64 arithmetic that wraps, RDCOST as at the decide above:
+ *   start     Initialize_cu_data_structure (:651-683): every square split_flag 1, part PARTITION_SPLIT (3), not tested; and, defined
+ *             HERE where the reference reads stale memory, cost 0, contexts 0, mdc_split_flag 0, best_d1_blk 0 for what no entry sets.
+ *   entries   the MDC leaf list in order.  An entry gives its block its cost (d_cost[src] or d_decision[src].cost); a PART_N entry
+ *             also makes its square tested and sets split_flag = mdc_split_flag = the entry's split_flag & 1 (a one-bit member) and
+ *             the square's partition contexts.  d1_blocks_accumlated restarts at 1 on a PART_N entry and counts up on others.
+ *   d1        d1_non_square_block_decision (EbFullLoop.c:1876-1898), at every entry that is the last block of its shape: the sum of
+ *             the shape's blocks (an absent one counts 0); PART_N always takes the square, another shape only when strictly cheaper
+ *             than the square's cost so far; part = NONE, HORZ, VERT, HORZ_A, HORZ_B, VERT_A, VERT_B, HORZ_4, VERT_4 (0, 1, 2, 4 .. 9),
+ *             best_d1_blk = the shape's first block.
+ *   d2        d2_inter_depth_block_decision (:2037-2103), at the entry whose count equals its tot_d1_blocks, when the square's
+ *             split_flag is 0: climbs while the square is a last quadrant.  At each parent compute_depth_costs (:1902-2035): the parent
+ *             takes child 0's contexts; parent cost = its cost + its PARTITION_NONE rate, MAX_MODE_COST (108 935 755 917 824) when it is
+ *             not tested; current cost = the four children's costs + the parent's PARTITION_SPLIT rate + the PARTITION_NONE rate of
+ *             every child with mdc_split_flag 0, these child rates NOT added in a climb that began at a 4x4 square (the reference tests
+ *             the last leaf's block size).  parent <= current keeps the parent (split_flag 0, cost = parent cost); else part =
+ *             PARTITION_SPLIT and cost = current.  On an I slice the 64x64 root is not computed: parent cost is MAX_MODE_COST, current
+ *             keeps the value of the climb's previous level (0 when the climb begins at a 32x32).
+ *   rate      av1_split_flag_rate (EbRateDistortionCost.c:2268-2342), as written: with the square's bottom and right halves inside
+ *             the picture partitionFacBits[partition_cdf_length(bsize)][type] (row 4 for 8x8, row 10 above: the row is the LENGTH, not
+ *             the context); on a picture edge 0 for PARTITION_SPLIT, else the row [left * 2 + above + 4 bsl] of BITS read as a CDF by
+ *             partition_gather_vert_alike (bottom half outside only) or _horz_alike, an int32 converted to uint64; then
+ *             RDCOST(rate, 0).  bsl = log2(size / 8), left / above = (context >> bsl) & 1, a context of -1 (INVALID_NEIGHBOR_DATA) is 0.
+ *   final     the squares in mds order: a square all of whose ancestors have part 3 and whose own part is not 3 emits the blocks of
+ *             its part (ns_blk_num[part] from ns_blk_offset[part]); d_final[sb][k] is the k-th of the superblock in coding order, with
+ *             its picture position, block size, the square's part and the src of its entry (SVT_HIP_PART_NO_SRC for a block no entry
+ *             listed); d_final_decision, when given, receives d_decision[src] (zeros for no entry).  At most 256 per superblock.
+ * The level-by-level form the kernel uses equals the sequential loop for a list as MDC makes it: ascending mds_idx without repeats, a
+ * square's entries carrying the count of its listed blocks as tot_d1_blocks, and no entry below a square listed with split_flag 0.
+ * Another list gives an unspecified tree for its own superblock.  The partition contexts are the caller's (what md_encode_block stores
+ * from the neighbour arrays); deriving them across blocks and superblocks stays with the caller.
+ * Device data is clamped: mds_idx to 1 100, src to nsrc - 1, a leaf range to nleaves and to 1 101 entries; no address outside the
+ * arrays is formed.  Entries of d_final / d_final_decision at or past d_final_count[sb] are not written; every d_sq entry and count is.
+ * Records: svt_hip_part_leaf, svt_hip_part_sb and svt_hip_part_final are 12 bytes, 4-byte aligned; svt_hip_part_sq is 16 bytes, 8-byte
+ * aligned.  Validation before the launch (SVT_HIP_ERR_INVALID): nsb 0 or above 2^31 / 341 (6 297 606); zero pic_width / pic_height; NULL
+ * d_sb / d_partition_bits / d_sq / d_final_count / d_final; NULL d_leaf or nsrc 0 with nleaves > 0; both or neither of d_decision /
+ * d_cost; d_final_decision without d_decision; misalignment (d_decision / d_cost / d_sq / d_final_decision 8 bytes, the others 4).
+ * 128-wide superblocks are not supported.  One launch, one wave per superblock; the call only enqueues, allocates nothing and can be
+ * captured into a HIP graph. */
+typedef struct svt_hip_blk_geom {         /* BlockGeom's members a caller needs to build lists and groups; sizeof 16 */
+    uint16_t sqi_mds;                     /* the block's square, in md scan */
+    uint8_t bsize, shape;                 /* AV1 block_size; PART_N, H, V, HA, HB, VA, VB, H4, V4 = 0 .. 8 */
+    uint8_t depth, nsi, totns, d1i;
+    uint8_t origin_x, origin_y, bwidth, bheight, sq_size;
+    uint8_t is_last_quadrant, has_uv, pad;
+} svt_hip_blk_geom;
+#define SVT_HIP_SB_BLOCKS 1101
+#define SVT_HIP_SB_SQUARES 341
+#define SVT_HIP_SB_MAX_FINAL 256
+#define SVT_HIP_PART_NO_SRC 0xFFFFFFFFu
+int svt_hip_blk_geom_mds(uint32_t mds_idx, svt_hip_blk_geom *out);      /* HOST; 64x64 superblock, 0 .. 1100; needs no device */
+typedef struct svt_hip_part_leaf {        /* one MDC leaf (EbMdcLeafData_t) */
+    uint16_t mds_idx;
+    uint8_t split_flag, tot_d1_blocks;
+    int8_t left_partition, above_partition;      /* read on PART_N entries */
+    uint8_t pad[2];
+    uint32_t src;                         /* index of this block's cost: into d_decision or d_cost */
+} svt_hip_part_leaf;
+typedef struct svt_hip_part_sb {
+    uint32_t leaf_first;                  /* the superblock's entries: d_leaf[leaf_first .. leaf_first + leaf_count) */
+    uint16_t leaf_count;
+    uint16_t origin_x, origin_y;          /* in the picture */
+    uint16_t pad;
+} svt_hip_part_sb;
+typedef struct svt_hip_part_sq {          /* one square after the decisions */
+    uint64_t cost;
+    uint16_t best_d1_blk;
+    uint8_t part, split_flag, tested;
+    uint8_t pad[3];                       /* written as 0 */
+} svt_hip_part_sq;
+typedef struct svt_hip_part_final {       /* one block the encode pass codes */
+    uint16_t mds_idx, x, y;               /* x, y in the picture */
+    uint8_t bsize, part;
+    uint32_t src;
+} svt_hip_part_final;
+typedef struct svt_hip_partition_args {
+    uint32_t nsb, nleaves, nsrc;
+    uint32_t lambda;                      /* full_lambda */
+    uint32_t pic_width, pic_height;       /* luma_width / luma_height */
+    int32_t slice_is_intra;               /* slice_type == I_SLICE */
+    int32_t pad;
+    const svt_hip_part_sb *d_sb;          /* [nsb] */
+    const svt_hip_part_leaf *d_leaf;      /* [nleaves] */
+    const svt_hip_md_decision *d_decision;       /* exactly one of d_decision / d_cost: [nsrc] */
+    const uint64_t *d_cost;
+    const int32_t *d_partition_bits;      /* partitionFacBits in its declaration shape [20][11] */
+    svt_hip_part_sq *d_sq;                /* [nsb][341], squares in mds order */
+    uint32_t *d_final_count;              /* [nsb] */
+    svt_hip_part_final *d_final;          /* [nsb][256], coding order */
+    svt_hip_md_decision *d_final_decision;       /* optional [nsb][256]; needs d_decision */
+} svt_hip_partition_args;
+int svt_hip_partition_decide_frame(const svt_hip_partition_args *a, void *stream);
+
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
  * aom_dsp_rtcd.h it implements (svt_hip_rtcd_slot_count() entries: the 19 av1_fwd_txfm2d_WxH, the 19
