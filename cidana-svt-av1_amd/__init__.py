@@ -217,6 +217,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_blk_geom_mds.restype = c_int
     L.svt_hip_partition_decide_frame.argtypes = [c_void_p, c_void_p]
     L.svt_hip_partition_decide_frame.restype = c_int
+    L.svt_hip_recon_final_scratch_bytes.argtypes = [c_uint32]
+    L.svt_hip_recon_final_scratch_bytes.restype = c_size_t
+    L.svt_hip_recon_final_frame.argtypes = [c_void_p, c_void_p]
+    L.svt_hip_recon_final_frame.restype = c_int
     L.svt_hip_md_search_scratch_bytes.argtypes = [c_void_p, c_int]
     L.svt_hip_md_search_scratch_bytes.restype = c_size_t
     L.svt_hip_md_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
@@ -472,6 +476,25 @@ class PartitionArgs(ctypes.Structure):
     """svt_hip_partition_args"""
     _fields_ = [(n, c_uint32) for n in ("nsb", "nleaves", "nsrc", "lambda_", "pic_width", "pic_height")] + [("slice_is_intra", c_int32), ("pad", c_int32)] + \
                [(n, c_void_p) for n in ("d_sb", "d_leaf", "d_decision", "d_cost", "d_partition_bits", "d_sq", "d_final_count", "d_final", "d_final_decision")]
+
+
+RECON_FINAL_MAX_GROUPS = 32
+RECON_OK, RECON_NO_SRC, RECON_BSIZE, RECON_OUTSIDE, RECON_TX_TYPE = 0, 1, 2, 3, 4      # d_status of svt_hip_recon_final_frame
+SB_QCOEFF_LUMA = 4096                                      # int32 per superblock of the luma coefficient stream; chroma a quarter
+
+
+class ReconFinalGroup(ctypes.Structure):
+    """svt_hip_recon_final_group"""
+    _fields_ = [("src_first", c_uint32), ("nblocks", c_uint32), ("bsize", c_int32), ("tx_type_uv", c_int32),
+                ("d_best_pred", c_void_p * 3), ("d_best_dqcoeff", c_void_p * 3), ("d_best_qcoeff", c_void_p * 3)]
+
+
+class ReconFinalArgs(ctypes.Structure):
+    """svt_hip_recon_final_args"""
+    _fields_ = [("nsb", c_uint32), ("nsrc", c_uint32), ("ngroups", c_int32), ("planes", c_int32)] + \
+               [(n, c_void_p) for n in ("d_final", "d_final_count", "d_decision", "groups")] + [("d_recon", c_void_p * 3)] + \
+               [("stride", c_uint32 * 3), ("width", c_uint32 * 3), ("height", c_uint32 * 3), ("d_status", c_void_p), ("d_sb_qcoeff", c_void_p * 3),
+                ("d_coeff_offset", c_void_p), ("d_scratch", c_void_p), ("scratch_bytes", ctypes.c_size_t)]
 
 
 def part_leaf_dtype():
@@ -2160,6 +2183,56 @@ class SvtHipDsp:
         if isinstance(args, dict):
             args = self.make_partition_args(args)
         return self.lib.svt_hip_partition_decide_frame(ctypes.byref(args), self._stream())
+
+    # -- the reconstruction of the final block list into picture planes, and the superblock coefficient stream ---------------------------
+    def recon_final_scratch_bytes(self, nsb):
+        """svt_hip_recon_final_scratch_bytes (a host computation; 0 for an nsb the call refuses)"""
+        return self.lib.svt_hip_recon_final_scratch_bytes(int(nsb))
+
+    def make_recon_final_args(self, a):
+        """a: dict with tensors final (uint8 [nsb, 256, 12]: part_final_dtype), final_count (int32 [nsb]), decision (uint8 [nsrc, 72]:
+        md_decision_dtype), recon (list of one or three uint8 plane tensors), scratch (uint8, recon_final_scratch_bytes(nsb)), optional
+        status (uint8 [nsb, 256]), sb_qcoeff (list of int32 tensors [nsb, 4096] and [nsb, 1024] twice), coeff_offset (int32 [nsb, 256, 2]);
+        groups: list of dicts {src_first, nblocks, bsize, tx_type_uv, best_pred, best_dqcoeff, optional best_qcoeff: lists of up to three
+        tensors}; stride / width / height (lists, samples; default the plane tensors' stride(0) and shape), planes (1 or 3; default the
+        number of recon planes) and optionally nsb / nsrc / ngroups / scratch_bytes (else from the tensors).
+        -> ReconFinalArgs (keep the tensors alive; the group array rides in its _groups)"""
+        P = lambda t: self._p(t) if t is not None else None
+        A = ReconFinalArgs()
+        groups = a.get("groups") or []
+        arr = (ReconFinalGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            arr[i].src_first, arr[i].nblocks, arr[i].bsize, arr[i].tx_type_uv = g["src_first"], g["nblocks"], g["bsize"], g.get("tx_type_uv", 0)
+            for key in ("best_pred", "best_dqcoeff", "best_qcoeff"):
+                planes = g.get(key) or ()
+                for p in range(3):
+                    getattr(arr[i], "d_" + key)[p] = P(planes[p]) if p < len(planes) else None
+        A._groups = arr
+        A.groups = ctypes.cast(arr, c_void_p) if a.get("groups") is not None else None
+        recon = list(a.get("recon") or ())
+        A.nsb = a["nsb"] if "nsb" in a else a["final_count"].shape[0]
+        A.nsrc = a["nsrc"] if "nsrc" in a else a["decision"].shape[0]
+        A.ngroups = a["ngroups"] if "ngroups" in a else len(groups)
+        A.planes = a["planes"] if "planes" in a else len(recon)
+        for p in range(3):
+            t = recon[p] if p < len(recon) else None
+            A.d_recon[p] = P(t)
+            for key, default in (("stride", t.stride(0) if t is not None else 0), ("width", t.shape[1] if t is not None else 0),
+                                 ("height", t.shape[0] if t is not None else 0)):
+                given = a.get(key)
+                getattr(A, key)[p] = given[p] if given is not None and p < len(given) else default
+            sbq = a.get("sb_qcoeff") or ()
+            A.d_sb_qcoeff[p] = P(sbq[p]) if p < len(sbq) else None
+        for k in ("final", "final_count", "decision", "status", "coeff_offset", "scratch"):
+            setattr(A, "d_" + k, P(a.get(k)))
+        A.scratch_bytes = a["scratch_bytes"] if "scratch_bytes" in a else (a["scratch"].numel() * a["scratch"].element_size() if a.get("scratch") is not None else 0)
+        return A
+
+    def recon_final_frame(self, args):
+        """svt_hip_recon_final_frame.  args: a ReconFinalArgs from make_recon_final_args or the dict -> the return code"""
+        if isinstance(args, dict):
+            args = self.make_recon_final_args(args)
+        return self.lib.svt_hip_recon_final_frame(ctypes.byref(args), self._stream())
 
     def make_md_search_groups(self, groups):
         """groups: list of dicts {"md": a make_md_decide_groups dict (its stage inputs luma, the chroma arrays, qcoeff and dqcoeff are set by

@@ -48,6 +48,7 @@ extern int g_tune_no_enc64;
 extern int g_tune_frame_single_launch;
 extern int g_tune_inv32_waves;
 extern int g_tune_inv32_var;
+extern int g_tune_recon_final_bin_only;
 
 #define HIP_TRY(expr)                                                                            \
     do {                                                                                         \

@@ -34,6 +34,7 @@ int g_tune_no_enc64 = 0;
 int g_tune_frame_single_launch = -1;      // -1: by call size (svt_hip_encode_recon_frame), 0 never, 1 always
 int g_tune_inv32_waves = 4;
 int g_tune_inv32_var = 0;
+int g_tune_recon_final_bin_only = 0;      // 1: svt_hip_recon_final_frame stops after its bin stage (tools/bench_recon_final.py times the stage)
 
 // The HIP "current device" is a per-THREAD setting and the encoder calls from many pthreads (Threading):
 // every entry point passes through here, so every thread is bound to the library's device once.
@@ -120,6 +121,7 @@ extern "C" int svt_hip_tune(const char* key, int value) {
     if (!strcmp(key, "frame_single_launch")) { g_tune_frame_single_launch = value; return SVT_HIP_OK; }
     if (!strcmp(key, "inv32_waves")) { g_tune_inv32_waves = value; return SVT_HIP_OK; }
     if (!strcmp(key, "inv32_var")) { g_tune_inv32_var = value; return SVT_HIP_OK; }
+    if (!strcmp(key, "recon_final_bin_only")) { g_tune_recon_final_bin_only = value; return SVT_HIP_OK; }
     return set_err(SVT_HIP_ERR_INVALID, "unknown tuning key %s", key);
 }
 extern "C" const char* svt_hip_device_name(void) { return g_devname; }

@@ -2031,6 +2031,80 @@ typedef struct svt_hip_partition_args {
 } svt_hip_partition_args;
 int svt_hip_partition_decide_frame(const svt_hip_partition_args *a, void *stream);
 
+/* The reconstruction of the final block list: AV1PerformInverseTransformRecon for the winner (EbProductCodingLoop.c:871-1020, called at
+ * :3205) over every block svt_hip_partition_decide_frame listed, 8-bit 4:2:0, into picture planes.  It takes d_final / d_final_count as
+ * that call writes them, the records and the winners' arrays as svt_hip_md_decide_frame gathers them, and learns on the device how many
+ * blocks of which size there are: no copy to the host, no synchronisation, no allocation; grid sizes come from nsb alone.
+ * A source group is one md-decide group: the records src_first .. src_first + nblocks - 1, all of block size bsize, with d_best_pred[p]
+ * dense [nblocks][h][w] (p = 0 luma bw x bh, 1 / 2 chroma max(bw / 2, 4) x max(bh / 2, 4)) and d_best_dqcoeff[p] / d_best_qcoeff[p]
+ * [nblocks][min(w, 32) * min(h, 32)].  The groups are ascending, disjoint and cover [0, nsrc).  tx_type_uv is the chroma transform
+ * type of the group (transform_type[PLANE_TYPE_UV], one scalar as in svt_hip_md_search_frame); the luma type is the record's tx_type.
+ * Per final entry k < d_final_count[sb] (a count above 256 is taken as 256), with src its record:
+ *   sizes     one transform block per plane: luma blk_geom->txsize[0] (the block size's own), chroma txsize_uv[0] (of the chroma block, a
+ *             64-sample side taken as 32).  Chroma is written only when the geometry of mds_idx (clamped to 1 100) has has_uv.
+ *   where     luma at (x, y); chroma at (((x >> 3) << 3) >> 1, ((y >> 3) << 3) >> 1) (:905-906).
+ *   content   a plane whose record eob[p] is 0 receives the prediction (picture_copy8_bit) and its coefficients are not read; otherwise
+ *             prediction + inverse transform of d_best_dqcoeff (bd 8) clipped: av1_inv_transform_recon8bit = av1_inv_txfm_add_c, bit for bit.
+ *   skipped   nothing is written for an entry, and d_status says why, when (1, SVT_HIP_RECON_NO_SRC) src is SVT_HIP_PART_NO_SRC or
+ *             >= nsrc; (2, _BSIZE) its bsize differs from its source group's; (3, _OUTSIDE) a plane block of it does not lie wholly inside
+ *             that plane's width x height (the chroma planes are tested in a three-plane call only); (4, _TX_TYPE) the record's tx_type is
+ *             not defined for the luma size (a 64-sample side: DCT_DCT; a 32-sample side: DCT_DCT, IDTX; else 0 .. 15).  The first
+ *             that applies is reported.
+ *   status    d_status (optional, uint8 [nsb][256]) receives 0 or the reason for every entry below the count; entries at or past the
+ *             count are not written.  Samples no final block covers are not written.
+ *   stream    the superblock coefficient stream of the entropy coder (coded_area_sb / coded_area_sb_uv, EbCodingLoop.c:3033-3035,
+ *             :3376-3378): running offsets per superblock in coding order, luma advancing by bw * bh of every reconstructed entry, chroma by
+ *             the chroma block's w * h of those with has_uv; skipped entries advance nothing.  d_coeff_offset (optional, uint32
+ *             [nsb][256][2]) receives the luma and chroma offset of every entry below the count (a skipped entry: the running values).
+ *             d_sb_qcoeff[p] (optional; with planes 3 all three or none; int32 [nsb][4096] luma, [nsb][1024] per chroma plane) receives at
+ *             the entry's offset its min(w, 32) * min(h, 32) packed d_best_qcoeff[p], zeros for a plane with eob 0; the rest of a 64-wide
+ *             span is not written.  An entry whose span would pass its superblock's 4096 / 1024 (a list that is no tiling) gets no copy.
+ * Everything from device memory is clamped or checked before it forms an address.  Overlapping entries (a list that is no tiling) are
+ * each reconstructed in an unspecified order, and a superblock that lists more plane blocks of one size than a tiling can hold may lose
+ * some of them; nothing outside the arrays is touched.
+ * Validation before anything is enqueued (SVT_HIP_ERR_INVALID): nsb 0 or above 2^20; nsrc 0; planes other than 1 / 3; NULL d_final /
+ * d_final_count / d_decision / groups; ngroups outside 1 .. 32; a group table that is not ascending and contiguous from 0 to nsrc; a
+ * bsize outside 0 .. 21 or 13 .. 15; a tx_type_uv the chroma size does not define; a requested plane without its d_recon, or with a stride
+ * below its width, a width or height above 65 535, or, in a non-empty group, without d_best_pred / d_best_dqcoeff (d_best_qcoeff when the
+ * stream is asked for); some but not all of the requested planes' d_sb_qcoeff; misalignment (prediction, coefficient and stream arrays
+ * and the scratch 16 bytes, d_decision 8, d_final / d_final_count / d_coeff_offset 4); a scratch that is NULL or smaller than
+ * svt_hip_recon_final_scratch_bytes(nsb), a HOST computation that needs no device (0 for an nsb the call refuses).
+ * Six launches on `stream` (the lists' counters cleared, the bin stage, then the reconstruction by register class, the class of the 32-
+ * and 64-sample sides in two halves); the call only enqueues, allocates nothing and can be captured into a HIP graph. */
+#define SVT_HIP_RECON_FINAL_MAX_GROUPS 32
+#define SVT_HIP_RECON_OK 0
+#define SVT_HIP_RECON_NO_SRC 1
+#define SVT_HIP_RECON_BSIZE 2
+#define SVT_HIP_RECON_OUTSIDE 3
+#define SVT_HIP_RECON_TX_TYPE 4
+#define SVT_HIP_SB_QCOEFF_LUMA 4096       /* int32 per superblock of d_sb_qcoeff[0]; [1], [2]: a quarter */
+typedef struct svt_hip_recon_final_group {
+    uint32_t src_first, nblocks;
+    int32_t bsize;                        /* 0 .. 21 without 13 .. 15 */
+    int32_t tx_type_uv;
+    const uint8_t *d_best_pred[3];
+    const int32_t *d_best_dqcoeff[3];
+    const int32_t *d_best_qcoeff[3];      /* read only with d_sb_qcoeff */
+} svt_hip_recon_final_group;
+typedef struct svt_hip_recon_final_args {
+    uint32_t nsb, nsrc;
+    int32_t ngroups;
+    int32_t planes;                       /* 1: luma only; 3: Y, Cb, Cr */
+    const svt_hip_part_final *d_final;    /* [nsb][256] */
+    const uint32_t *d_final_count;        /* [nsb] */
+    const svt_hip_md_decision *d_decision;       /* [nsrc] */
+    const svt_hip_recon_final_group *groups;     /* HOST array [ngroups] */
+    uint8_t *d_recon[3];
+    uint32_t stride[3], width[3], height[3];     /* samples; width x height: what is allocated of the plane */
+    uint8_t *d_status;                    /* optional [nsb][256] */
+    int32_t *d_sb_qcoeff[3];              /* optional */
+    uint32_t *d_coeff_offset;             /* optional [nsb][256][2] */
+    void *d_scratch;
+    size_t scratch_bytes;
+} svt_hip_recon_final_args;
+size_t svt_hip_recon_final_scratch_bytes(uint32_t nsb);      /* HOST */
+int svt_hip_recon_final_frame(const svt_hip_recon_final_args *a, void *stream);
+
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
  * aom_dsp_rtcd.h it implements (svt_hip_rtcd_slot_count() entries: the 19 av1_fwd_txfm2d_WxH, the 19
