@@ -221,6 +221,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_recon_final_scratch_bytes.restype = c_size_t
     L.svt_hip_recon_final_frame.argtypes = [c_void_p, c_void_p]
     L.svt_hip_recon_final_frame.restype = c_int
+    L.svt_hip_intra_encode_scratch_bytes.argtypes = [c_uint32, c_uint32]
+    L.svt_hip_intra_encode_scratch_bytes.restype = c_size_t
+    L.svt_hip_intra_encode_tables_bytes.argtypes = []
+    L.svt_hip_intra_encode_tables_bytes.restype = c_size_t
+    L.svt_hip_intra_encode_tables_fill.argtypes = [c_void_p]
+    L.svt_hip_intra_encode_tables_fill.restype = c_int
+    L.svt_hip_intra_encode_launches.argtypes = [c_uint32, c_uint32, c_int]
+    L.svt_hip_intra_encode_launches.restype = c_int
+    L.svt_hip_intra_encode_frame.argtypes = [c_void_p, c_void_p]
+    L.svt_hip_intra_encode_frame.restype = c_int
     L.svt_hip_md_search_scratch_bytes.argtypes = [c_void_p, c_int]
     L.svt_hip_md_search_scratch_bytes.restype = c_size_t
     L.svt_hip_md_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
@@ -495,6 +505,33 @@ class ReconFinalArgs(ctypes.Structure):
                [(n, c_void_p) for n in ("d_final", "d_final_count", "d_decision", "groups")] + [("d_recon", c_void_p * 3)] + \
                [("stride", c_uint32 * 3), ("width", c_uint32 * 3), ("height", c_uint32 * 3), ("d_status", c_void_p), ("d_sb_qcoeff", c_void_p * 3),
                 ("d_coeff_offset", c_void_p), ("d_scratch", c_void_p), ("scratch_bytes", ctypes.c_size_t)]
+
+
+# d_status of svt_hip_intra_encode_frame
+INTRA_ENC_OK, INTRA_ENC_NO_SRC, INTRA_ENC_OUTSIDE, INTRA_ENC_TX_TYPE, INTRA_ENC_NOT_INTRA, INTRA_ENC_MODE, INTRA_ENC_CFL_SIZE, INTRA_ENC_SCHEDULE = 0, 1, 3, 4, 5, 6, 7, 8
+
+
+class IntraEncodeArgs(ctypes.Structure):
+    """svt_hip_intra_encode_args"""
+    _fields_ = [(n, c_uint32) for n in ("npics", "sb_cols", "sb_rows", "sb_pitch", "nsrc", "blk_pitch")] + \
+               [(n, c_void_p) for n in ("d_final", "d_final_count", "d_blk")] + [("d_src", c_void_p * 3), ("d_recon", c_void_p * 3)] + \
+               [(n, c_uint32 * 3) for n in ("src_stride", "stride", "width", "height")] + \
+               [("src_pic_pitch", ctypes.c_size_t * 3), ("recon_pic_pitch", ctypes.c_size_t * 3)] + \
+               [(n, c_void_p) for n in ("q_luma", "q_chroma", "d_tables", "d_status", "d_result")] + [("d_sb_qcoeff", c_void_p * 3)] + \
+               [("d_coeff_offset", c_void_p), ("d_scratch", c_void_p), ("scratch_bytes", ctypes.c_size_t)]
+
+
+def intra_enc_blk_dtype():
+    """numpy dtype of svt_hip_intra_enc_blk (8 bytes)"""
+    import numpy as np
+    return np.dtype([("is_intra", "u1"), ("mode", "u1"), ("angle_delta", "i1"), ("uv_mode", "u1"), ("cfl_alpha_idx", "u1"), ("cfl_alpha_signs", "u1"),
+                     ("tx_type", "u1"), ("tx_type_uv", "u1")])
+
+
+def intra_enc_result_dtype():
+    """numpy dtype of svt_hip_intra_enc_result (8 bytes)"""
+    import numpy as np
+    return np.dtype([("eob", "<u2", (3,)), ("tx_type", "u1"), ("pad", "u1")])
 
 
 def part_leaf_dtype():
@@ -2233,6 +2270,63 @@ class SvtHipDsp:
         if isinstance(args, dict):
             args = self.make_recon_final_args(args)
         return self.lib.svt_hip_recon_final_frame(ctypes.byref(args), self._stream())
+
+    # -- the intra encode pass in coding order: prediction from the reconstructed picture, transform, quantiser, reconstruction in place ------
+    def intra_encode_scratch_bytes(self, npics, nsb):
+        """svt_hip_intra_encode_scratch_bytes (a host computation; 0 for parameters the call refuses)"""
+        return self.lib.svt_hip_intra_encode_scratch_bytes(int(npics), int(nsb))
+
+    def intra_encode_launches(self, sb_cols, sb_rows, planes=3):
+        """svt_hip_intra_encode_launches: the launches one call enqueues (a host computation)"""
+        return self.lib.svt_hip_intra_encode_launches(int(sb_cols), int(sb_rows), int(planes))
+
+    def intra_encode_tables(self):
+        """the inverse scans of every (transform size, type) as svt_hip_intra_encode_tables_fill lays them out -> int16 numpy array (host);
+        upload it once and pass it as `tables`"""
+        import numpy as np
+        t = np.zeros(self.lib.svt_hip_intra_encode_tables_bytes() // 2, np.int16)
+        rc = self.lib.svt_hip_intra_encode_tables_fill(t.ctypes.data)
+        if rc != 0:
+            raise RuntimeError(f"svt_hip_intra_encode_tables_fill: {rc}")
+        return t
+
+    def make_intra_encode_args(self, a):
+        """a: dict with sb_cols, sb_rows, optional npics (1), sb_pitch (0), blk_pitch (0), nsrc (else blk.shape[0]); tensors final (uint8
+        [npics * sb_pitch, 256, 12]), final_count (int32), blk (uint8 [nsrc, 8]: intra_enc_blk_dtype), src / recon (lists of one or three
+        uint8 plane tensors), tables (int16, intra_encode_tables() uploaded), scratch (uint8), optional status (uint8), result (uint8
+        [.., 256, 8]: intra_enc_result_dtype), sb_qcoeff (list of int32 tensors), coeff_offset (int32); q_luma / q_chroma (dicts of int16
+        rows as the quantiser tables give them); src_stride / stride / width / height (lists; default from the plane tensors),
+        src_pic_pitch / recon_pic_pitch (lists, samples; default 0), scratch_bytes.  -> IntraEncodeArgs (keep the tensors alive)"""
+        P = lambda t: self._p(t) if t is not None else None
+        A = IntraEncodeArgs()
+        A.npics, A.sb_cols, A.sb_rows, A.sb_pitch, A.blk_pitch = a.get("npics", 1), a["sb_cols"], a["sb_rows"], a.get("sb_pitch", 0), a.get("blk_pitch", 0)
+        A.nsrc = a["nsrc"] if "nsrc" in a else (a["blk"].shape[0] if a.get("blk") is not None else 0)
+        src, recon, sbq = list(a.get("src") or ()), list(a.get("recon") or ()), list(a.get("sb_qcoeff") or ())
+        for p in range(3):
+            s, r = (src[p] if p < len(src) else None), (recon[p] if p < len(recon) else None)
+            A.d_src[p], A.d_recon[p] = P(s), P(r)
+            A.d_sb_qcoeff[p] = P(sbq[p]) if p < len(sbq) else None
+            for key, default in (("src_stride", s.stride(0) if s is not None else 0), ("stride", r.stride(0) if r is not None else 0),
+                                 ("width", r.shape[1] if r is not None else 0), ("height", r.shape[0] if r is not None else 0),
+                                 ("src_pic_pitch", 0), ("recon_pic_pitch", 0)):
+                given = a.get(key)
+                getattr(A, key)[p] = given[p] if given is not None and p < len(given) else default
+        A._keep = []
+        for name in ("q_luma", "q_chroma"):
+            if a.get(name) is not None:
+                q, tabs = self._qrows(a[name])
+                A._keep += [q, tabs]
+                setattr(A, name, ctypes.cast(ctypes.pointer(q), c_void_p))
+        for k in ("final", "final_count", "blk", "tables", "status", "result", "coeff_offset", "scratch"):
+            setattr(A, "d_" + k, P(a.get(k)))
+        A.scratch_bytes = a["scratch_bytes"] if "scratch_bytes" in a else (a["scratch"].numel() * a["scratch"].element_size() if a.get("scratch") is not None else 0)
+        return A
+
+    def intra_encode_frame(self, args):
+        """svt_hip_intra_encode_frame.  args: an IntraEncodeArgs from make_intra_encode_args or the dict -> the return code"""
+        if isinstance(args, dict):
+            args = self.make_intra_encode_args(args)
+        return self.lib.svt_hip_intra_encode_frame(ctypes.byref(args), self._stream())
 
     def make_md_search_groups(self, groups):
         """groups: list of dicts {"md": a make_md_decide_groups dict (its stage inputs luma, the chroma arrays, qcoeff and dqcoeff are set by

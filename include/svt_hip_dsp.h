@@ -2105,6 +2105,96 @@ typedef struct svt_hip_recon_final_args {
 size_t svt_hip_recon_final_scratch_bytes(uint32_t nsb);      /* HOST */
 int svt_hip_recon_final_frame(const svt_hip_recon_final_args *a, void *stream);
 
+/* The intra encode pass in coding order: what the encode pass does with every intra block of the final list (EbCodingLoop.c:2853-3005
+ * with Av1EncodeLoop :545-980 and Av1EncodeGenerateRecon :1408-1500), 8-bit 4:2:0, 64x64 superblocks, one transform block per plane.
+ * Every intra entry is PREDICTED AGAIN from the reconstructed picture (av1_predict_intra_block at ED_STAGE, EbIntraPrediction.c:4078-4333),
+ * then residual -> forward transform -> quantiser -> eob -> inverse transform -> reconstruction, in place in d_recon.  Inter blocks
+ * depend on nothing inside the picture: the caller reconstructs them first (svt_hip_recon_final_frame or the encode calls), this call
+ * codes the intra entries around them, which equals the reference's single walk.
+ * Inputs: d_final / d_final_count of npics pictures of sb_cols x sb_rows superblocks in raster order (picture i at superblock
+ * i * sb_pitch of every per-superblock array; sb_pitch 0 means nsb = sb_cols * sb_rows); d_blk, one svt_hip_intra_enc_blk per src
+ * (picture i at element i * blk_pitch; 0: one table for all pictures); the source planes (read only) and the reconstruction planes
+ * (read and written; on entry whatever the caller has reconstructed), picture i at sample i * src_pic_pitch[p] / recon_pic_pitch[p];
+ * one set of quantiser rows for luma and one for chroma (HOST); the inverse scans of every (transform size, type) in one device blob the
+ * caller builds once with svt_hip_intra_encode_tables_bytes / _fill and uploads.
+ * Per entry k < count (a count above 256 is taken as 256) of a superblock, in coding order:
+ *   geometry  of mds_idx (clamped to 1 100) as svt_hip_recon_final_frame: block size, has_uv; luma at (x, y), chroma at
+ *             (((x >> 3) << 3) >> 1, ((y >> 3) << 3) >> 1), the chroma size txsize_uv with a 64-sample side taken as 32.
+ *   not coded the first that applies is reported in d_status: (1, _NO_SRC) and (3, _OUTSIDE) as svt_hip_recon_final_frame; (4, _TX_TYPE)
+ *             tx_type not defined for the luma size or, with has_uv, tx_type_uv for the chroma size; (5, _NOT_INTRA) is_intra 0: the
+ *             samples stay, no error; (6, _MODE) mode > 12, uv_mode > 13, angle_delta outside -3 .. 3 or not 0 on a non-directional mode;
+ *             (7, _CFL_SIZE) uv_mode 13 on a block wider or taller than 32 or narrower or lower than 8; (8, _SCHEDULE) the launch schedule
+ *             did not reach the entry, which happens only for a list that is no partition tree.  The stream offsets advance for coded and
+ *             for _NOT_INTRA entries alike and for no other, so they equal svt_hip_recon_final_frame's for the same list.
+ *   predicted every plane the block has, from the neighbour row and column of the reconstruction plane; the available sample counts follow
+ *             svt_hip_intra_neighbor_px (one tile, 8-bit; mi_cols / mi_rows from the luma width / height; the partition is the entry's
+ *             part); filt_type from the above and left blocks' modes (get_filt_type / is_smooth; a block this call does not code counts
+ *             as not smooth); the chroma mode is UV_DC_PRED when uv_mode is 13; disable_edge_filter 0; angle_delta applies to luma only.
+ *             Samples the availability rules exclude are not read.
+ *   coded     luma with tx_type and the luma rows; with uv_mode 13 cfl_luma_subsampling_420_lbd of the block's luma reconstruction,
+ *             subtract_average and cfl_predict_lbd on the Cb and Cr DC predictions (cfl_idx_to_alpha); Cb and Cr with tx_type_uv and the
+ *             chroma rows.  A plane with eob 0 keeps its prediction.
+ * Outputs: the planes in place; d_result (optional) per coded entry the three eobs and the luma transform type, DCT_DCT when the luma eob
+ * is 0 (:700-709); d_sb_qcoeff / d_coeff_offset (optional) with svt_hip_recon_final_frame's shapes and rules, filled for coded entries.
+ * Entries at or past the count and samples no coded entry covers are not written.  Everything read from device memory is clamped or
+ * checked before it forms an address; a list that is no tiling or breaks coding order gives unspecified samples for its own superblock
+ * and its dependants, and nothing outside the arrays is touched.
+ * Launch order carries the dependencies: no workgroup waits for another.  Superblock (r, c) is coded in step c + 2 r; a step is a fixed
+ * schedule of launches by register class (intra_encode_plan.h), all pictures share them.  The call only enqueues, allocates nothing,
+ * never synchronises and can be captured into a HIP graph.
+ * Validation before anything is enqueued (SVT_HIP_ERR_INVALID): NULL arguments or required members; npics, sb_cols, sb_rows or nsrc 0; npics above 65 535; nsb
+ * above 2^20; sb_pitch below nsb; a stride below its width; a width or height above 65 535 or no multiple of 8 (chroma: of 4, and half
+ * the luma's); chroma planes (source and reconstruction) not all present or all absent (absent: luma only); some but not all stream
+ * planes; misalignment (d_sb_qcoeff, d_tables and the scratch 16 bytes, d_result and d_blk 8, d_final / d_final_count / d_coeff_offset 4);
+ * quantiser rows the one-product quantiser does not take; a scratch that is NULL or below svt_hip_intra_encode_scratch_bytes(npics, nsb),
+ * a HOST computation (0 for parameters the call refuses); d_src[p] == d_recon[p]. */
+#define SVT_HIP_INTRA_ENC_OK 0
+#define SVT_HIP_INTRA_ENC_NO_SRC 1
+#define SVT_HIP_INTRA_ENC_OUTSIDE 3
+#define SVT_HIP_INTRA_ENC_TX_TYPE 4
+#define SVT_HIP_INTRA_ENC_NOT_INTRA 5
+#define SVT_HIP_INTRA_ENC_MODE 6
+#define SVT_HIP_INTRA_ENC_CFL_SIZE 7
+#define SVT_HIP_INTRA_ENC_SCHEDULE 8
+typedef struct svt_hip_intra_enc_blk {
+    uint8_t is_intra;
+    uint8_t mode;                         /* 0 .. 12 */
+    int8_t angle_delta;                   /* -3 .. 3, luma */
+    uint8_t uv_mode;                      /* 0 .. 12, 13 = UV_CFL_PRED */
+    uint8_t cfl_alpha_idx, cfl_alpha_signs;
+    uint8_t tx_type, tx_type_uv;
+} svt_hip_intra_enc_blk;
+typedef struct svt_hip_intra_enc_result {
+    uint16_t eob[3];
+    uint8_t tx_type;                      /* the luma type, DCT_DCT when eob[0] is 0 */
+    uint8_t pad;                          /* written as 0 */
+} svt_hip_intra_enc_result;
+typedef struct svt_hip_intra_encode_args {
+    uint32_t npics, sb_cols, sb_rows;
+    uint32_t sb_pitch;                    /* superblocks between pictures in the per-superblock arrays; 0: sb_cols * sb_rows */
+    uint32_t nsrc, blk_pitch;
+    const svt_hip_part_final *d_final;    /* [npics][sb_pitch][256] */
+    const uint32_t *d_final_count;        /* [npics][sb_pitch] */
+    const svt_hip_intra_enc_blk *d_blk;   /* [nsrc] */
+    const uint8_t *d_src[3];
+    uint8_t *d_recon[3];
+    uint32_t src_stride[3], stride[3], width[3], height[3];      /* samples; width x height of the source and of the reconstruction */
+    size_t src_pic_pitch[3], recon_pic_pitch[3];                  /* samples between pictures */
+    const svt_hip_qrows *q_luma, *q_chroma;      /* HOST */
+    const int16_t *d_tables;              /* svt_hip_intra_encode_tables_fill */
+    uint8_t *d_status;                    /* optional [npics][sb_pitch][256] */
+    svt_hip_intra_enc_result *d_result;   /* optional [npics][sb_pitch][256] */
+    int32_t *d_sb_qcoeff[3];              /* optional [npics][sb_pitch][4096], [1024], [1024] */
+    uint32_t *d_coeff_offset;             /* optional [npics][sb_pitch][256][2] */
+    void *d_scratch;
+    size_t scratch_bytes;
+} svt_hip_intra_encode_args;
+size_t svt_hip_intra_encode_scratch_bytes(uint32_t npics, uint32_t nsb);      /* HOST */
+size_t svt_hip_intra_encode_tables_bytes(void);                               /* HOST */
+int svt_hip_intra_encode_tables_fill(void *host);                             /* HOST: the blob d_tables holds */
+int svt_hip_intra_encode_launches(uint32_t sb_cols, uint32_t sb_rows, int planes);      /* HOST: launches of one call */
+int svt_hip_intra_encode_frame(const svt_hip_intra_encode_args *a, void *stream);
+
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
  * aom_dsp_rtcd.h it implements (svt_hip_rtcd_slot_count() entries: the 19 av1_fwd_txfm2d_WxH, the 19
