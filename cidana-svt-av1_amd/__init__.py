@@ -231,6 +231,19 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_intra_encode_launches.restype = c_int
     L.svt_hip_intra_encode_frame.argtypes = [c_void_p, c_void_p]
     L.svt_hip_intra_encode_frame.restype = c_int
+    L.svt_hip_dlf_mi_frame.argtypes = [c_void_p, c_void_p]
+    L.svt_hip_dlf_apply_frame.argtypes = [c_void_p, c_void_p]
+    L.svt_hip_dlf_search_frame.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_dlf_search_scratch_bytes.argtypes = [c_uint32, c_uint32, c_uint32]
+    L.svt_hip_dlf_search_scratch_bytes.restype = c_size_t
+    L.svt_hip_dlf_check.argtypes = [c_void_p, c_int]
+    L.svt_hip_dlf_mi_check.argtypes = [c_void_p]
+    L.svt_hip_dlf_limits.argtypes = [c_int, c_int, c_void_p]
+    L.svt_hip_dlf_levels.argtypes = [c_void_p, c_void_p]
+    L.svt_hip_dlf_pick_level.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+    L.svt_hip_dlf_level_from_q.argtypes = [c_int, c_int, c_int, c_void_p]
+    for name in ("mi_frame", "apply_frame", "search_frame", "check", "mi_check", "limits", "levels", "pick_level", "level_from_q"):
+        getattr(L, "svt_hip_dlf_" + name).restype = c_int
     L.svt_hip_md_search_scratch_bytes.argtypes = [c_void_p, c_int]
     L.svt_hip_md_search_scratch_bytes.restype = c_size_t
     L.svt_hip_md_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
@@ -2500,6 +2513,130 @@ class SvtHipDsp:
         self._check(self.lib.svt_hip_cdef_apply_frame(ctypes.addressof(p), self._p(luma_strength), self._p(chroma_strength), self._stream()),
                     "svt_hip_cdef_apply_frame")
         return dst
+
+    # -- deblocking: the mode-info grid, av1_loop_filter_frame, the filter-level search table and the host helpers of the pick ---------
+    class DlfPic(ctypes.Structure):
+        """svt_hip_dlf_pic"""
+        _fields_ = [("d_rec", c_void_p * 3), ("rec_stride", c_uint32 * 3), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3),
+                    ("d_dst", c_void_p * 3), ("dst_stride", c_uint32 * 3), ("d_mi", c_void_p), ("mi_stride", c_uint32),
+                    ("width", c_uint32), ("height", c_uint32), ("bit_depth", c_int32), ("npics", c_uint32),
+                    ("rec_pitch", ctypes.c_uint64 * 3), ("src_pitch", ctypes.c_uint64 * 3), ("dst_pitch", ctypes.c_uint64 * 3),
+                    ("mi_pitch", ctypes.c_uint64), ("filter_level", c_int32 * 2), ("filter_level_u", c_int32), ("filter_level_v", c_int32),
+                    ("sharpness_level", c_int32), ("mode_ref_delta_enabled", c_int32), ("ref_deltas", ctypes.c_int8 * 8),
+                    ("mode_deltas", ctypes.c_int8 * 2), ("pad", ctypes.c_uint8 * 6)]
+
+    class DlfMiArgs(ctypes.Structure):
+        """svt_hip_dlf_mi_args"""
+        _fields_ = [("d_final", c_void_p), ("d_final_count", c_void_p), ("d_info", c_void_p), ("d_mi", c_void_p), ("npics", c_uint32),
+                    ("nsb", c_uint32), ("sb_pitch", c_uint32), ("nsrc", c_uint32), ("mi_cols", c_uint32), ("mi_rows", c_uint32),
+                    ("mi_stride", c_uint32), ("pad", c_uint32), ("mi_pitch", ctypes.c_uint64)]
+
+    @staticmethod
+    def make_dlf_pic(rec, mi, width, height, bit_depth, levels=(0, 0, 0, 0), sharpness=0, ref_deltas=None, mode_deltas=None, src=None, dst=None):
+        """rec / src / dst: (Y, Cb, Cr) tensors, uint8 (bit depth 8) or uint16 / int16 (10), [rows, stride] for one picture or
+        [npics, rows, stride] for a stack; mi: uint8 [(npics,) rows, mi_stride, 4] (svt_hip_dlf_mi records); levels: filter_level[0],
+        filter_level[1], filter_level_u, filter_level_v; ref_deltas (8) / mode_deltas (2): given = mode_ref_delta_enabled.
+        -> DlfPic (keep the tensors alive!)"""
+        p = SvtHipDsp.DlfPic()
+        stack = rec[0].dim() == 3
+        p.npics = rec[0].shape[0] if stack else 1
+        for planes, ptr, stride, pitch in ((rec, p.d_rec, p.rec_stride, p.rec_pitch), (src, p.d_src, p.src_stride, p.src_pitch),
+                                           (dst, p.d_dst, p.dst_stride, p.dst_pitch)):
+            if planes is None:
+                continue
+            for i, t in enumerate(planes):
+                assert t.is_contiguous() and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
+                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.shape[-1], (t.shape[-2] * t.shape[-1] if stack else 0)
+        assert mi.is_contiguous() and mi.element_size() == 1 and mi.shape[-1] == 4 and mi.dim() == (4 if stack else 3)
+        p.d_mi, p.mi_stride, p.mi_pitch = mi.data_ptr(), mi.shape[-2], (mi.shape[-3] * mi.shape[-2] if stack else 0)
+        p.width, p.height, p.bit_depth = width, height, bit_depth
+        p.filter_level[0], p.filter_level[1], p.filter_level_u, p.filter_level_v = (int(v) for v in levels)
+        p.sharpness_level = int(sharpness)
+        p.mode_ref_delta_enabled = int(ref_deltas is not None or mode_deltas is not None)
+        for i, v in enumerate(ref_deltas if ref_deltas is not None else ()):
+            p.ref_deltas[i] = int(v)
+        for i, v in enumerate(mode_deltas if mode_deltas is not None else ()):
+            p.mode_deltas[i] = int(v)
+        return p
+
+    def dlf_mi_frame(self, final, final_count, info, mi, nsrc=None, mi_cols=None, mi_rows=None):
+        """svt_hip_dlf_mi_frame: scatter a final block list into the mode-info grid.  final: uint8 [(npics,) nsb, 256, 12]
+        (svt_hip_part_final) or int32 [(npics,) nsb, 256, 3]; final_count: int32 [(npics,) nsb]; info: uint8 [nsrc, 4] (ref_frame0, mode,
+        skip, 0); mi: uint8 [(npics,) rows, mi_stride, 4], written in place (units no entry covers keep what they held).  -> mi"""
+        a = self.DlfMiArgs()
+        stack = final_count.dim() == 2
+        a.npics = final_count.shape[0] if stack else 1
+        a.nsb = final_count.shape[-1]
+        a.sb_pitch = 0
+        a.nsrc = info.shape[0] if nsrc is None else nsrc
+        assert final.is_contiguous() and final_count.is_contiguous() and info.is_contiguous() and mi.is_contiguous() and mi.shape[-1] == 4
+        assert final.numel() * final.element_size() == a.npics * a.nsb * 256 * 12 and mi.dim() == (4 if stack else 3)
+        a.d_final, a.d_final_count, a.d_info, a.d_mi = final.data_ptr(), final_count.data_ptr(), info.data_ptr(), mi.data_ptr()
+        a.mi_stride = mi.shape[-2]
+        a.mi_cols = mi.shape[-2] if mi_cols is None else mi_cols
+        a.mi_rows = mi.shape[-3] if mi_rows is None else mi_rows
+        a.mi_pitch = mi.shape[-3] * mi.shape[-2] if stack else 0
+        self._check(self.lib.svt_hip_dlf_mi_frame(ctypes.byref(a), self._stream()), "svt_hip_dlf_mi_frame")
+        return mi
+
+    def dlf_apply_frame(self, rec, mi, width, height, bit_depth, levels, sharpness=0, ref_deltas=None, mode_deltas=None, dst=None, in_place=False):
+        """svt_hip_dlf_apply_frame (av1_loop_filter_frame over the three planes).  in_place: rec itself is filtered and returned; else
+        -> dst (Y, Cb, Cr), shaped as rec; only the picture area is written (the samples of a fresh dst outside it are zero)."""
+        t = self.torch
+        if in_place:
+            dst = rec
+        elif dst is None:
+            dst = tuple(t.zeros_like(x) for x in rec)      # partly written (the picture area of each plane): zeros define the rest
+        p = self.make_dlf_pic(rec, mi, width, height, bit_depth, levels, sharpness, ref_deltas, mode_deltas, dst=dst)
+        self._check(self.lib.svt_hip_dlf_apply_frame(ctypes.addressof(p), self._stream()), "svt_hip_dlf_apply_frame")
+        return dst
+
+    def dlf_search_scratch_bytes(self, width, height, npics=1):
+        """svt_hip_dlf_search_scratch_bytes (a host computation; 0 for a geometry the call refuses)"""
+        return self.lib.svt_hip_dlf_search_scratch_bytes(int(width), int(height), int(npics))
+
+    def dlf_search_frame(self, rec, src, mi, width, height, bit_depth, masks=(-1, -1, -1), sharpness=0, ref_deltas=None, mode_deltas=None,
+                         sse=None, scratch=None):
+        """svt_hip_dlf_search_frame: the table search_filter_level fills lazily.  masks: per plane the levels wanted (bit l = level l;
+        -1 = all 64).  -> sse int64 [(npics,) 3, 64]: ss_err[level] per plane, -1 (UINT64_MAX) for a level outside the mask."""
+        t = self.torch
+        p = self.make_dlf_pic(rec, mi, width, height, bit_depth, (0, 0, 0, 0), sharpness, ref_deltas, mode_deltas, src=src)
+        lead = (p.npics,) if rec[0].dim() == 3 else ()
+        if sse is None:
+            sse = t.empty(lead + (3, 64), dtype=t.int64, device=rec[0].device)
+        need = self.dlf_search_scratch_bytes(width, height, p.npics)
+        if scratch is None:
+            scratch = t.empty((max(need, 8),), dtype=t.uint8, device=rec[0].device)
+        assert sse.is_contiguous() and sse.numel() == p.npics * 3 * 64
+        m = (ctypes.c_uint64 * 3)(*[int(v) & 0xFFFFFFFFFFFFFFFF for v in masks])
+        self._check(self.lib.svt_hip_dlf_search_frame(ctypes.addressof(p), m, self._p(sse), self._p(scratch), scratch.numel() * scratch.element_size(),
+                                                      self._stream()), "svt_hip_dlf_search_frame")
+        return sse
+
+    @staticmethod
+    def dlf_pick_level(ss_err, start_level, loop_filter_mode, tx_mode_is_only_4x4):
+        """svt_hip_dlf_pick_level (search_filter_level's walk over a table of 64 int64, -1 = not computed; no device needed).
+        -> ("level", l) or ("need", l): the walk read level l, which the table does not hold"""
+        import numpy as np
+        tab = np.ascontiguousarray(ss_err, dtype=np.int64)
+        assert tab.shape == (64,)
+        level, need = ctypes.c_int(-1), ctypes.c_int(-1)
+        rc = load_library().svt_hip_dlf_pick_level(tab.ctypes.data, int(start_level), int(loop_filter_mode), int(tx_mode_is_only_4x4),
+                                                   ctypes.addressof(level), ctypes.addressof(need))
+        if rc == 1:
+            return "need", need.value
+        if rc != SVT_HIP_OK:
+            raise SvtHipError(f"svt_hip_dlf_pick_level = {rc}")
+        return "level", level.value
+
+    @staticmethod
+    def dlf_level_from_q(base_qindex, bit_depth, is_key_frame):
+        """svt_hip_dlf_level_from_q (the LPF_PICK_FROM_Q guess; no device needed) -> [filter_level[0], [1], u, v]"""
+        lv = (c_int * 4)()
+        rc = load_library().svt_hip_dlf_level_from_q(int(base_qindex), int(bit_depth), int(is_key_frame), lv)
+        if rc != SVT_HIP_OK:
+            raise SvtHipError(f"svt_hip_dlf_level_from_q = {rc}")
+        return list(lv)
 
     @staticmethod
     def md_intra_candidates(bwidth, bheight, sq_size, bsize, intra_pred_mode=0, is_16bit=False):

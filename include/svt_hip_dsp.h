@@ -2195,6 +2195,122 @@ int svt_hip_intra_encode_tables_fill(void *host);                             /*
 int svt_hip_intra_encode_launches(uint32_t sb_cols, uint32_t sb_rows, int planes);      /* HOST: launches of one call */
 int svt_hip_intra_encode_frame(const svt_hip_intra_encode_args *a, void *stream);
 
+/* Deblocking of whole pictures: av1_loop_filter_frame(recon, pcs, 0, 3) as the DLF process calls it (EbDlfProcess.c:162,
+ * EbDeblockingFilter.c:1351) and the filter-level search of av1_pick_filter_level (:1851), 8- and 10-bit 4:2:0, 64x64 superblocks.
+ *
+ * The mode-info grid.  The deblocker reads five members of MbModeInfo per 4x4 luma unit; they are held in a 4-byte record:
+ *   bsize            sb_type (clamped to 0 .. 21 on the device)
+ *   tx_size          the luma TxSize (clamped to 0 .. 18)
+ *   ref_frame_skip   ref_frame[0] (0 .. 7) in bits 0 .. 2, skip in bit 7
+ *   mode             the PredictionMode; anything at or above MB_MODE_COUNT (25), INTRA_MODE_4x4 among them, is read as DC_PRED
+ *                    (get_filter_level, :637)
+ * The grid is [mi_rows][mi_stride] records with mi_rows >= height / 4 and mi_stride >= width / 4 (the reference's is
+ * picture_width_in_sb * 16); pictures of a stack are mi_pitch records apart.
+ *
+ * svt_hip_dlf_mi_frame scatters a final block list (d_final / d_final_count as svt_hip_partition_decide_frame writes them) into the
+ * grid, what update_av1_mi_map (EbAdaptiveMotionVectorPrediction.c:1350-1415) does at the encode pass.  The fill rules are this
+ * project's glue: per entry k < d_final_count[sb] (a count above 256 is taken as 256) the geometry of mds_idx (clamped to 1 100) gives
+ * bsize and the block size's own transform size (blk_geom->txsize[0]); the entry's x, y are its place in the picture; d_info[src]
+ * gives ref_frame0, mode and skip; the bwidth / 4 x bheight / 4 units from (x / 4, y / 4) are written.  An entry is left out when its
+ * src is SVT_HIP_PART_NO_SRC or at or past nsrc, or when it reaches outside mi_cols x mi_rows.  Units no entry covers keep what they
+ * held.  One launch.  Validation (SVT_HIP_ERR_INVALID): NULL pointers, zero npics / nsb / nsrc / mi_cols / mi_rows, mi_stride below
+ * mi_cols, mi_cols or mi_rows above 16 384, npics * sb_pitch above 2^20, misalignment (4 bytes).
+ *
+ * svt_hip_dlf_apply_frame filters d_rec into d_dst; d_dst[i] == d_rec[i] for all three planes filters in place.
+ *   limits    update_sharpness and the hev threshold lvl >> 4 (:608-627, :691-692)
+ *   levels    av1_loop_filter_frame_init (:698-764): per plane, direction, reference frame and mode_lf_lut[mode], with the
+ *             1 << (lvl >> 5) scale of the deltas and the clamp to 0 .. 63
+ *   gating    loop_filter_sb (:1297-1303): both luma levels 0 end the plane loop (chroma is not filtered either); a chroma level 0
+ *             skips that plane; with two buffers an unfiltered plane is copied
+ *   edges     set_lpf_parameters (:893-1012) for every 4-sample edge unit: nothing at or beyond the plane's width / height; chroma
+ *             reads the mode-info at the odd row and column of the 8x8; the previous unit lies 1 << ss units back in the edge's
+ *             direction; the chroma transform size is av1_get_max_uv_txsize(bsize) through txsize_horz_map / txsize_vert_map; an edge
+ *             only where the coordinate is a non-zero multiple of the current unit's transform side; it is filtered when
+ *             (curr_level || pv_lvl) && (!pv_skip || !curr_skipped || pu_edge), a unit counting as skipped when skip &&
+ *             ref_frame[0] > INTRA_FRAME; length 4 / 8 / 14 (luma) or 4 / 6 (chroma) from the smaller transform side;
+ *             level = curr_level ? curr_level : pv_lvl
+ *   filters   aom_lpf_{vertical,horizontal}_{4,6,8,14} and their highbd twins (filter4 / 6 / 8 / 14, :133-370; the thresholds
+ *             shifted by bit_depth - 8)
+ * The reference filters superblock by superblock and delays the horizontal edges by one superblock column; that equals every
+ * vertical edge of the picture, then every horizontal one, and inside a pass no edge reads a sample another edge of the pass
+ * modifies.  The reference walks by the current transform size, the kernels decide every 4-sample unit on its own:
+ * the two agree on a grid whose blocks are aligned to their size; on any other grid the samples are unspecified, but nothing outside
+ * width x height of a plane is read or written.  In place: two launches (vertical edges, horizontal edges).  Two buffers: one launch
+ * over 64x64 tiles with a halo of 8 samples in the LDS.
+ * Validation (SVT_HIP_ERR_INVALID): NULL planes or grid; a side that is 0, not a multiple of 8 or above 65 535; a stride below the
+ * width; mi_stride below width / 4; a level above 63 or below 0; sharpness outside 0 .. 7; a bit depth other than 8 / 10; a delta
+ * outside -63 .. 63; npics 0 or above 65 535; d_dst planes that are partly equal to d_rec, or that overlap d_rec without being equal.
+ *
+ * svt_hip_dlf_search_frame builds the table search_filter_level (:1687) fills lazily: d_sse[pic][plane][64] (uint64) = ss_err[level]
+ * of the plane.  For every level in mask[plane] (bit l = level l) the plane is filtered as try_filter_frame does (:1632-1686; luma
+ * with the trial level in both directions, the reference's dir == 2 call; Cb / Cr with the trial level; sharpness and deltas from the
+ * descriptor, its four levels ignored) and the squared error against d_src is summed over width x height (PictureSseCalculations,
+ * :1470).  Level 0 is the unfiltered plane's SSE.  Levels outside the mask are written as UINT64_MAX, the reference's "not computed"
+ * -1, so every entry is defined after the call.  Filtered samples are never stored and d_rec is not written.  Two launches: per
+ * tile and plane the partial sums (the tile and the source staged once for all levels), then their sum per (picture, plane, level).
+ * d_scratch: svt_hip_dlf_search_scratch_bytes(width, height, npics) bytes, 8-byte aligned.
+ *
+ * Every call validates every host argument before anything is enqueued, only enqueues on the given stream, allocates nothing, never
+ * synchronises and can be captured into a HIP graph.  svt_hip_dlf_check runs the same validation without a device (for_search: 0 =
+ * apply, 1 = search).
+ * NOT here: delta LF (delta_lf_present_flag, which the reference itself refuses), segment features, 128-wide superblocks, more than
+ * one transform block per luma block, LPF_PICK_FROM_SUBIMAGE, loop restoration. */
+typedef struct svt_hip_dlf_mi { uint8_t bsize, tx_size, ref_frame_skip, mode; } svt_hip_dlf_mi;
+typedef struct svt_hip_dlf_info { uint8_t ref_frame0, mode, skip, pad; } svt_hip_dlf_info;      /* one per src */
+typedef struct svt_hip_dlf_mi_args {
+    const svt_hip_part_final *d_final;    /* [npics][sb_pitch][256] */
+    const uint32_t *d_final_count;        /* [npics][sb_pitch] */
+    const svt_hip_dlf_info *d_info;       /* [nsrc] */
+    svt_hip_dlf_mi *d_mi;                 /* [npics] grids of [mi_rows][mi_stride], mi_pitch records apart */
+    uint32_t npics, nsb, sb_pitch;        /* sb_pitch 0 = nsb */
+    uint32_t nsrc;
+    uint32_t mi_cols, mi_rows, mi_stride;
+    uint32_t pad;
+    uint64_t mi_pitch;
+} svt_hip_dlf_mi_args;
+typedef struct svt_hip_dlf_pic {
+    const void *d_rec[3];  uint32_t rec_stride[3];   /* the reconstruction (Y, Cb, Cr), strides in samples */
+    const void *d_src[3];  uint32_t src_stride[3];   /* the source picture (search only) */
+    void *d_dst[3];        uint32_t dst_stride[3];   /* the deblocked picture (apply only); all three equal to d_rec = in place */
+    const svt_hip_dlf_mi *d_mi; uint32_t mi_stride;
+    uint32_t width, height;
+    int32_t bit_depth;
+    uint32_t npics;                                 /* >= 1 */
+    uint64_t rec_pitch[3], src_pitch[3], dst_pitch[3], mi_pitch;      /* samples / records between the pictures of a stack */
+    int32_t filter_level[2];                        /* luma: [0] vertical edges, [1] horizontal edges (apply only) */
+    int32_t filter_level_u, filter_level_v;         /* (apply only) */
+    int32_t sharpness_level;
+    int32_t mode_ref_delta_enabled;
+    int8_t ref_deltas[8], mode_deltas[2];
+    uint8_t pad[6];
+} svt_hip_dlf_pic;
+int svt_hip_dlf_mi_frame(const svt_hip_dlf_mi_args *a, void *stream);
+int svt_hip_dlf_apply_frame(const svt_hip_dlf_pic *pic, void *stream);
+int svt_hip_dlf_search_frame(const svt_hip_dlf_pic *pic, const uint64_t mask[3], uint64_t *d_sse, void *d_scratch, size_t scratch_bytes,
+                             void *stream);
+size_t svt_hip_dlf_search_scratch_bytes(uint32_t width, uint32_t height, uint32_t npics);      /* HOST; 0 for a bad geometry */
+int svt_hip_dlf_check(const svt_hip_dlf_pic *pic, int for_search);                              /* HOST */
+int svt_hip_dlf_mi_check(const svt_hip_dlf_mi_args *a);                                         /* HOST */
+/* HOST: the tables the kernels use, for inspection: lim / mblim / hev_thr of a level at a sharpness (update_sharpness), and the
+ * level of (plane 0 .. 2, dir 0 .. 1, ref_frame 0 .. 7, mode_lf 0 .. 1) that av1_loop_filter_frame_init stores for pic. */
+int svt_hip_dlf_limits(int level, int sharpness_level, uint8_t out[3]);
+int svt_hip_dlf_levels(const svt_hip_dlf_pic *pic, uint8_t out[3][2][8][2]);
+
+/* HOST helpers of the level pick, no device.
+ * svt_hip_dlf_pick_level: the walk of search_filter_level (:1711-1848) over a table ss_err[64] (-1 = not computed).  start_level is
+ * what the reference takes from last_frame_filter_level: for luma entry [2], the previous picture's filter_level_u, because
+ * av1_pick_filter_level calls with dir 2 (:1918-1920, :1706); for Cb entry [2] and for Cr entry [3], the previous u and v levels.
+ * loop_filter_mode <= 2: one step of 2 either way; otherwise the halving search from step (start < 16 ? 4 : start / 4).  The bias
+ * against raising the level is (best_err >> (15 - filt_mid / 8)) * filter_step, halved unless tx_mode_is_only_4x4; a lower level
+ * wins when its error is below best + bias ("close to best"), a higher one when below best - bias ("significantly better").
+ * Returns SVT_HIP_OK with *level, or, when the walk reads an entry that is -1, SVT_HIP_DLF_NEED_LEVEL with that level in *need: a
+ * caller fills the table in rounds (svt_hip_dlf_search_frame with that bit) or asks for all 64 at once.
+ * svt_hip_dlf_level_from_q: the LPF_PICK_FROM_Q branch (:1867-1909) on the library's quantiser table: levels = {filter_level[0],
+ * filter_level[1], filter_level_u, filter_level_v}. */
+#define SVT_HIP_DLF_NEED_LEVEL 1
+int svt_hip_dlf_pick_level(const int64_t ss_err[64], int start_level, int loop_filter_mode, int tx_mode_is_only_4x4, int *level, int *need);
+int svt_hip_dlf_level_from_q(int base_qindex, int bit_depth, int is_key_frame, int levels[4]);
+
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
  * aom_dsp_rtcd.h it implements (svt_hip_rtcd_slot_count() entries: the 19 av1_fwd_txfm2d_WxH, the 19
