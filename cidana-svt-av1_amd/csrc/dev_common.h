@@ -137,6 +137,16 @@ __device__ __forceinline__ unsigned long long group_sum64(unsigned long long v) 
     for (int m = G / 2; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
     return v;
 }
+// inclusive prefix sum over the wave: lane i (the caller's threadIdx.x & 63) gets v of the lanes 0 .. i; lane 63 holds the wave's total
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v, int lane) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const uint32_t up = (uint32_t)__shfl_up((int)v, m, 64);
+        if (lane >= m) v += up;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_scan_total(uint32_t incl) { return (uint32_t)__shfl((int)incl, 63, 64); }
 
 // packed 16-bit helpers of the reconstruction stages (v_pk_add_i16, v_pk_max/min_i16, v_sat_pk_u8_i16)
 typedef short svt_v2s __attribute__((ext_vector_type(2)));

@@ -8,8 +8,8 @@
 #include <stdint.h>
 
 #include "../../include/svt_hip_dsp.h"
+#include "av1_geom.h"
 #include "host_err.h"
-#include "recon_final_plan.h"
 
 namespace svthost {
 
@@ -48,12 +48,12 @@ constexpr int dlf_level(int base, bool delta_on, int ref_delta, int mode_delta) 
 
 // the transform side across an edge (txsize_horz_map / txsize_vert_map of the plane's transform size) and the prediction block's side
 constexpr int dlf_tx_side(int plane, int dir, int bsize, int tx_size) {
-    if (plane == 0) return dir == 0 ? kRfTxW[tx_size] : kRfTxH[tx_size];
-    return dir == 0 ? rf_uv_w(bsize) : rf_uv_h(bsize);       // av1_get_max_uv_txsize: the 4:2:0 block's largest transform, 64 -> 32
+    if (plane == 0) return dir == 0 ? kTxW[tx_size] : kTxH[tx_size];
+    return dir == 0 ? bsize_uv_w(bsize) : bsize_uv_h(bsize);       // av1_get_max_uv_txsize: the 4:2:0 block's largest transform, 64 -> 32
 }
 constexpr int dlf_pu_side(int plane, int dir, int bsize) {
-    const int s = dir == 0 ? kRfBsW[bsize] : kRfBsH[bsize];
-    return plane == 0 ? s : rf_max(s / 2, 4);                // get_plane_block_size (ss_size_lookup)
+    const int s = dir == 0 ? kBsizeW[bsize] : kBsizeH[bsize];
+    return plane == 0 ? s : geom_max(s / 2, 4);                // get_plane_block_size (ss_size_lookup)
 }
 // the filter length from the smaller of the two transform sides
 constexpr int dlf_length(int plane, int min_side) { return min_side <= 4 ? 4 : (plane ? 6 : (min_side == 8 ? 8 : 14)); }

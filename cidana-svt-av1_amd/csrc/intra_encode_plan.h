@@ -7,7 +7,7 @@
 // workgroup waits for another.  A grid of sb_cols x sb_rows takes sb_cols + 2 (sb_rows - 1) steps.
 //
 // Schedule.  Inside a step one workgroup per (picture, superblock, plane) walks the superblock's entries strictly in order.  A walker
-// kernel holds the encode bodies of ONE launch kind (recon_final_plan.h's rf_class_of: 0 = both sides up to 16, 1 = a 32-sample side,
+// kernel holds the encode bodies of ONE launch kind (av1_geom.h's tx_launch_kind: 0 = both sides up to 16, 1 = a 32-sample side,
 // 2 = a 64-sample side except 64x64, 3 = 64x64; all nineteen bodies in one function go to scratch, kernel_frame.h), advances the plane's
 // cursor while the next entry's transform size is of its kind and stops at the first that is not.  A fixed sequence of kinds must
 // therefore contain, as a subsequence, the kind runs of every partition tree of a 64x64 superblock:
@@ -27,16 +27,15 @@
 #include <stdint.h>
 
 #include "../../include/svt_hip_dsp.h"
+#include "av1_geom.h"
 #include "host_err.h"
 #include "md_plan.h"
 #include "partition_plan.h"
-#include "recon_final_plan.h"
 
 namespace svthost {
 
-constexpr uint32_t IE_MAX_NSB = RF_MAX_NSB, IE_MAX_NPICS = 65535;      // pictures are a grid dimension of the walkers
+constexpr uint32_t IE_MAX_NSB = 1u << 20, IE_MAX_NPICS = 65535;      // pictures are a grid dimension of the walkers
 constexpr int IE_THREADS = 256;
-constexpr int ie_kind_of(int tx_size) { return rf_class_of(tx_size); }
 
 constexpr uint8_t kIeLumaSchedule[] = {3, 2, 0, 1, 0, 1, 0, 1, 0, 1, 0, 2};
 constexpr uint8_t kIeChromaSchedule[] = {0, 1, 0};
@@ -78,13 +77,13 @@ inline size_t intra_encode_scratch_bytes(uint32_t npics, uint32_t nsb) {
 }
 
 // ---- the inverse scans: [transform size][type][min(w, 32) * min(h, 32)] int16, sizes back to back ---------------------------------------
-constexpr uint32_t ie_ncoeff(int tx_size) { return (uint32_t)rf_min(kRfTxW[tx_size], 32) * (uint32_t)rf_min(kRfTxH[tx_size], 32); }
+constexpr uint32_t ie_ncoeff(int tx_size) { return (uint32_t)geom_min(kTxW[tx_size], 32) * (uint32_t)geom_min(kTxH[tx_size], 32); }
 constexpr uint32_t ie_iscan_first(int tx_size) {
     uint32_t n = 0;
     for (int t = 0; t < tx_size; t++) n += 16u * ie_ncoeff(t);
     return n;
 }
-constexpr size_t IE_TABLE_BYTES = (size_t)ie_iscan_first(RF_TX_SIZES) * 2;
+constexpr size_t IE_TABLE_BYTES = (size_t)ie_iscan_first(SVT_TX_SIZES_ALL) * 2;
 static_assert(IE_TABLE_BYTES % 16 == 0, "the blob in 16-byte units");
 
 inline int intra_encode_planes(const svt_hip_intra_encode_args* a) { return a->d_recon[1] || a->d_recon[2] || a->d_src[1] || a->d_src[2] ? 3 : 1; }

@@ -23,7 +23,7 @@
 #pragma once
 #include "dev_common.h"
 #include "dlf_plan.h"
-#include "partition_plan.h"
+#include "kernel_final_list.h"
 
 namespace svtdev {
 
@@ -33,28 +33,20 @@ template <typename T> constexpr int dlf_pitch() { return DLF_SIDE + (sizeof(T) =
 constexpr int DLF_EDGES = DLF_T / 4 + 1;                    // edges a tile filters per row / column: its own and the next tile's first
 
 struct DlfTab {
-    uint8_t tx_side[2][svthost::RF_TX_SIZES];      // [dir] luma transform side across the edge
+    uint8_t tx_side[2][SVT_TX_SIZES_ALL];          // [dir] luma transform side across the edge
     uint8_t uv_side[2][22];                        // [dir] chroma transform side, by block size
     uint8_t pu_side[2][2][22];                     // [chroma][dir] prediction block side
-    uint8_t bs_w4[22], bs_h4[22], bs_tx[22];       // block size -> width / 4, height / 4, its own transform size (the scatter)
-    uint8_t mds_bsize[svthost::PART_BLOCKS];
 };
 constexpr DlfTab dlf_tab() {
     DlfTab T{};
-    const svthost::PartGeomTab G = svthost::part_geom_tab();
     for (int d = 0; d < 2; d++) {
-        for (int t = 0; t < svthost::RF_TX_SIZES; t++) T.tx_side[d][t] = (uint8_t)svthost::dlf_tx_side(0, d, 0, t);
+        for (int t = 0; t < SVT_TX_SIZES_ALL; t++) T.tx_side[d][t] = (uint8_t)svthost::dlf_tx_side(0, d, 0, t);
         for (int b = 0; b < 22; b++) {
             T.uv_side[d][b] = (uint8_t)svthost::dlf_tx_side(1, d, b, 0);
             T.pu_side[0][d][b] = (uint8_t)svthost::dlf_pu_side(0, d, b);
             T.pu_side[1][d][b] = (uint8_t)svthost::dlf_pu_side(1, d, b);
         }
     }
-    for (int b = 0; b < 22; b++) {
-        T.bs_w4[b] = svthost::kRfBsW[b] / 4; T.bs_h4[b] = svthost::kRfBsH[b] / 4;
-        T.bs_tx[b] = (uint8_t)(svthost::rf_bsize_ok(b) ? svthost::rf_txsize(b) : 4);
-    }
-    for (int i = 0; i < svthost::PART_BLOCKS; i++) T.mds_bsize[i] = G.blk[i].bsize;
     return T;
 }
 static __device__ const DlfTab kDlfTab = dlf_tab();
@@ -338,17 +330,17 @@ __global__ __launch_bounds__(svthost::DLF_MI_THREADS) void dlf_mi_kernel(DlfMiDe
     if (unit >= F.npics * F.nsb) return;
     const uint32_t pic = unit / F.nsb, sb = unit % F.nsb;
     const size_t slot = (size_t)pic * F.sb_pitch + sb;
-    const uint32_t count = min(F.final_count[slot], (uint32_t)svthost::PART_MAX_FINAL);
+    const uint32_t count = final_count_of(F.final_count, slot);
     uint32_t* mi = F.mi + pic * F.mi_pitch;
     for (uint32_t k = lane; k < count; k += 64) {
-        const uint32_t* e = F.final_blk + (slot * svthost::PART_MAX_FINAL + k) * 3;
-        const uint32_t w0 = e[0], w1 = e[1], src = e[2];
+        const FinalEntry e = final_entry_load(F.final_blk, slot, k);
+        const uint32_t src = e.src;
         if (src >= F.nsrc) continue;                           // SVT_HIP_PART_NO_SRC among them
-        const uint32_t mds = min(w0 & 0xFFFFu, (uint32_t)svthost::PART_BLOCKS - 1), bsize = kDlfTab.mds_bsize[mds];
-        const uint32_t c0 = (w0 >> 16) >> 2, r0 = (w1 & 0xFFFFu) >> 2, nc = kDlfTab.bs_w4[bsize], nr = kDlfTab.bs_h4[bsize];
+        const uint32_t bsize = kGeomTab.bsize_of[e.mds];       // the md-scan block's size, in 4x4 units on the grid
+        const uint32_t c0 = e.x >> 2, r0 = e.y >> 2, nc = kGeomTab.bw[bsize] >> 2, nr = kGeomTab.bh[bsize] >> 2;
         if (c0 + nc > F.mi_cols || r0 + nr > F.mi_rows) continue;
         const uint32_t in = F.info[src];
-        const uint32_t rec = bsize | (uint32_t)kDlfTab.bs_tx[bsize] << 8 | ((in & 7u) | ((in >> 16 & 255u) ? 0x80u : 0u)) << 16 | (in >> 8 & 255u) << 24;
+        const uint32_t rec = bsize | (uint32_t)kGeomTab.tx[bsize] << 8 | ((in & 7u) | ((in >> 16 & 255u) ? 0x80u : 0u)) << 16 | (in >> 8 & 255u) << 24;
         for (uint32_t r = 0; r < nr; r++)
             for (uint32_t c = 0; c < nc; c++) mi[(size_t)(r0 + r) * F.mi_stride + c0 + c] = rec;
     }

@@ -6,7 +6,7 @@
 //           one 24-byte plan record per entry in scratch, a cleared result record per coded entry, and scatters the coded entries'
 //           smooth flags (is_smooth of the luma mode, of the chroma mode) into the grid of 4x4 units get_filt_type will consult.
 //   ie_walk_kernel<KIND> one workgroup per (superblock of the step, picture, plane).  It takes the plane's cursor and codes entry after
-//           entry while the entry's transform size is of launch kind KIND (intra_encode_plan.h): availability (intra_avail.h) ->
+//           entry while the entry's transform size is of launch kind KIND (av1_geom.h): availability (intra_avail.h) ->
 //           neighbour row / column from the reconstruction plane into LDS -> build_intra_predictors with run-time sizes into the plane
 //           -> (chroma, uv_mode 13) the CfL step -> the size's encode body (enc4_body / enc_staged_body / enc32_body / enc64_body, as
 //           enc_frame_kernel runs them) with pred == recon, one block.  It stops at the first entry of another kind and stores the
@@ -21,51 +21,28 @@
 #include "intra_avail.h"
 #include "intra_encode_plan.h"
 #include "kernel_bip.h"
+#include "kernel_final_list.h"
 #include "kernel_frame.h"
 
 namespace svtdev {
 
-constexpr int IE_FINAL = svthost::PART_MAX_FINAL;
-struct IeDevTab {
-    uint8_t tx[22], tx_uv[22], bw[22], bh[22], cw[22], ch[22];
-    uint8_t kind[svthost::RF_TX_SIZES], ls[svthost::RF_TX_SIZES];
-    uint32_t iscan_first[svthost::RF_TX_SIZES], ncoeff[svthost::RF_TX_SIZES];
-    uint8_t bsize_of[svthost::PART_BLOCKS];
-    uint32_t has_uv[(svthost::PART_BLOCKS + 31) / 32];
+constexpr int IE_FINAL = FL_MAX_FINAL;
+// the walkers' own, per transform size: the quantiser's log scale, and where the size's inverse scans start in the blob and how long
+// one is (the geometry and the launch kinds are kGeomTab's, kernel_final_list.h)
+struct IeWalkTab {
+    uint8_t ls[SVT_TX_SIZES_ALL];
+    uint32_t iscan_first[SVT_TX_SIZES_ALL], ncoeff[SVT_TX_SIZES_ALL];
 };
-constexpr IeDevTab ie_dev_tab() {
-    IeDevTab T{};
-    for (int b = 0; b < 22; b++) {
-        if (!svthost::rf_bsize_ok(b)) continue;
-        T.tx[b] = (uint8_t)svthost::rf_txsize(b); T.tx_uv[b] = (uint8_t)svthost::rf_txsize_uv(b);
-        T.bw[b] = svthost::kRfBsW[b]; T.bh[b] = svthost::kRfBsH[b];
-        T.cw[b] = (uint8_t)svthost::rf_uv_w(b); T.ch[b] = (uint8_t)svthost::rf_uv_h(b);
-    }
-    for (int t = 0; t < svthost::RF_TX_SIZES; t++) {
-        const int pels = svthost::kRfTxW[t] * svthost::kRfTxH[t];
-        T.kind[t] = (uint8_t)svthost::ie_kind_of(t); T.ls[t] = (uint8_t)(pels > 1024 ? 2 : (pels > 256 ? 1 : 0));
+constexpr IeWalkTab ie_walk_tab() {
+    IeWalkTab T{};
+    for (int t = 0; t < SVT_TX_SIZES_ALL; t++) {
+        const int pels = svthost::kTxW[t] * svthost::kTxH[t];
+        T.ls[t] = (uint8_t)(pels > 1024 ? 2 : (pels > 256 ? 1 : 0));
         T.iscan_first[t] = svthost::ie_iscan_first(t); T.ncoeff[t] = svthost::ie_ncoeff(t);
-    }
-    const svthost::PartGeomTab G = svthost::part_geom_tab();
-    for (int i = 0; i < svthost::PART_BLOCKS; i++) {
-        T.bsize_of[i] = G.blk[i].bsize;
-        if (G.blk[i].has_uv) T.has_uv[i >> 5] |= 1u << (i & 31);
     }
     return T;
 }
-static __device__ const IeDevTab kIeTab = ie_dev_tab();
-
-// the sizes of the launch kinds (kinds 0 and 3 are SVT_TX_CLASS0 and 64x64)
-#define SVT_IE_KIND1(X, L) X(3, 32, 32) X(9, 16, 32) X(10, 32, 16) X(15, 8, 32) L(16, 32, 8)
-#define SVT_IE_KIND2(X, L) X(11, 32, 64) X(12, 64, 32) X(17, 16, 64) L(18, 64, 16)
-#define SVT_IE_IS0(N, W, H) &&svthost::ie_kind_of(N) == 0 && svthost::kRfTxW[N] == W && svthost::kRfTxH[N] == H
-#define SVT_IE_IS1(N, W, H) &&svthost::ie_kind_of(N) == 1 && svthost::kRfTxW[N] == W && svthost::kRfTxH[N] == H
-#define SVT_IE_IS2(N, W, H) &&svthost::ie_kind_of(N) == 2 && svthost::kRfTxW[N] == W && svthost::kRfTxH[N] == H
-static_assert(svthost::ie_kind_of(4) == 3 SVT_TX_CLASS0(SVT_IE_IS0, SVT_IE_IS0) SVT_IE_KIND1(SVT_IE_IS1, SVT_IE_IS1) SVT_IE_KIND2(SVT_IE_IS2, SVT_IE_IS2),
-              "intra_encode_plan.h and the walkers agree on sizes and kinds");
-#undef SVT_IE_IS0
-#undef SVT_IE_IS1
-#undef SVT_IE_IS2
+static __device__ const IeWalkTab kIeTab = ie_walk_tab();
 
 struct IeDesc {
     const uint32_t* final_blk;             // svt_hip_part_final as three words
@@ -89,10 +66,6 @@ static_assert(sizeof(IeDesc) <= 3900, "kernel arguments");
 __device__ __forceinline__ char* ie_sb_scratch(const IeDesc& D, uint32_t pic, uint32_t sb) {
     return D.scratch + ((size_t)pic * D.nsb + sb) * svthost::IE_SB_BYTES;
 }
-__device__ __forceinline__ bool ie_type_ok(uint32_t tx_size, uint32_t type) {
-    const uint32_t k = kIeTab.kind[tx_size];
-    return type <= 15u && (k == 0 || (k == 1 && (type == 0 || type == 9)) || (k >= 2 && type == 0));
-}
 
 // ---- the pre-pass ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ie_prepass_kernel(const IeDesc in_kernarg) {
@@ -111,49 +84,39 @@ __global__ __launch_bounds__(256) void ie_prepass_kernel(const IeDesc in_kernarg
     if (lane < 8) hdr[lane] = 0;
     reinterpret_cast<uint32_t*>(grid)[lane] = 0;
     __threadfence_block();
-    const uint32_t count = min(D.final_count[gsb], (uint32_t)IE_FINAL);
+    const uint32_t count = final_count_of(D.final_count, gsb);
     const uint32_t sbx = (sb % D.sb_cols) * 16u, sby = (sb / D.sb_cols) * 16u;      // the superblock's origin in 4x4 units
     uint32_t run_y = 0, run_uv = 0;
 #pragma unroll 1
     for (uint32_t base = 0; base < count; base += 64) {
         const uint32_t k = base + (uint32_t)lane;
         const bool live = k < count;
-        uint32_t w0 = 0, w1 = 0, src = SVT_HIP_PART_NO_SRC;
-        if (live) { const uint32_t* e = D.final_blk + 3 * (gsb * IE_FINAL + k); w0 = e[0]; w1 = e[1]; src = e[2]; }
-        const uint32_t mds = min(w0 & 0xffffu, (uint32_t)svthost::PART_BLOCKS - 1), x = w0 >> 16, y = w1 & 0xffffu, part = w1 >> 24;
-        const uint32_t b = kIeTab.bsize_of[mds];
-        const uint32_t bw = kIeTab.bw[b], bh = kIeTab.bh[b], cw = kIeTab.cw[b], ch = kIeTab.ch[b];
-        const bool has_uv = (kIeTab.has_uv[mds >> 5] >> (mds & 31)) & 1u;
-        const uint32_t cx = ((x >> 3) << 3) >> 1, cy = ((y >> 3) << 3) >> 1;
+        FinalEntry e;
+        if (live) e = final_entry_load(D.final_blk, gsb, k);
+        const uint32_t src = e.src, x = e.x, y = e.y, part = e.part;
+        // the block size of the md-scan block; chroma inside plane 1 (the host requires both chroma planes to be exactly half)
+        const uint32_t b = kGeomTab.bsize_of[e.mds];
+        const EntryGeom g = entry_geom(e, b);
+        const uint32_t bw = g.bw, bh = g.bh;
+        const bool has_uv = g.has_uv;
         uint32_t reason = SVT_HIP_INTRA_ENC_OK;
         if (src == SVT_HIP_PART_NO_SRC || src >= D.nsrc) reason = SVT_HIP_INTRA_ENC_NO_SRC;
-        if (reason == SVT_HIP_INTRA_ENC_OK) {
-            bool inside = x + bw <= D.width[0] && y + bh <= D.height[0];
-            if (D.planes == 3 && has_uv) inside = inside && cx + cw <= D.width[1] && cy + ch <= D.height[1];
-            if (!inside) reason = SVT_HIP_INTRA_ENC_OUTSIDE;
-        }
+        if (reason == SVT_HIP_INTRA_ENC_OK && !entry_inside(e, g, D.width, D.height, D.planes == 3 ? 2u : 1u)) reason = SVT_HIP_INTRA_ENC_OUTSIDE;
         uint2 bl = make_uint2(0, 0);
         if (reason == SVT_HIP_INTRA_ENC_OK) bl = D.blk[(size_t)pic * D.blk_pitch + src];
         const uint32_t is_intra = bl.x & 0xffu, mode = (bl.x >> 8) & 0xffu, uv_mode = bl.x >> 24;
         const int delta = (int)(int8_t)((bl.x >> 16) & 0xffu);
         const uint32_t type = (bl.y >> 16) & 0xffu, type_uv = bl.y >> 24;
         if (reason == SVT_HIP_INTRA_ENC_OK) {
-            if (!ie_type_ok(kIeTab.tx[b], type) || (has_uv && !ie_type_ok(kIeTab.tx_uv[b], type_uv))) reason = SVT_HIP_INTRA_ENC_TX_TYPE;
+            if (!svthost::tx_type_ok_sides(bw, bh, type) || (has_uv && !svthost::tx_type_ok_sides(g.cw, g.ch, type_uv))) reason = SVT_HIP_INTRA_ENC_TX_TYPE;
             else if (!is_intra) reason = SVT_HIP_INTRA_ENC_NOT_INTRA;
             else if (mode > 12u || uv_mode > 13u || delta < -3 || delta > 3 || (delta != 0 && !(mode >= 1 && mode <= 8))) reason = SVT_HIP_INTRA_ENC_MODE;
             else if (uv_mode == 13u && (bw > 32 || bh > 32 || bw < 8 || bh < 8)) reason = SVT_HIP_INTRA_ENC_CFL_SIZE;
         }
         const bool coded = live && reason == SVT_HIP_INTRA_ENC_OK;
-        const bool adv = coded || (live && reason == SVT_HIP_INTRA_ENC_NOT_INTRA);
-        const uint32_t add_y = adv ? bw * bh : 0u, add_uv = adv && has_uv ? cw * ch : 0u;
-        uint32_t in_y = add_y, in_uv = add_uv;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const uint32_t uy = (uint32_t)__shfl_up((int)in_y, m, 64), uu = (uint32_t)__shfl_up((int)in_uv, m, 64);
-            if (lane >= m) { in_y += uy; in_uv += uu; }
-        }
-        const uint32_t off_y = run_y + in_y - add_y, off_uv = run_uv + in_uv - add_uv;
-        run_y += (uint32_t)__shfl((int)in_y, 63, 64); run_uv += (uint32_t)__shfl((int)in_uv, 63, 64);
+        const bool adv = coded || (live && reason == SVT_HIP_INTRA_ENC_NOT_INTRA);      // the offsets advance over the coded entries and the ones that are not intra
+        uint32_t off_y, off_uv;
+        stream_offsets(adv ? bw * bh : 0u, adv && has_uv ? g.cw * g.ch : 0u, lane, run_y, run_uv, off_y, off_uv);
         if (live) {
             if (D.status) D.status[gsb * IE_FINAL + k] = (uint8_t)reason;
             if (D.coeff_offset) { uint32_t* o = D.coeff_offset + 2 * (gsb * IE_FINAL + k); o[0] = off_y; o[1] = off_uv; }
@@ -184,7 +147,7 @@ __global__ __launch_bounds__(256) void ie_finish_kernel(const IeDesc in_kernarg)
     const char* S = ie_sb_scratch(D, pic, sb);
     const uint32_t* hdr = reinterpret_cast<const uint32_t*>(S);
     const uint32_t* plan = reinterpret_cast<const uint32_t*>(S + svthost::IE_OFF_PLAN);
-    const uint32_t count = min(D.final_count[gsb], (uint32_t)IE_FINAL);
+    const uint32_t count = final_count_of(D.final_count, gsb);
     const uint32_t c0 = hdr[0], c1 = hdr[1], c2 = hdr[2];
     for (uint32_t k = (uint32_t)lane; k < count; k += 64) {
         const uint32_t w1 = plan[svthost::IE_PLAN_WORDS * k + 1];
@@ -382,11 +345,11 @@ __global__ __launch_bounds__(svthost::IE_THREADS) void ie_walk_kernel(const IeDe
     uint32_t* hdr = reinterpret_cast<uint32_t*>(S);
     const uint32_t* plan = reinterpret_cast<const uint32_t*>(S + svthost::IE_OFF_PLAN);
     uint2* result = D.result ? D.result + gsb * IE_FINAL : reinterpret_cast<uint2*>(S + svthost::IE_OFF_RESULT);
-    const uint32_t count = min(D.final_count[gsb], (uint32_t)IE_FINAL);
+    const uint32_t count = final_count_of(D.final_count, gsb);
     const uint8_t* src = D.src[plane] + (size_t)pic * D.src_pitch[plane];
     uint8_t* recon = D.recon[plane] + (size_t)pic * D.recon_pitch[plane];
     const uint32_t stride = D.stride[plane], src_stride = D.src_stride[plane];
-    const uint32_t span = plane == 0 ? svthost::RF_LUMA_SPAN : svthost::RF_CHROMA_SPAN;
+    const uint32_t span = plane == 0 ? svthost::kSbLumaSpan : svthost::kSbChromaSpan;
     uint32_t k = min(hdr[plane], count);
 #pragma unroll 1
     for (; k < count; k++) {
@@ -395,12 +358,12 @@ __global__ __launch_bounds__(svthost::IE_THREADS) void ie_walk_kernel(const IeDe
         const uint32_t bsize = min(w1 & 0xffu, 21u), part = (w1 >> 8) & 0xffu;
         const bool has_uv = (w1 >> 24) & 1u;
         if (((w1 >> 16) & 0xffu) != SVT_HIP_INTRA_ENC_OK || (plane != 0 && !has_uv) || srci >= D.nsrc) continue;
-        const uint32_t txs = min((uint32_t)(plane == 0 ? kIeTab.tx[bsize] : kIeTab.tx_uv[bsize]), (uint32_t)svthost::RF_TX_SIZES - 1);
-        if (kIeTab.kind[txs] != KIND) break;
+        const uint32_t txs = min((uint32_t)(plane == 0 ? kGeomTab.tx[bsize] : kGeomTab.tx_uv[bsize]), (uint32_t)SVT_TX_SIZES_ALL - 1);
+        if (kGeomTab.kind[txs] != KIND) break;
         const uint32_t x = w0 & 0xffffu, y = w0 >> 16;
-        const uint32_t w = plane == 0 ? kIeTab.bw[bsize] : kIeTab.cw[bsize], h = plane == 0 ? kIeTab.bh[bsize] : kIeTab.ch[bsize];
+        const uint32_t w = plane == 0 ? kGeomTab.bw[bsize] : kGeomTab.cw[bsize], h = plane == 0 ? kGeomTab.bh[bsize] : kGeomTab.ch[bsize];
         const uint32_t px = plane == 0 ? x : ((x >> 3) << 3) >> 1, py = plane == 0 ? y : ((y >> 3) << 3) >> 1;
-        if (w == 0 || px + w > D.width[plane] || py + h > D.height[plane] || x + kIeTab.bw[bsize] > D.width[0] || y + kIeTab.bh[bsize] > D.height[0]) continue;
+        if (w == 0 || px + w > D.width[plane] || py + h > D.height[plane] || x + kGeomTab.bw[bsize] > D.width[0] || y + kGeomTab.bh[bsize] > D.height[0]) continue;
         const uint2 bl = D.blk[(size_t)pic * D.blk_pitch + srci];
         const uint32_t uv_mode = min(bl.x >> 24, 13u);
         const bool cfl = plane != 0 && uv_mode == 13u;
@@ -477,7 +440,7 @@ __global__ __launch_bounds__(svthost::IE_THREADS) void ie_walk_kernel(const IeDe
             SVT_IE_DEFAULT(16, 32, 8)
             }
         } else if constexpr (KIND == 2) {
-            switch (txs) { SVT_IE_KIND2(SVT_IE_CASE, SVT_IE_DEFAULT) }
+            switch (txs) { SVT_TX_CLASS1B(SVT_IE_CASE, SVT_IE_DEFAULT) }
         } else {
             enc64_body<uint8_t, 8, false>(src, recon, recon, nullptr, qcoeff, nullptr, eob, nullptr, iscan, qp, 1u, xy, src_stride, stride, stride, 0u, lds);
         }

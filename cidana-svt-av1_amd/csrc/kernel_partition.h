@@ -22,6 +22,7 @@
 // Every index from device data is clamped (mds to 1 100, src to nsrc - 1, the leaf range to nleaves and 1 101 entries).
 #pragma once
 #include "dev_common.h"
+#include "kernel_final_list.h"
 #include "partition_plan.h"
 
 namespace svtdev {
@@ -248,14 +249,9 @@ __global__ __launch_bounds__(PT_THREADS) void partition_kernel(const PartitionDe
             for (uint32_t a = q.parent; a != svthost::PART_NO_PARENT; a = kPartTab.sq[a].parent) reached = reached && part[a] == PT_PARTITION_SPLIT;
             if (reached && p != PT_PARTITION_SPLIT) n = pt_shape_n(pt_shape_of_part(min(p, 9u)));
         }
-        uint32_t incl = n;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, m, 64);
-            if (lane >= m) incl += up;
-        }
+        const uint32_t incl = wave_scan_incl(n, lane);
         const uint32_t slot0 = total + incl - n;
-        total += (uint32_t)__shfl((int)incl, 63, 64);
+        total += wave_scan_total(incl);
         for (uint32_t k = 0; k < n; k++) {
             const uint32_t slot = slot0 + k;
             if (slot >= (uint32_t)PT_MAX_FINAL) break;                      // (disjoint blocks of at least 4x4: cannot happen)
@@ -263,10 +259,9 @@ __global__ __launch_bounds__(PT_THREADS) void partition_kernel(const PartitionDe
             const PartBlkDev g = kPartTab.blk[mds];
             const uint32_t e = entry[mds];
             const uint32_t src = e ? min(F.leaf[3 * (size_t)(lf + e - 1) + 2], F.nsrc - 1) : SVT_HIP_PART_NO_SRC;
-            uint32_t* out = F.final_blk + 3 * ((size_t)sb * PT_MAX_FINAL + slot);
-            out[0] = mds | ((ox + g.x) & 0xffffu) << 16;
-            out[1] = ((oy + g.y) & 0xffffu) | (uint32_t)g.bsize << 16 | p << 24;
-            out[2] = src;
+            FinalEntry fe;
+            fe.mds = mds; fe.x = ox + g.x; fe.y = oy + g.y; fe.bsize_byte = g.bsize; fe.part = p; fe.src = src;
+            final_entry_store(F.final_blk, sb, slot, fe);
             fsrc[slot] = src;
         }
     }

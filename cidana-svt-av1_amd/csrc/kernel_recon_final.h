@@ -25,50 +25,25 @@
 // An item: word 0 = group | plane << 5 | tx_type << 7 | (eob == 0) << 11, word 1 = the block's index in its group, word 2 = x | y << 16
 // on the plane, word 3 = the element offset of its span in d_sb_qcoeff[plane] (0xFFFFFFFF: no copy).
 #pragma once
+#include "kernel_final_list.h"
 #include "kernel_txfm_staged.h"
-#include "partition_plan.h"
 #include "recon_final_plan.h"
 
 namespace svtdev {
 
-constexpr int RF_SIZES = svthost::RF_TX_SIZES, RF_GROUPS = svthost::RF_MAX_GROUPS, RF_FINAL = svthost::RF_MAX_FINAL;
+constexpr int RF_SIZES = SVT_TX_SIZES_ALL, RF_GROUPS = svthost::RF_MAX_GROUPS, RF_FINAL = FL_MAX_FINAL;
 constexpr uint32_t RF_NO_COPY = 0xFFFFFFFFu;
 
-// per block size: luma and chroma transform size, chroma sides; per transform size: list start and capacity per superblock; has_uv of
-// the 1 101 blocks as bits: all from the host plan's constexpr builders
-struct RfDevTab {
-    uint8_t tx[22], tx_uv[22], bw[22], bh[22], cw[22], ch[22];
-    uint16_t list_first[RF_SIZES + 1], cap[RF_SIZES];
-    uint32_t has_uv[(svthost::PART_BLOCKS + 31) / 32];
-};
-constexpr RfDevTab rf_dev_tab() {
-    RfDevTab T{};
-    for (int b = 0; b < 22; b++) {
-        if (!svthost::rf_bsize_ok(b)) continue;
-        T.tx[b] = (uint8_t)svthost::rf_txsize(b); T.tx_uv[b] = (uint8_t)svthost::rf_txsize_uv(b);
-        T.bw[b] = svthost::kRfBsW[b]; T.bh[b] = svthost::kRfBsH[b];
-        T.cw[b] = (uint8_t)svthost::rf_uv_w(b); T.ch[b] = (uint8_t)svthost::rf_uv_h(b);
-    }
+// the lists' own: per transform size the list's start and capacity per superblock, from the host plan's constexpr functions (the
+// geometry is kGeomTab's, kernel_final_list.h)
+struct RfListTab { uint16_t list_first[RF_SIZES + 1], cap[RF_SIZES]; };
+constexpr RfListTab rf_list_tab() {
+    RfListTab T{};
     for (int t = 0; t < RF_SIZES; t++) { T.list_first[t] = (uint16_t)svthost::rf_list_first(t); T.cap[t] = (uint16_t)svthost::rf_cap(t); }
     T.list_first[RF_SIZES] = (uint16_t)svthost::RF_ITEMS_PER_SB;
-    const svthost::PartGeomTab G = svthost::part_geom_tab();
-    for (int i = 0; i < svthost::PART_BLOCKS; i++)
-        if (G.blk[i].has_uv) T.has_uv[i >> 5] |= 1u << (i & 31);
     return T;
 }
-static __device__ const RfDevTab kRfTab = rf_dev_tab();
-// the launches: 0 = register class 0, 1 and 2 = class 1 without and with a 64-sample side, 3 = 64x64 (see recon_final_kernel)
-#define SVT_RF_CLASS1A(X, L) X(3, 32, 32) X(9, 16, 32) X(10, 32, 16) X(15, 8, 32) L(16, 32, 8)
-#define SVT_RF_CLASS1B(X, L) X(11, 32, 64) X(12, 64, 32) X(17, 16, 64) L(18, 64, 16)
-#define SVT_RF_LAUNCH_OK(N, W, H) &&(svthost::rf_class_of(N) + 1) / 2 == tx_class_of(N) && svthost::kRfTxW[N] == W && svthost::kRfTxH[N] == H
-static_assert(svthost::rf_class_of(4) == 3 && tx_class_of(4) == 2 SVT_TX_CLASS0(SVT_RF_LAUNCH_OK, SVT_RF_LAUNCH_OK) SVT_TX_CLASS1(SVT_RF_LAUNCH_OK, SVT_RF_LAUNCH_OK),
-              "recon_final_plan.h and kernel_txfm_staged.h agree on sizes and classes");
-#define SVT_RF_IS1(N, W, H) &&svthost::rf_class_of(N) == 1
-#define SVT_RF_IS2(N, W, H) &&svthost::rf_class_of(N) == 2
-static_assert(true SVT_RF_CLASS1A(SVT_RF_IS1, SVT_RF_IS1) SVT_RF_CLASS1B(SVT_RF_IS2, SVT_RF_IS2), "the two halves of class 1");
-#undef SVT_RF_LAUNCH_OK
-#undef SVT_RF_IS1
-#undef SVT_RF_IS2
+static __device__ const RfListTab kReconLists = rf_list_tab();
 
 // vtx_tab / htx_tab as two bits per type
 constexpr uint32_t rf_pack_kinds(const uint8_t (&k)[16]) {
@@ -99,15 +74,15 @@ __global__ __launch_bounds__(svthost::RF_BIN_THREADS) void recon_bin_kernel(cons
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t sb = blockIdx.x * svthost::RF_BIN_WAVES + wave;
     if (sb >= F.nsb) return;                                                // wave-uniform
-    const uint32_t count = min(F.final_count[sb], (uint32_t)RF_FINAL);
+    const uint32_t count = final_count_of(F.final_count, sb);
     uint32_t run_y = 0, run_uv = 0;                                         // coded_area_sb / coded_area_sb_uv so far
 #pragma unroll 1
     for (uint32_t base = 0; base < count; base += 64) {
         const uint32_t k = base + (uint32_t)lane;
         const bool live = k < count;
-        uint32_t w0 = 0, w1 = 0, src = SVT_HIP_PART_NO_SRC;
-        if (live) { const uint32_t* e = F.final_blk + 3 * ((size_t)sb * RF_FINAL + k); w0 = e[0]; w1 = e[1]; src = e[2]; }
-        const uint32_t mds = min(w0 & 0xffffu, (uint32_t)svthost::PART_BLOCKS - 1), x = w0 >> 16, y = w1 & 0xffffu, bsize = (w1 >> 16) & 0xffu;
+        FinalEntry e;
+        if (live) e = final_entry_load(F.final_blk, sb, k);
+        const uint32_t src = e.src;
         uint32_t reason = SVT_HIP_RECON_OK;
         // the source group: scalar compares against the table (the groups cover [0, nsrc))
         uint32_t gi = 0, local = 0, gbsize = 0xffffu, uvtype = 0;
@@ -117,35 +92,20 @@ __global__ __launch_bounds__(svthost::RF_BIN_THREADS) void recon_bin_kernel(cons
             const ReconBinGroup G = F.g[i];
             if (src - G.src_first < G.nblocks) { gi = (uint32_t)i; local = src - G.src_first; gbsize = G.bsize; uvtype = G.tx_type_uv; }
         }
-        if (reason == SVT_HIP_RECON_OK && gbsize != bsize) reason = SVT_HIP_RECON_BSIZE;
-        const uint32_t b = reason == SVT_HIP_RECON_OK ? bsize : 0u;         // (a matched group's bsize is one the host accepted)
-        const uint32_t bw = kRfTab.bw[b], bh = kRfTab.bh[b], cw = kRfTab.cw[b], ch = kRfTab.ch[b], txs = kRfTab.tx[b], txs_uv = kRfTab.tx_uv[b];
-        const bool has_uv = (kRfTab.has_uv[mds >> 5] >> (mds & 31)) & 1u;
-        const uint32_t cx = ((x >> 3) << 3) >> 1, cy = ((y >> 3) << 3) >> 1;
-        if (reason == SVT_HIP_RECON_OK) {
-            bool inside = x + bw <= F.width[0] && y + bh <= F.height[0];
-            if (F.planes == 3 && has_uv)
-                inside = inside && cx + cw <= F.width[1] && cy + ch <= F.height[1] && cx + cw <= F.width[2] && cy + ch <= F.height[2];
-            if (!inside) reason = SVT_HIP_RECON_OUTSIDE;
-        }
+        if (reason == SVT_HIP_RECON_OK && gbsize != e.bsize_byte) reason = SVT_HIP_RECON_BSIZE;
+        // the entry's own block size (a matched group's bsize is one the host accepted); chroma inside both chroma planes
+        const EntryGeom g = entry_geom(e, reason == SVT_HIP_RECON_OK ? e.bsize_byte : 0u);
+        if (reason == SVT_HIP_RECON_OK && !entry_inside(e, g, F.width, F.height, F.planes)) reason = SVT_HIP_RECON_OUTSIDE;
         uint32_t eob01 = 0, eob2 = 0, type = 0;
         if (reason == SVT_HIP_RECON_OK) {
             const uint32_t* d = F.decision + RF_DEC_WORDS * (size_t)src;
             eob01 = d[RF_DEC_EOB01]; eob2 = d[RF_DEC_EOB2] & 0xffffu; type = d[RF_DEC_TX_TYPE] & 0xffu;
-            const uint32_t m = max(bw, bh);
-            if (type > 15u || (m == 64 && type != 0) || (m == 32 && type != 0 && type != 9)) reason = SVT_HIP_RECON_TX_TYPE;
+            if (!svthost::tx_type_ok_sides(g.bw, g.bh, type)) reason = SVT_HIP_RECON_TX_TYPE;      // the luma size only: the host checked the group's chroma type
         }
         const bool ok = live && reason == SVT_HIP_RECON_OK;
-        // the stream offsets: exclusive prefix sums over the reconstructed entries, in coding order
-        const uint32_t add_y = ok ? bw * bh : 0u, add_uv = ok && has_uv ? cw * ch : 0u;
-        uint32_t in_y = add_y, in_uv = add_uv;
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            const uint32_t uy = (uint32_t)__shfl_up((int)in_y, m, 64), uu = (uint32_t)__shfl_up((int)in_uv, m, 64);
-            if (lane >= m) { in_y += uy; in_uv += uu; }
-        }
-        const uint32_t off_y = run_y + in_y - add_y, off_uv = run_uv + in_uv - add_uv;
-        run_y += (uint32_t)__shfl((int)in_y, 63, 64); run_uv += (uint32_t)__shfl((int)in_uv, 63, 64);
+        // the stream offsets advance over the reconstructed entries only
+        uint32_t off_y, off_uv;
+        stream_offsets(ok ? g.bw * g.bh : 0u, ok && g.has_uv ? g.cw * g.ch : 0u, lane, run_y, run_uv, off_y, off_uv);
         if (live) {
             if (F.status) F.status[(size_t)sb * RF_FINAL + k] = (uint8_t)reason;
             if (F.coeff_offset) { uint32_t* o = F.coeff_offset + 2 * ((size_t)sb * RF_FINAL + k); o[0] = off_y; o[1] = off_uv; }
@@ -153,14 +113,14 @@ __global__ __launch_bounds__(svthost::RF_BIN_THREADS) void recon_bin_kernel(cons
         // the work items, plane by plane
 #pragma unroll 1
         for (uint32_t p = 0; p < F.planes; p++) {
-            const bool has = ok && (p == 0 || has_uv);
-            const uint32_t size = p == 0 ? txs : txs_uv;
+            const bool has = ok && (p == 0 || g.has_uv);
+            const uint32_t size = p == 0 ? g.txs : g.txs_uv;
             const uint32_t eob = p == 0 ? (eob01 & 0xffffu) : (p == 1 ? eob01 >> 16 : eob2);
-            const uint32_t span = p == 0 ? svthost::RF_LUMA_SPAN : svthost::RF_CHROMA_SPAN, off = p == 0 ? off_y : off_uv, area = p == 0 ? bw * bh : cw * ch;
+            const uint32_t span = p == 0 ? svthost::kSbLumaSpan : svthost::kSbChromaSpan, off = p == 0 ? off_y : off_uv, area = p == 0 ? g.bw * g.bh : g.cw * g.ch;
             uint4 item;
             item.x = gi | p << 5 | (p == 0 ? type : uvtype) << 7 | (eob == 0 ? 1u : 0u) << 11;
             item.y = local;
-            item.z = p == 0 ? (x | y << 16) : (cx | cy << 16);
+            item.z = p == 0 ? (e.x | e.y << 16) : (g.cx | g.cy << 16);
             item.w = F.stream && off + area <= span ? sb * span + off : RF_NO_COPY;
             unsigned long long pend = __ballot(has);
             while (pend) {                                                  // wave-uniform: one round per size present
@@ -171,8 +131,8 @@ __global__ __launch_bounds__(svthost::RF_BIN_THREADS) void recon_bin_kernel(cons
                 uint32_t at = 0;
                 if (lane == leader) at = atomicAdd(F.counters + s, (uint32_t)__popcll(m));
                 at = (uint32_t)__shfl((int)at, leader, 64) + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                const uint32_t room = (uint32_t)kRfTab.cap[s] * F.nsb;
-                if (mine && at < room) F.items[(size_t)kRfTab.list_first[s] * F.nsb + at] = item;
+                const uint32_t room = (uint32_t)kReconLists.cap[s] * F.nsb;
+                if (mine && at < room) F.items[(size_t)kReconLists.list_first[s] * F.nsb + at] = item;
                 pend &= ~m;
             }
         }
@@ -212,8 +172,8 @@ struct RfLds {
 #define SVT_RF_LDS(N, W, H) RfLds<W, H>::WAVE,
 template <int CLS> struct RfClass;
 template <> struct RfClass<0> { static constexpr int WAVES = 4, WAVE_LDS = cmax_of({SVT_TX_CLASS0(SVT_RF_LDS, SVT_RF_LDS)}); };
-template <> struct RfClass<1> { static constexpr int WAVES = 4, WAVE_LDS = cmax_of({SVT_RF_CLASS1A(SVT_RF_LDS, SVT_RF_LDS)}); };
-template <> struct RfClass<2> { static constexpr int WAVES = 4, WAVE_LDS = cmax_of({SVT_RF_CLASS1B(SVT_RF_LDS, SVT_RF_LDS)}); };
+template <> struct RfClass<1> { static constexpr int WAVES = 4, WAVE_LDS = cmax_of({SVT_TX_CLASS1A(SVT_RF_LDS, SVT_RF_LDS)}); };
+template <> struct RfClass<2> { static constexpr int WAVES = 4, WAVE_LDS = cmax_of({SVT_TX_CLASS1B(SVT_RF_LDS, SVT_RF_LDS)}); };
 template <> struct RfClass<3> { static constexpr int WAVES = 2, WAVE_LDS = RfLds<64, 64>::WAVE; };
 #undef SVT_RF_LDS
 
@@ -230,7 +190,7 @@ __device__ __forceinline__ bool rf_item_ok(const ReconFinalDesc& D, const uint4&
     const ReconFinalGroupDev& G = rf_group(D, ib.x);
     const uint32_t nblocks = G.nblocks, tx = (G.txs >> (8 * p)) & 0xffu, pc = min(p, 2u);
     const uint32_t x = ib.z & 0xffffu, y = ib.z >> 16;
-    const unsigned long long room = (unsigned long long)D.nsb * (p == 0 ? svthost::RF_LUMA_SPAN : svthost::RF_CHROMA_SPAN);
+    const unsigned long long room = (unsigned long long)D.nsb * (p == 0 ? svthost::kSbLumaSpan : svthost::kSbChromaSpan);
     const bool span_ok = ib.w == RF_NO_COPY || (D.stream != 0 && (unsigned long long)ib.w + StagedGeom<W, H>::NC <= room);
     return gi < D.ngroups && p < D.planes && ib.y < nblocks && tx == (uint32_t)N && x + W <= D.width[pc] && y + H <= D.height[pc] && span_ok;
 }
@@ -246,7 +206,7 @@ __device__ __forceinline__ void recon_final_body(const ReconFinalDesc& D, uint32
     static_assert(S::WAVES == WAVES, "a class's sizes share the workgroup shape");
     const uint32_t first = (piece * WAVES + (uint32_t)wave) * G::BPW;
     if (first >= count) return;                                             // wave-uniform
-    const uint4* items = D.items + (size_t)kRfTab.list_first[N] * D.nsb;
+    const uint4* items = D.items + (size_t)kReconLists.list_first[N] * D.nsb;
     const int sub = lane / G::LPB, l = lane % G::LPB;
     bool valid = first + sub < count;
     uint32_t it0 = 1u << 11;
@@ -377,8 +337,8 @@ __global__ __launch_bounds__(RfClass<CLS>::WAVES * 64) void recon_final_kernel(c
         before += pieces;                                                                                                 \
     }
     if constexpr (CLS == 0) { SVT_TX_CLASS0(SVT_RF_SIZE, SVT_RF_SIZE) }
-    else if constexpr (CLS == 1) { SVT_RF_CLASS1A(SVT_RF_SIZE, SVT_RF_SIZE) }
-    else if constexpr (CLS == 2) { SVT_RF_CLASS1B(SVT_RF_SIZE, SVT_RF_SIZE) }
+    else if constexpr (CLS == 1) { SVT_TX_CLASS1A(SVT_RF_SIZE, SVT_RF_SIZE) }
+    else if constexpr (CLS == 2) { SVT_TX_CLASS1B(SVT_RF_SIZE, SVT_RF_SIZE) }
     else { SVT_RF_SIZE(4, 64, 64) }
 #undef SVT_RF_SIZE
 }

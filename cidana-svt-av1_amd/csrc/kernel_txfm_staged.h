@@ -10,6 +10,7 @@
 #include <initializer_list>
 #include <type_traits>
 
+#include "av1_geom.h"
 #include "group_table.h"
 #include "kernel_txfm.h"
 
@@ -384,11 +385,25 @@ __device__ __forceinline__ uint4 add_clip(uint4 p, const short* res, int maxpix)
 // reference's numbering (EbDefinitions.h:615-650); tx_class_of, the kernels' LDS maxima and the case lists of their switches are
 // generated from it.  X takes every entry but the last, L the last one (a switch's default:).
 #define SVT_TX_CLASS0(X, L) X(0, 4, 4) X(1, 8, 8) X(2, 16, 16) X(5, 4, 8) X(6, 8, 4) X(7, 8, 16) X(8, 16, 8) X(13, 4, 16) L(14, 16, 4)
-#define SVT_TX_CLASS1(X, L) X(3, 32, 32) X(9, 16, 32) X(10, 32, 16) X(11, 32, 64) X(12, 64, 32) X(15, 8, 32) X(16, 32, 8) X(17, 16, 64) L(18, 64, 16)
+// Class 1 in two halves, without and with a 64-sample side: the kernels that walk the final block list (recon_final_kernel,
+// ie_walk_kernel) launch them apart.  With class 0 and 64x64 they are the launch kinds 0 .. 3 of av1_geom.h's tx_launch_kind.
+#define SVT_TX_CLASS1A(X, L) X(3, 32, 32) X(9, 16, 32) X(10, 32, 16) X(15, 8, 32) L(16, 32, 8)
+#define SVT_TX_CLASS1B(X, L) X(11, 32, 64) X(12, 64, 32) X(17, 16, 64) L(18, 64, 16)
+#define SVT_TX_CLASS1(X, L) SVT_TX_CLASS1A(X, X) SVT_TX_CLASS1B(X, L)
 #define SVT_TX_BIT(N, W, H) | (1u << N)
 constexpr unsigned kTxClass0 = 0u SVT_TX_CLASS0(SVT_TX_BIT, SVT_TX_BIT), kTxClass1 = 0u SVT_TX_CLASS1(SVT_TX_BIT, SVT_TX_BIT), kTxClass2 = 1u << 4;
 #undef SVT_TX_BIT
 static_assert((kTxClass0 ^ kTxClass1 ^ kTxClass2) == (1u << 19) - 1 && !(kTxClass0 & kTxClass1), "each of the sizes 0 .. 18 lands in exactly one class");
+#define SVT_TX_KIND_IS(K, N, W, H) &&svthost::tx_launch_kind(N) == K && svthost::kTxW[N] == W && svthost::kTxH[N] == H
+#define SVT_TX_KIND0(N, W, H) SVT_TX_KIND_IS(0, N, W, H)
+#define SVT_TX_KIND1(N, W, H) SVT_TX_KIND_IS(1, N, W, H)
+#define SVT_TX_KIND2(N, W, H) SVT_TX_KIND_IS(2, N, W, H)
+static_assert(svthost::tx_launch_kind(4) == 3 SVT_TX_CLASS0(SVT_TX_KIND0, SVT_TX_KIND0) SVT_TX_CLASS1A(SVT_TX_KIND1, SVT_TX_KIND1) SVT_TX_CLASS1B(SVT_TX_KIND2, SVT_TX_KIND2),
+              "av1_geom.h and the four lists (class 1 being its two halves) agree on sizes, sides and launch kinds");
+#undef SVT_TX_KIND_IS
+#undef SVT_TX_KIND0
+#undef SVT_TX_KIND1
+#undef SVT_TX_KIND2
 // bit masks, not a table: usable on the device with a run-time size
 __host__ __device__ constexpr int tx_class_of(int tx_size) {
     return tx_size == 4 ? 2 : (((kTxClass0 >> tx_size) & 1u) ? 0 : 1);

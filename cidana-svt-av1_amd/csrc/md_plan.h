@@ -10,15 +10,13 @@
 #include <vector>
 
 #include "../../include/svt_hip_dsp.h"
+#include "av1_geom.h"
 #include "host_err.h"
 #include "quant_params.h"
 
 namespace svthost {
 // ---- sizes ------------------------------------------------------------------------------------------------------------------------
-extern const int kTxW[SVT_TX_SIZES_ALL], kTxH[SVT_TX_SIZES_ALL];      // host_tables.cpp
-bool txfm_allowed(int tx_size, int tx_type);                           // host_tables.cpp
-// of a block size 0 .. 21: size_group_lookup, num_pels_log2_lookup, block_size_wide, block_size_high (host_tables.cpp)
-extern const uint8_t kSizeGroup[22], kNumPelsLog2[22], kBsizeW[22], kBsizeH[22];
+// (kTxW / kTxH, kBsizeW / kBsizeH, kSizeGroup, kNumPelsLog2 and tx_type_ok: av1_geom.h)
 inline int log2_of(int v) { int l = 0; while ((1 << l) < v) l++; return l; }
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 // a side as the coefficient arrays hold it (a 64-sample side packs to 32), and the coefficients of a block: min(W,32) * min(H,32)
@@ -55,7 +53,7 @@ inline int group_types_check(int g, int tx_size, int ntypes, const uint8_t* type
     unsigned seen = 0;
     for (int t = 0; t < ntypes; t++) {
         const int ty = types[t];
-        if (!txfm_allowed(tx_size, ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d not defined for tx_size %d", g, ty, tx_size);
+        if (!tx_type_ok(tx_size, ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d not defined for tx_size %d", g, ty, tx_size);
         if (seen & (1u << ty)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d listed twice", g, ty);
         seen |= 1u << ty;
     }
@@ -87,7 +85,7 @@ inline int qrows_check(const svt_hip_qrows* q, const char* name, int nscales) {
 inline int cfl_size_check(int g, int tx_size, int tx_type, uint32_t nblocks) {
     if (tx_size < 0 || tx_size >= SVT_TX_SIZES_ALL || kTxW[tx_size] > 16 || kTxH[tx_size] > 16)
         return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_size %d is no CfL chroma size (both sides 4 .. 16)", g, tx_size);
-    if (tx_type < 0 || !txfm_allowed(tx_size, tx_type)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d not defined for tx_size %d", g, tx_type, tx_size);
+    if (tx_type < 0 || !tx_type_ok(tx_size, tx_type)) return set_err(SVT_HIP_ERR_INVALID, "group %d: tx_type %d not defined for tx_size %d", g, tx_type, tx_size);
     return pairs_check(g, nblocks, kCflCands, "nblocks * 66");
 }
 

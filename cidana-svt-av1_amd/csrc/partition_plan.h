@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/svt_hip_dsp.h"
+#include "av1_geom.h"
 #include "host_err.h"
 
 namespace svthost {
@@ -33,14 +34,6 @@ constexpr uint16_t kPartRects[PART_SHAPES][4] = {
 };
 constexpr int part_shapes_of(int sq_size) { return sq_size >= 16 ? 9 : (sq_size == 8 ? 3 : 1); }
 constexpr int part_totns(int shape) { return shape < 1 ? 1 : (shape < 3 ? 2 : (shape < 7 ? 3 : 4)); }
-// AV1 block_size of a width and height (both 4 .. 64, ratio at most 4)
-constexpr int part_bsize_of(int w, int h) {
-    constexpr uint8_t W[22] = {4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64, 128, 128, 4, 16, 8, 32, 16, 64};
-    constexpr uint8_t H[22] = {4, 8, 4, 8, 16, 8, 16, 32, 16, 32, 64, 32, 64, 128, 64, 128, 16, 4, 32, 8, 64, 16};
-    for (int b = 0; b < 22; b++)
-        if (W[b] == w && H[b] == h) return b;
-    return 255;
-}
 
 struct PartSquare { uint16_t mds, parent; uint8_t depth, x, y, last_quadrant; };      // parent: square index, PART_NO_PARENT at the root
 struct PartGeomTab {
@@ -62,7 +55,7 @@ constexpr void part_scan(PartGeomTab& T, int sq_size, int x, int y, int depth, i
             g.d1i = (uint8_t)d1i++; g.sq_size = (uint8_t)sq_size; g.is_last_quadrant = (uint8_t)last_quadrant;
             g.origin_x = (uint8_t)(x + q * (r & 15)); g.origin_y = (uint8_t)(y + q * (r >> 4 & 15));
             g.bwidth = (uint8_t)(q * (r >> 8 & 15)); g.bheight = (uint8_t)(q * (r >> 12 & 15));
-            g.bsize = (uint8_t)part_bsize_of(g.bwidth, g.bheight);
+            g.bsize = (uint8_t)bsize_of(g.bwidth, g.bheight);
             // chroma: a 4x4 carries it in the last quadrant only; a block with a side of 4 shares its chroma block with its neighbours,
             // and the last of each group of 2 (one side 4) or 4 (both) carries it
             g.has_uv = 1;

@@ -10,9 +10,6 @@
 using namespace svtdev;
 using namespace svthost;
 
-static_assert(sizeof(svt_hip_part_final) == 12 && offsetof(svt_hip_part_final, x) == 2 && offsetof(svt_hip_part_final, y) == 4 &&
-              offsetof(svt_hip_part_final, bsize) == 6 && offsetof(svt_hip_part_final, part) == 7 && offsetof(svt_hip_part_final, src) == 8,
-              "svt_hip_part_final as three words");
 static_assert(sizeof(svt_hip_intra_enc_blk) == 8 && offsetof(svt_hip_intra_enc_blk, mode) == 1 && offsetof(svt_hip_intra_enc_blk, angle_delta) == 2 &&
               offsetof(svt_hip_intra_enc_blk, uv_mode) == 3 && offsetof(svt_hip_intra_enc_blk, cfl_alpha_idx) == 4 && offsetof(svt_hip_intra_enc_blk, cfl_alpha_signs) == 5 &&
               offsetof(svt_hip_intra_enc_blk, tx_type) == 6 && offsetof(svt_hip_intra_enc_blk, tx_type_uv) == 7, "svt_hip_intra_enc_blk as two words");
@@ -26,10 +23,10 @@ extern "C" int svt_hip_intra_encode_tables_fill(void* host) {
     if (!host) return set_err(SVT_HIP_ERR_INVALID, "NULL table");
     int16_t* out = (int16_t*)host;
     int16_t scan[1024], iscan[1024];
-    for (int t = 0; t < RF_TX_SIZES; t++)
+    for (int t = 0; t < SVT_TX_SIZES_ALL; t++)
         for (int ty = 0; ty < 16; ty++) {
             int16_t* o = out + ie_iscan_first(t) + (size_t)ty * ie_ncoeff(t);
-            if (rf_type_ok(t, ty)) {
+            if (tx_type_ok(t, ty)) {
                 if (svt_hip_get_scan(t, ty, scan, iscan) < 0) return set_err(SVT_HIP_ERR_INVALID, "no scan for size %d type %d", t, ty);
                 memcpy(o, iscan, ie_ncoeff(t) * sizeof(int16_t));
             } else {

@@ -1,6 +1,6 @@
 // svt_hip_recon_final.hip — svt_hip_recon_final_frame: the reconstruction of the final block list of every superblock of a picture
 // (recon_clear_kernel, recon_bin_kernel and recon_final_kernel<0 .. 3>, kernel_recon_final.h): six launches on one stream.
-// The checks, the tables, the scratch layout and the launch shapes are recon_final_plan.h's.
+// The checks, the scratch layout and the launch shapes are recon_final_plan.h's, the block and transform sizes av1_geom.h's.
 #include <stddef.h>
 
 #include "host_common.h"
@@ -11,9 +11,7 @@ using namespace svthost;
 
 static_assert(sizeof(svt_hip_md_decision) == 4 * RF_DEC_WORDS && offsetof(svt_hip_md_decision, eob) == 4 * RF_DEC_EOB01 &&
               offsetof(svt_hip_md_decision, tx_type) == 4 * RF_DEC_TX_TYPE, "recon_bin_kernel reads the record as eighteen words");
-static_assert(sizeof(svt_hip_part_final) == 12 && offsetof(svt_hip_part_final, x) == 2 && offsetof(svt_hip_part_final, y) == 4 &&
-              offsetof(svt_hip_part_final, bsize) == 6 && offsetof(svt_hip_part_final, src) == 8, "svt_hip_part_final as three words");
-static_assert(RF_COUNTER_BYTES >= 4 * RF_TX_SIZES && RF_COUNTER_BYTES % 16 == 0, "the counters, then the 16-byte items");
+static_assert(RF_COUNTER_BYTES >= 4 * SVT_TX_SIZES_ALL && RF_COUNTER_BYTES % 16 == 0, "the counters, then the 16-byte items");
 
 extern "C" size_t svt_hip_recon_final_scratch_bytes(uint32_t nsb) { return recon_final_scratch_bytes(nsb); }
 
@@ -37,7 +35,7 @@ extern "C" int svt_hip_recon_final_frame(const svt_hip_recon_final_args* a, void
         const svt_hip_recon_final_group& G = a->groups[g];
         B.g[g].src_first = G.src_first; B.g[g].nblocks = G.nblocks; B.g[g].bsize = (uint8_t)G.bsize; B.g[g].tx_type_uv = (uint8_t)G.tx_type_uv;
         R.g[g].nblocks = G.nblocks;
-        R.g[g].txs = (uint32_t)rf_txsize(G.bsize) | (uint32_t)rf_txsize_uv(G.bsize) << 8 | (uint32_t)rf_txsize_uv(G.bsize) << 16;
+        R.g[g].txs = (uint32_t)bsize_tx(G.bsize) | (uint32_t)bsize_tx_uv(G.bsize) << 8 | (uint32_t)bsize_tx_uv(G.bsize) << 16;
         for (int p = 0; p < a->planes; p++) { R.g[g].pred[p] = G.d_best_pred[p]; R.g[g].dq[p] = G.d_best_dqcoeff[p]; R.g[g].q[p] = stream_out ? G.d_best_qcoeff[p] : nullptr; }
     }
     hipLaunchKernelGGL(recon_clear_kernel, dim3(1), dim3(64), 0, s, B.counters);

@@ -174,10 +174,10 @@ static int test_tables() {
                 CHECK(dlf_level(base, true, rd, md) == v && dlf_level(base, false, rd, md) == base);
             }
     // sides: the luma transform's own, the chroma block's halved, 4 at least, 32 at most
-    for (int t = 0; t < 19; t++) CHECK(dlf_tx_side(0, 0, 0, t) == kRfTxW[t] && dlf_tx_side(0, 1, 0, t) == kRfTxH[t]);
+    for (int t = 0; t < 19; t++) CHECK(dlf_tx_side(0, 0, 0, t) == kTxW[t] && dlf_tx_side(0, 1, 0, t) == kTxH[t]);
     for (int b = 0; b < 22; b++)
         for (int d = 0; d < 2; d++) {
-            const int s = d ? kRfBsH[b] : kRfBsW[b], half = s / 2 < 4 ? 4 : s / 2;
+            const int s = d ? kBsizeH[b] : kBsizeW[b], half = s / 2 < 4 ? 4 : s / 2;
             CHECK(dlf_pu_side(0, d, b) == s && dlf_pu_side(1, d, b) == half && dlf_tx_side(1, d, b, 0) == (half > 32 ? 32 : half));
         }
     for (int plane = 0; plane < 2; plane++)

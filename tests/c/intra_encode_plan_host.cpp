@@ -152,8 +152,8 @@ static int test_scratch_steps_and_launches() {
     CHECK(intra_encode_launches(0, 1, 3) == 0 && intra_encode_launches(1, 1, 2) == 0);
     // the inverse-scan blob
     uint32_t first = 0;
-    for (int t = 0; t < RF_TX_SIZES; t++) {
-        CHECK(ie_iscan_first(t) == first && ie_ncoeff(t) == (uint32_t)rf_min(kRfTxW[t], 32) * rf_min(kRfTxH[t], 32));
+    for (int t = 0; t < SVT_TX_SIZES_ALL; t++) {
+        CHECK(ie_iscan_first(t) == first && ie_ncoeff(t) == (uint32_t)geom_min(kTxW[t], 32) * geom_min(kTxH[t], 32));
         first += 16 * ie_ncoeff(t);
     }
     CHECK(IE_TABLE_BYTES == (size_t)first * 2 && ie_ncoeff(4) == 1024 && ie_ncoeff(17) == 512 && ie_ncoeff(0) == 16);
@@ -166,7 +166,7 @@ static void shape_kinds(const PartGeomTab& G, int sq, int shape, bool chroma, st
     for (int i = sq; i < G.nblk && G.blk[i].sqi_mds == sq; i++) {
         const svt_hip_blk_geom& b = G.blk[i];
         if (b.shape != shape || (chroma && !b.has_uv)) continue;
-        out.push_back((uint8_t)ie_kind_of(chroma ? rf_txsize_uv(b.bsize) : rf_txsize(b.bsize)));
+        out.push_back((uint8_t)tx_launch_kind(chroma ? bsize_tx_uv(b.bsize) : bsize_tx(b.bsize)));
     }
 }
 static int test_schedule() {
@@ -178,7 +178,7 @@ static int test_schedule() {
         if (G.sq[s].depth == 1) quad[nq++ < 4 ? nq - 1 : 3] = G.sq[s].mds;
     CHECK(nq == 4 && G.sq[0].mds == 0 && G.sq[0].depth == 0);
     for (int i = 0; i < G.nblk; i++)
-        if (G.blk[i].depth >= 2) CHECK(ie_kind_of(rf_txsize(G.blk[i].bsize)) == 0 && ie_kind_of(rf_txsize_uv(G.blk[i].bsize)) == 0);
+        if (G.blk[i].depth >= 2) CHECK(tx_launch_kind(bsize_tx(G.blk[i].bsize)) == 0 && tx_launch_kind(bsize_tx_uv(G.blk[i].bsize)) == 0);
     size_t trees = 0;
     for (int chroma = 0; chroma < 2; chroma++) {
         const uint8_t* sched = chroma ? kIeChromaSchedule : kIeLumaSchedule;
@@ -228,14 +228,14 @@ static int answer_availability() {
         while (n < 18 && sscanf(line + at, "%d%n", &v[n], &used) == 1) { at += used; n++; }
         if (kind == 't' && n == 12) {
             const int tx = v[7];
-            if (tx < 0 || tx >= RF_TX_SIZES || !svtavail::args_ok(v[0], v[1], v[6])) { printf("-2 -2\n"); continue; }
-            printf("%d %d\n", svtavail::has_top_right(v[0], v[1], v[2], v[3], v[4], v[5], v[6], kRfTxW[tx], v[8], v[9], v[10], v[11]),
-                   svtavail::has_bottom_left(v[0], v[1], v[2], v[3], v[4], v[5], v[6], kRfTxH[tx], v[8], v[9], v[10], v[11]));
+            if (tx < 0 || tx >= SVT_TX_SIZES_ALL || !svtavail::args_ok(v[0], v[1], v[6])) { printf("-2 -2\n"); continue; }
+            printf("%d %d\n", svtavail::has_top_right(v[0], v[1], v[2], v[3], v[4], v[5], v[6], kTxW[tx], v[8], v[9], v[10], v[11]),
+                   svtavail::has_bottom_left(v[0], v[1], v[2], v[3], v[4], v[5], v[6], kTxH[tx], v[8], v[9], v[10], v[11]));
         } else if (kind == 'p' && n == 17) {
             svtavail::Pos q{};
             q.sb_mi = 16; q.is_16bit = v[0]; q.mi_rows = v[1]; q.mi_cols = v[2]; q.tile_mi_row_start = v[3]; q.tile_mi_row_end = v[4]; q.tile_mi_col_start = v[5];
             q.tile_mi_col_end = v[6]; q.partition = v[7]; q.bsize = v[8]; q.plane = v[10]; q.bl_org_x_pict = v[11]; q.bl_org_y_pict = v[12]; q.col_off = v[13];
-            q.row_off = v[14]; q.wpx = v[15]; q.hpx = v[16]; q.txw = kRfTxW[v[9]]; q.txh = kRfTxH[v[9]];
+            q.row_off = v[14]; q.wpx = v[15]; q.hpx = v[16]; q.txw = kTxW[v[9]]; q.txh = kTxH[v[9]];
             svtavail::Px o{};
             const bool ok = svtavail::neighbor_px(q, o);
             printf("%d %d %d %d %d\n", ok ? 1 : 0, o.n_top, o.n_topright, o.n_left, o.n_bottomleft);

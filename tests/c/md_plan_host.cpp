@@ -628,11 +628,11 @@ int main() {
         for (int t = -1; t <= SVT_TX_TYPES; t++) {
             const int m = w > h ? w : h;
             const bool want = t >= 0 && t < SVT_TX_TYPES && (m == 64 ? t == SVT_DCT_DCT : (m == 32 ? (t == SVT_DCT_DCT || t == SVT_IDTX) : true));
-            CHECK(txfm_allowed(s, t) == want);
+            CHECK(tx_type_ok(s, t) == want);
         }
     }
     CHECK(kTxW[SVT_TX_64X64] == 64 && kTxH[SVT_TX_4X16] == 16 && kTxW[SVT_TX_16X4] == 16 && coeffs_of(SVT_TX_64X64) == 1024 && coeffs_of(SVT_TX_16X64) == 512);
-    CHECK(!txfm_allowed(-1, 0) && !txfm_allowed(SVT_TX_SIZES_ALL, 0));
+    CHECK(!tx_type_ok(-1, 0) && !tx_type_ok(SVT_TX_SIZES_ALL, 0));
     CHECK(align16(0) == 0 && align16(1) == 16 && align16(16) == 16 && align16(17) == 32 && log2_of(1) == 0 && log2_of(1024) == 10);
     // ---- the end of the fast loop: survivors, buffers, blocks per wave ----
     CHECK(fast_n(3, 8) == 3 && fast_n(40, 64) == 40 && fast_n(2, 64) == 2 && fast_n(12, 3) == 3);

@@ -126,7 +126,7 @@ static int test_geometry() {
                 CHECK(T.sq_of[i] == s && g.sqi_mds == q.mds && g.shape == shape && g.nsi == k && g.totns == shape_n[shape] && g.d1i == shape_off[shape] + k);
                 CHECK(g.depth == q.depth && g.sq_size == size && g.is_last_quadrant == q.last_quadrant && g.pad == 0);
                 CHECK(g.origin_x >= q.x && g.origin_y >= q.y && g.origin_x + g.bwidth <= q.x + size && g.origin_y + g.bheight <= q.y + size);
-                CHECK(g.bsize < 22 && g.bsize != 13 && g.bsize != 14 && g.bsize != 15 && part_bsize_of(g.bwidth, g.bheight) == g.bsize);
+                CHECK(g.bsize < 22 && g.bsize != 13 && g.bsize != 14 && g.bsize != 15 && bsize_of(g.bwidth, g.bheight) == g.bsize);
                 for (int y = 0; y < g.bheight; y++)
                     for (int x = 0; x < g.bwidth; x++) cover[g.origin_y + y][g.origin_x + x]++;
             }

@@ -130,14 +130,14 @@ static int test_scratch_and_launch_shapes() {
     CHECK(recon_final_scratch_bytes(RF_MAX_NSB) == 128 + (size_t)RF_MAX_NSB * 1271 * 16 && RF_MAX_NSB == 1u << 20);
     // a list's room: the luma blocks of a size that tile 64x64 and the chroma blocks that tile two 32x32
     uint32_t first = 0;
-    for (int t = 0; t < RF_TX_SIZES; t++) {
-        const uint32_t area = (uint32_t)kRfTxW[t] * kRfTxH[t];
+    for (int t = 0; t < SVT_TX_SIZES_ALL; t++) {
+        const uint32_t area = (uint32_t)kTxW[t] * kTxH[t];
         CHECK(rf_cap(t) == 4096 / area + 2 * (1024 / area) && rf_list_first(t) == first);
         first += rf_cap(t);
-        CHECK(rf_class_of(t) >= 0 && rf_class_of(t) < RF_LAUNCHES && rf_per_wg(t) >= 2 && rf_per_wg(t) <= 64);
+        CHECK(tx_launch_kind(t) >= 0 && tx_launch_kind(t) < RF_LAUNCHES && rf_per_wg(t) >= 2 && rf_per_wg(t) <= 64);
     }
     CHECK(first == RF_ITEMS_PER_SB && rf_cap(0) == 384 && rf_cap(4) == 1);
-    CHECK(rf_class_of(0) == 0 && rf_class_of(2) == 0 && rf_class_of(14) == 0 && rf_class_of(3) == 1 && rf_class_of(16) == 1 && rf_class_of(11) == 2 && rf_class_of(18) == 2 && rf_class_of(4) == 3);
+    CHECK(tx_launch_kind(0) == 0 && tx_launch_kind(2) == 0 && tx_launch_kind(14) == 0 && tx_launch_kind(3) == 1 && tx_launch_kind(16) == 1 && tx_launch_kind(11) == 2 && tx_launch_kind(18) == 2 && tx_launch_kind(4) == 3);
     CHECK(rf_per_wg(0) == 64 && rf_per_wg(2) == 16 && rf_per_wg(3) == 8 && rf_per_wg(12) == 4 && rf_per_wg(4) == 2);
     CHECK(recon_final_bin_grid(1) == 1 && recon_final_bin_grid(4) == 1 && recon_final_bin_grid(5) == 2 && recon_final_bin_grid(510) == 128 && recon_final_bin_grid(RF_MAX_NSB) == RF_MAX_NSB / 4);
     // the reconstruct grids: enough workgroups for every item the lists can hold, capped
@@ -153,23 +153,23 @@ static int test_scratch_and_launch_shapes() {
 
 static int test_tables() {
     // blocksize_to_txsize and av1_get_max_uv_txsize at hand-picked sizes (the test compares all of them with the recorded geometry)
-    CHECK(rf_txsize(0) == 0 && rf_txsize(3) == 1 && rf_txsize(12) == 4 && rf_txsize(10) == 11 && rf_txsize(16) == 13 && rf_txsize(21) == 18);
-    CHECK(rf_txsize_uv(0) == 0 && rf_txsize_uv(3) == 0 && rf_txsize_uv(12) == 3 && rf_txsize_uv(10) == 9 && rf_txsize_uv(16) == 5 && rf_txsize_uv(21) == 16 && rf_txsize_uv(20) == 15);
+    CHECK(bsize_tx(0) == 0 && bsize_tx(3) == 1 && bsize_tx(12) == 4 && bsize_tx(10) == 11 && bsize_tx(16) == 13 && bsize_tx(21) == 18);
+    CHECK(bsize_tx_uv(0) == 0 && bsize_tx_uv(3) == 0 && bsize_tx_uv(12) == 3 && bsize_tx_uv(10) == 9 && bsize_tx_uv(16) == 5 && bsize_tx_uv(21) == 16 && bsize_tx_uv(20) == 15);
     for (int b = 0; b < 22; b++) {
-        CHECK(rf_bsize_ok(b) == !(b >= 13 && b <= 15));
-        if (!rf_bsize_ok(b)) continue;
-        CHECK(rf_txsize(b) >= 0 && rf_txsize_uv(b) >= 0 && kRfTxW[rf_txsize(b)] == kRfBsW[b] && kRfTxH[rf_txsize(b)] == kRfBsH[b]);
+        CHECK(bsize_ok(b) == !(b >= 13 && b <= 15));
+        if (!bsize_ok(b)) continue;
+        CHECK(bsize_tx(b) >= 0 && bsize_tx_uv(b) >= 0 && kTxW[bsize_tx(b)] == kBsizeW[b] && kTxH[bsize_tx(b)] == kBsizeH[b]);
     }
-    CHECK(!rf_bsize_ok(-1) && !rf_bsize_ok(22));
-    CHECK(rf_type_ok(4, 0) && !rf_type_ok(4, 9) && !rf_type_ok(18, 1) && rf_type_ok(3, 9) && rf_type_ok(3, 0) && !rf_type_ok(3, 1) && !rf_type_ok(16, 10));
-    CHECK(rf_type_ok(2, 15) && !rf_type_ok(2, 16) && !rf_type_ok(0, -1));
+    CHECK(!bsize_ok(-1) && !bsize_ok(22));
+    CHECK(tx_type_ok(4, 0) && !tx_type_ok(4, 9) && !tx_type_ok(18, 1) && tx_type_ok(3, 9) && tx_type_ok(3, 0) && !tx_type_ok(3, 1) && !tx_type_ok(16, 10));
+    CHECK(tx_type_ok(2, 15) && !tx_type_ok(2, 16) && !tx_type_ok(0, -1));
     return 0;
 }
 
 int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "tables")) {
         for (int b = 0; b < 22; b++)
-            if (rf_bsize_ok(b)) printf("%d %d %d %d %d\n", b, rf_txsize(b), rf_txsize_uv(b), rf_uv_w(b), rf_uv_h(b));
+            if (bsize_ok(b)) printf("%d %d %d %d %d\n", b, bsize_tx(b), bsize_tx_uv(b), bsize_uv_w(b), bsize_uv_h(b));
         return 0;
     }
     if (test_check() || test_scratch_and_launch_shapes() || test_tables()) return 1;

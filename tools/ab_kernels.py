@@ -5,7 +5,9 @@ usage: ab_kernels.py [--out=FILE.json] <workload> [<workload> ...]      workload
        (every allowed type), c4 (one 1080p frame, five sizes, svt_hip_encode_recon_frame), ois8 ois16 (open-loop intra search of a 1080p
        picture), bip, me85 me209, fpick ifpick (svt_hip_fast_pick_frame with gather on 61 candidates, svt_hip_inter_fast_pick_frame on 48 inter
        candidates: the 8x8 blocks of a 1080p picture, nfl 12), ipred isse (svt_hip_inter_pred_frame, prediction stored and SSD, and
-       svt_hip_interp_sse_frame with use_uv 1: the 16x16 luma blocks of a 1080p picture, fractional vectors, single reference and BI_PRED mixed)
+       svt_hip_interp_sse_frame with use_uv 1: the 16x16 luma blocks of a 1080p picture, fractional vectors, single reference and BI_PRED mixed,
+       part rfinal ienc dlfmi (the writer and the three readers of the final block list on the inputs of tools/bench_partition.py,
+       bench_recon_final.py `mixed`, bench_intra_encode.py `mixed` with npics 1 in a HIP graph, and bench_dlf.py's mixed list)
 Prints per workload the minimum and median of 6 interleaved rounds per library, the spread of a's own rounds (minimum to median) and
 whether b's median lies within it of a's, and whether the two libraries' outputs are equal; --out also writes the rows to a file."""
 import json
@@ -242,6 +244,101 @@ def workload(name, d):
             assert call() == 0, d.lib.svt_hip_last_error()
         weighted = lambda t: (t.reshape(-1).to(torch.int64) * (torch.arange(t.numel(), device=dev) % 65521 + 1)).sum()
         return run, n, bpu, (lambda: [weighted(outs[k]) for k in sorted(outs)]), 2000
+    if name in ("part", "rfinal", "ienc", "dlfmi"):      # the writer and the three readers of the final block list, on the benchmarks' own inputs
+        for sub in ("tools", os.path.join("tests", "golden")):
+            sys.path.insert(0, os.path.join(ROOT, sub))
+        import bench_partition as bp
+        import make_golden_partition as mgp
+        D = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        Z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)      # (zeros: the digest also reads what a call leaves alone)
+        ok = lambda rc: rc == 0 or sys.exit(d.lib.svt_hip_last_error())
+        weighted = lambda t: (t.reshape(-1).to(torch.int64) * (torch.arange(t.numel(), device=dev) % 65521 + 1)).sum()
+        pgeom = mgp.load_geometry(dict(np.load(os.path.join(ROOT, "tests", "golden", "partition.npz"))))
+        origins = [(64 * x, 64 * y) for y in range((bp.PIC_H + 63) // 64) for x in range((bp.PIC_W + 63) // 64)]
+        nsb = len(origins)
+
+        def partition_args(c, rec, **more):      # bench_partition.py's arguments for a picture_case and its decision records
+            a = dict(sb=D(c["sb"].view(np.uint8).reshape(nsb, 12)), leaf=D(c["leaf"].view(np.uint8).reshape(-1, 12)), decision=D(rec.view(np.uint8).reshape(-1, 72)),
+                     partition_bits=D(c["bits"]), pic_width=bp.PIC_W, pic_height=bp.PIC_H, slice_is_intra=0, sq=Z((nsb, mgp.NSQ, 16), torch.uint8),
+                     final_count=Z((nsb,), torch.int32), final=Z((nsb, mgp.MAX_FINAL, 12), torch.uint8), **more)
+            a["lambda"] = bp.LAMBDA
+            return a
+        if name == "part":               # bench_partition.py: the squares with the H and V shapes of a 1080p picture, with d_final_decision
+            c = bp.picture_case(np.random.default_rng(19019), pgeom, bp.CLASSES[1][1], origins)
+            rec = np.zeros(len(c["leaf"]), pkg.md_decision_dtype())
+            rec["cost"], rec["cand"] = c["cost"], np.arange(len(rec)) % 64
+            pa = partition_args(c, rec, final_decision=Z((nsb, mgp.MAX_FINAL, 72), torch.uint8))
+            args = d.make_partition_args(pa)
+            return (lambda keep=pa: ok(d.partition_decide_frame(args))), nsb, 0, (lambda: [weighted(pa[k]) for k in ("sq", "final_count", "final", "final_decision")]), 200
+        if name == "rfinal":             # bench_recon_final.py's `mixed` partition, three planes, no optional output
+            import bench_recon_final as br
+            import make_golden_recon_final as mr
+            rng = np.random.default_rng(20020)
+            tabs = mr.bsize_tables(mr.load_geometry(dict(np.load(os.path.join(ROOT, "tests", "golden", "recon_final.npz")))))
+            c = bp.picture_case(rng, pgeom, bp.CLASSES[1][1], origins)
+            bsize = pgeom["bsize"][c["leaf"]["mds_idx"]].astype(np.int64)
+            order = np.argsort(bsize, kind="stable")
+            c["leaf"]["src"][order] = np.arange(len(order))
+            cost = np.zeros_like(c["cost"]); cost[c["leaf"]["src"]] = c["cost"]
+            rec, groups = br.records_and_groups(rng, pkg, bsize[order], tabs, D)
+            rec["cost"] = cost
+            pa = partition_args(c, rec)
+            ok(d.partition_decide_frame(pa))
+            planes = [Z((br.ROWS >> (p > 0), br.PIC_W >> (p > 0)), torch.uint8) for p in range(3)]
+            ra = dict(final=pa["final"], final_count=pa["final_count"], decision=pa["decision"], groups=groups, recon=planes,
+                      scratch=torch.empty((d.recon_final_scratch_bytes(nsb),), dtype=torch.uint8, device=dev),
+                      width=[br.PIC_W, br.PIC_W // 2, br.PIC_W // 2], height=[br.ROWS, br.ROWS // 2, br.ROWS // 2])
+            args = d.make_recon_final_args(ra)
+            return (lambda keep=(pa, ra): ok(d.recon_final_frame(args))), nsb, 0, (lambda: [weighted(p) for p in planes]), 50
+        if name == "ienc":               # bench_intra_encode.py's picture and `mixed` list, npics 1, the call in a HIP graph as there
+            import bench_intra_encode as bi
+            import make_golden_intra_encode as mi
+            import make_golden_recon_final as mr
+            rng = np.random.default_rng(21021)
+            geom = mr.load_geometry(dict(np.load(os.path.join(ROOT, "tests", "golden", "recon_final.npz"))))
+            gold = dict(np.load(os.path.join(ROOT, "tests", "golden", "intra_encode.npz")))
+            qrows = [{k: gold["c0_qrows"][i][j] for j, k in enumerate(mi.QKEYS)} for i in (0, 1)]
+            W, H = bi.PIC_W, bi.PIC_H
+            sb_cols, sb_rows = W // 64, H // 64
+            n = sb_cols * sb_rows
+            final, count, blk, _ = bi.build_list(rng, geom, bi.LISTS["mixed"], sb_cols, sb_rows)
+            ia = dict(npics=1, sb_cols=sb_cols, sb_rows=sb_rows, final=D(final.view(np.uint8).reshape(n, mi.MAX_FINAL, 12)), final_count=D(count.view(np.int32)),
+                      blk=D(blk.view(np.uint8).reshape(-1, 8)), src=[D(mi.smooth_noise(rng, H >> (p > 0), W >> (p > 0), 2)) for p in range(3)],
+                      recon=[torch.full((H >> (p > 0), W >> (p > 0)), 128, dtype=torch.uint8, device=dev) for p in range(3)],
+                      q_luma=qrows[0], q_chroma=qrows[1], tables=D(d.intra_encode_tables()), status=Z((1, n, mi.MAX_FINAL), torch.uint8),
+                      result=Z((n, mi.MAX_FINAL, 8), torch.uint8), coeff_offset=Z((n, mi.MAX_FINAL, 2), torch.int32),
+                      scratch=torch.empty((d.intra_encode_scratch_bytes(1, n),), dtype=torch.uint8, device=dev),
+                      width=[W, W // 2, W // 2], height=[H, H // 2, H // 2])
+            args = d.make_intra_encode_args(ia)
+            call = lambda: ok(d.intra_encode_frame(args))
+            call(); torch.cuda.synchronize()                                    # warm: nothing is created inside the capture
+            graph = torch.cuda.CUDAGraph()
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                with torch.cuda.graph(graph, stream=side):
+                    call()
+            torch.cuda.current_stream().wait_stream(side)
+            # (the planes are coded in place: each replay predicts from the last one's samples, the same work; both libraries are
+            # digested after the same number of runs)
+            return (lambda keep=(ia, args): graph.replay()), n, 0, (lambda: [weighted(t) for t in ia["recon"] + [ia["status"], ia["result"], ia["coeff_offset"]]]), 4
+        # dlfmi: svt_hip_dlf_mi_frame on bench_dlf.py's mixed list (the partition of the all_blocks lists) over an all-8x8 grid
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import bench_dlf as bd
+        rng = np.random.default_rng(2222)
+        c = bp.picture_case(np.random.default_rng(19019), pgeom, bp.CLASSES[2][1], origins)
+        nleaves = len(c["leaf"])
+        rec = np.zeros(nleaves, pkg.md_decision_dtype())
+        rec["cost"], rec["cand"] = c["cost"], np.arange(nleaves) % 64
+        pa = partition_args(c, rec)
+        ok(d.partition_decide_frame(pa))
+        info = np.zeros((nleaves, 4), np.uint8)
+        inter = rng.random(nleaves) < 0.5
+        info[:, 0] = np.where(inter, rng.integers(1, 8, nleaves), 0)
+        info[:, 1] = np.where(inter, rng.integers(13, 25, nleaves), rng.integers(0, 13, nleaves))
+        info[:, 2] = rng.random(nleaves) < 0.33
+        d_info, grid = D(info), D(bd.uniform_grid(3))
+        return (lambda keep=pa: d.dlf_mi_frame(pa["final"], pa["final_count"], d_info, grid)), nsb, 0, (lambda: [weighted(grid)]), 200
     if name in ("me85", "me209"):
         n = 2040
         src = torch.randint(0, 256, (n, 64, 64), dtype=torch.uint8, device=dev, generator=g); ref = torch.randint(0, 256, (n, 127, 128), dtype=torch.uint8, device=dev, generator=g)
