@@ -116,6 +116,16 @@ def tensor(shape, dtype, device):
     return _active.empty(tuple(shape) if isinstance(shape, (tuple, list)) else (shape,), dtype=dtype, device=device)
 
 
+def assert_guards(t, fill, what=""):
+    """For a tensor from tensor() / a poisoned empty() that outlives the block it was allocated in (whose records the block
+    drops when it ends): the GUARD bytes before and after it still hold the fill byte it was allocated with."""
+    import torch
+    raw = torch.empty(0, dtype=torch.uint8, device=t.device).set_(t.untyped_storage())
+    at, n = t.storage_offset() * t.element_size(), t.numel() * t.element_size()
+    assert at == GUARD and raw.numel() >= GUARD + n + GUARD, f"{what}: not a guarded allocation"
+    assert bool((raw[:GUARD] == fill).all()) and bool((raw[GUARD + n:GUARD + n + GUARD] == fill).all()), f"write outside the output {what}"
+
+
 def fill_value(dtype):
     """what an untouched element of a poisoned tensor of this torch dtype reads as (0x5A5A for int16, ...)"""
     assert _active is not None, "poison.fill_value() outside the poisoned_outputs fixture"
