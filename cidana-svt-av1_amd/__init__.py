@@ -171,6 +171,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_motion_estimate_frame_scratch_bytes.restype = c_size_t
     L.svt_hip_motion_estimate_frame.argtypes = [c_void_p] * 4 + [c_uint32] + [c_void_p] * 6 + [c_size_t, c_void_p]
     L.svt_hip_motion_estimate_frame.restype = c_int
+    L.svt_hip_me_subpel_check.argtypes = [c_void_p] * 5 + [c_uint32] + [c_void_p] * 4
+    L.svt_hip_me_subpel_check.restype = c_int
+    L.svt_hip_me_subpel_frame.argtypes = [c_void_p] * 5 + [c_uint32] + [c_void_p] * 5
+    L.svt_hip_me_subpel_frame.restype = c_int
+    L.svt_hip_motion_estimate_subpel_frame_scratch_bytes.argtypes = [c_void_p, c_uint32]
+    L.svt_hip_motion_estimate_subpel_frame_scratch_bytes.restype = c_size_t
+    L.svt_hip_motion_estimate_subpel_frame.argtypes = [c_void_p] * 5 + [c_uint32] + [c_void_p] * 6 + [c_size_t, c_void_p]
+    L.svt_hip_motion_estimate_subpel_frame.restype = c_int
+    L.svt_hip_me_subpel_planes.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint32, c_uint32, c_void_p, c_void_p]
+    L.svt_hip_me_subpel_planes.restype = c_int
     L.svt_hip_coeff_rate_frame.argtypes = [c_void_p, c_int, c_void_p]
     L.svt_hip_coeff_rate_frame.restype = c_int
     L.svt_hip_coeff_cost_index.argtypes = [c_int, c_void_p, c_void_p]
@@ -308,6 +318,11 @@ class MeFrameParams(ctypes.Structure):
                 p.hme_search_area_in_width_array[lv][i] = int(prm[42 + 4 * lv + i])
                 p.hme_search_area_in_height_array[lv][i] = int(prm[44 + 4 * lv + i])
         return p
+
+
+class MeSubpelParams(ctypes.Structure):
+    """svt_hip_me_subpel_params: the enables of the half- / quarter-pel refinement (the reference sets all of them to 1)"""
+    _fields_ = [(n, c_int32) for n in ("fractional_search64x64", "enable_half_pel32x32", "enable_half_pel16x16", "enable_half_pel8x8", "enable_quarter_pel")]
 
 
 class MePyramid(ctypes.Structure):
@@ -1471,6 +1486,48 @@ class SvtHipDsp:
                                                            self._p(out["area_origin"]), self._p(out["bipred_sad"]), self._p(out["results"]),
                                                            self._p(scratch), scratch.numel(), self._stream()), "svt_hip_motion_estimate_frame")
         out["_scratch"] = scratch
+        return out
+
+    # -- sub-pel motion estimation: the refinement stage alone, and MotionEstimateLcu with use_subpel_flag = 1 -------------
+    MeSubpelParams = MeSubpelParams
+
+    def me_subpel_frame(self, src, ref0, ref1, params, best_sad, best_mv, subpel=None, n_pictures=1, best_ssd=None, half_dir=None):
+        """svt_hip_me_subpel_frame: refines the rows best_sad / best_mv (int32 [s, nl, 209], as motion_estimate_frame writes them) in
+        place to quarter-pel.  subpel: MeSubpelParams (None: everything on).  best_ssd (int32 [s, nl, 209]) / half_dir (uint8 [s, nl, 209]):
+        optional outputs.  The call allocates nothing."""
+        self._check(self.lib.svt_hip_me_subpel_frame(ctypes.addressof(src), ctypes.addressof(ref0), ctypes.addressof(ref1) if ref1 is not None else None,
+                                                     ctypes.addressof(params), ctypes.addressof(subpel) if subpel is not None else None, n_pictures,
+                                                     self._p(best_sad), self._p(best_mv), self._p(best_ssd) if best_ssd is not None else None,
+                                                     self._p(half_dir) if half_dir is not None else None, self._stream()), "svt_hip_me_subpel_frame")
+
+    def motion_estimate_subpel_frame(self, src, ref0, ref1, params, n_pictures=1, subpel=None, out=None, scratch=None):
+        """svt_hip_motion_estimate_subpel_frame: motion_estimate_frame with the half- / quarter-pel refinement and the bi-prediction on
+        fractional vectors; the same dict of device tensors, the vectors in quarter-pel units."""
+        t = self.torch
+        nsb = ((params.picture_width + 63) // 64) * ((params.picture_height + 63) // 64)
+        nl = 1 if params.slice_type == 1 else 2
+        s = max(1, n_pictures) * max(1, nsb)
+        if out is None:
+            out = {"best_sad": t.empty((s, nl, 209), dtype=t.int32, device=self.device), "best_mv": t.empty((s, nl, 209), dtype=t.int32, device=self.device),
+                   "area_origin": t.empty((s, nl, 2), dtype=t.int16, device=self.device), "bipred_sad": t.empty((s, 209), dtype=t.int32, device=self.device),
+                   "results": t.empty((s, 209, ctypes.sizeof(self.MeResult)), dtype=t.uint8, device=self.device)}
+        if scratch is None:
+            need = self.lib.svt_hip_motion_estimate_subpel_frame_scratch_bytes(ctypes.addressof(params), n_pictures)
+            scratch = t.empty(max(256, need), dtype=t.uint8, device=self.device)
+        self._check(self.lib.svt_hip_motion_estimate_subpel_frame(ctypes.addressof(src), ctypes.addressof(ref0), ctypes.addressof(ref1) if ref1 is not None else None,
+                                                                  ctypes.addressof(params), ctypes.addressof(subpel) if subpel is not None else None, n_pictures,
+                                                                  self._p(out["best_sad"]), self._p(out["best_mv"]), self._p(out["area_origin"]),
+                                                                  self._p(out["bipred_sad"]), self._p(out["results"]), self._p(scratch), scratch.numel(),
+                                                                  self._stream()), "svt_hip_motion_estimate_subpel_frame")
+        out["_scratch"] = scratch
+        return out
+
+    def me_subpel_planes(self, ref, picture_width, picture_height, x0, y0, w, h):
+        """svt_hip_me_subpel_planes -> uint8 [3, h, w]: the half-pel samples left of, above and above-left of the integer positions of the
+        w x h window at (x0, y0) of a reference's level 0"""
+        out = self.torch.empty((3, h, w), dtype=self.torch.uint8, device=self.device)
+        self._check(self.lib.svt_hip_me_subpel_planes(ctypes.addressof(ref), picture_width, picture_height, x0, y0, w, h, self._p(out), self._stream()),
+                    "svt_hip_me_subpel_planes")
         return out
 
     # -- GatheringPictureStatistics for a whole picture: one call, two launches --------------------------------------------

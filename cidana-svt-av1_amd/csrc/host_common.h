@@ -67,6 +67,15 @@ namespace svthost {
 // (shared with svt_hip_me_frame.hip)
 uint32_t me_window_pitch(uint32_t win_w);
 const svtdev::MePuMap& me_pu_map();
+// svt_hip_me_subpel.hip: the two launches that svt_hip_motion_estimate_subpel_frame (svt_hip_me_frame.hip) puts behind the full-pel search, for
+// arguments the caller has checked (me_subpel_plan.h): the refinement of the result rows in place, and the bi-prediction on the
+// fractional vectors with the me_results rows
+int me_subpel_enqueue_refine(const svt_hip_me_pyramid* src, const svt_hip_me_pyramid* ref0, const svt_hip_me_pyramid* ref1, const svt_hip_me_frame_params* params,
+                             const svt_hip_me_subpel_params* sp, uint32_t n_pictures, uint32_t* d_best_sad, uint32_t* d_best_mv, uint32_t* d_best_ssd,
+                             uint8_t* d_half_dir, hipStream_t s);
+int me_subpel_enqueue_bipred(const svt_hip_me_pyramid* src, const svt_hip_me_pyramid* ref0, const svt_hip_me_pyramid* ref1, const svt_hip_me_frame_params* params,
+                             uint32_t n_pictures, const uint32_t* d_best_sad, const uint32_t* d_best_mv, uint32_t* d_bipred_sad, svt_hip_me_result* d_results,
+                             hipStream_t s);
 // svt_hip_frame.hip: the one-launch form of svt_hip_encode_recon_frame (its kernel lives in a translation unit of its own)
 int launch_enc_frame_one(const svtdev::FrameDesc* fd, uint32_t total_wgs, int is_16bit, hipStream_t s);
 

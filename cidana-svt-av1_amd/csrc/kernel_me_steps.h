@@ -896,6 +896,37 @@ struct MeResult {                       // == svt_hip_me_result (include/svt_hip
     uint8_t direction[3], total_me_candidate_index;
 };
 
+// The me_results row of RASTER PU p, whose vectors and SADs sit at index n of the result rows (shared by me_bipred_body and the
+// bi-prediction on fractional vectors, kernel_me_subpel.h): {list 0, list 1, bi} ordered as Sort3Elements (:6809) / the two-candidate
+// rule do; bi = the PU's bi-prediction SAD, written to bipred_sad[n] where the PU has one.
+__device__ __forceinline__ void me_result_row(int p, int n, const uint32_t* __restrict__ best_sad0, const uint32_t* __restrict__ best_mv0,
+                                              const uint32_t* __restrict__ best_sad1, const uint32_t* __restrict__ best_mv1, int bipred_all_pus, uint32_t bi,
+                                              uint32_t* __restrict__ bipred_sad, MeResult* __restrict__ results) {
+    const bool two = best_sad1 != nullptr;
+    const uint32_t l0 = best_sad0[n], m0 = best_mv0[n];
+    const uint32_t l1 = two ? best_sad1[n] : 0, m1 = two ? best_mv1[n] : 0;
+    const bool has_bi = two && (bipred_all_pus || p < 21);
+    if (bipred_sad && has_bi) bipred_sad[n] = bi;
+    MeResult r;
+    r.x_mv_l0 = (int16_t)(m0 & 0xffffu); r.y_mv_l0 = (int16_t)(m0 >> 16); r.x_mv_l1 = (int16_t)(m1 & 0xffffu); r.y_mv_l1 = (int16_t)(m1 >> 16);
+    const uint32_t d[3] = {l0, l1, bi};
+    int o0 = 0, o1 = 1, o2 = 2, total = two ? 2 : 1;
+    if (has_bi) {
+        total = 3;
+        if (l0 <= l1 && l0 <= bi) { o0 = 0; o1 = l1 <= bi ? 1 : 2; o2 = l1 <= bi ? 2 : 1; }
+        else if (l1 <= l0 && l1 <= bi) { o0 = 1; o1 = l0 <= bi ? 0 : 2; o2 = l0 <= bi ? 2 : 0; }
+        else if (l0 <= l1) { o0 = 2; o1 = 0; o2 = 1; }
+        else { o0 = 2; o1 = 1; o2 = 0; }
+    } else if (two) {
+        o0 = l0 <= l1 ? 0 : 1; o1 = 1 - o0;
+    }
+    r.distortion[0] = d[o0]; r.direction[0] = (uint8_t)o0;
+    r.distortion[1] = total > 1 ? d[o1] : 0; r.direction[1] = total > 1 ? (uint8_t)o1 : 0;
+    r.distortion[2] = total > 2 ? d[o2] : 0; r.direction[2] = total > 2 ? (uint8_t)o2 : 0;
+    r.total_me_candidate_index = (uint8_t)total;
+    results[p] = r;
+}
+
 // One SB (body shared by me_bipred_kernel and me_frame_bipred_kernel, kernel_me_frame.h): (ox, oy) = the SB's origin, best_* / bipred_sad /
 // results = ITS rows.
 __device__ __forceinline__ void me_bipred_body(
@@ -950,32 +981,8 @@ __device__ __forceinline__ void me_bipred_body(
         }
     }
     __syncthreads();
-    if (tid < npus) {
-        const int p = tid, n = s_map.storage[p];
-        const uint32_t l0 = best_sad0[n], m0 = best_mv0[n];
-        const uint32_t l1 = two ? best_sad1[n] : 0, m1 = two ? best_mv1[n] : 0;
-        const bool has_bi = two && (bipred_all_pus || p < 21);
-        const uint32_t bi = s_bi[n];
-        if (bipred_sad && has_bi) bipred_sad[n] = bi;
-        MeResult r;
-        r.x_mv_l0 = (int16_t)(m0 & 0xffffu); r.y_mv_l0 = (int16_t)(m0 >> 16); r.x_mv_l1 = (int16_t)(m1 & 0xffffu); r.y_mv_l1 = (int16_t)(m1 >> 16);
-        const uint32_t d[3] = {l0, l1, bi};
-        int o0 = 0, o1 = 1, o2 = 2, total = two ? 2 : 1;
-        if (has_bi) {
-            total = 3;
-            if (l0 <= l1 && l0 <= bi) { o0 = 0; o1 = l1 <= bi ? 1 : 2; o2 = l1 <= bi ? 2 : 1; }
-            else if (l1 <= l0 && l1 <= bi) { o0 = 1; o1 = l0 <= bi ? 0 : 2; o2 = l0 <= bi ? 2 : 0; }
-            else if (l0 <= l1) { o0 = 2; o1 = 0; o2 = 1; }
-            else { o0 = 2; o1 = 1; o2 = 0; }
-        } else if (two) {
-            o0 = l0 <= l1 ? 0 : 1; o1 = 1 - o0;
-        }
-        r.distortion[0] = d[o0]; r.direction[0] = (uint8_t)o0;
-        r.distortion[1] = total > 1 ? d[o1] : 0; r.direction[1] = total > 1 ? (uint8_t)o1 : 0;
-        r.distortion[2] = total > 2 ? d[o2] : 0; r.direction[2] = total > 2 ? (uint8_t)o2 : 0;
-        r.total_me_candidate_index = (uint8_t)total;
-        results[p] = r;
-    }
+    if (tid < npus)
+        me_result_row(tid, s_map.storage[tid], best_sad0, best_mv0, best_sad1, best_mv1, bipred_all_pus, s_bi[s_map.storage[tid]], bipred_sad, results);
 }
 
 // ---------------------------------------------------------------------------

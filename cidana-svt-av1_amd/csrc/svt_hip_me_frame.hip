@@ -1,8 +1,10 @@
 // svt_hip_me_frame.hip — svt_hip_motion_estimate_frame: MotionEstimateLcu for every SB of a picture (or of a stack of pictures
 // under one parameter set) in three launches (kernel_me_frame.h): prologue (HME levels, best region, CheckZeroZeroCenter, search
-// area), full-pel search, bi-prediction + me_results rows.
+// area), full-pel search, bi-prediction + me_results rows.  svt_hip_motion_estimate_subpel_frame: the same with use_subpel_flag = 1 -
+// prologue, search, then the two sub-pel launches of svt_hip_me_subpel.hip (refinement, bi-prediction on fractional vectors).
 #include "host_common.h"
 #include "kernel_me_frame.h"
+#include "me_subpel_plan.h"
 
 using namespace svtdev;
 using namespace svthost;
@@ -144,19 +146,25 @@ static int me_pyramid_check(const svt_hip_me_pyramid* p, const char* what, const
     return SVT_HIP_OK;
 }
 
-extern "C" int svt_hip_motion_estimate_frame(const svt_hip_me_pyramid* src, const svt_hip_me_pyramid* ref0, const svt_hip_me_pyramid* ref1,
-                                             const svt_hip_me_frame_params* params, uint32_t n_pictures, uint32_t* d_best_sad, uint32_t* d_best_mv,
-                                             int16_t* d_area_origin, uint32_t* d_bipred_sad, svt_hip_me_result* d_results, void* d_scratch,
-                                             size_t scratch_bytes, void* stream) {
+// Both whole-picture calls: the checks, then the launches.  subpel: use_subpel_flag = 1 - after the search the result rows are refined to
+// quarter-pel and the bi-prediction runs on the fractional vectors (svt_hip_me_subpel.hip); sp = its enables (NULL: all on).
+static int me_frame_enqueue(const svt_hip_me_pyramid* src, const svt_hip_me_pyramid* ref0, const svt_hip_me_pyramid* ref1, const svt_hip_me_frame_params* params,
+                            bool subpel, const svt_hip_me_subpel_params* sp, uint32_t n_pictures, uint32_t* d_best_sad, uint32_t* d_best_mv,
+                            int16_t* d_area_origin, uint32_t* d_bipred_sad, svt_hip_me_result* d_results, void* d_scratch, size_t scratch_bytes, void* stream) {
     if (int rc = require_init()) return rc;
     MeFramePlan pl;
     if (int rc = me_frame_plan(params, pl)) return rc;
     const svt_hip_me_frame_params& P = *params;
+    if (subpel) {
+        if (int rc = me_subpel_frame_check(params)) return rc;
+        if (int rc = me_subpel_params_check(sp)) return rc;
+    }
     if (n_pictures > 65535) return set_err(SVT_HIP_ERR_INVALID, "%u pictures (at most 65535)", n_pictures);
     if (int rc = me_pyramid_check(src, "source", params, pl, n_pictures)) return rc;
     if (int rc = me_pyramid_check(ref0, "list 0", params, pl, n_pictures)) return rc;
     if (pl.nl == 2) { if (int rc = me_pyramid_check(ref1, "list 1", params, pl, n_pictures)) return rc; }
     else if (ref1) return set_err(SVT_HIP_ERR_INVALID, "a P picture takes no list-1 reference");
+    if (subpel) { if (int rc = me_subpel_pictures_check(src, ref0, ref1, params, n_pictures)) return rc; }      // the interpolation's wider padding
     // levels 0 and 1 clip against the reference's padding; one parameter row serves both lists, so their origins must agree
     if (pl.nl == 2)
         for (int lv = 0; lv < 2; lv++)
@@ -224,8 +232,33 @@ extern "C" int svt_hip_motion_estimate_frame(const svt_hip_me_pyramid* src, cons
     else
         hipLaunchKernelGGL(me_frame_search_kernel<false>, grid, dim3(ME_THREADS), pl.search_lds, s, d, pl.max_w, pl.max_h, P.flavour, pl.search_wpitch, pl.pair_off);
     if (int rc = launch_status("me_frame_search")) return rc;
+    if (subpel) {
+        if (int rc = me_subpel_enqueue_refine(src, ref0, ref1, params, sp, n_pictures, d_best_sad, d_best_mv, nullptr, nullptr, s)) return rc;
+        return me_subpel_enqueue_bipred(src, ref0, ref1, params, n_pictures, d_best_sad, d_best_mv, d_bipred_sad, d_results, s);
+    }
     static_assert(sizeof(MeResult) == sizeof(svt_hip_me_result), "layout");
     hipLaunchKernelGGL(me_frame_bipred_kernel, dim3(nsb, 1, n_pictures), dim3(ME_THREADS), 0, s, d, (P.cu8x8_mode == 0 || pl.nsq) ? 1 : 0,
                        P.fractional_search_method == 0 ? 1 : 0, me_pu_map(), d_bipred_sad, reinterpret_cast<MeResult*>(d_results));
     return launch_status("me_frame_bipred");
+}
+
+extern "C" int svt_hip_motion_estimate_frame(const svt_hip_me_pyramid* src, const svt_hip_me_pyramid* ref0, const svt_hip_me_pyramid* ref1,
+                                             const svt_hip_me_frame_params* params, uint32_t n_pictures, uint32_t* d_best_sad, uint32_t* d_best_mv,
+                                             int16_t* d_area_origin, uint32_t* d_bipred_sad, svt_hip_me_result* d_results, void* d_scratch,
+                                             size_t scratch_bytes, void* stream) {
+    return me_frame_enqueue(src, ref0, ref1, params, false, nullptr, n_pictures, d_best_sad, d_best_mv, d_area_origin, d_bipred_sad, d_results, d_scratch,
+                            scratch_bytes, stream);
+}
+
+extern "C" size_t svt_hip_motion_estimate_subpel_frame_scratch_bytes(const svt_hip_me_frame_params* params, uint32_t n_pictures) {
+    if (me_subpel_frame_check(params) != SVT_HIP_OK) return 0;
+    return svt_hip_motion_estimate_frame_scratch_bytes(params, n_pictures);
+}
+
+extern "C" int svt_hip_motion_estimate_subpel_frame(const svt_hip_me_pyramid* src, const svt_hip_me_pyramid* ref0, const svt_hip_me_pyramid* ref1,
+                                                    const svt_hip_me_frame_params* params, const svt_hip_me_subpel_params* subpel, uint32_t n_pictures,
+                                                    uint32_t* d_best_sad, uint32_t* d_best_mv, int16_t* d_area_origin, uint32_t* d_bipred_sad,
+                                                    svt_hip_me_result* d_results, void* d_scratch, size_t scratch_bytes, void* stream) {
+    return me_frame_enqueue(src, ref0, ref1, params, true, subpel, n_pictures, d_best_sad, d_best_mv, d_area_origin, d_bipred_sad, d_results, d_scratch,
+                            scratch_bytes, stream);
 }

@@ -497,7 +497,7 @@ int svt_hip_me_fullpel_search_batch(const uint8_t *d_src, uint32_t src_stride, s
  *     puSearchIndexMap, EbMotionEstimation.h:178-315) and read the SAD / vector rows at the storage index of the same rectangle
  *     (svt_hip_me_pu_storage_index).  d_best_sad1 / d_best_mv1 NULL: P picture, one candidate.  bipred_all_pus = (cu8x8_mode ==
  *     CU_8x8_MODE_0 || pic_depth_mode <= PIC_ALL_C_DEPTH_MODE): otherwise only PUs 0 .. 20 are bi-predicted (:8297).  npus 85 or
- *     209.  me_nsq[] of the reference's rows is not produced (it is written by the sub-pel stage, which is outside this path).
+ *     209.  me_nsq[] of the reference's rows is not produced (the reference forces is_nsq_table_used off, :7633).
  *     Every entry of both outputs is written: all pu_pitch entries of an SB's d_bipred_sad row (may be NULL), 0 where no
  *     bi-prediction is made (P pictures, PUs past 20 without bipred_all_pus, entries past the PU count), and all npus result rows. */
 typedef struct svt_hip_me_setup_params {
@@ -540,7 +540,7 @@ int svt_hip_me_pu_storage_index(int pu_index);
  * full-pel search over that area (85 or 209 PUs) and BiPredictionSearch with the me_results rows.  It derives the SB origins,
  * the plane offsets and the svt_hip_hme_params rows itself and issues three launches (prologue, search, bi-prediction); nothing
  * is allocated, nothing returns to the host, the call only enqueues and can be captured into a HIP graph.  Sub-pel refinement
- * is outside this path (use_subpel_flag = 0), as for the stage calls.
+ * is outside this call (use_subpel_flag = 0), as for the stage calls; svt_hip_motion_estimate_subpel_frame below runs it.
  *
  * Pictures: a pyramid is the padded 8-bit luma picture and its 1/4 and 1/16 decimations (svt_hip_picture_pad / _decimate), level
  * k = 0 full, 1 quarter, 2 sixteenth: d_plane[k] is the START of the padded buffer, the picture's sample (0, 0) sits at
@@ -596,6 +596,60 @@ int svt_hip_motion_estimate_frame(const svt_hip_me_pyramid *src, const svt_hip_m
                                   const svt_hip_me_frame_params *params, uint32_t n_pictures, uint32_t *d_best_sad,
                                   uint32_t *d_best_mv, int16_t *d_area_origin, uint32_t *d_bipred_sad, svt_hip_me_result *d_results,
                                   void *d_scratch, size_t scratch_bytes, void *stream);
+
+/* ---- Sub-pel motion estimation: the half- and quarter-pel refinement of MotionEstimateLcu (use_subpel_flag = 1, which the reference
+ * sets for every picture; EbMotionEstimation.c:8162-8236) and BiPredictionSearch on the refined vectors ----
+ * svt_hip_me_subpel_frame is the refinement stage alone: for every 64x64 SB, list and picture of a stack it refines the full-pel rows
+ * that svt_hip_motion_estimate_frame wrote - InterpolateSearchRegionAVC's three half-pel planes (taps (-2, 18, 18, -2), + 16 >> 5, clipped;
+ * plane j is the vertical filter over the ROUNDED plane b), HalfPelSearch_LCU (eight neighbours in the order L R T B TL TR BR BL, strict
+ * '<'; the direction is the first equality in the order L R T B TL TR BL BR) and QuarterPelSearch_LCU (the eight rounded averages of two
+ * planes per case (y & 2) + ((x & 2) >> 1), masked by the half-pel direction).  All three values of fractional_search_method are
+ * served: SUB_SAD_SEARCH 0 (every other row, doubled), FULL_SAD_SEARCH 1, SSD_SEARCH 2 (the decision is on the SSE, starting from the
+ * full-pel winner's; the SAD row takes the SAD of the position that won).  The reference's quirks are kept: the 64x64 PU's quarter-pel
+ * pass measures a 32x32 block (:4809), so its SAD row usually ends as a 32x32 distortion; the quarter pass addresses its planes by
+ * ((mv + 2) >> 2) - origin on negative vectors too.
+ *   d_best_sad, d_best_mv    uint32 [s][nl][209], in / out (s, nl as above): vectors in quarter-pel units (uint16 y << 16 | uint16 x)
+ *   d_best_ssd (may be NULL) uint32 [s][nl][209], out: p_sb_best_ssd under SSD_SEARCH, 0 otherwise and for PUs not refined
+ *   d_half_dir (may be NULL) uint8 [s][nl][209], out: psubPelDirection (TOP_LEFT 0, TOP 1, TOP_RIGHT 2, RIGHT 3, BOTTOM_RIGHT 4,
+ *                            BOTTOM 5, BOTTOM_LEFT 6, LEFT 7), 0 for PUs whose half-pel pass is off
+ * params: picture_width / _height, slice_type, max_number_of_pus_per_sb, cu8x8_mode (1: the 8x8 PUs are not refined) and
+ * fractional_search_method are read.  The pyramids' level 0 is read only.  One launch.  The search-area origins are not an argument: the
+ * reference uses them only to address its per-area planes, whose samples depend on the picture position alone.  A PU whose vector points outside what the padding
+ * holds (no vector of the search does) keeps its rows.
+ *
+ * svt_hip_motion_estimate_subpel_frame is svt_hip_motion_estimate_frame with use_subpel_flag = 1 and the reference's enables (all on
+ * when `subpel` is NULL): prologue, full-pel search, refinement, bi-prediction on the fractional vectors (BiPredictionCompensation /
+ * SelectBuffer / QuarterPelCompensation: a half or integer position reads one plane, a quarter position the rounded average of two) and
+ * the me_results rows - four launches, the same outputs in the same layouts, the vectors in quarter-pel units as the reference stores
+ * them.  Its scratch is svt_hip_motion_estimate_subpel_frame_scratch_bytes (= the full-pel call's).
+ *
+ * Padding: the interpolation reads further than the search.  A search area's origin is clipped to 63 samples left of / above the picture
+ * and its last point to the picture's last sample; a PU's planes need 2 samples before its block and, the quarter pass starting up to one
+ * sample further, 3 after it: samples -65 .. width + 65 (rows likewise).  Level 0 of every pyramid needs origin_x, origin_y >= 66,
+ * stride >= origin_x + width + 66 and as many rows below the picture; the encoder's 68 pass.  (The reference interpolates the whole
+ * ROUND_UP_MUL_8(width + 2)-wide region and reads up to 72 samples right of the picture; those samples are never used.)
+ * Both calls only enqueue, allocate nothing, do not synchronise and can be captured into a HIP graph; every argument is checked before
+ * the first launch (SVT_HIP_ERR_INVALID), svt_hip_me_subpel_check runs those checks alone (no device needed; d_* may be any non-NULL
+ * addresses).  svt_hip_me_subpel_planes writes B / H / J (the samples left of, above and above-left of each integer position) of the
+ * w x h window at (x0, y0) of a reference's level 0 into d_planes [3][h][w]: the interpolation by itself, for pinning. */
+typedef struct svt_hip_me_subpel_params {
+    int32_t fractional_search64x64;                   /* the 64x64 PU is refined (half and quarter) */
+    int32_t enable_half_pel32x32, enable_half_pel16x16, enable_half_pel8x8;
+    int32_t enable_quarter_pel;                       /* the 32x32, 16x16 and 8x8 PUs; the non-square PUs of a 209-PU search always run both */
+} svt_hip_me_subpel_params;
+int svt_hip_me_subpel_check(const svt_hip_me_pyramid *src, const svt_hip_me_pyramid *ref0, const svt_hip_me_pyramid *ref1,
+                            const svt_hip_me_frame_params *params, const svt_hip_me_subpel_params *subpel, uint32_t n_pictures,
+                            const uint32_t *d_best_sad, const uint32_t *d_best_mv, const uint32_t *d_best_ssd, const uint8_t *d_half_dir);
+int svt_hip_me_subpel_frame(const svt_hip_me_pyramid *src, const svt_hip_me_pyramid *ref0, const svt_hip_me_pyramid *ref1,
+                            const svt_hip_me_frame_params *params, const svt_hip_me_subpel_params *subpel, uint32_t n_pictures,
+                            uint32_t *d_best_sad, uint32_t *d_best_mv, uint32_t *d_best_ssd, uint8_t *d_half_dir, void *stream);
+size_t svt_hip_motion_estimate_subpel_frame_scratch_bytes(const svt_hip_me_frame_params *params, uint32_t n_pictures);    /* 0: bad parameters */
+int svt_hip_motion_estimate_subpel_frame(const svt_hip_me_pyramid *src, const svt_hip_me_pyramid *ref0, const svt_hip_me_pyramid *ref1,
+                                         const svt_hip_me_frame_params *params, const svt_hip_me_subpel_params *subpel, uint32_t n_pictures,
+                                         uint32_t *d_best_sad, uint32_t *d_best_mv, int16_t *d_area_origin, uint32_t *d_bipred_sad,
+                                         svt_hip_me_result *d_results, void *d_scratch, size_t scratch_bytes, void *stream);
+int svt_hip_me_subpel_planes(const svt_hip_me_pyramid *ref, int32_t picture_width, int32_t picture_height, int32_t x0, int32_t y0,
+                             uint32_t w, uint32_t h, uint8_t *d_planes, void *stream);
 
 /* K7 coefficient-domain distortion (full_distortion_kernel32_bits_func_ptr_array /
  * full_distortion_kernel_cbf_zero32_bits_func_ptr_array, EbPictureOperators.h:268-280;

@@ -50,9 +50,10 @@ def synthetic_clip(path, w, h, nf, seed=3, pan=(3, 1), bd=8):
 
 
 class Pipeline:
-    def __init__(self, dsp, path, qindex=100, use_graph=False, me_frame=False, picture_stats=False):
+    def __init__(self, dsp, path, qindex=100, use_graph=False, me_frame=False, picture_stats=False, subpel=False):
         self.dsp = dsp
         self.me_frame = me_frame
+        self.subpel = subpel                              # the one call with use_subpel_flag = 1: svt_hip_motion_estimate_subpel_frame
         self.picture_stats, self.stats_out = picture_stats, None
         self.use_graph, self.graph, self.graph_out, self.count = use_graph, None, None, 0
         self.pi = frames.PictureInput(dsp, pkg, path, origin=(68, 68))
@@ -138,9 +139,10 @@ class Pipeline:
         if self.prev is not None and self.me_frame:
             # HME 0 / 1 / 2, ME set-up and the search in one call; the bi-prediction launch writes a P picture's me_results rows
             pads = [(self.pad >> k, self.pad >> k) for k in range(3)]
-            o = dsp.motion_estimate_frame(dsp.me_pyramid([y, pi.quarter, pi.sixteenth], pads),
-                                          dsp.me_pyramid([self.prev["pyr"][2], self.prev["pyr"][1], self.prev["pyr"][0]], pads), None,
-                                          self.me_frame_params, out=self.me_frame_out, scratch=self.me_frame_out and self.me_frame_out["_scratch"])
+            call = dsp.motion_estimate_subpel_frame if self.subpel else dsp.motion_estimate_frame
+            o = call(dsp.me_pyramid([y, pi.quarter, pi.sixteenth], pads),
+                     dsp.me_pyramid([self.prev["pyr"][2], self.prev["pyr"][1], self.prev["pyr"][0]], pads), None,
+                     self.me_frame_params, out=self.me_frame_out, scratch=self.me_frame_out and self.me_frame_out["_scratch"])
             self.me_frame_out = o
             out["me_area_origin"], out["me_sad"], out["me_mv"] = o["area_origin"][:, 0], o["best_sad"][:, 0], o["best_mv"][:, 0]
             out["_cur_luma"] = y
@@ -230,6 +232,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="capture the per-picture analysis into a HIP graph and replay it")
     ap.add_argument("--me-frame", action="store_true", help="HME, ME set-up and the search through svt_hip_motion_estimate_frame (one call, "
                     "three launches); a stage-call pass runs first and the digests both paths share must be equal")
+    ap.add_argument("--subpel", action="store_true", help="motion estimation through svt_hip_motion_estimate_subpel_frame in both passes (one call, four "
+                    "launches: the search, the half- / quarter-pel refinement, bi-prediction on fractional vectors); the vectors are in quarter-pel units")
     ap.add_argument("--picture-stats", action="store_true", help="GatheringPictureStatistics between the input and HME "
                     "(svt_hip_picture_stats_frame: one call, two launches); 8-bit clips")
     a = ap.parse_args()
@@ -243,7 +247,7 @@ def main():
         synthetic_clip(path, w, h, a.frames, bd=a.bd)
     results = []
     for rep in range(2):                                  # the second pass is timed (page cache, allocator, first-launch costs settled)
-        p = Pipeline(dsp, path, use_graph=a.graph, me_frame=a.me_frame and rep == 1, picture_stats=a.picture_stats)
+        p = Pipeline(dsp, path, use_graph=a.graph, me_frame=a.subpel or (a.me_frame and rep == 1), picture_stats=a.picture_stats, subpel=a.subpel)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         n, last = 0, None
@@ -258,7 +262,7 @@ def main():
         del p.graph
         p.pi.close()
     n, dt, dg = results[-1]
-    if a.me_frame:                                        # pass 0 took the stage calls, pass 1 the one call: what both produce must be equal
+    if a.me_frame and not a.subpel:                       # pass 0 took the stage calls, pass 1 the one call: what both produce must be equal
         shared = sorted(set(results[0][2]) & set(dg))
         assert {"me_sad_sum", "me_mv_sum", "ois_best_sum", "enc_digest"} <= set(shared), shared
         assert all(results[0][2][k] == dg[k] for k in shared), "the stage calls and svt_hip_motion_estimate_frame disagree"
@@ -266,7 +270,7 @@ def main():
     else:
         assert results[0][2] == dg, "the two passes disagree"
     print(json.dumps({"file": os.path.basename(path), "picture": f"{p.W}x{p.H}", "frames": n, "seconds": round(dt, 4), "frames_per_s": round(n / dt, 1),
-                      "ms_per_frame": round(1e3 * dt / n, 3), "hip_graph": bool(a.graph), **({"me_frame": True} if a.me_frame else {}), "stages": "input + decimation, OIS (4 sizes), HME 0/1/2, ME set-up + 209 PUs per-SB areas, encode pass (5 sizes, YUV)",
+                      "ms_per_frame": round(1e3 * dt / n, 3), "hip_graph": bool(a.graph), **({"me_frame": True} if a.me_frame else {}), **({"subpel": True} if a.subpel else {}), "stages": "input + decimation, OIS (4 sizes), HME 0/1/2, ME set-up + 209 PUs per-SB areas, encode pass (5 sizes, YUV)",
                       "last_frame_digest": dg, "device": dsp.device_name()}), flush=True)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     json.dump({"picture": f"{p.W}x{p.H}", "bd": a.bd, "frames": n, "seconds": dt, "frames_per_s": n / dt, "ms_per_frame": 1e3 * dt / n, "hip_graph": bool(a.graph),
