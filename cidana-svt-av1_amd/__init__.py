@@ -2523,7 +2523,8 @@ class SvtHipDsp:
 
     def make_cdef_pic(self, rec, skip, width, height, bit_depth, base_qindex, src=None, dst=None):
         """rec / src / dst: (Y, Cb, Cr) tensors, uint8 (bit depth 8) or uint16 / int16 (10), [rows, stride] for one picture or
-        [npics, rows, stride] for a stack; skip: uint8 [height / 8 (or more), stride] (or [npics, ..]).  -> CdefPic (keep the tensors
+        [npics, rows, stride] for a stack, or views of such with rows (and pictures) further apart (the strides are
+        the tensors' own); skip: uint8 [height / 8 (or more), stride] (or [npics, ..]).  -> CdefPic (keep the tensors
         alive!)"""
         p = self.CdefPic()
         stack = rec[0].dim() == 3
@@ -2533,10 +2534,10 @@ class SvtHipDsp:
             if planes is None:
                 continue
             for i, t in enumerate(planes):
-                assert t.is_contiguous() and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
-                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.shape[-1], (t.shape[-2] * t.shape[-1] if stack else 0)
-        assert skip.is_contiguous() and skip.element_size() == 1
-        p.d_skip, p.skip_stride, p.skip_pitch = skip.data_ptr(), skip.shape[-1], (skip.shape[-2] * skip.shape[-1] if stack else 0)
+                assert t.stride(-1) == 1 and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
+                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.stride(-2), (t.stride(0) if stack else 0)
+        assert skip.stride(-1) == 1 and skip.element_size() == 1
+        p.d_skip, p.skip_stride, p.skip_pitch = skip.data_ptr(), skip.stride(-2), (skip.stride(0) if stack else 0)
         p.width, p.height, p.bit_depth, p.base_qindex = width, height, bit_depth, base_qindex
         return p
 
@@ -2591,7 +2592,8 @@ class SvtHipDsp:
     @staticmethod
     def make_dlf_pic(rec, mi, width, height, bit_depth, levels=(0, 0, 0, 0), sharpness=0, ref_deltas=None, mode_deltas=None, src=None, dst=None):
         """rec / src / dst: (Y, Cb, Cr) tensors, uint8 (bit depth 8) or uint16 / int16 (10), [rows, stride] for one picture or
-        [npics, rows, stride] for a stack; mi: uint8 [(npics,) rows, mi_stride, 4] (svt_hip_dlf_mi records); levels: filter_level[0],
+        [npics, rows, stride] for a stack, or views of such with rows (and pictures) further apart (the strides are
+        the tensors' own); mi: uint8 [(npics,) rows, mi_stride, 4] (svt_hip_dlf_mi records); levels: filter_level[0],
         filter_level[1], filter_level_u, filter_level_v; ref_deltas (8) / mode_deltas (2): given = mode_ref_delta_enabled.
         -> DlfPic (keep the tensors alive!)"""
         p = SvtHipDsp.DlfPic()
@@ -2602,10 +2604,10 @@ class SvtHipDsp:
             if planes is None:
                 continue
             for i, t in enumerate(planes):
-                assert t.is_contiguous() and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
-                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.shape[-1], (t.shape[-2] * t.shape[-1] if stack else 0)
-        assert mi.is_contiguous() and mi.element_size() == 1 and mi.shape[-1] == 4 and mi.dim() == (4 if stack else 3)
-        p.d_mi, p.mi_stride, p.mi_pitch = mi.data_ptr(), mi.shape[-2], (mi.shape[-3] * mi.shape[-2] if stack else 0)
+                assert t.stride(-1) == 1 and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
+                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.stride(-2), (t.stride(0) if stack else 0)
+        assert mi.stride(-1) == 1 and mi.stride(-2) == 4 and mi.element_size() == 1 and mi.shape[-1] == 4 and mi.dim() == (4 if stack else 3)
+        p.d_mi, p.mi_stride, p.mi_pitch = mi.data_ptr(), mi.stride(-3) // 4, (mi.stride(0) // 4 if stack else 0)
         p.width, p.height, p.bit_depth = width, height, bit_depth
         p.filter_level[0], p.filter_level[1], p.filter_level_u, p.filter_level_v = (int(v) for v in levels)
         p.sharpness_level = int(sharpness)

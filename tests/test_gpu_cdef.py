@@ -18,6 +18,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 import make_golden_cdef as mg      # noqa: E402  (the fixture's glue: case list, filter-block loop over the live reference)
 
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import layouts                     # noqa: E402
+import poison                      # noqa: E402
+
 GOLD = os.path.join(ROOT, "tests", "golden", "cdef.npz")
 CASES = [c[0] for c in mg.CASES]
 ERR_INVALID = -2
@@ -109,6 +113,45 @@ def test_stack_under_a_captured_graph_replayed_twice(dsp, gold):
         torch.cuda.synchronize()
         assert np.array_equal(mse.cpu().numpy(), want)
         assert np.array_equal(count.cpu().numpy(), np.stack([gold["b_count"], gold["c_count"]]))
+
+
+@pytest.mark.parametrize("names", [("b", "c"), ("e",)], ids=["stack_b_c", "e_10bit"])
+@pytest.mark.parametrize("fill", poison.FILLS, ids=lambda f: f"fill{f:02X}")
+def test_search_and_apply_with_every_operand_laid_out_differently_equal_the_reference(dsp, gold, names, fill):
+    """rec / src / skip (search) and rec / dst / skip (apply): a stride per plane and role that no other plane of the call has, the chroma
+    strides unrelated to luma's; cases b and c as a stack of two with a pitch per plane and role, case e (10-bit) alone.  Outputs are
+    poisoned (both fill bytes: 8-bit samples), guards checked on every operand.  tests/layouts.py asserts the layouts distinct and a
+    mix-up of them harmless before anything is uploaded."""
+    n = len(names)
+    bd, w, h, q = (int(v) for v in gold[names[0] + "_meta"])
+    get = (lambda key: np.stack([gold[m + key] for m in names])) if n == 2 else (lambda key: gold[names[0] + key])
+    with poison.poisoned(dsp, fill):
+        spec = layouts.cdef_spec("svt_hip_cdef_search_frame", w, h, ("rec", "src"), n)
+        lay = layouts.distinct_layouts(spec)
+        rec, p_rec = layouts.place_operand(spec, lay, "rec", [get("_rec_" + c) for c in "yuv"], n, fill)
+        src, p_src = layouts.place_operand(spec, lay, "src", [get("_src_" + c) for c in "yuv"], n, fill)
+        skip, p_skip = layouts.place_operand(spec, lay, "skip", [get("_skip")], n, fill)
+        mse, count = dsp.cdef_search_frame(rec, src, skip[0], w, h, bd, q)
+        torch.cuda.synchronize()
+        assert np.array_equal(count.cpu().numpy(), get("_count"))
+        got, want = mse.cpu().numpy(), get("_mse").astype(np.int64)
+        assert np.array_equal(got, want), (names, np.argwhere(got != want)[:5].tolist())
+        layouts.assert_all_intact(p_rec + p_src + p_skip, fill)
+
+        spec = layouts.cdef_spec("svt_hip_cdef_apply_frame", w, h, ("rec", "dst"), n)
+        lay = layouts.distinct_layouts(spec)
+        rec, p_rec = layouts.place_operand(spec, lay, "rec", [get("_rec_" + c) for c in "yuv"], n, fill)
+        dst, p_dst = layouts.place_operand(spec, lay, "dst", [layouts.poison_like(get("_rec_" + c), fill) for c in "yuv"], n, fill)
+        skip, p_skip = layouts.place_operand(spec, lay, "skip", [get("_skip")], n, fill)
+        ys, us = torch.from_numpy(get("_ystr")).cuda(), torch.from_numpy(get("_ustr")).cuda()
+        dsp.cdef_apply_frame(rec, skip[0], ys, us, w, h, bd, q, dst=dst)
+        torch.cuda.synchronize()
+        for i, c in enumerate("yuv"):
+            want = get("_out_" + c)
+            got = dst[i].cpu().numpy().view(want.dtype)
+            assert np.array_equal(got, want), (names, c, np.argwhere(got != want)[:5].tolist())
+        layouts.assert_all_intact(p_rec + p_skip, fill)
+        layouts.assert_all_intact(p_dst, fill, written=True)
 
 
 def test_invalid_arguments_are_refused_before_any_launch(dsp, gold):

@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import dlf_cases as dc      # noqa: E402
+import layouts            # noqa: E402
 import poison               # noqa: E402
 from poison import poisoned_outputs  # noqa: E402,F401
 
@@ -192,6 +193,41 @@ def test_stack_of_two_pictures_captured_into_a_graph(dsp):
         assert torch.equal(dst[i][1], alone[i]), i
     assert torch.equal(sse[1], alone_sse)
     assert not torch.equal(sse[0], sse[1])
+
+
+@pytest.mark.parametrize("name", ["edge_mixed", "hbd_delta"])
+def test_apply_and_search_with_every_operand_laid_out_differently_equal_the_reference(dsp, name, poisoned_outputs):
+    """rec / dst (apply into a second buffer) and rec / src (search): a stride per plane and role that no other plane of the call has, the
+    chroma strides unrelated to luma's, mi_stride above mi_cols; alone, and as a stack of two (the fixture's picture second) with a pitch
+    per plane, role and grid.  tests/layouts.py asserts the layouts distinct and a mix-up of them harmless before anything is uploaded."""
+    c = dc.case(name)
+    w, h, bd, levels, kw = call_args(c)
+    fill = poisoned_outputs.fill_byte
+    for n in (1, 2):
+        pics = (lambda p: np.stack([np.ascontiguousarray(p[::-1, ::-1]), p])) if n == 2 else (lambda p: p)
+        mi_np = np.stack([c["mi"], c["mi"]]) if n == 2 else c["mi"]
+        spec = layouts.dlf_spec("svt_hip_dlf_apply_frame", w, h, ("rec", "dst"), n)
+        lay = layouts.distinct_layouts(spec)
+        assert lay["mi"].stride > w // 4
+        rec, p_rec = layouts.place_operand(spec, lay, "rec", [pics(p) for p in c["rec"]], n, fill)
+        dst, p_dst = layouts.place_operand(spec, lay, "dst", [layouts.poison_like(pics(p), fill) for p in c["rec"]], n, fill)
+        mi, p_mi = layouts.place_operand(spec, lay, "mi", [mi_np], n, fill, record=True)
+        dsp.dlf_apply_frame(rec, mi[0], w, h, bd, levels, dst=dst, **kw)
+        torch.cuda.synchronize()
+        check_planes([d[-1] if n == 2 else d for d in dst], c["out"], w, h, None, ("apply", n))
+        layouts.assert_all_intact(p_rec + p_mi, fill)
+        layouts.assert_all_intact(p_dst, fill, written=True)
+
+        spec = layouts.dlf_spec("svt_hip_dlf_search_frame", w, h, ("rec", "src"), n)
+        lay = layouts.distinct_layouts(spec)
+        rec, p_rec = layouts.place_operand(spec, lay, "rec", [pics(p) for p in c["rec"]], n, fill)
+        src, p_src = layouts.place_operand(spec, lay, "src", [pics(p) for p in c["src"]], n, fill)
+        mi, p_mi = layouts.place_operand(spec, lay, "mi", [mi_np], n, fill, record=True)
+        got = dsp.dlf_search_frame(rec, src, mi[0], w, h, bd, **kw)
+        torch.cuda.synchronize()
+        got = got.cpu().numpy().view(np.uint64).reshape(n, 3, 64)[-1]
+        assert np.array_equal(got, c["sse"].astype(np.uint64)), ("search", n, np.argwhere(got != c["sse"].astype(np.uint64))[:4].tolist())
+        layouts.assert_all_intact(p_rec + p_src + p_mi, fill)
 
 
 def test_deblock_then_cdef_without_a_host_copy(dsp):

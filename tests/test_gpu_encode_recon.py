@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import layouts
 import poison
 import svtlibs
 from poison import poisoned_outputs  # noqa: F401
@@ -143,6 +144,49 @@ def test_encode_recon_on_planes(dsp, tx_size, tx_type, inplace):
     for i, (y, x) in enumerate([(y, x) for y in ys for x in xs]):
         expect[y:y + h, x:x + w] = rrec[i]
     assert np.array_equal(rec, expect)
+
+
+def test_the_frame_call_with_src_pred_and_recon_laid_out_unlike_each_other_equals_the_oracle(dsp):
+    """svt_hip_encode_recon_frame with an 8x8 and a 16x16 group on one 88 x 56 picture: src_stride, pred_stride and recon_stride all odd and
+    all different, the three planes at different places in allocations of different sizes (tests/layouts.py asserts that a mix-up stays
+    inside them).  Every block of both groups against the oracle stages; the reconstruction outside the blocks keeps the poison."""
+    rng = np.random.default_rng(8856)
+    PH, PW = 56, 88
+    src = rng.integers(0, 256, size=(PH, PW), dtype=np.uint8)
+    pred = np.clip(src.astype(int) + rng.integers(-9, 10, size=src.shape), 0, 255).astype(np.uint8)
+    fill = poison._active.fill_byte
+    spec = layouts.CallSpec("svt_hip_encode_recon_frame", [layouts.Plane(n, PW, PH, stacked=False) for n in ("src", "pred", "recon")])
+    lay = layouts.distinct_layouts(spec)
+    (d_src,), p_src = layouts.place_operand(spec, lay, "src", [src], 1, fill)
+    (d_pred,), p_pred = layouts.place_operand(spec, lay, "pred", [pred], 1, fill)
+    (d_recon,), p_recon = layouts.place_operand(spec, lay, "recon", [layouts.poison_like(src, fill)], 1, fill)
+    assert len({d_src.stride(0), d_pred.stride(0), d_recon.stride(0)}) == 3
+    qrow = {k: v[80].copy() for k, v in svtlibs.quant_tables(8).items()}
+    groups, where = [], []
+    for tx_size, tx_type, y0, y1 in ((1, 0, 0, 24), (2, 5, 24, 56)):              # 8x8 blocks in the rows above 24, 16x16 below
+        w, h = TX_W[tx_size], TX_H[tx_size]
+        pos = [(y, x) for y in range(y0, y1 - h + 1, h) for x in range(PW - w, -1, -w)]      # from the last column leftwards
+        xy = np.array([(y << 16) | x for y, x in pos], np.uint32)
+        n = len(pos)
+        groups.append(dict(src=d_src, src_stride=d_src.stride(0), pred=d_pred, pred_stride=d_pred.stride(0), recon=d_recon,
+                           recon_stride=d_recon.stride(0), tx_size=tx_size, tx_type=tx_type, xy=dev(xy.view(np.int32)),
+                           iscan=dev(svtlibs.scan_tables(tx_size, tx_type)[1]), qcoeff=poison.tensor((n, w * h), torch.int32, d_src.device),
+                           eob=poison.tensor((n,), torch.int16, d_src.device)))
+        where.append((tx_size, tx_type, w, h, pos))
+    dsp.encode_recon_frame(dsp.make_frame_groups(groups), qrow)
+    torch.cuda.synchronize()
+    expect = layouts.poison_like(src, fill)
+    for g, (tx_size, tx_type, w, h, pos) in zip(groups, where):
+        sb = np.stack([src[y:y + h, x:x + w] for y, x in pos]); pb = np.stack([pred[y:y + h, x:x + w] for y, x in pos])
+        rco, rq, rdq, reob, rsad = oracle_chain(sb, pb, tx_size, tx_type, qrow)
+        assert np.array_equal(g["qcoeff"].cpu().numpy(), rq), tx_size
+        assert np.array_equal(g["eob"].cpu().numpy().view(np.uint16), reob), tx_size
+        for (y, x), r in zip(pos, oracle_recon(pb, rdq, tx_size, tx_type)):
+            expect[y:y + h, x:x + w] = r
+    got = d_recon.cpu().numpy()
+    assert np.array_equal(got, expect), np.argwhere(got != expect)[:4].tolist()
+    layouts.assert_all_intact(p_src + p_pred, fill)
+    layouts.assert_all_intact(p_recon, fill, written=True)
 
 
 @pytest.mark.parametrize("tx_size,tx_type", [(3, 0), (3, 9), (2, 0), (2, 7), (1, 0), (4, 0), (9, 0), (8, 2), (5, 0), (13, 0), (18, 0)])

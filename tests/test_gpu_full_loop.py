@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+import layouts
+import poison
 import svtlibs
 from svtlibs import TX_H, TX_W, ptr, txfm_allowed
 
@@ -76,6 +78,48 @@ def test_golden_fixture_every_size_and_type(dsp):
                 assert np.array_equal(g["eob"].cpu().numpy(), we), (s, int(q))
                 assert np.array_equal(g["qcoeff"].cpu().numpy(), wq), (s, int(q))
                 assert np.array_equal(g["dqcoeff"].cpu().numpy(), wdq), (s, int(q))
+
+
+@pytest.mark.parametrize("fill", poison.FILLS, ids=lambda f: f"fill{f:02X}")
+def test_the_plane_form_with_source_and_prediction_laid_out_unlike_each_other_equals_the_fixture(dsp, fill):
+    """the fixture's 8x8 and 16x32 blocks painted into one source and one prediction picture, eight to a row: src_stride unlike
+    pred_stride (both odd), the two pictures at different places in allocations of different sizes (tests/layouts.py asserts that a
+    mix-up of the two stays inside them); one group per size, both flavours, against the fixture"""
+    z = np.load(GOLD)
+    sizes = (1, next(i for i in range(19) if (TX_W[i], TX_H[i]) == (16, 32)))
+    blocks = {s: (z[f"s{s}_src"].reshape(-1, TX_H[s], TX_W[s]), z[f"s{s}_pred"].reshape(-1, TX_H[s], TX_W[s])) for s in sizes}
+    PW = 8 * 16
+    bands = [-(-len(blocks[s][0]) // 8) * TX_H[s] for s in sizes]
+    srcp, predp, xy, y0 = np.zeros((sum(bands), PW), np.uint8), np.zeros((sum(bands), PW), np.uint8), {}, 0
+    for s, band in zip(sizes, bands):
+        w, h = TX_W[s], TX_H[s]
+        pos = [((i % 8) * w, y0 + (i // 8) * h) for i in range(len(blocks[s][0]))]
+        for (x, y), sb, pb in zip(pos, *blocks[s]):
+            srcp[y:y + h, x:x + w], predp[y:y + h, x:x + w] = sb, pb
+        xy[s] = np.array([x | (y << 16) for x, y in pos], np.int32)
+        y0 += band
+    spec = layouts.CallSpec("svt_hip_full_loop_frame", [layouts.Plane(n, PW, srcp.shape[0], stacked=False) for n in ("src", "pred")])
+    lay = layouts.distinct_layouts(spec)
+    with poison.poisoned(dsp, fill):
+        (d_src,), p_src = layouts.place_operand(spec, lay, "src", [srcp], 1, fill)
+        (d_pred,), p_pred = layouts.place_operand(spec, lay, "pred", [predp], 1, fill)
+        assert d_src.stride(0) != d_pred.stride(0) and d_src.stride(0) % 2 and d_pred.stride(0) % 2
+        for qi, q in enumerate(z["s0_qindex"]):
+            for flavour, key in ((0, "dist_c"), (1, "dist_avx2")):
+                groups = []
+                for s in sizes:
+                    types = [int(t) for t in z[f"s{s}_types"]]
+                    groups.append(dict(src=d_src, src_stride=d_src.stride(0), src_xy=torch.from_numpy(xy[s]).to(DEV), pred=d_pred,
+                                       pred_stride=d_pred.stride(0), pred_xy=torch.from_numpy(xy[s]).to(DEV), nblocks=len(xy[s]), tx_size=s,
+                                       tx_types=types, iscan=iscans(s, types), **outputs(len(xy[s]), s, len(types))))
+                run(dsp, groups, qrow_of(int(q)), flavour)
+                for g, s in zip(groups, sizes):
+                    T = len(g["tx_types"])
+                    assert np.array_equal(g["dist"].cpu().numpy(), z[f"s{s}_{key}"][:, qi].reshape(T, -1, 2).transpose(1, 0, 2).astype(np.int64)), (s, int(q), key)
+                    assert np.array_equal(g["eob"].cpu().numpy(), z[f"s{s}_eob"][:, qi].reshape(T, -1).T.astype(np.int16)), (s, int(q))
+                    assert np.array_equal(g["qcoeff"].cpu().numpy(), z[f"s{s}_qcoeff"][:, qi].reshape(T, -1, nc_of(s)).transpose(1, 0, 2)), (s, int(q))
+                    assert np.array_equal(g["dqcoeff"].cpu().numpy(), z[f"s{s}_dqcoeff"][:, qi].reshape(T, -1, nc_of(s)).transpose(1, 0, 2)), (s, int(q))
+        layouts.assert_all_intact(p_src + p_pred, fill)
 
 
 def oracle_chain(O, s, t, qrow, src_blk, pred_blk, iscan_np):

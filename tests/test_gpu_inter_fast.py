@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import layouts
 import poison
 from poison import poisoned_outputs  # noqa: F401
 
@@ -167,17 +168,22 @@ def test_pick_groups_large_enough_for_several_blocks_per_wave(dsp):
 
 
 # ---- the one-call search -------------------------------------------------------------------------------------------------------------------
-def search_group(dsp, si, own_dist, intra_pred=True, chroma_pred=True):
-    """(group dict, expected pick outputs, expected distortions | None) of fixture search group si"""
+def search_group(dsp, si, own_dist, intra_pred=True, chroma_pred=True, laid_out=None):
+    """(group dict, expected pick outputs, expected distortions | None) of fixture search group si.  laid_out: (views, {"ref": strides,
+    "src": strides}, placed) of layouts.place_ref_src in place of the shared planes"""
     P, A = case("search", si)
     g, want = pick_group(dsp, "search", si, with_dist=False)
     bd, nb, ni, na = P["bd"], P["nblocks"], P["ninter"], P["nintra"]
     n = min(P["nfl"], ni + na)
-    Pl, strides = planes(dsp, bd)
+    if laid_out is None:
+        Pl, strides = planes(dsp, bd)
+        strides = {"ref": strides, "src": strides}
+    else:
+        Pl, strides = laid_out[:2]
     np_ = 3 if P["chroma"] else 1
     st = torch.uint8 if bd == 8 else torch.int16
     g.update(bwidth=P["bwidth"], bheight=P["bheight"], use_chroma=P["chroma"], bd=bd, ref0=Pl["ref0"][:np_], ref1=Pl["ref1"][:np_],
-             ref_stride=strides[:np_], src=Pl["src"][:np_], src_stride=strides[:np_])
+             ref_stride=strides["ref"][:np_], src=Pl["src"][:np_], src_stride=strides["src"][:np_])
     g["pred_out"] = [poison.tensor((nb, n, P["bheight"] >> (p > 0), P["bwidth"] >> (p > 0)), st, dsp.device) for p in range(np_ if chroma_pred else 1)]
     dists = None
     if own_dist:
@@ -233,6 +239,20 @@ def test_search_each_fixture_group(dsp, si, own_dist):
     check_search(dsp, g, want, dists, (si, own_dist))
     if own_dist:
         assert untouched(scratch)
+
+
+def test_search_with_six_different_strides_equals_the_fixture(dsp):
+    """the first 8-bit fixture group with chroma: ref_stride[3] and src_stride[3] all different and odd, chroma's unrelated to luma's, the
+    nine planes at different places; the distortions of all three planes and every pick output against the fixture, the survivors'
+    predictions against svt_hip_inter_pred_frame on the same planes"""
+    si = next(i for i in range(len(mg.SEARCH_GROUPS)) if case("search", i)[0]["chroma"] and case("search", i)[0]["bd"] == 8)
+    spec = layouts.ref_src_spec("svt_hip_inter_fast_search_frame", W, H, ip.PAD)
+    lp = layouts.place_ref_src(spec, layouts.distinct_layouts(spec), ip.planes_of(8, "random"))
+    g, want, dists = search_group(dsp, si, True, laid_out=lp)
+    rc, _ = dsp.inter_fast_search_frame([g], W, H, g["metric"], scratch=None, bd=g["bd"])
+    ok(dsp, rc)
+    check_search(dsp, g, want, dists, si)
+    layouts.assert_all_intact(lp[2], poison._active.fill_byte)
 
 
 def test_search_all_8_bit_groups_in_one_call_without_intra_pred(dsp):

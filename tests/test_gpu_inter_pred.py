@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import layouts
 import poison
 from poison import poisoned_outputs  # noqa: F401
 
@@ -61,23 +62,53 @@ def origin(plane_t, k):
     return plane_t[pad:, pad:]
 
 
-def group_dict(dsp, gi, want_pred="dense", with_dist=False, dense_out=None):
-    """the fixture's group gi as an inter_pred_frame group with poisoned outputs"""
+def inter_pred_spec(plane):
+    """ref (one stride for both references), src and pred of a group of luma (plane 0) or chroma blocks: pointers to sample (0, 0) of
+    planes with the fixture's border on every side"""
+    w, h, pad = (W, H, mg.PAD[0]) if plane == 0 else (W // 2, H // 2, mg.PAD[1])
+    return layouts.CallSpec("svt_hip_inter_pred_frame", [layouts.Plane(n, w, h, (pad, pad), (pad, pad), stacked=False) for n in ("ref", "src", "pred")])
+
+
+def laid_out_planes(bd, content, plane, spec, lay):
+    """({name: {plane: strided view of the padded plane}}, placed) with ref0 / ref1 at the layout of "ref" and src at its own"""
+    p = mg.planes_of(bd, content)
+    P, placed = {}, []
+    for name in ("ref0", "ref1", "src"):
+        pl = spec.plane("src" if name == "src" else "ref")
+        buf, view = layouts.place_plane(pl, p[name][plane], lay[pl.name])
+        P[name] = {plane: view}
+        placed.append((name, buf, view, p[name][plane]))
+    return P, placed
+
+
+def group_dict(dsp, gi, want_pred="dense", with_dist=False, dense_out=None, laid_out=None):
+    """the fixture's group gi as an inter_pred_frame group with poisoned outputs.  laid_out = (spec, layouts) of tests/layouts.py: the
+    reference, source and prediction planes each at a layout of their own (the group's "placed" lists them for the guard checks)"""
     g = gold()
     bd, content, ss, bw, bh, same, plane = (int(v) for v in g["groups"][gi])
-    P = device_planes(dsp, bd, mg.CONTENTS[content])
+    placed = []
+    if laid_out is None:
+        P = device_planes(dsp, bd, mg.CONTENTS[content])
+    else:
+        P, placed = laid_out_planes(bd, mg.CONTENTS[content], plane, *laid_out)
     blk = g[f"blk_{gi}"]
     n, w, h = len(blk), bw >> ss, bh >> ss
-    d = dict(ref0=origin(P["ref0"][plane], plane), ref1=origin(P["ref0" if same else "ref1"][plane], plane), ref_stride=P["ref0"][plane].shape[1],
-             ss=ss, bwidth=bw, bheight=bh, nblocks=n, blk=torch.from_numpy(blk.copy()).to(dsp.device))
+    d = dict(ref0=origin(P["ref0"][plane], plane), ref1=origin(P["ref0" if same else "ref1"][plane], plane), ref_stride=P["ref0"][plane].stride(0),
+             ss=ss, bwidth=bw, bheight=bh, nblocks=n, blk=torch.from_numpy(blk.copy()).to(dsp.device), placed=placed)
     if want_pred == "dense":
         d["pred"] = dense_out if dense_out is not None else poison.tensor((n, h, w), tdtype(bd), dsp.device)
     elif want_pred == "plane":
-        full = poison.tensor(tuple(P["src"][plane].shape), tdtype(bd), dsp.device)
+        if laid_out is None:
+            full = poison.tensor(tuple(P["src"][plane].shape), tdtype(bd), dsp.device)
+        else:
+            spec, lay = laid_out
+            blank = layouts.poison_like(mg.planes_of(bd, mg.CONTENTS[content])["src"][plane], poison._active.fill_byte)
+            buf, full = layouts.place_plane(spec.plane("pred"), blank, lay["pred"])
+            d["placed_pred"] = [("pred", buf, full, blank)]
         d["pred_full"] = full
-        d["pred"], d["pred_stride"] = origin(full, plane), full.shape[1]
+        d["pred"], d["pred_stride"] = origin(full, plane), full.stride(0)
     if with_dist:
-        d["src"], d["src_stride"] = origin(P["src"][plane], plane), P["src"][plane].shape[1]
+        d["src"], d["src_stride"] = origin(P["src"][plane], plane), P["src"][plane].stride(0)
         d["dist"] = poison.tensor((n,), torch.int64, dsp.device)
     return d, bd
 
@@ -132,6 +163,43 @@ def test_every_fixture_case_into_a_plane_equals_the_fixture_and_leaves_the_rest_
                 px, py, _ = mg.block_glue(blk[i], ss, bw, bh)
                 want[pad + py:pad + py + h, pad + px:pad + px + w] = g[f"pred_{gi}"][i]
             assert np.array_equal(got, want), (gi, take[:4])
+
+
+@pytest.mark.parametrize("bd", (8, 10))
+def test_ref_src_and_pred_planes_laid_out_unlike_each_other_equal_the_fixture(dsp, bd):
+    """the 8x8 luma group and the 4x4 Cb group of 8x8 blocks (both lists alone and BI_PRED in each), prediction into a plane and the fused SAD against the source: ref_stride, src_stride
+    and pred_stride all odd and all different, the three planes at different places in allocations of different sizes.  The blocks of a
+    group overlap in the plane, so the call takes a set that does not, the BI_PRED blocks first."""
+    g = gold()
+    fill = poison.fill_value(tdtype(bd)) & ((1 << 16) - 1 if bd > 8 else 255)
+    for want_group in ((bd, 0, 0, 8, 8, 0, 0), (bd, 0, 1, 8, 8, 0, 1)):
+        gi = next(i for i, r in enumerate(g["groups"]) if tuple(int(v) for v in r) == want_group)
+        _, content, ss, bw, bh, same, plane = want_group
+        pad, w, h = (mg.PAD[1] if ss else mg.PAD[0]), bw >> ss, bh >> ss
+        blk = mg.blocks_of(g, gi)
+        take, used = [], np.zeros((H + 2 * mg.PAD[0], W + 2 * mg.PAD[0]), bool)
+        for i in sorted(range(len(blk)), key=lambda i: int(blk[i]["pred_direction"]) != mg.BI):
+            px, py, _ = mg.block_glue(blk[i], ss, bw, bh)
+            if not used[py:py + h, px:px + w].any():
+                used[py:py + h, px:px + w] = True
+                take.append(i)
+        assert {int(blk[i]["pred_direction"]) for i in take} == {mg.LIST0, mg.LIST1, mg.BI}
+        spec = inter_pred_spec(plane)
+        d, _ = group_dict(dsp, gi, want_pred="plane", with_dist=True, laid_out=(spec, layouts.distinct_layouts(spec)))
+        assert len({d["ref_stride"], d["src_stride"], d["pred_stride"]}) == 3
+        d["blk"], d["nblocks"] = d["blk"][take].contiguous(), len(take)
+        d["dist"] = poison.tensor((len(take),), torch.int64, dsp.device)
+        run(dsp, [d], bd)
+        got = to_np(d["pred_full"], bd)
+        want = np.full(got.shape, fill, got.dtype)
+        for i in take:
+            px, py, _ = mg.block_glue(blk[i], ss, bw, bh)
+            want[pad + py:pad + py + h, pad + px:pad + px + w] = g[f"pred_{gi}"][i]
+        assert np.array_equal(got, want), (gi, np.argwhere(got != want)[:4].tolist())
+        src = mg.planes_of(bd, mg.CONTENTS[content])["src"][plane]
+        assert np.array_equal(d["dist"].cpu().numpy(), mg.np_dist(g[f"pred_{gi}"], src, ss, blk, mg.SAD)[take]), gi
+        layouts.assert_all_intact(d["placed"], poison._active.fill_byte)
+        layouts.assert_all_intact(d["placed_pred"], poison._active.fill_byte, written=True)
 
 
 @pytest.mark.parametrize("metric", (mg.SAD, mg.SSD))

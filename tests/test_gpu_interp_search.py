@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import layouts
 import poison
 from poison import poisoned_outputs  # noqa: F401
 
@@ -44,6 +45,13 @@ def planes(dsp):
     return _dev["planes"], _dev["strides"]
 
 
+def laid_out_planes(dsp, call):
+    """the same picture with every plane of the references and of the source at a layout of its own (tests/layouts.py)
+    -> (views at sample (0, 0), {"ref": strides, "src": strides}, placed)"""
+    spec = layouts.ref_src_spec(call, W, H, mg.PAD)
+    return layouts.place_ref_src(spec, layouts.distinct_layouts(spec), mg.planes_of(8, "random"))
+
+
 def rates(dsp, idx):
     if ("rates", idx) not in _dev:
         _dev[("rates", idx)] = torch.from_numpy(gold()["rates"][idx].copy()).to(dsp.device)
@@ -54,15 +62,21 @@ def up(dsp, a):
     return torch.from_numpy(np.ascontiguousarray(a)).to(dsp.device)
 
 
-def sse_group(dsp, gi, use_uv, with_sse=True):
+def sse_group(dsp, gi, use_uv, with_sse=True, laid_out=None):
+    """laid_out: what laid_out_planes returns, in place of the shared planes"""
     g = gold()
     bw, bh, d, same = (int(v) for v in g["groups"][gi])
-    P, strides = planes(dsp)
+    if laid_out is None:
+        P, strides = planes(dsp)
+        strides = {"ref": strides, "src": strides}
+    else:
+        P, strides = laid_out[:2]
+        assert not same                                   # a source that is list 0's planes would have list 0's strides
     blk = g[f"blk_{gi}"]
     n = len(blk)
     np_ = 3 if use_uv else 1
-    out = dict(ref0=P["ref0"][:np_], ref1=P["ref1"][:np_], ref_stride=strides[:np_], src=P["ref0" if same else "src"][:np_],
-               src_stride=strides[:np_], bwidth=bw, bheight=bh, nblocks=n, blk=up(dsp, blk))
+    out = dict(ref0=P["ref0"][:np_], ref1=P["ref1"][:np_], ref_stride=strides["ref"][:np_], src=P["ref0" if same else "src"][:np_],
+               src_stride=strides["ref" if same else "src"][:np_], bwidth=bw, bheight=bh, nblocks=n, blk=up(dsp, blk))
     if with_sse:
         out["sse"] = poison.tensor((n, np_, 9), torch.int32, dsp.device)
     return out
@@ -174,6 +188,28 @@ def test_the_one_call_search_equals_the_two_calls_and_the_fixture(dsp, use_uv):
             assert_records(dec_np(d["decision"]), g[f"dec_{gi}_{ci}_{ms.FULL}"], gi)
             if f"winblk_{gi}" in g:
                 assert np.array_equal(d["blk_out"].cpu().numpy(), g[f"winblk_{gi}"]), gi
+
+
+def test_the_search_with_six_different_strides_equals_the_fixture(dsp):
+    """ref_stride[3] and src_stride[3] all different and odd, chroma's unrelated to luma's, the nine planes at different places: the SSE
+    table and the decision records of a group of BI_PRED blocks, luma and chroma, against the fixture"""
+    g = gold()
+    ci = 0
+    use_uv, lam, q, rt = ms.REAL_CASES[ci]
+    assert use_uv
+    prm = dsp.make_interp_params(lam, q, rates(dsp, rt), use_uv, ms.FULL)
+    gi = next(i for i, r in enumerate(g["groups"]) if int(r[2]) == mg.BI and not int(r[3]))
+    lp = laid_out_planes(dsp, "svt_hip_interp_search_frame")
+    d = sse_group(dsp, gi, use_uv, laid_out=lp)
+    n = d["nblocks"]
+    d.update(ctx=up(dsp, g[f"ctx_{gi}"]), searchable=up(dsp, g[f"searchable_{gi}"]), decision=poison.tensor((n, 32), torch.uint8, dsp.device),
+             blk_out=poison.tensor((n, 16), torch.uint8, dsp.device))
+    rc, _ = dsp.interp_search_frame([d], W, H, prm, poison.tensor((max(16, dsp.interp_search_scratch_bytes([d], use_uv)),), torch.uint8, dsp.device))
+    ok(dsp, rc)
+    got, want = sse_np(d["sse"]), want_sse(gi, use_uv)
+    assert np.array_equal(got, want), (gi, np.argwhere(got != want)[:4].tolist())
+    assert_records(dec_np(d["decision"]), g[f"dec_{gi}_{ci}_{ms.FULL}"], gi)
+    layouts.assert_all_intact(lp[2], poison._active.fill_byte)
 
 
 def test_blk_out_fed_to_inter_pred_frame_reproduces_the_fixture_s_winner_prediction(dsp):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import layouts
 import poison
 from poison import poisoned_outputs  # noqa: F401
 
@@ -54,11 +55,15 @@ def initial_planes(c, name):
     return [c[f"init{p}"] if name in GIVEN else np.full(c[f"init{p}"].shape, fill_byte(), np.uint8) for p in range(3)]
 
 
-def args_of(dsp, tables, c, name, planes=3, optional=OPTIONAL):
-    """the call's dict for case inputs c with fresh poisoned outputs; the planes of all pictures lie in one tensor [npics * rows, stride]"""
+def args_of(dsp, tables, c, name, planes=3, optional=OPTIONAL, laid_out=None):
+    """the call's dict for case inputs c with fresh poisoned outputs; the planes of all pictures lie in one tensor [npics * rows, stride].
+    laid_out = (spec, layouts) of tests/layouts.py: the picture area of every source and reconstruction plane sits at a layout of its
+    own instead (views [npics, height, width]); the dict's "placed" lists them for layouts.assert_all_intact"""
     npics, sb_cols, sb_rows, width, height, stride, rows = (int(v) for v in c["dims"])
     nsb = sb_cols * sb_rows
     init = initial_planes(c, name)
+    if laid_out is not None:
+        return laid_out_args(dsp, tables, c, init, optional, *laid_out)
     recon = []
     for p in range(planes):
         t = poison.tensor((npics * (rows >> (p > 0)), stride >> (p > 0)), torch.uint8, DEV)
@@ -82,6 +87,19 @@ def args_of(dsp, tables, c, name, planes=3, optional=OPTIONAL):
     return a
 
 
+def laid_out_args(dsp, tables, c, init, optional, spec, lay):
+    npics, sb_cols, sb_rows, width, height, stride, rows = (int(v) for v in c["dims"])
+    area = lambda a, p: np.ascontiguousarray(a[:, :height >> (p > 0), :width >> (p > 0)])
+    src, p_src = layouts.place_operand(spec, lay, "src", [area(c[f"src{p}"], p) for p in range(3)], npics, fill_byte())
+    recon, p_recon = layouts.place_operand(spec, lay, "recon", [area(init[p], p) for p in range(3)], npics, fill_byte())
+    a = args_of(dsp, tables, c, "", 3, optional)
+    a.update(src=list(src), recon=list(recon), placed=(p_src, p_recon),
+             src_stride=[lay[f"src.{q}"].stride for q in "yuv"], stride=[lay[f"recon.{q}"].stride for q in "yuv"],
+             src_pic_pitch=[layouts.pitch_of(lay[f"src.{q}"], spec.plane(f"src.{q}")) for q in "yuv"],
+             recon_pic_pitch=[layouts.pitch_of(lay[f"recon.{q}"], spec.plane(f"recon.{q}")) for q in "yuv"])
+    return a
+
+
 def run(dsp, a):
     assert dsp.intra_encode_frame(a) == 0, dsp.lib.svt_hip_last_error()
     torch.cuda.synchronize()
@@ -102,11 +120,15 @@ def check(a, c, o, name):
     live = np.arange(mi.MAX_FINAL)[None, None] < np.minimum(c["count"], mi.MAX_FINAL)[..., None]
     init = initial_planes(c, name)
     for p, t in enumerate(a["recon"]):
-        want, mask = o[f"recon{p}"], o[f"rmask{p}"]
-        got = t.cpu().numpy().reshape(want.shape)
+        want, mask, was = o[f"recon{p}"], o[f"rmask{p}"], init[p]
+        got = t.cpu().numpy()
+        if got.ndim == 3:                                                    # laid out: the picture area alone, no sample is written outside it
+            assert not mask[:, got.shape[1]:].any() and not mask[:, :, got.shape[2]:].any()
+            want, mask, was = (x[:, :got.shape[1], :got.shape[2]] for x in (want, mask, was))
+        got = got.reshape(want.shape)
         bad = np.nonzero((got != want) & mask)
         assert not len(bad[0]), (name, p, [b[:8] for b in bad], got[bad][:8], want[bad][:8])
-        assert np.array_equal(got[~mask], init[p][~mask]), (name, p, [b[:8] for b in np.nonzero((got != init[p]) & ~mask)])
+        assert np.array_equal(got[~mask], was[~mask]), (name, p, [b[:8] for b in np.nonzero((got != was) & ~mask)])
     if a.get("status") is not None:
         got = a["status"].cpu().numpy()
         assert np.array_equal(got[live], o["status"][live]), (name, np.nonzero((got != o["status"]) & live), got[live][:32])
@@ -134,6 +156,22 @@ def test_case_equals_the_fixture(dsp, gold, tables, k):
     a = args_of(dsp, tables, c, mi.CASE_NAMES[k])
     run(dsp, a)
     check(a, c, o, mi.CASE_NAMES[k])
+
+
+def test_the_two_picture_case_with_every_plane_laid_out_differently_equals_the_fixture(dsp, gold, tables):
+    """cover1 (two pictures): src_stride[p] unlike stride[p] for every plane, the chroma strides neither luma's nor luma's >> 1,
+    src_pic_pitch[p] unlike recon_pic_pitch[p]: twelve strides and pitches no two of which are equal.  tests/layouts.py asserts that,
+    and that a mix-up of them stays inside the planes' own allocations, before anything is uploaded."""
+    name = "cover1"
+    c, o = mi.load_case(gold, mi.CASE_NAMES.index(name))
+    npics, sb_cols, sb_rows, width, height, stride, rows = (int(v) for v in c["dims"])
+    spec = layouts.picture_spec("svt_hip_intra_encode_frame", width, height, ("src", "recon"), npics)
+    a = args_of(dsp, tables, c, name, laid_out=(spec, layouts.distinct_layouts(spec)))
+    assert len(set(a["src_stride"] + a["stride"] + a["src_pic_pitch"] + a["recon_pic_pitch"])) == 12
+    run(dsp, a)
+    check(a, c, o, name)
+    layouts.assert_all_intact(a["placed"][0], fill_byte())
+    layouts.assert_all_intact(a["placed"][1], fill_byte(), written=True)
 
 
 @pytest.mark.parametrize("name", ["cover1", "refuse"])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import layouts
 import poison
 import svtlibs
 import test_gpu_me_setup as stage
@@ -40,13 +41,43 @@ def case_names():
 NAMES, PICTURE_OF = case_names()
 
 
-def device_pyramid(dsp, lumas):
-    """lumas: one [H, W] picture or a list of them (a stack) -> (MePyramid, geometry)"""
+def device_pyramid(dsp, lumas, laid_out=None):
+    """lumas: one [H, W] picture or a list of them (a stack) -> (MePyramid, geometry).  laid_out = (spec, {plane: Layout}, operand) from
+    tests/layouts.py: every level of this operand ("src", "ref0", "ref1") sits at a Layout of its own in a poisoned allocation, cut down
+    to the padding the calls read; the pyramid's `placed` lists (name, buffer, view, content) for layouts.assert_guards_intact"""
     stack = isinstance(lumas, (list, tuple))
     pyr = [svtlibs.me_pyramid(l) for l in (lumas if stack else [lumas])]
     geo = pyr[0][1]
-    planes = [torch.from_numpy(np.stack([p[0][k] for p in pyr]) if stack else pyr[0][0][k]).cuda() for k in range(3)]
-    return dsp.me_pyramid(planes, [(g[1], g[2]) for g in geo]), geo
+    if laid_out is None:
+        planes = [torch.from_numpy(np.stack([p[0][k] for p in pyr]) if stack else pyr[0][0][k]).cuda() for k in range(3)]
+        return dsp.me_pyramid(planes, [(g[1], g[2]) for g in geo]), geo
+    spec, lay, operand = laid_out
+    planes, origins, placed = [None] * 3, [(0, 0)] * 3, []
+    for pl in (q for q in spec.planes if q.operand == operand):
+        k = int(pl.name.split(".")[1])
+        l, (_, ox, oy, w, h) = lay[pl.name], geo[k]
+        content = np.stack([p[0][k][oy - pl.before[1]:oy + h + pl.after[1], ox - pl.before[0]:ox + w + pl.after[0]] for p in pyr])
+        buf, view = layouts.place_plane(pl, content if stack else content[0], l, len(pyr))
+        rows, pitch = layouts.rows_of(l, pl), layouts.pitch_of(l, pl)
+        base = layouts.start(buf, l)
+        planes[k] = torch.as_strided(base, (len(pyr), rows, l.stride), (pitch, l.stride, 1)) if stack else base[:rows * l.stride].view(rows, l.stride)
+        origins[k] = (l.origin_x, l.origin_y)
+        placed.append((pl.name, buf, view, content if stack else content[0]))
+    out = dsp.me_pyramid(planes, origins)
+    out.placed = placed
+    return out, geo
+
+
+def laid_out_pyramids(dsp, spec, triple):
+    """src / ref0 / ref1 of one call, every plane at a layout no other plane of the call has (layouts.distinct_layouts asserts it)"""
+    lay = layouts.distinct_layouts(spec)
+    return [device_pyramid(dsp, t, (spec, lay, who))[0] for t, who in zip(triple, ("src", "ref0", "ref1"))]
+
+
+def assert_pyramids_intact(pyr, fill):
+    for p in pyr:
+        for name, buf, view, content in p.placed:
+            layouts.assert_guards_intact(buf, view, fill, name, content)
 
 
 def as_arrays(dsp, out, nl):
@@ -109,6 +140,36 @@ def test_a_stack_of_two_pictures_under_a_captured_graph_equals_two_single_calls(
         for i in range(2):
             for k in KEYS:
                 assert np.array_equal(got[k][i * nsb:(i + 1) * nsb], singles[i][k]), (i, k)
+
+
+def assert_equals_the_fixture(got, g, prefix, sbs=slice(None)):
+    for k in KEYS:
+        want = g[prefix + k]
+        assert np.array_equal(got[k][sbs], want), (k, np.argwhere(got[k][sbs] != want)[:4].tolist())
+
+
+def test_every_operand_laid_out_differently_equals_the_reference(dsp, pkg, poisoned_outputs):
+    """b_edge_full (B, all three HME levels, 6 SBs): nine strides that all differ, the source's origins unlike the references' at every
+    level, list 0's level-0 origin unlike list 1's and neither the fixture's 68; levels 1 and 2 of the references keep the fixture's
+    origin (layouts.ME_FIXED_WHY).  Alone and as a stack of two at nine pitches.  The expected values are the fixture's."""
+    g = gold()
+    name = "b_edge_full"
+    prm = g[name + "_prm"][0]
+    params = pkg.MeFrameParams.from_lcu_prm(prm)
+    a = [g[f"pic_edge_{i}"] for i in range(3)]
+    H, W = a[0].shape
+    fill = poisoned_outputs.fill_byte
+    pyr = laid_out_pyramids(dsp, layouts.me_spec("svt_hip_motion_estimate_frame", W, H), a)
+    out = dsp.motion_estimate_frame(pyr[0], pyr[1], pyr[2], params)
+    torch.cuda.synchronize()
+    assert_equals_the_fixture(as_arrays(dsp, out, 2), g, name + "_")
+    assert_pyramids_intact(pyr, fill)
+    b = [np.ascontiguousarray(p[::-1, ::-1]) for p in (a[0], a[2], a[1])]
+    pyr = laid_out_pyramids(dsp, layouts.me_spec("svt_hip_motion_estimate_frame", W, H, n_pictures=2), [[b[i], a[i]] for i in range(3)])
+    out = dsp.motion_estimate_frame(pyr[0], pyr[1], pyr[2], params, 2)
+    torch.cuda.synchronize()
+    assert_equals_the_fixture(as_arrays(dsp, out, 2), g, name + "_", slice(6, 12))        # the fixture's picture is the SECOND of the stack
+    assert_pyramids_intact(pyr, fill)
 
 
 @pytest.mark.parametrize("slice_type", [1, 0])

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import layouts
 import me_subpel_cases as sp
 import poison
 import svtlibs
@@ -215,6 +216,79 @@ def test_a_stack_of_two_pictures_under_a_captured_graph_equals_two_single_calls(
         for i in range(2):
             for k in KEYS:
                 assert np.array_equal(got[k][i * nsb:(i + 1) * nsb], singles[i][k]), (i, k)
+
+
+LAID_OUT = "b_edge_fullsad_nsq"               # B, HME on, 209 PUs, both lists, 6 SBs
+
+
+def laid_out_case(g):
+    a = [g[f"pic_edge_{i}"] for i in range(3)]
+    b = [np.ascontiguousarray(p[::-1, ::-1]) for p in (a[0], a[2], a[1])]
+    return a, b, g[LAID_OUT + "_prm"][0]
+
+
+def test_the_whole_call_with_every_operand_laid_out_differently_equals_the_reference(dsp, pkg, poisoned_outputs):
+    """svt_hip_motion_estimate_subpel_frame: nine strides, origins and (in the stack of two) pitches that all differ, as
+    tests/test_gpu_me_frame.py lays them out; the refinement and the bi-prediction index src, list 0 and list 1 with fields of their own"""
+    g = gold()
+    a, b, prm = laid_out_case(g)
+    params = pkg.MeFrameParams.from_lcu_prm(prm)
+    H, W = a[0].shape
+    fill = poisoned_outputs.fill_byte
+    for n, triple, sbs in ((1, a, slice(0, 6)), (2, [[b[i], a[i]] for i in range(3)], slice(6, 12))):
+        pyr = mf.laid_out_pyramids(dsp, layouts.me_spec("svt_hip_motion_estimate_subpel_frame", W, H, n_pictures=n), triple)
+        out = dsp.motion_estimate_subpel_frame(pyr[0], pyr[1], pyr[2], params, n)
+        torch.cuda.synchronize()
+        mf.assert_equals_the_fixture(mf.as_arrays(dsp, out, 2), g, LAID_OUT + "_lcu_", sbs)
+        mf.assert_pyramids_intact(pyr, fill)
+
+
+def test_the_stage_with_every_operand_laid_out_differently_equals_the_reference(dsp, pkg, poisoned_outputs):
+    """svt_hip_me_subpel_frame reads level 0 only: three strides, origins and pitches; a stack of two whose second picture is the fixture's"""
+    g = gold()
+    a, b, prm = laid_out_case(g)
+    params = pkg.MeFrameParams.from_lcu_prm(prm)
+    H, W = a[0].shape
+    fill = poisoned_outputs.fill_byte
+    full_sad, full_mv = (g[f"{LAID_OUT}_full_{k}"].view(np.int32) for k in ("sad", "mv"))
+    for n, triple in ((1, a), (2, [[b[i], a[i]] for i in range(3)])):
+        pyr = mf.laid_out_pyramids(dsp, layouts.me_spec("svt_hip_me_subpel_frame", W, H, n_pictures=n, levels=(0,)), triple)
+        sad, mv, ssd = (poison.tensor((6 * n, 2, 209), torch.int32, dsp.device) for _ in range(3))
+        dirn = poison.tensor((6 * n, 2, 209), torch.uint8, dsp.device)
+        sad.copy_(torch.from_numpy(np.concatenate([full_sad] * n)))
+        mv.copy_(torch.from_numpy(np.concatenate([full_mv] * n)))
+        dsp.me_subpel_frame(pyr[0], pyr[1], pyr[2], params, sad, mv, n_pictures=n, best_ssd=ssd, half_dir=dirn)
+        torch.cuda.synchronize()
+        for got, key in ((sad, "quarter_sad"), (mv, "quarter_mv"), (ssd, "quarter_ssd"), (dirn, "half_dir")):
+            got, want = got.cpu().numpy()[-6:], g[f"{LAID_OUT}_{key}"]
+            assert np.array_equal(got.view(want.dtype), want), (n, key, np.argwhere(got.view(want.dtype) != want)[:4].tolist())
+        mf.assert_pyramids_intact(pyr, fill)
+
+
+def test_the_planes_of_a_reference_laid_out_on_its_own_equal_the_fixture(dsp, poisoned_outputs):
+    """svt_hip_me_subpel_planes: the reference's level 0 at an odd stride and an origin of (67, 69) or thereabouts, not the fixture's 68"""
+    g = gold()
+    for k, (ci, sb, l) in enumerate(g["plane_windows"]):
+        name = NAMES[ci]
+        prm = g[name + "_prm"][sb]
+        xo, yo, saw, sah = (int(v) for v in g[name + "_area"][sb, l])
+        pic = g[f"pic_{PICTURE_OF[name]}_{1 + l}"]
+        spec = layouts.me_spec("svt_hip_me_subpel_planes", pic.shape[1], pic.shape[0], n_lists=1, levels=(0,))
+        spec.planes = [p for p in spec.planes if p.operand == "ref0"]
+        lay = layouts.distinct_layouts(spec)
+        ref = mf.device_pyramid(dsp, pic, (spec, lay, "ref0"))[0]
+        assert ref.stride[0] % 2 == 1 and 68 not in (ref.origin_x[0], ref.origin_y[0])
+        got = dsp.me_subpel_planes(ref, int(prm[0]), int(prm[1]), int(prm[2]) + xo, int(prm[3]) + yo, saw + 64, sah + 64).cpu().numpy()
+        want = g[f"planes_{k}"]
+        assert np.array_equal(got, want), (name, sb, l, np.argwhere(got != want)[:4].tolist())
+        mf.assert_pyramids_intact([ref], poisoned_outputs.fill_byte)
+
+
+def test_the_planes_of_a_reference_laid_out_on_its_own_equal_the_fixture_fillA5(dsp, poisoned_outputs):      # 8-bit samples, as above
+    test_the_planes_of_a_reference_laid_out_on_its_own_equal_the_fixture(dsp, poisoned_outputs)
+
+
+test_the_planes_of_a_reference_laid_out_on_its_own_equal_the_fixture_fillA5.poison_fill = poison.FILLS[1]
 
 
 def test_pictures_without_the_interpolations_padding_are_refused_and_nothing_is_written(dsp, pkg):

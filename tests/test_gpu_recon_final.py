@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import layouts
 import poison
 from poison import poisoned_outputs  # noqa: F401
 
@@ -109,6 +110,28 @@ def test_case_equals_the_fixture(dsp, gold, k):
     a = args_of(dsp, c, tabs)
     run(dsp, a)
     check(a, c, o)
+
+
+def test_planes_laid_out_unlike_each_other_equal_the_fixture(dsp, gold):
+    """skips (96 x 80 in 128 x 128 of superblocks): stride[0 .. 2] odd, all different and chroma's neither luma's nor half of it; the
+    picture area of each plane alone in a poisoned allocation, so a sample written with another plane's stride lands on a guard"""
+    z, geom, tabs = gold
+    c, o = mr.load_case(z, mr.ALL_NAMES.index("skips"), tabs)
+    w, h = int(c["width"][0]), int(c["height"][0])
+    spec = layouts.picture_spec("svt_hip_recon_final_frame", w, h, ("recon",))
+    lay = layouts.distinct_layouts(spec)
+    a = args_of(dsp, c, tabs)
+    area = [np.full((int(c["height"][p]), int(c["width"][p])), fill_byte(), np.uint8) for p in range(3)]
+    recon, placed = layouts.place_operand(spec, lay, "recon", area, 1, fill_byte())
+    a.update(recon=list(recon), stride=[lay[f"recon.{q}"].stride for q in "yuv"])
+    run(dsp, a)
+    o = dict(o)
+    for p in range(3):                                                  # check() on the picture area: nothing is written outside it
+        hh, ww = area[p].shape
+        assert not o[f"rmask{p}"][hh:].any() and not o[f"rmask{p}"][:, ww:].any()
+        o[f"recon{p}"], o[f"rmask{p}"] = o[f"recon{p}"][:hh, :ww], o[f"rmask{p}"][:hh, :ww]
+    check(a, c, o)
+    layouts.assert_all_intact(placed, fill_byte(), written=True)
 
 
 @pytest.mark.parametrize("name", ["main2", "skips"])
