@@ -63,9 +63,7 @@ int launch_status(const char* what);
 }  // namespace svthost
 namespace svtdev { struct FrameDesc; struct MePuMap; }
 namespace svthost {
-// svt_hip_pixel.hip: the LDS row pitch of the motion search's reference window, and the raster PU order of the me_results rows
-// (shared with svt_hip_me_frame.hip)
-uint32_t me_window_pitch(uint32_t win_w);
+// svt_hip_pixel.hip: the raster PU order of the me_results rows (shared with svt_hip_me_frame.hip)
 const svtdev::MePuMap& me_pu_map();
 // svt_hip_me_subpel.hip: the two launches that svt_hip_motion_estimate_subpel_frame (svt_hip_me_frame.hip) puts behind the full-pel search, for
 // arguments the caller has checked (me_subpel_plan.h): the refinement of the result rows in place, and the bi-prediction on the

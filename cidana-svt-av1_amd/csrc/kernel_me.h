@@ -133,7 +133,7 @@ __global__ __launch_bounds__(ME_THREADS) void hme_level_kernel(
     mv += (size_t)blockIdx.y * ntasks * 2;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t* s_src = reinterpret_cast<uint32_t*>(smem);            // [32 rows][16 dwords]: the block's even rows, zero-padded
-    uint8_t* s_ref = smem + 32 * 64;
+    uint8_t* s_ref = smem + svthost::ME_SRC_LDS;
     __shared__ unsigned long long s_red[4];
     const uint32_t task = blockIdx.x;
     if (task >= ntasks) return;

@@ -41,7 +41,7 @@ constexpr unsigned ME_MAX_SAD_VALUE = 128 * 128 * 255;          // EbMotionEstim
 __global__ __launch_bounds__(ME_THREADS) void me_frame_prologue_kernel(const MeFrameDev d) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t* s_src = reinterpret_cast<uint32_t*>(smem);            // [32 rows][16 dwords]: the level's SB block, even rows
-    uint8_t* s_ref = smem + 32 * 64;                                // the region's clipped window
+    uint8_t* s_ref = smem + svthost::ME_SRC_LDS;                              // the region's clipped window
     __shared__ unsigned long long s_red[4];
     __shared__ unsigned long long s_sad[4];                         // the level's result per region: what the stage calls keep in HBM
     __shared__ int s_cx[4], s_cy[4];

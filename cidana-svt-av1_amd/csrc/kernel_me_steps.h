@@ -22,6 +22,7 @@
 // Limits: search_w * search_h <= 4096 (12-bit index), window must fit 64 KiB LDS.
 #pragma once
 #include "dev_common.h"
+#include "search_plan.h"
 
 namespace svtdev {
 
@@ -81,7 +82,7 @@ __device__ __forceinline__ void me_sb_search16_body(
     // reference's EbMeTierZeroPu order instead of 8x8 | 16x16 | 32x32 | 64x64 back to back.
     int w8q, int ref_layout) {
     uint32_t* s_src = reinterpret_cast<uint32_t*>(smem);            // [32 even rows][16 dwords]
-    uint8_t* s_ref = smem + 32 * 64;                                // [(64+sh-1)][wpitch], wpitch % 16 == 0
+    uint8_t* s_ref = smem + svthost::ME_SRC_LDS;                              // [(64+sh-1)][wpitch], wpitch % 16 == 0
     __shared__ unsigned s_red[4][ME_PUS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // ---- stage the even source rows and the reference window (16-B unaligned loads, 4 in flight) ----
@@ -423,7 +424,7 @@ __device__ __forceinline__ void me_nsq4_body(
     uint8_t* smem, const uint8_t* __restrict__ gs, uint32_t src_stride, const uint8_t* __restrict__ gr, uint32_t ref_stride,
     int search_w, int search_h, int ox, int oy, uint32_t* __restrict__ bs, uint32_t* __restrict__ bm, uint32_t wpitch, uint2* s_pair) {
     uint32_t* s_src = reinterpret_cast<uint32_t*>(smem);            // [32 even rows][16 dwords]
-    uint8_t* s_ref = smem + 32 * 64;                                // [(64+sh-1)][wpitch], wpitch % 16 == 0
+    uint8_t* s_ref = smem + svthost::ME_SRC_LDS;                              // [(64+sh-1)][wpitch], wpitch % 16 == 0
     __shared__ unsigned s_red[4][NSQ_BATCHES * 16];                 // [wave][batch][slot]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool sp = (search_w & 7) != 0;                            // single-search-point form (search_w < 8)
@@ -763,7 +764,7 @@ __device__ __forceinline__ void me_fullpel_area_body(
     } else if ((sw & 7) == 0 || (sw < 8 && flavour == 0 && pair_off)) {
         me_nsq4_body(smem, gs, src_stride, gr, ref_stride, sw, sh, ox, oy, bs, bm, wpitch, reinterpret_cast<uint2*>(smem + pair_off));
     } else {
-        me_exact_body(reinterpret_cast<uint32_t*>(smem), reinterpret_cast<uint32_t(*)[64]>(smem + 2048), gs, src_stride, gr, ref_stride, sw, sh, ox,
+        me_exact_body(reinterpret_cast<uint32_t*>(smem), reinterpret_cast<uint32_t(*)[64]>(smem + svthost::ME_SRC_LDS), gs, src_stride, gr, ref_stride, sw, sh, ox,
                       oy, flavour, 1, bs, bm);
     }
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include <type_traits>
 #include "dev_common.h"
+#include "search_plan.h"
 
 namespace svtdev {
 
@@ -144,8 +145,8 @@ __global__ __launch_bounds__(256) void sad_search_kernel(
     const uint32_t win_w = width + search_w - 1;
     // rows of the window that can be touched: candidate row ys adds ys*ref_stride_raw,
     // block row y adds y*ref_stride; stage (row, offset) pairs as needed.
-    const uint32_t wpitch = (win_w + 3 + 8) & ~3u;   // host uses the same formula
-    const uint32_t spitch = (width + 3) & ~3u;
+    const uint32_t wpitch = svthost::sad_plain_wpitch(win_w);
+    const uint32_t spitch = svthost::sad_plain_spitch(width);
     uint8_t* s_src = smem + (size_t)wave * (src_lds_bytes + ref_lds_bytes);
     uint8_t* s_ref = s_src + src_lds_bytes;
     if (blk >= nblocks) return;   // whole wave exits together (blk is wave-uniform)
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(256) void sad_search_kernel(
     // ref_stride = 2*ref_stride_raw).  When ref_stride == ref_stride_raw the rows
     // overlap and only search_h + height - 1 distinct rows are staged.
     const bool plain = (ref_stride == ref_stride_raw);
-    const uint32_t nrows = plain ? (uint32_t)(search_h + height - 1) : (uint32_t)search_h * height;
+    const uint32_t nrows = svthost::sad_nrows<uint32_t>(plain, search_h, height);
     for (uint32_t i = lane; i < wpitch * nrows; i += 64) {
         const uint32_t rr = i / wpitch, x = i - rr * wpitch;
         size_t off;
@@ -239,9 +240,9 @@ __global__ __launch_bounds__(256) void sad_search_q_kernel(
     const uint32_t blk = blockIdx.x * slots + slot;
     const bool valid = blk < nblocks;
     const uint32_t win_w = width + search_w - 1;
-    const uint32_t wpitch = ((win_w + 15) & ~15u) + 16;      // whole 16-B chunks + slack for the sliding window
+    const uint32_t wpitch = svthost::sad_q_wpitch(win_w);      // whole 16-B chunks + slack for the sliding window
     const bool plain = (ref_stride == ref_stride_raw);
-    const uint32_t nrows = plain ? (uint32_t)(search_h + height - 1) : (uint32_t)search_h * height;
+    const uint32_t nrows = svthost::sad_nrows<uint32_t>(plain, search_h, height);
     uint8_t* s_src = smem + (size_t)slot * (src_lds_bytes + ref_lds_bytes);
     uint8_t* s_ref = s_src + src_lds_bytes;
     const uint32_t wq = width >> 2;
@@ -283,7 +284,7 @@ __global__ __launch_bounds__(256) void sad_search_q_kernel(
         {   // reference window: rows of wpitch bytes in 16-B chunks; a chunk is loaded wide when it
             // ends inside the window's own footprint (row tails over-read the next row: harmless, only
             // excluded candidates can touch those bytes), else byte-wise with zero fill
-            const uint32_t cpr = (win_w + 15) >> 4;
+            const uint32_t cpr = svthost::sad_cpr(win_w);
             const size_t span = plain ? (size_t)(nrows - 1) * ref_stride_raw + win_w
                                       : (size_t)(search_h - 1) * ref_stride_raw + (size_t)(height - 1) * ref_stride + win_w;
             uint32_t rxs = 1;
@@ -420,7 +421,7 @@ __global__ __launch_bounds__(256) void sad_search_q2_kernel(
     static_assert(CW % 4 == 0 && CW * CH <= 256, "source block must fit 64 VGPRs");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int WQ = CW / 4;
-    constexpr uint32_t SRC_BYTES = (CW * CH + 15) & ~15;
+    constexpr uint32_t SRC_BYTES = svthost::sad_q_src_bytes(CW, CH);
     const uint32_t tid = threadIdx.x;
     const uint32_t lsh = __builtin_ctz(lpb);
     const uint32_t slot = tid >> lsh, l = tid & (lpb - 1);
@@ -428,8 +429,8 @@ __global__ __launch_bounds__(256) void sad_search_q2_kernel(
     const uint32_t blk = blockIdx.x * slots + slot;
     const bool valid = blk < nblocks;
     const uint32_t win_w = CW + search_w - 1;
-    const uint32_t wpitch = ((win_w + 15) & ~15u) + 16;
-    const uint32_t nrows = (uint32_t)(search_h + CH - 1);
+    const uint32_t wpitch = svthost::sad_q_wpitch(win_w);
+    const uint32_t nrows = svthost::sad_nrows<uint32_t>(true, search_h, CH);
     // LDS: all source blocks first (16-B aligned), then the windows at a pitch of ref_lds_bytes == 8 (mod 32)
     // bytes: with the 48-B row pitch of a 23-wide window the 32 lanes of a ds_read_b32 group (4 blocks x
     // 4 row pairs x 2 column groups) then hit 32 different banks (measured before: 56 % of the LDS
@@ -448,7 +449,7 @@ __global__ __launch_bounds__(256) void sad_search_q2_kernel(
         constexpr uint32_t CS = CW % 16 == 0 ? 16 : (CW % 8 == 0 ? 8 : 4);
         constexpr uint32_t NSRC = CW * CH / CS;
         constexpr int SU = Q2_SU;
-        const uint32_t cpr = (win_w + 15) >> 4;
+        const uint32_t cpr = svthost::sad_cpr(win_w);
         const uint32_t nref = nrows * cpr;
         const size_t span = (size_t)(nrows - 1) * ref_stride + win_w;
         // every load below is unconditional (clamped index / clamped offset), so nothing separates them
@@ -602,15 +603,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void s
     // source blocks sit 16 B apart from a multiple of 256 B: the broadcast b128 reads of a row (one address per block) then
     // fall on different banks (at a stride of 256 B all eight blocks of a wave hit the same four: PMC showed 38 % of the LDS
     // cycles as bank conflicts)
-    constexpr uint32_t SRC_BYTES = ((CW * CH + 15) & ~15) + 16;
+    constexpr uint32_t SRC_BYTES = svthost::sad_q2p_src_bytes(CW, CH);
     constexpr uint32_t CS = CW % 16 == 0 ? 16 : (CW % 8 == 0 ? 8 : 4);
     constexpr uint32_t NSRC = CW * CH / CS;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t lsh = __builtin_ctz(lpb), bpw = 64u >> lsh;
     const uint32_t wslot = lane >> lsh, l = lane & (lpb - 1);
     const uint32_t win_w = CW + search_w - 1;
-    const uint32_t nrows = (uint32_t)(search_h + CH - 1);
-    const uint32_t cpr = (win_w + 15) >> 4;
+    const uint32_t nrows = svthost::sad_nrows<uint32_t>(true, search_h, CH);
+    const uint32_t cpr = svthost::sad_cpr(win_w);
     const uint32_t nref = nrows * cpr;
     const size_t span = (size_t)(nrows - 1) * ref_stride + win_w;
     // LDS of a wave: its source blocks, then its windows at a row pitch of wpitch = 16 * cpr + 8 bytes and a block stride
@@ -820,8 +821,8 @@ __global__ __launch_bounds__(256) void sad_search_q16_kernel(
     const uint32_t blk = blockIdx.x * slots + slot;
     const bool valid = blk < nblocks;
     const uint32_t win_w = CW + search_w - 1;
-    const uint32_t nrows = (uint32_t)search_h + height - 1;
-    const uint32_t src_bytes = CW * height;
+    const uint32_t nrows = svthost::sad_nrows<uint32_t>(true, search_h, height);
+    const uint32_t src_bytes = svthost::sad_q16_src_bytes(CW, height);
     uint8_t* s_src = smem + (size_t)slot * (src_bytes + ref_lds_bytes);
     uint8_t* s_ref = s_src + src_bytes;
     if (valid) {
@@ -831,7 +832,7 @@ __global__ __launch_bounds__(256) void sad_search_q16_kernel(
         // per lane issued back to back, then the LDS writes - one memory latency per SU chunks
         constexpr int SU = 4;
         const uint32_t nsrc = WC * height;
-        const uint32_t cpr = (win_w + 15) >> 4;
+        const uint32_t cpr = svthost::sad_cpr(win_w);
         const uint32_t nref = nrows * cpr;
         const size_t span = (size_t)(nrows - 1) * ref_stride + win_w;
         for (uint32_t i0 = l; i0 < nsrc || i0 < nref; i0 += SU * lpb) {

@@ -5,6 +5,7 @@
 #include "host_common.h"
 #include "kernel_me_frame.h"
 #include "me_subpel_plan.h"
+#include "search_plan.h"
 
 using namespace svtdev;
 using namespace svthost;
@@ -26,8 +27,8 @@ struct MeFramePlan {
     int level_on[3];
     uint32_t nsbx, nsby;
     int max_w, max_h;
-    uint32_t hme_wpitch, search_wpitch, pair_off;
-    size_t hme_lds, search_lds;
+    MeWindow search;
+    HmeWindow hme_win;
     svt_hip_hme_params hme[3][4];
 };
 }  // namespace
@@ -74,18 +75,11 @@ static int me_frame_plan(const svt_hip_me_frame_params* P, MeFramePlan& pl) {
         return set_err(SVT_HIP_ERR_INVALID, "search area %d x %d", P->search_area_width, P->search_area_height);
     pl.max_w = (P->search_area_width + 7) & ~7;
     pl.max_h = P->search_area_height;
-    if (pl.max_w * pl.max_h > 4096) return set_err(SVT_HIP_ERR_INVALID, "search area %d x %d (at most 4096 points)", pl.max_w, pl.max_h);
-    {   // as svt_hip_me_fullpel_search_areas_batch sizes its window
-        const uint32_t win_w = 64 + pl.max_w - 1, win_h = 64 + pl.max_h - 1;
-        pl.search_wpitch = me_window_pitch(win_w);
-        pl.search_lds = 32 * 64 + (size_t)pl.search_wpitch * win_h;
-        if (pl.nsq) {
-            pl.pair_off = (uint32_t)((pl.search_lds + 15) & ~(size_t)15);
-            pl.search_lds = pl.pair_off + (size_t)8 * 7 * pl.max_h;
-        }
-        if (pl.search_lds > 58 * 1024) return set_err(SVT_HIP_ERR_INVALID, "search window of %d x %d needs %zu B of LDS (> 58 KiB)", pl.max_w, pl.max_h, pl.search_lds);
-    }
+    // as svt_hip_me_fullpel_search_areas_batch sizes its window (search_plan.h)
+    if (int rc = me_window_check(pl.max_w, pl.max_h, pl.nsq, ME_NSQ_LDS_MAX, pl.search)) return rc;
     const uint32_t mult = hme_level0_multiplier(P->hierarchical_levels, P->temporal_layer_index);
+    svt_hip_hme_params all[3 * 4];
+    int nall = 0;
     for (int lv = 0; lv < 3; lv++) {
         if (!pl.level_on[lv]) continue;
         const int k = 2 - lv;                             // pyramid level of HME level lv
@@ -104,18 +98,10 @@ static int me_frame_plan(const svt_hip_me_frame_params* P, MeFramePlan& pl) {
                 return set_err(SVT_HIP_ERR_INVALID, "HME level %d parameters", lv);
             if (hp.search_area_width < 1 || hp.search_area_height < 1)
                 return set_err(SVT_HIP_ERR_INVALID, "HME level %d region %d: search area %d x %d", lv, r, hp.search_area_width, hp.search_area_height);
-            const uint32_t wp = ((64 + (uint32_t)hp.search_area_width - 1 + 3) & ~3u) + 8;       // as svt_hip_hme_level_regions_batch
-            if (wp > pl.hme_wpitch) pl.hme_wpitch = wp;
+            all[nall++] = hp;
         }
     }
-    for (int lv = 0; lv < 3; lv++)
-        for (int r = 0; r < pl.nreg && pl.level_on[lv]; r++) {
-            const size_t need = 32 * 64 + (size_t)pl.hme_wpitch * ((uint32_t)pl.hme[lv][r].search_area_height + 62);
-            if (need > pl.hme_lds) pl.hme_lds = need;
-        }
-    if (pl.hme_lds > 60 * 1024) return set_err(SVT_HIP_ERR_INVALID, "HME search window needs %zu B of LDS (> 60 KiB)", pl.hme_lds);
-    if (pl.hme_lds == 0) pl.hme_lds = 32 * 64;
-    return SVT_HIP_OK;
+    return hme_window(all, nall, pl.hme_win);             // as svt_hip_hme_level_regions_batch sizes its window, over every level's regions
 }
 
 static size_t me_frame_scratch(const MeFramePlan& pl, uint32_t n_pictures) {
@@ -218,19 +204,17 @@ static int me_frame_enqueue(const svt_hip_me_pyramid* src, const svt_hip_me_pyra
     d.nreg = pl.nreg; d.last_level = pl.last_level;
     d.nlists = pl.nl; d.npus = P.max_number_of_pus_per_sb;
     d.nsbx = pl.nsbx; d.nsb = nsb;
-    d.hme_wpitch = pl.hme_wpitch ? pl.hme_wpitch : 8;
+    d.hme_wpitch = pl.hme_win.wpitch ? pl.hme_win.wpitch : 8;
     d.area = (int16_t*)d_scratch;
     d.area_origin = d_area_origin;
     d.best_sad = d_best_sad; d.best_mv = d_best_mv;
 
     const hipStream_t s = (hipStream_t)stream;
     const dim3 grid(nsb, (uint32_t)pl.nl, n_pictures);
-    hipLaunchKernelGGL(me_frame_prologue_kernel, grid, dim3(ME_THREADS), pl.hme_lds, s, d);
+    hipLaunchKernelGGL(me_frame_prologue_kernel, grid, dim3(ME_THREADS), pl.hme_win.lds, s, d);
     if (int rc = launch_status("me_frame_prologue")) return rc;
-    if (pl.nsq)
-        hipLaunchKernelGGL(me_frame_search_kernel<true>, grid, dim3(ME_THREADS), pl.search_lds, s, d, pl.max_w, pl.max_h, P.flavour, pl.search_wpitch, pl.pair_off);
-    else
-        hipLaunchKernelGGL(me_frame_search_kernel<false>, grid, dim3(ME_THREADS), pl.search_lds, s, d, pl.max_w, pl.max_h, P.flavour, pl.search_wpitch, pl.pair_off);
+    auto* search = pl.nsq ? me_frame_search_kernel<true> : me_frame_search_kernel<false>;
+    hipLaunchKernelGGL(search, grid, dim3(ME_THREADS), pl.search.lds, s, d, pl.max_w, pl.max_h, P.flavour, pl.search.wpitch, pl.search.pair_off);
     if (int rc = launch_status("me_frame_search")) return rc;
     if (subpel) {
         if (int rc = me_subpel_enqueue_refine(src, ref0, ref1, params, sp, n_pictures, d_best_sad, d_best_mv, nullptr, nullptr, s)) return rc;

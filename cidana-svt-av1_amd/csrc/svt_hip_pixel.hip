@@ -3,6 +3,7 @@
 #include "host_common.h"
 #include "kernel_me.h"
 #include "kernel_pixel.h"
+#include "search_plan.h"
 
 using namespace svtdev;
 using namespace svthost;
@@ -98,158 +99,52 @@ extern "C" int svt_hip_residual16_batch(const uint16_t* d_src, uint32_t src_stri
                                    res_block_pitch, width, height, nblocks, stream);
 }
 
-static int sad_search_impl(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs,
-                           const uint8_t* d_ref, uint32_t ref_stride, uint32_t ref_stride_raw,
-                           size_t ref_block_pitch, const uint32_t* d_ref_offs, uint32_t width, uint32_t height,
-                           int16_t search_area_width, int16_t search_area_height,
-                           uint64_t* d_best_sad, int16_t* d_x, int16_t* d_y, size_t nblocks,
-                           void* stream) {
+static int sad_search_impl(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs, const uint8_t* d_ref,
+                           uint32_t ref_stride, uint32_t ref_stride_raw, size_t ref_block_pitch, const uint32_t* d_ref_offs, uint32_t width, uint32_t height,
+                           int16_t search_area_width, int16_t search_area_height, uint64_t* d_best_sad, int16_t* d_x, int16_t* d_y, size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
     if (!d_src || !d_ref || !d_best_sad || !d_x || !d_y) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (width == 0 || height == 0 || width > 64 || height > 64) return set_err(SVT_HIP_ERR_INVALID, "block %ux%u", width, height);
-    if (search_area_width <= 0 || search_area_height <= 0) return set_err(SVT_HIP_ERR_INVALID, "empty search area");
-    if (nblocks == 0) return SVT_HIP_OK;
-    const uint32_t win_w = width + search_area_width - 1;
-    const bool plain = ref_stride == ref_stride_raw;
-    const uint32_t nrows = plain ? (uint32_t)(search_area_height + height - 1) : (uint32_t)search_area_height * height;
-    const bool q16_for_16x16 = !g_tune_no_q16 && width == 16 && search_area_width % 16 == 0;      // see the q16 routing below
-    if (plain && !g_tune_no_qsad && !g_tune_no_q2 && ((width == 16 && height == 16 && !q16_for_16x16) || (width == 8 && height == 8))) {
-        // small blocks: source block in registers, 4 x 2 candidates per lane
-        const uint32_t wpitch = ((win_w + 15) & ~15u) + 16;
-        const uint32_t src_bytes = (width * height + 15) & ~15u;
-        const uint32_t groups = (uint32_t)((search_area_width + 3) / 4) * (uint32_t)((search_area_height + 1) / 2);
-        uint32_t lpb = 1;
-        while (lpb < groups && lpb < 64) lpb <<= 1;
-        // window + one spare row + 16 spare bytes per lane, padded to 8 (mod 32) bytes (LDS bank spread, see the kernel)
-        uint32_t ref_bytes = wpitch * (nrows + 1) + 16 * lpb;
-        ref_bytes = ((ref_bytes + 31) & ~31u) + 8;
-        const uint32_t per_blk = src_bytes + ref_bytes;
-        if (per_blk <= 64 * 1024) {
-            uint32_t threads = 256;
-            while (threads > lpb && (size_t)(threads / lpb) * per_blk > 64 * 1024) threads >>= 1;
-            const uint32_t slots = threads / lpb;
-            const uint32_t grid = (uint32_t)((nblocks + slots - 1) / slots);
-#define SSQ2(CW, CH, SU)                                                                                                \
-    hipLaunchKernelGGL((sad_search_q2_kernel<CW, CH, SU>), dim3(grid), dim3(threads), (size_t)slots * per_blk, (hipStream_t)stream, \
-                       d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, (int)search_area_width,         \
-                       (int)search_area_height, (unsigned long long*)d_best_sad, d_x, d_y, ref_bytes, lpb, cpr_magic,           \
-                       d_src_offs, d_ref_offs, (uint32_t)nblocks)
-            // exact j / cpr for j < 2^16 chunks (cpr <= 8): floor(2^32 / cpr) + 1
-            const uint32_t cpr_magic = (uint32_t)(0x100000000ull / ((win_w + 15) >> 4)) + 1u;
-            // staging depth: all of a lane's chunks in ONE batch of loads when that takes at most 8 per lane (one memory
-            // latency per block instead of two: the kernel is latency-bound at 3 waves per SIMD)
-            const uint32_t nchunk = ((win_w + 15) >> 4) * nrows;
-            const bool deep = !g_tune_q2_su4 && nchunk > 4 * lpb;
-            // persistent, software-pipelined form (loads of the next set of blocks in flight during the search): whenever a
-            // lane's share of one block's chunks fits 8 registers-of-16-B
-            const uint32_t nsrc_chunks = width * height / (width % 16 == 0 ? 16u : 8u);
-            if (!g_tune_no_q2p && nsrc_chunks + nchunk <= 8 * lpb && search_area_width <= 256 && search_area_height <= 256) {
-                // LDS per block: source + 16 B, window rows at 16 * cpr + 8 bytes, block stride == 64 (mod 128) (bank spread, see the kernel)
-                const uint32_t cpr = (win_w + 15) >> 4, wpitch_p = 16 * cpr + 8;
-                uint32_t wstride = wpitch_p * nrows + 8;
-                wstride = ((wstride + 63) & ~127u) + 64;
-                if (wstride < wpitch_p * nrows + 8) wstride += 128;
-                const uint32_t per_blk_p = src_bytes + 16 + wstride;
-                uint32_t pthreads = 256;
-                while (pthreads > 64 && (size_t)(pthreads / lpb) * per_blk_p > 64 * 1024) pthreads >>= 1;
-                const uint32_t pslots = pthreads / lpb, pwaves = pthreads / 64;
-                const size_t plds = (size_t)pslots * per_blk_p;
-                if (lpb <= 64 && pslots >= pwaves && plds <= 64 * 1024) {
-                    const uint32_t nsets = (uint32_t)((nblocks + 64 / lpb - 1) / (64 / lpb));
-                    const uint32_t wg_per_cu = (uint32_t)(160 * 1024 / plds);
-                    const uint32_t by_waves = 16 / pwaves;                       // 4 waves per SIMD (124 VGPRs)
-                    uint32_t pgrid = (uint32_t)g_num_cu * (wg_per_cu < by_waves ? (wg_per_cu ? wg_per_cu : 1) : by_waves);
-                    const uint32_t need = (nsets + pwaves - 1) / pwaves;
-                    if (pgrid > need) pgrid = need;
-#define SSQ2P(CW, CH)                                                                                                   \
-    hipLaunchKernelGGL((sad_search_q2p_kernel<CW, CH>), dim3(pgrid), dim3(pthreads), plds, (hipStream_t)stream,                     \
-                       d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, (int)search_area_width,         \
-                       (int)search_area_height, (unsigned long long*)d_best_sad, d_x, d_y, wstride, wpitch_p, lpb, cpr_magic,    \
-                       d_src_offs, d_ref_offs, (uint32_t)nblocks)
-                    if (width == 16) SSQ2P(16, 16); else SSQ2P(8, 8);
-#undef SSQ2P
-                    return launch_status("sad_search_q2p");
-                }
-            }
-            if (width == 16) { if (deep) SSQ2(16, 16, 8); else SSQ2(16, 16, 4); }
-            else { if (deep) SSQ2(8, 8, 8); else SSQ2(8, 8, 4); }
-#undef SSQ2
-            return launch_status("sad_search_q2");
-        }
-    }
-    // 16-wide blocks: 16x32 / 16x64 always (measured 2.1-2.3x over sad_search_q_kernel); 16x16 when no candidate
-    // of a lane is masked (search width % 16 == 0: 10 % over q2, equal otherwise)
-    if (plain && !g_tune_no_qsad && !g_tune_no_q16 && height % (256 / (width ? width : 1)) == 0 &&
-        (width == 32 || width == 64 || (width == 16 && (height != 16 || search_area_width % 16 == 0)))) {
-        // wide blocks: 16 candidates per lane on b128 LDS reads (sad_search_q16_kernel)
-        uint32_t wpitch = (((uint32_t)search_area_width + 15) & ~15u) + width;
-        if (((wpitch >> 4) & 1) == 0) wpitch += 16;            // odd multiple of 16 B: bank spread over search rows
-        const uint32_t ref_bytes = wpitch * nrows;
-        const uint32_t per_blk = width * height + ref_bytes;
-        if (per_blk <= 64 * 1024) {
-            const uint32_t tasks = (uint32_t)((search_area_width + 15) / 16) * (uint32_t)search_area_height;
-            uint32_t tsh = 0;
-            while ((1u << tsh) < tasks && tsh < 6) tsh++;
-            const uint32_t row_groups = height / (256 / width);
-            uint32_t lpb = 1u << tsh;
-            while (lpb < 64 && (lpb >> tsh) * 2 <= row_groups) lpb <<= 1;
-            uint32_t threads = 256;
-            while (threads > lpb && (size_t)(threads / lpb) * per_blk > 64 * 1024) threads >>= 1;
-            const uint32_t slots = threads / lpb;
-            const uint32_t grid = (uint32_t)((nblocks + slots - 1) / slots);
-            const uint32_t cpr_magic = (uint32_t)(0x100000000ull / ((win_w + 15) >> 4)) + 1u;
-#define SSQ16(CW)                                                                                                       \
-    hipLaunchKernelGGL((sad_search_q16_kernel<CW>), dim3(grid), dim3(threads), (size_t)slots * per_blk, (hipStream_t)stream, \
-                       d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, height, (int)search_area_width,  \
-                       (int)search_area_height, (unsigned long long*)d_best_sad, d_x, d_y, wpitch, ref_bytes, lpb, tsh,         \
-                       cpr_magic, d_src_offs, d_ref_offs, (uint32_t)nblocks)
-            if (width == 16) SSQ16(16); else if (width == 32) SSQ16(32); else SSQ16(64);
-#undef SSQ16
-            return launch_status("sad_search_q16");
-        }
-    }
-    if ((width & 3) == 0 && !g_tune_no_qsad) {
-        // quad-SAD kernel: 4 candidates per lane
-        const uint32_t wpitch = ((win_w + 15) & ~15u) + 16;
-        const uint32_t src_bytes = (width * height + 15) & ~15u;
-        const uint32_t ref_bytes = (wpitch * nrows + 16 + 15) & ~15u;
-        const uint32_t per_blk = src_bytes + ref_bytes;
-        if (per_blk > 64 * 1024) return set_err(SVT_HIP_ERR_INVALID, "search window needs %u B of LDS per block (> 64 KiB)", per_blk);
-        const uint32_t groups = (uint32_t)((search_area_width + 3) / 4) * (uint32_t)search_area_height;
-        uint32_t lpb = 1;
-        while (lpb < groups && lpb < 64) lpb <<= 1;
-        uint32_t threads = 256;
-        while (threads > lpb && (size_t)(threads / lpb) * per_blk > 64 * 1024) threads >>= 1;
-        const uint32_t slots = threads / lpb;
-        const uint32_t grid = (uint32_t)((nblocks + slots - 1) / slots);
-#define SSQ(CW, CH)                                                                                                     \
-    hipLaunchKernelGGL((sad_search_q_kernel<CW, CH>), dim3(grid), dim3(threads), (size_t)slots * per_blk, (hipStream_t)stream, \
-                       d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_stride_raw, ref_block_pitch, width, height,  \
-                       (int)search_area_width, (int)search_area_height, (unsigned long long*)d_best_sad, d_x, d_y, src_bytes, \
-                       ref_bytes, lpb, d_src_offs, d_ref_offs, (uint32_t)nblocks)
-        if (width == 16 && height == 16) SSQ(16, 16);
-        else if (width == 8 && height == 8) SSQ(8, 8);
-        else if (width == 32 && height == 32) SSQ(32, 32);
-        else if (width == 64 && height == 64) SSQ(64, 64);
-        else SSQ(0, 0);
-#undef SSQ
+    // the kernel, its variant, the launch shape and the LDS layout: search_plan.h
+    const SadSearchKnobs knobs = {g_tune_no_qsad, g_tune_no_q2, g_tune_no_q2p, g_tune_no_q16, g_tune_q2_su4};
+    SadSearchPlan p;
+    if (int rc = sad_search_plan(width, height, search_area_width, search_area_height, ref_stride == ref_stride_raw, nblocks, knobs, g_num_cu, p)) return rc;
+    const int sw = search_area_width, sh = search_area_height;
+    unsigned long long* best = (unsigned long long*)d_best_sad;
+    const uint32_t n = (uint32_t)nblocks;
+#define SSL(KERNEL, ...) hipLaunchKernelGGL((KERNEL), dim3(p.grid), dim3(p.threads), p.lds, (hipStream_t)stream, __VA_ARGS__, d_src_offs, d_ref_offs, n)
+#define SSQ(CW, CH) SSL((sad_search_q_kernel<CW, CH>), d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_stride_raw, ref_block_pitch, width, height, sw, sh, \
+                        best, d_x, d_y, p.src_bytes, p.ref_bytes, p.lpb)
+#define SSQ16(CW) SSL(sad_search_q16_kernel<CW>, d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, height, sw, sh, best, d_x, d_y, p.wpitch, \
+                      p.ref_bytes, p.lpb, p.tsh, p.cpr_magic)
+#define SSQ2(CW, CH, SU) SSL((sad_search_q2_kernel<CW, CH, SU>), d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, sw, sh, best, d_x, d_y, \
+                             p.ref_bytes, p.lpb, p.cpr_magic)
+#define SSQ2P(CW, CH) SSL((sad_search_q2p_kernel<CW, CH>), d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, sw, sh, best, d_x, d_y, p.wstride, \
+                          p.wpitch, p.lpb, p.cpr_magic)
+    switch (p.kernel) {
+    case SAD_K_Q2P:
+        if (p.cw == 16) SSQ2P(16, 16); else SSQ2P(8, 8);
+        return launch_status("sad_search_q2p");
+    case SAD_K_Q2:
+        if (p.cw == 16) { if (p.su == 8) SSQ2(16, 16, 8); else SSQ2(16, 16, 4); }
+        else { if (p.su == 8) SSQ2(8, 8, 8); else SSQ2(8, 8, 4); }
+        return launch_status("sad_search_q2");
+    case SAD_K_Q16:
+        if (p.cw == 16) SSQ16(16); else if (p.cw == 32) SSQ16(32); else SSQ16(64);
+        return launch_status("sad_search_q16");
+    case SAD_K_Q:
+        if (p.cw == 16) SSQ(16, 16); else if (p.cw == 8) SSQ(8, 8); else if (p.cw == 32) SSQ(32, 32); else if (p.cw == 64) SSQ(64, 64); else SSQ(0, 0);
         return launch_status("sad_search_q");
+    default:
+        SSL(sad_search_kernel, d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_stride_raw, ref_block_pitch, width, height, sw, sh, best, d_x, d_y,
+            p.src_bytes, p.ref_bytes);
+        return launch_status("sad_search");
     }
-    const uint32_t wpitch = (win_w + 3 + 8) & ~3u;
-    const uint32_t spitch = (width + 3) & ~3u;
-    const uint32_t src_bytes = (spitch * height + 15) & ~15u;
-    const uint32_t ref_bytes = (wpitch * nrows + 16 + 15) & ~15u;
-    const uint32_t per_wave = src_bytes + ref_bytes;
-    if (per_wave > 64 * 1024) return set_err(SVT_HIP_ERR_INVALID, "search window needs %u B of LDS per block (> 64 KiB)", per_wave);
-    uint32_t waves = (64 * 1024) / per_wave;
-    if (waves > 4) waves = 4;
-    const uint32_t grid = (uint32_t)((nblocks + waves - 1) / waves);
-    hipLaunchKernelGGL(sad_search_kernel, dim3(grid), dim3(waves * 64), waves * per_wave, (hipStream_t)stream, d_src,
-                       src_stride, src_block_pitch, d_ref, ref_stride, ref_stride_raw, ref_block_pitch, width, height,
-                       (int)search_area_width, (int)search_area_height, (unsigned long long*)d_best_sad, d_x, d_y,
-                       src_bytes, ref_bytes, d_src_offs, d_ref_offs, (uint32_t)nblocks);
-    return launch_status("sad_search");
+#undef SSQ2P
+#undef SSQ2
+#undef SSQ16
+#undef SSQ
+#undef SSL
 }
 
 extern "C" int svt_hip_sad_search_batch(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch,
@@ -272,16 +167,16 @@ extern "C" int svt_hip_sad_search_planes_batch(const uint8_t* d_src_plane, uint3
                            width, height, search_area_width, search_area_height, d_best_sad, d_x, d_y, nblocks, stream);
 }
 
-// Row pitch of the reference window the motion-search kernels stage in LDS: whole 16-byte chunks + one chunk of slack for the
-// sliding reads, and == 64 (mod 128) so that the lanes of consecutive SEARCH ROWS fall on different halves of the 32 banks.  A
-// wave's b128 reads are served eight lanes at a time - four 16-point groups of one search row and four of the next - and with
-// the first pitch (144 B for a 64-wide area, == 16 mod 128) the second row's lanes landed on the first row's banks: 31 % of the
-// kernel's LDS cycles were bank conflicts (profiles/r03_a_pmc_me_sb.json); the 4-points-per-lane kernel's dword reads (16 lanes
-// per search row) collide the same way.
-uint32_t svthost::me_window_pitch(uint32_t win_w) {
-    uint32_t p = ((win_w + 15) & ~15u) + 16;
-    while ((p & 127) != 64) p += 16;
-    return p;
+// me_sb_search16_kernel for a window me_window (search_plan.h) accepted: 16 points per lane; widths that are not a multiple of 16 mask the
+// tail of each row.  w8q, ref_layout, pu_pitch: the reference's result layout (kernel_me_steps.h)
+static void launch_me_sb_search16(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs, const uint8_t* d_ref,
+                                  uint32_t ref_stride, size_t ref_block_pitch, const uint32_t* d_ref_offs, int search_w, int search_h,
+                                  const int16_t* d_origins, int x_origin, int y_origin, uint32_t* d_best_sad, uint32_t* d_best_mv, const MeWindow& w,
+                                  size_t nblocks, int w8q, int ref_layout, uint32_t pu_pitch, void* stream) {
+    auto* kernel = (search_w & 15) == 0 ? me_sb_search16_kernel<false> : me_sb_search16_kernel<true>;
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)nblocks), dim3(ME_THREADS), w.lds, (hipStream_t)stream, d_src, src_stride, src_block_pitch, d_ref, ref_stride,
+                       ref_block_pitch, search_w, search_h, d_origins, x_origin, y_origin, d_best_sad, d_best_mv, w.wpitch, d_src_offs, d_ref_offs,
+                       (uint32_t)nblocks, w8q, ref_layout, pu_pitch);
 }
 
 static int me_sb_search_impl(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs,
@@ -292,21 +187,10 @@ static int me_sb_search_impl(const uint8_t* d_src, uint32_t src_stride, size_t s
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
     if (!d_src || !d_ref || !d_best_sad || !d_best_mv) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (search_w <= 0 || search_h <= 0 || search_w * search_h > 4096)
-        return set_err(SVT_HIP_ERR_INVALID, "search area %dx%d (1..4096 points)", search_w, search_h);
-    const uint32_t win_w = 64 + search_w - 1, win_h = 64 + search_h - 1;
-    const uint32_t wpitch = me_window_pitch(win_w);
-    const size_t lds = 32 * 64 + (size_t)wpitch * win_h;
-    if (lds > 60 * 1024) return set_err(SVT_HIP_ERR_INVALID, "search window needs %zu B of LDS (> 60 KiB)", lds);
-    // 16 points per lane; widths that are not a multiple of 16 mask the tail of each row
-    if ((search_w & 15) == 0)
-        hipLaunchKernelGGL(me_sb_search16_kernel<false>, dim3((uint32_t)nblocks), dim3(ME_THREADS), lds, (hipStream_t)stream, d_src,
-                           src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, search_w, search_h, d_origins,
-                           x_origin, y_origin, d_best_sad, d_best_mv, wpitch, d_src_offs, d_ref_offs, (uint32_t)nblocks);
-    else
-        hipLaunchKernelGGL(me_sb_search16_kernel<true>, dim3((uint32_t)nblocks), dim3(ME_THREADS), lds, (hipStream_t)stream, d_src,
-                           src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, search_w, search_h, d_origins,
-                           x_origin, y_origin, d_best_sad, d_best_mv, wpitch, d_src_offs, d_ref_offs, (uint32_t)nblocks);
+    MeWindow w;
+    if (int rc = me_window_check(search_w, search_h, 0, ME_LDS_MAX, w)) return rc;
+    launch_me_sb_search16(d_src, src_stride, src_block_pitch, d_src_offs, d_ref, ref_stride, ref_block_pitch, d_ref_offs, search_w, search_h, d_origins,
+                          x_origin, y_origin, d_best_sad, d_best_mv, w, nblocks, 0, 0, ME_PUS, stream);
     return launch_status("me_sb_search16");
 }
 
@@ -342,27 +226,18 @@ extern "C" int svt_hip_hme_level_regions_batch(const uint8_t* d_src_pic, uint32_
     HmeParamSets hp;
     static_assert(sizeof(HmeParams) == sizeof(svt_hip_hme_params), "layout");
     memset(&hp, 0, sizeof(hp));
-    size_t lds = 0;
-    uint32_t wpitch = 0;
     for (int r = 0; r < nregions; r++) {
         const svt_hip_hme_params& P = params[r];
         if (P.search_area_width < 1 || P.search_area_height < 1 || (P.round_down != 8 && P.round_down != 16) || P.mv_shift < 0 || P.mv_shift > 2 ||
             P.ref_width < 1 || P.ref_height < 1)
             return set_err(SVT_HIP_ERR_INVALID, "HME parameters: area %dx%d, round_down %d, mv_shift %d", P.search_area_width, P.search_area_height,
                            P.round_down, P.mv_shift);
-        // the clipped area never exceeds the nominal one; blocks are at most 64 x 64 (32 compared rows)
-        const uint32_t win_w = 64 + (uint32_t)P.search_area_width - 1;
-        const uint32_t wp = ((win_w + 3) & ~3u) + 8;
-        if (wp > wpitch) wpitch = wp;
         memcpy(&hp.p[r], &P, sizeof(HmeParams));
     }
-    for (int r = 0; r < nregions; r++) {
-        const size_t need = 32 * 64 + (size_t)wpitch * ((uint32_t)params[r].search_area_height + 62);
-        if (need > lds) lds = need;
-    }
-    if (lds > 60 * 1024) return set_err(SVT_HIP_ERR_INVALID, "HME search window needs %zu B of LDS (> 60 KiB)", lds);
-    hipLaunchKernelGGL(hme_level_kernel, dim3((uint32_t)ntasks, (uint32_t)nregions), dim3(ME_THREADS), lds, (hipStream_t)stream, d_src_pic, src_stride,
-                       d_ref_pic, ref_stride, d_sb_origin, d_sb_size, d_centers, center_shift, hp, (unsigned long long*)d_best_sad, d_mv, wpitch,
+    HmeWindow w;
+    if (int rc = hme_window(params, nregions, w)) return rc;
+    hipLaunchKernelGGL(hme_level_kernel, dim3((uint32_t)ntasks, (uint32_t)nregions), dim3(ME_THREADS), w.lds, (hipStream_t)stream, d_src_pic, src_stride,
+                       d_ref_pic, ref_stride, d_sb_origin, d_sb_size, d_centers, center_shift, hp, (unsigned long long*)d_best_sad, d_mv, w.wpitch,
                        (uint32_t)ntasks);
     return launch_status("hme_level");
 }
@@ -387,40 +262,22 @@ extern "C" int svt_hip_me_fullpel_search_batch(const uint8_t* d_src, uint32_t sr
     if (flavour != SVT_HIP_FLAVOUR_C && flavour != SVT_HIP_FLAVOUR_AVX2) return set_err(SVT_HIP_ERR_INVALID, "flavour %d", flavour);
     const uint32_t npus = nsq ? SVT_HIP_ME_PUS_ALL : SVT_HIP_ME_PUS;
     if (pu_pitch < npus) return set_err(SVT_HIP_ERR_INVALID, "pu_pitch %u < %u PUs", pu_pitch, npus);
-    if (search_w <= 0 || search_h <= 0 || search_w * search_h > 4096)
-        return set_err(SVT_HIP_ERR_INVALID, "search area %dx%d (1..4096 points)", search_w, search_h);
-    if (!nsq && !g_tune_me_exact) {
+    MeWindow w;
+    if (int rc = me_window(search_w, search_h, 0, w)) return rc;
+    if (!nsq && !g_tune_me_exact && w.lds <= ME_LDS_MAX) {
         // square PUs: the 16-points-per-lane kernel, any width; the AVX2 flavour only re-labels the 32x32 keys
-        const uint32_t win_w = 64 + search_w - 1, win_h = 64 + search_h - 1;
-        const uint32_t wpitch = me_window_pitch(win_w);
-        const size_t lds = 32 * 64 + (size_t)wpitch * win_h;
-        if (lds <= 60 * 1024) {
-            const int w8q = flavour == SVT_HIP_FLAVOUR_AVX2 ? (search_w & ~7) : 0;
-            if ((search_w & 15) == 0)
-                hipLaunchKernelGGL(me_sb_search16_kernel<false>, dim3((uint32_t)nblocks), dim3(ME_THREADS), lds, (hipStream_t)stream, d_src,
-                                   src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, search_w, search_h, d_origins,
-                                   x_origin, y_origin, d_best_sad, d_best_mv, wpitch, d_src_offsets, d_ref_offsets, (uint32_t)nblocks,
-                                   w8q, 1, pu_pitch);
-            else
-                hipLaunchKernelGGL(me_sb_search16_kernel<true>, dim3((uint32_t)nblocks), dim3(ME_THREADS), lds, (hipStream_t)stream, d_src,
-                                   src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, search_w, search_h, d_origins,
-                                   x_origin, y_origin, d_best_sad, d_best_mv, wpitch, d_src_offsets, d_ref_offsets, (uint32_t)nblocks,
-                                   w8q, 1, pu_pitch);
-            return launch_status("me_sb_search16 (reference layout)");
-        }
+        launch_me_sb_search16(d_src, src_stride, src_block_pitch, d_src_offsets, d_ref, ref_stride, ref_block_pitch, d_ref_offsets, search_w, search_h,
+                              d_origins, x_origin, y_origin, d_best_sad, d_best_mv, w, nblocks, flavour == SVT_HIP_FLAVOUR_AVX2 ? (search_w & ~7) : 0, 1,
+                              pu_pitch, stream);
+        return launch_status("me_sb_search16 (reference layout)");
     }
-    if (nsq && !g_tune_me_exact && (search_w & 7) == 0) {
+    if (nsq && !g_tune_me_exact && (search_w & 7) == 0 && w.lds <= ME_NSQ_LDS_MAX) {
         // all 209 PUs, widths where every point takes the reference's eight-point form: 4 points per lane, every shape folded
         // out of the packed 8x8 SADs (me_nsq4_kernel); other widths keep the exact kernel (single-point quirks)
-        const uint32_t win_w = 64 + search_w - 1, win_h = 64 + search_h - 1;
-        const uint32_t wpitch = me_window_pitch(win_w);
-        const size_t lds = 32 * 64 + (size_t)wpitch * win_h;
-        if (lds <= 58 * 1024) {
-            hipLaunchKernelGGL(me_nsq4_kernel, dim3((uint32_t)nblocks), dim3(ME_THREADS), lds, (hipStream_t)stream, d_src, src_stride,
-                               src_block_pitch, d_ref, ref_stride, ref_block_pitch, search_w, search_h, d_origins, x_origin, y_origin,
-                               d_best_sad, d_best_mv, wpitch, d_src_offsets, d_ref_offsets, (uint32_t)nblocks, pu_pitch);
-            return launch_status("me_nsq4");
-        }
+        hipLaunchKernelGGL(me_nsq4_kernel, dim3((uint32_t)nblocks), dim3(ME_THREADS), w.lds, (hipStream_t)stream, d_src, src_stride,
+                           src_block_pitch, d_ref, ref_stride, ref_block_pitch, search_w, search_h, d_origins, x_origin, y_origin,
+                           d_best_sad, d_best_mv, w.wpitch, d_src_offsets, d_ref_offsets, (uint32_t)nblocks, pu_pitch);
+        return launch_status("me_nsq4");
     }
     hipLaunchKernelGGL(me_fullpel_exact_kernel, dim3((uint32_t)nblocks), dim3(ME_THREADS), 0, (hipStream_t)stream, d_src, src_stride,
                        src_block_pitch, d_src_offsets, d_ref, ref_stride, ref_block_pitch, d_ref_offsets, search_w, search_h,
@@ -464,26 +321,12 @@ extern "C" int svt_hip_me_fullpel_search_areas_batch(const uint8_t* d_src, uint3
     if (flavour != SVT_HIP_FLAVOUR_C && flavour != SVT_HIP_FLAVOUR_AVX2) return set_err(SVT_HIP_ERR_INVALID, "flavour %d", flavour);
     const uint32_t npus = nsq ? SVT_HIP_ME_PUS_ALL : SVT_HIP_ME_PUS;
     if (pu_pitch < npus) return set_err(SVT_HIP_ERR_INVALID, "pu_pitch %u < %u PUs", pu_pitch, npus);
-    if (max_search_w <= 0 || max_search_h <= 0 || max_search_w * max_search_h > 4096)
-        return set_err(SVT_HIP_ERR_INVALID, "search area bound %dx%d (1..4096 points)", max_search_w, max_search_h);
     if (nblocks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks");
-    const uint32_t win_w = 64 + max_search_w - 1, win_h = 64 + max_search_h - 1;
-    const uint32_t wpitch = me_window_pitch(win_w);
-    size_t lds = 32 * 64 + (size_t)wpitch * win_h;
-    uint32_t pair_off = 0;
-    if (nsq) {                                            // (64x32_1, 32x16_5) pairs of the narrow single-point areas: <= 7 x max_h points
-        pair_off = (uint32_t)((lds + 15) & ~(size_t)15);
-        lds = pair_off + (size_t)8 * 7 * max_search_h;
-    }
-    if (lds > 58 * 1024) return set_err(SVT_HIP_ERR_INVALID, "search window of %dx%d needs %zu B of LDS (> 58 KiB)", max_search_w, max_search_h, lds);
-    if (nsq)
-        hipLaunchKernelGGL(me_fullpel_areas_kernel<true>, dim3((uint32_t)nblocks), dim3(ME_THREADS), lds, (hipStream_t)stream, d_src, src_stride, d_src_offsets,
-                           d_ref, ref_stride, d_ref_offsets, d_areas, max_search_w, max_search_h, flavour, d_best_sad, d_best_mv, pu_pitch, wpitch,
-                           pair_off, (uint32_t)nblocks);
-    else
-        hipLaunchKernelGGL(me_fullpel_areas_kernel<false>, dim3((uint32_t)nblocks), dim3(ME_THREADS), lds, (hipStream_t)stream, d_src, src_stride, d_src_offsets,
-                           d_ref, ref_stride, d_ref_offsets, d_areas, max_search_w, max_search_h, flavour, d_best_sad, d_best_mv, pu_pitch, wpitch,
-                           pair_off, (uint32_t)nblocks);
+    MeWindow w;                                           // sized by the bound of the areas; nsq: with the single-point areas' pairs
+    if (int rc = me_window_check(max_search_w, max_search_h, nsq, ME_NSQ_LDS_MAX, w)) return rc;
+    auto* kernel = nsq ? me_fullpel_areas_kernel<true> : me_fullpel_areas_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)nblocks), dim3(ME_THREADS), w.lds, (hipStream_t)stream, d_src, src_stride, d_src_offsets, d_ref, ref_stride,
+                       d_ref_offsets, d_areas, max_search_w, max_search_h, flavour, d_best_sad, d_best_mv, pu_pitch, w.wpitch, w.pair_off, (uint32_t)nblocks);
     return launch_status("me_fullpel_areas");
 }
 

@@ -317,6 +317,26 @@ def test_sad_search(dsp, w, h, sw, sh):
         assert (int(best[i]), int(x[i]), int(y[i])) == (int(rb[0]), int(rx[0]), int(ry[0])), f"block {i}"
 
 
+@pytest.mark.parametrize("w,h,sw,sh", [(16, 16, 8, 4), (24, 24, 5, 3)])
+def test_sad_search_line_skipping(dsp, w, h, sw, sh):
+    """sad_loop_kernel as HME calls it, for a batch: ref_stride = 2 * ref_stride_raw, so candidate row ys compares window rows ys, ys + 2, ..
+    and the window staged per block has search_h * height rows"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(w + 7 * sw)
+    n = 5
+    rw, rh = w + sw - 1, sh + 2 * h - 2
+    src = rng.integers(0, 256, size=(n, h, w), dtype=np.uint8)
+    ref = rng.integers(0, 256, size=(n, rh, rw), dtype=np.uint8)
+    ref[0] = 7; src[0] = 9                                   # ties everywhere: (0, 0)
+    ref[1, 2:2 + 2 * h:2, 3:3 + w] = src[1]                  # an exact match at (3, 2), on every other row
+    best, x, y = (t.cpu().numpy() for t in dsp.sad_search(dev(src), dev(ref), sw, sh, ref_stride=2 * rw, ref_stride_raw=rw))
+    for i in range(n):
+        rb = np.zeros(1, np.uint64); rx = np.zeros(1, np.int16); ry = np.zeros(1, np.int16)
+        O.svt_oracle_sad_loop(ptr(src[i]), w, ptr(ref[i]), 2 * rw, h, w, ptr(rb), ptr(rx), ptr(ry), rw, ctypes.c_int16(sw), ctypes.c_int16(sh))
+        assert (int(best[i]), int(x[i]), int(y[i])) == (int(rb[0]), int(rx[0]), int(ry[0])), f"block {i}"
+    assert (int(best[1]), int(x[1]), int(y[1])) == (0, 3, 2)
+
+
 # ---------------------------------------------------------------------------------------
 # intra prediction (no reference unit test exists: SURVEY F5 — oracle is pinned by the
 # reference's scalar C functions, tests/test_oracle_vs_ref.py + tests/golden/intra.npz)
