@@ -59,6 +59,9 @@ constexpr bool tx_type_ok(int tx_size, int tx_type) {
     return tx_size >= 0 && tx_size < SVT_TX_SIZES_ALL && tx_type >= 0 && tx_type_ok_sides((uint32_t)kTxW[tx_size], (uint32_t)kTxH[tx_size], (uint32_t)tx_type);
 }
 
+// the quantiser's log_scale of a transform size (av1_get_tx_scale): 1 above 256 pixels, 2 above 1024
+constexpr int tx_log_scale(int tx_size) { return kTxW[tx_size] * kTxH[tx_size] > 1024 ? 2 : (kTxW[tx_size] * kTxH[tx_size] > 256 ? 1 : 0); }
+
 // the launch kind of a transform size: 0 = both sides up to 16, 1 = a 32-sample side, 2 = a 64-sample side except 64x64, 3 = 64x64.
 // 0 and 3 are register classes 0 and 2 of kernel_txfm_staged.h, 1 and 2 the two halves of its class 1 (asserted there, against the
 // lists SVT_TX_CLASS0 / 1A / 1B): the nine bodies of class 1 in one function left their register arrays in scratch in the kernels

@@ -15,6 +15,7 @@
 #include "group_table.h"
 #include "host_err.h"
 #include "md_plan.h"
+#include "tx_plan.h"
 
 namespace svthost {
 static_assert(kGroupTooLarge == SVT_HIP_ERR_INVALID, "group_table.h");
@@ -49,6 +50,11 @@ extern int g_tune_frame_single_launch;
 extern int g_tune_inv32_waves;
 extern int g_tune_inv32_var;
 extern int g_tune_recon_final_bin_only;
+// the knobs the transform family's plans read (tx_plan.h): filled from the globals here and nowhere else
+inline TxKnobs tx_knobs() {
+    return TxKnobs{g_tune_no_staged, g_tune_no_f32p, g_tune_no_inv_planes, g_tune_no_enc_staged, g_tune_no_enc64, g_tune_f32_wg_per_cu, g_tune_f32_nt,
+                   g_tune_f32_qmode1, g_tune_inv32_waves, g_tune_inv32_var, g_tune_frame_single_launch};
+}
 
 #define HIP_TRY(expr)                                                                            \
     do {                                                                                         \
@@ -77,12 +83,6 @@ int me_subpel_enqueue_bipred(const svt_hip_me_pyramid* src, const svt_hip_me_pyr
 // svt_hip_frame.hip: the one-launch form of svt_hip_encode_recon_frame (its kernel lives in a translation unit of its own)
 int launch_enc_frame_one(const svtdev::FrameDesc* fd, uint32_t total_wgs, int is_16bit, hipStream_t s);
 
-// blocks per workgroup of a staged body (enc_staged_body, full_loop_body): StagedGeom<W, H>::WAVES waves of TxGeom<W, H>::BPW blocks
-inline uint32_t staged_blocks_per_wg(int tx_size) {
-    const int w = kTxW[tx_size], h = kTxH[tx_size], m = w > h ? w : h;
-    return (uint32_t)((w * h >= 4096 ? 2 : 4) * (64 / m));
-}
-int frame_groups_check(const svt_hip_frame_group* groups, int ngroups);      // svt_hip_txfm.hip
 // The launches of the mode-decision stages for groups their *_check (md_plan.h) accepted: the group-table fill and the launches, nothing
 // validated.  Every public entry point is require_init, check, enqueue; the composed calls (svt_hip_tx_search_frame,
 // svt_hip_intra_fast_search_frame, svt_hip_cfl_search_frame, svt_hip_cfl_pick_frame, svt_hip_md_search_frame) check every stage, then enqueue every stage.

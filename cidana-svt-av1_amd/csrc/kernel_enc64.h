@@ -21,6 +21,7 @@
 namespace svtdev {
 
 constexpr int E64_WAVES = 2;
+static_assert(E64_WAVES == svthost::kE64Waves && 2 * E64_WAVES == svthost::kE64BlocksPerWg, "tx_plan.h plans the grids of the 64x64 pair kernels");
 constexpr int E64_TILE = 32 * 65 * 4;            // 8320
 constexpr int E64_WAVE_LDS = 2 * E64_TILE;
 

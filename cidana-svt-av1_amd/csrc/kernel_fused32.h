@@ -48,10 +48,12 @@
 #pragma once
 #include "dev_common.h"
 #include "gen/txfm1d_gen.h"
+#include "tx_plan.h"
 
 namespace svtdev {
 
 constexpr int F32_WAVES = 4;                 // waves per workgroup
+static_assert(F32_WAVES == svthost::kF32Waves && svthost::f32_blocks_per_wg() == 2 * F32_WAVES, "tx_plan.h plans the grids of the 32x32 pair kernels");
 constexpr int F32_TILE_WORDS = 1024;         // one 32x32 int32 tile per block
 constexpr int F32_COS_BIT = 12;              // fwd_cos_bit_col/row[3][3] (EbTransforms.h:141-156)
 

@@ -1,6 +1,7 @@
 // kernel_quant.h — K3: stand-alone quantize / dequantize / eob kernel (aom_highbd_quantize_b*, EbFullLoop.c:239-333).
 #pragma once
 #include "dev_common.h"
+#include "tx_plan.h"
 
 namespace svtdev {
 
@@ -16,6 +17,7 @@ __global__ __launch_bounds__(256) void quantize_b_kernel(
     uint16_t* __restrict__ eob, const int16_t* __restrict__ iscan, QParams qp, int n, int skip_block,
     uint32_t nblocks) {
     constexpr int BPW = 64 / LPB;
+    static_assert(4 * BPW == svthost::quantize_b_blocks_per_wg(LPB), "tx_plan.h plans the grid");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPB, l = lane % LPB;
     const uint32_t blk = (blockIdx.x * 4 + wave) * BPW + sub;

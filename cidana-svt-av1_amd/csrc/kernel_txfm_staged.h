@@ -13,6 +13,7 @@
 #include "av1_geom.h"
 #include "group_table.h"
 #include "kernel_txfm.h"
+#include "tx_plan.h"
 
 namespace svtdev {
 
@@ -408,6 +409,13 @@ static_assert(svthost::tx_launch_kind(4) == 3 SVT_TX_CLASS0(SVT_TX_KIND0, SVT_TX
 __host__ __device__ constexpr int tx_class_of(int tx_size) {
     return tx_size == 4 ? 2 : (((kTxClass0 >> tx_size) & 1u) ? 0 : 1);
 }
+// the launch geometry the host plans with (tx_plan.h) is the kernels', for every one of the 19 sizes
+#define SVT_TX_GEOM_IS(N, W, H)                                                                                                                   \
+    &&svthost::tx_general_blocks_per_wg(N) == TX_WAVES * TxGeom<W, H>::BPW && svthost::tx_staged_waves(W, H) == StagedGeom<W, H>::WAVES &&         \
+        svthost::tx_staged_blocks_per_wg(N) == StagedGeom<W, H>::WAVES * TxGeom<W, H>::BPW && svthost::tx_class(N) == tx_class_of(N)
+static_assert(svthost::kTxWaves == TX_WAVES SVT_TX_CLASS0(SVT_TX_GEOM_IS, SVT_TX_GEOM_IS) SVT_TX_CLASS1(SVT_TX_GEOM_IS, SVT_TX_GEOM_IS) SVT_TX_GEOM_IS(4, 64, 64),
+              "tx_plan.h and the kernels agree on waves, blocks per workgroup and register class");
+#undef SVT_TX_GEOM_IS
 // the largest of a list: cmax_of({SVT_TX_CLASS0(V, V)}) with V(N, W, H) = a size's value and a comma
 constexpr int cmax_of(std::initializer_list<int> v) {
     int m = 0;

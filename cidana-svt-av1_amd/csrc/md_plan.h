@@ -16,14 +16,12 @@
 
 namespace svthost {
 // ---- sizes ------------------------------------------------------------------------------------------------------------------------
-// (kTxW / kTxH, kBsizeW / kBsizeH, kSizeGroup, kNumPelsLog2 and tx_type_ok: av1_geom.h)
+// (kTxW / kTxH, kBsizeW / kBsizeH, kSizeGroup, kNumPelsLog2, tx_type_ok and tx_log_scale: av1_geom.h)
 inline int log2_of(int v) { int l = 0; while ((1 << l) < v) l++; return l; }
 inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 // a side as the coefficient arrays hold it (a 64-sample side packs to 32), and the coefficients of a block: min(W,32) * min(H,32)
 inline int packed_side(int v) { return v < 32 ? v : 32; }
 inline int coeffs_of(int tx_size) { return packed_side(kTxW[tx_size]) * packed_side(kTxH[tx_size]); }
-// the quantiser's log_scale of a transform size (av1_get_tx_scale): 1 above 256 pixels, 2 above 1024
-inline int tx_log_scale(int tx_size) { const int pels = kTxW[tx_size] * kTxH[tx_size]; return pels > 1024 ? 2 : (pels > 256 ? 1 : 0); }
 constexpr int kCflCands = 2 * SVT_HIP_CFL_NALPHA;      // per block: two planes of SVT_HIP_CFL_NALPHA
 // the end of the fast loop (fast pick, inter fast pick): the survivors of a list of ncand, the buffers the walk uses for them (one more
 // as a scratch when the list is longer), and the blocks a wave takes: one until every wave slot of the device (32 per CU; 256 CUs when

@@ -26,7 +26,7 @@ static int search_enqueue(const svt_hip_cfl_search_group* groups, int ngroups, i
         const svt_hip_cfl_search_group& G = groups[g];
         if (G.nblocks == 0) continue;
         // a workgroup's waves take (blocks, plane) units: half as many blocks as a staged body's workgroup
-        const uint32_t per_wg = staged_blocks_per_wg(G.tx_size) / 2;
+        const uint32_t per_wg = tx_staged_blocks_per_wg(G.tx_size) / 2;
         CflSearchGroupDev* D = tab.add((G.nblocks + per_wg - 1) / per_wg, launch);
         if (!D) return tab.rc;
         const svt_hip_coeff_rate_group& C = cr[(size_t)g];

@@ -26,7 +26,7 @@ int svthost::full_loop_enqueue(const svt_hip_full_loop_group* groups, int ngroup
         for (int g = 0; g < ngroups; g++) {
             const svt_hip_full_loop_group& G = groups[g];
             if (G.nblocks == 0 || tx_class_of(G.tx_size) != cls) continue;
-            const uint32_t per_wg = staged_blocks_per_wg(G.tx_size);
+            const uint32_t per_wg = tx_staged_blocks_per_wg(G.tx_size);
             FullLoopGroupDev* D = tab.add((G.nblocks + per_wg - 1) / per_wg, launch);
             if (!D) return tab.rc;
             D->src = (const uint8_t*)G.d_src; D->pred = (const uint8_t*)G.d_pred; D->src_xy = G.d_src_xy; D->pred_xy = G.d_pred_xy;

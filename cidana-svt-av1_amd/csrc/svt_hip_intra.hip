@@ -6,6 +6,7 @@
 #include "kernel_bip.h"
 #include "kernel_ois.h"
 #include "ois_plan.h"
+#include "tx_plan.h"
 
 using namespace svtdev;
 using namespace svthost;
@@ -152,7 +153,7 @@ extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, 
     if (ncfl && (first_chroma_group < 0 || first_chroma_group > ngroups)) return set_err(SVT_HIP_ERR_INVALID, "first_chroma_group %d of %d", first_chroma_group, ngroups);
     if (!sample_depth_ok(is_16bit, bd)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
     // everything is validated before anything is enqueued
-    if (int rc = frame_groups_check(groups, ngroups)) return rc;
+    if (int rc = frame_groups_check(groups, ngroups, tx_knobs())) return rc;
     GroupTable<CflFrameDesc, CFL_MAX_GROUPS> ctab;       // (ncfl <= CFL_MAX_GROUPS: one launch, after the luma pass)
     for (int g = 0; g < ncfl; g++) {
         const svt_hip_frame_cfl_group& C = cfl[g];

@@ -142,6 +142,11 @@ int svt_hip_md_intra_candidates(uint32_t bwidth, uint32_t bheight, uint32_t sq_s
 /* ============================================================================
  * (B) batched API — device pointers, `stream` is a hipStream_t (NULL = default)
  * Every call only enqueues work; it returns before the GPU finishes.
+ * A batch holds at most 2^31 - 1 blocks: every call of this section returns
+ * SVT_HIP_ERR_INVALID ("nblocks too large") above that, before it launches
+ * anything (svt_hip_inv_txfm2d_add_batch, svt_hip_quantize_b_batch,
+ * svt_hip_pack64_batch and svt_hip_fwd_quant_batch included, which once took
+ * the count modulo 2^32).
  * ==========================================================================*/
 
 /* K1 forward 2-D transform.  Replaces av1_fwd_txfm2d_WxH

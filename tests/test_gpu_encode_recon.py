@@ -285,4 +285,50 @@ def test_encode_recon_tail_counts(dsp, tx_size, tx_type, n, keep):
     check(dsp, src, pred, tx_size, tx_type, 60, keep)
 
 
+def test_encode_recon_32x32_keeps_coefficients_without_the_sad(dsp):
+    """enc32_kernel<uint8_t, 8, true, false>, which no other caller reaches: coefficients kept, no SAD; 8 blocks per workgroup"""
+    rng = np.random.default_rng(8201)
+    src, pred = make_pixels(rng, 9, 32, 32, "smooth")
+    qrow = {k: v[60].copy() for k, v in svtlibs.quant_tables(8).items()}
+    _, iscan = svtlibs.scan_tables(3, 0)
+    out = dsp.encode_recon(dev(src), dev(pred), 3, 0, qrow, dev(iscan), keep_coeff=True, want_sad=False)
+    torch.cuda.synchronize()
+    rco, rq, rdq, reob, _ = oracle_chain(src, pred, 3, 0, qrow)
+    assert out["sad"] is None
+    assert np.array_equal(out["qcoeff"].cpu().numpy(), rq) and np.array_equal(out["eob"].cpu().numpy().view(np.uint16), reob)
+    assert np.array_equal(out["coeff"].cpu().numpy(), rco) and np.array_equal(out["dqcoeff"].cpu().numpy(), rdq)
+    assert np.array_equal(out["recon"].cpu().numpy(), oracle_recon(pred, rdq, 3, 0))
+
+
+def test_encode_recon_4x4_10bit_keeps_coefficients(dsp):
+    """enc4_kernel<uint16_t, 10, true>, which no other caller reaches: 10-bit planes, coefficients kept; 256 blocks per workgroup"""
+    import ctypes
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(8202)
+    PH, PW = 18, 280
+    src = rng.integers(0, 1024, size=(PH, PW)).astype(np.uint16)
+    pred = np.clip(src.astype(int) + rng.integers(-30, 31, size=src.shape), 0, 1023).astype(np.uint16)
+    origins = [(y, x) for y in range(1, PH - 3, 4) for x in range(3, PW - 3, 4)][:257]
+    assert len(origins) == 257
+    xy = np.array([(y << 16) | x for y, x in origins], np.uint32)
+    qrow = {k: v[120].copy() for k, v in svtlibs.quant_tables(10).items()}
+    _, iscan = svtlibs.scan_tables(0, 0)
+    d_pred = dev(pred.view(np.int16))
+    d_recon = poison.tensor(d_pred.shape, d_pred.dtype, d_pred.device).fill_(9)
+    out = dsp.encode_recon_planes(dev(src.view(np.int16)), PW, d_pred, PW, d_recon, PW, dev(xy.view(np.int32)), 0, 0, qrow, dev(iscan), keep_coeff=True, bd=10)
+    torch.cuda.synchronize()
+    expect = np.full_like(pred, 9)
+    for i, (y, x) in enumerate(origins):
+        rc = np.zeros(16, np.int32); rq = np.zeros(16, np.int32); rdq = np.zeros(16, np.int32); reob = np.zeros(1, np.uint16)
+        sp = ctypes.c_void_p(int(src.ctypes.data) + int(y * PW + x) * 2); pp = ctypes.c_void_p(int(pred.ctypes.data) + int(y * PW + x) * 2)
+        O.svt_oracle_fwd_quant_planes(sp, PW, pp, PW, 1, 10, 0, 0, ptr(qrow["zbin"]), ptr(qrow["round"]), ptr(qrow["quant"]), ptr(qrow["quant_shift"]),
+                                      ptr(qrow["dequant"]), ptr(rc), ptr(rq), ptr(rdq), ptr(reob), None, None)
+        blk = np.ascontiguousarray(pred[y:y + 4, x:x + 4])
+        O.svt_oracle_inv_txfm2d_add(ptr(rdq), ptr(blk), 4, 0, 0, 10)
+        expect[y:y + 4, x:x + 4] = blk
+        assert np.array_equal(out["qcoeff"][i].cpu().numpy(), rq) and np.array_equal(out["coeff"][i].cpu().numpy(), rc), i
+        assert np.array_equal(out["dqcoeff"][i].cpu().numpy(), rdq) and int(out["eob"][i].cpu().numpy().view(np.uint16)) == int(reob[0]), i
+    assert np.array_equal(d_recon.cpu().numpy().view(np.uint16), expect)
+
+
 poison.add_second_fill(globals())

@@ -778,3 +778,117 @@ def test_intra_pred_tail_counts(dsp, tx_size, n):
                 else:
                     O.svt_oracle_intra_pred_hbd(mode, ptr(ref[i]), ctypes.c_ssize_t(bw), bw, bh, pa, pl, bd)
             assert np.array_equal(out, ref), (TX_SIZES[tx_size], mode, bd)
+
+
+# ---- routes and template variants of svt_hip_txfm.hip that no other test, benchmark or tool reaches (tests/c/tx_plan_host.cpp pins their
+# plans): one full workgroup and one more block, which is where the grid rounding and the tail guard can go wrong, with the knob, table or
+# operand that selects the route ----
+class _tuned:
+    def __init__(self, dsp, **knobs):
+        self.dsp, self.knobs = dsp, knobs
+
+    def __enter__(self):
+        for k, v in self.knobs.items():
+            assert self.dsp.lib.svt_hip_tune(k.encode(), int(v)) == 0
+
+    def __exit__(self, *exc):
+        defaults = {"inv32_waves": 4}
+        for k in self.knobs:
+            assert self.dsp.lib.svt_hip_tune(k.encode(), defaults.get(k, 0)) == 0
+
+
+NONSTANDARD_QROW = {"zbin": np.array([37, 41] + [41] * 6, np.int16), "round": np.array([19, 23] + [23] * 6, np.int16),
+                    "quant": np.array([-12345, 7001] + [7001] * 6, np.int16), "quant_shift": np.array([12000, 777] + [777] * 6, np.int16),
+                    "dequant": np.array([53, 61] + [61] * 6, np.int16)}
+
+
+def test_fwd_txfm2d_general_kernel(dsp):
+    """fwd_txfm2d_kernel (dense aligned batches go to the staged kernel): no_staged, 8x8, 32 blocks per workgroup"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(2501)
+    n = 33
+    x = rng.integers(-255, 256, size=(n, 8, 8)).astype(np.int16)
+    with _tuned(dsp, no_staged=1):
+        out = dsp.fwd_txfm2d(dev(x), 1, 5, 8).cpu().numpy()
+    ref = np.zeros((n, 64), np.int32)
+    for i in range(n):
+        O.svt_oracle_fwd_txfm2d(ptr(x[i]), ptr(ref[i]), ctypes.c_uint32(8), 5, 1, 8)
+    assert np.array_equal(out, ref)
+
+
+@pytest.mark.parametrize("want_sad,nt,pow2", [(False, 0, True), (False, 0, False), (True, 1, True), (False, 1, True), (True, 1, False), (False, 1, False)])
+def test_fused_32x32_variants(dsp, want_sad, nt, pow2):
+    """fwd32_kernel<1, true, SAD, NT, QMODE>: without the SAD, with streaming stores (f32_nt), with a table whose quant_shift is no power of
+    two (QMODE 1); 8 blocks per workgroup"""
+    rng = np.random.default_rng(2502 + 4 * nt + 2 * pow2 + want_sad)
+    n = 9
+    src, pred = make_pixels(rng, n, 32, 32, "random")
+    qrow = {k: v[100].copy() for k, v in svtlibs.quant_tables(8).items()} if pow2 else NONSTANDARD_QROW
+    _, iscan = svtlibs.scan_tables(3, 0)
+    sad0 = torch.full((n,), -7, dtype=torch.int32, device=DEV)
+    outs = tuple(torch.empty((n, 1024), dtype=torch.int32, device=DEV) for _ in range(3)) + (torch.empty(n, dtype=torch.int16, device=DEV), sad0)
+    with _tuned(dsp, f32_nt=nt):
+        co, q, dq, eob, sad = dsp.fwd_quant_sad(dev(src), dev(pred), 3, 0, qrow, dev(iscan), outs=outs, want_sad=want_sad)
+        torch.cuda.synchronize()
+    rco, rq, rdq, reob, rsad = oracle_chain(src, pred, 3, 0, qrow)
+    assert np.array_equal(co.cpu().numpy(), rco) and np.array_equal(q.cpu().numpy(), rq) and np.array_equal(dq.cpu().numpy(), rdq)
+    assert np.array_equal(eob.cpu().numpy().view(np.uint16), reob)
+    assert np.array_equal(sad.cpu().numpy().view(np.uint32), rsad) if want_sad else bool((sad == -7).all())
+
+
+def test_fwd_quant_planes_32x32_with_sad(dsp):
+    """fwd32_kernel<1, true, true, false, 2, true>: 8-bit planes, the SAD asked for and the energy not"""
+    rng = np.random.default_rng(2503)
+    PH, PW = 96, 99
+    src = rng.integers(0, 256, size=(PH, PW), dtype=np.uint8); pred = rng.integers(0, 256, size=(PH, PW + 5), dtype=np.uint8)
+    origins = [(y, x) for y in (0, 32, 64) for x in (0, 33, 67)]
+    xy = np.array([(y << 16) | x for y, x in origins], np.uint32)
+    qrow = {k: v[80].copy() for k, v in svtlibs.quant_tables(8).items()}
+    _, iscan = svtlibs.scan_tables(3, 0)
+    co, q, dq, eob, sad, _ = dsp.fwd_quant_planes(dev(src), PW, dev(pred), PW + 5, dev(xy.view(np.int32)), 3, 0, qrow, dev(iscan), want_sad=True)
+    sb = np.stack([src[y:y + 32, x:x + 32] for y, x in origins]); pb = np.stack([pred[y:y + 32, x:x + 32] for y, x in origins])
+    rco, rq, rdq, reob, rsad = oracle_chain(sb, pb, 3, 0, qrow)
+    assert np.array_equal(co.cpu().numpy(), rco) and np.array_equal(q.cpu().numpy(), rq) and np.array_equal(dq.cpu().numpy(), rdq)
+    assert np.array_equal(eob.cpu().numpy().view(np.uint16), reob) and np.array_equal(sad.cpu().numpy().view(np.uint32), rsad)
+
+
+def test_fwd_quant_planes_32x32_dense_10bit(dsp):
+    """fwd32_kernel<2, true, false, false, 2, false>: a dense batch of 10-bit blocks, svt_hip_fwd_quant_planes_batch without an origin table"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(2504)
+    n = 9
+    src = rng.integers(0, 1024, size=(n, 32, 32)).astype(np.uint16)
+    pred = np.clip(src.astype(int) + rng.integers(-40, 41, size=src.shape), 0, 1023).astype(np.uint16)
+    qrow = {k: v[120].copy() for k, v in svtlibs.quant_tables(10).items()}
+    _, iscan = svtlibs.scan_tables(3, 0)
+    d_src, d_pred, d_iscan = dev(src.view(np.int16)), dev(pred.view(np.int16)), dev(iscan)
+    co, q, dq = (torch.empty((n, 1024), dtype=torch.int32, device=DEV) for _ in range(3))
+    eob = torch.empty(n, dtype=torch.int16, device=DEV)
+    tabs = [np.ascontiguousarray(qrow[k], dtype=np.int16) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
+    dsp._check(dsp.lib.svt_hip_fwd_quant_planes_batch(dsp._p(d_src), 32, dsp._p(d_pred), 32, None, n, 1, 10, 3, 0, *[t.ctypes.data for t in tabs], dsp._p(d_iscan),
+                                                      dsp._p(co), dsp._p(q), dsp._p(dq), dsp._p(eob), None, None, dsp._stream()), "svt_hip_fwd_quant_planes_batch")
+    torch.cuda.synchronize()
+    for i in range(n):
+        rc = np.zeros(1024, np.int32); rq = np.zeros(1024, np.int32); rdq = np.zeros(1024, np.int32); reob = np.zeros(1, np.uint16)
+        O.svt_oracle_fwd_quant_planes(ptr(src[i]), 32, ptr(pred[i]), 32, 1, 10, 3, 0, *[ptr(t) for t in tabs], ptr(rc), ptr(rq), ptr(rdq), ptr(reob), None, None)
+        assert np.array_equal(co[i].cpu().numpy(), rc) and np.array_equal(q[i].cpu().numpy(), rq) and np.array_equal(dq[i].cpu().numpy(), rdq), i
+        assert int(eob[i].item()) & 0xffff == int(reob[0]), i
+
+
+@pytest.mark.parametrize("waves,var", [(2, 0), (4, 8)])
+def test_inv32_probe_variants_that_compute(dsp, waves, var):
+    """inv32_kernel<uint8_t, 8, WV, VR>, the two tuning probes that do the whole job (two waves per workgroup; five waves per SIMD); the
+    others leave a step out on purpose and have no reference.  2 * waves blocks per workgroup"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(2505 + var)
+    n = 2 * waves + 1
+    co = rng.integers(-600, 601, size=(n, 1024)).astype(np.int32)
+    dst = rng.integers(0, 256, size=(n, 32, 32), dtype=np.uint8)
+    d_dst = dev(dst)
+    with _tuned(dsp, inv32_waves=waves, inv32_var=var):
+        dsp.inv_txfm2d_add(dev(co), d_dst, 3, 0, 8)
+        torch.cuda.synchronize()
+    ref = dst.copy()
+    for i in range(n):
+        O.svt_oracle_inv_txfm2d_add_u8(ptr(co[i]), ptr(ref[i]), 32, 0, 3)
+    assert np.array_equal(d_dst.cpu().numpy(), ref)
