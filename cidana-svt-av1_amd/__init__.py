@@ -254,6 +254,25 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_dlf_level_from_q.argtypes = [c_int, c_int, c_int, c_void_p]
     for name in ("mi_frame", "apply_frame", "search_frame", "check", "mi_check", "limits", "levels", "pick_level", "level_from_q"):
         getattr(L, "svt_hip_dlf_" + name).restype = c_int
+    L.svt_hip_lr_apply_frame.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
+    L.svt_hip_lr_try_frame.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]
+    L.svt_hip_lr_wiener_stats_frame.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_lr_check.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_uint32]
+    L.svt_hip_lr_unit_grid.argtypes = [c_uint32, c_uint32, c_void_p, c_int, c_void_p]
+    L.svt_hip_lr_unit_limits.argtypes = [c_uint32, c_uint32, c_void_p, c_int, c_uint32, c_void_p]
+    for name in ("apply_frame", "try_frame", "wiener_stats_frame", "check", "unit_grid", "unit_limits"):
+        getattr(L, "svt_hip_lr_" + name).restype = c_int
+    L.svt_hip_lr_wiener_solve.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.svt_hip_lr_walk_start.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
+    L.svt_hip_lr_walk_next.argtypes = [c_void_p, ctypes.c_int64]
+    L.svt_hip_lr_finish.argtypes = [c_int, c_int, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]
+    for name in ("wiener_solve", "walk_start", "walk_next", "finish"):
+        getattr(L, "svt_hip_lr_" + name).restype = c_int
+    L.svt_hip_lr_stats_scratch_bytes.argtypes = [c_uint32, c_uint32, c_void_p, c_uint32]
+    L.svt_hip_lr_stats_scratch_bytes.restype = c_size_t
+    for name in ("unit_offset", "units_per_pic"):
+        getattr(L, "svt_hip_lr_" + name).argtypes = [c_uint32, c_uint32, c_void_p] + ([c_int] if name == "unit_offset" else [])
+        getattr(L, "svt_hip_lr_" + name).restype = c_uint32
     L.svt_hip_md_search_scratch_bytes.argtypes = [c_void_p, c_int]
     L.svt_hip_md_search_scratch_bytes.restype = c_size_t
     L.svt_hip_md_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
@@ -2696,6 +2715,224 @@ class SvtHipDsp:
         if rc != SVT_HIP_OK:
             raise SvtHipError(f"svt_hip_dlf_level_from_q = {rc}")
         return list(lv)
+
+    # -- loop restoration: av1_loop_restoration_filter_frame, try_restoration_unit_seg per candidate, av1_compute_stats per unit ----------
+    class LrPic(ctypes.Structure):
+        """svt_hip_lr_pic"""
+        _fields_ = [("d_cdef", c_void_p * 3), ("cdef_stride", c_uint32 * 3), ("pad0", c_uint32), ("d_dblk", c_void_p * 3), ("dblk_stride", c_uint32 * 3),
+                    ("pad1", c_uint32), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3), ("pad2", c_uint32), ("d_dst", c_void_p * 3),
+                    ("dst_stride", c_uint32 * 3), ("pad3", c_uint32), ("width", c_uint32), ("height", c_uint32), ("bit_depth", c_int32),
+                    ("unit_size", c_uint32 * 3), ("npics", c_uint32), ("pad4", c_uint32), ("cdef_pitch", ctypes.c_uint64 * 3),
+                    ("dblk_pitch", ctypes.c_uint64 * 3), ("src_pitch", ctypes.c_uint64 * 3), ("dst_pitch", ctypes.c_uint64 * 3)]
+
+    LR_UNIT_DTYPE = [("type", "<i4"), ("vfilter", "<i2", 3), ("hfilter", "<i2", 3), ("xqd", "<i2", 2), ("ep", "<i4")]              # svt_hip_lr_unit
+    LR_CAND_DTYPE = [("pic", "<u4"), ("plane", "<u4"), ("unit", "<u4"), ("u", LR_UNIT_DTYPE)]                                       # svt_hip_lr_cand
+
+    @staticmethod
+    def make_lr_pic(cdef, dblk, width, height, bit_depth, unit_size, src=None, dst=None):
+        """cdef / dblk / src / dst: (Y, Cb, Cr) tensors, uint8 (bit depth 8) or uint16 / int16 (10), [rows, stride] for one picture or
+        [npics, rows, stride] for a stack, or views of such (the strides are the tensors' own); unit_size: (luma, Cb, Cr).
+        -> LrPic (keep the tensors alive!)"""
+        p = SvtHipDsp.LrPic()
+        stack = cdef[0].dim() == 3
+        p.npics = cdef[0].shape[0] if stack else 1
+        for planes, ptr, stride, pitch in ((cdef, p.d_cdef, p.cdef_stride, p.cdef_pitch), (dblk, p.d_dblk, p.dblk_stride, p.dblk_pitch),
+                                           (src, p.d_src, p.src_stride, p.src_pitch), (dst, p.d_dst, p.dst_stride, p.dst_pitch)):
+            if planes is None:
+                continue
+            for i, t in enumerate(planes):
+                assert t.stride(-1) == 1 and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
+                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.stride(-2), (t.stride(0) if stack else 0)
+        p.width, p.height, p.bit_depth = width, height, bit_depth
+        for i in range(3):
+            p.unit_size[i] = int(unit_size[i])
+        return p
+
+    @staticmethod
+    def lr_unit_grid(width, height, unit_size, lib=None):
+        """The unit grids of the three planes (no device needed) -> [(horz_units, vert_units, offset of the plane's records)], units per
+        picture.  Raises on a geometry the calls refuse.  lib: a library handle to use instead of loading one."""
+        lib = lib if lib is not None else load_library()
+        us = (c_uint32 * 3)(*[int(v) for v in unit_size])
+        out, grids = (ctypes.c_int32 * 3)(), []
+        for plane in range(3):
+            rc = lib.svt_hip_lr_unit_grid(int(width), int(height), us, plane, out)
+            if rc != SVT_HIP_OK:
+                raise SvtHipError(f"svt_hip_lr_unit_grid = {rc}")
+            grids.append((out[0], out[1], lib.svt_hip_lr_unit_offset(int(width), int(height), us, plane)))
+        return grids, lib.svt_hip_lr_units_per_pic(int(width), int(height), us)
+
+    @staticmethod
+    def lr_unit_limits(width, height, unit_size, plane, index):
+        """(h_start, h_end, v_start, v_end) of unit `index` (row-major) of a plane; no device needed"""
+        us = (c_uint32 * 3)(*[int(v) for v in unit_size])
+        out = (ctypes.c_int32 * 4)()
+        rc = load_library().svt_hip_lr_unit_limits(int(width), int(height), us, int(plane), int(index), out)
+        if rc != SVT_HIP_OK:
+            raise SvtHipError(f"svt_hip_lr_unit_limits = {rc}")
+        return tuple(out)
+
+    def _lr_records(self, records, dtype, device):
+        """a numpy structured array (or an uint8 tensor already on the device) of records -> uint8 tensor on the device"""
+        import numpy as np
+        t = self.torch
+        if isinstance(records, t.Tensor):
+            assert records.dtype == t.uint8 and records.is_contiguous()
+            return records
+        a = np.ascontiguousarray(records, dtype=np.dtype(dtype))
+        return t.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(device)
+
+    def lr_apply_frame(self, cdef, dblk, width, height, bit_depth, unit_size, frame_type, units, dst=None):
+        """svt_hip_lr_apply_frame (av1_loop_restoration_filter_frame over the three planes).  frame_type: per plane 0 none, 1 Wiener,
+        2 self-guided, 3 switchable; units: LR_UNIT_DTYPE records [(npics,) units per picture] (the planes' blocks one after another,
+        see lr_unit_grid), a numpy array or an uint8 tensor on the device.  -> dst (Y, Cb, Cr), shaped as cdef; only the picture area
+        is written (the samples of a fresh dst outside it are zero)."""
+        t = self.torch
+        if dst is None:
+            dst = tuple(t.zeros_like(x) for x in cdef)      # partly written (the picture area of each plane): zeros define the rest
+        p = self.make_lr_pic(cdef, dblk, width, height, bit_depth, unit_size, dst=dst)
+        rec = self._lr_records(units, self.LR_UNIT_DTYPE, cdef[0].device)
+        _, per_pic = self.lr_unit_grid(width, height, unit_size, self.lib)
+        assert rec.numel() == p.npics * per_pic * 24, (rec.numel(), p.npics, per_pic)
+        ft = (c_int32 * 3)(*[int(v) for v in frame_type])
+        self._check(self.lib.svt_hip_lr_apply_frame(ctypes.addressof(p), ft, self._p(rec), self._stream()), "svt_hip_lr_apply_frame")
+        return dst
+
+    def lr_try_frame(self, cdef, dblk, src, width, height, bit_depth, unit_size, cands, sse=None):
+        """svt_hip_lr_try_frame (try_restoration_unit_seg per candidate).  cands: LR_CAND_DTYPE records (pic, plane, unit, record), a
+        numpy array or an uint8 tensor on the device.  -> sse int64 [ncand]: the squared error of the filtered unit against src."""
+        t = self.torch
+        p = self.make_lr_pic(cdef, dblk, width, height, bit_depth, unit_size, src=src)
+        rec = self._lr_records(cands, self.LR_CAND_DTYPE, cdef[0].device)
+        ncand = rec.numel() // 36
+        assert rec.numel() == ncand * 36
+        if sse is None:
+            sse = t.empty((ncand,), dtype=t.int64, device=cdef[0].device)
+        assert sse.is_contiguous() and sse.numel() == ncand and sse.dtype == t.int64
+        self._check(self.lib.svt_hip_lr_try_frame(ctypes.addressof(p), self._p(rec), ncand, self._p(sse), self._stream()), "svt_hip_lr_try_frame")
+        return sse
+
+    def lr_stats_scratch_bytes(self, width, height, unit_size, npics=1):
+        """svt_hip_lr_stats_scratch_bytes (a host computation; 0 for a geometry the call refuses)"""
+        us = (c_uint32 * 3)(*[int(v) for v in unit_size])
+        return self.lib.svt_hip_lr_stats_scratch_bytes(int(width), int(height), us, int(npics))
+
+    def lr_wiener_stats_frame(self, cdef, src, width, height, bit_depth, unit_size, wiener_win, M=None, H=None, scratch=None):
+        """svt_hip_lr_wiener_stats_frame (av1_compute_stats[_highbd] per unit).  wiener_win: per plane 7, 5 or 3.
+        -> M int64 [(npics,) units per picture, 49], H int64 [(npics,) units per picture, 2401]; a unit's block is dense at win * win
+        (M[u, :win2], H[u, :win2 * win2].reshape(win2, win2)), the rest of it zero."""
+        t = self.torch
+        p = self.make_lr_pic(cdef, None, width, height, bit_depth, unit_size, src=src)
+        _, per_pic = self.lr_unit_grid(width, height, unit_size, self.lib)
+        lead = (p.npics,) if cdef[0].dim() == 3 else ()
+        if M is None:
+            M = t.empty(lead + (per_pic, 49), dtype=t.int64, device=cdef[0].device)
+        if H is None:
+            H = t.empty(lead + (per_pic, 2401), dtype=t.int64, device=cdef[0].device)
+        need = self.lr_stats_scratch_bytes(width, height, unit_size, p.npics)
+        if scratch is None:
+            scratch = t.empty((max(need, 8),), dtype=t.uint8, device=cdef[0].device)
+        assert M.is_contiguous() and M.numel() == p.npics * per_pic * 49 and H.is_contiguous() and H.numel() == p.npics * per_pic * 2401
+        win = (c_int32 * 3)(*[int(v) for v in wiener_win])
+        self._check(self.lib.svt_hip_lr_wiener_stats_frame(ctypes.addressof(p), win, self._p(M), self._p(H), self._p(scratch),
+                                                           scratch.numel() * scratch.element_size(), self._stream()), "svt_hip_lr_wiener_stats_frame")
+        return M, H
+
+    class LrWalk(ctypes.Structure):
+        """svt_hip_lr_walk"""
+        _fields_ = [("vfilter", ctypes.c_int16 * 3), ("hfilter", ctypes.c_int16 * 3), ("win", c_int32), ("step", c_int32), ("dir", c_int32), ("p", c_int32),
+                    ("phase", c_int32), ("skip", c_int32), ("state", c_int32), ("err", ctypes.c_int64)]
+
+    LR_WALK_TRY, LR_WALK_DONE = 1, 2
+
+    @staticmethod
+    def lr_wiener_solve(win, M, H, lib=None):
+        """svt_hip_lr_wiener_solve (wiener_decompose_sep_sym, finalize_sym_filter, compute_score; no device needed).  M [win2], H [win2,
+        win2] int64 -> (vfilter taps 0 .. 2, hfilter taps 0 .. 2, accepted)"""
+        import numpy as np
+        lib = lib if lib is not None else load_library()
+        M, H = np.ascontiguousarray(M, np.int64), np.ascontiguousarray(H, np.int64)
+        assert M.size == win * win and H.size == win ** 4
+        v, h, ok = (ctypes.c_int16 * 3)(), (ctypes.c_int16 * 3)(), c_int(-1)
+        rc = lib.svt_hip_lr_wiener_solve(int(win), M.ctypes.data, H.ctypes.data, v, h, ctypes.addressof(ok))
+        if rc != SVT_HIP_OK:
+            raise SvtHipError(f"svt_hip_lr_wiener_solve = {rc}")
+        return list(v), list(h), bool(ok.value)
+
+    @staticmethod
+    def lr_walk_start(win, vfilter, hfilter, lib=None):
+        """svt_hip_lr_walk_start -> LrWalk asking for its first trial (the taps given)"""
+        lib = lib if lib is not None else load_library()
+        w = SvtHipDsp.LrWalk()
+        rc = lib.svt_hip_lr_walk_start(ctypes.addressof(w), int(win), (ctypes.c_int16 * 3)(*vfilter), (ctypes.c_int16 * 3)(*hfilter))
+        if rc != SvtHipDsp.LR_WALK_TRY:
+            raise SvtHipError(f"svt_hip_lr_walk_start = {rc}")
+        return w
+
+    @staticmethod
+    def lr_walk_next(w, sse, lib=None):
+        """svt_hip_lr_walk_next -> LR_WALK_TRY (measure w.vfilter / w.hfilter next) or LR_WALK_DONE (they are final, w.err their SSE)"""
+        lib = lib if lib is not None else load_library()
+        rc = lib.svt_hip_lr_walk_next(ctypes.addressof(w), int(sse))
+        if rc not in (SvtHipDsp.LR_WALK_TRY, SvtHipDsp.LR_WALK_DONE):
+            raise SvtHipError(f"svt_hip_lr_walk_next = {rc}")
+        return rc
+
+    LR_RESULT_DTYPE = [("sse", "<i8", 3), ("vfilter", "<i2", 3), ("hfilter", "<i2", 3), ("xqd", "<i2", 2), ("ep", "<i4"), ("pad", "<i4")]      # svt_hip_lr_result
+    LR_COSTS_DTYPE = [("rdmult", "<i4"), ("wiener_restore_cost", "<i4", 2), ("sgrproj_restore_cost", "<i4", 2), ("switchable_restore_cost", "<i4", 3)]
+
+    @staticmethod
+    def lr_finish(plane, wn_filter_mode, costs, results, lib=None):
+        """svt_hip_lr_finish (rest_finish_search for one plane; no device needed).  costs: (rdmult, wiener_restore_cost[2],
+        sgrproj_restore_cost[2], switchable_restore_cost[3]) as 8 ints or one LR_COSTS_DTYPE record; results: LR_RESULT_DTYPE records, one
+        per unit of the plane -> (frame_restoration_type, LR_UNIT_DTYPE records for svt_hip_lr_apply_frame)"""
+        import numpy as np
+        lib = lib if lib is not None else load_library()
+        c = np.ascontiguousarray(costs, np.int32).reshape(-1) if not (hasattr(costs, "dtype") and costs.dtype.names) else np.ascontiguousarray(costs).view(np.int32).reshape(-1)
+        assert c.size == 8
+        r = np.ascontiguousarray(results, np.dtype(SvtHipDsp.LR_RESULT_DTYPE))
+        units = np.zeros(len(r), np.dtype(SvtHipDsp.LR_UNIT_DTYPE))
+        ft = c_int32(-1)
+        rc = lib.svt_hip_lr_finish(int(plane), int(wn_filter_mode), c.ctypes.data, r.ctypes.data, len(r), ctypes.addressof(ft), units.ctypes.data)
+        if rc != SVT_HIP_OK:
+            raise SvtHipError(f"svt_hip_lr_finish = {rc}: {lib.svt_hip_last_error().decode()}")
+        return ft.value, units
+
+    def lr_wiener_search(self, cdef, dblk, src, width, height, bit_depth, unit_size, wiener_win):
+        """search_wiener_seg for every unit of one picture: svt_hip_lr_wiener_stats_frame, then per unit svt_hip_lr_wiener_solve on the
+        host, then the refinement walks of all accepted units in lock step: one svt_hip_lr_try_frame per round with one candidate per
+        still-active unit.  -> (taps int16 [units, 6]: vfilter 0 .. 2, hfilter 0 .. 2, zero where compute_score rejects; sse int64 [units],
+        INT64_MAX where it rejects; rounds).  The host pacing is deliberate: a round costs one launch and one read-back."""
+        import numpy as np
+        t = self.torch
+        assert cdef[0].dim() == 2, "one picture"
+        grids, per_pic = self.lr_unit_grid(width, height, unit_size, self.lib)
+        M, H = self.lr_wiener_stats_frame(cdef, src, width, height, bit_depth, unit_size, wiener_win)
+        M, H = M.cpu().numpy(), H.cpu().numpy()
+        taps, sse = np.zeros((per_pic, 6), np.int16), np.full(per_pic, np.iinfo(np.int64).max, np.int64)
+        walks = {}
+        for plane, (nh, nv, off) in enumerate(grids):
+            win = int(wiener_win[plane])
+            for k in range(nh * nv):
+                v, h, ok = self.lr_wiener_solve(win, M[off + k, :win * win], H[off + k, :win ** 4], self.lib)
+                if ok:
+                    walks[off + k] = (plane, k, self.lr_walk_start(win, v, h, self.lib))
+        rounds = 0
+        while walks:
+            order = sorted(walks)
+            cands = np.zeros(len(order), np.dtype(self.LR_CAND_DTYPE))
+            for i, u in enumerate(order):
+                plane, k, w = walks[u]
+                cands[i]["plane"], cands[i]["unit"] = plane, k
+                cands[i]["u"]["type"], cands[i]["u"]["vfilter"], cands[i]["u"]["hfilter"] = 1, list(w.vfilter), list(w.hfilter)
+            got = self.lr_try_frame(cdef, dblk, src, width, height, bit_depth, unit_size, cands).cpu().numpy()
+            rounds += 1
+            for i, u in enumerate(order):
+                w = walks[u][2]
+                if self.lr_walk_next(w, int(got[i]), self.lib) == self.LR_WALK_DONE:
+                    taps[u], sse[u] = list(w.vfilter) + list(w.hfilter), w.err
+                    del walks[u]
+        return taps, sse, rounds
 
     @staticmethod
     def md_intra_candidates(bwidth, bheight, sq_size, bsize, intra_pred_mode=0, is_16bit=False):

@@ -2313,7 +2313,7 @@ int svt_hip_intra_encode_frame(const svt_hip_intra_encode_args *a, void *stream)
  * synchronises and can be captured into a HIP graph.  svt_hip_dlf_check runs the same validation without a device (for_search: 0 =
  * apply, 1 = search).
  * NOT here: delta LF (delta_lf_present_flag, which the reference itself refuses), segment features, 128-wide superblocks, more than
- * one transform block per luma block, LPF_PICK_FROM_SUBIMAGE, loop restoration. */
+ * one transform block per luma block, LPF_PICK_FROM_SUBIMAGE.  Loop restoration has its own block below (svt_hip_lr_*). */
 typedef struct svt_hip_dlf_mi { uint8_t bsize, tx_size, ref_frame_skip, mode; } svt_hip_dlf_mi;
 typedef struct svt_hip_dlf_info { uint8_t ref_frame0, mode, skip, pad; } svt_hip_dlf_info;      /* one per src */
 typedef struct svt_hip_dlf_mi_args {
@@ -2369,6 +2369,150 @@ int svt_hip_dlf_levels(const svt_hip_dlf_pic *pic, uint8_t out[3][2][8][2]);
 #define SVT_HIP_DLF_NEED_LEVEL 1
 int svt_hip_dlf_pick_level(const int64_t ss_err[64], int start_level, int loop_filter_mode, int tx_mode_is_only_4x4, int *level, int *need);
 int svt_hip_dlf_level_from_q(int base_qindex, int bit_depth, int is_key_frame, int levels[4]);
+
+/* ---- loop restoration of whole pictures --------------------------------------------------------------------------
+ * The reference's Rest process (EbRestProcess.c:205): the stage behind CDEF.  One tile, 4:2:0, bit depth 8 or 10, optimized_lr 0.
+ * All of it is integer arithmetic and equals the reference bit for bit.
+ *
+ * Two operands instead of boundary buffers.  The reference saves lines of the deblocked picture and of the CDEF output
+ * (av1_loop_restoration_save_boundary_lines, EbRestoration.c:1734), patches three rows into the frame above and below every
+ * stripe (setup_processing_stripe_boundary, :374) and puts them back (restore_processing_stripe_boundary, :478); which rows is
+ * get_stripe_boundary_info's business (:342).  All of that is a choice of the picture a halo row is read from, so the calls take
+ * the CDEF output d_cdef (the filter's input) and the deblocked picture d_dblk (stripe context only) and read
+ *   rows above a stripe that starts at y0 > 0                deblocked rows y0 - 2, y0 - 2, y0 - 1
+ *   rows below a stripe that ends at y1 < plane height       deblocked rows y1, y1 + 1, y1 + 1
+ *   at the picture's top / bottom                            the CDEF picture's edge row three times (extend_frame, :276)
+ *   every column                                             clamped to 0 .. plane width - 1, in both pictures (extend_frame by 3,
+ *                                                            extend_lines by 4, :1570)
+ * With sides that are multiples of 8 a stripe never ends one row above the picture's bottom, so the reference's one-line case
+ * (lines_to_save == 1, :1608) cannot occur; other sides are refused.
+ *
+ *   units     foreach_rest_unit_in_tile (:1331-1377): a unit is unit_size wide / high, the last of a row / column absorbs a
+ *             remainder below unit_size * 3 / 2; v_start / v_end are shifted up by RESTORATION_UNIT_OFFSET >> ss_y (8 / 4) but at the
+ *             picture's top / bottom; the counts are av1_alloc_restoration_struct's (:198-235).  unit_size: luma 64 / 128 / 256, chroma
+ *             equal to luma or half of it (the reference: 256 above 352x288 luma samples, else 128; EbPictureControlSet.c:32-48).
+ *   stripes   av1_loop_restoration_filter_unit (:1168-1236): 64 >> ss_y rows, the first shorter by 8 >> ss_y, cut at the unit's v_end
+ *             (which, with these unit sizes, is a stripe boundary or the picture's bottom).
+ *
+ * svt_hip_lr_apply_frame is av1_loop_restoration_filter_frame (:1271-1329).  frame_type[plane]: 0 RESTORE_NONE, 1 RESTORE_WIENER,
+ * 2 RESTORE_SGRPROJ, 3 RESTORE_SWITCHABLE.  d_units [pic][plane][units_per_tile(plane)] records, row-major over the unit grid (a plane's
+ * block starts at svt_hip_lr_unit_offset(..)).  A plane of frame type none, and a unit of type none, is copied from d_cdef
+ * (copy_tile, :1182-1185): every sample of the three planes of d_dst is defined after the call, and nothing outside them is written.
+ *   Wiener        wiener_filter_stripe[_highbd] -> av1_[highbd_]wiener_convolve_add_src_c (convolve.c:64-143, 145-230): taps 0 .. 2 of the
+ *                 record, the rest by symmetry with centre -2 * (t0 + t1 + t2) (finalize_sym_filter) plus the implicit 128; horizontal
+ *                 pass with round_0 = 3 and the clamp to WIENER_CLAMP_LIMIT(3, bd) - 1, vertical pass with round_1 = 11, which is what
+ *                 get_conv_params_wiener gives at 8 and 10 bit (:110-132).  The reference rounds a call's width up to 16 and writes past
+ *                 the unit, which the next unit overwrites; here only the unit's own samples are produced.
+ *   self-guided   sgrproj_filter_stripe -> apply_selfguided_restoration_c (:1062-1099) -> av1_selfguided_restoration_c (:1022-1060):
+ *                 sgr_params[ep]; r[0] > 0: selfguided_restoration_fast_internal (:770-900; A / B on every other row counted from the
+ *                 stripe's first row minus one, other weights on even and odd rows); r[1] > 0: selfguided_restoration_internal
+ *                 (:902-1020); boxsum for r = 1, 2, the a * n < b * b saturation, x_by_xplus1, one_by_x; decode_xq, the projection and
+ *                 the clip.  Each pass reads real neighbours, so the result does not depend on the reference's 64-column processing
+ *                 units.
+ * A record of the device array is not validated on the host: an out-of-range field is clamped (a type above 2 or one the plane's frame
+ * type does not allow reads as none), and nothing outside the planes is touched.
+ *
+ * svt_hip_lr_try_frame is try_restoration_unit_seg (EbRestorationPick.c:197-224) for ncand candidates (pic, plane, unit, record): the
+ * unit is filtered exactly as in apply and its squared error against d_src over the unit's rectangle goes to d_sse[cand] (int64;
+ * sse_restoration_unit, :65-72).  A record of type none gives rusi->sse[RESTORE_NONE] (search_norestore_seg).  The plane's frame type
+ * plays no part.  Filtered samples are never stored, d_cdef is not written, every d_sse entry is defined after the call (INT64_MAX for a
+ * candidate whose pic / plane / unit is out of range), and many candidates for one unit are allowed: a search round.
+ *
+ * svt_hip_lr_wiener_stats_frame is av1_compute_stats_c / av1_compute_stats_highbd_c (:765-858) per unit of every plane: the truncating
+ * average of the unit of d_cdef (find_average, EbRestorationPick.h:33), X = src - avg, the win x win window of d_cdef - avg indexed
+ * k-major as written (:781-786: column offset outer, row offset inner), M[win2] and the full symmetric H[win2 * win2]; at 10 bit the
+ * truncating division by 4 of M and of H's upper triangle before mirroring (:850-857).  Window reads outside the picture clamp (the
+ * reference runs on the frame extended by 3); the stripe rule plays no part here.  wiener_win[plane]: 7, 5 or 3.  d_M [unit][49] and
+ * d_H [unit][49 * 49] int64, each unit's block dense at win2 as the reference packs it; unit = svt_hip_lr_unit_offset + index, per
+ * picture svt_hip_lr_units_per_pic records.  d_scratch: svt_hip_lr_stats_scratch_bytes(..) bytes, 8-byte aligned.
+ *
+ * Every call validates every host argument before anything is enqueued, only enqueues on the given stream, allocates nothing, never
+ * synchronises and can be captured into a HIP graph.  svt_hip_lr_check runs the validation without a device: what = 0 apply, 1 try,
+ * 2 statistics; h_units (may be NULL) is a HOST copy of the records ([plane][units], one picture, nunits of them) checked against
+ * frame_type: a type the frame type does not allow, taps outside WIENER_FILT_TAP{0,1,2}_{MINV,MAXV}, ep outside 0 .. 15, xqd outside
+ * SGRPROJ_PRJ_{MIN,MAX}{0,1}.  Validation (SVT_HIP_ERR_INVALID): NULL planes; a side that is 0, not a multiple of 8 or above 65 535; a
+ * stride below the width; a bit depth other than 8 / 10; a bad unit_size; a frame type outside 0 .. 3; a window other than 7 / 5 / 3;
+ * npics 0; an output plane that overlaps an input plane; in a stack an output pitch below one picture; misaligned 64-bit outputs.
+ * NOT here: the self-guided parameter search (EbRestorationPick.c:605-661; the Wiener derivation, the refinement walk and the
+ * picture-level finish are host helpers, below); more than one tile, superres, optimized_lr, bit depth 12, 4:2:2 / 4:4:4. */
+typedef struct svt_hip_lr_unit {
+    int32_t type;                       /* 0 none, 1 Wiener, 2 self-guided */
+    int16_t vfilter[3], hfilter[3];     /* taps 0 .. 2 */
+    int16_t xqd[2];
+    int32_t ep;                         /* 0 .. 15 */
+} svt_hip_lr_unit;
+typedef struct svt_hip_lr_cand { uint32_t pic, plane, unit; svt_hip_lr_unit u; } svt_hip_lr_cand;
+typedef struct svt_hip_lr_pic {
+    const void *d_cdef[3]; uint32_t cdef_stride[3]; uint32_t pad0;   /* the CDEF output: the filter's input; strides in samples */
+    const void *d_dblk[3]; uint32_t dblk_stride[3]; uint32_t pad1;   /* the deblocked picture before CDEF: stripe context only */
+    const void *d_src[3];  uint32_t src_stride[3];  uint32_t pad2;   /* the source picture (try and statistics) */
+    void *d_dst[3];        uint32_t dst_stride[3];  uint32_t pad3;   /* the restored picture (apply only) */
+    uint32_t width, height;
+    int32_t bit_depth;
+    uint32_t unit_size[3];
+    uint32_t npics;                                                  /* >= 1 */
+    uint32_t pad4;
+    uint64_t cdef_pitch[3], dblk_pitch[3], src_pitch[3], dst_pitch[3];      /* samples between the pictures of a stack */
+} svt_hip_lr_pic;
+int svt_hip_lr_apply_frame(const svt_hip_lr_pic *pic, const int32_t frame_type[3], const svt_hip_lr_unit *d_units, void *stream);
+int svt_hip_lr_try_frame(const svt_hip_lr_pic *pic, const svt_hip_lr_cand *d_cand, uint32_t ncand, int64_t *d_sse, void *stream);
+int svt_hip_lr_wiener_stats_frame(const svt_hip_lr_pic *pic, const int32_t wiener_win[3], int64_t *d_M, int64_t *d_H, void *d_scratch,
+                                  size_t scratch_bytes, void *stream);
+size_t svt_hip_lr_stats_scratch_bytes(uint32_t width, uint32_t height, const uint32_t unit_size[3], uint32_t npics);      /* HOST; 0 = refused */
+int svt_hip_lr_check(const svt_hip_lr_pic *pic, int what, const int32_t frame_type[3], const svt_hip_lr_unit *h_units, uint32_t nunits);   /* HOST */
+/* HOST: the unit grid of a plane: out = {horz_units_per_tile, vert_units_per_tile, units_per_tile}; the limits of unit `index`
+ * (row-major): out = {h_start, h_end, v_start, v_end}; where a plane's records start inside a picture's block, and that block's size */
+int svt_hip_lr_unit_grid(uint32_t width, uint32_t height, const uint32_t unit_size[3], int plane, int32_t out[3]);
+int svt_hip_lr_unit_limits(uint32_t width, uint32_t height, const uint32_t unit_size[3], int plane, uint32_t index, int32_t out[4]);
+uint32_t svt_hip_lr_unit_offset(uint32_t width, uint32_t height, const uint32_t unit_size[3], int plane);      /* 0 for a refused geometry */
+uint32_t svt_hip_lr_units_per_pic(uint32_t width, uint32_t height, const uint32_t unit_size[3]);
+
+/* HOST helpers of the Wiener search, no device, integer arithmetic as in the reference.
+ * svt_hip_lr_wiener_solve: wiener_decompose_sep_sym (EbRestorationPick.c:1021-1052; update_a_sep_sym / update_b_sep_sym / linsolve_wiener,
+ * NUM_WIENER_ITERS 5, WIENER_TAP_SCALE_FACTOR 2^16, the c / 256 * A / cd * 256 elimination), finalize_sym_filter (:1094-1126, with the
+ * shuffle of the 5- and 3-tap windows) and compute_score (:1053-1092) on one unit's M [win2] / H [win2 * win2] as
+ * svt_hip_lr_wiener_stats_frame packs them: taps 0 .. 2 of the vertical and the horizontal filter, and *accepted = 0 when the score is
+ * above 0 (search_wiener_seg then leaves the unit's Wiener SSE at INT64_MAX and tries nothing), else 1.
+ * svt_hip_lr_walk_start / _next: finer_tile_search_wiener_seg (:1278-1387) turned inside out.  start takes the solve's taps and
+ * returns SVT_HIP_LR_WALK_TRY: the caller measures the taps in w->vfilter / w->hfilter (svt_hip_lr_try_frame) and hands the SSE to
+ * next, which answers SVT_HIP_LR_WALK_TRY with the next taps to measure or SVT_HIP_LR_WALK_DONE with the final taps in the same place
+ * and their SSE in w->err.  start_step 4; per step the horizontal taps, then the vertical ones, from the window's first tap (plane_off);
+ * a successful downward move ends that tap loop (`if (skip) break;`); at step 4 a successful move is repeated; err2 > err rejects, so a tie
+ * is accepted.  The walk makes no device call; many units' walks advance in lock step with one svt_hip_lr_try_frame per round. */
+#define SVT_HIP_LR_WALK_TRY 1
+#define SVT_HIP_LR_WALK_DONE 2
+typedef struct svt_hip_lr_walk {
+    int16_t vfilter[3], hfilter[3];     /* the taps to measure (TRY) or the final taps (DONE) */
+    int32_t win, step, dir, p, phase, skip, state;      /* the walk's position: private to the two functions */
+    int64_t err;                        /* the SSE of the taps kept so far */
+} svt_hip_lr_walk;
+int svt_hip_lr_wiener_solve(int win, const int64_t *M, const int64_t *H, int16_t vfilter[3], int16_t hfilter[3], int *accepted);
+int svt_hip_lr_walk_start(svt_hip_lr_walk *w, int win, const int16_t vfilter[3], const int16_t hfilter[3]);
+int svt_hip_lr_walk_next(svt_hip_lr_walk *w, int64_t sse);
+
+/* svt_hip_lr_finish: rest_finish_search (EbRestorationPick.c:1989-2058) for one plane, on the host.  results[u]: what the unit's searches
+ * left in RestUnitSearchInfo - sse[0] of the unfiltered unit (search_norestore_seg), sse[1] and the taps of the Wiener search (INT64_MAX =
+ * compute_score refused), sse[2], ep and xqd of the self-guided search (input data here: that search is not built).  Mirrored as written:
+ * force_restore_type_d (wn_filter_mode 0 allows none and self-guided only); num_rtypes = RESTORE_SWITCHABLE_TYPES when the plane has one
+ * unit, so such a plane never ends switchable; per frame type search_rest_type_finish over the units in index order with the running
+ * reference filters rsc->wiener / rsc->sgrproj reset to their defaults by rsc_on_tile; count_wiener_bits / count_sgrproj_bits with
+ * aom_count_primitive_refsubexpfin (EbEntropyCoding.c:3293-3460); bits >> 4 inside RDCOST_DBL (binary64); search_wiener_finish's window
+ * from wn_filter_mode and the plane, search_switchable's WIENER_WIN for luma whatever the mode (:1518-1519); r == 0 || cost < best_cost;
+ * copy_unit_info into units[u] (all zero when the plane ends RESTORE_NONE).  *frame_restoration_type and units are what
+ * svt_hip_lr_apply_frame takes for the plane. */
+typedef struct svt_hip_lr_result {
+    int64_t sse[3];                     /* none, Wiener (INT64_MAX = refused), self-guided */
+    int16_t vfilter[3], hfilter[3];     /* taps 0 .. 2 of the Wiener search */
+    int16_t xqd[2];
+    int32_t ep;
+    int32_t pad;
+} svt_hip_lr_result;
+typedef struct svt_hip_lr_costs {
+    int32_t rdmult;
+    int32_t wiener_restore_cost[2], sgrproj_restore_cost[2], switchable_restore_cost[3];
+} svt_hip_lr_costs;
+int svt_hip_lr_finish(int plane, int wn_filter_mode, const svt_hip_lr_costs *costs, const svt_hip_lr_result *results, uint32_t nunits,
+                      int32_t *frame_restoration_type, svt_hip_lr_unit *units);
 
 /* ---- dispatch registration ---------------------------------------------------------------------------------------
  * The library keeps a registry {reference slot name -> drop-in of the same signature} for every RTCD global of
