@@ -268,6 +268,16 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_lr_finish.argtypes = [c_int, c_int, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]
     for name in ("wiener_solve", "walk_start", "walk_next", "finish"):
         getattr(L, "svt_hip_lr_" + name).restype = c_int
+    L.svt_hip_lr_sgr_stats_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_lr_sgr_walk_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
+    L.svt_hip_lr_sgr_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.svt_hip_lr_sgr_solve.argtypes = [c_void_p, c_uint32, c_int, c_void_p]
+    L.svt_hip_lr_sgr_walk_host.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_int]
+    L.svt_hip_lr_sgr_ep_range.argtypes = [c_void_p, c_int, c_void_p]
+    for name in ("sgr_stats_frame", "sgr_walk_frame", "sgr_search_frame", "sgr_solve", "sgr_walk_host", "sgr_ep_range"):
+        getattr(L, "svt_hip_lr_" + name).restype = c_int
+    L.svt_hip_lr_sgr_scratch_bytes.argtypes = [c_uint32, c_uint32, c_void_p, c_uint32, c_int, c_int]
+    L.svt_hip_lr_sgr_scratch_bytes.restype = c_size_t
     L.svt_hip_lr_stats_scratch_bytes.argtypes = [c_uint32, c_uint32, c_void_p, c_uint32]
     L.svt_hip_lr_stats_scratch_bytes.restype = c_size_t
     for name in ("unit_offset", "units_per_pic"):
@@ -2933,6 +2943,144 @@ class SvtHipDsp:
                     taps[u], sse[u] = list(w.vfilter) + list(w.hfilter), w.err
                     del walks[u]
         return taps, sse, rounds
+
+    # -- the self-guided parameter search: search_sgrproj_seg -> search_selfguided_restoration per unit ------------------------------
+    LR_SGR_WALK_DTYPE = [("err", "<i8"), ("xqd", "<i2", 2), ("start", "<i2", 2), ("evals", "<i4"), ("pad", "<i4")]                         # svt_hip_lr_sgr_walk
+    LR_SGR_BEST_DTYPE = [("sse", "<i8"), ("proj_err", "<i8"), ("ep", "<i4"), ("xqd", "<i2", 2)]        # svt_hip_lr_sgr_best
+    LR_SGR_MAX_EVALS = 137
+
+    def lr_sgr_scratch_bytes(self, width, height, unit_size, npics=1, ep_lo=0, ep_hi=16):
+        """svt_hip_lr_sgr_scratch_bytes (a host computation; 0 for a geometry or a range the calls refuse)"""
+        us = (c_uint32 * 3)(*[int(v) for v in unit_size])
+        return self.lib.svt_hip_lr_sgr_scratch_bytes(int(width), int(height), us, int(npics), int(ep_lo), int(ep_hi))
+
+    def _lr_sgr_scratch(self, scratch, width, height, unit_size, npics, ep_lo, ep_hi, device):
+        if scratch is None:
+            need = self.lr_sgr_scratch_bytes(width, height, unit_size, npics, ep_lo, ep_hi)
+            scratch = self.torch.empty((max(need, 16),), dtype=self.torch.uint8, device=device)
+        return scratch
+
+    def lr_sgr_stats_frame(self, cdef, src, width, height, bit_depth, unit_size, ep_lo=0, ep_hi=16, stats=None, scratch=None):
+        """svt_hip_lr_sgr_stats_frame (apply_sgr and the sums of get_proj_subspace per unit and ep of the range).
+        -> (stats int64 [(npics,) units per picture, 16, 5] = H00, H11, H01, C0, C1, zero outside the range when allocated here;
+        scratch: the uint8 tensor svt_hip_lr_sgr_walk_frame reads f1 / f2 / src - dat from)"""
+        t = self.torch
+        p = self.make_lr_pic(cdef, None, width, height, bit_depth, unit_size, src=src)
+        _, per_pic = self.lr_unit_grid(width, height, unit_size, self.lib)
+        lead = (p.npics,) if cdef[0].dim() == 3 else ()
+        if stats is None:
+            stats = t.zeros(lead + (per_pic, 16, 5), dtype=t.int64, device=cdef[0].device)
+        scratch = self._lr_sgr_scratch(scratch, width, height, unit_size, p.npics, ep_lo, ep_hi, cdef[0].device)
+        assert stats.is_contiguous() and stats.dtype == t.int64 and stats.numel() == p.npics * per_pic * 80
+        self._check(self.lib.svt_hip_lr_sgr_stats_frame(ctypes.addressof(p), int(ep_lo), int(ep_hi), self._p(stats), self._p(scratch),
+                                                        scratch.numel() * scratch.element_size(), self._stream()), "svt_hip_lr_sgr_stats_frame")
+        return stats, scratch
+
+    def lr_sgr_walk_frame(self, cdef, src, width, height, bit_depth, unit_size, scratch, ep_lo=0, ep_hi=16, stats=None, start=None, walk=None):
+        """svt_hip_lr_sgr_walk_frame (finer_search_pixel_proj_error per unit and ep of the range) on the scratch lr_sgr_stats_frame left for
+        the same range.  start: int16 [(npics,) units, 16, 2] on the device, or None: solved on the device from stats.
+        -> walk: uint8 [(npics,) units per picture, 16, 24], LR_SGR_WALK_DTYPE records (zero outside the range when allocated here)"""
+        t = self.torch
+        p = self.make_lr_pic(cdef, None, width, height, bit_depth, unit_size, src=src)
+        _, per_pic = self.lr_unit_grid(width, height, unit_size, self.lib)
+        lead = (p.npics,) if cdef[0].dim() == 3 else ()
+        if walk is None:
+            walk = t.zeros(lead + (per_pic, 16, 24), dtype=t.uint8, device=cdef[0].device)
+        assert walk.is_contiguous() and walk.dtype == t.uint8 and walk.numel() == p.npics * per_pic * 384
+        assert start is None or (start.is_contiguous() and start.dtype == t.int16 and start.numel() == p.npics * per_pic * 32)
+        assert stats is None or (stats.is_contiguous() and stats.dtype == t.int64 and stats.numel() == p.npics * per_pic * 80)
+        self._check(self.lib.svt_hip_lr_sgr_walk_frame(ctypes.addressof(p), int(ep_lo), int(ep_hi), None if stats is None else self._p(stats),
+                                                       None if start is None else self._p(start), self._p(scratch), scratch.numel() * scratch.element_size(),
+                                                       self._p(walk), self._stream()), "svt_hip_lr_sgr_walk_frame")
+        return walk
+
+    def lr_sgr_search_frame(self, cdef, dblk, src, width, height, bit_depth, unit_size, ep_lo=0, ep_hi=16, best=None, scratch=None):
+        """svt_hip_lr_sgr_search_frame (search_sgrproj_seg per unit: statistics, walk, the first lowest error of the range, the try of the
+        winner).  -> best: uint8 [(npics,) units per picture, 24], LR_SGR_BEST_DTYPE records"""
+        t = self.torch
+        p = self.make_lr_pic(cdef, dblk, width, height, bit_depth, unit_size, src=src)
+        _, per_pic = self.lr_unit_grid(width, height, unit_size, self.lib)
+        lead = (p.npics,) if cdef[0].dim() == 3 else ()
+        if best is None:
+            best = t.empty(lead + (per_pic, 24), dtype=t.uint8, device=cdef[0].device)
+        scratch = self._lr_sgr_scratch(scratch, width, height, unit_size, p.npics, ep_lo, ep_hi, cdef[0].device)
+        assert best.is_contiguous() and best.dtype == t.uint8 and best.numel() == p.npics * per_pic * 24
+        self._check(self.lib.svt_hip_lr_sgr_search_frame(ctypes.addressof(p), int(ep_lo), int(ep_hi), self._p(best), self._p(scratch),
+                                                         scratch.numel() * scratch.element_size(), self._stream()), "svt_hip_lr_sgr_search_frame")
+        return best
+
+    @staticmethod
+    def lr_sgr_solve(stats, npix, ep, lib=None):
+        """svt_hip_lr_sgr_solve (the tail of get_proj_subspace and encode_xq; no device needed).  stats: H00, H11, H01, C0, C1 -> [xqd0, xqd1]"""
+        import numpy as np
+        lib = lib if lib is not None else load_library()
+        s = np.ascontiguousarray(stats, np.int64)
+        assert s.size == 5
+        xqd = (ctypes.c_int16 * 2)()
+        rc = lib.svt_hip_lr_sgr_solve(s.ctypes.data, int(npix), int(ep), xqd)
+        if rc != SVT_HIP_OK:
+            raise SvtHipError(f"svt_hip_lr_sgr_solve = {rc}: {lib.svt_hip_last_error().decode()}")
+        return list(xqd)
+
+    @staticmethod
+    def lr_sgr_walk_host(f1, f2, sd, ep, xqd, lib=None):
+        """svt_hip_lr_sgr_walk_host (finer_search_pixel_proj_error over int16 arrays; no device needed)
+        -> (final xqd, its error, trials int64 [evaluations, 3]: xq0, xq1, error)"""
+        import numpy as np
+        lib = lib if lib is not None else load_library()
+        a = [np.ascontiguousarray(v, np.int16).reshape(-1) for v in (f1, f2, sd)]
+        assert a[0].size == a[1].size == a[2].size
+        x = (ctypes.c_int16 * 2)(*[int(v) for v in xqd])
+        err = ctypes.c_int64(0)
+        trials = np.zeros((SvtHipDsp.LR_SGR_MAX_EVALS, 3), np.int64)
+        n = lib.svt_hip_lr_sgr_walk_host(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[0].size, int(ep), x, ctypes.addressof(err),
+                                         trials.ctypes.data, len(trials))
+        if n <= 0:
+            raise SvtHipError(f"svt_hip_lr_sgr_walk_host = {n}: {lib.svt_hip_last_error().decode()}")
+        return list(x), err.value, trials[:n].copy()
+
+    @staticmethod
+    def lr_sgr_ep_range(sg_ref_frame_ep, sg_filter_mode, lib=None):
+        """svt_hip_lr_sgr_ep_range (get_sg_step and start_ep / end_ep; no device needed) -> (ep_lo, ep_hi)"""
+        lib = lib if lib is not None else load_library()
+        ref, out = (ctypes.c_int8 * 2)(*[int(v) for v in sg_ref_frame_ep]), (c_int32 * 2)()
+        rc = lib.svt_hip_lr_sgr_ep_range(ref, int(sg_filter_mode), out)
+        if rc != SVT_HIP_OK:
+            raise SvtHipError(f"svt_hip_lr_sgr_ep_range = {rc}: {lib.svt_hip_last_error().decode()}")
+        return out[0], out[1]
+
+    def lr_search_units(self, cdef, dblk, src, width, height, bit_depth, unit_size, wiener_win, sg_ref_frame_ep=(-1, -1), sg_filter_mode=4):
+        """The per-unit searches of one picture, what restoration_seg_search leaves in RestUnitSearchInfo: the unfiltered error
+        (search_norestore_seg, one svt_hip_lr_try_frame), the Wiener search (lr_wiener_search) and the self-guided search
+        (svt_hip_lr_sgr_search_frame over svt_hip_lr_sgr_ep_range's range).  -> (LR_RESULT_DTYPE records of the picture, the planes' blocks
+        one after another; sg_frame_ep_cnt int32 [16]: how many units' self-guided searches ended on each ep)"""
+        import numpy as np
+        assert cdef[0].dim() == 2, "one picture"
+        grids, per_pic = self.lr_unit_grid(width, height, unit_size, self.lib)
+        lo, hi = self.lr_sgr_ep_range(sg_ref_frame_ep, sg_filter_mode, self.lib)
+        best = self.lr_sgr_search_frame(cdef, dblk, src, width, height, bit_depth, unit_size, lo, hi)
+        none = np.zeros(per_pic, np.dtype(self.LR_CAND_DTYPE))
+        for plane, (nh, nv, off) in enumerate(grids):
+            none["plane"][off:off + nh * nv], none["unit"][off:off + nh * nv] = plane, np.arange(nh * nv)
+        sse0 = self.lr_try_frame(cdef, dblk, src, width, height, bit_depth, unit_size, none)
+        taps, wsse, _ = self.lr_wiener_search(cdef, dblk, src, width, height, bit_depth, unit_size, wiener_win)
+        best = best.cpu().numpy().view(np.dtype(self.LR_SGR_BEST_DTYPE)).reshape(-1)
+        res = np.zeros(per_pic, np.dtype(self.LR_RESULT_DTYPE))
+        res["sse"][:, 0], res["sse"][:, 1], res["sse"][:, 2] = sse0.cpu().numpy(), wsse, best["sse"]
+        res["vfilter"], res["hfilter"], res["ep"], res["xqd"] = taps[:, :3], taps[:, 3:], best["ep"], best["xqd"]
+        return res, np.bincount(best["ep"], minlength=16).astype(np.int32)
+
+    def lr_search(self, cdef, dblk, src, width, height, bit_depth, unit_size, wiener_win, wn_filter_mode, costs, sg_ref_frame_ep=(-1, -1), sg_filter_mode=4):
+        """The restoration search of one picture: lr_search_units, then svt_hip_lr_finish (rest_finish_search) per plane.
+        -> (frame types [3], LR_UNIT_DTYPE records of the picture for svt_hip_lr_apply_frame, sg_frame_ep_cnt int32 [16])"""
+        import numpy as np
+        grids, _ = self.lr_unit_grid(width, height, unit_size, self.lib)
+        res, cnt = self.lr_search_units(cdef, dblk, src, width, height, bit_depth, unit_size, wiener_win, sg_ref_frame_ep, sg_filter_mode)
+        types, units = [], []
+        for plane, (nh, nv, off) in enumerate(grids):
+            ft, un = self.lr_finish(plane, wn_filter_mode, costs, res[off:off + nh * nv], self.lib)
+            types.append(ft); units.append(un)
+        return types, np.concatenate(units), cnt
 
     @staticmethod
     def md_intra_candidates(bwidth, bheight, sq_size, bsize, intra_pred_mode=0, is_16bit=False):

@@ -91,8 +91,9 @@ struct LrLds {
 
 __device__ __forceinline__ uint32_t lr_rpot(uint32_t v, int n) { return (v + ((1u << n) >> 1)) >> n; }
 
-// the tile's samples with their halo: rows y0 - 3 .. y1 + 2, columns x0 - 3 .. x0 + tw + 2
-template <typename T>
+// the tile's samples with their halo: rows y0 - 3 .. y1 + 2, columns x0 - 3 .. x0 + tw + 2.  CDEF_ONLY: the halo rule of the parameter
+// search (kernel_lr_sgr.h), every row a row of the CDEF picture clamped to the plane; the deblocked picture is not touched
+template <typename T, bool CDEF_ONLY = false>
 __device__ __forceinline__ void lr_stage(const LrDev& F, LrLds<T>& L, int plane, uint32_t pic, int x0, int tw, int y0, int y1) {
     const LrPlane& P = F.pl[plane];
     const T* cdef = (const T*)F.cdef[plane] + pic * F.cdef_pitch[plane];
@@ -100,7 +101,7 @@ __device__ __forceinline__ void lr_stage(const LrDev& F, LrLds<T>& L, int plane,
     const int cols = tw + 2 * LR_B, n = (y1 - y0 + 2 * LR_B) * cols;
     for (int i = threadIdx.x; i < n; i += LR_NT) {
         const int lx = i % cols, ly = i / cols;
-        const svthost::LrRow hr = svthost::lr_halo_row(y0 - LR_B + ly, y0, y1, P.h);
+        const svthost::LrRow hr = CDEF_ONLY ? svthost::LrRow{svthost::lr_clamp(y0 - LR_B + ly, 0, P.h - 1), false} : svthost::lr_halo_row(y0 - LR_B + ly, y0, y1, P.h);
         const int x = svthost::lr_clamp(x0 - LR_B + lx, 0, P.w - 1);
         L.in[ly * LR_IN_P + lx] = hr.dblk ? dblk[(size_t)hr.row * F.dblk_stride[plane] + x] : cdef[(size_t)hr.row * F.cdef_stride[plane] + x];
     }
@@ -127,6 +128,54 @@ __device__ __forceinline__ void lr_sgr_ab(LrLds<T>& L, int tw, int rows, int r, 
         L.ab.A[ai * LR_AB_P + j] = (uint16_t)A;
         L.ab.B[ai * LR_AB_P + j] = lr_rpot((256u - A) * sum * one_by, 12);      // SGRPROJ_SGR, SGRPROJ_RECIP_BITS
     }
+}
+
+// The two passes of the self-guided filter (selfguided_restoration_fast_internal, :770-900; selfguided_restoration_internal, :902-1020)
+// on a staged tile, for the projection of apply / try (lr_filter_tile) and for the parameter search (kernel_lr_sgr.h).
+// lr_sgr_pass0: r[0] > 0 only; flt0[k] = the first pass at column threadIdx.x % tw, row threadIdx.x / tw + k * (256 / tw); it ends with
+// a barrier, after which the A / B planes may be rewritten.  lr_sgr_pass1_ab: r[1] > 0 only; the second pass's planes, ready for
+// lr_sgr_flt1 (one sample; px: the staged sample).  Every thread of the workgroup calls the first two.
+template <typename T>
+__device__ __forceinline__ void lr_sgr_pass0(LrLds<T>& L, int ep, int bd, int tw, int rows, int flt0[LR_PER_THREAD]) {
+    const int col = threadIdx.x % tw, row0 = threadIdx.x / tw, rstep = LR_NT / tw;
+    lr_sgr_ab<T, true>(L, tw, rows, kSgrR[ep][0], (uint32_t)kSgrS[ep][0], bd);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < LR_PER_THREAD; k++) {
+        const int row = row0 + k * rstep;
+        flt0[k] = 0;
+        if (row < rows) {
+            const int c = (row + 1) * LR_AB_P + col + 1, px = (int)L.in[(row + LR_B) * LR_IN_P + col + LR_B];
+            const uint16_t* A = L.ab.A; const uint32_t* B = L.ab.B;
+            if (!(row & 1)) {      // even row: the A / B rows above and below
+                const int a = ((int)A[c - LR_AB_P] + (int)A[c + LR_AB_P]) * 6 +
+                              ((int)A[c - 1 - LR_AB_P] + (int)A[c - 1 + LR_AB_P] + (int)A[c + 1 - LR_AB_P] + (int)A[c + 1 + LR_AB_P]) * 5;
+                const int b = ((int)B[c - LR_AB_P] + (int)B[c + LR_AB_P]) * 6 +
+                              ((int)B[c - 1 - LR_AB_P] + (int)B[c - 1 + LR_AB_P] + (int)B[c + 1 - LR_AB_P] + (int)B[c + 1 + LR_AB_P]) * 5;
+                flt0[k] = (a * px + b + (1 << 8)) >> 9;
+            } else {
+                const int a = (int)A[c] * 6 + ((int)A[c - 1] + (int)A[c + 1]) * 5;
+                const int b = (int)B[c] * 6 + ((int)B[c - 1] + (int)B[c + 1]) * 5;
+                flt0[k] = (a * px + b + (1 << 7)) >> 8;
+            }
+        }
+    }
+    __syncthreads();                                                // the planes are reused
+}
+template <typename T>
+__device__ __forceinline__ void lr_sgr_pass1_ab(LrLds<T>& L, int ep, int bd, int tw, int rows) {
+    lr_sgr_ab<T, false>(L, tw, rows, kSgrR[ep][1], (uint32_t)kSgrS[ep][1], bd);
+    __syncthreads();
+}
+template <typename T>
+__device__ __forceinline__ int lr_sgr_flt1(const LrLds<T>& L, int row, int col, int px) {
+    const int c = (row + 1) * LR_AB_P + col + 1;
+    const uint16_t* A = L.ab.A; const uint32_t* B = L.ab.B;
+    const int a = ((int)A[c] + (int)A[c - 1] + (int)A[c + 1] + (int)A[c - LR_AB_P] + (int)A[c + LR_AB_P]) * 4 +
+                  ((int)A[c - 1 - LR_AB_P] + (int)A[c - 1 + LR_AB_P] + (int)A[c + 1 - LR_AB_P] + (int)A[c + 1 + LR_AB_P]) * 3;
+    const int b = ((int)B[c] + (int)B[c - 1] + (int)B[c + 1] + (int)B[c - LR_AB_P] + (int)B[c + LR_AB_P]) * 4 +
+                  ((int)B[c - 1 - LR_AB_P] + (int)B[c - 1 + LR_AB_P] + (int)B[c + 1 - LR_AB_P] + (int)B[c + 1 + LR_AB_P]) * 3;
+    return (a * px + b + (1 << 8)) >> 9;
 }
 
 // Filters the staged tile under record R: out[k] = the restored sample at column threadIdx.x % tw, row threadIdx.x / tw + k * (256 /
@@ -172,40 +221,13 @@ __device__ __forceinline__ void lr_filter_tile(LrLds<T>& L, const LrRec& R, int 
     // apply_selfguided_restoration_c (:1062-1099)
     const int r0 = kSgrR[R.ep][0], r1 = kSgrR[R.ep][1];
     int flt0[LR_PER_THREAD];
-    if (r0 > 0) {
-        lr_sgr_ab<T, true>(L, tw, rows, r0, (uint32_t)kSgrS[R.ep][0], bd);
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < LR_PER_THREAD; k++) {
-            const int row = row0 + k * rstep;
-            flt0[k] = 0;
-            if (row < rows) {
-                const int c = (row + 1) * LR_AB_P + col + 1, px = (int)L.in[(row + LR_B) * LR_IN_P + col + LR_B];
-                const uint16_t* A = L.ab.A; const uint32_t* B = L.ab.B;
-                if (!(row & 1)) {      // even row: the A / B rows above and below
-                    const int a = ((int)A[c - LR_AB_P] + (int)A[c + LR_AB_P]) * 6 +
-                                  ((int)A[c - 1 - LR_AB_P] + (int)A[c - 1 + LR_AB_P] + (int)A[c + 1 - LR_AB_P] + (int)A[c + 1 + LR_AB_P]) * 5;
-                    const int b = ((int)B[c - LR_AB_P] + (int)B[c + LR_AB_P]) * 6 +
-                                  ((int)B[c - 1 - LR_AB_P] + (int)B[c - 1 + LR_AB_P] + (int)B[c + 1 - LR_AB_P] + (int)B[c + 1 + LR_AB_P]) * 5;
-                    flt0[k] = (a * px + b + (1 << 8)) >> 9;
-                } else {
-                    const int a = (int)A[c] * 6 + ((int)A[c - 1] + (int)A[c + 1]) * 5;
-                    const int b = (int)B[c] * 6 + ((int)B[c - 1] + (int)B[c + 1]) * 5;
-                    flt0[k] = (a * px + b + (1 << 7)) >> 8;
-                }
-            }
-        }
-        __syncthreads();                                                // the planes are reused
-    }
+    if (r0 > 0) lr_sgr_pass0<T>(L, R.ep, bd, tw, rows, flt0);
     // decode_xq (:727-740)
     int xq0, xq1;
     if (r0 == 0) { xq0 = 0; xq1 = 128 - R.xqd[1]; }
     else if (r1 == 0) { xq0 = R.xqd[0]; xq1 = 0; }
     else { xq0 = R.xqd[0]; xq1 = 128 - xq0 - R.xqd[1]; }
-    if (r1 > 0) {
-        lr_sgr_ab<T, false>(L, tw, rows, r1, (uint32_t)kSgrS[R.ep][1], bd);
-        __syncthreads();
-    }
+    if (r1 > 0) lr_sgr_pass1_ab<T>(L, R.ep, bd, tw, rows);
 #pragma unroll
     for (int k = 0; k < LR_PER_THREAD; k++) {
         const int row = row0 + k * rstep;
@@ -216,13 +238,7 @@ __device__ __forceinline__ void lr_filter_tile(LrLds<T>& L, const LrRec& R, int 
             int v = u << 7;                                             // SGRPROJ_PRJ_BITS
             if (r0 > 0) v += xq0 * (flt0[k] - u);
             if (r1 > 0) {
-                const int c = (row + 1) * LR_AB_P + col + 1;
-                const uint16_t* A = L.ab.A; const uint32_t* B = L.ab.B;
-                const int a = ((int)A[c] + (int)A[c - 1] + (int)A[c + 1] + (int)A[c - LR_AB_P] + (int)A[c + LR_AB_P]) * 4 +
-                              ((int)A[c - 1 - LR_AB_P] + (int)A[c - 1 + LR_AB_P] + (int)A[c + 1 - LR_AB_P] + (int)A[c + 1 + LR_AB_P]) * 3;
-                const int b = ((int)B[c] + (int)B[c - 1] + (int)B[c + 1] + (int)B[c - LR_AB_P] + (int)B[c + LR_AB_P]) * 4 +
-                              ((int)B[c - 1 - LR_AB_P] + (int)B[c - 1 + LR_AB_P] + (int)B[c + 1 - LR_AB_P] + (int)B[c + 1 + LR_AB_P]) * 3;
-                const int flt1 = (a * px + b + (1 << 8)) >> 9;
+                const int flt1 = lr_sgr_flt1<T>(L, row, col, px);
                 v += xq1 * (flt1 - u);
             }
             out[k] = svthost::lr_clamp((int)(int16_t)((v + (1 << 10)) >> 11), 0, maxv);

@@ -10,6 +10,7 @@
 
 #include "host_err.h"
 #include "lr_plan.h"
+#include "lr_sgr_solve.h"
 
 namespace svthost {
 
@@ -433,3 +434,43 @@ extern "C" int svt_hip_lr_walk_start(svt_hip_lr_walk* w, int win, const int16_t 
     return svthost::lr_walk_start(w, win, vfilter, hfilter);
 }
 extern "C" int svt_hip_lr_walk_next(svt_hip_lr_walk* w, int64_t sse) { return svthost::lr_walk_next(w, sse); }
+
+// ---- the self-guided parameter search's host side: lr_sgr_solve.h's text behind the C ABI -------------------------------------------
+extern "C" int svt_hip_lr_sgr_solve(const int64_t stats[5], uint32_t npix, int ep, int16_t xqd[2]) {
+    using namespace svthost;
+    if (!stats || !xqd || ep < 0 || ep >= LR_SGR_PARAMS || npix == 0 || npix > 0x7fffffffu)
+        return set_err(SVT_HIP_ERR_INVALID, "ep %d (0 .. 15), %u samples or a NULL argument", ep, npix);
+    int v[2];
+    lr_sgr_solve(stats, npix, ep, v);
+    xqd[0] = (int16_t)v[0]; xqd[1] = (int16_t)v[1];
+    return SVT_HIP_OK;
+}
+
+extern "C" int svt_hip_lr_sgr_walk_host(const int16_t* f1, const int16_t* f2, const int16_t* sd, uint32_t n, int ep, int16_t xqd[2], int64_t* err,
+                                        int64_t* trials, int max_trials) {
+    using namespace svthost;
+    if (!f1 || !f2 || !sd || !xqd || !err || n == 0 || ep < 0 || ep >= LR_SGR_PARAMS || (trials && max_trials < 0))
+        return set_err(SVT_HIP_ERR_INVALID, "ep %d (0 .. 15), %u samples or a NULL argument", ep, n);
+    int v[2] = {xqd[0], xqd[1]};
+    for (int p = 0; p < 2; p++)
+        if (v[p] < lr_sgr_xqd_min(p) || v[p] > lr_sgr_xqd_max(p)) return set_err(SVT_HIP_ERR_INVALID, "xqd[%d] = %d (%d .. %d)", p, v[p], lr_sgr_xqd_min(p), lr_sgr_xqd_max(p));
+    int made = 0, evals = 0;
+    const auto eval = [&](int xq0, int xq1) -> int64_t {
+        int64_t e = 0;
+        for (uint32_t i = 0; i < n; i++) e += lr_sgr_sample_err(xq0, xq1, f1[i], f2[i], sd[i]);
+        if (trials && made < max_trials) { trials[3 * made] = xq0; trials[3 * made + 1] = xq1; trials[3 * made + 2] = e; }
+        made++;
+        return e;
+    };
+    *err = lr_sgr_walk(ep, v, eval, LR_SGR_MAX_EVALS, &evals);
+    xqd[0] = (int16_t)v[0]; xqd[1] = (int16_t)v[1];
+    return evals;
+}
+
+extern "C" int svt_hip_lr_sgr_ep_range(const int8_t sg_ref_frame_ep[2], int sg_filter_mode, int32_t out[2]) {
+    using namespace svthost;
+    if (!sg_ref_frame_ep || !out || sg_ref_frame_ep[0] >= LR_SGR_PARAMS || sg_ref_frame_ep[1] >= LR_SGR_PARAMS)
+        return set_err(SVT_HIP_ERR_INVALID, "a NULL argument or a reference ep above 15");
+    lr_sgr_ep_range(sg_ref_frame_ep[0], sg_ref_frame_ep[1], sg_filter_mode, out);
+    return SVT_HIP_OK;
+}

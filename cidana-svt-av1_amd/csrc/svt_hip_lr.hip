@@ -5,6 +5,7 @@
 
 #include "host_common.h"
 #include "kernel_lr.h"
+#include "kernel_lr_sgr.h"
 
 using namespace svtdev;
 using namespace svthost;
@@ -31,6 +32,7 @@ static LrDev lr_dev(const svt_hip_lr_pic* p) {
 }
 
 extern "C" int svt_hip_lr_check(const svt_hip_lr_pic* pic, int what, const int32_t frame_type[3], const svt_hip_lr_unit* h_units, uint32_t nunits) {
+    if (what == LR_SGR_STATS_WALK || what == LR_SGR_SEARCH) return lr_sgr_pic_check(pic, what);
     return lr_check(pic, what, frame_type, h_units, nunits);
 }
 extern "C" size_t svt_hip_lr_stats_scratch_bytes(uint32_t width, uint32_t height, const uint32_t unit_size[3], uint32_t npics) {
@@ -75,18 +77,21 @@ extern "C" int svt_hip_lr_apply_frame(const svt_hip_lr_pic* pic, const int32_t f
     return launch_status("lr_apply_frame");
 }
 
-extern "C" int svt_hip_lr_try_frame(const svt_hip_lr_pic* pic, const svt_hip_lr_cand* d_cand, uint32_t ncand, int64_t* d_sse, void* stream) {
-    if (int rc = require_init()) return rc;
-    if (int rc = lr_try_check(pic, d_cand, ncand, d_sse)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    LrDev d = lr_dev(pic);
+// the two launches of a try, for arguments the caller has checked
+static int lr_try_enqueue(LrDev d, const void* d_cand, uint32_t ncand, void* d_sse, hipStream_t s) {
     d.cand = (const uint32_t*)d_cand; d.sse = (unsigned long long*)d_sse;
     for (int i = 0; i < 3; i++) d.try_tiles = umax(d.try_tiles, lr_try_tiles(d.pl[i]));
     hipLaunchKernelGGL(lr_zero_kernel, dim3((ncand + LR_NT - 1) / LR_NT), dim3(LR_NT), 0, s, d.sse, (size_t)ncand);
     if (int rc = launch_status("lr_try_frame (zero)")) return rc;
-    if (pic->bit_depth == 8) hipLaunchKernelGGL(lr_try_kernel<uint8_t>, dim3(ncand * d.try_tiles), dim3(LR_NT), 0, s, d);
+    if (d.bd == 8) hipLaunchKernelGGL(lr_try_kernel<uint8_t>, dim3(ncand * d.try_tiles), dim3(LR_NT), 0, s, d);
     else hipLaunchKernelGGL(lr_try_kernel<uint16_t>, dim3(ncand * d.try_tiles), dim3(LR_NT), 0, s, d);
     return launch_status("lr_try_frame");
+}
+
+extern "C" int svt_hip_lr_try_frame(const svt_hip_lr_pic* pic, const svt_hip_lr_cand* d_cand, uint32_t ncand, int64_t* d_sse, void* stream) {
+    if (int rc = require_init()) return rc;
+    if (int rc = lr_try_check(pic, d_cand, ncand, d_sse)) return rc;
+    return lr_try_enqueue(lr_dev(pic), d_cand, ncand, d_sse, (hipStream_t)stream);
 }
 
 template <typename T>
@@ -120,4 +125,76 @@ extern "C" int svt_hip_lr_wiener_stats_frame(const svt_hip_lr_pic* pic, const in
     if (int rc = pic->bit_depth == 8 ? lr_stats_launch<uint8_t>(d, units, s) : lr_stats_launch<uint16_t>(d, units, s)) return rc;
     hipLaunchKernelGGL(lr_stats_finish_kernel, dim3(units), dim3(LR_NT), 0, s, d);
     return launch_status("lr_wiener_stats_frame (finish)");
+}
+
+// ---- the self-guided parameter search ---------------------------------------------------------------------------------------------
+static_assert(sizeof(svt_hip_lr_sgr_walk) == sizeof(LrSgrWalkRec) && offsetof(svt_hip_lr_sgr_walk, xqd) == 8 && offsetof(svt_hip_lr_sgr_walk, start) == 12 && offsetof(svt_hip_lr_sgr_walk, evals) == 16 &&
+              sizeof(svt_hip_lr_sgr_best) == sizeof(LrSgrBestRec) && offsetof(svt_hip_lr_sgr_best, ep) == 16 && offsetof(svt_hip_lr_sgr_best, xqd) == 20,
+              "the kernels write svt_hip_lr_sgr_walk / svt_hip_lr_sgr_best through lr_sgr_plan.h's records");
+
+static LrSgrDev lr_sgr_dev(const svt_hip_lr_pic* p, int ep_lo, int ep_hi, void* d_scratch) {
+    const LrSgrLayout l = lr_sgr_layout(p->width, p->height, p->unit_size, p->npics, ep_lo, ep_hi);
+    LrSgrDev g;
+    memset(&g, 0, sizeof(g));
+    g.ep_lo = ep_lo; g.ep_hi = ep_hi; g.S = l.S;
+    g.sd = (short*)((char*)d_scratch + l.sd); g.f = (uint32_t*)((char*)d_scratch + l.f);
+    return g;
+}
+static int lr_sgr_stats_enqueue(const LrDev& d, const LrSgrDev& g, hipStream_t s) {
+    if (g.ep_lo == g.ep_hi) return SVT_HIP_OK;
+    const size_t n = (size_t)d.npics * d.units_per_pic * (size_t)(g.ep_hi - g.ep_lo) * LR_SGR_STATS;
+    hipLaunchKernelGGL(lr_sgr_zero_kernel, dim3((uint32_t)((n + LR_NT - 1) / LR_NT)), dim3(LR_NT), 0, s, d, g);
+    if (int rc = launch_status("lr_sgr_stats_frame (zero)")) return rc;
+    uint32_t tiles = 0;
+    for (int i = 0; i < 3; i++) tiles = umax(tiles, (uint32_t)(d.pl[i].ntx * d.pl[i].nstripes));
+    if (d.bd == 8) hipLaunchKernelGGL(lr_sgr_stats_kernel<uint8_t>, dim3(tiles, 3, d.npics), dim3(LR_NT), 0, s, d, g);
+    else hipLaunchKernelGGL(lr_sgr_stats_kernel<uint16_t>, dim3(tiles, 3, d.npics), dim3(LR_NT), 0, s, d, g);
+    return launch_status("lr_sgr_stats_frame");
+}
+static int lr_sgr_walk_enqueue(const LrDev& d, const LrSgrDev& g, hipStream_t s) {
+    if (g.ep_lo == g.ep_hi) return SVT_HIP_OK;
+    hipLaunchKernelGGL(lr_sgr_walk_kernel, dim3(d.npics * d.units_per_pic * (uint32_t)(g.ep_hi - g.ep_lo)), dim3(LR_SGR_NT), 0, s, d, g);
+    return launch_status("lr_sgr_walk_frame");
+}
+
+extern "C" size_t svt_hip_lr_sgr_scratch_bytes(uint32_t width, uint32_t height, const uint32_t unit_size[3], uint32_t npics, int ep_lo, int ep_hi) {
+    return lr_sgr_scratch_bytes(width, height, unit_size, npics, ep_lo, ep_hi);
+}
+
+extern "C" int svt_hip_lr_sgr_stats_frame(const svt_hip_lr_pic* pic, int ep_lo, int ep_hi, int64_t* d_stats, void* d_scratch, size_t scratch_bytes, void* stream) {
+    if (int rc = require_init()) return rc;
+    if (int rc = lr_sgr_stats_check(pic, ep_lo, ep_hi, d_stats, d_scratch, scratch_bytes)) return rc;
+    LrSgrDev g = lr_sgr_dev(pic, ep_lo, ep_hi, d_scratch);
+    g.stats = (long long*)d_stats;
+    return lr_sgr_stats_enqueue(lr_dev(pic), g, (hipStream_t)stream);
+}
+
+extern "C" int svt_hip_lr_sgr_walk_frame(const svt_hip_lr_pic* pic, int ep_lo, int ep_hi, const int64_t* d_stats, const int16_t* d_start, const void* d_scratch,
+                                         size_t scratch_bytes, svt_hip_lr_sgr_walk* d_walk, void* stream) {
+    if (int rc = require_init()) return rc;
+    if (int rc = lr_sgr_walk_check(pic, ep_lo, ep_hi, d_stats, d_start, d_scratch, scratch_bytes, d_walk)) return rc;
+    LrSgrDev g = lr_sgr_dev(pic, ep_lo, ep_hi, (void*)d_scratch);
+    g.stats = (long long*)d_stats; g.start = d_start; g.walk = (LrSgrWalkRec*)d_walk;
+    return lr_sgr_walk_enqueue(lr_dev(pic), g, (hipStream_t)stream);
+}
+
+extern "C" int svt_hip_lr_sgr_search_frame(const svt_hip_lr_pic* pic, int ep_lo, int ep_hi, svt_hip_lr_sgr_best* d_best, void* d_scratch, size_t scratch_bytes,
+                                           void* stream) {
+    if (int rc = require_init()) return rc;
+    if (int rc = lr_sgr_search_check(pic, ep_lo, ep_hi, d_best, d_scratch, scratch_bytes)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const LrSgrLayout l = lr_sgr_layout(pic->width, pic->height, pic->unit_size, pic->npics, ep_lo, ep_hi);
+    const LrDev d = lr_dev(pic);
+    LrSgrDev g = lr_sgr_dev(pic, ep_lo, ep_hi, d_scratch);
+    char* base = (char*)d_scratch;
+    g.stats = (long long*)(base + l.stats); g.walk = (LrSgrWalkRec*)(base + l.walk); g.best = (LrSgrBestRec*)d_best;
+    g.cand = (uint32_t*)(base + l.cand); g.sse = (const long long*)(base + l.sse);
+    if (int rc = lr_sgr_stats_enqueue(d, g, s)) return rc;
+    if (int rc = lr_sgr_walk_enqueue(d, g, s)) return rc;
+    const uint32_t units = d.npics * d.units_per_pic;
+    hipLaunchKernelGGL(lr_sgr_pick_kernel, dim3((units + LR_NT - 1) / LR_NT), dim3(LR_NT), 0, s, d, g);
+    if (int rc = launch_status("lr_sgr_search_frame (pick)")) return rc;
+    if (int rc = lr_try_enqueue(d, g.cand, units, base + l.sse, s)) return rc;
+    hipLaunchKernelGGL(lr_sgr_sse_kernel, dim3((units + LR_NT - 1) / LR_NT), dim3(LR_NT), 0, s, d, g);
+    return launch_status("lr_sgr_search_frame (sse)");
 }

@@ -2433,8 +2433,8 @@ int svt_hip_dlf_level_from_q(int base_qindex, int bit_depth, int is_key_frame, i
  * SGRPROJ_PRJ_{MIN,MAX}{0,1}.  Validation (SVT_HIP_ERR_INVALID): NULL planes; a side that is 0, not a multiple of 8 or above 65 535; a
  * stride below the width; a bit depth other than 8 / 10; a bad unit_size; a frame type outside 0 .. 3; a window other than 7 / 5 / 3;
  * npics 0; an output plane that overlaps an input plane; in a stack an output pitch below one picture; misaligned 64-bit outputs.
- * NOT here: the self-guided parameter search (EbRestorationPick.c:605-661; the Wiener derivation, the refinement walk and the
- * picture-level finish are host helpers, below); more than one tile, superres, optimized_lr, bit depth 12, 4:2:2 / 4:4:4. */
+ * NOT here (the Wiener derivation, its refinement walk and the picture-level finish are host helpers, and the self-guided parameter
+ * search has its own calls, both below): more than one tile, superres, optimized_lr, bit depth 12, 4:2:2 / 4:4:4. */
 typedef struct svt_hip_lr_unit {
     int32_t type;                       /* 0 none, 1 Wiener, 2 self-guided */
     int16_t vfilter[3], hfilter[3];     /* taps 0 .. 2 */
@@ -2490,9 +2490,58 @@ int svt_hip_lr_wiener_solve(int win, const int64_t *M, const int64_t *H, int16_t
 int svt_hip_lr_walk_start(svt_hip_lr_walk *w, int win, const int16_t vfilter[3], const int16_t hfilter[3]);
 int svt_hip_lr_walk_next(svt_hip_lr_walk *w, int64_t sse);
 
+/* The self-guided parameter search: search_sgrproj_seg -> search_selfguided_restoration (EbRestorationPick.c:1681-1722, :605-661) for
+ * every unit of every plane, for the parameter sets ep_lo <= ep < ep_hi (0 <= ep_lo <= ep_hi <= 16; one range per call).  Filter once,
+ * score many times:
+ *   svt_hip_lr_sgr_stats_frame   apply_sgr (:580-603) and the sums of get_proj_subspace (:463-521).  The filter runs on d_cdef alone, every
+ *                 halo row and column clamped to the plane: there is NO stripe rule here and d_dblk is not read (the reference filters
+ *                 the CDEF frame extended by 3).  With u = dat << 4, s = (src << 4) - u, f1 = flt0 - u, f2 = flt1 - u (0 for a radius of
+ *                 0): d_stats [pic][unit][16][5] int64 = H00 = sum f1 f1, H11 = sum f2 f2, H01 = sum f1 f2, C0 = sum f1 s, C1 = sum f2 s
+ *                 over the unit, exact totals (the reference adds the same integers in double, below 2^53).  Entries of the range are
+ *                 all defined after the call, entries outside it untouched.  f1 / f2 (an int16 pair per sample and ep) and src - dat
+ *                 (int16 per sample) are left in d_scratch, unit-contiguous, for the walk.
+ *   svt_hip_lr_sgr_solve   HOST: the tail of get_proj_subspace (:522-558: division by the sample count, the 1x1 or 2x2 solve, Det < 1e-8
+ *                 -> (0, 0), rint(x * 128), INT32_MIN where that leaves int32 as the reference's compiled conversion does) and encode_xq
+ *                 (:561-577) on one entry's five sums: binary64, nothing contracted.  npix: the unit's samples.
+ *   svt_hip_lr_sgr_walk_frame   finer_search_pixel_proj_error (:398-459, start_step 2) per (pic, unit, ep) on the scratch the statistics
+ *                 call left (same range): e = ((xq0 f1 + xq1 f2 + 1024) >> 11) - (src - dat), err = sum e e, no clip; a successful move is
+ *                 repeated at step 2; a successful downward move of xqd[0] skips xqd[1] at that step; err2 > err rejects, so a tie is
+ *                 accepted; components of radius 0 are skipped; SGRPROJ_PRJ_{MIN,MAX}{0,1} bound the moves.  d_start [pic][unit][16][2]
+ *                 int16: the start per entry (out-of-range values are clamped), or NULL: solved on the device from d_stats by the same
+ *                 text as svt_hip_lr_sgr_solve.  d_walk [pic][unit][16]: the final xqd, its error, the start the walk left from and the
+ *                 evaluations made (at most 137: the ranges bound the walk).  One workgroup per entry; none waits for another.
+ *   svt_hip_lr_sgr_walk_host   HOST: the same walk over arrays f1 / f2 / sd of n samples; xqd: start in, result out; trials (may be
+ *                 NULL) [max_trials][3] int64: xq[0], xq[1] and the error of every evaluation in order.  Returns the evaluations (> 0)
+ *                 or an error (< 0).
+ *   svt_hip_lr_sgr_search_frame   the whole search: statistics, walk with the device solve, per unit the first lowest error of the range
+ *                 (besterr == -1 || err < besterr), then try_restoration_unit_seg on the winner - the stripe-aware filter of
+ *                 svt_hip_lr_try_frame, which is where d_dblk is read.  d_best [pic][unit]: what svt_hip_lr_result takes at index 2.  An
+ *                 empty range (ep_lo == ep_hi: sg_filter_mode 1 with a reference ep) gives ep 0, xqd 0, 0, proj_err -1 and their SSE.
+ *   svt_hip_lr_sgr_ep_range   HOST: get_sg_step (:681-700) and mid_ep / start_ep / end_ep (:625-631): out = {start_ep, end_ep}.
+ *                 sg_ref_frame_ep: below 0 = none, else 0 .. 15.
+ * d_scratch: svt_hip_lr_sgr_scratch_bytes(..) bytes (0 = refused), 16-byte aligned, one size for the three device calls: 2 bytes per
+ * sample of a picture (width * height * 3 / 2) plus 4 per sample and ep of the range, plus a few bytes per unit for the search call's
+ * stages.  1920x1080 with all 16 ep: about 205 MB per picture; a narrower range shrinks it in proportion.
+ * The device calls follow the block's rules (validate everything first, enqueue only, allocate nothing, never synchronise, one stream,
+ * a linear chain of launches, capturable); svt_hip_lr_check takes what = 3 for the statistics / walk operands (d_cdef, d_src) and 4 for
+ * the search's (d_cdef, d_dblk, d_src).  Also refused: a bad ep range; a scratch that is NULL, too small or misaligned; d_stats, d_walk or
+ * d_best NULL or not 8-byte aligned. */
+typedef struct svt_hip_lr_sgr_walk { int64_t err; int16_t xqd[2], start[2]; int32_t evals, pad; } svt_hip_lr_sgr_walk;
+typedef struct svt_hip_lr_sgr_best { int64_t sse, proj_err; int32_t ep; int16_t xqd[2]; } svt_hip_lr_sgr_best;
+size_t svt_hip_lr_sgr_scratch_bytes(uint32_t width, uint32_t height, const uint32_t unit_size[3], uint32_t npics, int ep_lo, int ep_hi);      /* HOST */
+int svt_hip_lr_sgr_stats_frame(const svt_hip_lr_pic *pic, int ep_lo, int ep_hi, int64_t *d_stats, void *d_scratch, size_t scratch_bytes, void *stream);
+int svt_hip_lr_sgr_walk_frame(const svt_hip_lr_pic *pic, int ep_lo, int ep_hi, const int64_t *d_stats, const int16_t *d_start, const void *d_scratch,
+                              size_t scratch_bytes, svt_hip_lr_sgr_walk *d_walk, void *stream);
+int svt_hip_lr_sgr_search_frame(const svt_hip_lr_pic *pic, int ep_lo, int ep_hi, svt_hip_lr_sgr_best *d_best, void *d_scratch, size_t scratch_bytes,
+                                void *stream);
+int svt_hip_lr_sgr_solve(const int64_t stats[5], uint32_t npix, int ep, int16_t xqd[2]);                                                    /* HOST */
+int svt_hip_lr_sgr_walk_host(const int16_t *f1, const int16_t *f2, const int16_t *sd, uint32_t n, int ep, int16_t xqd[2], int64_t *err, int64_t *trials,
+                             int max_trials);                                                                                               /* HOST */
+int svt_hip_lr_sgr_ep_range(const int8_t sg_ref_frame_ep[2], int sg_filter_mode, int32_t out[2]);                                           /* HOST */
+
 /* svt_hip_lr_finish: rest_finish_search (EbRestorationPick.c:1989-2058) for one plane, on the host.  results[u]: what the unit's searches
  * left in RestUnitSearchInfo - sse[0] of the unfiltered unit (search_norestore_seg), sse[1] and the taps of the Wiener search (INT64_MAX =
- * compute_score refused), sse[2], ep and xqd of the self-guided search (input data here: that search is not built).  Mirrored as written:
+ * compute_score refused), sse[2], ep and xqd of the self-guided search (svt_hip_lr_sgr_search_frame's d_best).  Mirrored as written:
  * force_restore_type_d (wn_filter_mode 0 allows none and self-guided only); num_rtypes = RESTORE_SWITCHABLE_TYPES when the plane has one
  * unit, so such a plane never ends switchable; per frame type search_rest_type_finish over the units in index order with the running
  * reference filters rsc->wiener / rsc->sgrproj reset to their defaults by rsc_on_tile; count_wiener_bits / count_sgrproj_bits with
