@@ -207,6 +207,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     L.svt_hip_picture_stats_frame.restype = c_int
     L.svt_hip_inter_pred_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p]
     L.svt_hip_inter_pred_frame.restype = c_int
+    L.svt_hip_warp_fit_frame.argtypes = [c_void_p, c_int, c_void_p]
+    L.svt_hip_warp_fit_frame.restype = c_int
+    L.svt_hip_warp_pred_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p]
+    L.svt_hip_warp_pred_frame.restype = c_int
+    L.svt_hip_warp_tables.argtypes = [c_void_p, c_void_p]
+    L.svt_hip_warp_tables.restype = None
     L.svt_hip_interp_sse_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p]
     L.svt_hip_interp_sse_frame.restype = c_int
     L.svt_hip_interp_decide_frame.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
@@ -392,6 +398,30 @@ class InterPredGroup(ctypes.Structure):
     _fields_ = [("d_ref", c_void_p * 2), ("ref_stride", c_uint32), ("ss", c_int32), ("bwidth", c_int32), ("bheight", c_int32),
                 ("nblocks", c_uint32), ("d_blk", c_void_p), ("d_pred", c_void_p), ("pred_stride", c_uint32), ("d_src", c_void_p),
                 ("src_stride", c_uint32), ("d_dist", c_void_p)]
+
+
+class WarpSamples(ctypes.Structure):
+    """svt_hip_warp_samples: what av1_find_samples returns for a block (132 bytes; warp_samples_dtype() is its numpy twin)"""
+    _fields_ = [("nsamples", c_int32), ("pts", c_int32 * 16), ("pts_inref", c_int32 * 16)]
+
+
+class WarpModel(ctypes.Structure):
+    """svt_hip_warp_model: the local warp model of one (block, candidate) (36 bytes; warp_model_dtype() is its numpy twin)"""
+    _fields_ = [("mat", c_int32 * 6), ("alpha", ctypes.c_int16), ("beta", ctypes.c_int16), ("gamma", ctypes.c_int16), ("delta", ctypes.c_int16),
+                ("valid", ctypes.c_uint8), ("num_proj_ref", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2)]
+
+
+class WarpFitGroup(ctypes.Structure):
+    """svt_hip_warp_fit_group"""
+    _fields_ = [("bsize", c_int32), ("nblocks", c_uint32), ("ncand", c_int32), ("d_samples", c_void_p), ("d_blk", c_void_p), ("d_model", c_void_p),
+                ("d_nvalid", c_void_p)]
+
+
+class WarpPredGroup(ctypes.Structure):
+    """svt_hip_warp_pred_group"""
+    _fields_ = [("d_ref", c_void_p), ("ref_stride", c_uint32), ("ss", c_int32), ("bwidth", c_int32), ("bheight", c_int32), ("nblocks", c_uint32),
+                ("ncand", c_int32), ("d_blk", c_void_p), ("d_model", c_void_p), ("d_sel", c_void_p), ("n", c_int32), ("sel_first", c_int32),
+                ("d_pred", c_void_p), ("pred_stride", c_uint32), ("d_src", c_void_p), ("src_stride", c_uint32), ("d_dist", c_void_p)]
 
 
 UNI_PRED_LIST_0, UNI_PRED_LIST_1, BI_PRED = 0, 1, 2
@@ -678,6 +708,27 @@ def inter_blk_dtype():
     import numpy as np
     return np.dtype([("x", np.uint16), ("y", np.uint16), ("mv", np.int16, (2, 2)), ("pred_direction", np.uint8), ("filter_x", np.uint8),
                      ("filter_y", np.uint8), ("pad", np.uint8)])
+
+
+def warp_samples_dtype():
+    """numpy dtype of svt_hip_warp_samples"""
+    import numpy as np
+    return np.dtype([("nsamples", np.int32), ("pts", np.int32, (16,)), ("pts_inref", np.int32, (16,))])
+
+
+def warp_model_dtype():
+    """numpy dtype of svt_hip_warp_model"""
+    import numpy as np
+    return np.dtype([("mat", np.int32, (6,)), ("alpha", np.int16), ("beta", np.int16), ("gamma", np.int16), ("delta", np.int16),
+                     ("valid", np.uint8), ("num_proj_ref", np.uint8), ("pad", np.uint8, (2,))])
+
+
+def warp_tables(lib):
+    """HOST: the library's statement of the warp filter (int16 [193, 8]) and of Div_Lut (uint16 [257]) (svt_hip_warp_tables; no device)"""
+    import numpy as np
+    f, d = np.zeros((193, 8), np.int16), np.zeros(257, np.uint16)
+    lib.svt_hip_warp_tables(f.ctypes.data, d.ctypes.data)
+    return f, d
 
 
 class Y4mInfo(ctypes.Structure):
@@ -2087,6 +2138,54 @@ class SvtHipDsp:
         if isinstance(groups, list):
             groups = self.make_inter_pred_groups(groups)
         return self.lib.svt_hip_inter_pred_frame(groups, n, pic_width, pic_height, bd, metric, self._stream())
+
+    # -- warped motion: the local warp model of every (block, candidate), then its prediction with the distortion fused in -----------
+    def make_warp_fit_groups(self, groups):
+        """groups: list of dicts with bsize, ncand, samples (uint8 [n, 132]: warp_samples_dtype records), blk (uint8 [n, ncand, 16]:
+        inter_blk_dtype records), model (uint8 [n, ncand, 36], written: warp_model_dtype records), optional nvalid (int32 [n]).
+        -> ctypes array (keep the tensors alive!)"""
+        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
+        arr = (WarpFitGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            a = arr[i]
+            a.bsize, a.ncand = g.get("bsize", 0), g.get("ncand", 0)
+            a.nblocks = g["nblocks"] if "nblocks" in g else (g["samples"].shape[0] if g.get("samples") is not None else 0)
+            a.d_samples, a.d_blk, a.d_model, a.d_nvalid = P(g, "samples"), P(g, "blk"), P(g, "model"), P(g, "nvalid")
+        return arr
+
+    def warp_fit_frame(self, groups):
+        """svt_hip_warp_fit_frame.  groups: a ctypes array from make_warp_fit_groups or the list of dicts -> the library's return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_warp_fit_groups(groups)
+        return self.lib.svt_hip_warp_fit_frame(groups, n, self._stream())
+
+    def make_warp_pred_groups(self, groups):
+        """groups: list of dicts with ref (a tensor whose first element is sample (0, 0) of the picture plane; no border is read),
+        ref_stride (samples), ss, bwidth, bheight (luma), ncand, blk (uint8 [n, ncand, 16]) and model (uint8 [n, ncand, 36]), optional
+        sel (uint8 [n, nsel]: the pick's d_cand) with sel_first, optional pred (dense [slots, h, w], or a plane view with pred_stride),
+        optional src (a view at the picture's sample (0, 0)) with src_stride and dist (int64 [slots]).  -> ctypes array (keep the
+        tensors alive!)"""
+        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
+        arr = (WarpPredGroup * max(len(groups), 1))()
+        for i, g in enumerate(groups):
+            a = arr[i]
+            a.d_ref, a.ref_stride, a.ss, a.bwidth, a.bheight = P(g, "ref"), g.get("ref_stride", 0), g.get("ss", 0), g.get("bwidth", 0), g.get("bheight", 0)
+            a.nblocks = g["nblocks"] if "nblocks" in g else (g["blk"].shape[0] if g.get("blk") is not None else 0)
+            a.ncand, a.d_blk, a.d_model = g.get("ncand", 0), P(g, "blk"), P(g, "model")
+            a.d_sel = P(g, "sel")
+            a.n = g["n"] if "n" in g else (g["sel"].shape[1] if g.get("sel") is not None else 0)
+            a.sel_first = g.get("sel_first", 0)
+            a.d_pred, a.pred_stride = P(g, "pred"), g.get("pred_stride", 0)
+            a.d_src, a.src_stride, a.d_dist = P(g, "src"), g.get("src_stride", 0), P(g, "dist")
+        return arr
+
+    def warp_pred_frame(self, groups, pic_width, pic_height, bd=8, metric=0):
+        """svt_hip_warp_pred_frame.  groups: a ctypes array from make_warp_pred_groups or the list of dicts -> the library's return code"""
+        n = len(groups)
+        if isinstance(groups, list):
+            groups = self.make_warp_pred_groups(groups)
+        return self.lib.svt_hip_warp_pred_frame(groups, n, pic_width, pic_height, bd, metric, self._stream())
 
     # -- interpolation filter search: the nine-pair SSE table, the reference's walk, both in one call -------------------------------
     def _interp_sse_struct(self, a, g):

@@ -1612,7 +1612,9 @@ int svt_hip_picture_stats_frame(const svt_hip_pic_stats_planes *planes, const sv
  * 8 up to 16384; per group ss 0 / 1, bwidth and bheight in {4, 8, 16, 32, 64} (chroma: both >= 8) and not above the picture,
  * d_blk and d_ref[0] set, at least one of d_pred / (d_src, d_dist), d_src and d_dist together, d_dist 8-byte, d_blk 4-byte and a
  * dense d_pred 16-byte aligned, pred_stride 0 or >= the plane block's width, nblocks within one launch.  Not built: see DESIGN.md
- * section 7 (OBMC, warped / global motion, masked and distance-weighted compound, scaled references, intrabc, sub-8x8 chroma, bd 12). */
+ * section 7 (OBMC, global motion, masked and distance-weighted compound, scaled references, intrabc, sub-8x8 chroma, bd 12).  The local
+ * warp of WARPED_CAUSAL candidates is svt_hip_warp_fit_frame / svt_hip_warp_pred_frame below; the chroma of a warped block below 16 in
+ * either dimension is translational with interp_filters 0 (EbInterPrediction.c:2706-2768) and is this call's. */
 enum { SVT_HIP_UNI_PRED_LIST_0 = 0, SVT_HIP_UNI_PRED_LIST_1 = 1, SVT_HIP_BI_PRED = 2 };    /* EbDefinitions.h:2061-2063 */
 #define SVT_HIP_INTER_PRED_MAX_GROUPS 48
 typedef struct svt_hip_inter_blk {       /* sizeof 16 */
@@ -1637,6 +1639,106 @@ typedef struct svt_hip_inter_pred_group {
 } svt_hip_inter_pred_group;
 int svt_hip_inter_pred_frame(const svt_hip_inter_pred_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd,
                              int metric, void *stream);
+
+/* ---- Warped motion: the local warp model of a block and its prediction (WARPED_CAUSAL candidates) -----------------------------------
+ * The two steps every candidate of inject_warped_motion_candidates (EbModeDecision.c:1120-1318) needs, for many groups per call, one
+ * launch per SVT_HIP_INTER_PRED_MAX_GROUPS non-empty groups.  Both calls only enqueue (no allocation, no synchronisation) and can be
+ * captured into a HIP graph.
+ *
+ * svt_hip_warp_fit_frame: warped_motion_parameters (EbAdaptiveMotionVectorPrediction.c:1876-1937) from the point where the samples
+ * exist.  Gathering them (av1_find_samples / wm_count_samples, the walks over the mode-info grid of decided neighbours) stays the
+ * caller's, like MVP generation: d_samples[b] is what av1_find_samples returned for block b, and the ncand candidates of a block (the
+ * nine NEWMV refinements among them) share it.  A group is one block size (bsize in AV1 block_size order; a block below 8 in either
+ * dimension has no warped motion, :1898, and a 128 side is not built: both are refused).  Per (block, candidate), with the
+ * candidate's x, y and mv[0] (svt_hip_inter_blk; mi_col = x >> 2, mi_row = y >> 2), to the letter:
+ *   nsamples == 0 -> invalid, nothing else computed.
+ *   select_samples (:1512) when nsamples > 1: the threshold clamp(max(bw, bh), 16, 112) on |dx| + |dy| against the candidate's
+ *              vector; none below it -> "keep at least 1" (the first sample alone).  The reference then compacts the kept samples by
+ *              a walk from both ends; the walk only permutes them and every sum of the fit is order-free, so the device marks them.
+ *   find_affine_int (EbWarpedMotion.c:1066): the LS_* sums in int32 over the samples with |sx - dx| and |sy - dy| below LS_MV_MAX; Det == 0 ->
+ *              invalid; resolve_divisor_64 (the int16 iDet, `shift < 0` branch included); get_mult_shift_diag / _ndiag in 64 bits with
+ *              their clamps; vx / vy in wrapping int32 with the WARPEDMODEL_TRANS_CLAMP clamp.
+ *   get_shear_params (:344): resolve_divisor_32, the signed 64-bit rounding, the int16 clamps, the WARP_PARAM_REDUCE_BITS rounding
+ *              (stored back into int16) and is_affine_shear_allowed.
+ * d_model[b][c]: valid = local_warp_valid (!find_projection), num_proj_ref = the sample count find_projection saw (0 without
+ * samples), mat = wmmat[0..5] and the four shears as far as the reference wrote them into a zeroed EbWarpedMotionParams (all 0 when
+ * Det == 0; set, with valid 0, when the shear is refused).  d_nvalid[b] (optional) counts the block's valid models.  nsamples is
+ * device data and is clamped to 0 .. 8.
+ *
+ * svt_hip_warp_pred_frame: one plane of warped_motion_prediction (EbInterPrediction.c:2584): av1_warp_plane (8 bit) /
+ * av1_warp_plane_hbd (10 bit) -> av1_warp_affine_c / av1_highbd_warp_affine_c (EbWarpedMotion.c:672, :389) with a single reference,
+ * is_compound 0, round_0 3, 11 bits of vertical rounding and clip(sum - (1 << (bd - 1)) - (1 << bd)).  Per 8x8 tile at (j, i) of the
+ * plane block: the centre ((j + 4) << ss, (i + 4) << ss) in luma coordinates through mat in wrapping int32, arithmetic >> ss and
+ * >> 16, sx4 / sy4 after the -4 * (alpha + beta) / -4 * (gamma + delta) step and the 6-bit mask, offs = ((s + 512) >> 10) + 64 per
+ * sample, and BOTH source coordinates of every sample clamped to the plane, [0, (pic_width >> ss) - 1] x [0, (pic_height >> ss) - 1].
+ * The reference reads no border here, so this call has NO border contract: d_ref points at sample (0, 0) of the plane and nothing
+ * outside pic_width >> ss by pic_height >> ss is read.  A luma group takes bwidth / bheight 8 .. 64 (rectangles included); a chroma
+ * group (ss 1) needs both luma sides >= 16 (:2653).  The chroma of smaller blocks is predicted translationally with interp_filters 0
+ * (:2706-2768): that is svt_hip_inter_pred_frame's job and is not rebuilt here.
+ * Addressing, slots numbered [nblocks][k]:
+ *   direct     d_sel NULL, k = ncand: record r = b * ncand + c of d_blk / d_model is predicted into slot r.
+ *   survivors  d_sel = svt_hip_inter_fast_pick_frame's d_cand ([nblocks][n]), k = n: for slot (b, s), c = d_sel[b][s] - sel_first; when
+ *              0 <= c < ncand, record [b][c] is predicted into slot [b][s], otherwise the slot is left untouched.  This overwrites the
+ *              warped survivors in svt_hip_inter_fast_search_frame's d_pred_out after that call.
+ * A record whose model has valid == 0 leaves its slot untouched (prediction and distortion) in both modes.  Outputs per slot: d_pred
+ * (dense [slot][h][w] with pred_stride 0, else a plane with the block at its own origin) and / or the fused distortion d_dist[slot]
+ * against d_src at the block's origin (SVT_HIP_FAST_SAD / SVT_HIP_FAST_SSD, C flavour); d_pred is optional then.
+ * mat and the shears are device data: offs is clamped to 0 .. 192 before it indexes (a valid model never reaches the clamp,
+ * is_affine_shear_allowed bounds it), every source address is clamped as above and x / y beyond pic - bwidth / - bheight are read as
+ * that bound, so a garbage model gives an unspecified prediction for its own slot and nothing else.
+ *
+ * Validated before the first launch (SVT_HIP_ERR_INVALID, nothing launched).  Fit: bsize 0 .. 21 with both sides 8 .. 64; ncand
+ * 1 .. 64; d_samples, d_blk, d_model set and 4-byte aligned (d_nvalid too when given); nblocks within one launch.  Prediction: bd 8 /
+ * 10; metric; picture sides non-zero multiples of 8 up to 16384; ss 0 / 1; bwidth and bheight in {8, 16, 32, 64} (chroma: both >= 16)
+ * and not above the picture; ncand 1 .. 64; d_ref, d_blk, d_model set, d_blk and d_model 4-byte aligned; at least one of d_pred /
+ * (d_src, d_dist), d_src and d_dist together, d_dist 8-byte and a dense d_pred 16-byte aligned, pred_stride 0 or >= the plane block's
+ * width; with d_sel n 1 .. 64 and sel_first 0 .. 255, without it n == 0 and sel_first == 0; nblocks * k within one launch.
+ * Not built: see DESIGN.md section 7 (OBMC, global motion and ROTZOOM, compound warp, av1_warp_error, the sample walks, bd 12, 4:2:2 /
+ * 4:4:4, warped_motion_prediction_md). */
+typedef struct svt_hip_warp_samples {    /* sizeof 132: what av1_find_samples returns for a block */
+    int32_t nsamples;                    /* 0 .. 8 */
+    int32_t pts[16];                     /* [sample][x, y], 1/8 sample, relative to the block's origin */
+    int32_t pts_inref[16];
+} svt_hip_warp_samples;
+typedef struct svt_hip_warp_model {      /* sizeof 36 */
+    int32_t mat[6];                      /* EbWarpedMotionParams.wmmat[0..5] */
+    int16_t alpha, beta, gamma, delta;
+    uint8_t valid;                       /* local_warp_valid */
+    uint8_t num_proj_ref;
+    uint8_t pad[2];
+} svt_hip_warp_model;
+typedef struct svt_hip_warp_fit_group {
+    int32_t bsize;                       /* AV1 block_size order */
+    uint32_t nblocks;
+    int32_t ncand;                       /* candidates per block, 1 .. 64 */
+    const svt_hip_warp_samples *d_samples;   /* [nblocks] */
+    const svt_hip_inter_blk *d_blk;      /* [nblocks][ncand]: x, y, mv[0] */
+    svt_hip_warp_model *d_model;         /* [nblocks][ncand] */
+    uint32_t *d_nvalid;                  /* optional [nblocks] */
+} svt_hip_warp_fit_group;
+int svt_hip_warp_fit_frame(const svt_hip_warp_fit_group *groups, int ngroups, void *stream);
+typedef struct svt_hip_warp_pred_group {
+    const void *d_ref;                   /* sample (0, 0) of the picture plane; no border is read */
+    uint32_t ref_stride;
+    int32_t ss;                          /* 0: a luma plane; 1: a chroma plane of 4:2:0 */
+    int32_t bwidth, bheight;             /* LUMA block size */
+    uint32_t nblocks;
+    int32_t ncand;                       /* records per block, 1 .. 64 */
+    const svt_hip_inter_blk *d_blk;      /* [nblocks][ncand]: x, y */
+    const svt_hip_warp_model *d_model;   /* [nblocks][ncand] */
+    const uint8_t *d_sel;                /* NULL: direct; else [nblocks][n] list positions */
+    int32_t n, sel_first;                /* survivors per block; the list position of the block's record 0 */
+    void *d_pred;                        /* optional when the distortion is asked for */
+    uint32_t pred_stride;                /* 0: dense [slot][h][w]; else a plane, block at its origin */
+    const void *d_src;                   /* optional source plane, sample (0, 0) of the picture */
+    uint32_t src_stride;
+    uint64_t *d_dist;                    /* optional [slot] */
+} svt_hip_warp_pred_group;
+int svt_hip_warp_pred_frame(const svt_hip_warp_pred_group *groups, int ngroups, uint32_t pic_width, uint32_t pic_height, int bd, int metric,
+                            void *stream);
+/* HOST, no device: the project's statement of the warp filter of the AV1 specification (7.11.3.5, Warped_Filters), [193][8], and of its
+ * divisor table (Div_Lut, [257]), as the kernels use them. */
+void svt_hip_warp_tables(int16_t *filter, uint16_t *div_lut);
 
 /* ---- Interpolation filter search of mode decision (interpolation_filter_search, EbInterPrediction.c:3578-3917) ---------------------
  * For an inter candidate the reference predicts the block with up to nine (vertical, horizontal) filter pairs out of {REGULAR, SMOOTH,
