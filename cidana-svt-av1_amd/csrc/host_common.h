@@ -145,9 +145,6 @@ extern thread_local ThreadCtx t_ctx;
     } while (0)
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-// sample depths of the pixel entry points: 8 for uint8 samples; 8, 10 or 12 for uint16
-inline bool sample_depth_ok(int is_16bit, int bd) { return bd == 8 || (is_16bit && (bd == 10 || bd == 12)); }
-
 
 // Internal streams a frame-level call fans its independent groups out to (forked from, and joined back into, the caller's
 // stream: the call stays a pure enqueue and is graph-capturable).  One set per calling thread.

@@ -71,16 +71,9 @@ __device__ __forceinline__ int bip_use_upsample(int bs0, int bs1, int delta, int
     return type ? (wh <= 8) : (wh <= 16);
 }
 
-constexpr int BIP_WAVES = 4;
+// (BIP_WAVES waves per workgroup and bip_lanes_per_block lanes per block: intra_plan.h, where the host sizes the grid from them)
 // staged samples per edge: positions [-16, n): n covers w + h samples, twice that where the edge can be up-sampled (w + h <= 16)
 __host__ __device__ constexpr int bip_edge_len(int w, int h) { return (16 + (w + h <= 16 ? 2 * (w + h) : w + h) + 8 + 7) & ~7; }
-// lanes per block: w + h + 1 edge samples in at most three rounds (the smoothing stage keeps three values per lane)
-__host__ __device__ constexpr int bip_lanes_per_block(int w, int h) {
-    const int need = (w + h + 1 + 2) / 3;
-    int l = 4;
-    while (l < need) l <<= 1;
-    return l > 64 ? 64 : l;
-}
 
 // the predictor kind a block resolves to (stage 5 of bip_kernel; also the sort key of the ordering pass)
 __device__ __forceinline__ int bip_kind_of(const BipBlk& d, int w, int h, int& p_angle_out) {

@@ -9,6 +9,7 @@
 
 #include "dev_common.h"
 #include "group_table.h"
+#include "intra_plan.h"
 
 namespace svtdev {
 
@@ -207,15 +208,7 @@ __global__ __launch_bounds__(256) void txb_init_levels_kernel(const int32_t* __r
 //                      subtract_average, then cfl_predict on the Cb and the Cr prediction in place.  The Q3 values never leave
 //                      the registers (the reference keeps them in pred_buf_q3 between its four calls).
 // ---------------------------------------------------------------------------
-constexpr int LEVELS_MAX_GROUPS = 48;
-struct LevelsGroupDev {
-    const int32_t* coeff; uint8_t* levels;
-    uint32_t levels_pitch, w, h, lpb, ndw, row_magic, nblocks, wg_end;
-    uint32_t wide;                   // 16-byte stores (buffer and pitch 16-byte aligned)
-};
-struct LevelsFrameDesc { int32_t ngroups; LevelsGroupDev g[LEVELS_MAX_GROUPS]; };
-static_assert(sizeof(LevelsFrameDesc) <= 4000, "kernel arguments");
-
+// (the group tables, LevelsFrameDesc and CflFrameDesc: intra_plan.h, whose fill functions write them)
 __global__ __launch_bounds__(256) void levels_frame_kernel(const LevelsFrameDesc fd) {
     uint32_t bid;
     const int gi = group_of(fd, bid);
@@ -229,16 +222,6 @@ __global__ __launch_bounds__(256) void levels_frame_kernel(const LevelsFrameDesc
     if (G.wide) txb_levels_body<true>(cb, ob, G.w, G.h, threadIdx.x & (G.lpb - 1), G.lpb, G.ndw, G.row_magic);
     else txb_levels_body<false>(cb, ob, G.w, G.h, threadIdx.x & (G.lpb - 1), G.lpb, G.ndw, G.row_magic);
 }
-
-constexpr int CFL_MAX_GROUPS = 16;      // the chroma transform sizes 4 .. 32 in both dimensions
-struct CflGroupDev {
-    const void* luma; void* cb; void* cr;
-    const uint32_t* xy; const int32_t* alpha_cb; const int32_t* alpha_cr;
-    uint32_t luma_stride, cb_stride, cr_stride, nblocks, w, h, lpb, wg_end;
-    int32_t round_offset, num_pel_log2;
-};
-struct CflFrameDesc { int32_t ngroups; CflGroupDev g[CFL_MAX_GROUPS]; };
-static_assert(sizeof(CflFrameDesc) <= 4000, "kernel arguments");
 
 template <typename PixT>
 __global__ __launch_bounds__(256) void cfl_frame_kernel(const CflFrameDesc fd, int hi) {

@@ -11,6 +11,7 @@
 // allows; neighbour rows are tiny and served from L1/L2.
 #pragma once
 #include "dev_common.h"
+#include "intra_plan.h"
 #include <type_traits>
 
 namespace svtdev {
@@ -29,9 +30,7 @@ __device__ constexpr uint8_t kSmWeights[128] = {
     65, 61, 57, 54, 50, 47, 44, 41, 38, 35, 32, 29, 27, 25, 22, 20,
     18, 16, 15, 13, 12, 10, 9, 8, 7, 6, 6, 5, 5, 4, 4, 4};
 
-// Neighbour layout per block: `nb_pitch` samples; position p of the reference's
-// above_row / left_col lives at index NB_ORIGIN + p (p >= -2).
-constexpr int NB_ORIGIN = 16;
+// (the neighbour layout per block, NB_ORIGIN, and the lane and LDS geometry the host shares with these kernels: intra_plan.h)
 
 // ---- non-directional modes -------------------------------------------------------------
 // Work split: a block is covered by LB = bw*bh/ppl consecutive lanes (ppl = pixels per lane =
@@ -177,9 +176,10 @@ __global__ __launch_bounds__(256) void intra_pred_kernel(
     const PixT* __restrict__ above_all, const PixT* __restrict__ left_all, int32_t nb_pitch, int bw, int bh, int bd,
     uint32_t dc_magic, uint32_t nblocks) {
     constexpr int PXL = 16 / (int)sizeof(PixT);            // pixels per lane when the block is wide enough
-    const int ppl = WIDE ? PXL : bw;                       // pixels per lane (host picks WIDE = bw >= PXL)
-    const int lanes_per_row = WIDE ? bw >> __builtin_ctz((uint32_t)PXL) : 1;
-    const uint32_t per_block = (uint32_t)(lanes_per_row * bh);      // LB: power of two, 4 .. 512
+    const IntraLanes lanes = intra_lanes_of<WIDE, PXL>(bw, bh);     // (the host picks WIDE = bw >= PXL: intra_lanes)
+    const int ppl = lanes.ppl;                             // pixels per lane
+    const int lanes_per_row = lanes.lanes_per_row;
+    const uint32_t per_block = lanes.per_block;            // LB: power of two, 4 .. 512
     const size_t total = (size_t)per_block * nblocks;
     const size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int pb_shift = __builtin_ctz(per_block);                  // per_block is a power of two
@@ -289,14 +289,8 @@ struct DirMultiLite {
 // a full 16-B segment per lane and throw most of it away (the open-loop search's 8x8 pass spent half its VALU there).
 // TAB: zone 2 with the host's per-angle tables (DirMulti::z2_w2 / z2_ol); a separate instantiation so that the dense-output kernels
 // keep their own code (with both paths in one kernel the 32x32 single-angle form ran 15 % slower).
-// LDS pair dwords between the staged edges of consecutive blocks of a workgroup.  Lanes of `lpb` rows read a window of about lpb
-// consecutive dwords of their block's edge, and a half wave (32 lanes, one LDS pass) holds 32 / lpb blocks: a stride that is
-// lpb modulo 32 puts those windows on disjoint banks (2 * estride alone is 0 or 16 modulo 32: the open-loop search's 8x8 pass,
-// 8 lanes per block, measured 50 % of its LDS cycles in bank conflicts).  Even, so that the 8-byte staging stores stay aligned.
-__host__ __device__ inline int dir_slot_stride(int estride, uint32_t lpb) {
-    const int base = 2 * estride;
-    return lpb < 32u ? base + (int)(((uint32_t)lpb - (uint32_t)base) & 31u) : base;
-}
+// The LDS layout - dir_estride pair dwords per staged edge, dir_slot_stride between the blocks of a workgroup, zone 2's column table at
+// dir_tab_offset - is intra_plan.h's: the host sizes the launch's LDS from the same functions (dir_lds).
 
 // (the body is a device function so that ois_dir3_kernel below can run the three zones of one candidate list in ONE launch; MT is
 // DirMulti or DirMultiLite, ypart the angle chunk this workgroup takes)
@@ -315,18 +309,19 @@ __device__ __forceinline__ void intra_dir_body(
     constexpr int NW = NPX / PPW;                                          // output dwords per lane
     static_assert(NPX * (int)sizeof(PixT) <= 16 && NW >= 1, "a lane writes 4 .. 16 bytes");
     constexpr int ppl = NPX;                                               // host: NPX == min(bw, 16 / sizeof(PixT))
-    const int lanes_per_row = bw >> __builtin_ctz((uint32_t)ppl);
-    const uint32_t per_block = (uint32_t)(lanes_per_row * bh);             // power of two, 4 .. 512
+    const IntraLanes lanes = intra_lanes_of<true, NPX>(bw, bh);
+    const int lanes_per_row = lanes.lanes_per_row;
+    const uint32_t per_block = lanes.per_block;                            // power of two, 4 .. 512
     const int pb_shift = __builtin_ctz(per_block);
     const int lr_shift = __builtin_ctz((uint32_t)lanes_per_row);
-    const uint32_t lpb = per_block >= 256 ? 256u : per_block;              // this workgroup's lanes on one block
+    const uint32_t lpb = dir_lpb(per_block);                               // this workgroup's lanes on one block
     const uint32_t slot = threadIdx.x >> __builtin_ctz(lpb);               // which of the workgroup's blocks
     const uint32_t jl = threadIdx.x & (lpb - 1);                           // lane inside that block's group
     const size_t total = (size_t)per_block * nblocks;
     const size_t item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t j = (uint32_t)(item & (per_block - 1));
     const int r = (int)(j >> lr_shift), c0 = (int)(j & (uint32_t)(lanes_per_row - 1)) * ppl;
-    const int estride = (n_pad + 10) & ~7;                                 // pair dwords per staged edge (+ 3: the last group of four may pass n_pad)
+    const int estride = dir_estride(n_pad);                                // pair dwords per staged edge
     uint32_t* sa = sm + (size_t)slot * dir_slot_stride(estride, lpb);                      // above edge of this lane's block
     uint32_t* sl = sa + estride;
     const bool live = item < total;
@@ -371,7 +366,7 @@ __device__ __forceinline__ void intra_dir_body(
     // zone 2, one angle per launch, no up-sampling: the left-edge terms of column c - weight pair and 4 * ((-dy (c + 1)) >> 6) - are
     // the same in every row; 64 lanes tabulate them once per workgroup behind the staged edges (DirMulti documents the terms)
     const bool z2_lds_tab = MODE == IM_Z2 && !TAB && multi.n == 0 && (up_above | up_left) == 0;
-    uint32_t* tabw = sm + (size_t)(256u >> __builtin_ctz(lpb)) * dir_slot_stride(estride, lpb);
+    uint32_t* tabw = sm + dir_tab_offset(estride, lpb);
     if (z2_lds_tab && threadIdx.x < 64) {
         const int ys = -dy * ((int)threadIdx.x + 1);
         const uint32_t sh = ((uint32_t)ys & 63u) >> 1;

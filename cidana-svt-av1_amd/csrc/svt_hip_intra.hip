@@ -1,47 +1,38 @@
 // svt_hip_intra.hip — entry points of the intra family of libsvt_hip_dsp.so (include/svt_hip_dsp.h): intra prediction, edge
-// filters, chroma-from-luma helpers, txb_init_levels, the open-loop intra search and their drop-ins.
+// filters, chroma-from-luma helpers, txb_init_levels, the open-loop intra search and their drop-ins.  A device-pointer entry point is
+// require_init, the empty-batch return, its plan (intra_plan.h: every check, the grid, the LDS bytes) and one switch to the
+// instantiation with the launch.
 #include "host_common.h"
 #include "kernel_cfl.h"
 #include "kernel_intra.h"
 #include "kernel_bip.h"
 #include "kernel_ois.h"
+#include "intra_plan.h"
 #include "ois_plan.h"
 #include "tx_plan.h"
 
 using namespace svtdev;
 using namespace svthost;
 
+// the knobs the family's plans read (intra_plan.h): filled from the globals of host_common.h here and nowhere else
+static IntraKnobs intra_knobs() { return IntraKnobs{g_tune_dir_no_split, g_tune_dir_split_target, g_num_cu}; }
+
 // ---- K11 chroma-from-luma helpers + av1_txb_init_levels ----
 // f(T{}) with the sample type, for the uint8_t / uint16_t launch pairs
 template <typename F> static void by_sample(int is_16bit, F&& f) { if (is_16bit) f(uint16_t{}); else f(uint8_t{}); }
-
-static bool tx_side_ok(uint32_t v) { return v == 4 || v == 8 || v == 16 || v == 32 || v == 64; }
-static bool cfl_dim_ok(uint32_t v) { return v != 64 && tx_side_ok(v); }
-// a lane takes a chunk of 4 (4-wide blocks) or 8 samples of a row; at most 64 lanes per block, slots blocks per workgroup
-struct CflLanes { uint32_t nchunks, lpb, slots; };
-static CflLanes cfl_lanes(uint32_t w, uint32_t h) {
-    const uint32_t nchunks = (w / (w < 8 ? 4 : 8)) * h, lpb = nchunks < 64 ? nchunks : 64;
-    return {nchunks, lpb, 256 / lpb};
-}
 
 static int cfl_ac_launch(int in_mode, const void* d_luma, uint32_t luma_stride, size_t luma_block_pitch, const uint32_t* d_xy,
                          int16_t* d_q3, uint32_t q3_line, size_t q3_block_pitch, uint32_t w, uint32_t h, int subtract,
                          int round_offset, int num_pel_log2, size_t nblocks, void* stream, const char* what) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_q3 || (in_mode != 2 && !d_luma)) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (!cfl_dim_ok(w) || !cfl_dim_ok(h)) return set_err(SVT_HIP_ERR_INVALID, "chroma block %ux%u", w, h);
-    if (q3_line < w || q3_block_pitch < (size_t)q3_line * (h - 1) + w) return set_err(SVT_HIP_ERR_INVALID, "q3 layout: line %u, block pitch %zu", q3_line, q3_block_pitch);
-    if (num_pel_log2 < 0 || num_pel_log2 > 31) return set_err(SVT_HIP_ERR_INVALID, "num_pel_log2 %d", num_pel_log2);
-    const uint32_t lpb = cfl_lanes(w, h).lpb;
-    const size_t lanes = nblocks * lpb;
-    const size_t grid = (lanes + 255) / 256;
-    if (grid > 0x7fffffffu || nblocks > 0x7fffffffu / 64) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
+    CflAcPlan p;
+    if (int rc = cfl_ac_plan(p, in_mode, d_luma, d_q3, q3_line, q3_block_pitch, w, h, num_pel_log2, nblocks)) return rc;
 #define CFL_AC(IN)                                                                                                          \
-    hipLaunchKernelGGL((cfl_ac_kernel<IN>), dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_luma, luma_stride,   \
-                       luma_block_pitch, d_xy, d_q3, q3_line, q3_block_pitch, w, h, lpb, subtract, round_offset, num_pel_log2, \
-                       (uint32_t)nblocks)
-    if (in_mode == 0) CFL_AC(0); else if (in_mode == 1) CFL_AC(1); else CFL_AC(2);
+    hipLaunchKernelGGL((cfl_ac_kernel<IN>), dim3(p.grid), dim3(256), 0, (hipStream_t)stream, d_luma, luma_stride,           \
+                       luma_block_pitch, d_xy, d_q3, q3_line, q3_block_pitch, w, h, p.lpb, subtract, round_offset, num_pel_log2, \
+                       p.nblocks)
+    if (p.in_mode == 0) CFL_AC(0); else if (p.in_mode == 1) CFL_AC(1); else CFL_AC(2);
 #undef CFL_AC
     return launch_status(what);
 }
@@ -51,11 +42,9 @@ extern "C" int svt_hip_cfl_luma_subsampling_420_batch(const void* d_luma, uint32
                                                       size_t q3_block_pitch, uint32_t width, uint32_t height,
                                                       int subtract_average, size_t nblocks, void* stream) {
     if ((width & 1) || (height & 1)) return set_err(SVT_HIP_ERR_INVALID, "luma block %ux%u", width, height);
-    const uint32_t w = width >> 1, h = height >> 1;
-    int lg = 0;
-    while ((1u << lg) < w * h) lg++;
-    return cfl_ac_launch(is_16bit ? 1 : 0, d_luma, luma_stride, luma_block_pitch, d_xy, d_q3, q3_line, q3_block_pitch, w, h,
-                         subtract_average ? 1 : 0, (int)(w * h / 2), lg, nblocks, stream, "cfl_luma_subsampling_420");
+    const Cfl420Shape c = cfl_420_shape(width, height);
+    return cfl_ac_launch(is_16bit ? 1 : 0, d_luma, luma_stride, luma_block_pitch, d_xy, d_q3, q3_line, q3_block_pitch, c.w, c.h,
+                         subtract_average ? 1 : 0, c.round_offset, c.num_pel_log2, nblocks, stream, "cfl_luma_subsampling_420");
 }
 
 extern "C" int svt_hip_subtract_average_batch(int16_t* d_q3, uint32_t q3_line, size_t q3_block_pitch, uint32_t width,
@@ -71,156 +60,56 @@ extern "C" int svt_hip_cfl_predict_batch(const int16_t* d_ac_q3, uint32_t q3_lin
                                          int is_16bit, size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_ac_q3 || !d_pred || !d_dst || !d_alpha_q3) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (!cfl_dim_ok(width) || !cfl_dim_ok(height)) return set_err(SVT_HIP_ERR_INVALID, "chroma block %ux%u", width, height);
-    if (!sample_depth_ok(is_16bit, bit_depth)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bit_depth);
-    if (q3_line < width || pred_stride < width || dst_stride < width) return set_err(SVT_HIP_ERR_INVALID, "stride smaller than the block");
-    const uint32_t nchunks = cfl_lanes(width, height).nchunks;
-    uint32_t sh = 0;
-    while ((1u << sh) < nchunks) sh++;
-    const size_t grid = ((nblocks << sh) + 255) / 256;
-    if (grid > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
-    const int hi = (1 << bit_depth) - 1;
+    CflPredictPlan p;
+    if (int rc = cfl_predict_plan(p, d_ac_q3, d_pred, d_dst, d_alpha_q3, q3_line, pred_stride, dst_stride, bit_depth, width, height, is_16bit, nblocks)) return rc;
     by_sample(is_16bit, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((cfl_predict_kernel<T>), dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_ac_q3, q3_line, q3_block_pitch, (const T*)d_pred,
-                           pred_stride, (T*)d_dst, dst_stride, d_xy, d_alpha_q3, hi, width, height, sh, (uint32_t)nblocks);
+        hipLaunchKernelGGL((cfl_predict_kernel<T>), dim3(p.grid), dim3(256), 0, (hipStream_t)stream, d_ac_q3, q3_line, q3_block_pitch, (const T*)d_pred,
+                           pred_stride, (T*)d_dst, dst_stride, d_xy, d_alpha_q3, p.hi, width, height, p.sh, p.nblocks);
     });
     return launch_status("cfl_predict");
 }
-
-// The level map of a w x h coefficient block: (w + TX_PAD_HOR) * (h + TX_PAD_VER) + TX_PAD_END bytes = ndw dwords, written by lpb lanes
-// per block (a dword each, or 16 bytes when pitch and pointer allow: wide), slots blocks per workgroup; row_magic divides by a row's dwords
-struct LevelsGeom { uint32_t bytes, ndw, lpb, slots, row_magic; bool wide; };
-static LevelsGeom levels_geom(uint32_t w, uint32_t h, size_t pitch, const void* ptr) {
-    const uint32_t bytes = (w + 4) * (h + 6) + 16, ndw = bytes >> 2;
-    const bool wide = (pitch & 15) == 0 && ((uintptr_t)ptr & 15) == 0;
-    const uint32_t items = wide ? (ndw + 3) / 4 : ndw;
-    uint32_t lpb = 1;
-    while (lpb < items && lpb < 256) lpb <<= 1;
-    return {bytes, ndw, lpb, 256 / lpb, (uint32_t)(0x100000000ull / ((w + 4) >> 2)) + 1u, wide};
-}
-// get_txb_wide / get_txb_high: a side of the packed coefficient block (a 64-sample side keeps its 32 low-frequency columns / rows)
-static uint32_t txb_side(int v) { return v > 32 ? 32u : (uint32_t)v; }
 
 extern "C" int svt_hip_txb_init_levels_batch(const int32_t* d_coeff, size_t coeff_block_pitch, uint8_t* d_levels_buf,
                                              size_t levels_block_pitch, uint32_t width, uint32_t height, size_t nblocks,
                                              void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_coeff || !d_levels_buf) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (!tx_side_ok(width) || !tx_side_ok(height)) return set_err(SVT_HIP_ERR_INVALID, "block %ux%u", width, height);
-    const LevelsGeom lg = levels_geom(width, height, levels_block_pitch, d_levels_buf);
-    if (levels_block_pitch < lg.bytes || (levels_block_pitch & 3) || ((uintptr_t)d_levels_buf & 3))
-        return set_err(SVT_HIP_ERR_INVALID, "levels buffer: %zu B per block (need >= %u, multiple of 4, 4-byte aligned)", levels_block_pitch, lg.bytes);
-    if (coeff_block_pitch < (size_t)width * height) return set_err(SVT_HIP_ERR_INVALID, "coeff_block_pitch %zu", coeff_block_pitch);
-    const size_t grid = (nblocks + lg.slots - 1) / lg.slots;
-    if (grid > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
-    hipLaunchKernelGGL(lg.wide ? txb_init_levels_kernel<true> : txb_init_levels_kernel<false>, dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_coeff,
-                       coeff_block_pitch, d_levels_buf, levels_block_pitch, width, height, lg.lpb, lg.ndw, lg.row_magic, (uint32_t)nblocks);
+    LevelsPlan p;
+    if (int rc = txb_init_levels_plan(p, d_coeff, coeff_block_pitch, d_levels_buf, levels_block_pitch, width, height, nblocks)) return rc;
+    hipLaunchKernelGGL(p.lg.wide ? txb_init_levels_kernel<true> : txb_init_levels_kernel<false>, dim3(p.grid), dim3(256), 0, (hipStream_t)stream, d_coeff,
+                       coeff_block_pitch, d_levels_buf, levels_block_pitch, width, height, p.lg.lpb, p.lg.ndw, p.lg.row_magic, p.nblocks);
     return launch_status("txb_init_levels");
 }
 
 // ---- the frame call with its chroma-from-luma step and level maps (header: svt_hip_encode_recon_frame_ex) ----
-static int frame_levels_launch(const svt_hip_frame_group* groups, const svt_hip_frame_levels* levels, int ngroups, hipStream_t s) {
-    GroupTable<LevelsFrameDesc, LEVELS_MAX_GROUPS> tab;
-    auto launch = [&](const LevelsFrameDesc& fd, uint32_t total) -> int {
-        hipLaunchKernelGGL(levels_frame_kernel, dim3(total), dim3(256), 0, s, fd);
-        return launch_status("levels_frame");
-    };
-    for (int g = 0; g < ngroups; g++) {
-        const svt_hip_frame_group& G = groups[g];
-        const svt_hip_frame_levels& L = levels[g];
-        if (!G.nblocks || !L.d_levels_buf) continue;
-        const uint32_t w = txb_side(kTxW[G.tx_size]), h = txb_side(kTxH[G.tx_size]);
-        const LevelsGeom lg = levels_geom(w, h, L.levels_block_pitch, L.d_levels_buf);
-        LevelsGroupDev* D = tab.add((G.nblocks + lg.slots - 1) / lg.slots, launch);      // (nblocks < 2^31: checked by the caller)
-        if (!D) return tab.rc;
-        D->coeff = G.d_qcoeff; D->levels = L.d_levels_buf; D->levels_pitch = (uint32_t)L.levels_block_pitch; D->w = w; D->h = h; D->lpb = lg.lpb; D->ndw = lg.ndw;
-        D->row_magic = lg.row_magic; D->nblocks = G.nblocks; D->wide = lg.wide;
-    }
-    return tab.flush(launch);
-}
-
 extern "C" int svt_hip_encode_recon_frame_ex(const svt_hip_frame_group* groups, int ngroups, int first_chroma_group,
                                              const svt_hip_frame_cfl_group* cfl, int ncfl, const svt_hip_frame_levels* levels,
                                              int is_16bit, int bd, const int16_t* zbin, const int16_t* round, const int16_t* quant,
                                              const int16_t* quant_shift, const int16_t* dequant, void* stream) {
     if (int rc = require_init()) return rc;
-    if (ngroups < 0 || ncfl < 0 || (ngroups && !groups) || (ncfl && !cfl)) return set_err(SVT_HIP_ERR_INVALID, "group lists");
-    if (ngroups > 256) return set_err(SVT_HIP_ERR_INVALID, "more than 256 groups in one call");
-    if (ncfl > CFL_MAX_GROUPS) return set_err(SVT_HIP_ERR_INVALID, "%d chroma-from-luma groups (at most %d: one per chroma transform size)", ncfl, CFL_MAX_GROUPS);
-    if (ncfl && (first_chroma_group < 0 || first_chroma_group > ngroups)) return set_err(SVT_HIP_ERR_INVALID, "first_chroma_group %d of %d", first_chroma_group, ngroups);
-    if (!sample_depth_ok(is_16bit, bd)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
     // everything is validated before anything is enqueued
+    if (int rc = frame_ex_args_check(groups, ngroups, first_chroma_group, cfl, ncfl, is_16bit, bd)) return rc;
     if (int rc = frame_groups_check(groups, ngroups, tx_knobs())) return rc;
-    GroupTable<CflFrameDesc, CFL_MAX_GROUPS> ctab;       // (ncfl <= CFL_MAX_GROUPS: one launch, after the luma pass)
-    for (int g = 0; g < ncfl; g++) {
-        const svt_hip_frame_cfl_group& C = cfl[g];
-        if (C.nblocks == 0) continue;
-        if (!C.d_luma_recon || !C.d_pred_cb || !C.d_pred_cr || !C.d_xy || !C.d_alpha_q3_cb || !C.d_alpha_q3_cr)
-            return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: NULL member", g);
-        if (!cfl_dim_ok(C.width) || !cfl_dim_ok(C.height)) return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: chroma block %ux%u", g, C.width, C.height);
-        if (C.luma_stride < 2 * C.width || C.pred_stride_cb < C.width || C.pred_stride_cr < C.width)
-            return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: stride smaller than the block", g);
-        const CflLanes lanes = cfl_lanes(C.width, C.height);
-        CflGroupDev* D = ctab.add((C.nblocks - 1) / lanes.slots + 1);
-        if (!D) return set_err(SVT_HIP_ERR_INVALID, "chroma-from-luma group %d: too many blocks for one launch", g);
-        D->lpb = lanes.lpb;
-        D->luma = C.d_luma_recon; D->cb = C.d_pred_cb; D->cr = C.d_pred_cr; D->xy = C.d_xy; D->alpha_cb = C.d_alpha_q3_cb; D->alpha_cr = C.d_alpha_q3_cr;
-        D->luma_stride = C.luma_stride; D->cb_stride = C.pred_stride_cb; D->cr_stride = C.pred_stride_cr; D->nblocks = C.nblocks; D->w = C.width; D->h = C.height;
-        D->round_offset = (int32_t)(C.width * C.height / 2);
-        D->num_pel_log2 = __builtin_ctz(C.width) + __builtin_ctz(C.height);
-    }
-    if (levels)
-        for (int g = 0; g < ngroups; g++) {
-            const svt_hip_frame_levels& L = levels[g];
-            if (!groups[g].nblocks || !L.d_levels_buf) continue;
-            const size_t bytes = levels_geom(txb_side(kTxW[groups[g].tx_size]), txb_side(kTxH[groups[g].tx_size]), L.levels_block_pitch, L.d_levels_buf).bytes;
-            if (L.levels_block_pitch < bytes || (L.levels_block_pitch & 3) || ((uintptr_t)L.d_levels_buf & 3) || L.levels_block_pitch > 0xffffffffu)
-                return set_err(SVT_HIP_ERR_INVALID, "group %d: levels buffer %zu B per block (need >= %zu, multiple of 4, 4-byte aligned)", g, L.levels_block_pitch, bytes);
-            if (groups[g].nblocks > kMaxLaunchWgs) return set_err(SVT_HIP_ERR_INVALID, "group %d: too many blocks for one launch", g);
-        }
+    int ncfl_live = 0;
+    if (int rc = frame_ex_groups_check(groups, ngroups, cfl, ncfl, levels, ncfl_live)) return rc;
     hipStream_t s = (hipStream_t)stream;
     // stream order carries the dependencies: luma reconstruction -> chroma-from-luma prediction -> chroma encode -> level maps
-    const int n_first = ctab.size() ? first_chroma_group : ngroups;
+    const int n_first = ncfl_live ? first_chroma_group : ngroups;
     if (int rc = svt_hip_encode_recon_frame(groups, n_first, is_16bit, bd, zbin, round, quant, quant_shift, dequant, stream)) return rc;
-    if (ctab.size()) {
+    if (ncfl_live) {
         const int hi = (1 << bd) - 1;
-        if (int rc = ctab.flush([&](const CflFrameDesc& cd, uint32_t total) {
+        if (int rc = cfl_frame_enqueue(cfl, ncfl, [&](const CflFrameDesc& cd, uint32_t total) {
                 by_sample(is_16bit, [&](auto t) { hipLaunchKernelGGL((cfl_frame_kernel<decltype(t)>), dim3(total), dim3(256), 0, s, cd, hi); });
                 return launch_status("cfl_frame");
             })) return rc;
         if (int rc = svt_hip_encode_recon_frame(groups + n_first, ngroups - n_first, is_16bit, bd, zbin, round, quant, quant_shift, dequant, stream)) return rc;
     }
-    if (levels) return frame_levels_launch(groups, levels, ngroups, s);
-    return SVT_HIP_OK;
-}
-
-static bool intra_size_ok(int bw, int bh) {
-    if (!tx_side_ok((uint32_t)bw) || !tx_side_ok((uint32_t)bh)) return false;
-    const int m = bw > bh ? bw : bh, mn = bw < bh ? bw : bh;
-    return m <= 4 * mn;     // the 19 TX sizes
-}
-
-// zone 2's per-angle tables of the left-edge terms, see DirMulti
-static void dir_z2_tables(DirMulti& d) {
-    d.z2_tab = 1;
-    for (int a = 0; a < d.n; a++)
-        for (int k = 0; k < 16; k++) {
-            const int ys = -(int)d.dy[a] * (k + 1);
-            const uint32_t sh = ((uint32_t)ys & 63u) >> 1;
-            d.z2_w2[a][k] = (32u - sh) | (sh << 16);
-            d.z2_ol[a][k] = 4 * (ys >> 6);
-        }
-}
-// angles per workgroup (chunk) and the parts over grid.y: all n angles in one part when the batch alone gives `want` workgroups, else
-// split (each part re-stages the edges).  No angles: no part.
-static void dir_angle_split(int n, size_t grid, size_t want, int& chunk, uint32_t& grid_y) {
-    size_t parts = (g_tune_dir_no_split || grid >= want) ? 1 : (want + grid - 1) / grid;
-    if (parts > (size_t)n) parts = (size_t)n;
-    chunk = n ? (int)((n + parts - 1) / parts) : 1;
-    grid_y = n ? (uint32_t)((n + chunk - 1) / chunk) : 0;
+    if (!levels) return SVT_HIP_OK;
+    return levels_frame_enqueue(groups, levels, ngroups, [&](const LevelsFrameDesc& fd, uint32_t total) -> int {
+        hipLaunchKernelGGL(levels_frame_kernel, dim3(total), dim3(256), 0, s, fd);
+        return launch_status("levels_frame");
+    });
 }
 
 // multi (directional modes only): several (dx, dy) of the same zone in one launch on edges staged once, see DirMulti
@@ -231,74 +120,42 @@ static int intra_pred_impl(void* d_dst, int32_t dst_stride, size_t dst_block_pit
                            void* stream, const DirMulti* multi) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_dst || !d_above || !d_left) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (mode < 0 || mode >= SVT_INTRA_MODES) return set_err(SVT_HIP_ERR_INVALID, "intra mode %d", mode);
-    if (!intra_size_ok(bw, bh)) return set_err(SVT_HIP_ERR_INVALID, "block %dx%d is not an AV1 transform size", bw, bh);
-    if (!sample_depth_ok(is_16bit, bd)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
-    if ((upsample_above | upsample_left) & ~1) return set_err(SVT_HIP_ERR_INVALID, "upsample flags");
-    if (mode >= SVT_INTRA_Z1) {
-        if (dx <= 0 || dy <= 0) return set_err(SVT_HIP_ERR_INVALID, "dx/dy must be positive");
-        const int need = NB_ORIGIN + (((bw + bh) << 1) + 2);
-        if (nb_pitch < need) return set_err(SVT_HIP_ERR_INVALID, "nb_pitch %d < %d", nb_pitch, need);
-    } else if (nb_pitch < NB_ORIGIN + (bw > bh ? bw : bh)) {
-        return set_err(SVT_HIP_ERR_INVALID, "nb_pitch %d too small", nb_pitch);
-    }
-    const int es = is_16bit ? 2 : 1;
-    const int pxl = 16 / es, ppl = bw < pxl ? bw : pxl;
-    const size_t per_block = (size_t)(bw / ppl) * bh;            // lanes per block: power of two, 4..512
-    const size_t items = per_block * nblocks;
-    size_t grid = (items + 255) / 256;
-    if (grid > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
-    // grid * 256 must be a multiple of per_block so that a lane keeps its (row, column) across iterations
-    if (per_block > 256) grid = (grid + 1) & ~(size_t)1;
+    IntraPredPlan p;
+    if (int rc = intra_pred_plan(p, d_dst, d_above, d_left, nb_pitch, mode, bw, bh, upsample_above, upsample_left, dx, dy, is_16bit, bd, nblocks, multi ? multi->n : 0,
+                                 intra_knobs()))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (mode >= SVT_INTRA_Z1) {
-        // last edge sample the reference may read: index max_base = (bw + bh - 1) << upsample; the LDS copy
-        // continues with copies of it for one lane-row (+2) so the pixel loop needs no bounds test
-        const int lim_a = NB_ORIGIN + ((bw + bh - 1) << upsample_above), lim_l = NB_ORIGIN + ((bw + bh - 1) << upsample_left);
-        const int up = upsample_above > upsample_left ? upsample_above : upsample_left;
-        const int n_pad = (lim_a > lim_l ? lim_a : lim_l) + ((16 / es) << up) + 3;
-        const size_t slots = per_block >= 256 ? 1 : 256 / per_block;
-        const size_t shmem = slots * (size_t)dir_slot_stride((n_pad + 10) & ~7, (uint32_t)(per_block >= 256 ? 256 : per_block)) * 4 + 2 * 64 * 4;   // pair dwords + zone 2's column table (see the kernel)
+    if (p.family == INTRA_FAM_DIR) {
         DirMulti dm;
         if (multi) dm = *multi; else dm.n = 0;
         dm.z2_tab = 0;
-        if (dm.n > 0 && mode == SVT_INTRA_Z2 && bw == ppl && (upsample_above | upsample_left) == 0) dir_z2_tables(dm);     // see DirMulti
-        // angles per workgroup: all of them when the batch alone gives every CU a few workgroups, else split over grid.y (each part re-stages the edges)
-        uint32_t gy = 1;
-        dm.chunk = 1;
-        if (dm.n > 0) dir_angle_split(dm.n, grid, (size_t)g_tune_dir_split_target * (size_t)g_num_cu, dm.chunk, gy);
+        if (p.tab) dir_z2_tables(dm);
+        dm.chunk = p.chunk;
 #define IDL(T, M, P, TB)                                                                                                     \
-    hipLaunchKernelGGL((intra_dir_kernel<T, M, P, TB>), dim3((uint32_t)grid, gy), dim3(256), shmem, s, (T*)d_dst, dst_stride, \
+    hipLaunchKernelGGL((intra_dir_kernel<T, M, P, TB>), dim3(p.grid_x, p.grid_y), dim3(256), p.lds_bytes, s, (T*)d_dst, dst_stride, \
                        dst_block_pitch, d_dst_offsets, (const T*)d_above, (const T*)d_left, nb_pitch, bw, bh,               \
-                       upsample_above, upsample_left, dx, dy, lim_a, lim_l, n_pad, bd, (uint32_t)nblocks, dm)
+                       upsample_above, upsample_left, dx, dy, p.lds.lim_a, p.lds.lim_l, p.lds.n_pad, bd, p.nblocks, dm)
 #define IDM(T, P)                                                                                                             \
     switch (mode) {                                                                                                           \
     case SVT_INTRA_Z1: IDL(T, IM_Z1, P, false); break; default: IDL(T, IM_Z3, P, false); break;                                \
-    case SVT_INTRA_Z2: if (dm.z2_tab) IDL(T, IM_Z2, P, true); else IDL(T, IM_Z2, P, false); break;                              \
+    case SVT_INTRA_Z2: if (p.tab) IDL(T, IM_Z2, P, true); else IDL(T, IM_Z2, P, false); break;                                  \
     }
-        // samples per lane (ppl) is a template parameter: 4 / 8 / 16 for bytes, 4 / 8 for 16-bit samples
-        if (is_16bit) { if (ppl == 8) { IDM(uint16_t, 8) } else { IDM(uint16_t, 4) } }
-        else if (ppl == 16) { IDM(uint8_t, 16) } else if (ppl == 8) { IDM(uint8_t, 8) } else { IDM(uint8_t, 4) }
+        // samples per lane is a template parameter: 4 / 8 / 16 for bytes, 4 / 8 for 16-bit samples
+        if (is_16bit) { if (p.npx == 8) { IDM(uint16_t, 8) } else { IDM(uint16_t, 4) } }
+        else if (p.npx == 16) { IDM(uint8_t, 16) } else if (p.npx == 8) { IDM(uint8_t, 8) } else { IDM(uint8_t, 4) }
 #undef IDM
 #undef IDL
         return launch_status("intra_dir");
     }
-    const int cnt = mode == SVT_INTRA_DC ? bw + bh : (mode == SVT_INTRA_DC_TOP ? bw : bh);
-    const uint32_t dc_magic = (uint32_t)(0x100000000ull / (uint64_t)cnt) + 1u;
-    // blocks per lane in the wide kernels: 4 for the modes with per-pixel arithmetic (SMOOTH*, PAETH: + 9 % on 2^21 32x32 blocks, A/B),
-    // 2 for the copy-like ones (DC*, V, H: 2 - 4 % SLOWER at 4)
-    const bool iu4 = mode == SVT_INTRA_SMOOTH || mode == SVT_INTRA_SMOOTH_V || mode == SVT_INTRA_SMOOTH_H || mode == SVT_INTRA_PAETH;
-    const size_t grid_w = (grid + (iu4 ? 4 : 2) - 1) / (iu4 ? 4 : 2);
 #define IPL(T, M)                                                                                                     \
-    if (bw >= 16 / (int)sizeof(T))                                                                                    \
-        hipLaunchKernelGGL((intra_pred_kernel<T, M, true, (M == IM_SMOOTH || M == IM_SMOOTH_V || M == IM_SMOOTH_H || M == IM_PAETH) ? 4 : 2>), dim3((uint32_t)(per_block > 256 ? (grid_w + 1) & ~(size_t)1 : grid_w)), dim3(256), 0, s, (T*)d_dst, dst_stride, \
+    if (p.wide)                                                                                                       \
+        hipLaunchKernelGGL((intra_pred_kernel<T, M, true, intra_wide_iu(M)>), dim3(p.grid_x), dim3(256), 0, s, (T*)d_dst, dst_stride, \
                            dst_block_pitch, d_dst_offsets, (const T*)d_above, (const T*)d_left, nb_pitch, bw, bh, bd,    \
-                           dc_magic, (uint32_t)nblocks);                                                              \
+                           p.dc_magic, p.nblocks);                                                                    \
     else                                                                                                              \
-        hipLaunchKernelGGL((intra_pred_kernel<T, M, false, 1>), dim3((uint32_t)grid), dim3(256), 0, s, (T*)d_dst, dst_stride, \
+        hipLaunchKernelGGL((intra_pred_kernel<T, M, false, 1>), dim3(p.grid_x), dim3(256), 0, s, (T*)d_dst, dst_stride, \
                            dst_block_pitch, d_dst_offsets, (const T*)d_above, (const T*)d_left, nb_pitch, bw, bh, bd,    \
-                           dc_magic, (uint32_t)nblocks)
+                           p.dc_magic, p.nblocks)
 #define IPM(T)                                                                                                        \
     switch (mode) {                                                                                                   \
     case SVT_INTRA_DC: IPL(T, IM_DC); break; case SVT_INTRA_V: IPL(T, IM_V); break; case SVT_INTRA_H: IPL(T, IM_H); break; \
@@ -312,6 +169,9 @@ static int intra_pred_impl(void* d_dst, int32_t dst_stride, size_t dst_block_pit
 #undef IPL
     return launch_status("intra_pred");
 }
+// (intra_wide_iu takes an SVT_INTRA_* mode: the kernels' IM_* numbers of the non-directional modes are the same)
+static_assert((int)IM_DC == SVT_INTRA_DC && (int)IM_SMOOTH == SVT_INTRA_SMOOTH && (int)IM_SMOOTH_V == SVT_INTRA_SMOOTH_V && (int)IM_SMOOTH_H == SVT_INTRA_SMOOTH_H &&
+              (int)IM_PAETH == SVT_INTRA_PAETH && (int)IM_DC_128 == SVT_INTRA_DC_128, "IM_* == SVT_INTRA_*");
 
 extern "C" int svt_hip_intra_pred_batch(void* d_dst, int32_t dst_stride, size_t dst_block_pitch,
                                         const uint32_t* d_dst_offsets, const void* d_above, const void* d_left,
@@ -326,12 +186,10 @@ extern "C" int svt_hip_filter_intra_edge_batch(void* d_edges, int32_t nb_pitch, 
                                                size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0 || strength == 0) return SVT_HIP_OK;
-    if (!d_edges) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (sz < 1 || sz > 129 || strength < 0 || strength > 3 || nb_pitch < NB_ORIGIN + sz)
-        return set_err(SVT_HIP_ERR_INVALID, "edge sz %d strength %d pitch %d", sz, strength, nb_pitch);
-    hipStream_t s = (hipStream_t)stream;
+    EdgePlan p;
+    if (int rc = filter_edge_plan(p, d_edges, nb_pitch, sz, strength, nblocks)) return rc;
     by_sample(is_16bit, [&](auto t) {
-        hipLaunchKernelGGL((filter_edge_kernel<decltype(t)>), dim3((uint32_t)nblocks), dim3(256), 0, s, (decltype(t)*)d_edges, nb_pitch, NB_ORIGIN, sz, strength, (uint32_t)nblocks);
+        hipLaunchKernelGGL((filter_edge_kernel<decltype(t)>), dim3(p.grid), dim3(p.threads), 0, (hipStream_t)stream, (decltype(t)*)d_edges, nb_pitch, NB_ORIGIN, sz, strength, p.nblocks);
     });
     return launch_status("filter_intra_edge");
 }
@@ -339,11 +197,10 @@ extern "C" int svt_hip_upsample_intra_edge_batch(void* d_edges, int32_t nb_pitch
                                                  size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_edges) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (sz < 1 || sz > 16 || nb_pitch < NB_ORIGIN + 2 * sz) return set_err(SVT_HIP_ERR_INVALID, "upsample sz %d pitch %d", sz, nb_pitch);
-    hipStream_t s = (hipStream_t)stream;
+    EdgePlan p;
+    if (int rc = upsample_edge_plan(p, d_edges, nb_pitch, sz, is_16bit, bd, nblocks)) return rc;
     by_sample(is_16bit, [&](auto t) {
-        hipLaunchKernelGGL((upsample_edge_kernel<decltype(t)>), dim3((uint32_t)nblocks), dim3(64), 0, s, (decltype(t)*)d_edges, nb_pitch, NB_ORIGIN, sz, is_16bit ? bd : 8, (uint32_t)nblocks);
+        hipLaunchKernelGGL((upsample_edge_kernel<decltype(t)>), dim3(p.grid), dim3(p.threads), 0, (hipStream_t)stream, (decltype(t)*)d_edges, nb_pitch, NB_ORIGIN, sz, p.bd, p.nblocks);
     });
     return launch_status("upsample_intra_edge");
 }
@@ -357,10 +214,7 @@ namespace svtdev {
 // ITS four blocks to share a kind, and a tile of 4 096 blocks holds ~ 315 of each, so the waves of a tile are uniform except at its
 // (at most 12) kind boundaries - 1.2 % of the waves; a mixed wave runs every kind it holds, several times a uniform wave's cost
 // (tiles of 1 024 blocks measured no faster than the global sort for that reason).  1 024 threads per workgroup: 256 workgroups of
-// 16 waves keep enough loads in flight.
-constexpr int BIP_ORDER_ITEMS = 4;
-constexpr int BIP_ORDER_THREADS = 1024;
-constexpr int BIP_ORDER_TILE = BIP_ORDER_THREADS * BIP_ORDER_ITEMS;
+// 16 waves keep enough loads in flight.  (The tile constants: intra_plan.h.)
 __global__ __launch_bounds__(BIP_ORDER_THREADS) void bip_order_tile_kernel(const BipBlk* __restrict__ blks, int w, int h, uint32_t* __restrict__ order, uint32_t nblocks) {
     __shared__ uint32_t s_cnt[16], s_base[16];
     if (threadIdx.x < 16) s_cnt[threadIdx.x] = 0;
@@ -399,11 +253,11 @@ static_assert(sizeof(svt_hip_intra_blk) == sizeof(BipBlk), "svt_hip_intra_blk la
 template <int W, int H>
 static int bip_launch(void* d_dst, int32_t dst_stride, size_t dst_block_pitch, const uint32_t* d_dst_offsets, const void* d_top_neigh,
                       const void* d_left_neigh, int32_t neigh_pitch, const svt_hip_intra_blk* d_blocks, const uint32_t* d_order, int is_16bit,
-                      int bd, size_t nblocks, uint32_t grid, hipStream_t s) {
+                      int bd, const BipPlan& p, hipStream_t s) {
     by_sample(is_16bit, [&](auto t) {
         using T = decltype(t);
-        hipLaunchKernelGGL((bip_kernel<T, W, H>), dim3(grid), dim3(64 * BIP_WAVES), 0, s, (T*)d_dst, dst_stride, dst_block_pitch, d_dst_offsets,
-                           (const T*)d_top_neigh, (const T*)d_left_neigh, neigh_pitch, (const BipBlk*)d_blocks, d_order, bd, (uint32_t)nblocks);
+        hipLaunchKernelGGL((bip_kernel<T, W, H>), dim3(p.grid), dim3(p.threads), 0, s, (T*)d_dst, dst_stride, dst_block_pitch, d_dst_offsets,
+                           (const T*)d_top_neigh, (const T*)d_left_neigh, neigh_pitch, (const BipBlk*)d_blocks, d_order, bd, p.nblocks);
     });
     return launch_status("build_intra_predictors");
 }
@@ -412,19 +266,10 @@ static int bip_impl(void* d_dst, int32_t dst_stride, size_t dst_block_pitch, con
                     int is_16bit, int bd, size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_dst || !d_top_neigh || !d_left_neigh || !d_blocks) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (tx_size < 0 || tx_size >= SVT_TX_SIZES_ALL) return set_err(SVT_HIP_ERR_INVALID, "tx_size %d", tx_size);
-    if (!sample_depth_ok(is_16bit, bd)) return set_err(SVT_HIP_ERR_INVALID, "bit depth %d", bd);
-    const int w = kTxW[tx_size], h = kTxH[tx_size];
-    if (neigh_pitch < 1 + 2 * (w > h ? w : h)) return set_err(SVT_HIP_ERR_INVALID, "neigh_pitch %d < %d", neigh_pitch, 1 + 2 * (w > h ? w : h));
-    if (dst_stride < w) return set_err(SVT_HIP_ERR_INVALID, "dst_stride %d < width %d", dst_stride, w);
-    if (!d_dst_offsets && dst_block_pitch == 0) return set_err(SVT_HIP_ERR_INVALID, "dst_block_pitch 0 without offsets");
-    const size_t per_wg = (size_t)BIP_WAVES * (64 / bip_lanes_per_block(w, h));       // blocks per workgroup
-    const size_t grid = (nblocks + per_wg - 1) / per_wg;
-    if (grid > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
-    hipStream_t s = (hipStream_t)stream;
+    BipPlan p;
+    if (int rc = bip_plan(p, d_dst, dst_stride, dst_block_pitch, d_dst_offsets, d_top_neigh, d_left_neigh, neigh_pitch, d_blocks, tx_size, is_16bit, bd, nblocks)) return rc;
 #define BIP_LAUNCH(W, H) bip_launch<W, H>(d_dst, dst_stride, dst_block_pitch, d_dst_offsets, d_top_neigh, d_left_neigh, neigh_pitch, d_blocks, d_order, is_16bit, bd, \
-                                          nblocks, (uint32_t)grid, s)
+                                          p, (hipStream_t)stream)
     TX_SWITCH(tx_size, BIP_LAUNCH)
 #undef BIP_LAUNCH
 }
@@ -449,14 +294,10 @@ extern "C" int svt_hip_intra_order_blocks_batch(const svt_hip_intra_blk* d_block
                                                 uint32_t* d_work, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    static_assert(BIP_ORDER_TILE == SVT_HIP_INTRA_ORDER_TILE, "header constant");
     (void)d_work;                                             // (the first version's global counters; unused)
-    if (!d_blocks || !d_order) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (tx_size < 0 || tx_size >= SVT_TX_SIZES_ALL) return set_err(SVT_HIP_ERR_INVALID, "tx_size %d", tx_size);
-    if (nblocks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks");
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((uint32_t)((nblocks + BIP_ORDER_TILE - 1) / BIP_ORDER_TILE));
-    hipLaunchKernelGGL(bip_order_tile_kernel, grid, dim3(BIP_ORDER_THREADS), 0, s, (const BipBlk*)d_blocks, kTxW[tx_size], kTxH[tx_size], d_order, (uint32_t)nblocks);
+    BipOrderPlan p;
+    if (int rc = bip_order_plan(p, d_blocks, d_order, tx_size, nblocks)) return rc;
+    hipLaunchKernelGGL(bip_order_tile_kernel, dim3(p.grid), dim3(p.threads), 0, (hipStream_t)stream, (const BipBlk*)d_blocks, p.w, p.h, d_order, p.nblocks);
     return launch_status("intra_order_blocks");
 }
 
@@ -510,26 +351,20 @@ static int ois_seg_enqueue(const OisPic& P, const OisJob& J, const OisDirSeg& S,
 
 // the directional candidates of the three zones in ONE launch (ois_dir3_kernel): 8x8 / 16x16 SAD mode
 static int ois_dir3_enqueue(const OisPic& P, const OisJob& J) {
-    const uint32_t bsize = J.plan.bsize;                         // = lanes per block: one lane per row
-    const size_t grid = ((size_t)bsize * J.nblocks + 255) / 256;
-    const int lim = NB_ORIGIN + (int)(2 * bsize - 1), n_pad = lim + 16 + 3;
-    const size_t shmem = (size_t)(256 / bsize) * dir_slot_stride((n_pad + 10) & ~7, bsize) * 4 + 2 * 64 * 4;
+    const uint32_t bsize = J.plan.bsize;
     const OisDirSeg* of[3] = {};                                 // at most one segment per zone (OisPlan::dir3)
     for (int i = 0; i < J.plan.nseg; i++) of[J.plan.seg[i].zone] = &J.plan.seg[i];
     DirOis3 m;
     memset(&m, 0, sizeof(m));
     ois_dir_multi(m.z1, P, J, of[0], false); ois_dir_multi(m.z2, P, J, of[1], false); ois_dir_multi(m.z3, P, J, of[2], false);
     dir_z2_tables(m.z2);
-    // angles per workgroup, per zone: as separate launches each zone wants dir_split_target (4) workgroups per CU before it stops
-    // spreading its angles over grid.y; with the three zones in one launch the sum counts - swept 1 .. 8 on the 1080p search
-    // (gpurun_out r03_f): 1 is best for 8x8 (0.0526 against 0.0567 ms at 4) and 16x16 (0.0443 against 0.0471)
-    uint32_t gy[3];
-    dir_angle_split(m.z1.n, grid, (size_t)g_num_cu, m.z1.chunk, gy[0]);
-    dir_angle_split(m.z2.n, grid, (size_t)g_num_cu, m.z2.chunk, gy[1]);
-    dir_angle_split(m.z3.n, grid, (size_t)g_num_cu, m.z3.chunk, gy[2]);
-    m.y_end[0] = gy[0]; m.y_end[1] = gy[0] + gy[1];
-    hipLaunchKernelGGL(bsize == 8 ? ois_dir3_kernel<8> : ois_dir3_kernel<16>, dim3((uint32_t)grid, gy[0] + gy[1] + gy[2]), dim3(256), shmem, P.s, J.above, J.left,
-                       (int32_t)ois_nb_pitch(bsize), (int)bsize, lim, n_pad, (uint32_t)J.nblocks, m);
+    const int n[3] = {m.z1.n, m.z2.n, m.z3.n};
+    OisDir3Plan p;                                               // the grid, the LDS and each zone's angle chunk (intra_plan.h)
+    ois_dir3_plan(p, bsize, J.nblocks, n, intra_knobs());
+    m.z1.chunk = p.chunk[0]; m.z2.chunk = p.chunk[1]; m.z3.chunk = p.chunk[2];
+    m.y_end[0] = p.y_end[0]; m.y_end[1] = p.y_end[1];
+    hipLaunchKernelGGL(bsize == 8 ? ois_dir3_kernel<8> : ois_dir3_kernel<16>, dim3(p.grid_x, p.grid_y), dim3(256), p.lds.bytes, P.s, J.above, J.left,
+                       (int32_t)ois_nb_pitch(bsize), (int)bsize, p.lds.lim_a, p.lds.n_pad, p.nblocks, m);
     return launch_status("ois_dir3");
 }
 

@@ -984,7 +984,11 @@ int svt_hip_ois_search_frame(const uint8_t *d_pic, uint32_t stride, uint32_t wid
  * (CFL_BUF_SQUARE = 1024 there).  subtract_average != 0 also applies subtract_average with the
  * encode pass's arguments (round_offset = w*h/2, num_pel_log2 = log2(w*h) of the chroma block) in
  * the same kernel.  Chroma sizes 4..32 in both dimensions.  Only the width/2 x height/2 entries of a block's Q3 buffer are
- * written; the rest of each row and the rows below keep what they held (the reference's pred_buf_q3 is not cleared either). */
+ * written; the rest of each row and the rows below keep what they held (the reference's pred_buf_q3 is not cleared either).
+ *
+ * Block counts: svt_hip_cfl_luma_subsampling_420_batch and svt_hip_subtract_average_batch take at most 2^25 - 1 blocks per call (the
+ * kernel counts lanes in 32 bits), svt_hip_cfl_predict_batch and svt_hip_txb_init_levels_batch at most 2^31 - 1; a larger nblocks is
+ * SVT_HIP_ERR_INVALID ("too many blocks for one launch"), checked on the size_t before anything is derived from it. */
 int svt_hip_cfl_luma_subsampling_420_batch(const void *d_luma, uint32_t luma_stride,
                                            size_t luma_block_pitch, const uint32_t *d_xy, int is_16bit,
                                            int16_t *d_q3, uint32_t q3_line, size_t q3_block_pitch,
@@ -1021,7 +1025,8 @@ int svt_hip_txb_init_levels_batch(const int32_t *d_coeff, size_t coeff_block_pit
  * Samples are uint8 (is_16bit = 0, bd = 8) or uint16.  mode: SVT_INTRA_*; for the
  * directional modes dx, dy, upsample_above, upsample_left are the reference's
  * arguments (dr_intra_derivative based).  Destination addressing as in
- * svt_hip_inv_txfm2d_add_batch. */
+ * svt_hip_inv_txfm2d_add_batch.  nblocks: at most 2^31 - 1, and at most 2^31 - 1 workgroups of 256
+ * lanes (a block takes 4 .. 512 lanes); more is SVT_HIP_ERR_INVALID. */
 enum { SVT_INTRA_DC, SVT_INTRA_V, SVT_INTRA_H, SVT_INTRA_SMOOTH, SVT_INTRA_SMOOTH_V, SVT_INTRA_SMOOTH_H,
        SVT_INTRA_PAETH, SVT_INTRA_DC_TOP, SVT_INTRA_DC_LEFT, SVT_INTRA_DC_128, SVT_INTRA_Z1, SVT_INTRA_Z2,
        SVT_INTRA_Z3, SVT_INTRA_MODES };
@@ -1041,7 +1046,8 @@ int svt_hip_intra_pred_batch(void *d_dst, int32_t dst_stride, size_t dst_block_p
  *     `neigh_pitch` samples apart: element 0 = the above-left corner sample, element 1 + i = above[i] / left[i];
  *     neigh_pitch >= 1 + 2 * max(width, height).  Samples uint8 (is_16bit = 0, bd 8) or uint16.
  *   d_blocks: one descriptor per block (device memory); n_top_px / n_left_px above the block's width / height are clamped.
- *   Destination addressing as in svt_hip_inv_txfm2d_add_batch. */
+ *   Destination addressing as in svt_hip_inv_txfm2d_add_batch.
+ *   nblocks: at most 2^31 - 1 in this call, in the ordered form and in svt_hip_intra_order_blocks_batch; more is SVT_HIP_ERR_INVALID. */
 typedef struct svt_hip_intra_blk {
     uint8_t mode;                 /* AV1 PredictionMode: DC 0, V 1, H 2, D45 3, D135 4, D113 5, D157 6, D203 7, D67 8,
                                      SMOOTH 9, SMOOTH_V 10, SMOOTH_H 11, PAETH 12 */
@@ -1293,7 +1299,8 @@ int svt_hip_intra_has_bottom_left(int sb_size_mi, int bsize, int mi_row, int mi_
                                   int ss_y);
 
 /* av1_filter_intra_edge{,_high} / av1_upsample_intra_edge{,_high} (aom_dsp_rtcd.h:152,
- * 431; C: EbIntraPrediction.c:3539-3660) on nblocks edges laid out like d_above. */
+ * 431; C: EbIntraPrediction.c:3539-3660) on nblocks edges laid out like d_above, an edge per
+ * workgroup: at most 2^31 - 1 of them, more is SVT_HIP_ERR_INVALID. */
 int svt_hip_filter_intra_edge_batch(void *d_edges, int32_t nb_pitch, int sz, int strength,
                                     int is_16bit, size_t nblocks, void *stream);
 int svt_hip_upsample_intra_edge_batch(void *d_edges, int32_t nb_pitch, int sz, int is_16bit,

@@ -120,6 +120,26 @@ def test_txb_init_levels_at_scale(dsp):
         assert not body[:, :2].any() and not body[:, 2 + h:].any() and not body[:, :, w:].any()
 
 
+@pytest.mark.parametrize("w,h", [(4, 4), (64, 64)])
+@pytest.mark.parametrize("slack", [0, 4])
+def test_txb_init_levels_both_store_widths_three_blocks(dsp, w, h, slack):
+    """the smallest and the largest level map, three blocks, with a 16-byte-aligned pitch (16-byte stores: 8 and 256 lanes per block) and
+    with one that is only 4-byte aligned (dword stores: 32 and 256 lanes); oracle per block, the slack between buffers untouched"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(9100 + w + slack)
+    n = 3
+    coeff = rng.integers(-200, 201, size=(n, h * w)).astype(np.int32)
+    coeff[1] *= 1 << 16
+    pitch = ((w + 4) * (h + 6) + 16 + 15) // 16 * 16 + 16 + slack
+    buf = poison.tensor((n, pitch), torch.uint8, "cuda").fill_(0x77)
+    dsp.txb_init_levels(dev(coeff), w, h, buf)
+    got = buf.cpu().numpy()
+    for i in range(n):
+        lv = np.full(pitch, 0x77, np.uint8)
+        O.svt_oracle_txb_init_levels(ptr(coeff[i]), c_int(w), c_int(h), ctypes.c_void_p(lv.ctypes.data + 2 * (w + 4)))
+        assert np.array_equal(got[i], lv), (w, h, i)
+
+
 def test_cfl_argument_errors(dsp):
     L = dsp.lib
     z = torch.zeros(4096, dtype=torch.int16, device="cuda")

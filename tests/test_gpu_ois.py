@@ -143,6 +143,35 @@ def test_ois_directional_angles_split_over_grid_variant(dsp, bsize):
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
 
 
+@pytest.mark.parametrize("no_split", [0, 1])
+def test_ois_zone2_tables_three_angles_few_blocks(dsp, no_split):
+    """zone 2 with the host's per-angle tables (intra_dir_kernel<.., IM_Z2, 8, true>) on 8x8 blocks: three angles of that zone alone (one
+    segment, so not the three-zone launch) on 12 blocks - one workgroup per part, the angle split gives grid.y 3, chunk 1 - and with
+    dir_no_split one part that walks the three angles; each against the oracle"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(8811)
+    W, H, pad, bsize = 48, 16, 16, 8
+    buf = rng.integers(0, 256, size=(H + 2 * pad, W + 2 * pad), dtype=np.uint8)
+    stride = buf.shape[1]
+    blocks = [(x, y) for y in range(0, H, bsize) for x in range(0, W, bsize)]
+    modes, deltas = np.array([0, 4, 5, 6], np.uint8), np.array([0, 1, -2, 3], np.int8)      # DC; D135 + 3, D113 - 6, D157 + 9 degrees
+    n = len(modes)
+    plane = dev(buf)
+    try:
+        assert dsp.lib.svt_hip_tune(b"dir_no_split", no_split) == 0
+        dist, best = dsp.ois_search(plane[pad:, pad:], stride, W, H, _xy(blocks), bsize, modes, deltas)
+    finally:
+        dsp.lib.svt_hip_tune(b"dir_no_split", 0)
+    dist = dist.cpu().numpy(); best = best.cpu().numpy()
+    pic = ctypes.c_void_p(buf.ctypes.data + pad * stride + pad)
+    om = np.zeros(61, np.uint8); od = np.zeros(61, np.int8); ds = np.zeros(61, np.uint32)
+    om[:n] = modes; od[:n] = deltas
+    for i, (x, y) in enumerate(blocks):
+        bi = O.svt_oracle_ois_block(pic, c_int(stride), c_int(W), c_int(H), c_int(x), c_int(y), c_int(bsize), c_int(n), ptr(om), ptr(od), ptr(ds))
+        assert np.array_equal(dist[i].astype(np.int64), ds[:n].astype(np.int64)), (i, x, y)
+        assert int(best[i]) == bi, (i, x, y)
+
+
 @pytest.mark.parametrize("bsize,tl", [(8, 0), (16, 0), (8, 2), (32, 0), (64, 0), (32, 2)])
 def test_ois_fused_non_directional_variant(dsp, bsize, tl):
     """ois_nd_kernel (non-directional candidates predicted and summed straight from the picture, one launch when the list has no

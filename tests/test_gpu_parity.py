@@ -780,6 +780,23 @@ def test_intra_pred_tail_counts(dsp, tx_size, n):
             assert np.array_equal(out, ref), (TX_SIZES[tx_size], mode, bd)
 
 
+@pytest.mark.parametrize("n", [1, 3])
+def test_intra_directional_64x64_16bit_block_counts(dsp, n):
+    """64x64 at 16 bits is the one shape with 512 lanes per block, two workgroups each: one and three blocks, the three zones (the pinned
+    rows of tests/c/intra_plan_pins.h had zone 3 at seven blocks only)"""
+    O = svtlibs.oracle()
+    bw = bh = 64; bd = 10
+    rng = np.random.default_rng(7900 + n)
+    a = rng.integers(0, 1 << bd, size=(n, 304)).astype(np.uint16); l = rng.integers(0, 1 << bd, size=(n, 304)).astype(np.uint16)
+    for zone, dx, dy in ((1, DR_DERIV[3], 1), (2, DR_DERIV[23], DR_DERIV[67]), (3, 1, DR_DERIV[87])):
+        out = dsp.intra_pred(_as_dev(a), _as_dev(l), 9 + zone, bw, bh, bd, 0, 0, dx, dy).cpu().numpy().view(np.uint16)
+        ref = np.zeros((n, bh, bw), np.uint16)
+        for i in range(n):
+            pa = ctypes.c_void_p(a[i].ctypes.data + NB * 2); pl = ctypes.c_void_p(l[i].ctypes.data + NB * 2)
+            O.svt_oracle_dr_prediction_hbd(zone, ptr(ref[i]), ctypes.c_ssize_t(bw), bw, bh, pa, pl, 0, 0, dx, dy, bd)
+        assert np.array_equal(out, ref), (zone, n)
+
+
 # ---- routes and template variants of svt_hip_txfm.hip that no other test, benchmark or tool reaches (tests/c/tx_plan_host.cpp pins their
 # plans): one full workgroup and one more block, which is where the grid rounding and the tail guard can go wrong, with the knob, table or
 # operand that selects the route ----
