@@ -14,12 +14,13 @@ The directory name contains '-', so import it through
 """
 from __future__ import annotations
 
-import collections
 import ctypes
 import os
-from ctypes import c_int, c_int16, c_int32, c_size_t, c_uint32, c_void_p
+from ctypes import c_int, c_int32, c_uint32, c_void_p
 
+from . import records, signatures
 from . import tables  # noqa: F401  (host-side quantiser / scan tables for callers outside the encoder)
+from .records import *  # noqa: F401,F403  (every ctypes record, numpy dtype and constant that mirrors include/svt_hip_dsp.h)
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libsvt_hip_dsp.so")
@@ -51,249 +52,7 @@ def tx_log_scale(tx_size: int) -> int:
 def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise SvtHipError(f"{path} not built - run `python __graft_entry__.py build` (no CPU fallback exists)")
-    L = ctypes.CDLL(path)
-    L.svt_hip_last_error.restype = ctypes.c_char_p
-    L.svt_hip_device_name.restype = ctypes.c_char_p
-    L.svt_hip_malloc.restype = c_void_p
-    L.svt_hip_malloc.argtypes = [c_size_t]
-    L.svt_hip_free.argtypes = [c_void_p]
-    L.svt_hip_memcpy_h2d.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_memcpy_d2h.argtypes = [c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_stream_sync.argtypes = [c_void_p]
-    L.svt_hip_malloc_spread.argtypes = [c_void_p, c_int, c_size_t, c_void_p]
-    L.svt_hip_me_setup_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32] + [c_void_p] * 7 + [c_size_t, c_void_p]
-    L.svt_hip_me_fullpel_search_areas_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                                        c_void_p, c_void_p, c_uint32, c_size_t, c_void_p]
-    L.svt_hip_me_bipred_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_uint32] + [c_void_p] * 5 + [c_uint32, c_int, c_int, c_int,
-                                          c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_fwd_txfm2d_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]
-    L.svt_hip_pack64_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_void_p]
-    L.svt_hip_inv_txfm2d_add_batch.argtypes = [c_void_p, c_void_p, c_int, c_int32, c_size_t, c_void_p, c_size_t,
-                                               c_int, c_int, c_int, c_void_p]
-    L.svt_hip_quantize_b_batch.argtypes = [c_void_p, c_size_t, c_int] + [c_void_p] * 4 + [c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_void_p, c_int, c_size_t, c_void_p]
-    L.svt_hip_encode_recon_planes_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_size_t,
-                                                    c_int, c_int, c_int, c_int] + [c_void_p] * 5 + [c_void_p] * 7
-    L.svt_hip_encode_recon_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_int] + [c_void_p] * 5 + [c_void_p] * 8
-    L.svt_hip_fwd_quant_sad_batch.argtypes = [c_void_p, c_void_p, c_size_t, c_int, c_int] + [c_void_p] * 5 + \
-                                             [c_void_p] * 6 + [c_void_p]
-    for name in ("svt_hip_sad_batch", "svt_hip_sse_batch"):
-        getattr(L, name).argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_size_t, c_uint32, c_uint32,
-                                     c_void_p, c_size_t, c_void_p]
-    L.svt_hip_residual_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_size_t, c_void_p, c_uint32,
-                                         c_size_t, c_uint32, c_uint32, c_size_t, c_void_p]
-    L.svt_hip_sad_search_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_uint32, c_size_t,
-                                           c_uint32, c_uint32, c_int16, c_int16, c_void_p, c_void_p, c_void_p, c_size_t,
-                                           c_void_p]
-    L.svt_hip_intra_pred_batch.argtypes = [c_void_p, c_int32, c_size_t, c_void_p, c_void_p, c_void_p, c_int32, c_int,
-                                           c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_size_t, c_void_p]
-    L.svt_hip_filter_intra_edge_batch.argtypes = [c_void_p, c_int32, c_int, c_int, c_int, c_size_t, c_void_p]
-    L.svt_hip_upsample_intra_edge_batch.argtypes = [c_void_p, c_int32, c_int, c_int, c_int, c_size_t, c_void_p]
-    L.svt_hip_full_distortion32_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_size_t, c_uint32,
-                                                  c_uint32, c_int, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_fwd_quant_batch.argtypes = [c_void_p, c_size_t, c_int, c_int, c_int] + [c_void_p] * 5 + [c_void_p] * 5 + [c_void_p]
-    L.svt_hip_fwd_quant_planes_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_size_t, c_int, c_int,
-                                                 c_int, c_int] + [c_void_p] * 5 + [c_void_p] * 7 + [c_void_p]
-    L.svt_hip_me_sb_search_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_size_t, c_int, c_int,
-                                             c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_me_sb_search_planes_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_int, c_int,
-                                                    c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_sad_search_planes_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p,
-                                                  c_uint32, c_uint32, c_int16, c_int16, c_void_p, c_void_p, c_void_p,
-                                                  c_size_t, c_void_p]
-    L.svt_hip_cfl_luma_subsampling_420_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_int, c_void_p, c_uint32,
-                                                         c_size_t, c_uint32, c_uint32, c_int, c_size_t, c_void_p]
-    L.svt_hip_subtract_average_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_uint32, c_uint32, c_int32, c_int32, c_size_t,
-                                                 c_void_p]
-    L.svt_hip_cfl_predict_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p,
-                                            c_void_p, c_int, c_uint32, c_uint32, c_int, c_size_t, c_void_p]
-    L.svt_hip_ois_work_bytes.argtypes = [c_uint32, c_int, c_size_t]
-    L.svt_hip_ois_work_bytes.restype = c_size_t
-    L.svt_hip_ois_search_batch.argtypes = [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_int,
-                                           c_void_p, c_void_p, c_void_p, c_size_t, c_size_t, c_void_p]
-    L.svt_hip_txb_init_levels_batch.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_uint32, c_uint32, c_size_t, c_void_p]
-    L.svt_hip_encode_recon_frame.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.svt_hip_encode_recon_frame_ex.argtypes = [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.svt_hip_sad_planes_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_void_p,
-                                           c_size_t, c_void_p]
-    L.svt_hip_sad_x4d_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_uint32,
-                                        c_void_p, c_size_t, c_void_p]
-    L.svt_hip_sad_avg_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_size_t,
-                                        c_uint32, c_uint32, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_residual16_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_size_t, c_void_p, c_uint32, c_size_t,
-                                           c_uint32, c_uint32, c_size_t, c_void_p]
-    L.svt_hip_picture_full_distortion32_batch.argtypes = [c_void_p, c_size_t, c_void_p, c_size_t, c_uint32, c_uint32, c_void_p, c_int,
-                                                          c_void_p, c_size_t, c_void_p]
-    L.svt_hip_hme_level_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
-                                          c_void_p, c_size_t, c_void_p]
-    L.svt_hip_hme_level_regions_batch.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
-                                                  c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_hme_level_params.argtypes = [c_int, c_void_p, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32,
-                                           c_uint32, c_uint32, c_uint32, c_void_p]
-    L.svt_hip_me_fullpel_search_batch.argtypes = [c_void_p, c_uint32, c_size_t, c_void_p, c_void_p, c_uint32, c_size_t, c_void_p,
-                                                  c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_uint32,
-                                                  c_size_t, c_void_p]
-    L.svt_hip_build_intra_predictors_batch.argtypes = [c_void_p, c_int32, c_size_t, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int,
-                                                       c_int, c_int, c_size_t, c_void_p]
-    L.svt_hip_ois_search_frame.argtypes = [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_int, c_void_p]
-    L.svt_hip_intra_neighbor_px.argtypes = [c_void_p, c_void_p]
-    L.svt_hip_intra_has_top_right.argtypes = [c_int] * 12
-    L.svt_hip_intra_has_bottom_left.argtypes = [c_int] * 12
-    L.svt_hip_y4m_parse_header.argtypes = [ctypes.c_char_p, c_void_p]
-    L.svt_hip_y4m_frame_bytes.argtypes = [c_void_p]
-    L.svt_hip_y4m_frame_bytes.restype = c_size_t
-    L.svt_hip_y4m_open.argtypes = [ctypes.c_char_p, c_void_p, c_void_p]
-    L.svt_hip_y4m_read_frame.argtypes = [c_void_p, c_void_p, c_size_t]
-    L.svt_hip_y4m_close.argtypes = [c_void_p]
-    L.svt_hip_picture_import.argtypes = [c_void_p, c_uint32, c_uint32, c_int, c_int, c_int, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p,
-                                         c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_void_p]
-    L.svt_hip_picture_pad.argtypes = [c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, c_int, c_void_p]
-    L.svt_hip_picture_luma8.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_int, c_void_p]
-    L.svt_hip_picture_decimate.argtypes = [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint32,
-                                           c_uint32, c_uint32, c_void_p]
-    L.svt_hip_full_loop_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.svt_hip_full_loop_frame.restype = c_int
-    L.svt_hip_intra_fast_loop_frame.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p]
-    L.svt_hip_intra_fast_loop_frame.restype = c_int
-    L.svt_hip_fast_pick_frame.argtypes = [c_void_p, c_int, c_int, c_void_p]
-    L.svt_hip_fast_pick_frame.restype = c_int
-    L.svt_hip_intra_fast_search_scratch_bytes.argtypes = [c_void_p, c_int]
-    L.svt_hip_intra_fast_search_scratch_bytes.restype = c_size_t
-    L.svt_hip_intra_fast_search_frame.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_intra_fast_search_frame.restype = c_int
-    L.svt_hip_md_intra_candidates.argtypes = [c_uint32, c_uint32, c_uint32, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.svt_hip_md_intra_candidates.restype = c_int
-    L.svt_hip_cdef_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    L.svt_hip_cdef_search_frame.restype = c_int
-    L.svt_hip_cdef_apply_frame.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
-    L.svt_hip_cdef_apply_frame.restype = c_int
-    L.svt_hip_motion_estimate_frame_scratch_bytes.argtypes = [c_void_p, c_uint32]
-    L.svt_hip_motion_estimate_frame_scratch_bytes.restype = c_size_t
-    L.svt_hip_motion_estimate_frame.argtypes = [c_void_p] * 4 + [c_uint32] + [c_void_p] * 6 + [c_size_t, c_void_p]
-    L.svt_hip_motion_estimate_frame.restype = c_int
-    L.svt_hip_me_subpel_check.argtypes = [c_void_p] * 5 + [c_uint32] + [c_void_p] * 4
-    L.svt_hip_me_subpel_check.restype = c_int
-    L.svt_hip_me_subpel_frame.argtypes = [c_void_p] * 5 + [c_uint32] + [c_void_p] * 5
-    L.svt_hip_me_subpel_frame.restype = c_int
-    L.svt_hip_motion_estimate_subpel_frame_scratch_bytes.argtypes = [c_void_p, c_uint32]
-    L.svt_hip_motion_estimate_subpel_frame_scratch_bytes.restype = c_size_t
-    L.svt_hip_motion_estimate_subpel_frame.argtypes = [c_void_p] * 5 + [c_uint32] + [c_void_p] * 6 + [c_size_t, c_void_p]
-    L.svt_hip_motion_estimate_subpel_frame.restype = c_int
-    L.svt_hip_me_subpel_planes.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_uint32, c_uint32, c_void_p, c_void_p]
-    L.svt_hip_me_subpel_planes.restype = c_int
-    L.svt_hip_coeff_rate_frame.argtypes = [c_void_p, c_int, c_void_p]
-    L.svt_hip_coeff_rate_frame.restype = c_int
-    L.svt_hip_coeff_cost_index.argtypes = [c_int, c_void_p, c_void_p]
-    L.svt_hip_coeff_cost_index.restype = c_int
-    L.svt_hip_tx_decide_frame.argtypes = [c_void_p, c_int, c_void_p]
-    L.svt_hip_tx_decide_frame.restype = c_int
-    L.svt_hip_tx_search_scratch_bytes.argtypes = [c_void_p, c_int]
-    L.svt_hip_tx_search_scratch_bytes.restype = c_size_t
-    L.svt_hip_tx_search_frame.argtypes = [c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_void_p, c_size_t, c_void_p]
-    L.svt_hip_tx_search_frame.restype = c_int
-    L.svt_hip_tx_type_rate_index.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p]
-    L.svt_hip_tx_type_rate_index.restype = c_int
-    L.svt_hip_cfl_search_scratch_bytes.argtypes = [c_void_p, c_int]
-    L.svt_hip_cfl_search_scratch_bytes.restype = c_size_t
-    L.svt_hip_cfl_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_cfl_search_frame.restype = c_int
-    L.svt_hip_cfl_decide_frame.argtypes = [c_void_p, c_int, c_void_p]
-    L.svt_hip_cfl_decide_frame.restype = c_int
-    L.svt_hip_cfl_pick_scratch_bytes.argtypes = [c_void_p, c_int]
-    L.svt_hip_cfl_pick_scratch_bytes.restype = c_size_t
-    L.svt_hip_cfl_pick_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_cfl_pick_frame.restype = c_int
-    L.svt_hip_picture_stats_frame.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]
-    L.svt_hip_picture_stats_frame.restype = c_int
-    L.svt_hip_inter_pred_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p]
-    L.svt_hip_inter_pred_frame.restype = c_int
-    L.svt_hip_warp_fit_frame.argtypes = [c_void_p, c_int, c_void_p]
-    L.svt_hip_warp_fit_frame.restype = c_int
-    L.svt_hip_warp_pred_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p]
-    L.svt_hip_warp_pred_frame.restype = c_int
-    L.svt_hip_warp_tables.argtypes = [c_void_p, c_void_p]
-    L.svt_hip_warp_tables.restype = None
-    L.svt_hip_interp_sse_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p]
-    L.svt_hip_interp_sse_frame.restype = c_int
-    L.svt_hip_interp_decide_frame.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
-    L.svt_hip_interp_decide_frame.restype = c_int
-    L.svt_hip_interp_search_scratch_bytes.argtypes = [c_void_p, c_int, c_int]
-    L.svt_hip_interp_search_scratch_bytes.restype = c_size_t
-    L.svt_hip_interp_search_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_interp_search_frame.restype = c_int
-    L.svt_hip_inter_fast_pick_frame.argtypes = [c_void_p, c_int, c_int, c_void_p]
-    L.svt_hip_inter_fast_pick_frame.restype = c_int
-    L.svt_hip_inter_fast_search_scratch_bytes.argtypes = [c_void_p, c_int]
-    L.svt_hip_inter_fast_search_scratch_bytes.restype = c_size_t
-    L.svt_hip_inter_fast_search_frame.argtypes = [c_void_p, c_int, c_uint32, c_uint32, c_int, c_int, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_inter_fast_search_frame.restype = c_int
-    L.svt_hip_md_decide_frame.argtypes = [c_void_p, c_int, c_void_p]
-    L.svt_hip_md_decide_frame.restype = c_int
-    L.svt_hip_blk_geom_mds.argtypes = [c_uint32, c_void_p]
-    L.svt_hip_blk_geom_mds.restype = c_int
-    L.svt_hip_partition_decide_frame.argtypes = [c_void_p, c_void_p]
-    L.svt_hip_partition_decide_frame.restype = c_int
-    L.svt_hip_recon_final_scratch_bytes.argtypes = [c_uint32]
-    L.svt_hip_recon_final_scratch_bytes.restype = c_size_t
-    L.svt_hip_recon_final_frame.argtypes = [c_void_p, c_void_p]
-    L.svt_hip_recon_final_frame.restype = c_int
-    L.svt_hip_intra_encode_scratch_bytes.argtypes = [c_uint32, c_uint32]
-    L.svt_hip_intra_encode_scratch_bytes.restype = c_size_t
-    L.svt_hip_intra_encode_tables_bytes.argtypes = []
-    L.svt_hip_intra_encode_tables_bytes.restype = c_size_t
-    L.svt_hip_intra_encode_tables_fill.argtypes = [c_void_p]
-    L.svt_hip_intra_encode_tables_fill.restype = c_int
-    L.svt_hip_intra_encode_launches.argtypes = [c_uint32, c_uint32, c_int]
-    L.svt_hip_intra_encode_launches.restype = c_int
-    L.svt_hip_intra_encode_frame.argtypes = [c_void_p, c_void_p]
-    L.svt_hip_intra_encode_frame.restype = c_int
-    L.svt_hip_dlf_mi_frame.argtypes = [c_void_p, c_void_p]
-    L.svt_hip_dlf_apply_frame.argtypes = [c_void_p, c_void_p]
-    L.svt_hip_dlf_search_frame.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_dlf_search_scratch_bytes.argtypes = [c_uint32, c_uint32, c_uint32]
-    L.svt_hip_dlf_search_scratch_bytes.restype = c_size_t
-    L.svt_hip_dlf_check.argtypes = [c_void_p, c_int]
-    L.svt_hip_dlf_mi_check.argtypes = [c_void_p]
-    L.svt_hip_dlf_limits.argtypes = [c_int, c_int, c_void_p]
-    L.svt_hip_dlf_levels.argtypes = [c_void_p, c_void_p]
-    L.svt_hip_dlf_pick_level.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.svt_hip_dlf_level_from_q.argtypes = [c_int, c_int, c_int, c_void_p]
-    for name in ("mi_frame", "apply_frame", "search_frame", "check", "mi_check", "limits", "levels", "pick_level", "level_from_q"):
-        getattr(L, "svt_hip_dlf_" + name).restype = c_int
-    L.svt_hip_lr_apply_frame.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p]
-    L.svt_hip_lr_try_frame.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]
-    L.svt_hip_lr_wiener_stats_frame.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_lr_check.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_uint32]
-    L.svt_hip_lr_unit_grid.argtypes = [c_uint32, c_uint32, c_void_p, c_int, c_void_p]
-    L.svt_hip_lr_unit_limits.argtypes = [c_uint32, c_uint32, c_void_p, c_int, c_uint32, c_void_p]
-    for name in ("apply_frame", "try_frame", "wiener_stats_frame", "check", "unit_grid", "unit_limits"):
-        getattr(L, "svt_hip_lr_" + name).restype = c_int
-    L.svt_hip_lr_wiener_solve.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    L.svt_hip_lr_walk_start.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
-    L.svt_hip_lr_walk_next.argtypes = [c_void_p, ctypes.c_int64]
-    L.svt_hip_lr_finish.argtypes = [c_int, c_int, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]
-    for name in ("wiener_solve", "walk_start", "walk_next", "finish"):
-        getattr(L, "svt_hip_lr_" + name).restype = c_int
-    L.svt_hip_lr_sgr_stats_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_lr_sgr_walk_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]
-    L.svt_hip_lr_sgr_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_lr_sgr_solve.argtypes = [c_void_p, c_uint32, c_int, c_void_p]
-    L.svt_hip_lr_sgr_walk_host.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_void_p, c_int]
-    L.svt_hip_lr_sgr_ep_range.argtypes = [c_void_p, c_int, c_void_p]
-    for name in ("sgr_stats_frame", "sgr_walk_frame", "sgr_search_frame", "sgr_solve", "sgr_walk_host", "sgr_ep_range"):
-        getattr(L, "svt_hip_lr_" + name).restype = c_int
-    L.svt_hip_lr_sgr_scratch_bytes.argtypes = [c_uint32, c_uint32, c_void_p, c_uint32, c_int, c_int]
-    L.svt_hip_lr_sgr_scratch_bytes.restype = c_size_t
-    L.svt_hip_lr_stats_scratch_bytes.argtypes = [c_uint32, c_uint32, c_void_p, c_uint32]
-    L.svt_hip_lr_stats_scratch_bytes.restype = c_size_t
-    for name in ("unit_offset", "units_per_pic"):
-        getattr(L, "svt_hip_lr_" + name).argtypes = [c_uint32, c_uint32, c_void_p] + ([c_int] if name == "unit_offset" else [])
-        getattr(L, "svt_hip_lr_" + name).restype = c_uint32
-    L.svt_hip_md_search_scratch_bytes.argtypes = [c_void_p, c_int]
-    L.svt_hip_md_search_scratch_bytes.restype = c_size_t
-    L.svt_hip_md_search_frame.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.svt_hip_md_search_frame.restype = c_int
-    return L
+    return signatures.apply(ctypes.CDLL(path))
 
 
 COEFF_COST_WORDS, EOB_COST_WORDS = 529, 22          # one LV_MAP_COEFF_COST / LV_MAP_EOB_COST as int32 words
@@ -325,338 +84,6 @@ def tx_type_rate_index(tx_size: int, is_inter: bool, reduced_tx_set_used: bool =
     return bool(rc), a.value, b.value
 
 
-class MeFrameParams(ctypes.Structure):
-    """svt_hip_me_frame_params: what MotionEstimateLcu reads of its picture, sequence and ME context (include/svt_hip_dsp.h)"""
-    _fields_ = [(n, c_int32) for n in ("picture_width", "picture_height", "slice_type", "temporal_layer_index", "hierarchical_levels",
-                                       "enable_hme_flag", "enable_hme_level0_flag", "enable_hme_level1_flag", "enable_hme_level2_flag",
-                                       "number_hme_search_region_in_width", "number_hme_search_region_in_height",
-                                       "hme_level0_total_search_area_width", "hme_level0_total_search_area_height")] + \
-               [("hme_search_area_in_width_array", (ctypes.c_uint16 * 2) * 3), ("hme_search_area_in_height_array", (ctypes.c_uint16 * 2) * 3)] + \
-               [(n, c_int32) for n in ("search_area_width", "search_area_height")] + [("ref_pic_poc", c_int32 * 2)] + \
-               [(n, c_int32) for n in ("is_used_as_reference_flag", "max_number_of_pus_per_sb", "nsq_search_level", "cu8x8_mode",
-                                       "fractional_search_method", "flavour")]
-
-    @classmethod
-    def from_lcu_prm(cls, prm):
-        """from the int32 parameter block of oracle/ref_me.c's ref_motion_estimate_lcu (its slots 2 / 3, the SB origin, and 27 .. 41,
-        the picture geometry, are not parameters of a picture call)"""
-        p = cls()
-        (p.picture_width, p.picture_height, p.slice_type, p.temporal_layer_index, p.hierarchical_levels) = (int(prm[i]) for i in (0, 1, 4, 6, 7))
-        (p.enable_hme_flag, p.enable_hme_level0_flag, p.enable_hme_level1_flag, p.enable_hme_level2_flag) = (int(prm[i]) for i in (8, 9, 10, 11))
-        p.is_used_as_reference_flag, p.search_area_width, p.search_area_height = int(prm[12]), int(prm[13]), int(prm[14])
-        p.number_hme_search_region_in_width, p.number_hme_search_region_in_height = int(prm[15]), int(prm[16])
-        p.hme_level0_total_search_area_width, p.hme_level0_total_search_area_height = int(prm[17]), int(prm[18])
-        p.ref_pic_poc[0], p.ref_pic_poc[1], p.flavour = int(prm[19]), int(prm[20]), int(prm[21])
-        p.cu8x8_mode, p.fractional_search_method, p.max_number_of_pus_per_sb, p.nsq_search_level = (int(prm[i]) for i in (23, 24, 25, 26))
-        for lv in range(3):
-            for i in range(2):
-                p.hme_search_area_in_width_array[lv][i] = int(prm[42 + 4 * lv + i])
-                p.hme_search_area_in_height_array[lv][i] = int(prm[44 + 4 * lv + i])
-        return p
-
-
-class MeSubpelParams(ctypes.Structure):
-    """svt_hip_me_subpel_params: the enables of the half- / quarter-pel refinement (the reference sets all of them to 1)"""
-    _fields_ = [(n, c_int32) for n in ("fractional_search64x64", "enable_half_pel32x32", "enable_half_pel16x16", "enable_half_pel8x8", "enable_quarter_pel")]
-
-
-class MePyramid(ctypes.Structure):
-    """svt_hip_me_pyramid: the padded full / quarter / sixteenth luma buffers of one picture (or of a stack of pictures)"""
-    _fields_ = [("d_plane", c_void_p * 3), ("stride", c_uint32 * 3), ("origin_x", c_uint32 * 3), ("origin_y", c_uint32 * 3),
-                ("pitch", ctypes.c_uint64 * 3)]
-
-
-class PicStatsPlanes(ctypes.Structure):
-    """svt_hip_pic_stats_planes: the padded luma, Cb, Cr and 1/16 luma buffers of one picture (or of a stack of pictures)"""
-    _fields_ = [("d_plane", c_void_p * 4), ("stride", c_uint32 * 4), ("origin_x", c_uint32 * 4), ("origin_y", c_uint32 * 4),
-                ("pitch", ctypes.c_uint64 * 4)]
-
-
-class PicStatsParams(ctypes.Structure):
-    """svt_hip_pic_stats_params"""
-    _fields_ = [(n, c_int32) for n in ("picture_width", "picture_height", "block_mean_calc_prec", "regions_per_width", "regions_per_height")]
-
-
-class PicStatsOut(ctypes.Structure):
-    """svt_hip_pic_stats_out: the eight device outputs of svt_hip_picture_stats_frame"""
-    _fields_ = [(n, c_void_p) for n in ("d_y_mean", "d_variance", "d_cb_mean", "d_cr_mean", "d_pic_avg_variance", "d_histogram",
-                                        "d_avg_intensity_region", "d_avg_intensity")]
-
-
-PicStatsResult = collections.namedtuple("PicStatsResult", ("y_mean", "variance", "cb_mean", "cr_mean", "pic_avg_variance", "histogram",
-                                                           "avg_intensity_region", "avg_intensity"))
-
-
-class InterBlk(ctypes.Structure):
-    """svt_hip_inter_blk: one (block, candidate) of svt_hip_inter_pred_frame (16 bytes; inter_blk_dtype() is its numpy twin)"""
-    _fields_ = [("x", ctypes.c_uint16), ("y", ctypes.c_uint16), ("mv", (ctypes.c_int16 * 2) * 2), ("pred_direction", ctypes.c_uint8),
-                ("filter_x", ctypes.c_uint8), ("filter_y", ctypes.c_uint8), ("pad", ctypes.c_uint8)]
-
-
-class InterPredGroup(ctypes.Structure):
-    """svt_hip_inter_pred_group"""
-    _fields_ = [("d_ref", c_void_p * 2), ("ref_stride", c_uint32), ("ss", c_int32), ("bwidth", c_int32), ("bheight", c_int32),
-                ("nblocks", c_uint32), ("d_blk", c_void_p), ("d_pred", c_void_p), ("pred_stride", c_uint32), ("d_src", c_void_p),
-                ("src_stride", c_uint32), ("d_dist", c_void_p)]
-
-
-class WarpSamples(ctypes.Structure):
-    """svt_hip_warp_samples: what av1_find_samples returns for a block (132 bytes; warp_samples_dtype() is its numpy twin)"""
-    _fields_ = [("nsamples", c_int32), ("pts", c_int32 * 16), ("pts_inref", c_int32 * 16)]
-
-
-class WarpModel(ctypes.Structure):
-    """svt_hip_warp_model: the local warp model of one (block, candidate) (36 bytes; warp_model_dtype() is its numpy twin)"""
-    _fields_ = [("mat", c_int32 * 6), ("alpha", ctypes.c_int16), ("beta", ctypes.c_int16), ("gamma", ctypes.c_int16), ("delta", ctypes.c_int16),
-                ("valid", ctypes.c_uint8), ("num_proj_ref", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2)]
-
-
-class WarpFitGroup(ctypes.Structure):
-    """svt_hip_warp_fit_group"""
-    _fields_ = [("bsize", c_int32), ("nblocks", c_uint32), ("ncand", c_int32), ("d_samples", c_void_p), ("d_blk", c_void_p), ("d_model", c_void_p),
-                ("d_nvalid", c_void_p)]
-
-
-class WarpPredGroup(ctypes.Structure):
-    """svt_hip_warp_pred_group"""
-    _fields_ = [("d_ref", c_void_p), ("ref_stride", c_uint32), ("ss", c_int32), ("bwidth", c_int32), ("bheight", c_int32), ("nblocks", c_uint32),
-                ("ncand", c_int32), ("d_blk", c_void_p), ("d_model", c_void_p), ("d_sel", c_void_p), ("n", c_int32), ("sel_first", c_int32),
-                ("d_pred", c_void_p), ("pred_stride", c_uint32), ("d_src", c_void_p), ("src_stride", c_uint32), ("d_dist", c_void_p)]
-
-
-UNI_PRED_LIST_0, UNI_PRED_LIST_1, BI_PRED = 0, 1, 2
-INTER_PRED_MAX_GROUPS = 48
-
-
-class InterpSseGroup(ctypes.Structure):
-    """svt_hip_interp_sse_group"""
-    _fields_ = [("d_ref", (c_void_p * 3) * 2), ("ref_stride", c_uint32 * 3), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3),
-                ("bwidth", c_int32), ("bheight", c_int32), ("nblocks", c_uint32), ("d_blk", c_void_p), ("d_sse", c_void_p)]
-
-
-class InterpDecision(ctypes.Structure):
-    """svt_hip_interp_decision (32 bytes; interp_decision_dtype() is its numpy twin)"""
-    _fields_ = [("interp_filters", c_uint32), ("switchable_rate", c_int32), ("rd", ctypes.c_int64), ("skip_sse_sb", ctypes.c_int64),
-                ("skip_txfm_sb", c_int32), ("pad", c_uint32)]
-
-
-class InterpParams(ctypes.Structure):
-    """svt_hip_interp_params"""
-    _fields_ = [("full_lambda", c_uint32), ("ac_dequant_q3", c_int32), ("d_rates", c_void_p), ("use_uv", c_int32), ("mode", c_int32)]
-
-
-class InterpDecideGroup(ctypes.Structure):
-    """svt_hip_interp_decide_group"""
-    _fields_ = [("bwidth", c_int32), ("bheight", c_int32), ("nblocks", c_uint32), ("d_sse", c_void_p), ("d_ctx", c_void_p),
-                ("d_searchable", c_void_p), ("d_decision", c_void_p), ("d_blk", c_void_p), ("d_blk_out", c_void_p)]
-
-
-class InterpSearchGroup(ctypes.Structure):
-    """svt_hip_interp_search_group"""
-    _fields_ = [("sse", InterpSseGroup), ("d_ctx", c_void_p), ("d_searchable", c_void_p), ("d_decision", c_void_p), ("d_blk_out", c_void_p)]
-
-
-INTERP_DUAL_FAST, INTERP_FULL, INTERP_SINGLE = 0, 1, 2
-
-
-class InterCand(ctypes.Structure):
-    """svt_hip_inter_cand: what only the fast cost reads of an inter candidate (16 bytes; inter_cand_dtype() is its numpy twin)"""
-    _fields_ = [("pred_mv", (ctypes.c_int16 * 2) * 2), ("mode_ctx", ctypes.c_int16), ("pred_mode", ctypes.c_uint8),
-                ("ref_frame_type", ctypes.c_uint8), ("drl_index", ctypes.c_uint8), ("ref_mv_count", ctypes.c_uint8), ("drl_ctx", ctypes.c_uint8),
-                ("flags", ctypes.c_uint8)]
-
-
-class InterFastBlk(ctypes.Structure):
-    """svt_hip_inter_fast_blk: the block's context bytes (16 bytes; inter_fast_blk_dtype() is its numpy twin)"""
-    _fields_ = [(n, ctypes.c_uint8) for n in ("skip_flag_context", "is_inter_ctx", "reference_mode_context", "compoud_reference_type_context",
-                                              "comp_ref_p", "comp_ref_p1", "comp_ref_p2", "comp_bwdref_p", "comp_bwdref_p1")] + \
-               [("single_ref_p", ctypes.c_uint8 * 6), ("has_uv", ctypes.c_uint8)]
-
-
-INTER_FAST_RATE_TABLES = (("skipModeFacBits", (3, 3)), ("newMvModeFacBits", (6, 3)), ("zeroMvModeFacBits", (2, 3)), ("refMvModeFacBits", (6, 3)),
-                          ("drlModeFacBits", (3, 3)), ("interCompoundModeFacBits", (8, 9)), ("singleRefFacBits", (3, 6, 3)),
-                          ("compRefTypeFacBits", (5, 3)), ("compRefFacBits", (3, 3, 3)), ("compBwdRefFacBits", (3, 2, 3)),
-                          ("compInterFacBits", (5, 3)), ("motionModeFacBits", (22, 3)), ("motionModeFacBits1", (22, 2)),
-                          ("intraInterFacBits", (4, 2)), ("nmv_vec_cost", (4,)))      # svt_hip_inter_fast_rates
-INTER_FAST_RATE_WORDS = 383
-MV_VALS = 32767
-
-
-class InterFastRates(ctypes.Structure):
-    """svt_hip_inter_fast_rates"""
-    _fields_ = [("skipModeFacBits", (c_int32 * 3) * 3), ("newMvModeFacBits", (c_int32 * 3) * 6), ("zeroMvModeFacBits", (c_int32 * 3) * 2),
-                ("refMvModeFacBits", (c_int32 * 3) * 6), ("drlModeFacBits", (c_int32 * 3) * 3), ("interCompoundModeFacBits", (c_int32 * 9) * 8),
-                ("singleRefFacBits", ((c_int32 * 3) * 6) * 3), ("compRefTypeFacBits", (c_int32 * 3) * 5), ("compRefFacBits", ((c_int32 * 3) * 3) * 3),
-                ("compBwdRefFacBits", ((c_int32 * 3) * 2) * 3), ("compInterFacBits", (c_int32 * 3) * 5), ("motionModeFacBits", (c_int32 * 3) * 22),
-                ("motionModeFacBits1", (c_int32 * 2) * 22), ("intraInterFacBits", (c_int32 * 2) * 4), ("nmv_vec_cost", c_int32 * 4)]
-
-
-class InterFastPickGroup(ctypes.Structure):
-    """svt_hip_inter_fast_pick_group"""
-    _fields_ = [("bsize", c_int32), ("bsize_uv", c_int32), ("nblocks", c_uint32), ("ninter", c_int32), ("nintra", c_int32), ("nfl", c_int32),
-                ("lambda_", c_uint32), ("ac_dequant_q3", ctypes.c_int16), ("reference_mode_select", c_int32), ("switchable_motion_mode", c_int32)] + \
-               [(n, c_void_p) for n in ("d_blk", "d_cand_in", "d_ctx", "d_rates", "d_mv_cost", "d_dist", "d_dist_cb", "d_dist_cr", "d_intra_cost",
-                                        "d_intra_rate", "d_cand", "d_sorted", "d_cost", "d_rate", "d_ref_fast_cost", "d_all_cost", "d_blk_out",
-                                        "d_cand_out", "d_src_xy_out")]
-
-
-class InterFastSearchGroup(ctypes.Structure):
-    """svt_hip_inter_fast_search_group"""
-    _fields_ = [("pick", InterFastPickGroup), ("bwidth", c_int32), ("bheight", c_int32), ("use_chroma", c_int32), ("d_ref", (c_void_p * 3) * 2),
-                ("ref_stride", c_uint32 * 3), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3), ("d_pred_out", c_void_p * 3),
-                ("d_intra_pred", c_void_p)]
-
-
-class MdBlk(ctypes.Structure):
-    """svt_hip_md_blk: the block's bytes the full cost reads (4 bytes; md_blk_dtype() is its numpy twin)"""
-    _fields_ = [("skip_flag_context", ctypes.c_uint8), ("has_uv", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2)]
-
-
-MD_RATE_TABLES = (("skipModeFacBits", (3, 3)), ("intraUVmodeFacBits", (2, 13, 15)), ("cflAlphaFacBits", (8, 2, 16)))      # svt_hip_md_rates
-MD_RATE_WORDS = 655
-MD_NO_INTRA = 0xFF
-
-
-class MdRates(ctypes.Structure):
-    """svt_hip_md_rates"""
-    _fields_ = [("skipModeFacBits", (c_int32 * 3) * 3), ("intraUVmodeFacBits", ((c_int32 * 15) * 13) * 2), ("cflAlphaFacBits", ((c_int32 * 16) * 2) * 8)]
-
-
-class MdDecision(ctypes.Structure):
-    """svt_hip_md_decision (72 bytes; md_decision_dtype() is its numpy twin)"""
-    _fields_ = [("cost", ctypes.c_uint64), ("cost_luma", ctypes.c_uint64), ("merge_cost", ctypes.c_uint64), ("skip_cost", ctypes.c_uint64),
-                ("full_lambda_rate", ctypes.c_uint64), ("full_distortion", c_uint32), ("eob", ctypes.c_uint16 * 3)] + \
-               [(n, ctypes.c_uint8) for n in ("slot", "cand", "count", "is_intra", "skip_flag", "merge_flag", "y_has_coeff", "u_has_coeff",
-                                              "v_has_coeff", "block_has_coeff", "tx_type", "best_intra_mode", "uv_mode", "cfl_alpha_idx",
-                                              "cfl_alpha_signs")] + [("pad", ctypes.c_uint8 * 7)]
-
-
-class MdDecideGroup(ctypes.Structure):
-    """svt_hip_md_decide_group"""
-    _fields_ = [("bsize", c_int32), ("nblocks", c_uint32), ("n", c_int32), ("ninter", c_int32), ("nintra", c_int32), ("lambda_", c_uint32),
-                ("slice_is_intra", c_int32), ("full_loop_escape", c_int32), ("modes", ctypes.c_uint8 * 64)] + \
-               [(n, c_void_p) for n in ("d_luma", "d_dist_cb", "d_dist_cr", "d_bits_cb", "d_bits_cr", "d_eob_cb", "d_eob_cr", "d_rate", "d_cand",
-                                        "d_cand_out", "d_cfl", "d_blk", "d_rates", "d_decision", "d_full_cost")] + \
-               [(n, c_void_p * 3) for n in ("d_pred", "d_best_pred", "d_qcoeff", "d_dqcoeff", "d_best_qcoeff", "d_best_dqcoeff")] + \
-               [("d_inter_blk", c_void_p), ("d_best_inter_blk", c_void_p)]
-
-
-def md_blk_dtype():
-    """numpy dtype of svt_hip_md_blk"""
-    import numpy as np
-    return np.dtype([("skip_flag_context", np.uint8), ("has_uv", np.uint8), ("pad", np.uint8, (2,))])
-
-
-def md_decision_dtype():
-    """numpy dtype of svt_hip_md_decision"""
-    import numpy as np
-    return np.dtype([("cost", "<u8"), ("cost_luma", "<u8"), ("merge_cost", "<u8"), ("skip_cost", "<u8"), ("full_lambda_rate", "<u8"),
-                     ("full_distortion", "<u4"), ("eob", "<u2", (3,))] +
-                    [(n, np.uint8) for n in ("slot", "cand", "count", "is_intra", "skip_flag", "merge_flag", "y_has_coeff", "u_has_coeff",
-                                             "v_has_coeff", "block_has_coeff", "tx_type", "best_intra_mode", "uv_mode", "cfl_alpha_idx",
-                                             "cfl_alpha_signs")] + [("pad", np.uint8, (7,))])
-
-
-SB_BLOCKS, SB_SQUARES, SB_MAX_FINAL = 1101, 341, 256      # a 64x64 superblock: blocks in md scan, squares, the most blocks it can code
-PART_NO_SRC = 0xFFFFFFFF
-PARTITION_SPLIT = 3
-PARTITION_BITS_SHAPE = (20, 11)                            # partitionFacBits
-
-
-class BlkGeom(ctypes.Structure):
-    """svt_hip_blk_geom (16 bytes)"""
-    _fields_ = [("sqi_mds", ctypes.c_uint16)] + [(n, ctypes.c_uint8) for n in ("bsize", "shape", "depth", "nsi", "totns", "d1i", "origin_x", "origin_y",
-                                                                             "bwidth", "bheight", "sq_size", "is_last_quadrant", "has_uv", "pad")]
-
-
-class PartitionArgs(ctypes.Structure):
-    """svt_hip_partition_args"""
-    _fields_ = [(n, c_uint32) for n in ("nsb", "nleaves", "nsrc", "lambda_", "pic_width", "pic_height")] + [("slice_is_intra", c_int32), ("pad", c_int32)] + \
-               [(n, c_void_p) for n in ("d_sb", "d_leaf", "d_decision", "d_cost", "d_partition_bits", "d_sq", "d_final_count", "d_final", "d_final_decision")]
-
-
-RECON_FINAL_MAX_GROUPS = 32
-RECON_OK, RECON_NO_SRC, RECON_BSIZE, RECON_OUTSIDE, RECON_TX_TYPE = 0, 1, 2, 3, 4      # d_status of svt_hip_recon_final_frame
-SB_QCOEFF_LUMA = 4096                                      # int32 per superblock of the luma coefficient stream; chroma a quarter
-
-
-class ReconFinalGroup(ctypes.Structure):
-    """svt_hip_recon_final_group"""
-    _fields_ = [("src_first", c_uint32), ("nblocks", c_uint32), ("bsize", c_int32), ("tx_type_uv", c_int32),
-                ("d_best_pred", c_void_p * 3), ("d_best_dqcoeff", c_void_p * 3), ("d_best_qcoeff", c_void_p * 3)]
-
-
-class ReconFinalArgs(ctypes.Structure):
-    """svt_hip_recon_final_args"""
-    _fields_ = [("nsb", c_uint32), ("nsrc", c_uint32), ("ngroups", c_int32), ("planes", c_int32)] + \
-               [(n, c_void_p) for n in ("d_final", "d_final_count", "d_decision", "groups")] + [("d_recon", c_void_p * 3)] + \
-               [("stride", c_uint32 * 3), ("width", c_uint32 * 3), ("height", c_uint32 * 3), ("d_status", c_void_p), ("d_sb_qcoeff", c_void_p * 3),
-                ("d_coeff_offset", c_void_p), ("d_scratch", c_void_p), ("scratch_bytes", ctypes.c_size_t)]
-
-
-# d_status of svt_hip_intra_encode_frame
-INTRA_ENC_OK, INTRA_ENC_NO_SRC, INTRA_ENC_OUTSIDE, INTRA_ENC_TX_TYPE, INTRA_ENC_NOT_INTRA, INTRA_ENC_MODE, INTRA_ENC_CFL_SIZE, INTRA_ENC_SCHEDULE = 0, 1, 3, 4, 5, 6, 7, 8
-
-
-class IntraEncodeArgs(ctypes.Structure):
-    """svt_hip_intra_encode_args"""
-    _fields_ = [(n, c_uint32) for n in ("npics", "sb_cols", "sb_rows", "sb_pitch", "nsrc", "blk_pitch")] + \
-               [(n, c_void_p) for n in ("d_final", "d_final_count", "d_blk")] + [("d_src", c_void_p * 3), ("d_recon", c_void_p * 3)] + \
-               [(n, c_uint32 * 3) for n in ("src_stride", "stride", "width", "height")] + \
-               [("src_pic_pitch", ctypes.c_size_t * 3), ("recon_pic_pitch", ctypes.c_size_t * 3)] + \
-               [(n, c_void_p) for n in ("q_luma", "q_chroma", "d_tables", "d_status", "d_result")] + [("d_sb_qcoeff", c_void_p * 3)] + \
-               [("d_coeff_offset", c_void_p), ("d_scratch", c_void_p), ("scratch_bytes", ctypes.c_size_t)]
-
-
-def intra_enc_blk_dtype():
-    """numpy dtype of svt_hip_intra_enc_blk (8 bytes)"""
-    import numpy as np
-    return np.dtype([("is_intra", "u1"), ("mode", "u1"), ("angle_delta", "i1"), ("uv_mode", "u1"), ("cfl_alpha_idx", "u1"), ("cfl_alpha_signs", "u1"),
-                     ("tx_type", "u1"), ("tx_type_uv", "u1")])
-
-
-def intra_enc_result_dtype():
-    """numpy dtype of svt_hip_intra_enc_result (8 bytes)"""
-    import numpy as np
-    return np.dtype([("eob", "<u2", (3,)), ("tx_type", "u1"), ("pad", "u1")])
-
-
-def part_leaf_dtype():
-    """numpy dtype of svt_hip_part_leaf (12 bytes)"""
-    import numpy as np
-    return np.dtype([("mds_idx", "<u2"), ("split_flag", "u1"), ("tot_d1_blocks", "u1"), ("left_partition", "i1"), ("above_partition", "i1"),
-                     ("pad", "u1", (2,)), ("src", "<u4")])
-
-
-def part_sb_dtype():
-    """numpy dtype of svt_hip_part_sb (12 bytes)"""
-    import numpy as np
-    return np.dtype([("leaf_first", "<u4"), ("leaf_count", "<u2"), ("origin_x", "<u2"), ("origin_y", "<u2"), ("pad", "<u2")])
-
-
-def part_sq_dtype():
-    """numpy dtype of svt_hip_part_sq (16 bytes)"""
-    import numpy as np
-    return np.dtype([("cost", "<u8"), ("best_d1_blk", "<u2"), ("part", "u1"), ("split_flag", "u1"), ("tested", "u1"), ("pad", "u1", (3,))])
-
-
-def part_final_dtype():
-    """numpy dtype of svt_hip_part_final (12 bytes)"""
-    import numpy as np
-    return np.dtype([("mds_idx", "<u2"), ("x", "<u2"), ("y", "<u2"), ("bsize", "u1"), ("part", "u1"), ("src", "<u4")])
-
-
-def pack_md_rates(tables):
-    """dict of the three int32 tables (MD_RATE_TABLES shapes) -> int32 [655] in svt_hip_md_rates order"""
-    import numpy as np
-    parts = []
-    for name, shape in MD_RATE_TABLES:
-        a = np.asarray(tables[name], np.int32)
-        assert a.shape == shape, (name, a.shape)
-        parts.append(a.reshape(-1))
-    return np.concatenate(parts)
-
-
 BSIZE_W = (4, 4, 8, 8, 8, 16, 16, 16, 32, 32, 32, 64, 64, 64, 128, 128, 4, 16, 8, 32, 16, 64)      # block_size_wide / _high, AV1 block_size order
 BSIZE_H = (4, 8, 4, 8, 16, 8, 16, 32, 16, 32, 64, 32, 64, 128, 64, 128, 16, 4, 32, 8, 64, 16)
 
@@ -670,71 +97,12 @@ def md_plane_sizes(bsize):
     return out
 
 
-def inter_cand_dtype():
-    """numpy dtype of svt_hip_inter_cand"""
-    import numpy as np
-    return np.dtype([("pred_mv", np.int16, (2, 2)), ("mode_ctx", np.int16), ("pred_mode", np.uint8), ("ref_frame_type", np.uint8),
-                     ("drl_index", np.uint8), ("ref_mv_count", np.uint8), ("drl_ctx", np.uint8), ("flags", np.uint8)])
-
-
-def inter_fast_blk_dtype():
-    """numpy dtype of svt_hip_inter_fast_blk"""
-    import numpy as np
-    return np.dtype([(n, np.uint8) for n in ("skip_flag_context", "is_inter_ctx", "reference_mode_context", "compoud_reference_type_context",
-                                             "comp_ref_p", "comp_ref_p1", "comp_ref_p2", "comp_bwdref_p", "comp_bwdref_p1")] +
-                    [("single_ref_p", np.uint8, (6,)), ("has_uv", np.uint8)])
-
-
-def pack_inter_fast_rates(tables):
-    """dict of the fifteen int32 tables (INTER_FAST_RATE_TABLES shapes) -> int32 [383] in svt_hip_inter_fast_rates order"""
-    import numpy as np
-    parts = []
-    for name, shape in INTER_FAST_RATE_TABLES:
-        a = np.asarray(tables[name], np.int32)
-        assert a.shape == shape, (name, a.shape)
-        parts.append(a.reshape(-1))
-    return np.concatenate(parts)
-
-
-def interp_decision_dtype():
-    """numpy dtype of svt_hip_interp_decision"""
-    import numpy as np
-    return np.dtype([("interp_filters", np.uint32), ("switchable_rate", np.int32), ("rd", np.int64), ("skip_sse_sb", np.int64),
-                     ("skip_txfm_sb", np.int32), ("pad", np.uint32)])
-
-
-def inter_blk_dtype():
-    """numpy dtype of svt_hip_inter_blk"""
-    import numpy as np
-    return np.dtype([("x", np.uint16), ("y", np.uint16), ("mv", np.int16, (2, 2)), ("pred_direction", np.uint8), ("filter_x", np.uint8),
-                     ("filter_y", np.uint8), ("pad", np.uint8)])
-
-
-def warp_samples_dtype():
-    """numpy dtype of svt_hip_warp_samples"""
-    import numpy as np
-    return np.dtype([("nsamples", np.int32), ("pts", np.int32, (16,)), ("pts_inref", np.int32, (16,))])
-
-
-def warp_model_dtype():
-    """numpy dtype of svt_hip_warp_model"""
-    import numpy as np
-    return np.dtype([("mat", np.int32, (6,)), ("alpha", np.int16), ("beta", np.int16), ("gamma", np.int16), ("delta", np.int16),
-                     ("valid", np.uint8), ("num_proj_ref", np.uint8), ("pad", np.uint8, (2,))])
-
-
 def warp_tables(lib):
     """HOST: the library's statement of the warp filter (int16 [193, 8]) and of Div_Lut (uint16 [257]) (svt_hip_warp_tables; no device)"""
     import numpy as np
     f, d = np.zeros((193, 8), np.int16), np.zeros(257, np.uint16)
     lib.svt_hip_warp_tables(f.ctypes.data, d.ctypes.data)
     return f, d
-
-
-class Y4mInfo(ctypes.Structure):
-    """svt_hip_y4m_info: what read_y4m_header (Source/App/EncApp/EbAppInputy4m.c:35) takes from the header line"""
-    _fields_ = [("width", c_uint32), ("height", c_uint32), ("fr_n", c_uint32), ("fr_d", c_uint32), ("bit_depth", c_uint32),
-                ("interlaced", c_uint32), ("chroma", ctypes.c_char * 8), ("scan_type", ctypes.c_char)]
 
 
 def y4m_parse_header(lib, line):
@@ -789,6 +157,21 @@ def _np16(a):
     return a
 
 
+def _pic_planes(p, stack, bit_depth, **sets):
+    """the (Y, Cb, Cr) tensors of every named set -> d_<set>, <set>_stride and <set>_pitch of a picture record (a set that is None stays NULL)"""
+    for name, planes in sets.items():
+        for i, t in enumerate(planes or ()):
+            assert t.stride(-1) == 1 and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
+            getattr(p, "d_" + name)[i], getattr(p, name + "_stride")[i] = t.data_ptr(), t.stride(-2)
+            getattr(p, name + "_pitch")[i] = t.stride(0) if stack else 0
+
+
+def _per_plane(dst, given, defaults):
+    """dst[p] = given[p] where the caller's list reaches that far, else what the plane's own tensor says"""
+    for p in range(len(dst)):
+        dst[p] = given[p] if given is not None and p < len(given) else defaults[p]
+
+
 class SvtHipDsp:
     """Batched device API on torch CUDA(HIP) tensors.  Names follow the reference's
     dispatch slots (aom_dsp_rtcd.h): fwd_txfm2d <-> av1_fwd_txfm2d_WxH, ..."""
@@ -813,6 +196,16 @@ class SvtHipDsp:
     @staticmethod
     def _p(t):
         return c_void_p(t.data_ptr())
+
+    @staticmethod
+    def _as_groups(make, groups):
+        """groups: a ctypes array from the builder `make`, or the list of dicts itself -> (the array, the number of groups)"""
+        return (make(groups) if isinstance(groups, list) else groups), len(groups)
+
+    @staticmethod
+    def _scratch_args(scratch):
+        """-> (pointer, bytes) of a scratch tensor, (NULL, 0) of None"""
+        return (c_void_p(scratch.data_ptr()), scratch.numel() * scratch.element_size()) if scratch is not None else (None, 0)
 
     def device_name(self):
         return self.lib.svt_hip_device_name().decode()
@@ -839,13 +232,11 @@ class SvtHipDsp:
         """svt_hip_membw_probe: mode 0 fill / 1 copy / 2 the fused kernel's 1 : 6 read / write mix; enqueues one kernel"""
         if nbytes is None:
             nbytes = (src if mode else dst).numel() * (src if mode else dst).element_size()
-        self.lib.svt_hip_membw_probe.argtypes = [c_int, c_void_p, c_void_p, c_size_t, c_void_p]
         self._check(self.lib.svt_hip_membw_probe(mode, self._p(dst), self._p(src) if src is not None else None, nbytes,
                                                  self._stream()), "svt_hip_membw_probe")
 
     def membw_probe_chain(self, in0, in1, outs, nblocks):
         """svt_hip_membw_probe_chain: the fused 32x32 chain's traffic alone on the caller's arrays (2 x 1 KiB in, 3 x 4 KiB out per block)"""
-        self.lib.svt_hip_membw_probe_chain.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
         self._check(self.lib.svt_hip_membw_probe_chain(self._p(in0), self._p(in1), self._p(outs[0]), self._p(outs[1]), self._p(outs[2]), nblocks,
                                                        self._stream()), "svt_hip_membw_probe_chain")
 
@@ -1102,12 +493,6 @@ class SvtHipDsp:
                     "svt_hip_ois_search_batch")
         return dist, best
 
-    class OisGroup(ctypes.Structure):
-        """svt_hip_ois_group"""
-        _fields_ = [("d_xy", ctypes.c_void_p), ("bsize", ctypes.c_uint32), ("modes", ctypes.c_void_p), ("angle_deltas", ctypes.c_void_p),
-                    ("ncand", ctypes.c_int32), ("d_distortion", ctypes.c_void_p), ("d_best_index", ctypes.c_void_p), ("d_work", ctypes.c_void_p),
-                    ("work_bytes", ctypes.c_size_t), ("nblocks", ctypes.c_size_t)]
-
     def ois_search_frame(self, pic, stride, width, height, groups):
         """The open-loop intra search of a picture, every block size in ONE call (svt_hip_ois_search_frame).  groups: list of
         (xy int32 [n], bsize, modes, angle_deltas) -> list of (distortion int32 [n, ncand], best_index int8 [n])"""
@@ -1231,22 +616,10 @@ class SvtHipDsp:
         return best_sad, best_mv
 
     # -- frame-level encode pass: all (plane, size) groups of a frame in one call --------------------
-    class FrameGroup(ctypes.Structure):
-        _fields_ = [("d_src", c_void_p), ("src_stride", c_uint32), ("d_pred", c_void_p), ("pred_stride", c_uint32),
-                    ("d_recon", c_void_p), ("recon_stride", c_uint32), ("d_xy", c_void_p), ("d_offsets", c_void_p),
-                    ("nblocks", c_uint32), ("tx_size", ctypes.c_int32), ("tx_type", ctypes.c_int32), ("d_iscan", c_void_p),
-                    ("d_qcoeff", c_void_p), ("d_eob", c_void_p), ("d_coeff", c_void_p), ("d_dqcoeff", c_void_p)]
-
     def make_frame_groups(self, groups):
         """groups: list of dicts with tensors src, pred, recon (planes), xy, iscan, qcoeff, eob and optional offsets, coeff,
         dqcoeff, plus src_stride / pred_stride / recon_stride, tx_size, tx_type.  -> ctypes array (keep the tensors alive!)"""
-        arr = (self.FrameGroup * len(groups))()
-        for i, g in enumerate(groups):
-            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-            arr[i] = self.FrameGroup(P("src"), g["src_stride"], P("pred"), g["pred_stride"], P("recon"), g["recon_stride"], P("xy"),
-                                     P("offsets"), g["xy"].numel(), g["tx_size"], g["tx_type"], P("iscan"), P("qcoeff"), P("eob"),
-                                     P("coeff"), P("dqcoeff"))
-        return arr
+        return records.build(FrameGroup, groups, at_least=0)
 
     def encode_recon_frame(self, group_array, qrow, is_16bit=False, bd=8):
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
@@ -1254,23 +627,10 @@ class SvtHipDsp:
                                                         tabs[1].ctypes.data, tabs[2].ctypes.data, tabs[3].ctypes.data, tabs[4].ctypes.data,
                                                         self._stream()), "svt_hip_encode_recon_frame")
 
-    class FrameCflGroup(ctypes.Structure):
-        _fields_ = [("d_luma_recon", c_void_p), ("luma_stride", c_uint32), ("d_pred_cb", c_void_p), ("pred_stride_cb", c_uint32),
-                    ("d_pred_cr", c_void_p), ("pred_stride_cr", c_uint32), ("d_xy", c_void_p), ("d_alpha_q3_cb", c_void_p),
-                    ("d_alpha_q3_cr", c_void_p), ("width", c_uint32), ("height", c_uint32), ("nblocks", c_uint32)]
-
-    class FrameLevels(ctypes.Structure):
-        _fields_ = [("d_levels_buf", c_void_p), ("levels_block_pitch", ctypes.c_size_t)]
-
     def make_frame_cfl_groups(self, groups):
         """groups: list of dicts with tensors luma_recon, pred_cb, pred_cr (planes), xy, alpha_cb, alpha_cr (int32 per block), the
         strides luma_stride / cb_stride / cr_stride and the chroma block's width, height"""
-        arr = (self.FrameCflGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            arr[i] = self.FrameCflGroup(self._p(g["luma_recon"]), g["luma_stride"], self._p(g["pred_cb"]), g["cb_stride"], self._p(g["pred_cr"]),
-                                        g["cr_stride"], self._p(g["xy"]), self._p(g["alpha_cb"]), self._p(g["alpha_cr"]), g["width"], g["height"],
-                                        g["xy"].numel())
-        return arr
+        return records.build(FrameCflGroup, groups)
 
     def make_frame_levels(self, level_bufs):
         """level_bufs: one uint8 [nblocks, pitch] tensor (or None) per group of the call"""
@@ -1289,10 +649,6 @@ class SvtHipDsp:
                     "svt_hip_encode_recon_frame_ex")
 
     # -- hierarchical ME: one level for all SBs, clipping on the device ----------------------------
-    class HmeParams(ctypes.Structure):
-        _fields_ = [(n, ctypes.c_int32) for n in ("search_area_width", "search_area_height", "x_origin_offset", "y_origin_offset",
-                                                  "pad_width", "pad_height", "ref_width", "ref_height", "round_down", "mv_shift")]
-
     def hme_level_params(self, level, hme_w, hme_h, region_w, region_h, total_w, total_h, mult_x, mult_y, ref_origin_x, ref_origin_y,
                          ref_width, ref_height):
         p = self.HmeParams()
@@ -1364,18 +720,6 @@ class SvtHipDsp:
                     "svt_hip_hme_level_regions_batch")
         return best, mv
 
-    class IntraPos(ctypes.Structure):
-        """svt_hip_intra_pos: where one prediction block sits (the arguments of av1_predict_intra_block, EbIntraPrediction.c:4078)"""
-        _fields_ = [(n, ctypes.c_int32) for n in ("is_16bit", "sb_size_mi", "mi_rows", "mi_cols", "tile_mi_row_start", "tile_mi_row_end",
-                                                  "tile_mi_col_start", "tile_mi_col_end", "partition", "bsize", "tx_size", "plane",
-                                                  "bl_org_x_pict", "bl_org_y_pict", "col_off", "row_off", "wpx", "hpx")]
-
-    class IntraBlk(ctypes.Structure):
-        """svt_hip_intra_blk: per-block descriptor of svt_hip_build_intra_predictors_batch"""
-        _fields_ = [("mode", ctypes.c_uint8), ("angle_delta", ctypes.c_int8), ("filt_type", ctypes.c_uint8),
-                    ("disable_edge_filter", ctypes.c_uint8), ("n_top_px", ctypes.c_uint8), ("n_topright_px", ctypes.c_uint8),
-                    ("n_left_px", ctypes.c_uint8), ("n_bottomleft_px", ctypes.c_uint8)]
-
     def intra_neighbor_px(self, pos):
         """HOST: (n_top_px, n_topright_px, n_left_px, n_bottomleft_px) of one prediction block (svt_hip_intra_neighbor_px)"""
         blk = self.IntraBlk()
@@ -1396,8 +740,6 @@ class SvtHipDsp:
         else:
             pitch = 0 if dst_offsets is not None else h * dst_stride
         if order is not None:
-            self.lib.svt_hip_build_intra_predictors_ordered_batch.argtypes = [c_void_p, c_int32, c_size_t] + [c_void_p] * 3 + [c_int32, c_void_p, c_void_p,
-                                                                              c_int, c_int, c_int, c_size_t, c_void_p]
             self._check(self.lib.svt_hip_build_intra_predictors_ordered_batch(self._p(dst), dst_stride, pitch, self._p(dst_offsets) if dst_offsets is not None else None,
                                                                               self._p(top_neigh), self._p(left_neigh), top_neigh.shape[1], self._p(blocks),
                                                                               self._p(order), tx_size, int(is16), bd, n, self._stream()),
@@ -1415,7 +757,6 @@ class SvtHipDsp:
         t = self.torch
         n = blocks.shape[0]
         order = t.empty(n, dtype=t.int32, device=blocks.device)
-        self.lib.svt_hip_intra_order_blocks_batch.argtypes = [c_void_p, c_int, c_size_t, c_void_p, c_void_p, c_void_p]
         work = getattr(self, "_order_work", None)             # unused by the library since round 3 (older builds: 32 counters)
         if work is None or work.device != blocks.device:
             work = self._order_work = t.empty(32, dtype=t.int32, device=blocks.device)
@@ -1452,14 +793,6 @@ class SvtHipDsp:
         return best_sad, best_mv
 
     # -- MotionEstimateLcu's glue: set-up, per-SB areas, bi-prediction + result rows ------------------------
-    class MeSetupParams(ctypes.Structure):
-        _fields_ = [(n, ctypes.c_int32) for n in ("picture_width", "picture_height", "ref_width", "ref_height", "search_area_width",
-                                                  "search_area_height", "regions_w", "regions_h", "second_best", "zz_check")]
-
-    class MeResult(ctypes.Structure):
-        _fields_ = [("x_mv_l0", ctypes.c_int16), ("y_mv_l0", ctypes.c_int16), ("x_mv_l1", ctypes.c_int16), ("y_mv_l1", ctypes.c_int16),
-                    ("distortion", ctypes.c_uint32 * 3), ("direction", ctypes.c_uint8 * 3), ("total_me_candidate_index", ctypes.c_uint8)]
-
     def me_setup(self, src_pic00, src_stride, ref_pic00, ref_stride, sb_origin, sb_size, hme_sad, hme_mv, params, out=None):
         """svt_hip_me_setup_batch: search centre (best HME region, CheckZeroZeroCenter) and clipped search area per task.
         src_pic00 / ref_pic00: uint8 views whose data_ptr() is sample (0, 0) of the padded planes; sb_origin / sb_size int16 [n, 2];
@@ -1529,9 +862,6 @@ class SvtHipDsp:
         return out
 
     # -- MotionEstimateLcu for a whole picture: one call, three launches ---------------------------------------------------
-    MeFrameParams = MeFrameParams
-    MePyramid = MePyramid
-
     def me_pyramid(self, planes, origins):
         """planes: the padded full / quarter / sixteenth luma buffers, 2-D uint8 tensors [rows, stride] (one picture) or 3-D
         [pictures, rows, stride] (a stack); a level may be None when its HME level is off.  origins: (x, y) of sample (0, 0) per level"""
@@ -1569,8 +899,6 @@ class SvtHipDsp:
         return out
 
     # -- sub-pel motion estimation: the refinement stage alone, and MotionEstimateLcu with use_subpel_flag = 1 -------------
-    MeSubpelParams = MeSubpelParams
-
     def me_subpel_frame(self, src, ref0, ref1, params, best_sad, best_mv, subpel=None, n_pictures=1, best_ssd=None, half_dir=None):
         """svt_hip_me_subpel_frame: refines the rows best_sad / best_mv (int32 [s, nl, 209], as motion_estimate_frame writes them) in
         place to quarter-pel.  subpel: MeSubpelParams (None: everything on).  best_ssd (int32 [s, nl, 209]) / half_dir (uint8 [s, nl, 209]):
@@ -1611,10 +939,6 @@ class SvtHipDsp:
         return out
 
     # -- GatheringPictureStatistics for a whole picture: one call, two launches --------------------------------------------
-    PicStatsPlanes = PicStatsPlanes
-    PicStatsParams = PicStatsParams
-    PicStatsOut = PicStatsOut
-    PicStatsResult = PicStatsResult
     BLOCK_MEAN_PREC_FULL, BLOCK_MEAN_PREC_SUB = 0, 1
 
     def pic_stats_planes(self, planes, origins):
@@ -1690,58 +1014,26 @@ class SvtHipDsp:
         return outs
 
     # -- mode-decision full loop: residual -> transform -> quantiser -> distortion per (block, transform type) ----------------
-    class FullLoopGroup(ctypes.Structure):
-        _fields_ = [("d_src", c_void_p), ("src_stride", c_uint32), ("d_src_xy", c_void_p),
-                    ("d_pred", c_void_p), ("pred_stride", c_uint32), ("d_pred_xy", c_void_p),
-                    ("nblocks", c_uint32), ("tx_size", c_int32), ("ntypes", c_int32), ("tx_types", ctypes.c_uint8 * 16),
-                    ("d_iscan", c_void_p), ("d_dist", c_void_p), ("d_eob", c_void_p), ("d_qcoeff", c_void_p), ("d_dqcoeff", c_void_p)]
-
     def make_full_loop_groups(self, groups):
         """groups: list of dicts with tensors src, pred (planes or dense [n, H, W] uint8), optional src_xy / pred_xy (int32
         x | y << 16; absent: dense), iscan (int16 [ntypes, NC] in tx_types order), dist (int64 [n, ntypes, 2]), eob (int16 [n, ntypes]),
         optional qcoeff / dqcoeff (int32 [n, ntypes, NC]), plus src_stride / pred_stride, nblocks, tx_size, tx_types.
         -> ctypes array (keep the tensors alive!)"""
-        arr = (self.FullLoopGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-            types = list(g["tx_types"])
-            tt = (ctypes.c_uint8 * 16)(*(types + [0] * (16 - len(types)))[:16])
-            arr[i] = self.FullLoopGroup(P("src"), g.get("src_stride", 0), P("src_xy"), P("pred"), g.get("pred_stride", 0), P("pred_xy"),
-                                        g["nblocks"], g["tx_size"], g.get("ntypes", len(types)), tt, P("iscan"), P("dist"), P("eob"),
-                                        P("qcoeff"), P("dqcoeff"))
-        return arr
+        return records.build(FullLoopGroup, groups)
 
     def full_loop_frame(self, groups, qrow, flavour=1):
         """groups: a ctypes array from make_full_loop_groups (or the list of dicts itself); one quantiser row set (qrow)"""
-        if isinstance(groups, list):
-            keep = groups
-            groups = self.make_full_loop_groups(keep)
-            n = len(keep)
-        else:
-            n = len(groups)
+        groups, n = self._as_groups(self.make_full_loop_groups, groups)
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         return self.lib.svt_hip_full_loop_frame(groups, n, flavour, tabs[0].ctypes.data, tabs[1].ctypes.data, tabs[2].ctypes.data,
                                                 tabs[3].ctypes.data, tabs[4].ctypes.data, self._stream())
 
     # -- coefficient rate of quantised blocks: av1_cost_coeffs_txb / av1_cost_skip_txb per (block, transform type) ------------------
-    class CoeffRateGroup(ctypes.Structure):
-        _fields_ = [("tx_size", c_int32), ("ntypes", c_int32), ("tx_types", ctypes.c_uint8 * 16), ("nblocks", c_uint32),
-                    ("d_qcoeff", c_void_p), ("d_eob", c_void_p), ("d_iscan", c_void_p), ("d_txb_skip_ctx", c_void_p),
-                    ("d_dc_sign_ctx", c_void_p), ("d_type_bits", c_void_p), ("d_coeff_cost", c_void_p), ("d_eob_cost", c_void_p),
-                    ("d_bits", c_void_p)]
-
     def make_coeff_rate_groups(self, groups):
         """groups: list of dicts with tensors qcoeff (int32 [n, ntypes, NC]), eob (int16 [n, ntypes]) and iscan (int16 [ntypes, NC]) as in
         the full-loop groups, txb_skip_ctx / dc_sign_ctx (uint8 [n]), optional type_bits (int32 [n, ntypes]), coeff_cost (int32 [529]),
         eob_cost (int32 [22]), bits (int64 [n, ntypes]), plus nblocks, tx_size, tx_types.  -> ctypes array (keep the tensors alive!)"""
-        arr = (self.CoeffRateGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-            types = list(g["tx_types"])
-            tt = (ctypes.c_uint8 * 16)(*(types + [0] * (16 - len(types)))[:16])
-            arr[i] = self.CoeffRateGroup(g["tx_size"], g.get("ntypes", len(types)), tt, g["nblocks"], P("qcoeff"), P("eob"), P("iscan"),
-                                         P("txb_skip_ctx"), P("dc_sign_ctx"), P("type_bits"), P("coeff_cost"), P("eob_cost"), P("bits"))
-        return arr
+        return records.build(CoeffRateGroup, groups)
 
     def coeff_rate_frame(self, groups):
         """svt_hip_coeff_rate_frame.  groups: a ctypes array from make_coeff_rate_groups, or the list of dicts itself; a dict without
@@ -1752,11 +1044,7 @@ class SvtHipDsp:
             for g in groups:
                 if g.get("bits") is None and g.get("qcoeff") is not None:
                     g["bits"] = t.empty((g["nblocks"], g.get("ntypes", len(g["tx_types"]))), dtype=t.int64, device=g["qcoeff"].device)
-            keep = groups
-            groups = self.make_coeff_rate_groups(keep)
-            n = len(keep)
-        else:
-            n = len(groups)
+        groups, n = self._as_groups(self.make_coeff_rate_groups, groups)
         return self.lib.svt_hip_coeff_rate_frame(groups, n, self._stream())
 
     def coeff_rate(self, qcoeff, eob, tx_size, tx_types, txb_skip_ctx, dc_sign_ctx, coeff_cost, eob_cost, type_bits=None, iscan=None, bits=None):
@@ -1776,37 +1064,11 @@ class SvtHipDsp:
         return bits
 
     # -- transform-type decision: RD cost, best type and the winner's coefficients per block ----------------------------------------
-    class TxDecision(ctypes.Structure):
-        _fields_ = [("cost", ctypes.c_uint64), ("dist", ctypes.c_uint64 * 2), ("bits", ctypes.c_uint64), ("eob", ctypes.c_uint16),
-                    ("tx_type", ctypes.c_uint8), ("type_index", ctypes.c_uint8), ("has_coeff", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3)]
-
-    class TxDecideGroup(ctypes.Structure):
-        _fields_ = [("tx_size", c_int32), ("ntypes", c_int32), ("tx_types", ctypes.c_uint8 * 16), ("nblocks", c_uint32), ("lambda_", c_uint32),
-                    ("d_dist", c_void_p), ("d_eob", c_void_p), ("d_bits", c_void_p), ("d_qcoeff", c_void_p), ("d_dqcoeff", c_void_p),
-                    ("d_decision", c_void_p), ("d_best_qcoeff", c_void_p), ("d_best_dqcoeff", c_void_p)]
-
-    class TxSearchGroup(ctypes.Structure):
-        pass                                                              # (a nested class body does not see FullLoopGroup)
-
-    TxSearchGroup._fields_ = [("fl", FullLoopGroup), ("d_txb_skip_ctx", c_void_p), ("d_dc_sign_ctx", c_void_p), ("d_type_bits", c_void_p),
-                              ("d_coeff_cost", c_void_p), ("d_eob_cost", c_void_p), ("lambda_", c_uint32), ("d_decision", c_void_p),
-                              ("d_best_qcoeff", c_void_p), ("d_best_dqcoeff", c_void_p)]
-
-    TX_DECISION_DTYPE = [("cost", "<u8"), ("dist", "<u8", (2,)), ("bits", "<u8"), ("eob", "<u2"), ("tx_type", "u1"), ("type_index", "u1"),
-                         ("has_coeff", "u1"), ("pad", "u1", (3,))]        # numpy view of a downloaded uint8 [n, 40] decision tensor
-
     def make_tx_decide_groups(self, groups):
         """groups: list of dicts with tensors dist (int64 [n, T, 2]), eob (int16 [n, T]), bits (int64 [n, T]), optional qcoeff / dqcoeff
         (int32 [n, T, NC]), decision (uint8 [n, 40]: TxDecision records), optional best_qcoeff / best_dqcoeff (int32 [n, NC]), plus
         nblocks, tx_size, tx_types, lambda.  -> ctypes array (keep the tensors alive!)"""
-        arr = (self.TxDecideGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-            types = list(g["tx_types"])
-            tt = (ctypes.c_uint8 * 16)(*(types + [0] * (16 - len(types)))[:16])
-            arr[i] = self.TxDecideGroup(g["tx_size"], g.get("ntypes", len(types)), tt, g["nblocks"], g.get("lambda", 0), P("dist"), P("eob"),
-                                        P("bits"), P("qcoeff"), P("dqcoeff"), P("decision"), P("best_qcoeff"), P("best_dqcoeff"))
-        return arr
+        return records.build(TxDecideGroup, groups)
 
     def tx_decide_frame(self, groups):
         """svt_hip_tx_decide_frame.  groups: a ctypes array from make_tx_decide_groups, or the list of dicts itself; a dict without
@@ -1817,11 +1079,7 @@ class SvtHipDsp:
             for g in groups:
                 if g.get("decision") is None and g.get("dist") is not None:
                     g["decision"] = t.empty((g["nblocks"], ctypes.sizeof(self.TxDecision)), dtype=t.uint8, device=g["dist"].device)
-            keep = groups
-            groups = self.make_tx_decide_groups(keep)
-            n = len(keep)
-        else:
-            n = len(groups)
+        groups, n = self._as_groups(self.make_tx_decide_groups, groups)
         return self.lib.svt_hip_tx_decide_frame(groups, n, self._stream())
 
     def tx_decide(self, dist, eob, bits, tx_size, tx_types, lam, qcoeff=None, dqcoeff=None, decision=None, best_qcoeff=None, best_dqcoeff=None):
@@ -1845,64 +1103,24 @@ class SvtHipDsp:
         """groups: list of dicts: a full-loop group's keys (make_full_loop_groups; dist / eob / qcoeff / dqcoeff may be absent: scratch),
         txb_skip_ctx / dc_sign_ctx (uint8 [n]), optional type_bits (int32 [n, T]), coeff_cost (int32 [529]), eob_cost (int32 [22]), lambda,
         decision (uint8 [n, 40]), optional best_qcoeff / best_dqcoeff (int32 [n, NC]).  -> ctypes array (keep the tensors alive!)"""
-        fl = self.make_full_loop_groups(groups)
-        arr = (self.TxSearchGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-            arr[i] = self.TxSearchGroup(fl[i], P("txb_skip_ctx"), P("dc_sign_ctx"), P("type_bits"), P("coeff_cost"), P("eob_cost"),
-                                        g.get("lambda", 0), P("decision"), P("best_qcoeff"), P("best_dqcoeff"))
-        return arr
+        return records.build(TxSearchGroup, groups)
 
     def tx_search_scratch_bytes(self, groups):
         """svt_hip_tx_search_scratch_bytes of a ctypes array from make_tx_search_groups or of the list of dicts (0: bad parameters)"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_tx_search_groups(groups)
+        groups, n = self._as_groups(self.make_tx_search_groups, groups)
         return self.lib.svt_hip_tx_search_scratch_bytes(groups, n)
 
     def tx_search_frame(self, groups, qrow, scratch, flavour=1):
         """svt_hip_tx_search_frame: full loop -> coefficient rate -> decide in one call.  groups: a ctypes array from
         make_tx_search_groups or the list of dicts; scratch: a uint8 device tensor of at least tx_search_scratch_bytes(groups) bytes (None
         where that is 0).  -> the library's return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            keep = groups
-            groups = self.make_tx_search_groups(keep)
+        groups, n = self._as_groups(self.make_tx_search_groups, groups)
         tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
         return self.lib.svt_hip_tx_search_frame(groups, n, flavour, tabs[0].ctypes.data, tabs[1].ctypes.data, tabs[2].ctypes.data,
-                                                tabs[3].ctypes.data, tabs[4].ctypes.data, self._p(scratch) if scratch is not None else None,
-                                                scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+                                                tabs[3].ctypes.data, tabs[4].ctypes.data, *self._scratch_args(scratch), self._stream())
 
     # -- CfL alpha search of mode decision: the (block, plane, alpha) table, cfl_rd_pick_alpha's walk, and both in one call ---------
     CFL_NALPHA = 33
-
-    class QRows(ctypes.Structure):
-        _fields_ = [(k, c_void_p) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
-
-    class CflSearchGroup(ctypes.Structure):
-        _fields_ = [("d_luma_recon", c_void_p), ("luma_stride", c_uint32), ("d_src", c_void_p * 2), ("src_stride", c_uint32 * 2),
-                    ("d_pred", c_void_p * 2), ("pred_stride", c_uint32 * 2), ("d_xy", c_void_p), ("nblocks", c_uint32),
-                    ("tx_size", c_int32), ("tx_type", c_int32), ("d_iscan", c_void_p), ("d_txb_skip_ctx", c_void_p * 2),
-                    ("d_dc_sign_ctx", c_void_p * 2), ("d_coeff_cost", c_void_p), ("d_eob_cost", c_void_p), ("d_dist", c_void_p),
-                    ("d_bits", c_void_p), ("d_eob", c_void_p)]
-
-    class CflDecision(ctypes.Structure):
-        _fields_ = [("best_rd", ctypes.c_int64), ("dc_rd", ctypes.c_int64), ("alpha_q3", c_int32 * 2), ("uv_mode", ctypes.c_uint8),
-                    ("cfl_alpha_idx", ctypes.c_uint8), ("cfl_alpha_signs", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 5)]
-
-    class CflDecideGroup(ctypes.Structure):
-        _fields_ = [("nblocks", c_uint32), ("lambda_", c_uint32), ("d_dist", c_void_p), ("d_bits", c_void_p), ("d_alpha_rate", c_void_p),
-                    ("d_cfl_mode_bits", c_void_p), ("d_dc_mode_bits", c_void_p), ("d_decision", c_void_p), ("d_alpha_q3_cb", c_void_p),
-                    ("d_alpha_q3_cr", c_void_p)]
-
-    class CflPickGroup(ctypes.Structure):
-        pass                                                              # (a nested class body does not see CflSearchGroup)
-
-    CflPickGroup._fields_ = [("search", CflSearchGroup), ("lambda_", c_uint32), ("d_alpha_rate", c_void_p), ("d_cfl_mode_bits", c_void_p),
-                             ("d_dc_mode_bits", c_void_p), ("d_decision", c_void_p), ("d_alpha_q3_cb", c_void_p), ("d_alpha_q3_cr", c_void_p)]
-
-    CFL_DECISION_DTYPE = [("best_rd", "<i8"), ("dc_rd", "<i8"), ("alpha_q3", "<i4", (2,)), ("uv_mode", "u1"), ("cfl_alpha_idx", "u1"),
-                          ("cfl_alpha_signs", "u1"), ("pad", "u1", (5,))]    # numpy view of a downloaded uint8 [n, 32] decision tensor
 
     def _qrows(self, qrow):
         """-> (QRows, the int16 arrays it points into: keep them alive over the call)"""
@@ -1914,126 +1132,71 @@ class SvtHipDsp:
         origins x | y << 16), iscan (int16 [NC]), txb_skip_ctx / dc_sign_ctx ((Cb, Cr) uint8 [n]), coeff_cost (int32 [529]), eob_cost
         (int32 [22]), dist (int64 [n, 2, 33, 2]), bits (int64 [n, 2, 33]), eob (int16 [n, 2, 33]), plus luma_stride, src_stride /
         pred_stride (pairs), nblocks, tx_size, tx_type (default DCT_DCT).  -> ctypes array (keep the tensors alive!)"""
-        arr = (self.CflSearchGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-            P2 = lambda k: (c_void_p * 2)(*[x.data_ptr() if x is not None else None for x in (g.get(k) or (None, None))])
-            S2 = lambda k: (c_uint32 * 2)(*(g.get(k) or (0, 0)))
-            arr[i] = self.CflSearchGroup(P("luma"), g.get("luma_stride", 0), P2("src"), S2("src_stride"), P2("pred"), S2("pred_stride"),
-                                         P("xy"), g["nblocks"], g["tx_size"], g.get("tx_type", DCT_DCT), P("iscan"), P2("txb_skip_ctx"),
-                                         P2("dc_sign_ctx"), P("coeff_cost"), P("eob_cost"), P("dist"), P("bits"), P("eob"))
-        return arr
+        return records.build(CflSearchGroup, groups)
 
     def cfl_search_scratch_bytes(self, groups):
         """svt_hip_cfl_search_scratch_bytes of a ctypes array from make_cfl_search_groups or of the list of dicts (0: bad parameters)"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_cfl_search_groups(groups)
+        groups, n = self._as_groups(self.make_cfl_search_groups, groups)
         return self.lib.svt_hip_cfl_search_scratch_bytes(groups, n)
 
     def cfl_search_frame(self, groups, qrow_cb, qrow_cr, scratch, flavour=1):
         """svt_hip_cfl_search_frame.  groups: a ctypes array from make_cfl_search_groups or the list of dicts; qrow_cb / qrow_cr: the
         planes' quantiser rows; scratch: a uint8 device tensor of at least cfl_search_scratch_bytes(groups) bytes (None where that is
         0).  -> the library's return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            keep = groups
-            groups = self.make_cfl_search_groups(keep)
+        groups, n = self._as_groups(self.make_cfl_search_groups, groups)
         qb, kb = self._qrows(qrow_cb)
         qr, kr = self._qrows(qrow_cr)
         return self.lib.svt_hip_cfl_search_frame(groups, n, flavour, ctypes.addressof(qb), ctypes.addressof(qr),
-                                                 self._p(scratch) if scratch is not None else None,
-                                                 scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+                                                 *self._scratch_args(scratch), self._stream())
 
     def make_cfl_decide_groups(self, groups):
         """groups: list of dicts with tensors dist (int64 [n, 2, 33, 2]), bits (int64 [n, 2, 33]), alpha_rate (int32 [8, 2, 16]),
         cfl_mode_bits / dc_mode_bits (int32 [n]), decision (uint8 [n, 32]: CflDecision records), optional alpha_q3_cb / alpha_q3_cr
         (int32 [n]), plus nblocks, lambda.  -> ctypes array (keep the tensors alive!)"""
-        arr = (self.CflDecideGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-            arr[i] = self.CflDecideGroup(g["nblocks"], g.get("lambda", 0), P("dist"), P("bits"), P("alpha_rate"), P("cfl_mode_bits"),
-                                         P("dc_mode_bits"), P("decision"), P("alpha_q3_cb"), P("alpha_q3_cr"))
-        return arr
+        return records.build(CflDecideGroup, groups)
 
     def cfl_decide_frame(self, groups):
         """svt_hip_cfl_decide_frame.  groups: a ctypes array from make_cfl_decide_groups, or the list of dicts itself; a dict without
         "decision" gets a fresh uint8 [nblocks, 32] tensor there (preallocate it to keep the call allocation-free).  -> return code"""
-        n = len(groups)
         if isinstance(groups, list):
             t = self.torch
             for g in groups:
                 if g.get("decision") is None and g.get("dist") is not None:
                     g["decision"] = t.empty((g["nblocks"], ctypes.sizeof(self.CflDecision)), dtype=t.uint8, device=g["dist"].device)
-            keep = groups
-            groups = self.make_cfl_decide_groups(keep)
+        groups, n = self._as_groups(self.make_cfl_decide_groups, groups)
         return self.lib.svt_hip_cfl_decide_frame(groups, n, self._stream())
 
     def make_cfl_pick_groups(self, groups):
         """groups: list of dicts: a search group's keys (dist / bits / eob may be absent: scratch) and a decide group's (alpha_rate,
         cfl_mode_bits, dc_mode_bits, decision, optional alpha_q3_cb / alpha_q3_cr, lambda).  -> ctypes array (keep the tensors alive!)"""
-        sg = self.make_cfl_search_groups(groups)
-        arr = (self.CflPickGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-            arr[i] = self.CflPickGroup(sg[i], g.get("lambda", 0), P("alpha_rate"), P("cfl_mode_bits"), P("dc_mode_bits"), P("decision"),
-                                       P("alpha_q3_cb"), P("alpha_q3_cr"))
-        return arr
+        return records.build(CflPickGroup, groups)
 
     def cfl_pick_scratch_bytes(self, groups):
         """svt_hip_cfl_pick_scratch_bytes of a ctypes array from make_cfl_pick_groups or of the list of dicts (0: bad parameters)"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_cfl_pick_groups(groups)
+        groups, n = self._as_groups(self.make_cfl_pick_groups, groups)
         return self.lib.svt_hip_cfl_pick_scratch_bytes(groups, n)
 
     def cfl_pick_frame(self, groups, qrow_cb, qrow_cr, scratch, flavour=1):
         """svt_hip_cfl_pick_frame: search -> decide in one call; arguments as cfl_search_frame.  -> the library's return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            keep = groups
-            groups = self.make_cfl_pick_groups(keep)
+        groups, n = self._as_groups(self.make_cfl_pick_groups, groups)
         qb, kb = self._qrows(qrow_cb)
         qr, kr = self._qrows(qrow_cr)
         return self.lib.svt_hip_cfl_pick_frame(groups, n, flavour, ctypes.addressof(qb), ctypes.addressof(qr),
-                                               self._p(scratch) if scratch is not None else None,
-                                               scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+                                               *self._scratch_args(scratch), self._stream())
 
     # -- mode-decision fast loop, intra candidates: prediction -> distortion per (block, candidate) ------------------------------
     FAST_SAD, FAST_SSD = 0, 1
-
-    class FastLoopGroup(ctypes.Structure):
-        _fields_ = [("d_src", c_void_p), ("src_stride", c_uint32), ("d_src_xy", c_void_p),
-                    ("d_top_neigh", c_void_p), ("d_left_neigh", c_void_p), ("neigh_pitch", c_int32),
-                    ("d_blocks", c_void_p), ("nblocks", c_uint32), ("tx_size", c_int32),
-                    ("ncand", c_int32), ("modes", ctypes.c_uint8 * 64), ("angle_deltas", ctypes.c_int8 * 64),
-                    ("d_dist", c_void_p), ("d_pred", c_void_p)]
 
     def make_fast_loop_groups(self, groups):
         """groups: list of dicts with tensors src (plane or dense [n, H, W] uint8), optional src_xy (int32 x | y << 16; absent:
         dense), top / left (uint8 [n, pitch], element 0 = the corner), blocks (uint8 [n, 8], IntraBlk layout), dist (int64
         [n, ncand]), optional pred (uint8 [n, ncand, H, W]), plus src_stride, nblocks, tx_size, modes, deltas (host lists; ncand
         defaults to len(modes)).  -> ctypes array (keep the tensors alive!)"""
-        arr = (self.FastLoopGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-            modes, deltas = list(g["modes"])[:64], list(g["deltas"])[:64]
-            m = (ctypes.c_uint8 * 64)(*(modes + [0] * (64 - len(modes))))
-            d = (ctypes.c_int8 * 64)(*(deltas + [0] * (64 - len(deltas))))
-            top = g.get("top")
-            arr[i] = self.FastLoopGroup(P("src"), g.get("src_stride", 0), P("src_xy"), P("top"), P("left"),
-                                        g.get("neigh_pitch", top.shape[1] if top is not None else 0), P("blocks"), g["nblocks"],
-                                        g["tx_size"], g.get("ncand", len(modes)), m, d, P("dist"), P("pred"))
-        return arr
+        return records.build(FastLoopGroup, groups)
 
     def intra_fast_loop_frame(self, groups, metric, flavour=1):
         """groups: a ctypes array from make_fast_loop_groups (or the list of dicts itself) -> the library's return code"""
-        if isinstance(groups, list):
-            keep = groups
-            groups = self.make_fast_loop_groups(keep)
-            n = len(keep)
-        else:
-            n = len(groups)
+        groups, n = self._as_groups(self.make_fast_loop_groups, groups)
         return self.lib.svt_hip_intra_fast_loop_frame(groups, n, metric, flavour, self._stream())
 
     def intra_fast_loop(self, src, top, left, blocks, tx_size, modes, deltas, metric, flavour=1, want_pred=False, src_xy=None, src_stride=0):
@@ -2051,51 +1214,8 @@ class SvtHipDsp:
 
     # -- the end of the fast loop: fast cost, the N best, their order, the survivors' predictions gathered --------------------------
     MAX_NFL = 40
-    FAST_RATE_TABLES = (("yModeFacBits", (5, 5, 14)), ("mbModeFacBits", (4, 14)), ("intraUVmodeFacBits", (2, 13, 15)),
-                        ("angleDeltaFacBits", (8, 8)), ("skipModeFacBits", (3, 3)), ("intraInterFacBits", (4, 2)))       # svt_hip_fast_rates
-    FAST_RATE_WORDS = 877
-    FAST_PICK_BLK_DTYPE = [("top_mode", "u1"), ("left_mode", "u1"), ("skip_mode_ctx", "u1"), ("is_inter_ctx", "u1"), ("has_chroma", "u1"),
-                           ("pad", "u1", (3,))]                              # svt_hip_fast_pick_blk
-
-    class FastPickGroup(ctypes.Structure):
-        _fields_ = [("tx_size", c_int32), ("bsize", c_int32), ("bsize_uv", c_int32), ("nblocks", c_uint32),
-                    ("ncand", c_int32), ("modes", ctypes.c_uint8 * 64), ("angle_deltas", ctypes.c_int8 * 64),
-                    ("uv_modes", ctypes.c_uint8 * 64), ("uv_angle_deltas", ctypes.c_int8 * 64),
-                    ("use_angle_delta", c_int32), ("nfl", c_int32), ("slice_is_intra", c_int32), ("lambda_", c_uint32),
-                    ("ac_dequant_q3", c_int16), ("intrabc_bits", c_uint32),
-                    ("d_dist", c_void_p), ("d_dist_cb", c_void_p), ("d_dist_cr", c_void_p), ("d_blk", c_void_p), ("d_rates", c_void_p),
-                    ("d_pred", c_void_p), ("d_src_xy", c_void_p), ("d_cand", c_void_p), ("d_sorted", c_void_p), ("d_cost", c_void_p),
-                    ("d_rate", c_void_p), ("d_ref_fast_cost", c_void_p), ("d_all_cost", c_void_p), ("d_pred_out", c_void_p),
-                    ("d_src_xy_out", c_void_p)]
-
-    class IntraFastSearchGroup(ctypes.Structure):
-        pass                                                              # (a nested class body does not see its siblings)
-
-    IntraFastSearchGroup._fields_ = [("luma", FastLoopGroup), ("use_chroma", c_int32), ("cb", FastLoopGroup), ("cr", FastLoopGroup),
-                                     ("pick", FastPickGroup)]
+    pack_fast_rates = staticmethod(records.pack_fast_rates)
     FAST_PICK_OUTPUTS = ("cand", "sorted", "cost", "rate", "ref_fast_cost", "all_cost", "pred_out", "src_xy_out")
-
-    @staticmethod
-    def pack_fast_rates(tables):
-        """dict of the six int32 tables (FAST_RATE_TABLES shapes) -> int32 [877] in svt_hip_fast_rates order"""
-        import numpy as np
-        parts = []
-        for name, shape in SvtHipDsp.FAST_RATE_TABLES:
-            a = np.asarray(tables[name], np.int32)
-            assert a.shape == shape, (name, a.shape)
-            parts.append(a.reshape(-1))
-        return np.concatenate(parts)
-
-    def _fast_pick_struct(self, g):
-        P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-        pad = lambda k, ct: (ct * 64)(*(list(g.get(k, []))[:64] + [0] * (64 - len(list(g.get(k, []))[:64]))))
-        modes = list(g.get("modes", []))
-        return self.FastPickGroup(g.get("tx_size", 0), g.get("bsize", 0), g.get("bsize_uv", 0), g.get("nblocks", 0), g.get("ncand", len(modes)),
-                                  pad("modes", ctypes.c_uint8), pad("deltas", ctypes.c_int8), pad("uv_modes", ctypes.c_uint8),
-                                  pad("uv_deltas", ctypes.c_int8), int(g.get("use_angle_delta", 0)), g.get("nfl", 0),
-                                  int(g.get("slice_is_intra", 0)), g.get("lambda", 0), g.get("ac_dequant_q3", 0), g.get("intrabc_bits", 0),
-                                  P("dist"), P("dist_cb"), P("dist_cr"), P("blk"), P("rates"), P("pred"), P("src_xy"), P("cand"), P("sorted"),
-                                  P("cost"), P("rate"), P("ref_fast_cost"), P("all_cost"), P("pred_out"), P("src_xy_out"))
 
     def make_fast_pick_groups(self, groups):
         """groups: list of dicts with tensors dist (int64 [n, ncand], the fast loop's), optional dist_cb / dist_cr, blk (uint8 [n, 8]:
@@ -2104,16 +1224,11 @@ class SvtHipDsp:
         (int64 [n, ncand]), pred_out (uint8 [n, N, H, W]), src_xy_out (int32 [n, N]) with N = min(nfl, ncand), plus tx_size, bsize, bsize_uv,
         nblocks, modes, deltas, uv_modes, uv_deltas (host lists), use_angle_delta, nfl, slice_is_intra, lambda, ac_dequant_q3,
         intrabc_bits.  -> ctypes array (keep the tensors alive!)"""
-        arr = (self.FastPickGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            arr[i] = self._fast_pick_struct(g)
-        return arr
+        return records.build(FastPickGroup, groups)
 
     def fast_pick_frame(self, groups, metric):
         """svt_hip_fast_pick_frame.  groups: a ctypes array from make_fast_pick_groups or the list of dicts -> the library's return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_fast_pick_groups(groups)
+        groups, n = self._as_groups(self.make_fast_pick_groups, groups)
         return self.lib.svt_hip_fast_pick_frame(groups, n, metric, self._stream())
 
     def make_inter_pred_groups(self, groups):
@@ -2121,22 +1236,11 @@ class SvtHipDsp:
         the PICTURE in the list's padded plane (a view plane[oy:, ox:]), ref_stride (samples), ss, bwidth, bheight (luma), blk (uint8
         [n, 16]: inter_blk_dtype records), optional pred (dense [n, h, w], or a plane view with pred_stride), optional src (a view at the
         picture's sample (0, 0)) with src_stride and dist (int64 [n]).  -> ctypes array (keep the tensors alive!)"""
-        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
-        arr = (InterPredGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            a = arr[i]
-            a.d_ref[0], a.d_ref[1] = P(g, "ref0"), P(g, "ref1")
-            a.ref_stride, a.ss, a.bwidth, a.bheight = g.get("ref_stride", 0), g.get("ss", 0), g.get("bwidth", 0), g.get("bheight", 0)
-            a.nblocks = g["nblocks"] if "nblocks" in g else (g["blk"].shape[0] if g.get("blk") is not None else 0)
-            a.d_blk, a.d_pred, a.pred_stride = P(g, "blk"), P(g, "pred"), g.get("pred_stride", 0)
-            a.d_src, a.src_stride, a.d_dist = P(g, "src"), g.get("src_stride", 0), P(g, "dist")
-        return arr
+        return records.build(InterPredGroup, groups)
 
     def inter_pred_frame(self, groups, pic_width, pic_height, bd=8, metric=0):
         """svt_hip_inter_pred_frame.  groups: a ctypes array from make_inter_pred_groups or the list of dicts -> the library's return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_inter_pred_groups(groups)
+        groups, n = self._as_groups(self.make_inter_pred_groups, groups)
         return self.lib.svt_hip_inter_pred_frame(groups, n, pic_width, pic_height, bd, metric, self._stream())
 
     # -- warped motion: the local warp model of every (block, candidate), then its prediction with the distortion fused in -----------
@@ -2144,20 +1248,11 @@ class SvtHipDsp:
         """groups: list of dicts with bsize, ncand, samples (uint8 [n, 132]: warp_samples_dtype records), blk (uint8 [n, ncand, 16]:
         inter_blk_dtype records), model (uint8 [n, ncand, 36], written: warp_model_dtype records), optional nvalid (int32 [n]).
         -> ctypes array (keep the tensors alive!)"""
-        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
-        arr = (WarpFitGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            a = arr[i]
-            a.bsize, a.ncand = g.get("bsize", 0), g.get("ncand", 0)
-            a.nblocks = g["nblocks"] if "nblocks" in g else (g["samples"].shape[0] if g.get("samples") is not None else 0)
-            a.d_samples, a.d_blk, a.d_model, a.d_nvalid = P(g, "samples"), P(g, "blk"), P(g, "model"), P(g, "nvalid")
-        return arr
+        return records.build(WarpFitGroup, groups)
 
     def warp_fit_frame(self, groups):
         """svt_hip_warp_fit_frame.  groups: a ctypes array from make_warp_fit_groups or the list of dicts -> the library's return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_warp_fit_groups(groups)
+        groups, n = self._as_groups(self.make_warp_fit_groups, groups)
         return self.lib.svt_hip_warp_fit_frame(groups, n, self._stream())
 
     def make_warp_pred_groups(self, groups):
@@ -2166,58 +1261,24 @@ class SvtHipDsp:
         sel (uint8 [n, nsel]: the pick's d_cand) with sel_first, optional pred (dense [slots, h, w], or a plane view with pred_stride),
         optional src (a view at the picture's sample (0, 0)) with src_stride and dist (int64 [slots]).  -> ctypes array (keep the
         tensors alive!)"""
-        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
-        arr = (WarpPredGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            a = arr[i]
-            a.d_ref, a.ref_stride, a.ss, a.bwidth, a.bheight = P(g, "ref"), g.get("ref_stride", 0), g.get("ss", 0), g.get("bwidth", 0), g.get("bheight", 0)
-            a.nblocks = g["nblocks"] if "nblocks" in g else (g["blk"].shape[0] if g.get("blk") is not None else 0)
-            a.ncand, a.d_blk, a.d_model = g.get("ncand", 0), P(g, "blk"), P(g, "model")
-            a.d_sel = P(g, "sel")
-            a.n = g["n"] if "n" in g else (g["sel"].shape[1] if g.get("sel") is not None else 0)
-            a.sel_first = g.get("sel_first", 0)
-            a.d_pred, a.pred_stride = P(g, "pred"), g.get("pred_stride", 0)
-            a.d_src, a.src_stride, a.d_dist = P(g, "src"), g.get("src_stride", 0), P(g, "dist")
-        return arr
+        return records.build(WarpPredGroup, groups)
 
     def warp_pred_frame(self, groups, pic_width, pic_height, bd=8, metric=0):
         """svt_hip_warp_pred_frame.  groups: a ctypes array from make_warp_pred_groups or the list of dicts -> the library's return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_warp_pred_groups(groups)
+        groups, n = self._as_groups(self.make_warp_pred_groups, groups)
         return self.lib.svt_hip_warp_pred_frame(groups, n, pic_width, pic_height, bd, metric, self._stream())
 
     # -- interpolation filter search: the nine-pair SSE table, the reference's walk, both in one call -------------------------------
-    def _interp_sse_struct(self, a, g):
-        P = lambda t: self._p(t) if t is not None else None
-        for l, key in enumerate(("ref0", "ref1")):
-            planes = g.get(key) or ()
-            for p in range(3):
-                a.d_ref[l][p] = P(planes[p]) if p < len(planes) else None
-        src = g.get("src") or ()
-        for p in range(3):
-            a.d_src[p] = P(src[p]) if p < len(src) else None
-            a.ref_stride[p] = list(g.get("ref_stride", ()))[p] if p < len(g.get("ref_stride", ())) else 0
-            a.src_stride[p] = list(g.get("src_stride", ()))[p] if p < len(g.get("src_stride", ())) else 0
-        a.bwidth, a.bheight = g.get("bwidth", 0), g.get("bheight", 0)
-        a.nblocks = g["nblocks"] if "nblocks" in g else (g["blk"].shape[0] if g.get("blk") is not None else 0)
-        a.d_blk, a.d_sse = P(g.get("blk")), P(g.get("sse"))
-
     def make_interp_sse_groups(self, groups):
         """groups: list of dicts with ref0 / ref1: lists of the Y, Cb, Cr tensors of a list whose first element is sample (0, 0) of the
         PICTURE in the padded plane (ref1 optional; Y alone without use_uv), ref_stride (three numbers, samples), src / src_stride
         likewise, bwidth, bheight (luma), blk (uint8 [n, 16]: inter_blk_dtype records), sse (int32 [n, planes, 9]).  -> ctypes array
         (keep the tensors alive!)"""
-        arr = (InterpSseGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            self._interp_sse_struct(arr[i], g)
-        return arr
+        return records.build(InterpSseGroup, groups)
 
     def interp_sse_frame(self, groups, pic_width, pic_height, use_uv, bd=8):
         """svt_hip_interp_sse_frame.  groups: a ctypes array from make_interp_sse_groups or the list of dicts -> the return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_interp_sse_groups(groups)
+        groups, n = self._as_groups(self.make_interp_sse_groups, groups)
         return self.lib.svt_hip_interp_sse_frame(groups, n, pic_width, pic_height, bd, int(use_uv), self._stream())
 
     def make_interp_params(self, full_lambda, ac_dequant_q3, rates, use_uv, mode):
@@ -2227,65 +1288,36 @@ class SvtHipDsp:
     def make_interp_decide_groups(self, groups):
         """groups: list of dicts with bwidth, bheight, sse (int32 [n, planes, 9]), ctx (uint8 [n, 2]), searchable (uint8 [n]), decision
         (uint8 [n, 32]: interp_decision_dtype records), optional blk and blk_out (uint8 [n, 16]).  -> ctypes array"""
-        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
-        arr = (InterpDecideGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            n = g["nblocks"] if "nblocks" in g else (g["decision"].shape[0] if g.get("decision") is not None else 0)
-            arr[i] = InterpDecideGroup(g.get("bwidth", 0), g.get("bheight", 0), n, P(g, "sse"), P(g, "ctx"), P(g, "searchable"),
-                                       P(g, "decision"), P(g, "blk"), P(g, "blk_out"))
-        return arr
+        return records.build(InterpDecideGroup, groups)
 
     def interp_decide_frame(self, groups, params):
         """svt_hip_interp_decide_frame.  params: make_interp_params' (or None) -> the return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_interp_decide_groups(groups)
+        groups, n = self._as_groups(self.make_interp_decide_groups, groups)
         return self.lib.svt_hip_interp_decide_frame(groups, n, ctypes.byref(params) if params is not None else None, self._stream())
 
     def make_interp_search_groups(self, groups):
         """groups: make_interp_sse_groups' dicts (sse optional: the table then lives in the scratch) plus ctx, searchable, decision and the
         optional blk_out.  -> ctypes array"""
-        P = lambda g, k: self._p(g[k]) if g.get(k) is not None else None
-        arr = (InterpSearchGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            self._interp_sse_struct(arr[i].sse, g)
-            arr[i].d_ctx, arr[i].d_searchable, arr[i].d_decision, arr[i].d_blk_out = P(g, "ctx"), P(g, "searchable"), P(g, "decision"), P(g, "blk_out")
-        return arr
+        return records.build(InterpSearchGroup, groups)
 
     def interp_search_scratch_bytes(self, groups, use_uv):
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_interp_search_groups(groups)
+        groups, n = self._as_groups(self.make_interp_search_groups, groups)
         return self.lib.svt_hip_interp_search_scratch_bytes(groups, n, int(use_uv))
 
     def interp_search_frame(self, groups, pic_width, pic_height, params, scratch=None, bd=8):
         """svt_hip_interp_search_frame.  scratch: a uint8 device tensor of interp_search_scratch_bytes, allocated here when None and
         needed (the tensor is returned beside the code so that it outlives the enqueued work) -> (return code, scratch)"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_interp_search_groups(groups)
+        groups, n = self._as_groups(self.make_interp_search_groups, groups)
         if scratch is None and params is not None:
             need = self.lib.svt_hip_interp_search_scratch_bytes(groups, n, params.use_uv)
             if need:
                 scratch = self.torch.empty((need,), dtype=self.torch.uint8, device=self.device)
         rc = self.lib.svt_hip_interp_search_frame(groups, n, pic_width, pic_height, bd, ctypes.byref(params) if params is not None else None,
-                                                  self._p(scratch) if scratch is not None else None, scratch.numel() if scratch is not None else 0,
-                                                  self._stream())
+                                                  *self._scratch_args(scratch), self._stream())
         return rc, scratch
 
     # -- the fast loop for inter candidates: fast cost, the N best of the combined list, the survivors' records; the one-call search ---------
     INTER_FAST_PICK_OUTPUTS = ("cand", "sorted", "cost", "rate", "ref_fast_cost", "all_cost", "blk_out", "cand_out", "src_xy_out")
-
-    def _inter_fast_pick_struct(self, a, g):
-        P = lambda k: self._p(g[k]) if g.get(k) is not None else None
-        a.bsize, a.bsize_uv, a.ninter, a.nintra, a.nfl = g.get("bsize", 0), g.get("bsize_uv", 0), g.get("ninter", 0), g.get("nintra", 0), g.get("nfl", 0)
-        a.nblocks = g["nblocks"] if "nblocks" in g else (g["ctx"].shape[0] if g.get("ctx") is not None else 0)
-        a.lambda_, a.ac_dequant_q3 = g.get("lambda", 0), g.get("ac_dequant_q3", 0)
-        a.reference_mode_select, a.switchable_motion_mode = int(g.get("reference_mode_select", 0)), int(g.get("switchable_motion_mode", 0))
-        a.d_blk, a.d_cand_in, a.d_ctx, a.d_rates, a.d_mv_cost = P("blk"), P("cand_in"), P("ctx"), P("rates"), P("mv_cost")
-        a.d_dist, a.d_dist_cb, a.d_dist_cr, a.d_intra_cost, a.d_intra_rate = P("dist"), P("dist_cb"), P("dist_cr"), P("intra_cost"), P("intra_rate")
-        a.d_cand, a.d_sorted, a.d_cost, a.d_rate, a.d_ref_fast_cost = P("cand"), P("sorted"), P("cost"), P("rate"), P("ref_fast_cost")
-        a.d_all_cost, a.d_blk_out, a.d_cand_out, a.d_src_xy_out = P("all_cost"), P("blk_out"), P("cand_out"), P("src_xy_out")
 
     def make_inter_fast_pick_groups(self, groups):
         """groups: list of dicts with tensors blk (uint8 [n, ninter, 16]: inter_blk_dtype records), cand_in (uint8 [n, ninter, 16]:
@@ -2295,79 +1327,35 @@ class SvtHipDsp:
         blk_out (uint8 [n, N, 16]) and the optional all_cost (int64 [n, ninter]), cand_out (uint8 [n, N, 16]), src_xy_out (int32 [n, N]),
         N = min(nfl, ninter + nintra); plus bsize, bsize_uv, ninter, nintra, nfl, lambda, ac_dequant_q3, reference_mode_select,
         switchable_motion_mode.  -> ctypes array (keep the tensors alive!)"""
-        arr = (InterFastPickGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            self._inter_fast_pick_struct(arr[i], g)
-        return arr
+        return records.build(InterFastPickGroup, groups)
 
     def inter_fast_pick_frame(self, groups, metric):
         """svt_hip_inter_fast_pick_frame.  groups: a ctypes array from make_inter_fast_pick_groups or the list of dicts -> the return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_inter_fast_pick_groups(groups)
+        groups, n = self._as_groups(self.make_inter_fast_pick_groups, groups)
         return self.lib.svt_hip_inter_fast_pick_frame(groups, n, metric, self._stream())
 
     def make_inter_fast_search_groups(self, groups):
         """groups: make_inter_fast_pick_groups' dicts (dist / dist_cb / dist_cr optional: scratch) plus bwidth, bheight, use_chroma, ref0 /
         ref1 (lists of the Y, Cb, Cr tensors whose first element is sample (0, 0) of the picture), ref_stride, src, src_stride (three
         each), pred_out (list of dense [n, N, h, w] tensors, Y required), optional intra_pred ([n, nintra, H, W]).  -> ctypes array"""
-        P = lambda t: self._p(t) if t is not None else None
-        arr = (InterFastSearchGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            a = arr[i]
-            self._inter_fast_pick_struct(a.pick, g)
-            a.bwidth, a.bheight, a.use_chroma = g.get("bwidth", 0), g.get("bheight", 0), int(g.get("use_chroma", 0))
-            for p in range(3):
-                for l, key in enumerate(("ref0", "ref1")):
-                    planes = g.get(key) or ()
-                    a.d_ref[l][p] = P(planes[p]) if p < len(planes) else None
-                src, out = g.get("src") or (), g.get("pred_out") or ()
-                a.d_src[p] = P(src[p]) if p < len(src) else None
-                a.d_pred_out[p] = P(out[p]) if p < len(out) else None
-                a.ref_stride[p] = list(g.get("ref_stride", ()))[p] if p < len(g.get("ref_stride", ())) else 0
-                a.src_stride[p] = list(g.get("src_stride", ()))[p] if p < len(g.get("src_stride", ())) else 0
-            a.d_intra_pred = P(g.get("intra_pred"))
-        return arr
+        return records.build(InterFastSearchGroup, groups)
 
     def inter_fast_search_scratch_bytes(self, groups):
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_inter_fast_search_groups(groups)
+        groups, n = self._as_groups(self.make_inter_fast_search_groups, groups)
         return self.lib.svt_hip_inter_fast_search_scratch_bytes(groups, n)
 
     def inter_fast_search_frame(self, groups, pic_width, pic_height, metric, scratch=None, bd=8):
         """svt_hip_inter_fast_search_frame.  scratch: a uint8 device tensor of inter_fast_search_scratch_bytes, allocated here when None
         and needed (returned beside the code so that it outlives the enqueued work) -> (return code, scratch)"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_inter_fast_search_groups(groups)
+        groups, n = self._as_groups(self.make_inter_fast_search_groups, groups)
         if scratch is None:
             need = self.lib.svt_hip_inter_fast_search_scratch_bytes(groups, n)
             if need:
                 scratch = self.torch.empty((need,), dtype=self.torch.uint8, device=self.device)
-        rc = self.lib.svt_hip_inter_fast_search_frame(groups, n, pic_width, pic_height, bd, metric, self._p(scratch) if scratch is not None else None,
-                                                      scratch.numel() if scratch is not None else 0, self._stream())
+        rc = self.lib.svt_hip_inter_fast_search_frame(groups, n, pic_width, pic_height, bd, metric, *self._scratch_args(scratch), self._stream())
         return rc, scratch
 
     # -- the join of mode decision: full cost, early exit, best candidate and the winner's arrays per block ------------------------------
-    MD_GATHERS = ("pred", "best_pred", "qcoeff", "dqcoeff", "best_qcoeff", "best_dqcoeff")
-
-    def _md_decide_struct(self, a, g):
-        """fills one MdDecideGroup from a dict (see make_md_decide_groups)"""
-        P = lambda t: self._p(t) if t is not None else None
-        a.bsize, a.nblocks, a.n = g["bsize"], g["nblocks"], g["n"]
-        a.ninter, a.nintra, a.lambda_ = g.get("ninter", 0), g.get("nintra", 0), g.get("lambda", 0)
-        a.slice_is_intra, a.full_loop_escape = int(g.get("slice_is_intra", 0)), g.get("full_loop_escape", 0)
-        modes = [int(m) for m in g.get("modes", ())][:64]
-        a.modes = (ctypes.c_uint8 * 64)(*(modes + [0] * (64 - len(modes))))
-        for k in ("luma", "dist_cb", "dist_cr", "bits_cb", "bits_cr", "eob_cb", "eob_cr", "rate", "cand", "cand_out", "cfl", "blk", "rates",
-                  "decision", "full_cost", "inter_blk", "best_inter_blk"):
-            setattr(a, "d_" + k, P(g.get(k)))
-        for k in self.MD_GATHERS:
-            planes = g.get(k) or ()
-            for p in range(3):
-                getattr(a, "d_" + k)[p] = P(planes[p]) if p < len(planes) else None
-
     def make_md_decide_groups(self, groups):
         """groups: list of dicts with tensors luma (uint8 [nb, n, 40]: TxDecision records), optional dist_cb / dist_cr (int64 [nb, n, 2]),
         bits_cb / bits_cr (int64 [nb, n]), eob_cb / eob_cr (int16 [nb, n]), rate (int32 [nb, n, 2]), cand (uint8 [nb, n]), cand_out (uint8
@@ -2376,16 +1364,11 @@ class SvtHipDsp:
         gathers pred / qcoeff / dqcoeff (lists of up to three tensors [nb, n, ...] for Y, Cb, Cr; None for a plane not given) with best_pred /
         best_qcoeff / best_dqcoeff ([nb, ...]), inter_blk (uint8 [nb, n, 16]) with best_inter_blk (uint8 [nb, 16]); plus bsize, nblocks, n,
         ninter, nintra, modes, lambda, slice_is_intra, full_loop_escape.  -> ctypes array (keep the tensors alive!)"""
-        arr = (MdDecideGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            self._md_decide_struct(arr[i], g)
-        return arr
+        return records.build(MdDecideGroup, groups)
 
     def md_decide_frame(self, groups):
         """svt_hip_md_decide_frame.  groups: a ctypes array from make_md_decide_groups or the list of dicts -> the return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_md_decide_groups(groups)
+        groups, n = self._as_groups(self.make_md_decide_groups, groups)
         return self.lib.svt_hip_md_decide_frame(groups, n, self._stream())
 
     # -- the partition decision: d1 / d2 per superblock and the final block list -------------------------------------------------------
@@ -2401,17 +1384,7 @@ class SvtHipDsp:
         part_sq_dtype), final_count (int32 [nsb]), final (uint8 [nsb, 256, 12]: part_final_dtype), optional final_decision (uint8 [nsb, 256,
         72]); plus lambda, pic_width, pic_height, slice_is_intra and optionally nsb / nleaves / nsrc (else the tensors' first dimensions).
         -> PartitionArgs (keep the tensors alive!)"""
-        P = lambda t: self._p(t) if t is not None else None
-        A = PartitionArgs()
-        src = a.get("decision") if a.get("decision") is not None else a.get("cost")
-        A.nsb = a["nsb"] if "nsb" in a else a["sb"].shape[0]
-        A.nleaves = a["nleaves"] if "nleaves" in a else (a["leaf"].shape[0] if a.get("leaf") is not None else 0)
-        A.nsrc = a["nsrc"] if "nsrc" in a else (src.shape[0] if src is not None else 0)
-        A.lambda_, A.pic_width, A.pic_height = a.get("lambda", 0), a.get("pic_width", 0), a.get("pic_height", 0)
-        A.slice_is_intra = int(a.get("slice_is_intra", 0))
-        for k in ("sb", "leaf", "decision", "cost", "partition_bits", "sq", "final_count", "final", "final_decision"):
-            setattr(A, "d_" + k, P(a.get(k)))
-        return A
+        return records.fill(PartitionArgs(), a)
 
     def partition_decide_frame(self, args):
         """svt_hip_partition_decide_frame.  args: a PartitionArgs from make_partition_args or the dict -> the return code"""
@@ -2432,35 +1405,13 @@ class SvtHipDsp:
         tensors}; stride / width / height (lists, samples; default the plane tensors' stride(0) and shape), planes (1 or 3; default the
         number of recon planes) and optionally nsb / nsrc / ngroups / scratch_bytes (else from the tensors).
         -> ReconFinalArgs (keep the tensors alive; the group array rides in its _groups)"""
-        P = lambda t: self._p(t) if t is not None else None
-        A = ReconFinalArgs()
-        groups = a.get("groups") or []
-        arr = (ReconFinalGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            arr[i].src_first, arr[i].nblocks, arr[i].bsize, arr[i].tx_type_uv = g["src_first"], g["nblocks"], g["bsize"], g.get("tx_type_uv", 0)
-            for key in ("best_pred", "best_dqcoeff", "best_qcoeff"):
-                planes = g.get(key) or ()
-                for p in range(3):
-                    getattr(arr[i], "d_" + key)[p] = P(planes[p]) if p < len(planes) else None
-        A._groups = arr
-        A.groups = ctypes.cast(arr, c_void_p) if a.get("groups") is not None else None
-        recon = list(a.get("recon") or ())
-        A.nsb = a["nsb"] if "nsb" in a else a["final_count"].shape[0]
-        A.nsrc = a["nsrc"] if "nsrc" in a else a["decision"].shape[0]
-        A.ngroups = a["ngroups"] if "ngroups" in a else len(groups)
-        A.planes = a["planes"] if "planes" in a else len(recon)
-        for p in range(3):
-            t = recon[p] if p < len(recon) else None
-            A.d_recon[p] = P(t)
-            for key, default in (("stride", t.stride(0) if t is not None else 0), ("width", t.shape[1] if t is not None else 0),
-                                 ("height", t.shape[0] if t is not None else 0)):
-                given = a.get(key)
-                getattr(A, key)[p] = given[p] if given is not None and p < len(given) else default
-            sbq = a.get("sb_qcoeff") or ()
-            A.d_sb_qcoeff[p] = P(sbq[p]) if p < len(sbq) else None
-        for k in ("final", "final_count", "decision", "status", "coeff_offset", "scratch"):
-            setattr(A, "d_" + k, P(a.get(k)))
-        A.scratch_bytes = a["scratch_bytes"] if "scratch_bytes" in a else (a["scratch"].numel() * a["scratch"].element_size() if a.get("scratch") is not None else 0)
+        A = records.fill(ReconFinalArgs(), a)
+        A._groups = records.build(ReconFinalGroup, a.get("groups") or [])
+        A.groups = ctypes.cast(A._groups, c_void_p) if a.get("groups") is not None else None
+        recon = list(a.get("recon") or ()) + [None] * 3
+        _per_plane(A.stride, a.get("stride"), [t.stride(0) if t is not None else 0 for t in recon])
+        _per_plane(A.width, a.get("width"), [t.shape[1] if t is not None else 0 for t in recon])
+        _per_plane(A.height, a.get("height"), [t.shape[0] if t is not None else 0 for t in recon])
         return A
 
     def recon_final_frame(self, args):
@@ -2495,29 +1446,18 @@ class SvtHipDsp:
         [.., 256, 8]: intra_enc_result_dtype), sb_qcoeff (list of int32 tensors), coeff_offset (int32); q_luma / q_chroma (dicts of int16
         rows as the quantiser tables give them); src_stride / stride / width / height (lists; default from the plane tensors),
         src_pic_pitch / recon_pic_pitch (lists, samples; default 0), scratch_bytes.  -> IntraEncodeArgs (keep the tensors alive)"""
-        P = lambda t: self._p(t) if t is not None else None
-        A = IntraEncodeArgs()
-        A.npics, A.sb_cols, A.sb_rows, A.sb_pitch, A.blk_pitch = a.get("npics", 1), a["sb_cols"], a["sb_rows"], a.get("sb_pitch", 0), a.get("blk_pitch", 0)
-        A.nsrc = a["nsrc"] if "nsrc" in a else (a["blk"].shape[0] if a.get("blk") is not None else 0)
-        src, recon, sbq = list(a.get("src") or ()), list(a.get("recon") or ()), list(a.get("sb_qcoeff") or ())
-        for p in range(3):
-            s, r = (src[p] if p < len(src) else None), (recon[p] if p < len(recon) else None)
-            A.d_src[p], A.d_recon[p] = P(s), P(r)
-            A.d_sb_qcoeff[p] = P(sbq[p]) if p < len(sbq) else None
-            for key, default in (("src_stride", s.stride(0) if s is not None else 0), ("stride", r.stride(0) if r is not None else 0),
-                                 ("width", r.shape[1] if r is not None else 0), ("height", r.shape[0] if r is not None else 0),
-                                 ("src_pic_pitch", 0), ("recon_pic_pitch", 0)):
-                given = a.get(key)
-                getattr(A, key)[p] = given[p] if given is not None and p < len(given) else default
+        A = records.fill(IntraEncodeArgs(), a)
+        src, recon = list(a.get("src") or ()) + [None] * 3, list(a.get("recon") or ()) + [None] * 3
+        _per_plane(A.src_stride, a.get("src_stride"), [t.stride(0) if t is not None else 0 for t in src])
+        _per_plane(A.stride, a.get("stride"), [t.stride(0) if t is not None else 0 for t in recon])
+        _per_plane(A.width, a.get("width"), [t.shape[1] if t is not None else 0 for t in recon])
+        _per_plane(A.height, a.get("height"), [t.shape[0] if t is not None else 0 for t in recon])
         A._keep = []
         for name in ("q_luma", "q_chroma"):
             if a.get(name) is not None:
                 q, tabs = self._qrows(a[name])
                 A._keep += [q, tabs]
                 setattr(A, name, ctypes.cast(ctypes.pointer(q), c_void_p))
-        for k in ("final", "final_count", "blk", "tables", "status", "result", "coeff_offset", "scratch"):
-            setattr(A, "d_" + k, P(a.get(k)))
-        A.scratch_bytes = a["scratch_bytes"] if "scratch_bytes" in a else (a["scratch"].numel() * a["scratch"].element_size() if a.get("scratch") is not None else 0)
         return A
 
     def intra_encode_frame(self, args):
@@ -2532,16 +1472,15 @@ class SvtHipDsp:
         optional "cb" / "cr": make_full_loop_groups dicts with one type (dist / eob / qcoeff / dqcoeff optional: scratch) and then
         txb_skip_ctx_c / dc_sign_ctx_c (two uint8 [nb * n] tensors each), coeff_cost_uv (int32 [529]), eob_cost_uv (int32 [22]), optional
         bits_c (two int64 [nb, n] tensors)}.  -> ctypes array (keep the tensors alive!)"""
-        P = lambda t: self._p(t) if t is not None else None
         arr = (MdSearchGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            a = arr[i]
-            self._md_decide_struct(a.md, g["md"])
-            a.luma = self.make_tx_search_groups([g["luma"]])[0]
+        for a, g in zip(arr, groups):
+            records.fill(a.md, g["md"])
+            records.fill(a.luma, g["luma"])
             a.use_chroma = int(g.get("cb") is not None)
             if a.use_chroma:
-                fl = self.make_full_loop_groups([g["cb"], g["cr"]])
-                a.cb, a.cr = fl[0], fl[1]
+                records.fill(a.cb, g["cb"])
+                records.fill(a.cr, g["cr"])
+                P = lambda t: t.data_ptr() if t is not None else None
                 for p in range(2):
                     a.d_txb_skip_ctx_c[p], a.d_dc_sign_ctx_c[p] = P(g["txb_skip_ctx_c"][p]), P(g["dc_sign_ctx_c"][p])
                     a.d_bits_c[p] = P(g["bits_c"][p]) if g.get("bits_c") is not None else None
@@ -2550,9 +1489,7 @@ class SvtHipDsp:
 
     def md_search_scratch_bytes(self, groups):
         """svt_hip_md_search_scratch_bytes of a ctypes array from make_md_search_groups or of the list of dicts (0: bad parameters)"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_md_search_groups(groups)
+        groups, n = self._as_groups(self.make_md_search_groups, groups)
         return self.lib.svt_hip_md_search_scratch_bytes(groups, n)
 
     def md_search_frame(self, groups, qrow_luma, qrow_chroma, scratch, flavour=1):
@@ -2560,21 +1497,10 @@ class SvtHipDsp:
         from make_md_search_groups or the list of dicts; qrow_luma / qrow_chroma: quantiser row sets as full_loop_frame takes them
         (qrow_chroma None without chroma); scratch: a uint8 device tensor of at least md_search_scratch_bytes(groups) bytes (None where
         that is 0).  -> the library's return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_md_search_groups(groups)
-        keep, rows = [], []
-        for qrow in (qrow_luma, qrow_chroma):
-            if qrow is None:
-                rows.append(None)
-                continue
-            tabs = [_np16(qrow[k]) for k in ("zbin", "round", "quant", "quant_shift", "dequant")]
-            keep.append(tabs)
-            rows.append(self.QRows(*[tb.ctypes.data for tb in tabs]))
-        return self.lib.svt_hip_md_search_frame(groups, n, flavour, ctypes.addressof(rows[0]) if rows[0] is not None else None,
-                                                ctypes.addressof(rows[1]) if rows[1] is not None else None,
-                                                self._p(scratch) if scratch is not None else None,
-                                                scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+        groups, n = self._as_groups(self.make_md_search_groups, groups)
+        rows = [self._qrows(qrow) if qrow is not None else None for qrow in (qrow_luma, qrow_chroma)]      # (QRows, the arrays it points into)
+        return self.lib.svt_hip_md_search_frame(groups, n, flavour, *[ctypes.addressof(r[0]) if r is not None else None for r in rows],
+                                                *self._scratch_args(scratch), self._stream())
 
     def fast_pick(self, dist, blk, rates, tx_size, bsize, bsize_uv, modes, deltas, uv_modes, uv_deltas, nfl, lam, metric, use_angle_delta=True,
                   slice_is_intra=True, ac_dequant_q3=0, intrabc_bits=0, dist_cb=None, dist_cr=None, pred=None, src_xy=None, want_all_cost=False):
@@ -2605,31 +1531,26 @@ class SvtHipDsp:
         """groups: list of dicts {"luma": a fast-loop group dict (make_fast_loop_groups; dist / pred may be absent: scratch), optional "cb" /
         "cr": fast-loop group dicts of the chroma planes (dist may be absent), "pick": a fast-pick group dict (its size, list, dist*, pred
         come from the fast-loop groups)}.  -> ctypes array (keep the tensors alive!)"""
-        arr = (self.IntraFastSearchGroup * max(len(groups), 1))()
-        for i, g in enumerate(groups):
-            arr[i].luma = self.make_fast_loop_groups([g["luma"]])[0]
-            arr[i].use_chroma = int(g.get("cb") is not None)
-            if g.get("cb") is not None:
-                arr[i].cb = self.make_fast_loop_groups([g["cb"]])[0]
-                arr[i].cr = self.make_fast_loop_groups([g["cr"]])[0]
-            arr[i].pick = self._fast_pick_struct(g["pick"])
+        arr = (IntraFastSearchGroup * max(len(groups), 1))()
+        for a, g in zip(arr, groups):
+            records.fill(a.luma, g["luma"])
+            a.use_chroma = int(g.get("cb") is not None)
+            if a.use_chroma:
+                records.fill(a.cb, g["cb"])
+                records.fill(a.cr, g["cr"])
+            records.fill(a.pick, g["pick"])
         return arr
 
     def intra_fast_search_scratch_bytes(self, groups):
         """svt_hip_intra_fast_search_scratch_bytes of a ctypes array from make_intra_fast_search_groups or of the list of dicts"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_intra_fast_search_groups(groups)
+        groups, n = self._as_groups(self.make_intra_fast_search_groups, groups)
         return self.lib.svt_hip_intra_fast_search_scratch_bytes(groups, n)
 
     def intra_fast_search_frame(self, groups, metric, scratch, flavour=1):
         """svt_hip_intra_fast_search_frame: fast loop (luma, Cb, Cr) -> pick in one call.  scratch: a uint8 device tensor of at least
         intra_fast_search_scratch_bytes(groups) bytes (None where that is 0).  -> the library's return code"""
-        n = len(groups)
-        if isinstance(groups, list):
-            groups = self.make_intra_fast_search_groups(groups)
-        return self.lib.svt_hip_intra_fast_search_frame(groups, n, metric, flavour, self._p(scratch) if scratch is not None else None,
-                                                        scratch.numel() * scratch.element_size() if scratch is not None else 0, self._stream())
+        groups, n = self._as_groups(self.make_intra_fast_search_groups, groups)
+        return self.lib.svt_hip_intra_fast_search_frame(groups, n, metric, flavour, *self._scratch_args(scratch), self._stream())
 
     def intra_fast_search(self, luma, pick, metric, cb=None, cr=None, flavour=1):
         """One group with the per-candidate arrays in a scratch allocated here: luma / cb / cr fast-loop group dicts without dist / pred, pick
@@ -2641,14 +1562,6 @@ class SvtHipDsp:
         self._check(self.intra_fast_search_frame(g, metric, scratch, flavour), "svt_hip_intra_fast_search_frame")
         return pick
 
-    class CdefPic(ctypes.Structure):
-        """svt_hip_cdef_pic"""
-        _fields_ = [("d_rec", c_void_p * 3), ("rec_stride", c_uint32 * 3), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3),
-                    ("d_dst", c_void_p * 3), ("dst_stride", c_uint32 * 3), ("d_skip", c_void_p), ("skip_stride", c_uint32),
-                    ("width", c_uint32), ("height", c_uint32), ("bit_depth", c_int32), ("base_qindex", c_int32), ("npics", c_uint32),
-                    ("rec_pitch", ctypes.c_uint64 * 3), ("src_pitch", ctypes.c_uint64 * 3), ("dst_pitch", ctypes.c_uint64 * 3),
-                    ("skip_pitch", ctypes.c_uint64)]
-
     def make_cdef_pic(self, rec, skip, width, height, bit_depth, base_qindex, src=None, dst=None):
         """rec / src / dst: (Y, Cb, Cr) tensors, uint8 (bit depth 8) or uint16 / int16 (10), [rows, stride] for one picture or
         [npics, rows, stride] for a stack, or views of such with rows (and pictures) further apart (the strides are
@@ -2657,13 +1570,7 @@ class SvtHipDsp:
         p = self.CdefPic()
         stack = rec[0].dim() == 3
         p.npics = rec[0].shape[0] if stack else 1
-        for planes, ptr, stride, pitch in ((rec, p.d_rec, p.rec_stride, p.rec_pitch), (src, p.d_src, p.src_stride, p.src_pitch),
-                                           (dst, p.d_dst, p.dst_stride, p.dst_pitch)):
-            if planes is None:
-                continue
-            for i, t in enumerate(planes):
-                assert t.stride(-1) == 1 and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
-                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.stride(-2), (t.stride(0) if stack else 0)
+        _pic_planes(p, stack, bit_depth, rec=rec, src=src, dst=dst)
         assert skip.stride(-1) == 1 and skip.element_size() == 1
         p.d_skip, p.skip_stride, p.skip_pitch = skip.data_ptr(), skip.stride(-2), (skip.stride(0) if stack else 0)
         p.width, p.height, p.bit_depth, p.base_qindex = width, height, bit_depth, base_qindex
@@ -2701,22 +1608,6 @@ class SvtHipDsp:
         return dst
 
     # -- deblocking: the mode-info grid, av1_loop_filter_frame, the filter-level search table and the host helpers of the pick ---------
-    class DlfPic(ctypes.Structure):
-        """svt_hip_dlf_pic"""
-        _fields_ = [("d_rec", c_void_p * 3), ("rec_stride", c_uint32 * 3), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3),
-                    ("d_dst", c_void_p * 3), ("dst_stride", c_uint32 * 3), ("d_mi", c_void_p), ("mi_stride", c_uint32),
-                    ("width", c_uint32), ("height", c_uint32), ("bit_depth", c_int32), ("npics", c_uint32),
-                    ("rec_pitch", ctypes.c_uint64 * 3), ("src_pitch", ctypes.c_uint64 * 3), ("dst_pitch", ctypes.c_uint64 * 3),
-                    ("mi_pitch", ctypes.c_uint64), ("filter_level", c_int32 * 2), ("filter_level_u", c_int32), ("filter_level_v", c_int32),
-                    ("sharpness_level", c_int32), ("mode_ref_delta_enabled", c_int32), ("ref_deltas", ctypes.c_int8 * 8),
-                    ("mode_deltas", ctypes.c_int8 * 2), ("pad", ctypes.c_uint8 * 6)]
-
-    class DlfMiArgs(ctypes.Structure):
-        """svt_hip_dlf_mi_args"""
-        _fields_ = [("d_final", c_void_p), ("d_final_count", c_void_p), ("d_info", c_void_p), ("d_mi", c_void_p), ("npics", c_uint32),
-                    ("nsb", c_uint32), ("sb_pitch", c_uint32), ("nsrc", c_uint32), ("mi_cols", c_uint32), ("mi_rows", c_uint32),
-                    ("mi_stride", c_uint32), ("pad", c_uint32), ("mi_pitch", ctypes.c_uint64)]
-
     @staticmethod
     def make_dlf_pic(rec, mi, width, height, bit_depth, levels=(0, 0, 0, 0), sharpness=0, ref_deltas=None, mode_deltas=None, src=None, dst=None):
         """rec / src / dst: (Y, Cb, Cr) tensors, uint8 (bit depth 8) or uint16 / int16 (10), [rows, stride] for one picture or
@@ -2727,13 +1618,7 @@ class SvtHipDsp:
         p = SvtHipDsp.DlfPic()
         stack = rec[0].dim() == 3
         p.npics = rec[0].shape[0] if stack else 1
-        for planes, ptr, stride, pitch in ((rec, p.d_rec, p.rec_stride, p.rec_pitch), (src, p.d_src, p.src_stride, p.src_pitch),
-                                           (dst, p.d_dst, p.dst_stride, p.dst_pitch)):
-            if planes is None:
-                continue
-            for i, t in enumerate(planes):
-                assert t.stride(-1) == 1 and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
-                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.stride(-2), (t.stride(0) if stack else 0)
+        _pic_planes(p, stack, bit_depth, rec=rec, src=src, dst=dst)
         assert mi.stride(-1) == 1 and mi.stride(-2) == 4 and mi.element_size() == 1 and mi.shape[-1] == 4 and mi.dim() == (4 if stack else 3)
         p.d_mi, p.mi_stride, p.mi_pitch = mi.data_ptr(), mi.stride(-3) // 4, (mi.stride(0) // 4 if stack else 0)
         p.width, p.height, p.bit_depth = width, height, bit_depth
@@ -2826,17 +1711,6 @@ class SvtHipDsp:
         return list(lv)
 
     # -- loop restoration: av1_loop_restoration_filter_frame, try_restoration_unit_seg per candidate, av1_compute_stats per unit ----------
-    class LrPic(ctypes.Structure):
-        """svt_hip_lr_pic"""
-        _fields_ = [("d_cdef", c_void_p * 3), ("cdef_stride", c_uint32 * 3), ("pad0", c_uint32), ("d_dblk", c_void_p * 3), ("dblk_stride", c_uint32 * 3),
-                    ("pad1", c_uint32), ("d_src", c_void_p * 3), ("src_stride", c_uint32 * 3), ("pad2", c_uint32), ("d_dst", c_void_p * 3),
-                    ("dst_stride", c_uint32 * 3), ("pad3", c_uint32), ("width", c_uint32), ("height", c_uint32), ("bit_depth", c_int32),
-                    ("unit_size", c_uint32 * 3), ("npics", c_uint32), ("pad4", c_uint32), ("cdef_pitch", ctypes.c_uint64 * 3),
-                    ("dblk_pitch", ctypes.c_uint64 * 3), ("src_pitch", ctypes.c_uint64 * 3), ("dst_pitch", ctypes.c_uint64 * 3)]
-
-    LR_UNIT_DTYPE = [("type", "<i4"), ("vfilter", "<i2", 3), ("hfilter", "<i2", 3), ("xqd", "<i2", 2), ("ep", "<i4")]              # svt_hip_lr_unit
-    LR_CAND_DTYPE = [("pic", "<u4"), ("plane", "<u4"), ("unit", "<u4"), ("u", LR_UNIT_DTYPE)]                                       # svt_hip_lr_cand
-
     @staticmethod
     def make_lr_pic(cdef, dblk, width, height, bit_depth, unit_size, src=None, dst=None):
         """cdef / dblk / src / dst: (Y, Cb, Cr) tensors, uint8 (bit depth 8) or uint16 / int16 (10), [rows, stride] for one picture or
@@ -2845,13 +1719,7 @@ class SvtHipDsp:
         p = SvtHipDsp.LrPic()
         stack = cdef[0].dim() == 3
         p.npics = cdef[0].shape[0] if stack else 1
-        for planes, ptr, stride, pitch in ((cdef, p.d_cdef, p.cdef_stride, p.cdef_pitch), (dblk, p.d_dblk, p.dblk_stride, p.dblk_pitch),
-                                           (src, p.d_src, p.src_stride, p.src_pitch), (dst, p.d_dst, p.dst_stride, p.dst_pitch)):
-            if planes is None:
-                continue
-            for i, t in enumerate(planes):
-                assert t.stride(-1) == 1 and t.element_size() == (1 if bit_depth == 8 else 2) and t.dim() == (3 if stack else 2)
-                ptr[i], stride[i], pitch[i] = t.data_ptr(), t.stride(-2), (t.stride(0) if stack else 0)
+        _pic_planes(p, stack, bit_depth, cdef=cdef, dblk=dblk, src=src, dst=dst)
         p.width, p.height, p.bit_depth = width, height, bit_depth
         for i in range(3):
             p.unit_size[i] = int(unit_size[i])
@@ -2947,11 +1815,6 @@ class SvtHipDsp:
                                                            scratch.numel() * scratch.element_size(), self._stream()), "svt_hip_lr_wiener_stats_frame")
         return M, H
 
-    class LrWalk(ctypes.Structure):
-        """svt_hip_lr_walk"""
-        _fields_ = [("vfilter", ctypes.c_int16 * 3), ("hfilter", ctypes.c_int16 * 3), ("win", c_int32), ("step", c_int32), ("dir", c_int32), ("p", c_int32),
-                    ("phase", c_int32), ("skip", c_int32), ("state", c_int32), ("err", ctypes.c_int64)]
-
     LR_WALK_TRY, LR_WALK_DONE = 1, 2
 
     @staticmethod
@@ -2986,9 +1849,6 @@ class SvtHipDsp:
         if rc not in (SvtHipDsp.LR_WALK_TRY, SvtHipDsp.LR_WALK_DONE):
             raise SvtHipError(f"svt_hip_lr_walk_next = {rc}")
         return rc
-
-    LR_RESULT_DTYPE = [("sse", "<i8", 3), ("vfilter", "<i2", 3), ("hfilter", "<i2", 3), ("xqd", "<i2", 2), ("ep", "<i4"), ("pad", "<i4")]      # svt_hip_lr_result
-    LR_COSTS_DTYPE = [("rdmult", "<i4"), ("wiener_restore_cost", "<i4", 2), ("sgrproj_restore_cost", "<i4", 2), ("switchable_restore_cost", "<i4", 3)]
 
     @staticmethod
     def lr_finish(plane, wn_filter_mode, costs, results, lib=None):
@@ -3044,8 +1904,6 @@ class SvtHipDsp:
         return taps, sse, rounds
 
     # -- the self-guided parameter search: search_sgrproj_seg -> search_selfguided_restoration per unit ------------------------------
-    LR_SGR_WALK_DTYPE = [("err", "<i8"), ("xqd", "<i2", 2), ("start", "<i2", 2), ("evals", "<i4"), ("pad", "<i4")]                         # svt_hip_lr_sgr_walk
-    LR_SGR_BEST_DTYPE = [("sse", "<i8"), ("proj_err", "<i8"), ("ep", "<i4"), ("xqd", "<i2", 2)]        # svt_hip_lr_sgr_best
     LR_SGR_MAX_EVALS = 137
 
     def lr_sgr_scratch_bytes(self, width, height, unit_size, npics=1, ep_lo=0, ep_hi=16):
@@ -3241,13 +2099,6 @@ class SvtHipDsp:
         return dist, eob, q, dq
 
 
-TxDecision, TxDecideGroup, TxSearchGroup = SvtHipDsp.TxDecision, SvtHipDsp.TxDecideGroup, SvtHipDsp.TxSearchGroup
-QRows, CflSearchGroup, CflDecision, CflDecideGroup, CflPickGroup = (SvtHipDsp.QRows, SvtHipDsp.CflSearchGroup, SvtHipDsp.CflDecision,
-                                                                    SvtHipDsp.CflDecideGroup, SvtHipDsp.CflPickGroup)
+for _name in records.DSP_ATTRIBUTES:                   # SvtHipDsp.TxDecision is TxDecision, and so on
+    setattr(SvtHipDsp, _name, getattr(records, _name))
 
-
-class MdSearchGroup(ctypes.Structure):
-    """svt_hip_md_search_group"""
-    _fields_ = [("md", MdDecideGroup), ("luma", TxSearchGroup), ("use_chroma", c_int32), ("cb", SvtHipDsp.FullLoopGroup), ("cr", SvtHipDsp.FullLoopGroup),
-                ("d_txb_skip_ctx_c", c_void_p * 2), ("d_dc_sign_ctx_c", c_void_p * 2), ("d_coeff_cost_uv", c_void_p), ("d_eob_cost_uv", c_void_p),
-                ("d_bits_c", c_void_p * 2)]
