@@ -1,6 +1,7 @@
 // me_subpel_plan.h — what the sub-pel motion estimation calls (svt_hip_me_subpel_frame, svt_hip_motion_estimate_subpel_frame,
 // svt_hip_me_subpel_planes) settle on the host before they enqueue: the checks, the padding the interpolation needs, the LDS sizes and
-// the grid.  Host only (no HIP header): tests/c/me_subpel_plan_host.cpp compiles it with g++; the kernels (kernel_me_subpel.h) use the same
+// the grid; and every check of both whole-picture calls put together (me_frame_check).  The clauses it shares with the full-pel calls, the
+// padded-plane check and the geometry are me_plan.h's.  Host only (no HIP header): tests/c/me_subpel_plan_host.cpp compiles it with g++; the kernels (kernel_me_subpel.h) use the same
 // constants.
 #pragma once
 #include <stddef.h>
@@ -8,6 +9,7 @@
 
 #include "../../include/svt_hip_dsp.h"
 #include "host_err.h"
+#include "me_plan.h"
 
 namespace svthost {
 
@@ -44,7 +46,7 @@ constexpr int ME_SP_BIPRED_TABLES = 209 * 4 + 1472;                  // the kern
 static_assert(ME_SP_IW >= ME_SP_WIN && ME_SP_BW >= 64 + 2 && ME_SP_REFINE_LDS <= 64 * 1024 && ME_SP_BIPRED_LDS + ME_SP_BIPRED_TABLES <= 64 * 1024,
               "static LDS of a workgroup");
 
-constexpr uint32_t ME_SP_MAX_PICS = 65535;
+constexpr uint32_t ME_SP_MAX_PICS = ME_FRAME_MAX_PICS;
 
 inline bool me_sp_flag(int32_t v) { return v == 0 || v == 1; }
 
@@ -56,58 +58,44 @@ inline int me_subpel_params_check(const svt_hip_me_subpel_params* s) {
     return SVT_HIP_OK;
 }
 
-// what the stage reads of the frame parameters
+// what the stage reads of the frame parameters: the shared clauses (me_plan.h), then its own
 inline int me_subpel_frame_check(const svt_hip_me_frame_params* P) {
-    if (!P) return set_err(SVT_HIP_ERR_INVALID, "NULL parameters");
-    if (P->picture_width < 8 || P->picture_height < 8 || (P->picture_width & 7) || (P->picture_height & 7) || P->picture_width > 16384 ||
-        P->picture_height > 16384)
-        return set_err(SVT_HIP_ERR_INVALID, "picture %d x %d: both sides must be multiples of 8, 8 .. 16384", P->picture_width, P->picture_height);
-    if (P->slice_type != SVT_HIP_SLICE_B && P->slice_type != SVT_HIP_SLICE_P) return set_err(SVT_HIP_ERR_INVALID, "slice type %d (B 0 / P 1)", P->slice_type);
-    if (P->max_number_of_pus_per_sb != SVT_HIP_ME_PUS && P->max_number_of_pus_per_sb != SVT_HIP_ME_PUS_ALL)
-        return set_err(SVT_HIP_ERR_INVALID, "%d PUs per SB (85 or 209)", P->max_number_of_pus_per_sb);
+    if (int rc = me_picture_check(P)) return rc;
+    if (int rc = me_pus_check(P)) return rc;
     if (P->fractional_search_method < 0 || P->fractional_search_method > 2)
         return set_err(SVT_HIP_ERR_INVALID, "fractional_search_method %d (SUB_SAD 0, FULL_SAD 1, SSD 2)", P->fractional_search_method);
     if (P->cu8x8_mode < 0) return set_err(SVT_HIP_ERR_INVALID, "negative cu8x8_mode");
     return SVT_HIP_OK;
 }
 
-// level 0 of a pyramid: the margin above
-inline int me_subpel_plane_check(const svt_hip_me_pyramid* p, const char* what, int32_t width, int32_t height, uint32_t n_pictures) {
-    if (!p) return set_err(SVT_HIP_ERR_INVALID, "%s: NULL pyramid", what);
-    if (!p->d_plane[0]) return set_err(SVT_HIP_ERR_INVALID, "%s: level 0 plane is NULL", what);
-    const uint32_t m = (uint32_t)ME_SP_MARGIN;
-    if (p->origin_x[0] < m || p->origin_y[0] < m || p->origin_x[0] > 32767 || p->origin_y[0] > 32767)
-        return set_err(SVT_HIP_ERR_INVALID, "%s: origin (%u, %u) below the %u samples of padding the interpolation reads", what, p->origin_x[0], p->origin_y[0], m);
-    if ((uint64_t)p->stride[0] < (uint64_t)p->origin_x[0] + (uint32_t)width + m || p->stride[0] > (1u << 20))
-        return set_err(SVT_HIP_ERR_INVALID, "%s: stride %u below origin + width + %u", what, p->stride[0], m);
-    if (n_pictures > 1 && p->pitch[0] < (uint64_t)p->stride[0] * ((uint64_t)p->origin_y[0] + (uint32_t)height + m))
-        return set_err(SVT_HIP_ERR_INVALID, "%s: pitch below one padded picture", what);
-    return SVT_HIP_OK;
-}
-
 inline int me_subpel_pictures_check(const svt_hip_me_pyramid* src, const svt_hip_me_pyramid* ref0, const svt_hip_me_pyramid* ref1,
                                     const svt_hip_me_frame_params* P, uint32_t n_pictures) {
     if (n_pictures > ME_SP_MAX_PICS) return set_err(SVT_HIP_ERR_INVALID, "%u pictures (at most %u)", n_pictures, ME_SP_MAX_PICS);
+    const uint32_t w = (uint32_t)P->picture_width, h = (uint32_t)P->picture_height;
     // the source is read inside its SBs only (a partial SB's block reaches 56 samples into the padding): the search's own 64 do
-    if (!src) return set_err(SVT_HIP_ERR_INVALID, "source: NULL pyramid");
-    if (!src->d_plane[0]) return set_err(SVT_HIP_ERR_INVALID, "source: level 0 plane is NULL");
-    if ((uint64_t)src->stride[0] < (uint64_t)src->origin_x[0] + (uint32_t)P->picture_width + 64u || src->stride[0] > (1u << 20) || src->origin_x[0] > 32767 ||
-        src->origin_y[0] > 32767)
-        return set_err(SVT_HIP_ERR_INVALID, "source: stride %u below origin + width + 64", src->stride[0]);
-    if (n_pictures > 1 && src->pitch[0] < (uint64_t)src->stride[0] * ((uint64_t)src->origin_y[0] + (uint32_t)P->picture_height + 64u))
-        return set_err(SVT_HIP_ERR_INVALID, "source: pitch below one padded picture");
-    if (int rc = me_subpel_plane_check(ref0, "list 0", P->picture_width, P->picture_height, n_pictures)) return rc;
-    if (P->slice_type == SVT_HIP_SLICE_B) { if (int rc = me_subpel_plane_check(ref1, "list 1", P->picture_width, P->picture_height, n_pictures)) return rc; }
+    if (int rc = me_plane_check(src, 0, w, h, 64, n_pictures, "source", ME_READ_BLOCKS)) return rc;
+    if (int rc = me_plane_check(ref0, 0, w, h, ME_SP_MARGIN, n_pictures, "list 0", ME_READ_INTERPOLATION)) return rc;
+    if (P->slice_type == SVT_HIP_SLICE_B) { if (int rc = me_plane_check(ref1, 0, w, h, ME_SP_MARGIN, n_pictures, "list 1", ME_READ_INTERPOLATION)) return rc; }
     else if (ref1) return set_err(SVT_HIP_ERR_INVALID, "a P picture takes no list-1 reference");
     return SVT_HIP_OK;
 }
 
 // grid of the refinement: (SB, list, picture); the bi-prediction's: (SB, 1, picture)
 inline int me_subpel_grid(const svt_hip_me_frame_params* P, uint32_t n_pictures, uint32_t g[3]) {
-    const uint32_t nsbx = (uint32_t)(P->picture_width + 63) / 64, nsby = (uint32_t)(P->picture_height + 63) / 64;
-    g[0] = nsbx * nsby; g[1] = P->slice_type == SVT_HIP_SLICE_P ? 1u : 2u; g[2] = n_pictures;
-    if (g[0] > 0x7fffffffu / 2) return set_err(SVT_HIP_ERR_INVALID, "too many SBs");
-    return SVT_HIP_OK;
+    const MeGeom m = me_geom(*P);
+    g[0] = m.nsb; g[1] = (uint32_t)m.nl; g[2] = n_pictures;
+    return me_geom_check(m);
+}
+
+// the scalars the two kernels take: a NULL enable set is the reference's, everything on
+struct MeSubpelScalars { int f64, h32, h16, h8, qp, no8; };
+inline MeSubpelScalars me_subpel_scalars(const svt_hip_me_frame_params& P, const svt_hip_me_subpel_params* sp) {
+    MeSubpelScalars s;
+    s.f64 = sp ? sp->fractional_search64x64 : 1;
+    s.h32 = sp ? sp->enable_half_pel32x32 : 1; s.h16 = sp ? sp->enable_half_pel16x16 : 1; s.h8 = sp ? sp->enable_half_pel8x8 : 1;
+    s.qp = sp ? sp->enable_quarter_pel : 1;
+    s.no8 = P.cu8x8_mode == 1 ? 1 : 0;                   // disable8x8CuInMeFlag = cu8x8_mode == CU_8x8_MODE_1 (:8205)
+    return s;
 }
 
 // every check of svt_hip_me_subpel_frame
@@ -125,11 +113,27 @@ inline int me_subpel_check(const svt_hip_me_pyramid* src, const svt_hip_me_pyram
     return me_subpel_grid(P, n_pictures, g);
 }
 
+// every check of svt_hip_motion_estimate_frame (subpel off) and svt_hip_motion_estimate_subpel_frame, in the order a caller observes;
+// then the plan holds the launches' scalars (me_plan.h).  An empty stack is validated like any other.
+inline int me_frame_check(const svt_hip_me_pyramid* src, const svt_hip_me_pyramid* ref0, const svt_hip_me_pyramid* ref1, const svt_hip_me_frame_params* P, bool subpel,
+                          const svt_hip_me_subpel_params* sp, uint32_t n_pictures, const uint32_t* d_best_sad, const uint32_t* d_best_mv,
+                          const int16_t* d_area_origin, const uint32_t* d_bipred_sad, const svt_hip_me_result* d_results, const void* d_scratch, size_t scratch_bytes,
+                          MeFramePlan& pl) {
+    if (int rc = me_frame_plan(P, pl)) return rc;
+    if (subpel) {
+        if (int rc = me_subpel_frame_check(P)) return rc;
+        if (int rc = me_subpel_params_check(sp)) return rc;
+    }
+    if (int rc = me_frame_pictures_check(src, ref0, ref1, P, pl, n_pictures)) return rc;
+    if (subpel) { if (int rc = me_subpel_pictures_check(src, ref0, ref1, P, n_pictures)) return rc; }      // the interpolation's wider padding
+    return me_frame_outputs_check(ref0, ref1, pl, n_pictures, d_best_sad, d_best_mv, d_area_origin, d_bipred_sad, d_results, d_scratch, scratch_bytes);
+}
+
 // svt_hip_me_subpel_planes: the window's samples and the filter's reach must lie inside the padded plane
 inline int me_subpel_planes_check(const svt_hip_me_pyramid* ref, int32_t width, int32_t height, int32_t x0, int32_t y0, uint32_t w, uint32_t h,
                                   const uint8_t* d_planes) {
     if (width < 8 || height < 8 || width > 16384 || height > 16384) return set_err(SVT_HIP_ERR_INVALID, "picture %d x %d", width, height);
-    if (int rc = me_subpel_plane_check(ref, "reference", width, height, 1)) return rc;
+    if (int rc = me_plane_check(ref, 0, (uint32_t)width, (uint32_t)height, ME_SP_MARGIN, 1, "reference", ME_READ_INTERPOLATION)) return rc;
     if (!d_planes) return set_err(SVT_HIP_ERR_INVALID, "NULL d_planes");
     if (w < 1 || h < 1 || w > 4096 || h > 4096) return set_err(SVT_HIP_ERR_INVALID, "window %u x %u (1 .. 4096)", w, h);
     // plane J at (y, x) reads I[y - 2 .. y + 1][x - 2 .. x + 1]
@@ -137,5 +141,6 @@ inline int me_subpel_planes_check(const svt_hip_me_pyramid* ref, int32_t width, 
         return set_err(SVT_HIP_ERR_INVALID, "window (%d, %d) %u x %u reaches outside the %d samples of padding", x0, y0, w, h, ME_SP_MARGIN);
     return SVT_HIP_OK;
 }
+inline uint32_t me_subpel_planes_grid(uint32_t w, uint32_t h) { return (w * h + 255) / 256; }      // one lane per sample of the window
 
 }  // namespace svthost

@@ -2,7 +2,9 @@
 // svt_hip_me_fullpel_search_*, svt_hip_hme_level_*, svt_hip_motion_estimate_frame) settle on the host before they enqueue: the LDS layout
 // of each kernel, the kernel a shape is routed to with its grid, threads and dynamic LDS, and the window of the motion search.  The layout
 // functions are constexpr and are called by the kernels too (kernel_pixel.h, kernel_me_steps.h), so a pitch has one statement.  Host
-// only otherwise (no HIP header): tests/c/search_plan_host.cpp compiles it with g++.
+// only otherwise (no HIP header): tests/c/search_plan_host.cpp compiles it with g++.  Everything else the motion-search calls decide - their
+// refusals in order, the kernel of a full-pel search, the grids, the frame call's plan - is me_plan.h's, which builds on the windows here;
+// the SAD / SSE / residual / distortion calls' is pixel_plan.h's.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -79,6 +81,19 @@ constexpr uint32_t sad_threads(uint32_t lpb, uint64_t per_blk, uint32_t floor) {
     uint32_t threads = 256;
     while (threads > floor && (threads / lpb) * per_blk > SAD_LDS_MAX) threads >>= 1;
     return threads;
+}
+
+// the *_planes_batch form of a search addresses its blocks by two offset tables
+inline int search_offsets_check(bool need_offs, const void* d_src_offs, const void* d_ref_offs) {
+    if (need_offs && (!d_src_offs || !d_ref_offs)) return set_err(SVT_HIP_ERR_INVALID, "NULL offset table");
+    return SVT_HIP_OK;
+}
+// the SAD search's pointers
+inline int sad_search_args_check(bool need_offs, const void* d_src_offs, const void* d_ref_offs, const void* d_src, const void* d_ref, const void* d_best_sad,
+                                 const void* d_x, const void* d_y) {
+    if (int rc = search_offsets_check(need_offs, d_src_offs, d_ref_offs)) return rc;
+    if (!d_src || !d_ref || !d_best_sad || !d_x || !d_y) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
+    return SVT_HIP_OK;
 }
 
 // Every refusal of the SAD search that needs no pointer, then the kernel and its launch.  All byte and row counts are 64-bit: a

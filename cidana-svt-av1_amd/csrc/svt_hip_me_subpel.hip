@@ -13,25 +13,20 @@ static MeSubpelDev me_subpel_dev(const svt_hip_me_pyramid* src, const svt_hip_me
                                  const svt_hip_me_subpel_params* sp, uint32_t n_pictures) {
     MeSubpelDev d;
     memset(&d, 0, sizeof(d));
-    d.nlists = P.slice_type == SVT_HIP_SLICE_P ? 1 : 2;
-    const svt_hip_me_pyramid* refs[2] = {ref0, d.nlists == 2 ? ref1 : nullptr};
-    d.src = src->d_plane[0] + (size_t)src->origin_y[0] * src->stride[0] + src->origin_x[0];
-    d.src_stride = src->stride[0];
-    d.src_pitch = n_pictures > 1 ? src->pitch[0] : 0;
-    for (int l = 0; l < d.nlists; l++) {
-        d.ref[l] = refs[l]->d_plane[0] + (size_t)refs[l]->origin_y[0] * refs[l]->stride[0] + refs[l]->origin_x[0];
-        d.ref_stride[l] = refs[l]->stride[0];
-        d.ref_pitch[l] = n_pictures > 1 ? refs[l]->pitch[0] : 0;
+    const MeGeom g = me_geom(P);
+    const MeSubpelScalars sc = me_subpel_scalars(P, sp);
+    const svt_hip_me_pyramid* refs[2] = {ref0, ref1};
+    const MePlaneAt at = me_plane_at(src, 0, n_pictures);
+    d.src = at.p; d.src_stride = at.stride; d.src_pitch = at.pitch;
+    for (int l = 0; l < g.nl; l++) {
+        const MePlaneAt rt = me_plane_at(refs[l], 0, n_pictures);
+        d.ref[l] = rt.p; d.ref_stride[l] = rt.stride; d.ref_pitch[l] = rt.pitch;
     }
     d.width = P.picture_width; d.height = P.picture_height;
-    d.npus = P.max_number_of_pus_per_sb;
+    d.nlists = g.nl; d.npus = P.max_number_of_pus_per_sb;
     d.method = P.fractional_search_method;
-    d.f64 = sp ? sp->fractional_search64x64 : 1;
-    d.h32 = sp ? sp->enable_half_pel32x32 : 1; d.h16 = sp ? sp->enable_half_pel16x16 : 1; d.h8 = sp ? sp->enable_half_pel8x8 : 1;
-    d.qp = sp ? sp->enable_quarter_pel : 1;
-    d.no8 = P.cu8x8_mode == 1 ? 1 : 0;                   // disable8x8CuInMeFlag = cu8x8_mode == CU_8x8_MODE_1 (:8205)
-    d.nsbx = (uint32_t)(P.picture_width + 63) / 64;
-    d.nsb = d.nsbx * ((uint32_t)(P.picture_height + 63) / 64);
+    d.f64 = sc.f64; d.h32 = sc.h32; d.h16 = sc.h16; d.h8 = sc.h8; d.qp = sc.qp; d.no8 = sc.no8;
+    d.nsbx = g.nsbx; d.nsb = g.nsb;
     return d;
 }
 
@@ -50,9 +45,9 @@ int svthost::me_subpel_enqueue_bipred(const svt_hip_me_pyramid* src, const svt_h
     const svt_hip_me_frame_params& P = *params;
     const MeSubpelDev d = me_subpel_dev(src, ref0, ref1, P, nullptr, n_pictures);
     static_assert(sizeof(MeResult) == sizeof(svt_hip_me_result), "layout");
-    const int bipred_all = (P.cu8x8_mode == 0 || P.max_number_of_pus_per_sb == SVT_HIP_ME_PUS_ALL) ? 1 : 0;
-    hipLaunchKernelGGL(me_subpel_bipred_kernel, dim3(d.nsb, 1, n_pictures), dim3(ME_SP_THREADS), 0, s, d, bipred_all, P.fractional_search_method == 0 ? 1 : 0,
-                       me_pu_map(), d_best_sad, d_best_mv, d_bipred_sad, reinterpret_cast<MeResult*>(d_results));
+    const MeBipredSwitches b = me_bipred_switches(P);
+    hipLaunchKernelGGL(me_subpel_bipred_kernel, dim3(d.nsb, 1, n_pictures), dim3(ME_SP_THREADS), 0, s, d, b.all_pus, b.sub_sad, me_pu_map(), d_best_sad, d_best_mv,
+                       d_bipred_sad, reinterpret_cast<MeResult*>(d_results));
     return launch_status("me_subpel_bipred");
 }
 
@@ -75,7 +70,7 @@ extern "C" int svt_hip_me_subpel_planes(const svt_hip_me_pyramid* ref, int32_t p
                                         uint32_t h, uint8_t* d_planes, void* stream) {
     if (int rc = require_init()) return rc;
     if (int rc = me_subpel_planes_check(ref, picture_width, picture_height, x0, y0, w, h, d_planes)) return rc;
-    const uint8_t* p = ref->d_plane[0] + (size_t)ref->origin_y[0] * ref->stride[0] + ref->origin_x[0];
-    hipLaunchKernelGGL(me_subpel_planes_kernel, dim3((w * h + 255) / 256), dim3(256), 0, (hipStream_t)stream, p, ref->stride[0], x0, y0, w, h, d_planes);
+    const MePlaneAt at = me_plane_at(ref, 0, 1);
+    hipLaunchKernelGGL(me_subpel_planes_kernel, dim3(me_subpel_planes_grid(w, h)), dim3(256), 0, (hipStream_t)stream, at.p, at.stride, x0, y0, w, h, d_planes);
     return launch_status("me_subpel_planes");
 }

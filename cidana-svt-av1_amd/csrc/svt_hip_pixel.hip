@@ -3,59 +3,60 @@
 #include "host_common.h"
 #include "kernel_me.h"
 #include "kernel_pixel.h"
-#include "search_plan.h"
+#include "me_plan.h"
+#include "pixel_plan.h"
 
 using namespace svtdev;
 using namespace svthost;
 
-// mode 0 SAD, 1 SSE, 2 averaging SAD (kernel_pixel.h); a_shift = 2: four references per source block (x4d)
-static int sad_sse_common(int mode, const uint8_t* a, uint32_t as, size_t ap, const uint32_t* a_offs, int a_shift,
+// mode 0 SAD, 1 SSE, 2 averaging SAD (kernel_pixel.h); a_shift = 2: four references per source block (x4d); needs_offs: pixel_plan.h
+static int sad_sse_common(int mode, int needs_offs, const uint8_t* a, uint32_t as, size_t ap, const uint32_t* a_offs, int a_shift,
                           const uint8_t* b, uint32_t bs, size_t bp, const uint32_t* b_offs, const uint8_t* c, uint32_t cst,
                           size_t cp, uint32_t w, uint32_t h, void* out, size_t n, void* stream) {
     if (int rc = require_init()) return rc;
     if (n == 0) return SVT_HIP_OK;
-    if (!a || !b || !out || (mode == 2 && !c)) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (w == 0 || h == 0 || w > 128 || h > 128) return set_err(SVT_HIP_ERR_INVALID, "block %ux%u", w, h);
-    const uint32_t grid = (uint32_t)((n + 15) / 16);
-#define SADL(M) hipLaunchKernelGGL((sad_sse_kernel<M>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a, as, ap, a_offs, a_shift, b, bs, bp, \
-                                   b_offs, c, cst, cp, w, h, out, (uint32_t)n)
-    if (mode == 1) SADL(1); else if (mode == 2) SADL(2); else SADL(0);
+    SadSsePlan p;
+    if (int rc = sad_sse_plan(p, mode, needs_offs, a_shift, a, a_offs, b, b_offs, c, out, w, h, n)) return rc;
+#define SADL(M) hipLaunchKernelGGL((sad_sse_kernel<M>), dim3(p.grid), dim3(256), 0, (hipStream_t)stream, a, as, ap, a_offs, a_shift, b, bs, bp, \
+                                   b_offs, c, cst, cp, w, h, out, p.n)
+    switch (p.mode) {
+    case SAD_MODE_SSE: SADL(1); break;
+    case SAD_MODE_AVG: SADL(2); break;
+    default: SADL(0); break;
+    }
 #undef SADL
-    return launch_status(mode == 1 ? "sse" : (mode == 2 ? "sad_avg" : "sad"));
+    return launch_status(p.name);
 }
 extern "C" int svt_hip_sad_batch(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch,
                                  const uint8_t* d_ref, uint32_t ref_stride, size_t ref_block_pitch, uint32_t width,
                                  uint32_t height, uint32_t* d_out, size_t nblocks, void* stream) {
-    return sad_sse_common(0, d_src, src_stride, src_block_pitch, nullptr, 0, d_ref, ref_stride, ref_block_pitch, nullptr, nullptr, 0, 0,
+    return sad_sse_common(0, 0, d_src, src_stride, src_block_pitch, nullptr, 0, d_ref, ref_stride, ref_block_pitch, nullptr, nullptr, 0, 0,
                           width, height, d_out, nblocks, stream);
 }
 extern "C" int svt_hip_sse_batch(const uint8_t* d_a, uint32_t a_stride, size_t a_block_pitch, const uint8_t* d_b,
                                  uint32_t b_stride, size_t b_block_pitch, uint32_t width, uint32_t height,
                                  uint64_t* d_out, size_t nblocks, void* stream) {
-    return sad_sse_common(1, d_a, a_stride, a_block_pitch, nullptr, 0, d_b, b_stride, b_block_pitch, nullptr, nullptr, 0, 0, width, height,
+    return sad_sse_common(1, 0, d_a, a_stride, a_block_pitch, nullptr, 0, d_b, b_stride, b_block_pitch, nullptr, nullptr, 0, 0, width, height,
                           d_out, nblocks, stream);
 }
 extern "C" int svt_hip_sad_planes_batch(const uint8_t* d_src_plane, uint32_t src_stride, const uint32_t* d_src_offsets,
                                         const uint8_t* d_ref_plane, uint32_t ref_stride, const uint32_t* d_ref_offsets,
                                         uint32_t width, uint32_t height, uint32_t* d_out, size_t nblocks, void* stream) {
-    if (nblocks && (!d_src_offsets || !d_ref_offsets)) { if (int rc = require_init()) return rc; return set_err(SVT_HIP_ERR_INVALID, "NULL offset table"); }
-    return sad_sse_common(0, d_src_plane, src_stride, 0, d_src_offsets, 0, d_ref_plane, ref_stride, 0, d_ref_offsets, nullptr, 0, 0, width,
+    return sad_sse_common(0, SAD_NEEDS_A_OFFS | SAD_NEEDS_B_OFFS, d_src_plane, src_stride, 0, d_src_offsets, 0, d_ref_plane, ref_stride, 0, d_ref_offsets, nullptr, 0, 0, width,
                           height, d_out, nblocks, stream);
 }
 extern "C" int svt_hip_sad_x4d_batch(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch,
                                      const uint32_t* d_src_offsets, const uint8_t* d_ref_plane, uint32_t ref_stride,
                                      const uint32_t* d_ref_offsets, uint32_t width, uint32_t height, uint32_t* d_out,
                                      size_t nblocks, void* stream) {
-    if (nblocks && !d_ref_offsets) { if (int rc = require_init()) return rc; return set_err(SVT_HIP_ERR_INVALID, "NULL offset table"); }
-    if (nblocks > 0x3fffffffu) { if (int rc = require_init()) return rc; return set_err(SVT_HIP_ERR_INVALID, "too many blocks"); }
-    return sad_sse_common(0, d_src, src_stride, src_block_pitch, d_src_offsets, 2, d_ref_plane, ref_stride, 0, d_ref_offsets, nullptr, 0, 0,
-                          width, height, d_out, nblocks * 4, stream);
+    return sad_sse_common(0, SAD_NEEDS_B_OFFS, d_src, src_stride, src_block_pitch, d_src_offsets, 2, d_ref_plane, ref_stride, 0, d_ref_offsets, nullptr, 0, 0,
+                          width, height, d_out, nblocks, stream);
 }
 extern "C" int svt_hip_sad_avg_batch(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint8_t* d_ref1,
                                      uint32_t ref1_stride, size_t ref1_block_pitch, const uint8_t* d_ref2,
                                      uint32_t ref2_stride, size_t ref2_block_pitch, uint32_t width, uint32_t height,
                                      uint32_t* d_out, size_t nblocks, void* stream) {
-    return sad_sse_common(2, d_src, src_stride, src_block_pitch, nullptr, 0, d_ref1, ref1_stride, ref1_block_pitch, nullptr, d_ref2,
+    return sad_sse_common(2, 0, d_src, src_stride, src_block_pitch, nullptr, 0, d_ref1, ref1_stride, ref1_block_pitch, nullptr, d_ref2,
                           ref2_stride, ref2_block_pitch, width, height, d_out, nblocks, stream);
 }
 template <typename PixT>
@@ -64,22 +65,18 @@ static int residual_impl(const PixT* d_src, uint32_t src_stride, size_t src_bloc
                          uint32_t height, size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_src || !d_pred || !d_res) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (width == 0 || height == 0) return set_err(SVT_HIP_ERR_INVALID, "empty block");
-    // samples per lane: 16 bytes of input where the width allows it
-    constexpr uint32_t MAXCS = 16 / sizeof(PixT);
-    const uint32_t rcs = (width % MAXCS) == 0 ? MAXCS : ((width & 7) == 0 ? 8u : ((width & 3) == 0 ? 4u : 1u));
-    const size_t total = (size_t)(width / rcs) * height * nblocks;
-    const size_t grid = (total + 255) / 256;
-    if (grid > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks for one launch");
-    const uint32_t cpr = width / rcs;
-    const size_t per = (size_t)cpr * height;
-    const bool pow2 = (cpr & (cpr - 1)) == 0 && (per & (per - 1)) == 0;
-#define RESL(CS, P2) hipLaunchKernelGGL((residual_kernel<CS, P2, PixT>), dim3((uint32_t)grid), dim3(256), 0, (hipStream_t)stream, d_src, src_stride, \
+    ResidualPlan p;
+    if (int rc = residual_plan(p, sizeof(PixT), d_src, d_pred, d_res, width, height, nblocks)) return rc;
+#define RESL(CS, P2) hipLaunchKernelGGL((residual_kernel<CS, P2, PixT>), dim3(p.grid), dim3(256), 0, (hipStream_t)stream, d_src, src_stride, \
                        src_block_pitch, d_pred, pred_stride, pred_block_pitch, d_res, res_stride, res_block_pitch,   \
                        width, height, (uint32_t)nblocks)
-#define RESC(CS) if (pow2) RESL(CS, true); else RESL(CS, false)
-    if (rcs == 16) { if constexpr (MAXCS == 16) { RESC(16); } } else if (rcs == 8) { RESC(8); } else if (rcs == 4) { RESC(4); } else { RESC(1); }
+#define RESC(CS) if (p.pow2) RESL(CS, true); else RESL(CS, false)
+    switch (p.rcs) {
+    case 16: if constexpr (sizeof(PixT) == 1) { RESC(16); } break;
+    case 8: RESC(8); break;
+    case 4: RESC(4); break;
+    default: RESC(1); break;
+    }
 #undef RESC
 #undef RESL
     return launch_status("residual");
@@ -99,12 +96,12 @@ extern "C" int svt_hip_residual16_batch(const uint16_t* d_src, uint32_t src_stri
                                    res_block_pitch, width, height, nblocks, stream);
 }
 
-static int sad_search_impl(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs, const uint8_t* d_ref,
+static int sad_search_impl(bool need_offs, const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs, const uint8_t* d_ref,
                            uint32_t ref_stride, uint32_t ref_stride_raw, size_t ref_block_pitch, const uint32_t* d_ref_offs, uint32_t width, uint32_t height,
                            int16_t search_area_width, int16_t search_area_height, uint64_t* d_best_sad, int16_t* d_x, int16_t* d_y, size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_src || !d_ref || !d_best_sad || !d_x || !d_y) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
+    if (int rc = sad_search_args_check(need_offs, d_src_offs, d_ref_offs, d_src, d_ref, d_best_sad, d_x, d_y)) return rc;
     // the kernel, its variant, the launch shape and the LDS layout: search_plan.h
     const SadSearchKnobs knobs = {g_tune_no_qsad, g_tune_no_q2, g_tune_no_q2p, g_tune_no_q16, g_tune_q2_su4};
     SadSearchPlan p;
@@ -153,7 +150,7 @@ extern "C" int svt_hip_sad_search_batch(const uint8_t* d_src, uint32_t src_strid
                                         int16_t search_area_width, int16_t search_area_height,
                                         uint64_t* d_best_sad, int16_t* d_x, int16_t* d_y, size_t nblocks,
                                         void* stream) {
-    return sad_search_impl(d_src, src_stride, src_block_pitch, nullptr, d_ref, ref_stride, ref_stride_raw, ref_block_pitch,
+    return sad_search_impl(false, d_src, src_stride, src_block_pitch, nullptr, d_ref, ref_stride, ref_stride_raw, ref_block_pitch,
                            nullptr, width, height, search_area_width, search_area_height, d_best_sad, d_x, d_y, nblocks, stream);
 }
 extern "C" int svt_hip_sad_search_planes_batch(const uint8_t* d_src_plane, uint32_t src_stride, const uint32_t* d_src_offsets,
@@ -162,36 +159,45 @@ extern "C" int svt_hip_sad_search_planes_batch(const uint8_t* d_src_plane, uint3
                                                int16_t search_area_width, int16_t search_area_height,
                                                uint64_t* d_best_sad, int16_t* d_x, int16_t* d_y, size_t nblocks,
                                                void* stream) {
-    if (nblocks && (!d_src_offsets || !d_ref_offsets)) { if (int rc = require_init()) return rc; return set_err(SVT_HIP_ERR_INVALID, "NULL offset table"); }
-    return sad_search_impl(d_src_plane, src_stride, 0, d_src_offsets, d_ref_plane, ref_stride, ref_stride_raw, 0, d_ref_offsets,
+    return sad_search_impl(true, d_src_plane, src_stride, 0, d_src_offsets, d_ref_plane, ref_stride, ref_stride_raw, 0, d_ref_offsets,
                            width, height, search_area_width, search_area_height, d_best_sad, d_x, d_y, nblocks, stream);
 }
 
-// me_sb_search16_kernel for a window me_window (search_plan.h) accepted: 16 points per lane; widths that are not a multiple of 16 mask the
-// tail of each row.  w8q, ref_layout, pu_pitch: the reference's result layout (kernel_me_steps.h)
-static void launch_me_sb_search16(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs, const uint8_t* d_ref,
-                                  uint32_t ref_stride, size_t ref_block_pitch, const uint32_t* d_ref_offs, int search_w, int search_h,
-                                  const int16_t* d_origins, int x_origin, int y_origin, uint32_t* d_best_sad, uint32_t* d_best_mv, const MeWindow& w,
-                                  size_t nblocks, int w8q, int ref_layout, uint32_t pu_pitch, void* stream) {
-    auto* kernel = (search_w & 15) == 0 ? me_sb_search16_kernel<false> : me_sb_search16_kernel<true>;
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)nblocks), dim3(ME_THREADS), w.lds, (hipStream_t)stream, d_src, src_stride, src_block_pitch, d_ref, ref_stride,
-                       ref_block_pitch, search_w, search_h, d_origins, x_origin, y_origin, d_best_sad, d_best_mv, w.wpitch, d_src_offs, d_ref_offs,
-                       (uint32_t)nblocks, w8q, ref_layout, pu_pitch);
+// A full-pel search the plan routed (me_plan.h): one workgroup per block
+static int launch_me_fullpel(const MeFullpelRoute& r, const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs,
+                             const uint8_t* d_ref, uint32_t ref_stride, size_t ref_block_pitch, const uint32_t* d_ref_offs, int search_w, int search_h,
+                             const int16_t* d_origins, int x_origin, int y_origin, int flavour, int nsq, uint32_t* d_best_sad, uint32_t* d_best_mv, void* stream) {
+    const dim3 grid(r.grid), threads(ME_THREADS);
+    const hipStream_t s = (hipStream_t)stream;
+    switch (r.kernel) {
+    case ME_K_SQ16: {
+        auto* kernel = !r.masked ? me_sb_search16_kernel<false> : me_sb_search16_kernel<true>;
+        hipLaunchKernelGGL(kernel, grid, threads, r.lds, s, d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, search_w, search_h, d_origins,
+                           x_origin, y_origin, d_best_sad, d_best_mv, r.window.wpitch, d_src_offs, d_ref_offs, r.grid, r.w8q, r.ref_layout, r.pu_pitch);
+        return launch_status(r.ref_layout ? "me_sb_search16 (reference layout)" : "me_sb_search16");
+    }
+    case ME_K_NSQ4:
+        hipLaunchKernelGGL(me_nsq4_kernel, grid, threads, r.lds, s, d_src, src_stride, src_block_pitch, d_ref, ref_stride, ref_block_pitch, search_w, search_h,
+                           d_origins, x_origin, y_origin, d_best_sad, d_best_mv, r.window.wpitch, d_src_offs, d_ref_offs, r.grid, r.pu_pitch);
+        return launch_status("me_nsq4");
+    default:
+        hipLaunchKernelGGL(me_fullpel_exact_kernel, grid, threads, 0, s, d_src, src_stride, src_block_pitch, d_src_offs, d_ref, ref_stride, ref_block_pitch,
+                           d_ref_offs, search_w, search_h, d_origins, x_origin, y_origin, flavour, nsq ? 1 : 0, d_best_sad, d_best_mv, r.pu_pitch, r.grid);
+        return launch_status("me_fullpel_exact");
+    }
 }
 
-static int me_sb_search_impl(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs,
+static int me_sb_search_impl(bool need_offs, const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch, const uint32_t* d_src_offs,
                              const uint8_t* d_ref, uint32_t ref_stride, size_t ref_block_pitch, const uint32_t* d_ref_offs,
                              int search_w, int search_h, const int16_t* d_origins, int x_origin,
                              int y_origin, uint32_t* d_best_sad, uint32_t* d_best_mv, size_t nblocks,
                              void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_src || !d_ref || !d_best_sad || !d_best_mv) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    MeWindow w;
-    if (int rc = me_window_check(search_w, search_h, 0, ME_LDS_MAX, w)) return rc;
-    launch_me_sb_search16(d_src, src_stride, src_block_pitch, d_src_offs, d_ref, ref_stride, ref_block_pitch, d_ref_offs, search_w, search_h, d_origins,
-                          x_origin, y_origin, d_best_sad, d_best_mv, w, nblocks, 0, 0, ME_PUS, stream);
-    return launch_status("me_sb_search16");
+    MeFullpelRoute r;
+    if (int rc = me_sb_search_plan(r, need_offs, d_src_offs, d_ref_offs, d_src, d_ref, d_best_sad, d_best_mv, search_w, search_h, nblocks)) return rc;
+    return launch_me_fullpel(r, d_src, src_stride, src_block_pitch, d_src_offs, d_ref, ref_stride, ref_block_pitch, d_ref_offs, search_w, search_h, d_origins,
+                             x_origin, y_origin, SVT_HIP_FLAVOUR_C, 0, d_best_sad, d_best_mv, stream);
 }
 
 extern "C" int svt_hip_me_sb_search_batch(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch,
@@ -199,7 +205,7 @@ extern "C" int svt_hip_me_sb_search_batch(const uint8_t* d_src, uint32_t src_str
                                           int search_w, int search_h, const int16_t* d_origins, int x_origin,
                                           int y_origin, uint32_t* d_best_sad, uint32_t* d_best_mv, size_t nblocks,
                                           void* stream) {
-    return me_sb_search_impl(d_src, src_stride, src_block_pitch, nullptr, d_ref, ref_stride, ref_block_pitch, nullptr, search_w,
+    return me_sb_search_impl(false, d_src, src_stride, src_block_pitch, nullptr, d_ref, ref_stride, ref_block_pitch, nullptr, search_w,
                              search_h, d_origins, x_origin, y_origin, d_best_sad, d_best_mv, nblocks, stream);
 }
 extern "C" int svt_hip_me_sb_search_planes_batch(const uint8_t* d_src_plane, uint32_t src_stride, const uint32_t* d_src_offsets,
@@ -207,8 +213,7 @@ extern "C" int svt_hip_me_sb_search_planes_batch(const uint8_t* d_src_plane, uin
                                                  int search_w, int search_h, const int16_t* d_origins, int x_origin,
                                                  int y_origin, uint32_t* d_best_sad, uint32_t* d_best_mv, size_t nblocks,
                                                  void* stream) {
-    if (nblocks && (!d_src_offsets || !d_ref_offsets)) { if (int rc = require_init()) return rc; return set_err(SVT_HIP_ERR_INVALID, "NULL offset table"); }
-    return me_sb_search_impl(d_src_plane, src_stride, 0, d_src_offsets, d_ref_plane, ref_stride, 0, d_ref_offsets, search_w,
+    return me_sb_search_impl(true, d_src_plane, src_stride, 0, d_src_offsets, d_ref_plane, ref_stride, 0, d_ref_offsets, search_w,
                              search_h, d_origins, x_origin, y_origin, d_best_sad, d_best_mv, nblocks, stream);
 }
 
@@ -219,26 +224,15 @@ extern "C" int svt_hip_hme_level_regions_batch(const uint8_t* d_src_pic, uint32_
                                                int16_t* d_mv, size_t ntasks, void* stream) {
     if (int rc = require_init()) return rc;
     if (ntasks == 0) return SVT_HIP_OK;
-    if (!d_src_pic || !d_ref_pic || !d_sb_origin || !d_sb_size || !params || !d_best_sad || !d_mv) return set_err(SVT_HIP_ERR_INVALID, "NULL argument");
-    if (nregions < 1 || nregions > 4) return set_err(SVT_HIP_ERR_INVALID, "%d search regions (1..4)", nregions);
-    if (center_shift < 0 || center_shift > 2) return set_err(SVT_HIP_ERR_INVALID, "centre shift %d", center_shift);
-    if (ntasks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many tasks");
+    HmeLevelPlan p;
+    if (int rc = hme_level_plan(p, d_src_pic, d_ref_pic, d_sb_origin, d_sb_size, center_shift, params, nregions, d_best_sad, d_mv, ntasks)) return rc;
     HmeParamSets hp;
     static_assert(sizeof(HmeParams) == sizeof(svt_hip_hme_params), "layout");
     memset(&hp, 0, sizeof(hp));
-    for (int r = 0; r < nregions; r++) {
-        const svt_hip_hme_params& P = params[r];
-        if (P.search_area_width < 1 || P.search_area_height < 1 || (P.round_down != 8 && P.round_down != 16) || P.mv_shift < 0 || P.mv_shift > 2 ||
-            P.ref_width < 1 || P.ref_height < 1)
-            return set_err(SVT_HIP_ERR_INVALID, "HME parameters: area %dx%d, round_down %d, mv_shift %d", P.search_area_width, P.search_area_height,
-                           P.round_down, P.mv_shift);
-        memcpy(&hp.p[r], &P, sizeof(HmeParams));
-    }
-    HmeWindow w;
-    if (int rc = hme_window(params, nregions, w)) return rc;
-    hipLaunchKernelGGL(hme_level_kernel, dim3((uint32_t)ntasks, (uint32_t)nregions), dim3(ME_THREADS), w.lds, (hipStream_t)stream, d_src_pic, src_stride,
-                       d_ref_pic, ref_stride, d_sb_origin, d_sb_size, d_centers, center_shift, hp, (unsigned long long*)d_best_sad, d_mv, w.wpitch,
-                       (uint32_t)ntasks);
+    memcpy(hp.p, params, (size_t)nregions * sizeof(HmeParams));
+    hipLaunchKernelGGL(hme_level_kernel, dim3(p.grid_x, p.grid_y), dim3(ME_THREADS), p.win.lds, (hipStream_t)stream, d_src_pic, src_stride,
+                       d_ref_pic, ref_stride, d_sb_origin, d_sb_size, d_centers, center_shift, hp, (unsigned long long*)d_best_sad, d_mv, p.win.wpitch,
+                       p.grid_x);
     return launch_status("hme_level");
 }
 extern "C" int svt_hip_hme_level_batch(const uint8_t* d_src_pic, uint32_t src_stride, const uint8_t* d_ref_pic, uint32_t ref_stride,
@@ -249,7 +243,7 @@ extern "C" int svt_hip_hme_level_batch(const uint8_t* d_src_pic, uint32_t src_st
                                            d_best_sad, d_mv, ntasks, stream);
 }
 
-// K6 in the reference's result layout, both result flavours, square or all 209 PUs (include/svt_hip_dsp.h)
+// K6 in the reference's result layout, both result flavours, square or all 209 PUs (include/svt_hip_dsp.h); the kernel: me_fullpel_route
 extern "C" int svt_hip_me_fullpel_search_batch(const uint8_t* d_src, uint32_t src_stride, size_t src_block_pitch,
                                                const uint32_t* d_src_offsets, const uint8_t* d_ref, uint32_t ref_stride,
                                                size_t ref_block_pitch, const uint32_t* d_ref_offsets, int search_w,
@@ -258,31 +252,10 @@ extern "C" int svt_hip_me_fullpel_search_batch(const uint8_t* d_src, uint32_t sr
                                                uint32_t pu_pitch, size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_src || !d_ref || !d_best_sad || !d_best_mv) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (flavour != SVT_HIP_FLAVOUR_C && flavour != SVT_HIP_FLAVOUR_AVX2) return set_err(SVT_HIP_ERR_INVALID, "flavour %d", flavour);
-    const uint32_t npus = nsq ? SVT_HIP_ME_PUS_ALL : SVT_HIP_ME_PUS;
-    if (pu_pitch < npus) return set_err(SVT_HIP_ERR_INVALID, "pu_pitch %u < %u PUs", pu_pitch, npus);
-    MeWindow w;
-    if (int rc = me_window(search_w, search_h, 0, w)) return rc;
-    if (!nsq && !g_tune_me_exact && w.lds <= ME_LDS_MAX) {
-        // square PUs: the 16-points-per-lane kernel, any width; the AVX2 flavour only re-labels the 32x32 keys
-        launch_me_sb_search16(d_src, src_stride, src_block_pitch, d_src_offsets, d_ref, ref_stride, ref_block_pitch, d_ref_offsets, search_w, search_h,
-                              d_origins, x_origin, y_origin, d_best_sad, d_best_mv, w, nblocks, flavour == SVT_HIP_FLAVOUR_AVX2 ? (search_w & ~7) : 0, 1,
-                              pu_pitch, stream);
-        return launch_status("me_sb_search16 (reference layout)");
-    }
-    if (nsq && !g_tune_me_exact && (search_w & 7) == 0 && w.lds <= ME_NSQ_LDS_MAX) {
-        // all 209 PUs, widths where every point takes the reference's eight-point form: 4 points per lane, every shape folded
-        // out of the packed 8x8 SADs (me_nsq4_kernel); other widths keep the exact kernel (single-point quirks)
-        hipLaunchKernelGGL(me_nsq4_kernel, dim3((uint32_t)nblocks), dim3(ME_THREADS), w.lds, (hipStream_t)stream, d_src, src_stride,
-                           src_block_pitch, d_ref, ref_stride, ref_block_pitch, search_w, search_h, d_origins, x_origin, y_origin,
-                           d_best_sad, d_best_mv, w.wpitch, d_src_offsets, d_ref_offsets, (uint32_t)nblocks, pu_pitch);
-        return launch_status("me_nsq4");
-    }
-    hipLaunchKernelGGL(me_fullpel_exact_kernel, dim3((uint32_t)nblocks), dim3(ME_THREADS), 0, (hipStream_t)stream, d_src, src_stride,
-                       src_block_pitch, d_src_offsets, d_ref, ref_stride, ref_block_pitch, d_ref_offsets, search_w, search_h,
-                       d_origins, x_origin, y_origin, flavour, nsq ? 1 : 0, d_best_sad, d_best_mv, pu_pitch, (uint32_t)nblocks);
-    return launch_status("me_fullpel_exact");
+    MeFullpelRoute r;
+    if (int rc = me_fullpel_search_plan(r, d_src, d_ref, d_best_sad, d_best_mv, search_w, search_h, flavour, nsq, pu_pitch, nblocks, g_tune_me_exact)) return rc;
+    return launch_me_fullpel(r, d_src, src_stride, src_block_pitch, d_src_offsets, d_ref, ref_stride, ref_block_pitch, d_ref_offsets, search_w, search_h,
+                             d_origins, x_origin, y_origin, flavour, nsq, d_best_sad, d_best_mv, stream);
 }
 
 // ---- MotionEstimateLcu's glue: set-up, per-SB areas, bi-prediction + result rows (include/svt_hip_dsp.h) --------------------
@@ -291,22 +264,12 @@ extern "C" int svt_hip_me_setup_batch(const uint8_t* d_src_pic, uint32_t src_str
                                       const svt_hip_me_setup_params* params, int16_t* d_center, int16_t* d_area, size_t ntasks, void* stream) {
     if (int rc = require_init()) return rc;
     if (ntasks == 0) return SVT_HIP_OK;
-    if (!d_src_pic || !d_ref_pic || !d_sb_origin || !d_sb_size || !params || !d_area) return set_err(SVT_HIP_ERR_INVALID, "NULL argument");
-    if ((d_hme_sad == nullptr) != (d_hme_mv == nullptr)) return set_err(SVT_HIP_ERR_INVALID, "d_hme_sad and d_hme_mv go together");
-    const svt_hip_me_setup_params& P = *params;
-    if (P.regions_w < 0 || P.regions_w > 2 || P.regions_h < 0 || P.regions_h > 2 || (P.regions_w == 0) != (P.regions_h == 0))
-        return set_err(SVT_HIP_ERR_INVALID, "%d x %d search regions (0 x 0, or 1 .. 2 each)", P.regions_w, P.regions_h);
-    // the reference's sort walks its [width][height] arrays through [q / regions_w][q % regions_w]: outside a square grid that reads
-    // entries no level has written (stack garbage in the reference) - refused rather than guessed
-    if (P.second_best && P.regions_w != P.regions_h) return set_err(SVT_HIP_ERR_INVALID, "second_best needs regions_w == regions_h");
-    if (P.search_area_width < 1 || P.search_area_height < 1 || P.search_area_width > 4096 || P.search_area_height > 4096 || P.picture_width < 1 ||
-        P.picture_height < 1 || P.ref_width < 1 || P.ref_height < 1)
-        return set_err(SVT_HIP_ERR_INVALID, "search area %d x %d, picture %d x %d", P.search_area_width, P.search_area_height, P.picture_width, P.picture_height);
-    if (ntasks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many tasks");
+    uint32_t grid;
+    if (int rc = me_setup_plan(grid, d_src_pic, d_ref_pic, d_sb_origin, d_sb_size, d_hme_sad, d_hme_mv, params, d_area, ntasks)) return rc;
     static_assert(sizeof(MeSetupParams) == sizeof(svt_hip_me_setup_params), "layout");
     MeSetupParams mp;
     memcpy(&mp, params, sizeof(mp));
-    hipLaunchKernelGGL(me_setup_kernel, dim3((uint32_t)((ntasks + 3) / 4)), dim3(256), 0, (hipStream_t)stream, d_src_pic, src_stride, d_ref_pic,
+    hipLaunchKernelGGL(me_setup_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_src_pic, src_stride, d_ref_pic,
                        ref_stride, d_sb_origin, d_sb_size, (const unsigned long long*)d_hme_sad, d_hme_mv, mp, d_center, d_area, (uint32_t)ntasks);
     return launch_status("me_setup");
 }
@@ -317,16 +280,13 @@ extern "C" int svt_hip_me_fullpel_search_areas_batch(const uint8_t* d_src, uint3
                                                      uint32_t pu_pitch, size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_src || !d_ref || !d_src_offsets || !d_ref_offsets || !d_areas || !d_best_sad || !d_best_mv) return set_err(SVT_HIP_ERR_INVALID, "NULL argument");
-    if (flavour != SVT_HIP_FLAVOUR_C && flavour != SVT_HIP_FLAVOUR_AVX2) return set_err(SVT_HIP_ERR_INVALID, "flavour %d", flavour);
-    const uint32_t npus = nsq ? SVT_HIP_ME_PUS_ALL : SVT_HIP_ME_PUS;
-    if (pu_pitch < npus) return set_err(SVT_HIP_ERR_INVALID, "pu_pitch %u < %u PUs", pu_pitch, npus);
-    if (nblocks > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many blocks");
-    MeWindow w;                                           // sized by the bound of the areas; nsq: with the single-point areas' pairs
-    if (int rc = me_window_check(max_search_w, max_search_h, nsq, ME_NSQ_LDS_MAX, w)) return rc;
-    auto* kernel = nsq ? me_fullpel_areas_kernel<true> : me_fullpel_areas_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((uint32_t)nblocks), dim3(ME_THREADS), w.lds, (hipStream_t)stream, d_src, src_stride, d_src_offsets, d_ref, ref_stride,
-                       d_ref_offsets, d_areas, max_search_w, max_search_h, flavour, d_best_sad, d_best_mv, pu_pitch, w.wpitch, w.pair_off, (uint32_t)nblocks);
+    MeAreasPlan p;
+    if (int rc = me_fullpel_areas_plan(p, d_src, d_ref, d_src_offsets, d_ref_offsets, d_areas, d_best_sad, d_best_mv, max_search_w, max_search_h, flavour, nsq,
+                                       pu_pitch, nblocks))
+        return rc;
+    auto* kernel = p.nsq ? me_fullpel_areas_kernel<true> : me_fullpel_areas_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(ME_THREADS), p.window.lds, (hipStream_t)stream, d_src, src_stride, d_src_offsets, d_ref, ref_stride,
+                       d_ref_offsets, d_areas, max_search_w, max_search_h, flavour, d_best_sad, d_best_mv, pu_pitch, p.window.wpitch, p.window.pair_off, p.grid);
     return launch_status("me_fullpel_areas");
 }
 
@@ -370,16 +330,14 @@ extern "C" int svt_hip_me_bipred_batch(const uint8_t* d_src_pic, uint32_t src_st
                                        int bipred_all_pus, int sub_sad, uint32_t* d_bipred_sad, svt_hip_me_result* d_results, size_t nsb, void* stream) {
     if (int rc = require_init()) return rc;
     if (nsb == 0) return SVT_HIP_OK;
-    if (!d_src_pic || !d_sb_origin || !d_best_sad0 || !d_best_mv0 || !d_results) return set_err(SVT_HIP_ERR_INVALID, "NULL argument");
-    if ((d_best_sad1 == nullptr) != (d_best_mv1 == nullptr)) return set_err(SVT_HIP_ERR_INVALID, "d_best_sad1 and d_best_mv1 go together");
-    if (d_best_sad1 && (!d_ref0_pic || !d_ref1_pic)) return set_err(SVT_HIP_ERR_INVALID, "two lists need both reference planes");
-    if (npus != SVT_HIP_ME_PUS && npus != SVT_HIP_ME_PUS_ALL) return set_err(SVT_HIP_ERR_INVALID, "npus %d (85 or 209)", npus);
-    if (pu_pitch < (uint32_t)npus) return set_err(SVT_HIP_ERR_INVALID, "pu_pitch %u < %d PUs", pu_pitch, npus);
-    if (nsb > 0x7fffffffu) return set_err(SVT_HIP_ERR_INVALID, "too many SBs");
+    MeBipredPlan p;
+    if (int rc = me_bipred_plan(p, d_src_pic, d_ref0_pic, d_ref1_pic, d_sb_origin, d_best_sad0, d_best_mv0, d_best_sad1, d_best_mv1, pu_pitch, npus, bipred_all_pus,
+                                sub_sad, d_results, nsb))
+        return rc;
     static_assert(sizeof(MeResult) == sizeof(svt_hip_me_result), "layout");
-    hipLaunchKernelGGL(me_bipred_kernel, dim3((uint32_t)nsb), dim3(ME_THREADS), 0, (hipStream_t)stream, d_src_pic, src_stride, d_ref0_pic, ref0_stride,
-                       d_ref1_pic, ref1_stride, d_sb_origin, d_best_sad0, d_best_mv0, d_best_sad1, d_best_mv1, pu_pitch, npus, bipred_all_pus ? 1 : 0,
-                       sub_sad ? 1 : 0, me_pu_map(), d_bipred_sad, reinterpret_cast<MeResult*>(d_results), (uint32_t)nsb);
+    hipLaunchKernelGGL(me_bipred_kernel, dim3(p.grid), dim3(ME_THREADS), 0, (hipStream_t)stream, d_src_pic, src_stride, d_ref0_pic, ref0_stride,
+                       d_ref1_pic, ref1_stride, d_sb_origin, d_best_sad0, d_best_mv0, d_best_sad1, d_best_mv1, pu_pitch, npus, p.all_pus, p.sub_sad, me_pu_map(),
+                       d_bipred_sad, reinterpret_cast<MeResult*>(d_results), p.grid);
     return launch_status("me_bipred");
 }
 
@@ -388,17 +346,11 @@ static int full_distortion32_impl(const int32_t* d_coeff, uint32_t coeff_stride,
                                   int cbf_zero, const uint32_t* d_nz, int flavour, uint64_t* d_out, size_t nblocks, void* stream) {
     if (int rc = require_init()) return rc;
     if (nblocks == 0) return SVT_HIP_OK;
-    if (!d_coeff || !d_out || (!cbf_zero && !d_recon)) return set_err(SVT_HIP_ERR_INVALID, "NULL buffer");
-    if (width == 0 || height == 0 || width > 128 || height > 128) return set_err(SVT_HIP_ERR_INVALID, "area %ux%u", width, height);
-    if (flavour != SVT_HIP_FLAVOUR_C && flavour != SVT_HIP_FLAVOUR_AVX2) return set_err(SVT_HIP_ERR_INVALID, "flavour %d", flavour);
-    if (flavour == SVT_HIP_FLAVOUR_AVX2 && (width & 3)) return set_err(SVT_HIP_ERR_INVALID, "the AVX2 kernel is defined for widths that are a multiple of 4");
-    const dim3 grid((uint32_t)((nblocks + 15) / 16));
-    if (flavour == SVT_HIP_FLAVOUR_AVX2)
-        hipLaunchKernelGGL(full_distortion32_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, d_coeff, coeff_stride, coeff_block_pitch,
-                           d_recon, recon_stride, recon_block_pitch, width, height, cbf_zero, d_nz, (unsigned long long*)d_out, (uint32_t)nblocks);
-    else
-        hipLaunchKernelGGL(full_distortion32_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, d_coeff, coeff_stride, coeff_block_pitch,
-                           d_recon, recon_stride, recon_block_pitch, width, height, cbf_zero, d_nz, (unsigned long long*)d_out, (uint32_t)nblocks);
+    Dist32Plan p;
+    if (int rc = full_distortion32_plan(p, d_coeff, d_recon, d_out, width, height, cbf_zero, flavour, nblocks)) return rc;
+    auto* kernel = p.avx2 ? full_distortion32_kernel<true> : full_distortion32_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), 0, (hipStream_t)stream, d_coeff, coeff_stride, coeff_block_pitch, d_recon, recon_stride,
+                       recon_block_pitch, width, height, cbf_zero, d_nz, (unsigned long long*)d_out, (uint32_t)nblocks);
     return launch_status("full_distortion32");
 }
 extern "C" int svt_hip_full_distortion32_batch(const int32_t* d_coeff, uint32_t coeff_stride, size_t coeff_block_pitch,
@@ -412,10 +364,9 @@ extern "C" int svt_hip_picture_full_distortion32_batch(const int32_t* d_coeff, s
                                                        size_t recon_block_pitch, uint32_t bwidth, uint32_t bheight,
                                                        const uint32_t* d_count_non_zero_coeffs, int flavour, uint64_t* d_out,
                                                        size_t nblocks, void* stream) {
-    // picture_full_distortion32_bits (EbPictureOperators.c:349-457): a 64-sample dimension covers 32 coefficients, the row
-    // stride of both buffers is the (clamped) width, count_non_zero_coeffs == 0 selects the cbf_zero kernel per block
-    const uint32_t w = bwidth < 64 ? bwidth : 32, h = bheight < 64 ? bheight : 32;
-    if (nblocks && !d_recon) { if (int rc = require_init()) return rc; return set_err(SVT_HIP_ERR_INVALID, "NULL buffer"); }
+    // picture_full_distortion32_bits (EbPictureOperators.c:349-457): the row stride of both buffers is the (clamped) width,
+    // count_non_zero_coeffs == 0 selects the cbf_zero kernel per block.  (cbf_zero 0: a NULL d_recon is refused like any NULL buffer)
+    const uint32_t w = dist32_picture_side(bwidth), h = dist32_picture_side(bheight);
     return full_distortion32_impl(d_coeff, w, coeff_block_pitch, d_recon, w, recon_block_pitch, w, h, 0, d_count_non_zero_coeffs, flavour,
                                   d_out, nblocks, stream);
 }

@@ -97,6 +97,28 @@ def test_me_fullpel_vs_oracle_batches(dsp, sw, sh, nsq, flavour):
             assert np.array_equal(gm[i], exp_m[i]), (exact, i, "mv", np.nonzero(gm[i] != exp_m[i])[0][:8])
 
 
+def test_me_fullpel_window_past_the_lds_limit(dsp):
+    """the one routing branch of svt_hip_me_fullpel_search_batch no other test launches (its row of tests/c/me_plan_pins.h comes from this
+    case): square PUs whose window passes the 60 KiB of the 16-points-per-lane kernel - 2 x 320 points, 192 B x 383 rows - fall through
+    to the general kernel, without the me_exact knob; equal to the oracle"""
+    O = svtlibs.oracle()
+    rng = np.random.default_rng(2320)
+    n, sw, sh = 3, 2, 320
+    rw, rh = 64 + sw - 1 + 21, 64 + sh - 1 + 9
+    src = rng.integers(0, 256, size=(n, 64, 64), dtype=np.uint8)
+    ref = rng.integers(0, 256, size=(n, rh, rw), dtype=np.uint8)
+    ref[1, 300:364, 1:65] = src[1]                     # an exact match on the area's last rows
+    ref[2] = (ref[2] >> 7) << 7; src[2] = (src[2] >> 7) << 7      # ties
+    org = np.array([[-32, -160], [0, 0], [5, -300]], np.int16)
+    bs, bm = dsp.me_fullpel_search(dev(src), dev(ref), sw, sh, origins=dev(org), flavour=0, nsq=False)
+    gs = bs.cpu().numpy().view(np.uint32); gm = bm.cpu().numpy().view(np.uint32)
+    for i in range(n):
+        es = np.full(209, ME_MAX, np.uint32); em = np.zeros(209, np.uint32)
+        O.svt_oracle_me_sb_search_full(ptr(src[i]), 64, ptr(ref[i]), rw, sw, sh, int(org[i, 0]), int(org[i, 1]), 0, 0, ptr(es), ptr(em))
+        assert np.array_equal(gs[i], es[:85]), (i, "sad", np.nonzero(gs[i] != es[:85])[0][:8])
+        assert np.array_equal(gm[i], em[:85]), (i, "mv", np.nonzero(gm[i] != em[:85])[0][:8])
+
+
 def test_estimate_transform_pack64_energy_golden_gpu(dsp, pins):
     """a5: svt_hip_fwd_txfm2d_batch + svt_hip_pack64_batch == the reference's av1_estimate_transform (coefficients re-packed
     to stride 32 and three_quad_energy), all five 64-point sizes and control sizes, bd 8 / 10"""
